@@ -24,7 +24,14 @@ Two ways to run N > 1, the same library calls underneath:
 --steps steps ("scaling": "strong").  BASELINE config 4 is `--gpus 8 --total-samplings 4096`, config 5
 `--scene rtcamp6_dodeca --width 3840 --height 2160 --gpus 8 --total-samplings 1024`.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit, ms_per_step, config, multi_gpu);
+`--dump-outputs DIR` first writes what the timed steps computed — the all-reduced fp32 radiance accumulator — to DIR/accumulator.npy
+(above 64 MB: a fixed, seeded sample of its pixels, DIR/accumulator_sample.npy, with their row-major indices in
+DIR/accumulator_sample_pixels.npy).  The same arguments render the same samplings of the same scene, so two builds compare output for output.
+
+`--full` adds the measurements that cost runs of their own (roofline, post_chain, seed_kernel, headline, cpu_baseline below; the
+instrumented counter launch, the trace kernel alone and the traversal-only workload behind them; the PMC figures replayed from profiles/).
+Extra objects on the JSON line with --full:
   roofline     — trace kernel, `achieved` / `frac` (= `frac_survey_8d`): SURVEY.md §8(d)'s byte booking (32 B per node test, 36 B per
                  triangle, 16 B per sphere, 24 B per cuboid; test counts from an instrumented run of the same kernel on the same
                  seeds) per launch, divided by the kernel's mean launch duration (HIP events on its stream), vs the 8 TB/s HBM peak —
@@ -114,6 +121,26 @@ def latest_pmc_traffic(scene="rtcamp6_v3_1"):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory, total_acc):
+    """--dump-outputs: the timed steps' output, the all-reduced fp32 accumulator (H x W x 3), as DIR/accumulator.npy; one larger than
+    64 MB (4K and up) as a fixed sample of its pixels (seed 0, the same pixels for every build at that resolution) with their row-major
+    indices (float64: exact)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    a = np.ascontiguousarray(total_acc, dtype=np.float32)
+    if a.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "accumulator.npy"), a)
+        return
+    h, w, c = a.shape
+    n = DUMP_LIMIT_BYTES // 2 // (c * 4 + 8)
+    pixels = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+    np.save(os.path.join(directory, "accumulator_sample.npy"), a.reshape(h * w, c)[pixels])
+    np.save(os.path.join(directory, "accumulator_sample_pixels.npy"), pixels.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -140,8 +167,12 @@ def main():
     ap.add_argument("--debug", action="append", default=[], metavar="KEY=VALUE",
                     help="measurement knob of hr_set_debug_option (adv_den, leaf_den, min_waves, kchunk, node_unroll, trace_wgs, seed_mode, seed_split, seed_prio, init_prio, ploc_top)")
     ap.add_argument("--debug-skip", type=int, default=0, help="timing experiments: drop parts of the pipeline after the warm-up (image is garbage)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-counters", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-counters", action="store_true", help="with --full: no instrumented launch, trace kernel alone, traversal-only workload or seed account")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, post chain, seed kernel account, CPU baseline (runs of their own, after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed steps' output (the all-reduced fp32 accumulator, or a fixed seeded sample of it above 64 MB) to DIR/<name>.npy")
     args = ap.parse_args()
 
     import numpy as np
@@ -286,13 +317,19 @@ def main():
 
     # ---- test counts per path: instrumented run of the same kernel on the same seeds (outside the timed region)
     counters = None
-    if rank == 0 and not args.no_counters:
+    if rank == 0 and args.full and not args.no_counters:
         r0.set_option("counters", 1)
         r0.clear()
         r0.render(1, 3)
         r0.synchronize()
         counters = r0.stats()
         r0.set_option("counters", 0)
+    elif rank == 0 and not args.no_counters:
+        # a process's first launch loads the kernels' code object and sizes the hand-off buffers: one untimed launch, whatever --warmup
+        # (with --full the instrumented launch above is that launch).  --no-counters runs keep no launch before the warm-up: the PMC
+        # passes of tools/prof_pmc.sh count every dispatch of their command as one launch of 4 samplings
+        r0.render(1, 3)
+        r0.synchronize()
     for r in rs:
         r.clear()
 
@@ -341,9 +378,13 @@ def main():
         dist.all_gather_object(gathered, per_rank)
         per_rank = [x for part in gathered for x in part]
     st = r0.stats()
-    acc_mean = float(acc.mean().item()) if one_device else float(r0.read_accumulator().mean())   # after the all-reduce: the total
-    if os.environ.get("HR_BENCH_CHECKSUM") == "1" and rank == 0:
-        sys.stderr.write("accumulator mean after all-reduce: %.9g\n" % acc_mean)
+    if rank == 0 and (args.dump_outputs or os.environ.get("HR_BENCH_CHECKSUM") == "1"):
+        total_acc = acc.cpu().numpy() if one_device else r0.read_accumulator()    # after the all-reduce: the total
+        if os.environ.get("HR_BENCH_CHECKSUM") == "1":
+            acc_mean = float(acc.mean().item()) if one_device else float(total_acc.mean())
+            sys.stderr.write("accumulator mean after all-reduce: %.9g\n" % acc_mean)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, total_acc)
     # ---- outside the timed region: the evidence that the exchange happened.  Every context reports what its communicator says about
     # itself (hr_comm_info: ncclCommCount / ncclCommUserRank / ncclCommCuDevice / ncclGetVersion, asked of RCCL now) and the f64 sum of
     # its OWN accumulator (untouched by the all-reduce, which writes the total to a buffer of its own) and of the total it received.
@@ -365,7 +406,7 @@ def main():
 
     # ---- outside the timed region, rank 0: the post chain (renderer.rs:64-90 as two HIP kernels) on the all-reduced accumulator
     post = None
-    if rank == 0 and not args.debug_skip:
+    if rank == 0 and args.full and not args.debug_skip:
         n_s = S_TOTAL if S_TOTAL else HEADLINE * world if HEADLINE else SPS * world * args.steps
         p0 = r0.stats()["post_kernel_ms"]
         tp0 = time.perf_counter()
@@ -377,7 +418,7 @@ def main():
     # ---- outside the timed region, rank 0: the trace kernel with the chip to itself, and the traversal-only workload
     alone_ms = None
     trav = None
-    if rank == 0 and not args.debug_skip and not args.no_counters:
+    if rank == 0 and args.full and not args.debug_skip and not args.no_counters:
         # seed kernel skipped: the hand-off buffers still hold the previous batches' draws, so the workload is the same
         r0.set_debug_option("debug_skip", 2)
         r0.render(*step_range(0, SPS, world, mine[0][0]))
@@ -590,7 +631,7 @@ def main():
                         "the *_normalised figures divide the same bytes (and SURVEY 8(d)'s) by the HBM peak for comparison with the render kernel's line and are NOT fractions of anything physical (they exceed 1)"}
         # HBM / fabric traffic and instruction counts are PMC measurements (separate rocprofv3 --pmc passes of this same command,
         # tools/prof_pmc.sh, which also writes the JSON read here); per launch like `achieved`
-        pmc = latest_pmc_traffic(args.scene)
+        pmc = latest_pmc_traffic(args.scene) if args.full else None
         if pmc and (W, H) == (1920, 1080):
             stale = pmc.get("csrc_sha") != kernel_source_sha()
             tk = pmc["kernels"].get("trace_kernel", {})
@@ -628,13 +669,14 @@ def main():
                 roof["issue"] = {"wave_instructions_per_path": per_path, "valu_wave_instructions_per_path_both_kernels": round(valu, 1),
                                  "valu_ceiling_Mpaths_per_s": round(chip_valu_per_s / valu / 1e6, 1), "frac": round(value / world * 1e6 * valu / chip_valu_per_s, 4),
                                  "source": pmc["source"], "stale": stale}
-        out["roofline"] = roof
+        if args.full:
+            out["roofline"] = roof
         if post:
             out["post_chain"] = post
         # The other kernel of the pair: per-path ISAAC-64 seeding.  Bound neither by HBM nor by MFMA but by LDS capacity x the
         # serial chain of ONE wave (SEED_CEILING_US_PER_GROUP above).
         seed_ms = st["seed_kernel_ms"] / max(1, st["seed_launches"])
-        if seed_ms > 0:
+        if args.full and seed_ms > 0:
             seed_rate = paths_per_launch / (seed_ms * 1e-3) / 1e6
             ceiling = 80.0 / (SEED_CEILING_US_PER_GROUP * 1e-6) * 256 / 1e6
             out["seed_kernel"] = {"kernel": "seed_seg_kernel", "bound": "lds_capacity_x_single_wave_serial_chain", "avg_launch_ms": round(seed_ms, 4),
@@ -686,7 +728,7 @@ def main():
                     r0.set_debug_option("debug_skip", 0)
             out["headline"] = head
 
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle_py as orc
             o = orc.OracleScene(scene.desc_ptr)

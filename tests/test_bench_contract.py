@@ -106,3 +106,25 @@ def test_committed_headline_line_proves_its_exchange_and_its_shortcuts():
     g = r["priority_governor"]
     assert g["level"] == 0 and (g["trace_workgroups"] == "all" or 512 <= g["trace_workgroups"] <= 1024)
     assert r["replayed_from_profiles"]["fields"] == ["traffic", "traffic_write", "physical", "issue"] and "schema" in r
+
+
+def test_dump_outputs_writes_the_accumulator_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the accumulator as it is up to the size limit; above it a seeded sample of its pixels (the same pixels on
+    every call) with their indices, float32 / float64 only, within the limit."""
+    import numpy as np
+    # importing bench.py sets HSA_ENABLE_IPC_MODE_LEGACY (setdefault) and prepends its package to sys.path: undone at teardown
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    acc = np.random.default_rng(5).random((36, 64, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), acc)
+    assert sorted(os.listdir(tmp_path / "a")) == ["accumulator.npy"] and np.array_equal(np.load(tmp_path / "a" / "accumulator.npy"), acc)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", acc.nbytes // 2)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), acc)
+    names = ["accumulator_sample.npy", "accumulator_sample_pixels.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    s, p = (np.load(tmp_path / "b" / n) for n in names)
+    assert s.dtype == np.float32 and p.dtype == np.float64 and s.nbytes + p.nbytes <= acc.nbytes // 2
+    assert len(np.unique(p)) == len(p) > 0 and np.array_equal(s, acc.reshape(-1, 3)[p.astype(np.int64)])
+    assert all(np.array_equal(np.load(tmp_path / "b" / n), np.load(tmp_path / "c" / n)) for n in names)

@@ -1209,12 +1209,12 @@ def test_wave_budget_governor(gpu, scenes):
         gpu.set_option("batch", 0)
 
 
-def _run_bench(extra, env=None, launcher_ranks=0, port=29541):
+def _run_bench(extra, env=None, launcher_ranks=0, port=29541, full=True):
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--warmup", "0", "--spp-per-step", "2", "--width", "160", "--height", "90", "--no-cpu-baseline"]
+    common = ["--warmup", "0", "--spp-per-step", "2", "--width", "160", "--height", "90", "--no-cpu-baseline"] + (["--full"] if full else [])
     cmd = [sys.executable]
     if launcher_ranks:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(launcher_ranks), "--master-addr", "127.0.0.1", "--master-port", str(port)]
@@ -1231,6 +1231,27 @@ def _bench_line(proc):
     assert proc.returncode == 0, proc.stderr[-3000:]
     mean = float(re.search(r"accumulator mean after all-reduce: ([0-9.eE+-]+)", proc.stderr).group(1))
     return json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1]), mean
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the measurements that take runs of their own, and --dump-outputs writes
+    what its timed steps computed: the accumulator of samplings 1..8, the one a --full run of the same arguments ends its timed steps with."""
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    j1, m1 = _bench_line(_run_bench(["--steps", "4", "--dump-outputs", str(plain)], full=False))
+    j2, m2 = _bench_line(_run_bench(["--steps", "4", "--dump-outputs", str(full)]))
+    for k in ("roofline", "post_chain", "seed_kernel", "headline", "cpu_baseline"):
+        assert k not in j1, k
+    assert "roofline" in j2 and "post_chain" in j2 and j2["roofline"]["achieved"] > 0
+    assert j1["steps"] == 4 and j1["ms_per_step"] > 0 and j1["unit"] == "Mpaths/s" and j1["dtype"] == "f32" and j1["higher_is_better"] is True
+    assert j1["config"]["samplings_total"] == 8 and j1["multi_gpu"]["exchange_verified"]
+    x, y = np.load(plain / "accumulator.npy"), np.load(full / "accumulator.npy")
+    assert x.dtype == np.float32 and x.shape == (90, 160, 3) and sorted(os.listdir(plain)) == ["accumulator.npy"]
+    assert m1 > 0 and abs(float(x.mean()) - m1) <= 1e-6 * m1 and abs(m1 - m2) <= 1e-6 * m1
+    # against an independent reduction of the device buffer: the line's per-channel f64 sums (hr_accumulator_sum)
+    total = np.array(j1["multi_gpu"]["checksum"]["total"])
+    assert total.min() > 0 and np.allclose(x.astype(np.float64).sum(axis=(0, 1)), total, rtol=1e-9, atol=0), (x.astype(np.float64).sum(axis=(0, 1)), total)
+    print("plain vs --full accumulator: max abs diff %.3g" % float(np.abs(x.astype(np.float64) - y).max()))
+    assert np.abs(x.astype(np.float64) - y).max() <= 1e-5 * max(1.0, float(np.abs(y).max()))
 
 
 def test_bench_gpus_n_without_a_launcher(tmp_path):

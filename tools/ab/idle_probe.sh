@@ -7,7 +7,7 @@
 cp hanamaru-renderer_amd/libhanamaru_hip.so /tmp/lib_cur.so
 cp tools/ab/lib_idleprobe.so hanamaru-renderer_amd/libhanamaru_hip.so
 for sc in rtcamp6_v3_1 rtcamp6_v2 rtcamp6_v1 tbf3; do
-python bench.py --scene $sc --steps 4 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+python bench.py --full --scene $sc --steps 4 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('$sc: lanes that hold a path when the traversal starts (probe build: leaf counters reused): %.1f of 64; lanes per box pass %.1f, per shade call %.1f' % (r['lanes_per_leaf_call'], r['lanes_per_box_pass'], r['lanes_per_shade_call']))"
