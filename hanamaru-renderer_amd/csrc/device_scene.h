@@ -254,10 +254,10 @@ HD uint32_t gov_budget_next(uint32_t B, float ratio, uint32_t lo, uint32_t hi, u
 // the seed kernel's producer priorities of a level: bits 0-1 even groups, bits 2-3 odd groups
 HD uint32_t gov_producer_prio(int32_t level, uint32_t init_prio) { return level <= 0 ? (init_prio | init_prio << 2) : level == 1 ? init_prio : 0u; }
 
-// One render launch covers `num_k` samplings (sampling_begin + k*stride) of the whole image.
+// One render launch covers `num_k` samplings (sampling_begin + k*stride) of the region (hr_set_region; by default the whole frame).
 struct RenderParams {
-    uint32_t width, height;
-    uint32_t tiles_x, tiles_y;        // 4x4-pixel tiles
+    uint32_t width, height;           // the FRAME: seeds and camera rays are normalised by it (path_seed_words, path_start), whatever the region
+    uint32_t tiles_x, tiles_y;        // 4x4-pixel tiles of the region
     uint32_t sampling_begin, stride, num_k;
     uint32_t adv_den;                 // trace kernel: leave the traversal loop when 1/adv_den of the live lanes are done
     uint32_t leaf_den;                // trace kernel: run the leaf phase when 1/leaf_den of the traversing lanes parked a leaf
@@ -274,15 +274,31 @@ struct RenderParams {
     GovDev *gov;                      // nullptr: no governor (debug kernels, host emulation) — trace_boost / pad[1] as given
     uint64_t rec_lo_off;              // precise shading: the records' second half, in floats from the first — slot k of a path holds what rounding draw k to fp32
                                       // took away (isaac_core.h draw_lo_f32), same layout; 0: the launch carries no residuals (fp32 draws)
+    // the region (hr_set_region): the window [org_x, org_x + reg_w) x [org_y, org_y + reg_h) of the frame.  The tiles, the accumulator and the
+    // path log are the window's (region-local pixels); seeds and camera rays take frame pixels org + local.  reg_w = reg_h = 0: the whole frame.
+    uint32_t org_x, org_y, reg_w, reg_h;
 };
+HD uint32_t rp_reg_w(const RenderParams &rp) { return rp.reg_w ? rp.reg_w : rp.width; }
+HD uint32_t rp_reg_h(const RenderParams &rp) { return rp.reg_h ? rp.reg_h : rp.height; }
+// does the region-local pixel (px, py) of a tile lane lie inside the region (the tiles of its right and bottom edges overhang it)?
+HD bool rp_in_region(const RenderParams &rp, uint32_t px, uint32_t py) { return px < rp_reg_w(rp) && py < rp_reg_h(rp); }
 
-// lane j of tile `tile` -> pixel and sub-sample (tile = 4x4 pixels x 4 sub-samples = 64 paths per sampling)
+// lane j of tile `tile` -> region-local pixel and sub-sample (tile = 4x4 pixels x 4 sub-samples = 64 paths per sampling)
 HD void tile_lane_pixel(const RenderParams &rp, uint32_t tile, uint32_t j, uint32_t &px, uint32_t &py, uint32_t &sub) {
     uint32_t tx = tile % rp.tiles_x, ty = tile / rp.tiles_x;
     uint32_t pix = j >> 2;
     sub = j & 3u;
     px = tx * 4u + (pix & 3u);
     py = ty * 4u + (pix >> 2);
+}
+// ... -> FRAME pixel (region-local + the region's origin), what seeds and camera rays are made from.  The seed and trace kernels run the path
+// of every lane whose frame pixel lies in the frame, as they always have: the lanes of a region's edge tiles that overhang the region but not
+// the frame are traced too, and accumulate_kernel leaves them out.  Testing the region's edge there instead costs the trace kernel four
+// VGPR spills (two more SGPRs live across its loop); this way a full-frame launch does what it did, plus two adds of a scalar.
+HD void tile_lane_frame_pixel(const RenderParams &rp, uint32_t tile, uint32_t j, uint32_t &px, uint32_t &py, uint32_t &sub) {
+    tile_lane_pixel(rp, tile, j, px, py, sub);
+    px += rp.org_x;
+    py += rp.org_y;
 }
 
 // Hand-off from the seed kernel to the trace kernel: a 128-byte record of REC_FLOATS fp32 slots per path,

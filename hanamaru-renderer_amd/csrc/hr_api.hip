@@ -72,6 +72,9 @@ struct hr_ctx {
     uint64_t st_nodes = 0, st_tris = 0, st_spheres = 0, st_cuboids = 0;
     // target
     uint32_t W = 0, H = 0;
+    // the region (hr_set_region): the window [RX, RX + RW) x [RY, RY + RH) of the W x H frame that is rendered; the accumulator and
+    // everything shaped like it is RW x RH.  hr_set_resolution makes it the whole frame.
+    uint32_t RX = 0, RY = 0, RW = 0, RH = 0;
     float *accum_own = nullptr, *accum = nullptr;
     float *post_tmp = nullptr;
     uint8_t *d_rgb8 = nullptr;
@@ -716,15 +719,15 @@ int hr_upload_scene(hr_ctx *c, const hr_scene_desc *sd) {
     return HR_OK;
 }
 
-int hr_set_resolution(hr_ctx *c, uint32_t w, uint32_t h) {
-    if (!c || !w || !h) return fail(HR_ERR_INVALID, "hr_set_resolution: bad argument");
-    if ((uint64_t)w * h > (1ull << 27)) return fail(HR_ERR_UNSUPPORTED, "resolution too large");
+// The target: the W x H frame and the window of it that is rendered (the whole frame, or hr_set_region's).  The accumulator and the resolve's
+// buffers are (re)allocated for the window and zeroed.
+static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
     if (rc) return rc;
     // no target while the buffers are being replaced (a failed allocation leaves the context without one, not with dangling
-    // pointers); a caller-bound accumulator was sized for the old resolution: it is unbound, the caller rebinds
-    c->accum = nullptr; c->W = c->H = 0; c->total_valid = false;
+    // pointers); a caller-bound accumulator was sized for the old target: it is unbound, the caller rebinds
+    c->accum = nullptr; c->W = c->H = 0; c->RX = c->RY = c->RW = c->RH = 0; c->total_valid = false;
     unbind_accumulator(c);
     if (c->accum_own) { HIP_TRY(hipFree(c->accum_own)); c->accum_own = nullptr; }
     if (c->post_tmp) { HIP_TRY(hipFree(c->post_tmp)); c->post_tmp = nullptr; }
@@ -735,9 +738,38 @@ int hr_set_resolution(hr_ctx *c, uint32_t w, uint32_t h) {
     HIP_TRY(hipMemset(c->accum_own, 0, n * sizeof(float)));
     HIP_TRY(hipMalloc((void **)&c->post_tmp, n * sizeof(float)));
     HIP_TRY(hipMalloc((void **)&c->d_rgb8, n));
-    c->W = w; c->H = h;
+    c->W = W; c->H = H;
+    c->RX = x0; c->RY = y0; c->RW = w; c->RH = h;
     c->accum = c->accum_own;
     return govern_reset(c);
+}
+static bool has_region(const hr_ctx *c) { return c->RW != c->W || c->RH != c->H; }
+// the launch geometry of hr_render / hr_render_debug: the frame, the region and the region's tiles
+static void target_params(const hr_ctx *c, RenderParams &rp) {
+    rp.width = c->W; rp.height = c->H;
+    rp.org_x = c->RX; rp.org_y = c->RY; rp.reg_w = c->RW; rp.reg_h = c->RH;
+    rp.tiles_x = (c->RW + 3) / 4; rp.tiles_y = (c->RH + 3) / 4;
+}
+
+int hr_set_resolution(hr_ctx *c, uint32_t w, uint32_t h) {
+    if (!c || !w || !h) return fail(HR_ERR_INVALID, "hr_set_resolution: bad argument");
+    if ((uint64_t)w * h > (1ull << 27)) return fail(HR_ERR_UNSUPPORTED, "resolution too large");
+    return set_target(c, w, h, 0, 0, w, h);
+}
+
+int hr_set_region(hr_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+    if (!c) return fail(HR_ERR_INVALID, "hr_set_region: null ctx");
+    if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_set_region: hr_set_resolution not called");
+    if (!w || !h || x0 > c->W || w > c->W - x0 || y0 > c->H || h > c->H - y0)
+        return fail(HR_ERR_INVALID, "hr_set_region: the window %u,%u %ux%u does not fit in the %ux%u frame", x0, y0, w, h, c->W, c->H);
+    return set_target(c, c->W, c->H, x0, y0, w, h);
+}
+
+int hr_get_region(hr_ctx *c, uint32_t out_xywh[4]) {
+    if (!c || !out_xywh) return fail(HR_ERR_INVALID, "hr_get_region: null argument");
+    if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_get_region: hr_set_resolution not called");
+    out_xywh[0] = c->RX; out_xywh[1] = c->RY; out_xywh[2] = c->RW; out_xywh[3] = c->RH;
+    return HR_OK;
 }
 
 int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
@@ -745,9 +777,9 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_bind_accumulator: hr_set_resolution not called");
     HIP_TRY(hipSetDevice(c->device));
     if (device_rgb) {
-        // what can be checked of a caller's pointer is checked: device memory, of this context's device, float-aligned, and W x H x 3 floats
-        // inside the allocation it points into (a tensor of another shape or dtype would otherwise be overrun by plain stores, silently)
-        const size_t need = (size_t)c->W * c->H * 3 * sizeof(float);
+        // what can be checked of a caller's pointer is checked: device memory, of this context's device, float-aligned, and w x h x 3 floats
+        // (the region's) inside the allocation it points into (a tensor of another shape or dtype would otherwise be overrun by plain stores, silently)
+        const size_t need = (size_t)c->RW * c->RH * 3 * sizeof(float);
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, device_rgb) != hipSuccess || at.type != hipMemoryTypeDevice) {
             (void)hipGetLastError();
@@ -760,7 +792,7 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
         if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)device_rgb) == hipSuccess) {
             if ((const char *)device_rgb + need > (const char *)base + size)
                 return fail(HR_ERR_INVALID, "hr_bind_accumulator: the buffer is too small (%zu bytes from this address to the end of its allocation, %u x %u x 3 floats = %zu needed)",
-                            (size_t)((const char *)base + size - (const char *)device_rgb), c->W, c->H, need);
+                            (size_t)((const char *)base + size - (const char *)device_rgb), c->RW, c->RH, need);
         } else (void)hipGetLastError();
     }
     int rc = sync_all(c);
@@ -770,7 +802,7 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
         // cannot both pass.  The registry holds byte ranges: a buffer that overlaps another context's is refused like an equal one.
         // (The caller binds NULL before it frees a bound buffer: an entry left behind would refuse whoever is handed the address next.)
         std::lock_guard<std::mutex> lk(g_bound_mu);
-        const size_t bytes = (size_t)c->W * c->H * 3 * sizeof(float);
+        const size_t bytes = (size_t)c->RW * c->RH * 3 * sizeof(float);
         if (device_rgb)
             for (const auto &kv : g_bound) {
                 const char *a = (const char *)kv.first, *b = (const char *)device_rgb;
@@ -802,7 +834,7 @@ int hr_clear(hr_ctx *c) {
     int rc = sync_all(c);
     if (rc) return rc;
     invalidate_totals(c);
-    HIP_TRY(hipMemsetAsync(c->accum, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(c->accum, 0, (size_t)c->RW * c->RH * 3 * sizeof(float), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->seed_ms = c->trace_ms = c->post_ms = c->debug_ms = 0;
@@ -978,8 +1010,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     invalidate_totals(c);
     uint32_t total_k = (s_end - s_begin + stride - 1) / stride;
     RenderParams rp{};
-    rp.width = c->W; rp.height = c->H;
-    rp.tiles_x = (c->W + 3) / 4; rp.tiles_y = (c->H + 3) / 4;
+    target_params(c, rp);
     rp.stride = stride;
     rp.adv_den = c->adv_den;
     rp.leaf_den = c->leaf_den;
@@ -1088,7 +1119,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->trace_done[slot], c->stream));
         c->trace_pending[slot] = true;
-        c->paths_rendered += (uint64_t)c->W * c->H * 4 * nk;
+        c->paths_rendered += (uint64_t)c->RW * c->RH * 4 * nk;
         if (c->trace_events.size() >= 64 && c->seed_events.size() == c->trace_events.size()) retire_finished_launches(c);
         if (c->trace_events.size() > 4096) {  // (never reached while launches finish: the host would have to be 4,096 launches ahead)
             if ((rc = sync_all(c))) return rc;
@@ -1104,8 +1135,7 @@ int hr_render_debug(hr_ctx *c, int mode) {
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
     RenderParams rp{};
-    rp.width = c->W; rp.height = c->H;
-    rp.tiles_x = (c->W + 3) / 4; rp.tiles_y = (c->H + 3) / 4;
+    target_params(c, rp);
     rp.leaf_den = c->leaf_den; rp.node_unroll = c->node_unroll;
     EventPair ev{nullptr, nullptr};
     HIP_TRY(hipEventCreate(&ev.a));
@@ -1167,7 +1197,7 @@ int hr_read_accumulator(hr_ctx *c, float *host) {
     if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_read_accumulator: no accumulator");
     int rc = hr_synchronize(c);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(host, c->total_valid ? c->accum_total : c->accum, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host, c->total_valid ? c->accum_total : c->accum, (size_t)c->RW * c->RH * 3 * sizeof(float), hipMemcpyDeviceToHost));
     return HR_OK;
 }
 int hr_write_accumulator(hr_ctx *c, const float *host) {
@@ -1177,7 +1207,7 @@ int hr_write_accumulator(hr_ctx *c, const float *host) {
     int rc = sync_all(c);
     if (rc) return rc;
     invalidate_totals(c);
-    HIP_TRY(hipMemcpy(c->accum, host, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->accum, host, (size_t)c->RW * c->RH * 3 * sizeof(float), hipMemcpyHostToDevice));
     return HR_OK;
 }
 
@@ -1186,14 +1216,15 @@ int hr_resolve(hr_ctx *c, uint32_t samplings, uint8_t *host_rgb8) {
     if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_resolve: no accumulator");
     int rc = hr_synchronize(c);
     if (rc) return rc;
-    uint32_t n = c->W * c->H;
+    // the region's accumulator is resolved as an image of its own: the bilateral filter's clamp and wrap act at the region's edges
+    uint32_t n = c->RW * c->RH;
     float scale = 1.0f / (float)(samplings * 4u);
     EventPair ev{nullptr, nullptr};
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     HIP_TRY(hipEventRecord(ev.a, c->stream));
     hipLaunchKernelGGL(tonemap_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->total_valid ? c->accum_total : c->accum, c->post_tmp, n, scale);
-    hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->W + 31) / 32, (c->H + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->W, c->H);
+    hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->RW, c->RH);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, c->stream));
     c->post_events.push_back(ev);
@@ -1280,11 +1311,12 @@ static int allreduce_enqueue(hr_ctx *c) {
     if (!c->comm && c->same_device_peers.empty()) return fail(HR_ERR_INVALID, "hr_allreduce_accumulator: no communicator (hr_comm_init_rank / hr_comm_init_local)");
     if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_allreduce_accumulator: no accumulator");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)c->W * c->H * 3;
+    const size_t n = (size_t)c->RW * c->RH * 3;
     if (!c->accum_total) HIP_TRY(hipMalloc((void **)&c->accum_total, n * sizeof(float)));
     if (!c->same_device_peers.empty()) {
         for (hr_ctx *p : c->same_device_peers) {
-            if (p->W != c->W || p->H != c->H || !p->accum) return fail(HR_ERR_INVALID, "hr_allreduce_accumulator: the contexts of the group differ in resolution");
+            if (p->W != c->W || p->H != c->H || p->RX != c->RX || p->RY != c->RY || p->RW != c->RW || p->RH != c->RH || !p->accum)
+                return fail(HR_ERR_INVALID, "hr_allreduce_accumulator: the contexts of the group differ in resolution or region");
             if (p != c) { int rc = sync_all(p); if (rc) return rc; }   // the peers' render work (their own streams)
         }
         // rank order, so that every context of the group gets bit-identical totals (as an all-reduce delivers them)
@@ -1383,7 +1415,7 @@ int hr_accumulator_sum(hr_ctx *c, int which, double out_rgb[3]) {
     double *d = nullptr;
     std::vector<double> h(ACC_SUM_BLOCKS * 3);
     HIP_TRY(hipMalloc((void **)&d, h.size() * sizeof(double)));
-    hipLaunchKernelGGL(accumulator_sum_kernel, dim3(ACC_SUM_BLOCKS), dim3(256), 0, c->stream, which ? c->accum_total : c->accum, (size_t)c->W * c->H, d);
+    hipLaunchKernelGGL(accumulator_sum_kernel, dim3(ACC_SUM_BLOCKS), dim3(256), 0, c->stream, which ? c->accum_total : c->accum, (size_t)c->RW * c->RH, d);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1574,6 +1606,7 @@ int hr_set_debug_option(hr_ctx *c, const char *key, double value) {
 
 int hr_debug_draws(hr_ctx *c, uint32_t sampling, uint32_t first_path, uint32_t num_paths, uint32_t window, uint64_t *host_out) {
     if (!c || !host_out || !num_paths) return fail(HR_ERR_INVALID, "hr_debug_draws: bad argument");
+    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_draws: not while a region is set (hr_set_region)");
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_draws: hr_set_resolution not called");
     if (window == 0 || window > (uint32_t)ISAAC_TAIL) return fail(HR_ERR_INVALID, "window must be in [1,%d]", ISAAC_TAIL);
     if ((uint64_t)first_path + num_paths > (uint64_t)c->W * c->H * 4) return fail(HR_ERR_INVALID, "path range outside the image");
@@ -1594,6 +1627,7 @@ static int path_draws_out(hr_ctx *c, uint32_t sampling, float *host_out, bool re
     // the 20 fp32 draws per path exactly as the production seed kernel hands them to the trace kernel (residuals: the same slots of the
     // records' twin), re-ordered to pixel-major paths: out[((y*W + x)*4 + sub) * 20 + d]
     if (!c || !host_out) return fail(HR_ERR_INVALID, "%s: bad argument", who);
+    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "%s: not while a region is set (hr_set_region)", who);
     if (!c->W) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", who);
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "%s: no scene (lens shape needed)", who);
     if (residuals && !draws_twin(c)) return fail(HR_ERR_UNSUPPORTED, "%s: no residuals are written (needs precise shading in force, seed_mode 2, draw_residuals 1)", who);
@@ -1643,6 +1677,7 @@ int hr_debug_path_log(hr_ctx *c, uint32_t sampling, uint32_t *host_out) {
     // one sampling through the production pipeline — the seed kernel, then the LOG instantiation of trace_kernel (same traversal, same
     // path_advance) — with every path's radiance, ray count and event log written out instead of being accumulated
     if (!c || !host_out) return fail(HR_ERR_INVALID, "hr_debug_path_log: bad argument");
+    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_path_log: not while a region is set (hr_set_region)");
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_path_log: hr_set_resolution not called");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_path_log: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
@@ -1706,6 +1741,7 @@ int hr_debug_wf_profile(hr_ctx *c, uint32_t sampling, uint32_t num_k, double *ms
     // one launch of the split pipeline with the chip to itself, an event between every two kernels: ms_out[0] = wf_start_kernel,
     // ms_out[2 s - 1] / ms_out[2 s] = traversal / shading kernel of step s = 1 .. WF_STEPS; counts_out[2 s] / [2 s + 1] = rays / live paths of step s
     if (!c || !ms_out || !counts_out || !num_k) return fail(HR_ERR_INVALID, "hr_debug_wf_profile: bad argument");
+    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_wf_profile: not while a region is set (hr_set_region)");
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_wf_profile: hr_set_resolution not called");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_wf_profile: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
@@ -1744,6 +1780,7 @@ int hr_debug_wf_profile(hr_ctx *c, uint32_t sampling, uint32_t num_k, double *ms
 
 int hr_debug_intersect(hr_ctx *c, uint32_t n, const float *rays, float *out, int32_t *out_element) {
     if (!c || !rays || !out || !out_element || !n) return fail(HR_ERR_INVALID, "hr_debug_intersect: bad argument");
+    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_intersect: not while a region is set (hr_set_region)");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_intersect: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
     float *d_rays = nullptr, *d_out = nullptr;
@@ -1766,6 +1803,7 @@ int hr_debug_intersect(hr_ctx *c, uint32_t n, const float *rays, float *out, int
 
 int hr_debug_trace(hr_ctx *c, uint32_t n, const float *rays, const float *shadow_len, float *out, int32_t *out_element) {
     if (!c || !rays || !out || !out_element || !n) return fail(HR_ERR_INVALID, "hr_debug_trace: bad argument");
+    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: not while a region is set (hr_set_region)");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_trace: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
     float *d_rays = nullptr, *d_out = nullptr, *d_sl = nullptr;

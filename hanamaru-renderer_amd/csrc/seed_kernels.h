@@ -100,7 +100,7 @@ __device__ __forceinline__ void seed_fixup_wave(const RenderParams &rp, int lens
         const uint32_t item = pid >> 6, j = pid & 63u;
         const uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
         u64 s, t;
         path_seed_words(rp.width, rp.height, px, py, sub, s, t);
         if (lane_on) {
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(64 * SEED_WAVES) void seed_isaac64_kernel(RenderPar
         const uint32_t item = (uint32_t)((in_range ? pid : paths - 1) >> 6), j = (uint32_t)((in_range ? pid : paths - 1) & 63u);
         uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
         bool valid = in_range && px < rp.width && py < rp.height;
         u64 s, t;
         path_seed_words(rp.width, rp.height, valid ? px : 0u, valid ? py : 0u, sub, s, t);
@@ -302,7 +302,7 @@ __device__ __forceinline__ void seed_pc_consumer(const RenderParams &rp, int len
         const uint32_t item = (uint32_t)((in_range ? pid : r.paths - 1) >> 6), j = (uint32_t)((in_range ? pid : r.paths - 1) & 63u);
         uint32_t tile = item / rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
         const bool valid = in_range && px < rp.width && py < rp.height;
         HR_STAMP(0);
         if (PROF) { __builtin_amdgcn_s_waitcnt(0x0F70); HR_STAMP(1); }   // vmcnt(0)
@@ -376,7 +376,7 @@ __device__ __forceinline__ void seed_pc_producer(const RenderParams &rp, const P
                 const uint32_t item = (uint32_t)(ppid >> 6), j = (uint32_t)(ppid & 63u);
                 uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
                 uint32_t px, py, sub;
-                tile_lane_pixel(rp, tile, j, px, py, sub);
+                tile_lane_frame_pixel(rp, tile, j, px, py, sub);
                 bool pvalid = px < rp.width && py < rp.height;
                 u64 s, t;
                 path_seed_words(rp.width, rp.height, pvalid ? px : 0u, pvalid ? py : 0u, sub, s, t);
@@ -500,7 +500,7 @@ __device__ __forceinline__ void seed_seg_consumer(const RenderParams &rp, int le
         const uint32_t item = (uint32_t)((in_range ? pid : r.paths - 1) >> 6), j = (uint32_t)((in_range ? pid : r.paths - 1) & 63u);
         uint32_t tile = item / rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
         const bool valid = in_range && px < rp.width && py < rp.height;
         HR_STAMP(0);
         if (PROF) { __builtin_amdgcn_s_waitcnt(0x0F70); HR_STAMP(1); }   // vmcnt(0)
@@ -547,7 +547,7 @@ __device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const 
             const uint32_t item = (uint32_t)(ppid >> 6), j = (uint32_t)(ppid & 63u);
             uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
             uint32_t px, py, sub;
-            tile_lane_pixel(rp, tile, j, px, py, sub);
+            tile_lane_frame_pixel(rp, tile, j, px, py, sub);
             bool pvalid = px < rp.width && py < rp.height;
             u64 s, t;
             path_seed_words(rp.width, rp.height, pvalid ? px : 0u, pvalid ? py : 0u, sub, s, t);
@@ -700,7 +700,7 @@ __device__ __forceinline__ void seed_ps_consumer(const RenderParams &rp, int len
         const uint32_t item = (uint32_t)((in_range ? pid : r.paths - 1) >> 6), j = (uint32_t)((in_range ? pid : r.paths - 1) & 63u);
         uint32_t tile = item / rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
         const bool valid = in_range && px < rp.width && py < rp.height;
         if (P) tm = __builtin_readcyclecounter();
         __syncthreads();   // Ws: this half's LDS is free (the round before has read its last word)
@@ -750,7 +750,7 @@ __device__ __forceinline__ void seed_ps_producer(const RenderParams &rp, const P
             const uint32_t item = (uint32_t)(ppid >> 6), j = (uint32_t)(ppid & 63u);
             uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
             uint32_t px, py, sub;
-            tile_lane_pixel(rp, tile, j, px, py, sub);
+            tile_lane_frame_pixel(rp, tile, j, px, py, sub);
             bool pvalid = px < rp.width && py < rp.height;
             u64 s, t;
             path_seed_words(rp.width, rp.height, pvalid ? px : 0u, pvalid ? py : 0u, sub, s, t);
@@ -912,7 +912,7 @@ __device__ __forceinline__ void seed_w5_consumer(const RenderParams &rp, int len
         const uint32_t item = (uint32_t)((in_range ? pid : r.paths - 1) >> 6), j = (uint32_t)((in_range ? pid : r.paths - 1) & 63u);
         uint32_t tile = item / rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
         const bool valid = in_range && px < rp.width && py < rp.height;
         HR_STAMP(0);
         if (PROF) { __builtin_amdgcn_s_waitcnt(0x0F70); HR_STAMP(1); }   // vmcnt(0)
@@ -961,7 +961,7 @@ __device__ __forceinline__ void seed_w5_producer(const RenderParams &rp, const P
             const uint32_t item = (uint32_t)(ppid >> 6), j = (uint32_t)(ppid & 63u);
             uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
             uint32_t px, py, sub;
-            tile_lane_pixel(rp, tile, j, px, py, sub);
+            tile_lane_frame_pixel(rp, tile, j, px, py, sub);
             bool pvalid = px < rp.width && py < rp.height;
             u64 s, t;
             path_seed_words(rp.width, rp.height, pvalid ? px : 0u, pvalid ? py : 0u, sub, s, t);

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, MINW) void trace_kernel(Scene sc,
                 uint32_t q = next + lane_rank(idle);
                 if (p.q == PATH_IDLE && q < total) {
                     uint32_t k = cur_k0 + (q >> 6), j = q & 63u, px, py, sub;
-                    tile_lane_pixel(rp, cur_tile, j, px, py, sub);
+                    tile_lane_frame_pixel(rp, cur_tile, j, px, py, sub);
                     if (px < rp.width && py < rp.height) {
                         p.q = (k << 6) | j;   // slot inside the tile's batch (bits 0-5: lane of the tile -> pixel, sub-sample)
                         p.tile = cur_tile;
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const 
     if (tile >= rp.tiles_x * rp.tiles_y) return;
     uint32_t px, py, sub;
     tile_lane_pixel(rp, tile, lane, px, py, sub);
-    const bool valid = px < rp.width && py < rp.height;      // (the records of lanes beyond the image's edge were never written)
+    const bool valid = rp_in_region(rp, px, py);      // (lanes beyond the region's edge: their records hold nothing of the region)
     const f4 *src = reinterpret_cast<const f4 *>(recs + (size_t)tile * rp.num_k * REC_ITEM_FLOATS) + lane;
     float r = 0.0f, g = 0.0f, b = 0.0f;
     for (uint32_t k = 0; k < rp.num_k; k++) {
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const 
     r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
     r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
     if (valid && sub == 0u) {
-        float *dst = accum + ((size_t)py * rp.width + px) * 3;
+        float *dst = accum + ((size_t)py * rp_reg_w(rp) + px) * 3;
         dst[0] += r; dst[1] += g; dst[2] += b;
     }
 }
@@ -356,13 +356,13 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void debug_render_kernel(Scene sc
     if (tile >= rp.tiles_x * rp.tiles_y) return;
     uint32_t px, py, sub;
     tile_lane_pixel(rp, tile, lane, px, py, sub);
-    const bool active = px < rp.width && py < rp.height;
+    const bool active = rp_in_region(rp, px, py);
     LaneCounters lc = {0, 0, 0, 0, 0, 0};
     WaveStats ws = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}, 0};
     Path p;
     p.q = active ? lane : PATH_IDLE;
     p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
-    debug_camera_ray(sc, rp, active ? px : 0u, active ? py : 0u, sub, p.ray);
+    debug_camera_ray(sc, rp, rp.org_x + (active ? px : 0u), rp.org_y + (active ? py : 0u), sub, p.ray);
     ray_quantise(sc, p.ray);
     trace_begin(p.ts, T_INF, p.ray.start);
     if (!active) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void debug_render_kernel(Scene sc
     val.x += __shfl_xor(val.x, 1); val.y += __shfl_xor(val.y, 1); val.z += __shfl_xor(val.z, 1);
     val.x += __shfl_xor(val.x, 2); val.y += __shfl_xor(val.y, 2); val.z += __shfl_xor(val.z, 2);
     if (active && sub == 0u) {
-        float *o = accum + ((size_t)py * rp.width + px) * 3;
+        float *o = accum + ((size_t)py * rp_reg_w(rp) + px) * 3;
         o[0] += val.x; o[1] += val.y; o[2] += val.z;
     }
     flush_counters<CNT>(cnt, lane, (uint32_t)active, lc, ws);

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void wf_start_kernel(Scene sc, RenderParams rp
     for (uint32_t item = k + (w / WF_SUBQ) * WF_SUBQ; item < items; item += per * WF_SUBQ) {
         const uint32_t tile = item / rp.num_k, ks = item - tile * rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_pixel(rp, tile, lane, px, py, sub);
+        tile_lane_frame_pixel(rp, tile, lane, px, py, sub);
         const bool valid = px < rp.width && py < rp.height;
         Path p;
         p.q = (ks << 6) | lane;

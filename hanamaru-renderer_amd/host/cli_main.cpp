@@ -4,7 +4,8 @@
 // Additive flags (do not change defaults): --scene NAME, --assets DIR, --batch N, --launch L, --inflight K, --precise, --gpus N / --gpu-ids LIST,
 // --checkpoint FILE (write the fp32 accumulator + sampling count when the render stops) and --resume FILE
 // (continue from such a file: samplings are independent and seeded by index, so a resumed render adds exactly
-// the samplings that are missing — SURVEY.md §8f rank 3; the reference has no resumable state).
+// the samplings that are missing — SURVEY.md §8f rank 3; the reference has no resumable state), --region X,Y,W,H (render the
+// window [X, X+W) x [Y, Y+H) of the -w x -h frame, bit for bit the frame's pixels there: hr_set_region; the images are W x H).
 #include <algorithm>
 #include <chrono>
 #include <cstdarg>
@@ -61,7 +62,10 @@ static void usage(const char *prog) {
            "                        the accumulators are summed with one RCCL all-reduce when an image is written (default 1)\n"
            "        --gpu-ids LIST  the same with an explicit comma-separated device list\n"
            "        --checkpoint F  write accumulator + sampling count to F when the render stops\n"
-           "        --resume F      continue from a checkpoint file\n",
+           "        --resume F      continue from a checkpoint file\n"
+           "        --region X,Y,W,H\n"
+           "                        render only the window [X, X+W) x [Y, Y+H) of the -w x -h frame (border render): its pixels are the\n"
+           "                        frame's, bit for bit, and the images are W x H; stitch tiles from their checkpoints' accumulators\n",
            prog);
 }
 
@@ -75,6 +79,7 @@ int main(int argc, char **argv) {
     int inflight = 8;   // launches enqueued ahead of the one being reported
     bool debug = false;
     int precise = -1;    // option precise_shading: -1 = the library's automatic choice
+    std::string region_arg;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -99,6 +104,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpu-ids") gpu_ids = val("gpu-ids");
         else if (a == "--checkpoint") ckpt_out = val("checkpoint");
         else if (a == "--resume") ckpt_in = val("resume");
+        else if (a == "--region") region_arg = val("region");
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -106,6 +112,30 @@ int main(int argc, char **argv) {
     if (inflight < 1) { fprintf(stderr, "--inflight must be at least 1.\n"); return 1; }
     if (width == 0 || height == 0) { fprintf(stderr, "width and height must be positive.\n"); return 1; }
     if (gpus < 1) { fprintf(stderr, "--gpus must be at least 1.\n"); return 1; }
+    // --region X,Y,W,H: four unsigned integers, a non-empty window inside the frame (hr_set_region's rule, checked before any device is opened)
+    uint32_t region[4] = {0, 0, width, height};
+    bool has_region = false;
+    if (!region_arg.empty()) {
+        uint64_t v[4];
+        int n = 0;
+        for (const char *p = region_arg.c_str(); n < 4; n++) {
+            if (*p < '0' || *p > '9') break;
+            char *e = nullptr;
+            v[n] = strtoull(p, &e, 10);
+            if (v[n] > 0xffffffffull) break;
+            p = e;
+            if (n < 3 && *p++ != ',') break;
+            if (n == 3 && *p) break;
+        }
+        if (n != 4) { fprintf(stderr, "--region must be X,Y,W,H (four unsigned integers), not '%s'.\n", region_arg.c_str()); return 1; }
+        if (!v[2] || !v[3] || v[0] > width || v[2] > width - v[0] || v[1] > height || v[3] > height - v[1]) {
+            fprintf(stderr, "--region %s: the window must be non-empty and lie inside the %ux%u frame.\n", region_arg.c_str(), width, height);
+            return 1;
+        }
+        for (int k = 0; k < 4; k++) region[k] = (uint32_t)v[k];
+        has_region = region[2] != width || region[3] != height;   // the whole frame as a region is no region
+    }
+    const uint32_t out_w = region[2], out_h = region[3];   // the accumulator and the images: the region's
     if (assets.empty()) {
         FILE *probe = fopen("assets/models/box.obj", "rb");
         if (probe) { fclose(probe); assets = "assets"; } else assets = ".";
@@ -115,6 +145,7 @@ int main(int argc, char **argv) {
     double total_begin = now_sec();
     tee("num threads: %d.", 1);  // main.rs:1261 prints rayon's pool size; here: one host thread drives one GPU
     tee("resolution: %ux%u.", width, height);
+    if (has_region) tee("region: %u,%u %ux%u.", region[0], region[1], out_w, out_h);
     tee("max sampling: %ux%u spp.", sampling, 4u);
     tee("time limit: %.2f sec.", time_limit);
     tee("report interval: %.2f sec.", interval);
@@ -141,6 +172,7 @@ int main(int argc, char **argv) {
         CHECK_HR(hr_create(devices[r], &ctxs[r]));
         CHECK_HR(hr_upload_scene(ctxs[r], hh_scene_desc(scene)));
         CHECK_HR(hr_set_resolution(ctxs[r], width, height));
+        if (has_region) CHECK_HR(hr_set_region(ctxs[r], region[0], region[1], out_w, out_h));
         if (precise >= 0) CHECK_HR(hr_set_option(ctxs[r], "precise_shading", (double)precise));
     }
     hr_ctx *ctx = ctxs[0];
@@ -161,7 +193,7 @@ int main(int argc, char **argv) {
     auto combine = [&]() -> int {
         if (ndev == 1) return 0;
         if (!host_sum) return hr_allreduce_accumulators(ctxs.data(), (int)ndev) != 0;
-        sum_acc.resize((size_t)width * height * 3);
+        sum_acc.resize((size_t)out_w * out_h * 3);
         part.resize(sum_acc.size());
         if (hr_read_accumulator(ctxs[0], sum_acc.data()) != 0) return 1;
         for (uint32_t r = 1; r < ndev; r++) {
@@ -178,7 +210,7 @@ int main(int argc, char **argv) {
         return hr_write_accumulator(ctx, part.data()) != 0 ? 1 : rc;
     };
 
-    std::vector<uint8_t> rgb((size_t)width * height * 3);
+    std::vector<uint8_t> rgb((size_t)out_w * out_h * 3);
     double begin = now_sec(), last_progress = begin, last_image = begin;
     uint32_t counter = 0, sampled = 0;
     std::string last_png;     // the image file save() wrote last: result.png is a copy of the final one (one PNG encode, not two)
@@ -189,19 +221,35 @@ int main(int argc, char **argv) {
         if (combine() || resolve(s, rgb.data()) != 0) { fprintf(stderr, "hr_resolve: %s\n", hr_last_error()); return 1; }
         printf("update_imgbuf: %.3f sec\n", now_sec() - t0);
         last_png = path;
-        return hh_write_png_rgb8(path, rgb.data(), width, height);
+        return hh_write_png_rgb8(path, rgb.data(), out_w, out_h);
     };
     uint32_t first = 1;
-    // checkpoint = {magic, width, height, samplings done, FNV-1a of the scene name} + the fp32 accumulator
-    const uint32_t CKPT_MAGIC = 0x32415248u;   // "HRA2"
+    // checkpoint = {magic, width, height, samplings done, FNV-1a of the scene name} + the fp32 accumulator; with a region the magic is
+    // "HRR2" and the header goes on with {x0, y0, w, h}, the accumulator is the region's (a full-frame checkpoint keeps the "HRA2" format)
+    const uint32_t CKPT_MAGIC = 0x32415248u;          // "HRA2"
+    const uint32_t CKPT_REGION_MAGIC = 0x32525248u;   // "HRR2"
     uint32_t scene_hash = 2166136261u;
     for (char ch : scene_name) scene_hash = (scene_hash ^ (uint8_t)ch) * 16777619u;
     if (!ckpt_in.empty()) {
         FILE *f = fopen(ckpt_in.c_str(), "rb");
-        uint32_t hdr[5] = {0, 0, 0, 0, 0};
-        std::vector<float> acc((size_t)width * height * 3);
-        bool ok = f && fread(hdr, 4, 5, f) == 5 && hdr[0] == CKPT_MAGIC && hdr[1] == width && hdr[2] == height && hdr[4] == scene_hash &&
-                  fread(acc.data(), sizeof(float), acc.size(), f) == acc.size();
+        uint32_t hdr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::vector<float> acc((size_t)out_w * out_h * 3);
+        bool ok = f && fread(hdr, 4, 5, f) == 5 && (hdr[0] == CKPT_MAGIC || hdr[0] == CKPT_REGION_MAGIC);
+        if (ok && (hdr[0] == CKPT_REGION_MAGIC) != has_region) {
+            if (f) fclose(f);
+            fprintf(stderr, "cannot resume from %s: %s\n", ckpt_in.c_str(), has_region ? "it is a full-frame checkpoint and --region is given" : "it is a region checkpoint and no --region is given");
+            return 1;
+        }
+        if (ok && has_region) {
+            ok = fread(hdr + 5, 4, 4, f) == 4;
+            if (ok && (hdr[5] != region[0] || hdr[6] != region[1] || hdr[7] != out_w || hdr[8] != out_h)) {
+                fclose(f);
+                fprintf(stderr, "cannot resume from %s: its region is %u,%u,%u,%u, --region is %u,%u,%u,%u\n", ckpt_in.c_str(), hdr[5], hdr[6], hdr[7], hdr[8],
+                        region[0], region[1], out_w, out_h);
+                return 1;
+            }
+        }
+        ok = ok && hdr[1] == width && hdr[2] == height && hdr[4] == scene_hash && fread(acc.data(), sizeof(float), acc.size(), f) == acc.size();
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot resume from %s (missing, wrong magic, resolution or scene)\n", ckpt_in.c_str()); return 1; }
         CHECK_HR(hr_write_accumulator(ctx, acc.data()));
@@ -240,7 +288,7 @@ int main(int argc, char **argv) {
     const uint32_t B = (uint32_t)batch;
     uint32_t lrep = launch > 0 ? (uint32_t)launch : 0;   // reports per launch
     if (!lrep) {   // as many reports as make the library's own automatic launch size (hanamaru_hip.h "batch": about 33 M paths) on every device
-        const uint64_t per_sampling = ((uint64_t)(width + 3) / 4) * ((height + 3) / 4) * 64u;
+        const uint64_t per_sampling = ((uint64_t)(out_w + 3) / 4) * ((out_h + 3) / 4) * 64u;
         const uint64_t lsize = std::min<uint64_t>(64, std::max<uint64_t>(4, (33177600ull + per_sampling - 1) / per_sampling));
         lrep = (uint32_t)std::max<uint64_t>(1, lsize * ndev / B);
     }
@@ -337,13 +385,14 @@ int main(int argc, char **argv) {
     }
     for (uint32_t r = 0; r < ndev; r++) CHECK_HR(hr_synchronize(ctxs[r]));
     if (!ckpt_out.empty()) {
-        std::vector<float> acc((size_t)width * height * 3);
+        std::vector<float> acc((size_t)out_w * out_h * 3);
         if (combine()) { fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
         if (host_sum) acc = sum_acc;
         else CHECK_HR(hr_read_accumulator(ctx, acc.data()));
-        uint32_t hdr[5] = {CKPT_MAGIC, width, height, sampled, scene_hash};
+        uint32_t hdr[9] = {has_region ? CKPT_REGION_MAGIC : CKPT_MAGIC, width, height, sampled, scene_hash, region[0], region[1], out_w, out_h};
+        const size_t nhdr = has_region ? 9 : 5;
         FILE *f = fopen(ckpt_out.c_str(), "wb");
-        bool ok = f && fwrite(hdr, 4, 5, f) == 5 && fwrite(acc.data(), sizeof(float), acc.size(), f) == acc.size();
+        bool ok = f && fwrite(hdr, 4, nhdr, f) == nhdr && fwrite(acc.data(), sizeof(float), acc.size(), f) == acc.size();
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot write checkpoint %s\n", ckpt_out.c_str()); return 1; }
     }
@@ -361,7 +410,7 @@ int main(int argc, char **argv) {
             if (in) fclose(in);
             if (out) copied = (fclose(out) == 0) && copied;
         }
-        if (!copied && hh_write_png_rgb8("result.png", rgb.data(), width, height) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        if (!copied && hh_write_png_rgb8("result.png", rgb.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
     }
     tee("sampled: %ux%u spp.", sampled, 4u);
     hr_stats st;

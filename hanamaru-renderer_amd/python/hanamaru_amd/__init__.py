@@ -144,6 +144,8 @@ def hip_lib():
         L.hr_upload_scene.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
         L.hr_set_resolution.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.hr_bind_accumulator.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_set_region.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.hr_get_region.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.hr_accumulator_device_ptr.argtypes = [C.c_void_p]
         L.hr_accumulator_device_ptr.restype = C.c_void_p
         L.hr_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -305,6 +307,7 @@ class Renderer:
         self._check(self.L.hr_create(device, C.byref(h)))
         self._h = h
         self.width = self.height = 0
+        self._region = None   # (x0, y0, w, h) set by set_region; None = the whole frame
 
     def _check(self, rc):
         if rc != 0:
@@ -328,6 +331,22 @@ class Renderer:
     def set_resolution(self, w, h):
         self._check(self.L.hr_set_resolution(self._h, w, h))
         self.width, self.height = w, h
+        self._region = None
+
+    def set_region(self, x0, y0, w, h):
+        """Render only the window [x0, x0+w) x [y0, y0+h) of the frame (include/hanamaru_hip.h: hr_set_region).  The accumulator becomes the
+        window's, zeroed; read_accumulator / write_accumulator / resolve then take (h, w, 3) arrays.  (0, 0, width, height) is the whole frame."""
+        self._check(self.L.hr_set_region(self._h, x0, y0, w, h))
+        self._region = None if (w, h) == (self.width, self.height) else (x0, y0, w, h)
+
+    def region(self):
+        """The window in force as (x0, y0, w, h) — (0, 0, width, height) without a region."""
+        out = (C.c_uint32 * 4)()
+        self._check(self.L.hr_get_region(self._h, out))
+        return tuple(out)
+
+    def _acc_hw(self):
+        return (self._region[3], self._region[2]) if self._region else (self.height, self.width)
 
     def bind_accumulator(self, device_ptr):
         self._check(self.L.hr_bind_accumulator(self._h, device_ptr))
@@ -363,17 +382,17 @@ class Renderer:
         self._check(self.L.hr_synchronize(self._h))
 
     def read_accumulator(self):
-        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        out = np.empty(self._acc_hw() + (3,), dtype=np.float32)
         self._check(self.L.hr_read_accumulator(self._h, out.ctypes.data))
         return out
 
     def write_accumulator(self, acc):
         a = np.ascontiguousarray(acc, dtype=np.float32)
-        assert a.shape == (self.height, self.width, 3)
+        assert a.shape == self._acc_hw() + (3,)
         self._check(self.L.hr_write_accumulator(self._h, a.ctypes.data))
 
     def resolve(self, samplings_done):
-        out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
         self._check(self.L.hr_resolve(self._h, samplings_done, out.ctypes.data))
         return out
 

@@ -161,6 +161,25 @@ int hr_set_resolution(hr_ctx *ctx, uint32_t width, uint32_t height);
  * renders).  Binding a buffer another context of this process holds returns HR_ERR_INVALID, and so does a pointer that is not device memory of
  * this context's device, is not float-aligned, or has fewer than W*H*3 floats between it and the end of its allocation.  hr_set_resolution unbinds. */
 int hr_bind_accumulator(hr_ctx *ctx, float *device_rgb);
+/* Region rendering (border / crop render): render only the window [x0, x0+w) x [y0, y0+h) of the W x H frame set by hr_set_resolution.
+ *   - Needs hr_set_resolution first (else HR_ERR_NO_TARGET).  w == 0, h == 0 or a window that does not fit in the frame (x0 > W || w > W - x0,
+ *     the same for y) is HR_ERR_INVALID, and the previous region, accumulator and binding stay in place.
+ *   - On success the accumulator is reallocated to w*h*3 floats and zeroed, as hr_set_resolution does, and a bound accumulator is unbound.
+ *     (0, 0, W, H) is the whole frame, as without a region; hr_set_resolution resets the region to the whole frame.
+ *   - Every accumulator-shaped entry point then works on the region's w*h*3 floats, row-major, top row first: hr_render, hr_render_debug,
+ *     hr_read_accumulator / hr_write_accumulator, hr_bind_accumulator (its size check), hr_accumulator_sum, hr_allreduce_accumulator(s),
+ *     hr_total_device_ptr.  hr_stats.paths counts w*h*4 per sampling.
+ *   - The contract: a path's seed and camera ray come from its pixel's FRAME coordinates (renderer.rs:48-60, 164-168), so pixel (i, j) of a
+ *     region accumulator is bit-identical to pixel (x0+i, y0+j) of a full-frame render with the same hr_render calls and options — both
+ *     shading modes, both trace pipelines, and hr_render_debug's four modes.
+ *   - hr_resolve writes w*h*3 bytes: renderer.rs:64-90 applied to the region's accumulator as an image of its own.  The bilateral filter's
+ *     clamp and wrap (filter.rs) act at the region's edges, so every pixel at least one pixel inside them equals the full-frame image's byte and
+ *     the border ring does not.  Exact 8-bit tiles of a frame come from stitching the tiles' ACCUMULATORS (hr_write_accumulator into a
+ *     full-frame context, then one hr_resolve), not from stitching their images.
+ *   - The unit-level hr_debug_* entry points (hanamaru_hip_debug.h) return HR_ERR_UNSUPPORTED while a region is set.
+ * hr_get_region: the window in force as x0, y0, w, h ((0, 0, W, H) without a region). */
+int hr_set_region(hr_ctx *ctx, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h);
+int hr_get_region(hr_ctx *ctx, uint32_t out_xywh[4]);
 void *hr_accumulator_device_ptr(hr_ctx *ctx);
 /* Optional: run on a caller-owned hipStream_t (opaque).  NULL = the context's own stream. */
 int hr_set_stream(hr_ctx *ctx, void *hip_stream);

@@ -48,6 +48,9 @@ extern "C" {
     pub fn hr_write_accumulator(ctx: *mut HrCtx, host_rgb: *const f32) -> c_int;
     pub fn hr_resolve(ctx: *mut HrCtx, samplings_done: u32, host_rgb8: *mut u8) -> c_int;
     pub fn hr_bind_accumulator(ctx: *mut HrCtx, device_rgb: *mut f32) -> c_int;
+    /// render only the window [x0, x0+w) x [y0, y0+h) of the frame; the accumulator and the resolved image become w x h (hanamaru_hip.h)
+    pub fn hr_set_region(ctx: *mut HrCtx, x0: u32, y0: u32, w: u32, h: u32) -> c_int;
+    pub fn hr_get_region(ctx: *mut HrCtx, out_xywh: *mut u32 /* [4] */) -> c_int;
     pub fn hr_accumulator_device_ptr(ctx: *mut HrCtx) -> *mut c_void;
     /// e.g. ("bvh_builder", 1.0) = build the BVH on the GPU, ("batch", 4.0) = samplings per launch; see hanamaru_hip.h.  Every key this
     /// call accepts leaves the image as the reference computes it, except the documented opt-in "russian_roulette" (off by default).

@@ -36,6 +36,10 @@ pub struct HipRenderer {
     last_report_progress: time::Tm,
     last_report_image: time::Tm,
     report_image_counter: u32,
+    /// Region rendering (hr_set_region): Some((x0, y0, w, h)) renders only that window of the frame `render` is given — its pixels
+    /// are the frame's, bit for bit — and the images written are w x h; they are also copied into the frame's imgbuf at (x0, y0).
+    /// None (default) = the whole frame.
+    pub region: Option<(u32, u32, u32, u32)>,
 }
 unsafe impl Sync for HipRenderer {} // the context is only touched from render(), on the calling thread
 
@@ -86,8 +90,18 @@ impl HipRenderer {
             None => println!("output progress image: {}", path),
         }
         check(unsafe { hr_synchronize(self.ctx) });
-        check(unsafe { hr_resolve(self.ctx, sampling, imgbuf.as_mut_ptr()) }); // RGB8, row-major, top row first
-        let _ = image::ImageRgb8(imgbuf.clone()).save(&path);
+        match self.region {
+            None => {
+                check(unsafe { hr_resolve(self.ctx, sampling, imgbuf.as_mut_ptr()) }); // RGB8, row-major, top row first
+                let _ = image::ImageRgb8(imgbuf.clone()).save(&path);
+            }
+            Some((x0, y0, w, h)) => {   // the region's own image (w x h), and its pixels in their place of the frame
+                let mut out: ImageBuffer<Rgb<u8>, Vec<u8>> = ImageBuffer::new(w, h);
+                check(unsafe { hr_resolve(self.ctx, sampling, out.as_mut_ptr()) });
+                for (x, y, p) in out.enumerate_pixels() { imgbuf.put_pixel(x0 + x, y0 + y, *p); }
+                let _ = image::ImageRgb8(out).save(&path);
+            }
+        }
         if why.is_none() { self.report_image_counter += 1; }
     }
     pub fn new(sampling: u32, time_limit_sec: f64, report_interval_sec: f64) -> HipRenderer {
@@ -97,7 +111,7 @@ impl HipRenderer {
         check(unsafe { hr_create(0, &mut ctx) });
         let now = time::now();
         HipRenderer { ctx, sampling, time_limit_sec, report_interval_sec, begin: now, last_report_progress: now,
-                      last_report_image: now, report_image_counter: 0 }
+                      last_report_image: now, report_image_counter: 0, region: None }
     }
 
     fn upload(&mut self, scene: &BvhScene, camera: &Camera) {
@@ -151,6 +165,8 @@ impl Renderer for HipRenderer {
         // main.rs:1216 always passes a BvhScene; the trait object needs `fn as_bvh_scene(&self) -> &BvhScene` (one line in scene.rs)
         self.upload(scene.as_bvh_scene(), camera);
         check(unsafe { hr_set_resolution(self.ctx, imgbuf.width(), imgbuf.height()) });
+        if let Some((x0, y0, w, h)) = self.region { check(unsafe { hr_set_region(self.ctx, x0, y0, w, h) }); }
+        let (out_w, out_h) = self.region.map_or((imgbuf.width(), imgbuf.height()), |r| (r.2, r.3));
         // renderer.rs:32-43 with report_progress (renderer.rs:205-251) — the loop of hanamaru-hip's cli_main.cpp (compiled and tested there),
         // statement for statement.  Every sampling gets its own "rendering:" line; the GPU is fed LAUNCHES of `lrep` samplings (what fills the
         // chip: 4 at 1920x1080) and up to IN_FLIGHT launches are enqueued ahead (hr_mark behind each, hr_wait for the oldest).  A launch's lines
@@ -158,7 +174,7 @@ impl Renderer for HipRenderer {
         // are ISSUED, for the moment they would finish: n are issued only if used + 1.1 x last x (in flight + n) <= limit — with one sampling
         // in flight (report_interval_sec <= 0: an image is due after every report) the reference's rule to the letter.  A progress image is
         // written at a launch boundary, after the launches in flight have been reported: it holds exactly the samplings of the line before it.
-        let per_sampling = ((imgbuf.width() as u64 + 3) / 4) * ((imgbuf.height() as u64 + 3) / 4) * 64;
+        let per_sampling = ((out_w as u64 + 3) / 4) * ((out_h as u64 + 3) / 4) * 64;
         let lrep: u32 = if self.report_interval_sec <= 0.0 { 1 } else { ((33_177_600 + per_sampling - 1) / per_sampling).max(4).min(64) as u32 };
         let depth = if self.report_interval_sec <= 0.0 { 1 } else { IN_FLIGHT };
         if lrep > 1 { println!("launches of {} reports ({} samplings): a launch's time is split evenly over its reports' lines.", lrep, lrep); }
