@@ -55,6 +55,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "trace_kernel.h"
 #include "wf_kernels.h"
 #include "post_kernels.h"
+#include "noise_core.h"
 
 // ------------------------------------------------------------------------------------------ context
 
@@ -78,6 +79,11 @@ struct hr_ctx {
     float *accum_own = nullptr, *accum = nullptr;
     float *post_tmp = nullptr;
     uint8_t *d_rgb8 = nullptr;
+    // option "moments": per pixel {S1r, S1g, S1b, S2r, S2g, S2b} of the per-sampling values (accumulate_kernel<true>), the samplings behind
+    // them, and the noise image of the last estimate (allocated when one is first asked for)
+    bool moments_on = false;
+    double *moments = nullptr, *noise_img = nullptr;
+    uint64_t moments_n = 0;
     // multi-GPU: RCCL communicator of this rank, and the all-reduced accumulator (valid until the next render / clear / write)
     hrcomm::Comm comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -442,6 +448,8 @@ int hr_destroy(hr_ctx *c) {
     if (c->post_tmp) (void)hipFree(c->post_tmp);
     if (c->d_rgb8) (void)hipFree(c->d_rgb8);
     if (c->accum_total) (void)hipFree(c->accum_total);
+    if (c->moments) (void)hipFree(c->moments);
+    if (c->noise_img) (void)hipFree(c->noise_img);
     if (c->comm && hrcomm::api().CommDestroy) (void)hrcomm::api().CommDestroy(c->comm);
     for (hr_ctx *p : c->same_device_peers) if (p != c) { p->same_device_peers.clear(); p->comm_world = 0; p->total_valid = false; p->comm_path = HR_COMM_NONE; p->allreduces = 0; }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -719,6 +727,23 @@ int hr_upload_scene(hr_ctx *c, const hr_scene_desc *sd) {
     return HR_OK;
 }
 
+// The moments buffer (option "moments") follows the accumulator: the window's size, zeroed together with the count.
+static int free_moments(hr_ctx *c) {
+    c->moments_n = 0;
+    if (c->moments) { HIP_TRY(hipFree(c->moments)); c->moments = nullptr; }
+    if (c->noise_img) { HIP_TRY(hipFree(c->noise_img)); c->noise_img = nullptr; }
+    return HR_OK;
+}
+static int alloc_moments(hr_ctx *c, uint32_t w, uint32_t h) {
+    int rc = free_moments(c);
+    if (rc) return rc;
+    const size_t bytes = (size_t)w * h * 6 * sizeof(double);
+    HIP_TRY(hipMalloc((void **)&c->moments, bytes));
+    HIP_TRY(hipMemset(c->moments, 0, bytes));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // (the render streams do not wait for the null stream)
+    return HR_OK;
+}
+
 // The target: the W x H frame and the window of it that is rendered (the whole frame, or hr_set_region's).  The accumulator and the resolve's
 // buffers are (re)allocated for the window and zeroed.
 static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
@@ -733,6 +758,7 @@ static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y
     if (c->post_tmp) { HIP_TRY(hipFree(c->post_tmp)); c->post_tmp = nullptr; }
     if (c->d_rgb8) { HIP_TRY(hipFree(c->d_rgb8)); c->d_rgb8 = nullptr; }
     if (c->accum_total) { HIP_TRY(hipFree(c->accum_total)); c->accum_total = nullptr; }
+    if (c->moments_on) { int mrc = alloc_moments(c, w, h); if (mrc) return mrc; }
     size_t n = (size_t)w * h * 3;
     HIP_TRY(hipMalloc((void **)&c->accum_own, n * sizeof(float)));
     HIP_TRY(hipMemset(c->accum_own, 0, n * sizeof(float)));
@@ -836,7 +862,9 @@ int hr_clear(hr_ctx *c) {
     invalidate_totals(c);
     HIP_TRY(hipMemsetAsync(c->accum, 0, (size_t)c->RW * c->RH * 3 * sizeof(float), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
+    if (c->moments) HIP_TRY(hipMemsetAsync(c->moments, 0, (size_t)c->RW * c->RH * 6 * sizeof(double), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->moments_n = 0;
     c->seed_ms = c->trace_ms = c->post_ms = c->debug_ms = 0;
     c->seed_launches = c->trace_launches = c->debug_launches = 0;
     c->paths_rendered = 0;
@@ -1110,8 +1138,10 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         // the launch's radiance into the accumulator (the trace kernel left every path's in its record), in the gap in which this
         // stream waits for the next seed kernel anyway
         if (!(c->debug_skip & 16)) {
-            hipLaunchKernelGGL(accumulate_kernel, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->accum);
+            if (c->moments) hipLaunchKernelGGL(accumulate_kernel<true>, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->accum, c->moments);
+            else hipLaunchKernelGGL(accumulate_kernel<false>, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->accum, (double *)nullptr);
             HIP_TRY(hipGetLastError());
+            if (c->moments) c->moments_n += nk;
         }
         // the governor judges the launch that has just finished and frees its stamps; the seed kernel that reuses the slot waits for
         // trace_done, recorded behind it
@@ -1132,6 +1162,7 @@ int hr_render_debug(hr_ctx *c, int mode) {
     if (!c || mode < 0 || mode > 3) return fail(HR_ERR_INVALID, "hr_render_debug: mode must be 0..3");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_render_debug: no scene uploaded");
     if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_render_debug: hr_set_resolution not called");
+    if (c->moments_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option moments on (a debug sampling goes into the accumulator without per-sampling values)");
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
     RenderParams rp{};
@@ -1426,6 +1457,104 @@ int hr_accumulator_sum(hr_ctx *c, int which, double out_rgb[3]) {
     return HR_OK;
 }
 
+// ---- option "moments": the moments, and the noise estimate made of them (noise_core.h) ----
+static int moments_ready(hr_ctx *c, const char *who) {
+    if (!c) return fail(HR_ERR_INVALID, "%s: null ctx", who);
+    if (!c->moments_on || !c->moments) return fail(HR_ERR_INVALID, "%s: option moments is off", who);
+    return HR_OK;
+}
+int hr_read_moments(hr_ctx *c, double *host, uint64_t *samplings) {
+    int rc = moments_ready(c, "hr_read_moments");
+    if (rc) return rc;
+    if (!host) return fail(HR_ERR_INVALID, "hr_read_moments: null argument");
+    if ((rc = hr_synchronize(c))) return rc;
+    HIP_TRY(hipMemcpy(host, c->moments, (size_t)c->RW * c->RH * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (samplings) *samplings = c->moments_n;
+    return HR_OK;
+}
+int hr_write_moments(hr_ctx *c, const double *host, uint64_t samplings) {
+    int rc = moments_ready(c, "hr_write_moments");
+    if (rc) return rc;
+    if (!host) return fail(HR_ERR_INVALID, "hr_write_moments: null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = sync_all(c))) return rc;
+    HIP_TRY(hipMemcpy(c->moments, host, (size_t)c->RW * c->RH * 6 * sizeof(double), hipMemcpyHostToDevice));
+    c->moments_n = samplings;
+    return HR_OK;
+}
+
+// e of every pixel into `img`, and its summary, reduced in a fixed order (the scheme of accumulator_sum_kernel: a fixed grid, every thread its
+// strided pixels in order, lanes and waves in order, the host adds the blocks' partial sums in index order): reproducible run to run.
+// out[block] = {sum of e, max of e, pixels with e > threshold}.
+static const unsigned NOISE_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void noise_kernel(const double *__restrict__ moments, size_t pixels, uint64_t samplings, double floor, double threshold,
+                                                    double *__restrict__ img, double *__restrict__ out) {
+    double sum = 0.0, mx = 0.0, above = 0.0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
+        double m[6];
+        for (int k = 0; k < 6; k++) m[k] = moments[i * 6 + k];
+        const double e = hr::noise_pixel_error(m, samplings, floor);
+        img[i] = e;
+        sum += e;
+        mx = e > mx ? e : mx;
+        above += e > threshold ? 1.0 : 0.0;
+    }
+    __shared__ double part[4][3];
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_down(sum, off);
+        const double o = __shfl_down(mx, off);
+        mx = o > mx ? o : mx;
+        above += __shfl_down(above, off);
+    }
+    if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][0] = sum; part[threadIdx.x >> 6][1] = mx; part[threadIdx.x >> 6][2] = above; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *o = out + (size_t)blockIdx.x * 3;
+        o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
+        o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
+        o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
+    }
+}
+// host_img: the image as well (or NULL); est: the summary (or NULL)
+static int noise_run(hr_ctx *c, const char *who, double floor, double threshold, double *host_img, hr_noise *est) {
+    int rc = moments_ready(c, who);
+    if (rc) return rc;
+    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "%s: floor must be a positive finite radiance", who);
+    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
+    if (c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
+    if ((rc = hr_synchronize(c))) return rc;
+    const size_t pixels = (size_t)c->RW * c->RH;
+    if (!c->noise_img) HIP_TRY(hipMalloc((void **)&c->noise_img, pixels * sizeof(double)));
+    double *d = nullptr;
+    std::vector<double> h(NOISE_BLOCKS * 3);
+    HIP_TRY(hipMalloc((void **)&d, h.size() * sizeof(double)));
+    hipLaunchKernelGGL(noise_kernel, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && host_img) e = hipMemcpyAsync(host_img, c->noise_img, pixels * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    if (est) {
+        double sum = 0.0, mx = 0.0, above = 0.0;
+        for (unsigned b = 0; b < NOISE_BLOCKS; b++) { sum += h[b * 3]; mx = h[b * 3 + 1] > mx ? h[b * 3 + 1] : mx; above += h[b * 3 + 2]; }
+        est->samplings = c->moments_n;
+        est->pixels = (uint64_t)pixels;
+        est->pixels_above = (uint64_t)above;
+        est->mean_error = sum / (double)pixels;
+        est->max_error = mx;
+    }
+    return HR_OK;
+}
+int hr_noise_estimate(hr_ctx *c, double floor, double threshold, hr_noise *out) {
+    if (c && !out) return fail(HR_ERR_INVALID, "hr_noise_estimate: null argument");
+    return noise_run(c, "hr_noise_estimate", floor, threshold, nullptr, out);
+}
+int hr_read_noise_image(hr_ctx *c, double floor, double *host) {
+    if (c && !host) return fail(HR_ERR_INVALID, "hr_read_noise_image: null argument");
+    return noise_run(c, "hr_read_noise_image", floor, 0.0, host, nullptr);
+}
+
 int hr_get_stats(hr_ctx *c, hr_stats *out) {
     if (!c || !out) return fail(HR_ERR_INVALID, "hr_get_stats: null argument");
     HIP_TRY(hipSetDevice(c->device));
@@ -1476,6 +1605,17 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
         if (rc) return rc;
         c->trace_boost = (int)value;
         return govern_reset(c);
+    }
+    if (k == "moments") {   // per-pixel first and second moments of the per-sampling values, for the noise estimate
+        if (value != 0 && value != 1) return fail(HR_ERR_INVALID, "moments must be 0 or 1");
+        if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "moments: hr_set_resolution not called");
+        int rc = sync_all(c);
+        if (rc) return rc;
+        if (value == 0) { c->moments_on = false; return free_moments(c); }
+        if (c->moments_on) return HR_OK;   // already on: the moments gathered so far stay
+        if ((rc = alloc_moments(c, c->RW, c->RH))) { (void)free_moments(c); return rc; }
+        c->moments_on = true;
+        return HR_OK;
     }
     if (k == "quant_nodes") { c->quant_nodes = value != 0.0; return HR_OK; }
     if (k == "max_tail_gib") {

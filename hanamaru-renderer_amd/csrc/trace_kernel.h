@@ -262,7 +262,13 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, MINW) void trace_kernel(Scene sc,
 // scenes a near-mirror GGX from a roughness map's ~0 texel can overflow fp32's D term where the reference's f64 carries 1e29, and one NaN of an
 // approximate reciprocal was seen in 1.2e11 paths — one such path must not cost a pixel (and, through the bilateral filter, its neighbours).
 __device__ __forceinline__ float path_radiance_in(float x) { return x == x ? fminf(fmaxf(x, -1e30f), 1e30f) : 0.0f; }
-__global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const float *__restrict__ recs, float *__restrict__ accum) {
+// MOM (option "moments"): the same kernel — the accumulator comes out bit for bit — that also keeps the first and second moments of
+// the per-sampling pixel values x_k = (v0 + v1) + (v2 + v3) (fp32, the butterfly below done per k: what a launch of ONE sampling adds to a zeroed
+// pixel), S1 += (double)x_k, S2 += (double)x_k^2 (the product of two fp32 values is exact in f64), one sampling at a time in the order rendered,
+// from the values in the buffer: the lane of sub-sample 0 loads the pixel's six doubles, runs the loop, stores them — the moments do not depend
+// on how samplings are cut into launches.  moments[reg_h][reg_w][6] = {S1r, S1g, S1b, S2r, S2g, S2b}.  No clamp: |v| <= 1e30, x^2 <= 1.6e61.
+template <bool MOM>
+__global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const float *__restrict__ recs, float *__restrict__ accum, double *__restrict__ moments) {
     const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (tile >= rp.tiles_x * rp.tiles_y) return;
     uint32_t px, py, sub;
@@ -270,15 +276,30 @@ __global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const 
     const bool valid = rp_in_region(rp, px, py);      // (lanes beyond the region's edge: their records hold nothing of the region)
     const f4 *src = reinterpret_cast<const f4 *>(recs + (size_t)tile * rp.num_k * REC_ITEM_FLOATS) + lane;
     float r = 0.0f, g = 0.0f, b = 0.0f;
+    double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double *mom = nullptr;
+    if (MOM && valid && sub == 0u) {
+        mom = moments + ((size_t)py * rp_reg_w(rp) + px) * 6;
+        for (int i = 0; i < 6; i++) m[i] = mom[i];
+    }
     for (uint32_t k = 0; k < rp.num_k; k++) {
         const f4 v = valid ? src[(size_t)k * (REC_ITEM_FLOATS / 4u)] : f4{0.0f, 0.0f, 0.0f, 0.0f};
-        r += path_radiance_in(v.x); g += path_radiance_in(v.y); b += path_radiance_in(v.z);
+        const float vr = path_radiance_in(v.x), vg = path_radiance_in(v.y), vb = path_radiance_in(v.z);
+        r += vr; g += vg; b += vb;
+        if (MOM) {   // (every lane of the wave is here: the trip count is the launch's)
+            float xr = vr + __shfl_xor(vr, 1), xg = vg + __shfl_xor(vg, 1), xb = vb + __shfl_xor(vb, 1);
+            xr += __shfl_xor(xr, 2); xg += __shfl_xor(xg, 2); xb += __shfl_xor(xb, 2);
+            const double dr = (double)xr, dg = (double)xg, db = (double)xb;
+            m[0] += dr; m[1] += dg; m[2] += db;
+            m[3] += dr * dr; m[4] += dg * dg; m[5] += db * db;
+        }
     }
     r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
     r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
     if (valid && sub == 0u) {
         float *dst = accum + ((size_t)py * rp_reg_w(rp) + px) * 3;
         dst[0] += r; dst[1] += g; dst[2] += b;
+        if (MOM) for (int i = 0; i < 6; i++) mom[i] = m[i];
     }
 }
 

@@ -5,9 +5,12 @@
 // --checkpoint FILE (write the fp32 accumulator + sampling count when the render stops) and --resume FILE
 // (continue from such a file: samplings are independent and seeded by index, so a resumed render adds exactly
 // the samplings that are missing — SURVEY.md §8f rank 3; the reference has no resumable state), --region X,Y,W,H (render the
-// window [X, X+W) x [Y, Y+H) of the -w x -h frame, bit for bit the frame's pixels there: hr_set_region; the images are W x H).
+// window [X, X+W) x [Y, Y+H) of the -w x -h frame, bit for bit the frame's pixels there: hr_set_region; the images are W x H),
+// --noise-target E / --noise-floor F / --noise-check N / --noise-image FILE (option "moments": stop when the mean relative standard error of
+// the pixels is <= E; hr_noise_estimate — the reference stops on a sampling count or the clock only).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -65,7 +68,17 @@ static void usage(const char *prog) {
            "        --resume F      continue from a checkpoint file\n"
            "        --region X,Y,W,H\n"
            "                        render only the window [X, X+W) x [Y, Y+H) of the -w x -h frame (border render): its pixels are the\n"
-           "                        frame's, bit for bit, and the images are W x H; stitch tiles from their checkpoints' accumulators\n",
+           "                        frame's, bit for bit, and the images are W x H; stitch tiles from their checkpoints' accumulators\n"
+           "        --noise-target E\n"
+           "                        keep per-pixel sample moments and stop as soon as the mean over the pixels of the relative standard error\n"
+           "                        e = (se_r + se_g + se_b) / (r + g + b + 3 F) is <= E — or at -s samplings / the time limit, whichever comes\n"
+           "                        first (0 = never reached: measure only).  Every check prints a line \"noise: samplings= mean= max= above=\"\n"
+           "                        (above = pixels with e > E); the last one goes to result.txt as well\n"
+           "        --noise-floor F radiance below which a pixel's error is judged absolutely instead of relatively (default 0.01; > 0)\n"
+           "        --noise-check N ask every N samplings (default 64, rounded up to whole launches): the question waits for the launches\n"
+           "                        in flight, so it is asked rarely\n"
+           "        --noise-image FILE.png\n"
+           "                        write an 8-bit grey map of min(1, e / E) at the end of the render (E = the target, or 0.05 without one)\n",
            prog);
 }
 
@@ -79,7 +92,17 @@ int main(int argc, char **argv) {
     int inflight = 8;   // launches enqueued ahead of the one being reported
     bool debug = false;
     int precise = -1;    // option precise_shading: -1 = the library's automatic choice
-    std::string region_arg;
+    std::string region_arg, noise_png;
+    bool have_target = false;
+    double noise_target = 0.0, noise_floor = 0.01;
+    long long noise_check = 64;
+    // a number, the whole argument, not NaN; what is wrong with it is said with the flag's name, before any device is opened
+    auto number = [](const char *flag, const char *text, double *out) -> bool {
+        char *e = nullptr;
+        *out = strtod(text, &e);
+        if (e == text || *e || std::isnan(*out) || std::isinf(*out)) { fprintf(stderr, "%s: '%s' is not a number.\n", flag, text); return false; }
+        return true;
+    };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -105,6 +128,19 @@ int main(int argc, char **argv) {
         else if (a == "--checkpoint") ckpt_out = val("checkpoint");
         else if (a == "--resume") ckpt_in = val("resume");
         else if (a == "--region") region_arg = val("region");
+        else if (a == "--noise-target") {
+            if (!number("--noise-target", val("noise-target"), &noise_target)) return 1;
+            if (noise_target < 0.0) { fprintf(stderr, "--noise-target must not be negative.\n"); return 1; }
+            have_target = true;
+        } else if (a == "--noise-floor") {
+            if (!number("--noise-floor", val("noise-floor"), &noise_floor)) return 1;
+            if (!(noise_floor > 0.0)) { fprintf(stderr, "--noise-floor must be positive.\n"); return 1; }
+        } else if (a == "--noise-check") {
+            const char *t = val("noise-check");
+            char *e = nullptr;
+            noise_check = strtoll(t, &e, 10);
+            if (e == t || *e || noise_check < 1 || noise_check > 0x7fffffffll) { fprintf(stderr, "--noise-check must be a whole number of samplings, at least 1, not '%s'.\n", t); return 1; }
+        } else if (a == "--noise-image") noise_png = val("noise-image");
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -112,6 +148,9 @@ int main(int argc, char **argv) {
     if (inflight < 1) { fprintf(stderr, "--inflight must be at least 1.\n"); return 1; }
     if (width == 0 || height == 0) { fprintf(stderr, "width and height must be positive.\n"); return 1; }
     if (gpus < 1) { fprintf(stderr, "--gpus must be at least 1.\n"); return 1; }
+    const bool moments = have_target || !noise_png.empty();   // hr_set_option "moments"
+    if (moments && debug) { fprintf(stderr, "--noise-target / --noise-image cannot be combined with --debug (the debug renderer has no samplings to measure).\n"); return 1; }
+    const double noise_e = have_target && noise_target > 0.0 ? noise_target : (have_target ? 0.0 : 0.05);   // the threshold of "above" and of the grey map
     // --region X,Y,W,H: four unsigned integers, a non-empty window inside the frame (hr_set_region's rule, checked before any device is opened)
     uint32_t region[4] = {0, 0, width, height};
     bool has_region = false;
@@ -174,6 +213,7 @@ int main(int argc, char **argv) {
         CHECK_HR(hr_set_resolution(ctxs[r], width, height));
         if (has_region) CHECK_HR(hr_set_region(ctxs[r], region[0], region[1], out_w, out_h));
         if (precise >= 0) CHECK_HR(hr_set_option(ctxs[r], "precise_shading", (double)precise));
+        if (moments) CHECK_HR(hr_set_option(ctxs[r], "moments", 1.0));
     }
     hr_ctx *ctx = ctxs[0];
     if (ndev > 1) tee("devices: %u.", ndev);
@@ -210,6 +250,49 @@ int main(int argc, char **argv) {
         return hr_write_accumulator(ctx, part.data()) != 0 ? 1 : rc;
     };
 
+    // The noise estimate of everything rendered so far.  Several devices: every device holds the moments of its own samplings; they are
+    // additive, so the host adds them in rank order (as sum_acc does for accumulators without RCCL), device 0 estimates the total and gets
+    // its own moments back.  tot_out / n_out: the summed moments and their count as well (for the checkpoint).
+    // Returns 0, 1 = error, 2 = fewer than two samplings behind the moments (no variance yet).
+    std::vector<double> mom_tot, mom_part, mom_own;
+    auto noise_query = [&](hr_noise *est, double *img, std::vector<double> *tot_out, uint64_t *n_out) -> int {
+        uint64_t n_own = 0, n_tot = 0;
+        const size_t len = (size_t)out_w * out_h * 6;
+        if (ndev > 1 || tot_out) {
+            mom_tot.resize(len);
+            if (hr_read_moments(ctx, mom_tot.data(), &n_own) != 0) return 1;
+            n_tot = n_own;
+        }
+        if (ndev > 1) {
+            mom_own = mom_tot;
+            mom_part.resize(len);
+            for (uint32_t r = 1; r < ndev; r++) {
+                uint64_t n_r = 0;
+                if (hr_read_moments(ctxs[r], mom_part.data(), &n_r) != 0) return 1;
+                for (size_t i = 0; i < len; i++) mom_tot[i] += mom_part[i];
+                n_tot += n_r;
+            }
+            if (hr_write_moments(ctx, mom_tot.data(), n_tot) != 0) return 1;
+        }
+        memset(est, 0, sizeof *est);
+        int rc = hr_noise_estimate(ctx, noise_floor, noise_e, est);   // (HR_ERR_INVALID: n < 2 — floor and threshold were checked with the flags)
+        if (rc == 0 && img) rc = hr_read_noise_image(ctx, noise_floor, img);
+        if (ndev > 1 && hr_write_moments(ctx, mom_own.data(), n_own) != 0) return 1;
+        if (tot_out) *tot_out = mom_tot;
+        if (n_out) *n_out = n_tot;
+        return rc == 0 ? 0 : (rc == HR_ERR_INVALID ? 2 : 1);
+    };
+    hr_noise noise_last;
+    bool noise_known = false;
+    // one "noise:" line per check, after the "rendering:" lines of the samplings it covers
+    auto noise_check_now = [&]() -> int {
+        int rc = noise_query(&noise_last, nullptr, nullptr, nullptr);
+        if (rc == 1) { fprintf(stderr, "hr_noise_estimate: %s\n", hr_last_error()); return 1; }
+        noise_known = rc == 0;
+        if (noise_known) printf("noise: samplings=%llu mean=%.9g max=%.9g above=%llu\n", (unsigned long long)noise_last.samplings, noise_last.mean_error, noise_last.max_error,
+                                (unsigned long long)noise_last.pixels_above);
+        return 0;
+    };
     std::vector<uint8_t> rgb((size_t)out_w * out_h * 3);
     double begin = now_sec(), last_progress = begin, last_image = begin;
     uint32_t counter = 0, sampled = 0;
@@ -228,6 +311,7 @@ int main(int argc, char **argv) {
     // "HRR2" and the header goes on with {x0, y0, w, h}, the accumulator is the region's (a full-frame checkpoint keeps the "HRA2" format)
     const uint32_t CKPT_MAGIC = 0x32415248u;          // "HRA2"
     const uint32_t CKPT_REGION_MAGIC = 0x32525248u;   // "HRR2"
+    const uint32_t CKPT_MOMENTS_MAGIC = 0x534d5248u;  // "HRMS": the trailer behind the accumulator of a render with moments on
     uint32_t scene_hash = 2166136261u;
     for (char ch : scene_name) scene_hash = (scene_hash ^ (uint8_t)ch) * 16777619u;
     if (!ckpt_in.empty()) {
@@ -250,9 +334,25 @@ int main(int argc, char **argv) {
             }
         }
         ok = ok && hdr[1] == width && hdr[2] == height && hdr[4] == scene_hash && fread(acc.data(), sizeof(float), acc.size(), f) == acc.size();
+        // a checkpoint written with moments on goes on with the trailer {"HRMS", samplings behind the moments, w*h*6 doubles}
+        uint32_t mmagic = 0;
+        uint64_t mom_n = 0;
+        std::vector<double> mom;
+        bool have_mom = false;
+        if (ok && moments && fread(&mmagic, 4, 1, f) == 1 && mmagic == CKPT_MOMENTS_MAGIC) {
+            mom.resize((size_t)out_w * out_h * 6);
+            have_mom = fread(&mom_n, 8, 1, f) == 1 && fread(mom.data(), sizeof(double), mom.size(), f) == mom.size();
+        }
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot resume from %s (missing, wrong magic, resolution or scene)\n", ckpt_in.c_str()); return 1; }
+        if (have_target && !have_mom) {
+            fprintf(stderr, "--resume %s with --noise-target: the checkpoint holds no sample moments (it was written without --noise-target / --noise-image), "
+                            "so the noise of its %u samplings cannot be known; resume without --noise-target, or render again with it.\n", ckpt_in.c_str(), hdr[3]);
+            return 1;
+        }
         CHECK_HR(hr_write_accumulator(ctx, acc.data()));
+        if (have_mom) CHECK_HR(hr_write_moments(ctx, mom.data(), mom_n));
+        else if (moments) printf("the checkpoint holds no sample moments: the noise image covers the samplings rendered from here on\n");
         first = hdr[3] + 1;
         sampled = hdr[3];
         printf("resumed at %ux4 sampled\n", hdr[3]);
@@ -349,8 +449,12 @@ int main(int argc, char **argv) {
     };
     // how many reports may be enqueued now?  (samplings left, room in the pipeline, and the time-limit rule asked for the moment they would finish)
     const size_t depth = interval <= 0.0 ? 1 : (size_t)inflight;
+    // --noise-target: nothing is issued beyond the sampling at which the next question is due (whole launches: the launch that
+    // reaches it is not cut), so that a render that has reached its target stops there and not a pipeline's depth later
+    uint64_t check_at = (uint64_t)first - 1 + (uint64_t)noise_check;
     auto may_issue = [&]() -> uint32_t {
         if (next_s > sampling || q.size() >= depth) return 0;
+        if (have_target && (uint64_t)next_s > check_at) return 0;
         const uint32_t n = std::min<uint32_t>(lrep, reports_of(next_s, sampling + 1));
         if (!measured) return n;   // nothing measured yet: fill the pipeline
         const double room = time_limit - (now_sec() - begin);
@@ -365,6 +469,12 @@ int main(int argc, char **argv) {
     bool running = first <= sampling;
     while (running) {
         for (uint32_t n; (n = may_issue()) != 0;) if (issue(n)) return 1;
+        if (q.empty() && have_target && next_s <= sampling && (uint64_t)next_s > check_at) {   // the question is due, and nothing is in flight
+            if (noise_check_now()) return 1;
+            if (noise_known && noise_last.mean_error <= noise_target) { if (finish("reached noise target")) return 1; break; }
+            check_at = (uint64_t)next_s - 1 + (uint64_t)noise_check;
+            continue;
+        }
         if (q.empty()) {   // nothing in flight and nothing may follow: the render ends here (renderer.rs:222-241, the time limit asked first)
             // (samplings left over: only the time-limit rule can have refused them)
             if (finish(next_s <= sampling || used + 1.1 * last > time_limit ? "reached time limit" : "reached max sampling")) return 1;
@@ -393,6 +503,13 @@ int main(int argc, char **argv) {
         const size_t nhdr = has_region ? 9 : 5;
         FILE *f = fopen(ckpt_out.c_str(), "wb");
         bool ok = f && fwrite(hdr, 4, nhdr, f) == nhdr && fwrite(acc.data(), sizeof(float), acc.size(), f) == acc.size();
+        if (ok && moments) {   // the trailer; a file written without moments keeps the bytes it always had
+            hr_noise est;
+            std::vector<double> mom;
+            uint64_t mom_n = 0;
+            if (noise_query(&est, nullptr, &mom, &mom_n) == 1) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
+            ok = fwrite(&CKPT_MOMENTS_MAGIC, 4, 1, f) == 1 && fwrite(&mom_n, 8, 1, f) == 1 && fwrite(mom.data(), sizeof(double), mom.size(), f) == mom.size();
+        }
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot write checkpoint %s\n", ckpt_out.c_str()); return 1; }
     }
@@ -411,6 +528,24 @@ int main(int argc, char **argv) {
             if (out) copied = (fclose(out) == 0) && copied;
         }
         if (!copied && hh_write_png_rgb8("result.png", rgb.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+    }
+    if (moments) {   // the estimate of the final image, to result.txt as well; and its map
+        std::vector<double> e_img(noise_png.empty() ? 0 : (size_t)out_w * out_h);
+        int rc = noise_query(&noise_last, e_img.empty() ? nullptr : e_img.data(), nullptr, nullptr);
+        if (rc == 1) { fprintf(stderr, "hr_noise_estimate: %s\n", hr_last_error()); return 1; }
+        if (rc == 2) tee("noise: fewer than 2 samplings, no estimate.");
+        else tee("noise: samplings=%llu mean=%.9g max=%.9g above=%llu", (unsigned long long)noise_last.samplings, noise_last.mean_error, noise_last.max_error,
+                 (unsigned long long)noise_last.pixels_above);
+        if (!noise_png.empty() && rc == 0) {   // grey map of min(1, e / E)
+            const double E = noise_e > 0.0 ? noise_e : 0.05;
+            std::vector<uint8_t> grey((size_t)out_w * out_h * 3);
+            for (size_t i = 0; i < e_img.size(); i++) {
+                const double t = e_img[i] / E;
+                const uint8_t v = (uint8_t)((t >= 1.0 ? 1.0 : (t > 0.0 ? t : 0.0)) * 255.0 + 0.5);
+                grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = v;
+            }
+            if (hh_write_png_rgb8(noise_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        }
     }
     tee("sampled: %ux%u spp.", sampled, 4u);
     hr_stats st;

@@ -75,6 +75,11 @@ class CommInfo(C.Structure):
                 ("rccl_version", C.c_int32), ("_pad", C.c_int32), ("allreduces", C.c_uint64)]
 
 
+class Noise(C.Structure):
+    _fields_ = [("samplings", C.c_uint64), ("pixels", C.c_uint64), ("pixels_above", C.c_uint64),
+                ("mean_error", C.c_double), ("max_error", C.c_double)]
+
+
 COMM_PATHS = {0: "none", 1: "rccl-rank", 2: "rccl-group", 3: "same-device-fallback"}
 
 
@@ -178,6 +183,10 @@ def hip_lib():
         L.hr_total_device_ptr.restype = C.c_void_p
         L.hr_comm_info.argtypes = [C.c_void_p, C.POINTER(CommInfo)]
         L.hr_accumulator_sum.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        L.hr_read_moments.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.hr_write_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.hr_noise_estimate.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(Noise)]
+        L.hr_read_noise_image.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         _hip = L
     return _hip
 
@@ -427,6 +436,31 @@ class Renderer:
         out = (C.c_double * 3)()
         self._check(self.L.hr_accumulator_sum(self._h, 1 if total else 0, out))
         return [float(out[0]), float(out[1]), float(out[2])]
+
+    # ---- option "moments": per-pixel sample moments and the noise estimate (include/hanamaru_hip.h)
+    def read_moments(self):
+        """hr_read_moments: ((h, w, 6) float64 array {S1r, S1g, S1b, S2r, S2g, S2b}, samplings behind them)."""
+        out = np.empty(self._acc_hw() + (6,), dtype=np.float64)
+        n = C.c_uint64()
+        self._check(self.L.hr_read_moments(self._h, out.ctypes.data, C.byref(n)))
+        return out, int(n.value)
+
+    def write_moments(self, moments, samplings):
+        a = np.ascontiguousarray(moments, dtype=np.float64)
+        assert a.shape == self._acc_hw() + (6,)
+        self._check(self.L.hr_write_moments(self._h, a.ctypes.data, C.c_uint64(samplings)))
+
+    def noise_estimate(self, floor=0.01, threshold=0.05):
+        """hr_noise_estimate: {samplings, pixels, pixels_above, mean_error, max_error} of the per-pixel relative standard error e."""
+        n = Noise()
+        self._check(self.L.hr_noise_estimate(self._h, float(floor), float(threshold), C.byref(n)))
+        return {k: getattr(n, k) for k, _ in n._fields_}
+
+    def noise_image(self, floor=0.01):
+        """hr_read_noise_image: e of every pixel, (h, w) float64."""
+        out = np.empty(self._acc_hw(), dtype=np.float64)
+        self._check(self.L.hr_read_noise_image(self._h, float(floor), out.ctypes.data))
+        return out
 
     def debug_draws(self, sampling, first_path, num_paths, window):
         out = np.empty((num_paths, window), dtype=np.uint64)

@@ -258,6 +258,41 @@ int hr_comm_library(char *path_out, size_t cap, int *reused_out);
  * The checksum of the exchange: the ranks' own sums add up to the total's sum (to fp32 rounding of the all-reduce: ~1e-7 relative). */
 int hr_accumulator_sum(hr_ctx *ctx, int which, double out_rgb[3]);
 
+/* ---- per-pixel sample moments and the noise estimate (option "moments", off by default) ------------------------------
+ * "How converged is this image?"  With option "moments" = 1 the context keeps, per pixel and channel, the first and second moments of the
+ * per-sampling pixel values x_s (the 2x2 sub-sample sum of calc_pixel, renderer.rs:33-38,48-60: what a sampling adds to the accumulator),
+ *     S1 = sum x_s,  S2 = sum x_s^2   (f64; x_s is the fp32 value hr_clear + hr_render(s, s+1, 1) + hr_read_accumulator returns for the pixel)
+ * added one sampling at a time in the order the samplings are rendered — so, unlike the fp32 accumulator, they do not depend on how
+ * hr_render cuts samplings into launches ("batch", "max_tail_gib", calls in pieces).  Layout: h x w x 6 doubles {S1r, S1g, S1b, S2r, S2g, S2b},
+ * row-major, top row first (100 MB at 1920x1080), plus the count n of samplings behind them.  The accumulator is bit-identical with the
+ * option on or off; with it off nothing changes (same kernels).  Cost with it on: not yet measured on the device — from the code about
+ * 200 MB of extra traffic per 24-ms launch at 1080p (expected well under 1 %).
+ *   - hr_set_option "moments" 1 needs hr_set_resolution first (HR_ERR_NO_TARGET), allocates and zeroes the buffer and the count (set again
+ *     while on: nothing happens); 0 frees it.  The moments cover the samplings rendered since the latest of: switching on, hr_clear,
+ *     hr_set_resolution, hr_set_region (all zero them; the last two reallocate to the new size), hr_write_moments.  hr_write_accumulator
+ *     does not touch them (a host that resumes writes both).  hr_render_debug returns HR_ERR_UNSUPPORTED while the option is on.
+ *   - With the option off the four functions below return HR_ERR_INVALID.  With a region they work on its w x h pixels.
+ *   - The estimate, per pixel (n >= 2, else HR_ERR_INVALID; all f64):
+ *         m_c = S1_c / n      var_c = max(0, (S2_c - S1_c m_c) / (n - 1))      se_c = sqrt(var_c / n) / 4      mu_c = m_c / 4
+ *         e   = (se_r + se_g + se_b) / (mu_r + mu_g + mu_b + 3 floor)
+ *     se is the standard error of the pixel's radiance under independent samplings (the per-path seeding guarantees that).  `floor`
+ *     (radiance units, > 0) keeps black pixels from dividing by zero: below it error is judged absolutely instead of relatively.  It says
+ *     nothing about bias, nor about fireflies that have not happened yet.
+ *     hr_noise_estimate: mean and maximum of e over the pixels and how many have e > threshold (threshold >= 0), reduced on the device in a
+ *     fixed order (two calls return identical bits).  hr_read_noise_image: e of every pixel, w*h doubles.
+ *   - Multi-GPU: each context counts and accumulates its own shard (hr_render's stride).  Moments are additive: a host adds the ranks'
+ *     hr_read_moments results and counts in rank order and may hr_write_moments the total into one context to ask for the estimate.
+ *     (There is no library-side collective for them.)
+ *   - All of them synchronise (they read results back), like hr_accumulator_sum. */
+typedef struct hr_noise {
+    uint64_t samplings, pixels, pixels_above;
+    double mean_error, max_error;
+} hr_noise;
+int hr_read_moments(hr_ctx *ctx, double *host /* w*h*6 */, uint64_t *samplings /* may be NULL */);
+int hr_write_moments(hr_ctx *ctx, const double *host, uint64_t samplings);   /* resume, tile stitching */
+int hr_noise_estimate(hr_ctx *ctx, double floor, double threshold, hr_noise *out);
+int hr_read_noise_image(hr_ctx *ctx, double floor, double *host /* w*h */);
+
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):
  *   "counters"      0 / 1: instrumented build of the trace kernel (fills the counter fields of hr_stats)
@@ -282,6 +317,8 @@ int hr_get_stats(hr_ctx *ctx, hr_stats *out);
  *                   -1 (default) = automatic: ON for scenes without triangle meshes (BASELINE config 2: small spheres are what multiplies an
  *                   fp32 ray's error, and there it costs little), OFF for the others; 0 = off; 1 = on.  hr_stats.shading_in_force says
  *                   what runs.  (1 excludes "russian_roulette"; -1 stands back when the roulette is on.)
+ *   "moments"       0 (default) / 1: keep per-pixel first and second moments of the per-sampling values for hr_noise_estimate (see there);
+ *                   the image does not change by a bit
  *   next hr_upload_scene:
  *   "bvh_builder"   -1 = by scene size (default): the host's binned-SAH build below 200,000 primitives (the best tree; one host thread,
  *                   < 1 s), the device PLOC build from there on (0.97 - 0.99 of that tree's quality; 4 x 10^6 triangles in 38 ms instead of

@@ -27,6 +27,9 @@ pub const HR_MESH: i32 = 2;
 /// process, 3 same-device sum — not RCCL)
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrCommInfo { pub path: i32, pub nranks: i32, pub rank: i32, pub device: i32,
                                                                     pub rccl_version: i32, pub _pad: i32, pub allreduces: u64 }
+/// hr_noise: summary of the per-pixel relative standard error e (option "moments")
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrNoise { pub samplings: u64, pub pixels: u64, pub pixels_above: u64,
+                                                                 pub mean_error: f64, pub max_error: f64 }
 pub enum HrCtx {}
 
 extern "C" {
@@ -68,6 +71,12 @@ extern "C" {
     pub fn hr_comm_library(path_out: *mut c_char, cap: usize, reused_out: *mut c_int) -> c_int;
     /// which: 0 = this context's own accumulator, 1 = the all-reduced total; per-channel f64 sums (the checksum of the exchange)
     pub fn hr_accumulator_sum(ctx: *mut HrCtx, which: c_int, out_rgb: *mut f64) -> c_int;
+    // option "moments" (hr_set_option): per pixel {S1r, S1g, S1b, S2r, S2g, S2b} of the per-sampling values (w*h*6 doubles) and the noise
+    // estimate made of them; HR_ERR_INVALID while the option is off
+    pub fn hr_read_moments(ctx: *mut HrCtx, host: *mut f64, samplings: *mut u64) -> c_int;
+    pub fn hr_write_moments(ctx: *mut HrCtx, host: *const f64, samplings: u64) -> c_int;
+    pub fn hr_noise_estimate(ctx: *mut HrCtx, floor: f64, threshold: f64, out: *mut HrNoise) -> c_int;
+    pub fn hr_read_noise_image(ctx: *mut HrCtx, floor: f64, host: *mut f64 /* w*h */) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----
@@ -81,6 +90,7 @@ const _: () = assert!(std::mem::size_of::<HrCamera>() == 168 && std::mem::align_
 const _: () = assert!(std::mem::size_of::<HrSkybox>() == 48 && std::mem::align_of::<HrSkybox>() == 8);   // hr_skybox
 const _: () = assert!(std::mem::size_of::<HrSceneDesc>() == 248 && std::mem::align_of::<HrSceneDesc>() == 8);   // hr_scene_desc
 const _: () = assert!(std::mem::size_of::<HrCommInfo>() == 32 && std::mem::align_of::<HrCommInfo>() == 8);   // hr_comm_info_t
+const _: () = assert!(std::mem::size_of::<HrNoise>() == 40 && std::mem::align_of::<HrNoise>() == 8);   // hr_noise
 const _: () = assert!(std::mem::size_of::<Vector3>() == 24);   // hr_vec3
 #[cfg(test)]
 mod layout {
@@ -132,6 +142,11 @@ mod layout {
         assert_eq!(off!(HrCommInfo, device), 12);
         assert_eq!(off!(HrCommInfo, rccl_version), 16);
         assert_eq!(off!(HrCommInfo, allreduces), 24);
+        assert_eq!(off!(HrNoise, samplings), 0);
+        assert_eq!(off!(HrNoise, pixels), 8);
+        assert_eq!(off!(HrNoise, pixels_above), 16);
+        assert_eq!(off!(HrNoise, mean_error), 24);
+        assert_eq!(off!(HrNoise, max_error), 32);
     }
 }
 // ---- END GENERATED ----

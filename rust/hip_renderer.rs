@@ -40,6 +40,10 @@ pub struct HipRenderer {
     /// are the frame's, bit for bit — and the images written are w x h; they are also copied into the frame's imgbuf at (x0, y0).
     /// None (default) = the whole frame.
     pub region: Option<(u32, u32, u32, u32)>,
+    /// Noise target (option "moments" + hr_noise_estimate): Some((target, floor)) keeps the per-pixel sample moments and ends the render
+    /// as soon as the mean relative standard error of the pixels is <= target.  Asked where the pipeline is drained anyway (when a
+    /// progress image is due), so it costs no drain of its own.  None (default) = moments off, nothing changes.
+    pub noise_target: Option<(f64, f64)>,
 }
 unsafe impl Sync for HipRenderer {} // the context is only touched from render(), on the calling thread
 
@@ -111,7 +115,27 @@ impl HipRenderer {
         check(unsafe { hr_create(0, &mut ctx) });
         let now = time::now();
         HipRenderer { ctx, sampling, time_limit_sec, report_interval_sec, begin: now, last_report_progress: now,
-                      last_report_image: now, report_image_counter: 0, region: None }
+                      last_report_image: now, report_image_counter: 0, region: None, noise_target: None }
+    }
+    /// hr_noise_estimate of what has been rendered (needs `noise_target` set before `render`, which switches option "moments" on).
+    pub fn noise_estimate(&self, floor: f64, threshold: f64) -> HrNoise {
+        let mut n = HrNoise::default();
+        check(unsafe { hr_noise_estimate(self.ctx, floor, threshold, &mut n) });
+        n
+    }
+    /// hr_read_moments: (w*h*6 doubles {S1r, S1g, S1b, S2r, S2g, S2b}, samplings behind them) of a w x h target
+    pub fn read_moments(&self, w: u32, h: u32) -> (Vec<f64>, u64) {
+        let mut m = vec![0.0f64; w as usize * h as usize * 6];
+        let mut n = 0u64;
+        check(unsafe { hr_read_moments(self.ctx, m.as_mut_ptr(), &mut n) });
+        (m, n)
+    }
+    pub fn write_moments(&mut self, m: &[f64], samplings: u64) { check(unsafe { hr_write_moments(self.ctx, m.as_ptr(), samplings) }); }
+    /// hr_read_noise_image: e of every pixel of a w x h target
+    pub fn noise_image(&self, w: u32, h: u32, floor: f64) -> Vec<f64> {
+        let mut e = vec![0.0f64; w as usize * h as usize];
+        check(unsafe { hr_read_noise_image(self.ctx, floor, e.as_mut_ptr()) });
+        e
     }
 
     fn upload(&mut self, scene: &BvhScene, camera: &Camera) {
@@ -166,6 +190,7 @@ impl Renderer for HipRenderer {
         self.upload(scene.as_bvh_scene(), camera);
         check(unsafe { hr_set_resolution(self.ctx, imgbuf.width(), imgbuf.height()) });
         if let Some((x0, y0, w, h)) = self.region { check(unsafe { hr_set_region(self.ctx, x0, y0, w, h) }); }
+        if self.noise_target.is_some() { check(unsafe { hr_set_option(self.ctx, b"moments\0".as_ptr() as *const _, 1.0) }); }
         let (out_w, out_h) = self.region.map_or((imgbuf.width(), imgbuf.height()), |r| (r.2, r.3));
         // renderer.rs:32-43 with report_progress (renderer.rs:205-251) — the loop of hanamaru-hip's cli_main.cpp (compiled and tested there),
         // statement for statement.  Every sampling gets its own "rendering:" line; the GPU is fed LAUNCHES of `lrep` samplings (what fills the
@@ -233,6 +258,13 @@ impl Renderer for HipRenderer {
                 // nothing is in flight now: the reference's own rules apply as they stand, in their order (renderer.rs:222-241)
                 if used + 1.1 * last > self.time_limit_sec { self.write_image(Some("reached time limit"), done, used, imgbuf); return done; }
                 if done >= self.sampling { self.write_image(Some("reached max sampling"), done, used, imgbuf); return done; }
+                if let Some((target, floor)) = self.noise_target {
+                    if done >= 2 {
+                        let n = self.noise_estimate(floor, target);
+                        println!("noise: samplings={} mean={:.6} max={:.6} above={}", n.samplings, n.mean_error, n.max_error, n.pixels_above);
+                        if n.mean_error <= target { self.write_image(Some("reached noise target"), done, used, imgbuf); return done; }
+                    }
+                }
                 self.write_image(None, done, used, imgbuf);
                 self.last_report_image = self.last_report_progress;     // `now` of the report that triggered it (renderer.rs:250)
             }
