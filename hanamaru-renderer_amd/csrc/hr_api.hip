@@ -11,12 +11,16 @@
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
 //   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
+// Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
+// here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -56,6 +60,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "wf_kernels.h"
 #include "post_kernels.h"
 #include "noise_core.h"
+#include "kernel_variants.h"
 
 // ------------------------------------------------------------------------------------------ context
 
@@ -155,8 +160,6 @@ struct hr_ctx {
 
 // caller-owned accumulators (hr_bind_accumulator): one context per buffer.  accumulate_kernel adds a launch's radiance with plain loads and
 // stores (no atomics since round 3), so two contexts accumulating into one buffer would race silently: a second binding is refused.
-#include <map>
-#include <mutex>
 static std::mutex g_bound_mu;
 static std::map<const void *, std::pair<const hr_ctx *, size_t>> g_bound;   // buffer -> (context, bytes)
 static void unbind_accumulator(hr_ctx *c) {
@@ -342,6 +345,31 @@ static int sync_all(hr_ctx *c) {
     c->markers.clear();
     return drain_events(c);
 }
+// A timed launch: timed_begin / timed_end bracket what a caller enqueues on `st` with an event pair that the drains above sum into the
+// context's times.  A pair goes into its list (and its launch is counted) only when both events were really recorded; anything less is
+// destroyed on the spot, so no drain ever queries an event that was not recorded.  timed_end is handed what the launch itself returned
+// and passes the first error on.
+static void drop_pair(EventPair &ev) {
+    if (ev.a) (void)hipEventDestroy(ev.a);
+    if (ev.b) (void)hipEventDestroy(ev.b);
+    ev = EventPair{nullptr, nullptr};
+}
+static hipError_t timed_begin(EventPair &ev, hipStream_t st) {
+    ev = EventPair{nullptr, nullptr};
+    hipError_t e = hipEventCreate(&ev.a);
+    if (e == hipSuccess) e = hipEventCreate(&ev.b);
+    if (e == hipSuccess) e = hipEventRecord(ev.a, st);
+    if (e != hipSuccess) drop_pair(ev);
+    return e;
+}
+static hipError_t timed_end(hipError_t launched, EventPair &ev, hipStream_t st, std::vector<EventPair> &list, uint64_t *launches = nullptr) {
+    hipError_t e = launched;
+    if (e == hipSuccess && ev.a) e = hipEventRecord(ev.b, st);
+    if (e != hipSuccess || !ev.a) { drop_pair(ev); return e; }
+    list.push_back(ev);
+    if (launches) ++*launches;
+    return hipSuccess;
+}
 
 // ------------------------------------------------------------------------------------------ C ABI
 
@@ -383,37 +411,19 @@ static int create_resources(hr_ctx *c) {
     HIP_TRY(hipMalloc((void **)&c->d_tile_counter, 2 * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&c->gov, sizeof(GovDev)));
     { int grc = govern_reset(c); if (grc) return grc; }
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_isaac64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<20>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<28>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_pc_kernel<20, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_seg_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_seg_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-#if defined(HR_EXPERIMENTS)
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_w5_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_w5_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_ps_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_ps_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_ps_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)seed_ps_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
-#endif
+    for (const SeedVariant &v : SEED_VARIANTS) HIP_TRY(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
     HIP_TRY(hipFuncSetAttribute((const void *)seed_debug_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 8));
-    // The seed kernel owns all 160 KiB of a CU's LDS and runs next to the trace kernel of the previous batch: a trace kernel that
+    // The seed kernel owns all 160 KiB of a CU's LDS and runs next to the trace side of the previous batch: a trace-side kernel that
     // uses ANY LDS (the compiler promotes small private arrays to LDS unless told not to, see the Makefile) could not share a CU
-    // with it — the two would silently run one after the other, 40 % slower.  Refuse to start in that state.
+    // with it — the two would silently run one after the other, 40 % slower.  Refuse to start in that state.  Every instantiation a
+    // launch can select is a row of these tables (kernel_variants.h).
     {
-        const void *trace_variants[] = {(const void *)trace_kernel<false, 5, true>, (const void *)trace_kernel<false, 5, false>, (const void *)trace_kernel<false, 4, true>,
-                                        (const void *)trace_kernel<false, 6, true>, (const void *)trace_kernel<true, 3, true>, (const void *)trace_kernel<true, 3, false>,
-                                        (const void *)trace_kernel<false, 5, true, true>, (const void *)trace_kernel<false, 5, false, true>,
-                                        (const void *)trace_kernel<true, 3, true, true>, (const void *)trace_kernel<true, 3, false, true>,
-                                        (const void *)trace_kernel<false, 3, true, false, true>, (const void *)trace_kernel<false, 3, false, false, true>,
-                                        (const void *)trace_kernel<false, 4, true, false, false, true>, (const void *)trace_kernel<false, 4, false, false, false, true>};
-        for (const void *f : trace_variants) {
+        std::vector<const void *> beside_seed;
+        for (const TraceVariant &v : TRACE_VARIANTS) beside_seed.push_back((const void *)v.fn);
+        for (const WfStartVariant &v : WF_START_VARIANTS) beside_seed.push_back((const void *)v.fn);
+        for (const WfTraverseVariant &v : WF_TRAVERSE_VARIANTS) beside_seed.push_back((const void *)v.fn);
+        for (const WfShadeVariant &v : WF_SHADE_VARIANTS) beside_seed.push_back((const void *)v.fn);
+        for (const void *f : beside_seed) {
             hipFuncAttributes fa;
             HIP_TRY(hipFuncGetAttributes(&fa, f));
             if (fa.sharedSizeBytes != 0) return fail(HR_ERR_DEVICE, "build error: a trace kernel variant uses %zu bytes of LDS (it must use none to run beside the seed kernel)", (size_t)fa.sharedSizeBytes);
@@ -770,12 +780,6 @@ static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y
     return govern_reset(c);
 }
 static bool has_region(const hr_ctx *c) { return c->RW != c->W || c->RH != c->H; }
-// the launch geometry of hr_render / hr_render_debug: the frame, the region and the region's tiles
-static void target_params(const hr_ctx *c, RenderParams &rp) {
-    rp.width = c->W; rp.height = c->H;
-    rp.org_x = c->RX; rp.org_y = c->RY; rp.reg_w = c->RW; rp.reg_h = c->RH;
-    rp.tiles_x = (c->RW + 3) / 4; rp.tiles_y = (c->RH + 3) / 4;
-}
 
 int hr_set_resolution(hr_ctx *c, uint32_t w, uint32_t h) {
     if (!c || !w || !h) return fail(HR_ERR_INVALID, "hr_set_resolution: bad argument");
@@ -945,34 +949,24 @@ static int launch_split(hr_ctx *c, const RenderParams &rp, int slot, std::vector
     const WfQueues wq = queues ? *queues : c->wf;
     hipStream_t st = c->stream;
     auto mark = [&]() -> hipError_t { if (!marks) return hipSuccess; hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; marks->push_back(e); return hipEventRecord(e, st); };
+    const bool log = plog != nullptr;
+    const WfStartFn start = select_wf_start_kernel(c->precise);
+    const WfTraverseFn traverse = select_wf_traverse_kernel(c->counters, c->dsc.qnodes != nullptr, log);
+    const WfShadeFn shade = select_wf_shade_kernel(c->counters, c->precise, log);
+    if (!start || !traverse || !shade) return fail(HR_ERR_UNSUPPORTED, "split pipeline: no kernel instantiation for these options (kernel_variants.h)");
     HIP_TRY(hipMemsetAsync(wq.counts, 0, (WF_STEPS + 2) * WF_SUBQ * sizeof(WfCounts), st));
-    const uint32_t items = rp.tiles_x * rp.tiles_y * rp.num_k;
-    const bool qn = c->dsc.qnodes != nullptr;
     HIP_TRY(mark());
     // grids: whole multiples of WF_SUBQ waves (16 workgroups of 4), so that every sub-queue has the same number of waves
     auto grid_of = [&](uint32_t wgs_per_cu) { return dim3(std::max<uint32_t>(16u, (uint32_t)c->num_cus * wgs_per_cu / 16u * 16u)); };
-    (void)items;
-    if (c->precise) hipLaunchKernelGGL(wf_start_kernel<true>, grid_of(8u), dim3(256), 0, st, c->dsc, rp, c->recs[slot], wq);
-    else hipLaunchKernelGGL(wf_start_kernel<false>, grid_of(8u), dim3(256), 0, st, c->dsc, rp, c->recs[slot], wq);
+    hipLaunchKernelGGL(start, grid_of(8u), dim3(256), 0, st, c->dsc, rp, c->recs[slot], wq);
     HIP_TRY(mark());
     RenderParams rt = rp;
     rt.adv_den = c->wf_adv_den;
     const dim3 gt = grid_of(c->wf_trav_wgs), gs = grid_of(c->wf_shade_wgs), b(256);
     for (uint32_t step = 1; step <= WF_STEPS; step++) {
-        if (c->counters && !plog) {
-            if (qn) hipLaunchKernelGGL((wf_traverse_kernel<true, true>), gt, b, 0, st, c->dsc, rt, wq, step, c->d_counters);
-            else hipLaunchKernelGGL((wf_traverse_kernel<true, false>), gt, b, 0, st, c->dsc, rt, wq, step, c->d_counters);
-        } else {
-            if (qn) hipLaunchKernelGGL((wf_traverse_kernel<false, true>), gt, b, 0, st, c->dsc, rt, wq, step, c->d_counters);
-            else hipLaunchKernelGGL((wf_traverse_kernel<false, false>), gt, b, 0, st, c->dsc, rt, wq, step, c->d_counters);
-        }
+        hipLaunchKernelGGL(traverse, gt, b, 0, st, c->dsc, rt, wq, step, c->d_counters);
         HIP_TRY(mark());
-#define HR_LAUNCH_SHADE(C, P, L) hipLaunchKernelGGL((wf_shade_kernel<C, P, L>), gs, b, 0, st, c->dsc, rp, c->recs[slot], wq, step, c->d_counters, plog)
-        if (plog) { if (c->precise) HR_LAUNCH_SHADE(false, true, true); else HR_LAUNCH_SHADE(false, false, true); }
-        else if (c->counters) { if (c->precise) HR_LAUNCH_SHADE(true, true, false); else HR_LAUNCH_SHADE(true, false, false); }
-        else if (c->precise) HR_LAUNCH_SHADE(false, true, false);
-        else HR_LAUNCH_SHADE(false, false, false);
-#undef HR_LAUNCH_SHADE
+        hipLaunchKernelGGL(shade, gs, b, 0, st, c->dsc, rp, c->recs[slot], wq, step, c->d_counters, plog);
         HIP_TRY(mark());
     }
     HIP_TRY(hipGetLastError());
@@ -982,51 +976,92 @@ static int launch_split(hr_ctx *c, const RenderParams &rp, int slot, std::vector
 static int launch_seed(hr_ctx *c, const RenderParams &rp, int slot, hipStream_t st) {
     uint64_t paths = (uint64_t)rp.tiles_x * rp.tiles_y * rp.num_k * 64u;
     uint32_t grid = (uint32_t)std::min<uint64_t>((paths + SEED_COLS - 1) / SEED_COLS, (uint64_t)c->num_cus);
-    EventPair ev{nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventRecord(ev.a, st));
-    if (c->debug_skip & 2) {
-    } else if (c->seed_mode == 2) {
-        if (!c->ring) HIP_TRY(hipMalloc((void **)&c->ring, (size_t)c->num_cus * SEED_RING_WORDS_MAX * sizeof(u64)));
-#define HR_LAUNCH_SEG(P, L) hipLaunchKernelGGL((seed_seg_kernel<P, L>), dim3(grid), dim3(256), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->ring, c->recs[slot], c->ovf, c->ovf_win, c->d_counters)
-        if (rp.rec_lo_off) { if (c->seed_prof) HR_LAUNCH_SEG(true, true); else HR_LAUNCH_SEG(false, true); }   // + the draws' residuals (precise shading)
-        else if (c->seed_prof) HR_LAUNCH_SEG(true, false);
-        else HR_LAUNCH_SEG(false, false);
-#undef HR_LAUNCH_SEG
-#if defined(HR_EXPERIMENTS)
-    } else if (c->seed_mode == 4) {
-        if (!c->ring) HIP_TRY(hipMalloc((void **)&c->ring, (size_t)c->num_cus * SEED_RING_WORDS_MAX * sizeof(u64)));
-        if (c->seed_prof) hipLaunchKernelGGL((seed_w5_kernel<true>), dim3(grid), dim3(320), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->ring, c->recs[slot], c->ovf, c->ovf_win, c->d_counters);
-        else hipLaunchKernelGGL((seed_w5_kernel<false>), dim3(grid), dim3(320), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->ring, c->recs[slot], c->ovf, c->ovf_win, c->d_counters);
-    } else if (c->seed_mode == 3) {
-        if (!c->ring) HIP_TRY(hipMalloc((void **)&c->ring, (size_t)c->num_cus * SEED_RING_WORDS_MAX * sizeof(u64)));
-#define HR_LAUNCH_PS(P) hipLaunchKernelGGL(seed_ps_kernel<P>, dim3(grid), dim3(256), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->ring, c->recs[slot], c->ovf, c->ovf_win, c->d_counters)
-        switch (c->seed_prof) { case 1: HR_LAUNCH_PS(1); break; case 2: HR_LAUNCH_PS(2); break; case 3: HR_LAUNCH_PS(3); break; default: HR_LAUNCH_PS(0); break; }
-#undef HR_LAUNCH_PS
-#endif
-    } else if (c->seed_mode == 1) {
-        if (!c->ring) HIP_TRY(hipMalloc((void **)&c->ring, (size_t)c->num_cus * SEED_RING_WORDS_MAX * sizeof(u64)));
-#define HR_LAUNCH_PC(HEAD) hipLaunchKernelGGL(seed_pc_kernel<HEAD>, dim3(grid), dim3(256), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->ring, c->recs[slot], c->ovf, c->ovf_win, c->d_counters)
-        if (c->seed_prof && c->seed_split == 20) hipLaunchKernelGGL((seed_pc_kernel<20, true>), dim3(grid), dim3(256), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->ring, c->recs[slot], c->ovf, c->ovf_win, c->d_counters);
-        else if (c->seed_prof) hipLaunchKernelGGL((seed_pc_kernel<16, true>), dim3(grid), dim3(256), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->ring, c->recs[slot], c->ovf, c->ovf_win, c->d_counters);
-        else switch (c->seed_split) {
-            case 8: HR_LAUNCH_PC(8); break;
-            case 12: HR_LAUNCH_PC(12); break;
-            case 20: HR_LAUNCH_PC(20); break;
-            case 24: HR_LAUNCH_PC(24); break;
-            case 28: HR_LAUNCH_PC(28); break;
-            default: HR_LAUNCH_PC(16); break;
-        }
-#undef HR_LAUNCH_PC
-    } else
-        hipLaunchKernelGGL(seed_isaac64_kernel, dim3(grid), dim3(64 * SEED_WAVES), SEED_LDS_BYTES, st, rp, c->dsc.cam.lens_shape, c->recs[slot], c->ovf, c->ovf_win,
-                           c->d_counters);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.b, st));
-    c->seed_events.push_back(ev);
-    c->seed_launches++;
+    const SeedVariant *v = select_seed_kernel(c->seed_mode, c->seed_split, c->seed_prof, rp.rec_lo_off != 0);
+    if (!v) return fail(HR_ERR_UNSUPPORTED, "no seed kernel instantiation for seed_mode %d, seed_split %d, seed_prof %d (kernel_variants.h)", c->seed_mode, c->seed_split, c->seed_prof);
+    const bool skip = (c->debug_skip & 2) != 0;
+    if (!skip && v->ring && !c->ring) HIP_TRY(hipMalloc((void **)&c->ring, (size_t)c->num_cus * SEED_RING_WORDS_MAX * sizeof(u64)));
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, st));
+    hipError_t e = hipSuccess;
+    if (!skip) {
+        RenderParams krp = rp;
+        int lens_shape = c->dsc.cam.lens_shape;
+        void *args[7] = {&krp, &lens_shape, &c->ring, &c->recs[slot], &c->ovf, &c->ovf_win, &c->d_counters};
+        if (!v->ring) std::copy(args + 3, args + 7, args + 2);   // the fused kernel has no ring argument
+        e = hipLaunchKernel(v->fn, dim3(grid), dim3(v->threads), args, SEED_LDS_BYTES, st);
+    }
+    HIP_TRY(timed_end(e, ev, st, c->seed_events, &c->seed_launches));
     return HR_OK;
+}
+
+// ---- the launch plan ----
+// the launch geometry: the frame, the region and the region's tiles
+static void target_params(const hr_ctx *c, RenderParams &rp) {
+    rp.width = c->W; rp.height = c->H;
+    rp.org_x = c->RX; rp.org_y = c->RY; rp.reg_w = c->RW; rp.reg_h = c->RH;
+    rp.tiles_x = (c->RW + 3) / 4; rp.tiles_y = (c->RH + 3) / 4;
+}
+// the trace side's knobs (debug options adv_den, leaf_den, node_unroll, kchunk, nee_cull)
+static void knob_params(const hr_ctx *c, RenderParams &rp) {
+    rp.adv_den = c->adv_den; rp.leaf_den = c->leaf_den;
+    rp.node_unroll = c->node_unroll; rp.kchunk = c->kchunk;
+    rp.nee_cull_off = ~c->nee_cull & 7u;
+}
+// Samplings per launch of hr_render: option batch, or automatically launches of the size the kernels are tuned on (4 samplings of
+// 1920x1080), at most 64 samplings — under the caps of the launch's buffers.
+static uint32_t render_batch(const hr_ctx *c, uint32_t tiles, bool split) {
+    uint64_t batch = c->batch;
+    if (!batch) {
+        const uint64_t per_sampling_paths = (uint64_t)tiles * 64u;
+        batch = std::min<uint64_t>(64, std::max<uint64_t>(4, (33177600ull + per_sampling_paths - 1) / per_sampling_paths));
+    }
+    // the hand-off costs 8 KiB per (tile, sampling): keep each of the two buffers under max_tail_bytes
+    const uint64_t per_sampling = (uint64_t)tiles * REC_ITEM_FLOATS * sizeof(float) * (draws_twin(c) ? 2 : 1);
+    batch = std::min(batch, std::max<uint64_t>(1, c->max_tail_bytes / std::max<uint64_t>(1, per_sampling)));
+    if (split) {
+        // the split pipeline's queues are sized for the worst case (a main ray + a shadow ray per emitter for every path, both parities): keep
+        // them under the same cap as a hand-off buffer — a 3840x2160 launch then holds one sampling (33 M paths) instead of four
+        const uint64_t per_path = (1ull + c->dsc.num_emitters) * (4 * sizeof(f4) + sizeof(WfHitRec)) + (c->precise ? 10 : 6) * sizeof(f4);
+        batch = std::min(batch, std::max<uint64_t>(1, c->max_tail_bytes / std::max<uint64_t>(1, (uint64_t)tiles * 64u * per_path)));
+    }
+    return (uint32_t)batch;
+}
+// What traces a planned launch: nothing (the seed kernel alone), whatever is in force, or the split pipeline whatever is in force.
+enum TraceSide { TRACE_NONE, TRACE_IN_FORCE, TRACE_SPLIT };
+// The launch plan: the RenderParams for samplings begin, begin + stride, .. of the current target, `batch` of them per launch (0: hr_render's
+// own batch), and the hand-off buffers made ready for a launch of that size — the records with their residual twin, the fix-up lists and,
+// when the split pipeline traces, its queues.  What belongs to ONE launch stays with the caller: sampling_begin and num_k of the launches
+// after the first, and the governor's fields (left at none: the queries launch with the chip to themselves).
+struct LaunchPlan {
+    RenderParams rp;
+    uint32_t tiles;   // 4x4-pixel tiles of the target
+    uint32_t batch;   // samplings per launch
+    bool split;       // the split pipeline traces (the roulette estimator lives in the megakernel only)
+};
+static int plan_launch(hr_ctx *c, uint32_t begin, uint32_t stride, uint32_t batch, TraceSide side, LaunchPlan &p) {
+    p = LaunchPlan{};
+    RenderParams &rp = p.rp;
+    target_params(c, rp);
+    knob_params(c, rp);
+    rp.sampling_begin = begin; rp.stride = stride; rp.num_k = batch;
+    rp.pad[0] = c->seed_prio;
+    p.tiles = rp.tiles_x * rp.tiles_y;
+    p.split = side == TRACE_SPLIT || (side == TRACE_IN_FORCE && c->trace_mode == 1 && !c->rr_start);
+    p.batch = batch ? batch : render_batch(c, p.tiles, p.split);
+    int rc = ensure_draws(c, (size_t)p.tiles * p.batch);
+    if (rc) return rc;
+    rp.rec_lo_off = rec_lo_off(c);
+    if ((rc = ensure_ovf(c, (uint64_t)p.tiles * 64u * p.batch))) return rc;
+    if (p.split && (rc = ensure_wf(c, (uint64_t)p.tiles * 64u * p.batch))) return rc;
+    rp.ovf_cap = c->ovf_cap;
+    return HR_OK;
+}
+// the grid of a trace_kernel launch: persistent waves, enough workgroups to fill every CU (6 per CU covers every occupancy variant), never
+// more waves than work units
+static uint32_t trace_grid_size(const hr_ctx *c, uint32_t tiles, uint32_t nk, uint32_t fixed_grid) {
+    const uint32_t kch = c->kchunk ? c->kchunk : TRACE_KCHUNK;
+    const uint64_t units = (uint64_t)tiles * ((nk + kch - 1) / kch);   // work units of the trace kernel
+    return (uint32_t)std::min<uint64_t>(fixed_grid ? fixed_grid : (uint64_t)c->num_cus * c->trace_wgs, (units + TRACE_WAVES - 1) / TRACE_WAVES);
 }
 
 int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
@@ -1036,45 +1071,20 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     if (s_end <= s_begin) return HR_OK;
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
-    uint32_t total_k = (s_end - s_begin + stride - 1) / stride;
-    RenderParams rp{};
-    target_params(c, rp);
-    rp.stride = stride;
-    rp.adv_den = c->adv_den;
-    rp.leaf_den = c->leaf_den;
-    rp.node_unroll = c->node_unroll; rp.kchunk = c->kchunk;
-    rp.pad[0] = c->seed_prio;
-    rp.pad[2] = (uint32_t)c->debug_skip;
-    uint32_t tiles = rp.tiles_x * rp.tiles_y;
-    // the hand-off costs 8 KiB per (tile, sampling): keep each of the two buffers under max_tail_bytes
-    uint32_t batch = c->batch;
-    if (!batch) {   // automatic: launches of the size the kernels are tuned on (4 samplings of 1920x1080), at most 64 samplings
-        const uint64_t per_sampling_paths = (uint64_t)tiles * 64u;
-        batch = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(4, (33177600ull + per_sampling_paths - 1) / per_sampling_paths));
-    }
-    {
-        uint64_t per_sampling = (uint64_t)tiles * REC_ITEM_FLOATS * sizeof(float) * (draws_twin(c) ? 2 : 1);
-        uint64_t fit = std::max<uint64_t>(1, c->max_tail_bytes / std::max<uint64_t>(1, per_sampling));
-        batch = (uint32_t)std::min<uint64_t>(batch, fit);
-    }
     if (c->precise_opt == 1 && c->rr_start) return fail(HR_ERR_UNSUPPORTED, "hr_render: russian_roulette and precise_shading exclude each other (the roulette estimator has no f64 instantiation)");
-    const bool split = c->trace_mode == 1 && !c->rr_start;   // (the roulette estimator lives in the megakernel only)
-    if (split) {
-        // the split pipeline's queues are sized for the worst case (a main ray + a shadow ray per emitter for every path, both parities): keep
-        // them under the same cap as a hand-off buffer — a 3840x2160 launch then holds one sampling (33 M paths) instead of four
-        const uint64_t per_path = (1ull + c->dsc.num_emitters) * (4 * sizeof(f4) + sizeof(WfHitRec)) + (c->precise ? 10 : 6) * sizeof(f4);
-        const uint64_t fit = std::max<uint64_t>(1, c->max_tail_bytes / std::max<uint64_t>(1, (uint64_t)tiles * 64u * per_path));
-        batch = (uint32_t)std::min<uint64_t>(batch, fit);
-    }
-    int rc = ensure_draws(c, (size_t)tiles * batch);
+    const uint32_t total_k = (s_end - s_begin + stride - 1) / stride;
+    LaunchPlan plan;
+    int rc = plan_launch(c, s_begin, stride, 0, TRACE_IN_FORCE, plan);
     if (rc) return rc;
-    rp.rec_lo_off = rec_lo_off(c);
-    if ((rc = ensure_ovf(c, (uint64_t)tiles * 64u * batch))) return rc;
-    if (split && (rc = ensure_wf(c, (uint64_t)tiles * 64u * batch))) return rc;
-    rp.ovf_cap = c->ovf_cap;
+    RenderParams &rp = plan.rp;
+    const uint32_t tiles = plan.tiles, batch = plan.batch;
+    // hr_render alone: the roulette estimator, the finer tail, the timing experiments, the debug wave budget
     rp.rr_start = c->rr_start;
-    rp.nee_cull_off = ~c->nee_cull & 7u;
     rp.tail_div = c->tail_div;
+    rp.pad[2] = (uint32_t)c->debug_skip;
+    rp.wg_budget = c->trace_budget;
+    const TraceFn trace = select_trace_kernel(c->counters, c->dsc.qnodes != nullptr, c->rr_start != 0, c->precise, c->min_waves, false);
+    if (!trace) return fail(HR_ERR_UNSUPPORTED, "hr_render: no trace kernel instantiation for these options (kernel_variants.h)");
     for (uint32_t done = 0; done < total_k; done += batch) {
         uint32_t nk = std::min(batch, total_k - done);
         rp.sampling_begin = s_begin + done * stride;
@@ -1092,49 +1102,16 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         HIP_TRY(hipEventRecord(c->seed_done[slot], sstream));
         c->seed_pending[slot] = true;
         HIP_TRY(hipStreamWaitEvent(c->stream, c->seed_done[slot], 0));
-        EventPair ev{nullptr, nullptr};
-        HIP_TRY(hipEventCreate(&ev.a));
-        HIP_TRY(hipEventCreate(&ev.b));
-        HIP_TRY(hipEventRecord(ev.a, c->stream));
-        // persistent waves: enough workgroups to fill every CU (6 per CU covers every occupancy variant), never more
-        // waves than tiles
-        const uint32_t kch = c->kchunk ? c->kchunk : TRACE_KCHUNK;
-        const uint64_t units = (uint64_t)tiles * ((nk + kch - 1) / kch);   // work units of the trace kernel
-        uint32_t grid = (uint32_t)std::min<uint64_t>(c->trace_grid ? c->trace_grid : (uint64_t)c->num_cus * c->trace_wgs, (units + TRACE_WAVES - 1) / TRACE_WAVES);
-        rp.wg_budget = c->trace_budget;
+        EventPair ev;
+        HIP_TRY(timed_begin(ev, c->stream));
         HIP_TRY(hipMemsetAsync(c->d_tile_counter + slot, 0, sizeof(uint32_t), c->stream));
-        {
-            dim3 g(grid), b(64 * TRACE_WAVES);
-#define HR_LAUNCH_TRACE(C, W, Q) hipLaunchKernelGGL((trace_kernel<C, W, Q>), g, b, 0, c->stream, c->dsc, rp, c->recs[slot], c->d_counters, c->d_tile_counter + slot)
-            const bool qn = c->dsc.qnodes != nullptr;
-#define HR_LAUNCH_TRACE_RR(C, W, Q) hipLaunchKernelGGL((trace_kernel<C, W, Q, true>), g, b, 0, c->stream, c->dsc, rp, c->recs[slot], c->d_counters, c->d_tile_counter + slot)
-            if (c->debug_skip & 16) {
-            } else if (split) {
-                if ((rc = launch_split(c, rp, slot))) return rc;
-            } else if (c->rr_start) {   // the non-parity estimator has its own instantiations (one occupancy variant)
-                if (c->counters) { if (qn) HR_LAUNCH_TRACE_RR(true, 3, true); else HR_LAUNCH_TRACE_RR(true, 3, false); }
-                else if (qn) HR_LAUNCH_TRACE_RR(false, 5, true);
-                else HR_LAUNCH_TRACE_RR(false, 5, false);
-            } else if (c->precise) {    // precise shading: path_advance<.., PREC>, 128 VGPRs
-#define HR_LAUNCH_TRACE_PREC(C, W, Q) hipLaunchKernelGGL((trace_kernel<C, W, Q, false, false, true>), g, b, 0, c->stream, c->dsc, rp, c->recs[slot], c->d_counters, c->d_tile_counter + slot)
-                if (c->counters) { if (qn) HR_LAUNCH_TRACE_PREC(true, 3, true); else HR_LAUNCH_TRACE_PREC(true, 3, false); }
-                else if (qn && c->min_waves == 6) HR_LAUNCH_TRACE_PREC(false, 5, true);      // debug option min_waves 6 -> the 96-VGPR form, 4 -> the 168-VGPR form (A/B only)
-                else if (qn && c->min_waves == 4) HR_LAUNCH_TRACE_PREC(false, 3, true);
-                else if (qn) HR_LAUNCH_TRACE_PREC(false, 4, true);
-                else HR_LAUNCH_TRACE_PREC(false, 4, false);
-#undef HR_LAUNCH_TRACE_PREC
-            } else if (c->counters) { if (qn) HR_LAUNCH_TRACE(true, 3, true); else HR_LAUNCH_TRACE(true, 3, false); }
-            else if (!qn) HR_LAUNCH_TRACE(false, 5, false);
-            else if (c->min_waves == 4) HR_LAUNCH_TRACE(false, 4, true);
-            else if (c->min_waves == 6) HR_LAUNCH_TRACE(false, 6, true);
-            else HR_LAUNCH_TRACE(false, 5, true);
-#undef HR_LAUNCH_TRACE
-#undef HR_LAUNCH_TRACE_RR
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev.b, c->stream));
-        c->trace_events.push_back(ev);
-        c->trace_launches++;
+        if (c->debug_skip & 16) {
+        } else if (plan.split) {
+            if ((rc = launch_split(c, rp, slot))) return rc;
+        } else
+            hipLaunchKernelGGL(trace, dim3(trace_grid_size(c, tiles, nk, c->trace_grid)), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, c->recs[slot], c->d_counters,
+                               c->d_tile_counter + slot, (uint32_t *)nullptr);
+        HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->trace_events, &c->trace_launches));
         // the launch's radiance into the accumulator (the trace kernel left every path's in its record), in the gap in which this
         // stream waits for the next seed kernel anyway
         if (!(c->debug_skip & 16)) {
@@ -1167,24 +1144,14 @@ int hr_render_debug(hr_ctx *c, int mode) {
     invalidate_totals(c);
     RenderParams rp{};
     target_params(c, rp);
-    rp.leaf_den = c->leaf_den; rp.node_unroll = c->node_unroll;
-    EventPair ev{nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventRecord(ev.a, c->stream));
-    {
-        const uint32_t tiles = rp.tiles_x * rp.tiles_y;
-        dim3 g((tiles + TRACE_WAVES - 1) / TRACE_WAVES), b(64 * TRACE_WAVES);
-        const bool qn = c->dsc.qnodes != nullptr;
-#define HR_LAUNCH_DEBUG(C, Q) hipLaunchKernelGGL((debug_render_kernel<C, Q>), g, b, 0, c->stream, c->dsc, rp, mode, c->accum, c->d_counters)
-        if (c->counters) { if (qn) HR_LAUNCH_DEBUG(true, true); else HR_LAUNCH_DEBUG(true, false); }
-        else { if (qn) HR_LAUNCH_DEBUG(false, true); else HR_LAUNCH_DEBUG(false, false); }
-#undef HR_LAUNCH_DEBUG
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.b, c->stream));
-    c->debug_events.push_back(ev);
-    c->debug_launches++;
+    knob_params(c, rp);   // (the debug kernels read leaf_den and node_unroll of them)
+    const DebugRenderFn fn = select_debug_render_kernel(c->counters, c->dsc.qnodes != nullptr);
+    if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: no kernel instantiation for these options (kernel_variants.h)");
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
+    hipLaunchKernelGGL(fn, dim3((tiles + TRACE_WAVES - 1) / TRACE_WAVES), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, mode, c->accum, c->d_counters);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->debug_events, &c->debug_launches));
     return HR_OK;
 }
 
@@ -1250,15 +1217,11 @@ int hr_resolve(hr_ctx *c, uint32_t samplings, uint8_t *host_rgb8) {
     // the region's accumulator is resolved as an image of its own: the bilateral filter's clamp and wrap act at the region's edges
     uint32_t n = c->RW * c->RH;
     float scale = 1.0f / (float)(samplings * 4u);
-    EventPair ev{nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventRecord(ev.a, c->stream));
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
     hipLaunchKernelGGL(tonemap_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->total_valid ? c->accum_total : c->accum, c->post_tmp, n, scale);
     hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->RW, c->RH);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.b, c->stream));
-    c->post_events.push_back(ev);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
     HIP_TRY(hipMemcpyAsync(host_rgb8, c->d_rgb8, (size_t)n * 3, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return drain_events(c);
@@ -1587,25 +1550,77 @@ int hr_get_stats(hr_ctx *c, hr_stats *out) {
     return HR_OK;
 }
 
+// ---- options ----
+// A plain knob is a row: the key, the member it is stored into, what is accepted, what is said otherwise, and whether the context is
+// synchronised first / the governor starts over afterwards.  Accepted: any value with lo > hi; else lo <= value <= hi — every value in
+// between with step 0 (the fraction is dropped when it is stored), only lo, lo + step, .. with a step.  Keys with logic of their own are
+// explicit code in hr_set_option / hr_set_debug_option, behind the table.
+struct OptionField {
+    bool hr_ctx::*b = nullptr;
+    uint32_t hr_ctx::*u = nullptr;
+    int hr_ctx::*i = nullptr;
+    constexpr OptionField(bool hr_ctx::*p) : b(p) {}
+    constexpr OptionField(uint32_t hr_ctx::*p) : u(p) {}
+    constexpr OptionField(int hr_ctx::*p) : i(p) {}
+};
+enum { OPT_SYNC = 1, OPT_GOVERN = 2 };
+struct OptionRow {
+    const char *key;
+    OptionField field;
+    double lo, hi, step;
+    const char *error;
+    int flags;
+};
+static const OptionRow PRODUCT_OPTIONS[] = {
+    {"counters", &hr_ctx::counters, 1, 0, 0, "", 0},
+    {"batch", &hr_ctx::batch, 0, 64, 0, "batch must be in [1,64], or 0 for automatic", OPT_SYNC},
+    {"trace_boost", &hr_ctx::trace_boost, -1, 4, 1, "trace_boost must be -1 (governed by the measured kernel times) or a level 0 .. 4", OPT_SYNC | OPT_GOVERN},
+    // the bounce geometry in f64: closer to the reference's f64 arithmetic, a few per cent slower
+    {"precise_shading", &hr_ctx::precise_opt, -1, 1, 1, "precise_shading must be -1 (automatic), 0 or 1", OPT_SYNC | OPT_GOVERN},
+    {"quant_nodes", &hr_ctx::quant_nodes, 1, 0, 0, "", 0},   // next hr_upload_scene
+    {"bvh_builder", &hr_ctx::bvh_builder, -1, 2, 1, "bvh_builder must be -1 (by scene size), 0 (host SAH), 1 (device LBVH) or 2 (device PLOC)", 0},   // next hr_upload_scene
+    {"max_leaf", &hr_ctx::max_leaf, 1, 15, 0, "max_leaf must be in [1,15]", 0},   // next hr_upload_scene
+};
+static const OptionRow DEBUG_OPTIONS[] = {
+    {"adv_den", &hr_ctx::adv_den, 1, 64, 0, "adv_den must be in [1,64]", 0},
+    {"leaf_den", &hr_ctx::leaf_den, 1, 64, 0, "leaf_den must be in [1,64]", 0},
+    {"min_waves", &hr_ctx::min_waves, 4, 6, 0, "min_waves must be in [4,6]", 0},
+    {"kchunk", &hr_ctx::kchunk, 0, 64, 0, "kchunk must be in [1,64], or 0 for the default", 0},
+    {"node_unroll", &hr_ctx::node_unroll, 1, 2, 1, "node_unroll must be 1 or 2", 0},
+    {"tail_div", &hr_ctx::tail_div, 1, 0, 0, "", 0},
+    {"trace_grid", &hr_ctx::trace_grid, 1, 0, 0, "", 0},
+    {"trace_budget", &hr_ctx::trace_budget, 1, 0, 0, "", 0},
+    {"trace_wgs", &hr_ctx::trace_wgs, 1, 8, 0, "trace_wgs must be in [1,8]", 0},
+    {"seed_prio", &hr_ctx::seed_prio, 0, 3, 0, "seed_prio must be in [0,3]", 0},
+    {"init_prio", &hr_ctx::init_prio, 0, 3, 0, "init_prio must be in [0,3]", 0},
+    {"seed_split", &hr_ctx::seed_split, 8, 28, 4, "seed_split must be 8, 12, 16, 20, 24 or 28", 0},
+    {"seed_prof", &hr_ctx::seed_prof, 1, 0, 0, "", 0},
+    {"ploc_top", &hr_ctx::ploc_top, 1, 1 << 16, 0, "ploc_top must be in [1,65536]", 0},
+    {"trace_mode", &hr_ctx::trace_mode_opt, -1, 1, 1, "trace_mode must be -1 (automatic), 0 (megakernel) or 1 (split: traversal kernel + shading kernel)", OPT_SYNC | OPT_GOVERN},
+    {"draw_residuals", &hr_ctx::draw_residuals, 0, 1, 1, "draw_residuals must be 0 or 1", 0},
+    {"wf_adv_den", &hr_ctx::wf_adv_den, 0, 64, 0, "wf_adv_den must be in [0,64]", 0},
+    {"wf_trav_wgs", &hr_ctx::wf_trav_wgs, 1, 16, 0, "wf_trav_wgs must be in [1,16]", 0},
+    {"wf_shade_wgs", &hr_ctx::wf_shade_wgs, 1, 16, 0, "wf_shade_wgs must be in [1,16]", 0},
+    {"debug_skip", &hr_ctx::debug_skip, 1, 0, 0, "", 0},
+};
+static int apply_option(hr_ctx *c, const OptionRow &r, double value) {
+    if (r.lo <= r.hi) {
+        bool ok = !(value < r.lo || value > r.hi);
+        if (ok && r.step > 0) ok = std::fmod(value - r.lo, r.step) == 0.0;
+        if (!ok) return fail(HR_ERR_INVALID, "%s", r.error);
+    }
+    if (r.flags & OPT_SYNC) { int rc = sync_all(c); if (rc) return rc; }
+    if (r.field.b) c->*r.field.b = value != 0.0;
+    else if (r.field.u) c->*r.field.u = (uint32_t)value;
+    else c->*r.field.i = (int)value;
+    return r.flags & OPT_GOVERN ? govern_reset(c) : HR_OK;
+}
+
 int hr_set_option(hr_ctx *c, const char *key, double value) {
     if (!c || !key) return fail(HR_ERR_INVALID, "hr_set_option: null argument");
     HIP_TRY(hipSetDevice(c->device));
     std::string k = key;
-    if (k == "counters") { c->counters = value != 0.0; return HR_OK; }
-    if (k == "batch") {
-        if (value < 0 || value > 64) return fail(HR_ERR_INVALID, "batch must be in [1,64], or 0 for automatic");
-        int rc = sync_all(c);
-        if (rc) return rc;
-        c->batch = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "trace_boost") {
-        if (value != -1 && !(value >= 0 && value <= 4 && value == (int)value)) return fail(HR_ERR_INVALID, "trace_boost must be -1 (governed by the measured kernel times) or a level 0 .. 4");
-        int rc = sync_all(c);
-        if (rc) return rc;
-        c->trace_boost = (int)value;
-        return govern_reset(c);
-    }
+    if (const OptionRow *row = find_row(PRODUCT_OPTIONS, [&](const OptionRow &r) { return k == r.key; })) return apply_option(c, *row, value);
     if (k == "moments") {   // per-pixel first and second moments of the per-sampling values, for the noise estimate
         if (value != 0 && value != 1) return fail(HR_ERR_INVALID, "moments must be 0 or 1");
         if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "moments: hr_set_resolution not called");
@@ -1617,7 +1632,6 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
         c->moments_on = true;
         return HR_OK;
     }
-    if (k == "quant_nodes") { c->quant_nodes = value != 0.0; return HR_OK; }
     if (k == "max_tail_gib") {
         if (value < 1 || value > 128) return fail(HR_ERR_INVALID, "max_tail_gib must be in [1,128]");
         c->max_tail_bytes = (uint64_t)value << 30;
@@ -1628,26 +1642,9 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
         c->split_ratio = value;
         return HR_OK;
     }
-    if (k == "bvh_builder") {  // takes effect at the next hr_upload_scene
-        if (value != -1 && value != 0 && value != 1 && value != 2) return fail(HR_ERR_INVALID, "bvh_builder must be -1 (by scene size), 0 (host SAH), 1 (device LBVH) or 2 (device PLOC)");
-        c->bvh_builder = (int)value;
-        return HR_OK;
-    }
-    if (k == "max_leaf") {  // takes effect at the next hr_upload_scene
-        if (value < 1 || value > 15) return fail(HR_ERR_INVALID, "max_leaf must be in [1,15]");
-        c->max_leaf = (int)value;
-        return HR_OK;
-    }
     if (k == "rng_window") {
         if ((int)value != ISAAC_TAIL) return fail(HR_ERR_UNSUPPORTED, "rng_window is fixed at %d in this build", ISAAC_TAIL);
         return HR_OK;
-    }
-    if (k == "precise_shading") {   // the bounce geometry in f64 (split pipeline): closer to the reference's f64 arithmetic, a few per cent slower
-        if (value != -1 && value != 0 && value != 1) return fail(HR_ERR_INVALID, "precise_shading must be -1 (automatic), 0 or 1");
-        int rc = sync_all(c);
-        if (rc) return rc;
-        c->precise_opt = (int)value;
-        return govern_reset(c);
     }
     if (k == "russian_roulette") {  // NOT image-preserving (see the header): 0 = off, else the first path iteration that plays
         if (value != 0 && (value < 2 || value > 9)) return fail(HR_ERR_INVALID, "russian_roulette must be 0 (off) or the first iteration that plays, in [2,9]");
@@ -1658,60 +1655,13 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
     return fail(HR_ERR_INVALID, "unknown option '%s' (measurement knobs live behind hr_set_debug_option)", key);
 }
 
-// Measurement / experiment knobs.  Kept apart from hr_set_option on purpose: a host that only uses hr_set_option cannot change the
-// kernels' schedule, and cannot reach "debug_skip", which produces a garbage image.
+// Measurement / experiment knobs.  Kept apart from hr_set_option on purpose (two tables, each looked up by its own entry point only): a host
+// that only uses hr_set_option cannot change the kernels' schedule, and cannot reach "debug_skip", which produces a garbage image.
 int hr_set_debug_option(hr_ctx *c, const char *key, double value) {
     if (!c || !key) return fail(HR_ERR_INVALID, "hr_set_debug_option: null argument");
     HIP_TRY(hipSetDevice(c->device));
     std::string k = key;
-    if (k == "adv_den") {
-        if (value < 1 || value > 64) return fail(HR_ERR_INVALID, "adv_den must be in [1,64]");
-        c->adv_den = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "leaf_den") {
-        if (value < 1 || value > 64) return fail(HR_ERR_INVALID, "leaf_den must be in [1,64]");
-        c->leaf_den = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "min_waves") {
-        if (value < 4 || value > 6) return fail(HR_ERR_INVALID, "min_waves must be in [4,6]");
-        c->min_waves = (int)value;
-        return HR_OK;
-    }
-    if (k == "kchunk") {
-        if (value < 0 || value > 64) return fail(HR_ERR_INVALID, "kchunk must be in [1,64], or 0 for the default");
-        c->kchunk = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "node_unroll") {
-        if (value != 1 && value != 2) return fail(HR_ERR_INVALID, "node_unroll must be 1 or 2");
-        c->node_unroll = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "tail_div") { c->tail_div = (uint32_t)value; return HR_OK; }
-    if (k == "trace_grid") { c->trace_grid = (uint32_t)value; return HR_OK; }
-    if (k == "trace_budget") { c->trace_budget = (uint32_t)value; return HR_OK; }
-    if (k == "trace_wgs") {
-        if (value < 1 || value > 8) return fail(HR_ERR_INVALID, "trace_wgs must be in [1,8]");
-        c->trace_wgs = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "seed_prio") {
-        if (value < 0 || value > 3) return fail(HR_ERR_INVALID, "seed_prio must be in [0,3]");
-        c->seed_prio = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "init_prio") {
-        if (value < 0 || value > 3) return fail(HR_ERR_INVALID, "init_prio must be in [0,3]");
-        c->init_prio = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "seed_split") {
-        if (value != 8 && value != 12 && value != 16 && value != 20 && value != 24 && value != 28) return fail(HR_ERR_INVALID, "seed_split must be 8, 12, 16, 20, 24 or 28");
-        c->seed_split = (int)value;
-        return HR_OK;
-    }
+    if (const OptionRow *row = find_row(DEBUG_OPTIONS, [&](const OptionRow &r) { return k == r.key; })) return apply_option(c, *row, value);
     if (k == "seed_mode") {
         if (value != 0 && value != 1 && value != 2 && value != 3 && value != 4) return fail(HR_ERR_INVALID, "seed_mode must be 4 (five-wave four-run kernel), 3 (phase-shifted four-run kernel), 2 (three-run kernel), 1 (producer / consumer kernel with a state ring) or 0 (fused kernel)");
 #if !defined(HR_EXPERIMENTS)
@@ -1722,24 +1672,6 @@ int hr_set_debug_option(hr_ctx *c, const char *key, double value) {
         c->seed_mode = (int)value;
         return HR_OK;
     }
-    if (k == "seed_prof") { c->seed_prof = (int)value; return HR_OK; }
-    if (k == "ploc_top") {
-        if (value < 1 || value > (1 << 16)) return fail(HR_ERR_INVALID, "ploc_top must be in [1,65536]");
-        c->ploc_top = (uint32_t)value;
-        return HR_OK;
-    }
-    if (k == "trace_mode") {
-        if (value != -1 && value != 0 && value != 1) return fail(HR_ERR_INVALID, "trace_mode must be -1 (automatic), 0 (megakernel) or 1 (split: traversal kernel + shading kernel)");
-        int rc = sync_all(c);
-        if (rc) return rc;
-        c->trace_mode_opt = (int)value;
-        return govern_reset(c);
-    }
-    if (k == "draw_residuals") { if (value != 0 && value != 1) return fail(HR_ERR_INVALID, "draw_residuals must be 0 or 1"); c->draw_residuals = (int)value; return HR_OK; }
-    if (k == "wf_adv_den") { if (value < 0 || value > 64) return fail(HR_ERR_INVALID, "wf_adv_den must be in [0,64]"); c->wf_adv_den = (uint32_t)value; return HR_OK; }
-    if (k == "wf_trav_wgs") { if (value < 1 || value > 16) return fail(HR_ERR_INVALID, "wf_trav_wgs must be in [1,16]"); c->wf_trav_wgs = (uint32_t)value; return HR_OK; }
-    if (k == "wf_shade_wgs") { if (value < 1 || value > 16) return fail(HR_ERR_INVALID, "wf_shade_wgs must be in [1,16]"); c->wf_shade_wgs = (uint32_t)value; return HR_OK; }
-    if (k == "debug_skip") { c->debug_skip = (int)value; return HR_OK; }
     if (k == "nee_cull") { c->nee_cull = (uint32_t)value & 7u; return HR_OK; }
     return fail(HR_ERR_INVALID, "unknown debug option '%s'", key);
 }
@@ -1774,15 +1706,13 @@ static int path_draws_out(hr_ctx *c, uint32_t sampling, float *host_out, bool re
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
     if (rc) return rc;
-    RenderParams rp{};
-    rp.width = c->W; rp.height = c->H; rp.tiles_x = (c->W + 3) / 4; rp.tiles_y = (c->H + 3) / 4;
-    rp.sampling_begin = sampling; rp.stride = 1; rp.num_k = 1;
-    uint32_t tiles = rp.tiles_x * rp.tiles_y;
-    if ((rc = ensure_draws(c, tiles))) return rc;
-    if (residuals) rp.rec_lo_off = rec_lo_off(c);
-    if ((rc = ensure_ovf(c, (uint64_t)tiles * 64u))) return rc;
-    rp.ovf_cap = c->ovf_cap;
-    if ((rc = launch_seed(c, rp, 0, c->stream))) return rc;
+    LaunchPlan plan;
+    if ((rc = plan_launch(c, sampling, 1, 1, TRACE_NONE, plan))) return rc;   // (no region: refused above)
+    RenderParams &rp = plan.rp;
+    const uint32_t tiles = plan.tiles;
+    if (!residuals) rp.rec_lo_off = 0;   // the fp32 draws are asked for: the seed kernel's form without the twin
+    rp.pad[0] = 0;                       // the seed kernel alone on the chip: its consumer waves stay at the priority they start with
+    if ((rc = launch_seed(c, rp, 0, c->stream))) return rc;   // on the main stream, slot 0: nothing else is in flight
     std::vector<float> h((size_t)tiles * REC_ITEM_FLOATS), lo;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(h.data(), c->recs[0], h.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1823,22 +1753,15 @@ int hr_debug_path_log(hr_ctx *c, uint32_t sampling, uint32_t *host_out) {
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
     if (rc) return rc;
-    RenderParams rp{};
-    rp.width = c->W; rp.height = c->H; rp.tiles_x = (c->W + 3) / 4; rp.tiles_y = (c->H + 3) / 4;
-    rp.sampling_begin = sampling; rp.stride = 1; rp.num_k = 1;
-    rp.adv_den = c->adv_den; rp.leaf_den = c->leaf_den; rp.node_unroll = c->node_unroll; rp.kchunk = c->kchunk;
-    rp.pad[0] = c->seed_prio;
-    rp.nee_cull_off = ~c->nee_cull & 7u;
-    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
-    if ((rc = ensure_draws(c, tiles))) return rc;
-    rp.rec_lo_off = rec_lo_off(c);
-    if ((rc = ensure_ovf(c, (uint64_t)tiles * 64u))) return rc;
-    rp.ovf_cap = c->ovf_cap;
-    if ((rc = launch_seed(c, rp, 0, c->stream))) return rc;
+    LaunchPlan plan;
+    if ((rc = plan_launch(c, sampling, 1, 1, TRACE_IN_FORCE, plan))) return rc;   // (no region: refused above)
+    const RenderParams &rp = plan.rp;
+    const bool split = plan.split;
+    const TraceFn trace = select_trace_kernel(c->counters, c->dsc.qnodes != nullptr, c->rr_start != 0, c->precise, c->min_waves, true);
+    if (!split && !trace) return fail(HR_ERR_UNSUPPORTED, "hr_debug_path_log: no trace kernel instantiation for these options (kernel_variants.h)");
+    if ((rc = launch_seed(c, rp, 0, c->stream))) return rc;   // on the main stream, slot 0: nothing else is in flight
     const size_t words = (size_t)c->W * c->H * 4u * 8u;
     uint32_t *d_log = nullptr;
-    const bool split = c->trace_mode == 1 && !c->rr_start;
-    if (split && (rc = ensure_wf(c, (uint64_t)tiles * 64u))) return rc;
     HIP_TRY(hipMalloc((void **)&d_log, words * sizeof(uint32_t)));
     hipError_t e = hipMemsetAsync(d_log, 0, words * sizeof(uint32_t), c->stream);
     void *log_block = nullptr;
@@ -1857,15 +1780,7 @@ int hr_debug_path_log(hr_ctx *c, uint32_t sampling, uint32_t *host_out) {
     } else if (e == hipSuccess) {
         e = hipMemsetAsync(c->d_tile_counter, 0, sizeof(uint32_t), c->stream);
         if (e == hipSuccess) {
-            const uint32_t kch = c->kchunk ? c->kchunk : TRACE_KCHUNK;
-            const uint64_t units = (uint64_t)tiles * ((1u + kch - 1) / kch);
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)c->num_cus * c->trace_wgs, (units + TRACE_WAVES - 1) / TRACE_WAVES);
-            dim3 g(grid), b(64 * TRACE_WAVES);
-            if (c->precise) {
-                if (c->dsc.qnodes) hipLaunchKernelGGL((trace_kernel<false, 3, true, false, true, true>), g, b, 0, c->stream, c->dsc, rp, c->recs[0], c->d_counters, c->d_tile_counter, d_log);
-                else hipLaunchKernelGGL((trace_kernel<false, 3, false, false, true, true>), g, b, 0, c->stream, c->dsc, rp, c->recs[0], c->d_counters, c->d_tile_counter, d_log);
-            } else if (c->dsc.qnodes) hipLaunchKernelGGL((trace_kernel<false, 3, true, false, true>), g, b, 0, c->stream, c->dsc, rp, c->recs[0], c->d_counters, c->d_tile_counter, d_log);
-            else hipLaunchKernelGGL((trace_kernel<false, 3, false, false, true>), g, b, 0, c->stream, c->dsc, rp, c->recs[0], c->d_counters, c->d_tile_counter, d_log);
+            hipLaunchKernelGGL(trace, dim3(trace_grid_size(c, plan.tiles, 1, 0)), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, c->recs[0], c->d_counters, c->d_tile_counter, d_log);
             e = hipGetLastError();
         }
     }
@@ -1887,19 +1802,11 @@ int hr_debug_wf_profile(hr_ctx *c, uint32_t sampling, uint32_t num_k, double *ms
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
     if (rc) return rc;
-    RenderParams rp{};
-    rp.width = c->W; rp.height = c->H; rp.tiles_x = (c->W + 3) / 4; rp.tiles_y = (c->H + 3) / 4;
-    rp.sampling_begin = sampling; rp.stride = 1; rp.num_k = num_k;
-    rp.adv_den = c->adv_den; rp.leaf_den = c->leaf_den; rp.node_unroll = c->node_unroll;
-    rp.pad[0] = c->seed_prio;
-    rp.nee_cull_off = ~c->nee_cull & 7u;
-    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
-    if ((rc = ensure_draws(c, (size_t)tiles * num_k))) return rc;
-    rp.rec_lo_off = rec_lo_off(c);
-    if ((rc = ensure_ovf(c, (uint64_t)tiles * 64u * num_k))) return rc;
-    if ((rc = ensure_wf(c, (uint64_t)tiles * 64u * num_k))) return rc;
-    rp.ovf_cap = c->ovf_cap;
-    if ((rc = launch_seed(c, rp, 0, c->stream))) return rc;
+    LaunchPlan plan;
+    if ((rc = plan_launch(c, sampling, 1, num_k, TRACE_SPLIT, plan))) return rc;   // (no region: refused above); the split pipeline whatever is in force
+    RenderParams &rp = plan.rp;
+    rp.kchunk = 0;   // not passed: the split pipeline has no work units of samplings
+    if ((rc = launch_seed(c, rp, 0, c->stream))) return rc;   // on the main stream, slot 0: nothing else is in flight
     std::vector<hipEvent_t> marks;
     rc = launch_split(c, rp, 0, &marks);
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -1946,6 +1853,8 @@ int hr_debug_trace(hr_ctx *c, uint32_t n, const float *rays, const float *shadow
     if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: not while a region is set (hr_set_region)");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_trace: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
+    const TraceDebugFn fn = select_trace_debug_kernel(c->counters, c->dsc.qnodes != nullptr);
+    if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: no kernel instantiation for these options (kernel_variants.h)");
     float *d_rays = nullptr, *d_out = nullptr, *d_sl = nullptr;
     int32_t *d_el = nullptr;
     hipError_t e = hipMalloc((void **)&d_rays, (size_t)n * 6 * 4);
@@ -1956,20 +1865,15 @@ int hr_debug_trace(hr_ctx *c, uint32_t n, const float *rays, const float *shadow
     if (e == hipSuccess && shadow_len) e = hipMemcpy(d_sl, shadow_len, (size_t)n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         RenderParams rp{};
-        rp.leaf_den = c->leaf_den; rp.node_unroll = c->node_unroll;
-        // the record format hr_render walks on this scene; timed with HIP events (hr_stats.debug_kernel_ms), counted with option "counters"
-        EventPair ev{nullptr, nullptr};
-        bool timed = hipEventCreate(&ev.a) == hipSuccess && hipEventCreate(&ev.b) == hipSuccess && hipEventRecord(ev.a, c->stream) == hipSuccess;
-        const dim3 g((n + 63) / 64), b(64);
-        if (c->counters) {
-            if (c->dsc.qnodes) hipLaunchKernelGGL((trace_debug_kernel<true, true>), g, b, 0, c->stream, c->dsc, rp, n, d_rays, d_sl, d_out, d_el, c->d_counters);
-            else hipLaunchKernelGGL((trace_debug_kernel<false, true>), g, b, 0, c->stream, c->dsc, rp, n, d_rays, d_sl, d_out, d_el, c->d_counters);
-        } else if (c->dsc.qnodes) hipLaunchKernelGGL((trace_debug_kernel<true>), g, b, 0, c->stream, c->dsc, rp, n, d_rays, d_sl, d_out, d_el);
-        else hipLaunchKernelGGL((trace_debug_kernel<false>), g, b, 0, c->stream, c->dsc, rp, n, d_rays, d_sl, d_out, d_el);
+        knob_params(c, rp);   // (no geometry: the rays are the caller's)
+        // the record format hr_render walks on this scene; timed with HIP events (hr_stats.debug_kernel_ms), counted with option "counters".
+        // The timing is best effort: the launch goes out without it if an event cannot be made, and only a pair that was really recorded
+        // is ever queried (timed_end)
+        EventPair ev;
+        (void)timed_begin(ev, c->stream);
+        hipLaunchKernelGGL(fn, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, rp, n, d_rays, d_sl, d_out, d_el, c->counters ? c->d_counters : (Counters *)nullptr);
         e = hipGetLastError();
-        timed = timed && e == hipSuccess && hipEventRecord(ev.b, c->stream) == hipSuccess;
-        if (timed) { c->debug_events.push_back(ev); c->debug_launches++; }   // only a pair that was really recorded is ever queried
-        else { if (ev.a) (void)hipEventDestroy(ev.a); if (ev.b) (void)hipEventDestroy(ev.b); }
+        (void)timed_end(e, ev, c->stream, c->debug_events, &c->debug_launches);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 8 * 4, hipMemcpyDeviceToHost);

@@ -1,0 +1,142 @@
+// kernel_variants.h — which instantiation of a kernel family a launch runs.  One table per family and one select_*() beside it:
+//   * a row names an instantiation ONCE (HR_VARIANT spells the template arguments as the row's key and as the function),
+//   * select_*() turns the run-time facts of a launch (options, the scene's record format, the query that launches) into a key and looks the
+//     row up — the quirks of that mapping are written there and nowhere else; nullptr: the table has no such row, the caller refuses,
+//   * create_resources (hr_api.hip) walks the same tables: the LDS attribute of every seed kernel, the "no LDS" guard of every trace-side
+//     kernel.  What a launch can run is a row, so both loops have seen it.
+// A new variant is a new row (and a line in its selector if a new fact selects it); nothing else spells a <...> list of these kernels.
+// No row for a combination that is never launched: every trace_kernel instantiation costs compile time and code-object size.
+// Included by hr_api.hip behind the kernel headers (one translation unit; the kernels are static to it).
+#pragma once
+
+#define HR_VARIANT(kernel, ...) {__VA_ARGS__, kernel<__VA_ARGS__>}
+template <class Row, size_t N, class Match>
+static const Row *find_row(const Row (&table)[N], Match match) {
+    for (const Row &r : table)
+        if (match(r)) return &r;
+    return nullptr;
+}
+template <class Row>
+static auto fn_of(const Row *r) -> decltype(r->fn) { return r ? r->fn : nullptr; }   // nullptr: no such row
+
+// ---- trace_kernel<CNT, MINW, QN, RR, LOG, PREC> (trace_kernel.h) ----
+typedef void (*TraceFn)(Scene, RenderParams, float *, Counters *, uint32_t *, uint32_t *);
+struct TraceVariant { bool cnt; int minw; bool qn, rr, log, prec; TraceFn fn; };
+static const TraceVariant TRACE_VARIANTS[] = {
+    // fp32 shading: the default (5 waves), the tree of 32-byte nodes, debug option min_waves 4 / 6, the counters build
+    HR_VARIANT(trace_kernel, false, 5, true, false, false, false), HR_VARIANT(trace_kernel, false, 5, false, false, false, false),
+    HR_VARIANT(trace_kernel, false, 4, true, false, false, false), HR_VARIANT(trace_kernel, false, 6, true, false, false, false),
+    HR_VARIANT(trace_kernel, true, 3, true, false, false, false), HR_VARIANT(trace_kernel, true, 3, false, false, false, false),
+    // the roulette estimator (option russian_roulette)
+    HR_VARIANT(trace_kernel, false, 5, true, true, false, false), HR_VARIANT(trace_kernel, false, 5, false, true, false, false),
+    HR_VARIANT(trace_kernel, true, 3, true, true, false, false), HR_VARIANT(trace_kernel, true, 3, false, true, false, false),
+    // precise shading (path_advance<.., PREC>): 128 VGPRs, debug option min_waves 6 -> the 96-VGPR form, 4 -> the 168-VGPR form, the counters build
+    HR_VARIANT(trace_kernel, false, 4, true, false, false, true), HR_VARIANT(trace_kernel, false, 4, false, false, false, true),
+    HR_VARIANT(trace_kernel, false, 5, true, false, false, true), HR_VARIANT(trace_kernel, false, 3, true, false, false, true),
+    HR_VARIANT(trace_kernel, true, 3, true, false, false, true), HR_VARIANT(trace_kernel, true, 3, false, false, false, true),
+    // the path log (hr_debug_path_log)
+    HR_VARIANT(trace_kernel, false, 3, true, false, true, false), HR_VARIANT(trace_kernel, false, 3, false, false, true, false),
+    HR_VARIANT(trace_kernel, false, 3, true, false, true, true), HR_VARIANT(trace_kernel, false, 3, false, false, true, true),
+};
+// counters / qn (the scene has quantised nodes) / rr (rr_start != 0) / precise / min_waves as the context has them; log: the path log's launch.
+//   * the log builds are one occupancy form (MINW 3) and know neither counters nor roulette
+//   * the roulette estimator ignores min_waves (and has no f64 form: hr_render refuses the pair)
+//   * counters builds are MINW 3 whatever min_waves says
+//   * precise: min_waves 6 -> MINW 5, 4 -> MINW 3, otherwise MINW 4 — with quantised nodes only; without them MINW 4
+//   * fp32: min_waves is MINW — with quantised nodes only; without them <false, 5, false>
+static TraceFn select_trace_kernel(bool counters, bool qn, bool rr, bool precise, int min_waves, bool log) {
+    bool cnt = counters, prec = precise;
+    int minw;
+    if (log) { cnt = false; rr = false; minw = 3; }
+    else if (rr) { prec = false; minw = cnt ? 3 : 5; }
+    else if (cnt) minw = 3;
+    else if (prec) minw = !qn ? 4 : min_waves == 6 ? 5 : min_waves == 4 ? 3 : 4;
+    else minw = !qn ? 5 : min_waves == 4 ? 4 : min_waves == 6 ? 6 : 5;
+    return fn_of(find_row(TRACE_VARIANTS, [&](const TraceVariant &r) { return r.cnt == cnt && r.minw == minw && r.qn == qn && r.rr == rr && r.log == log && r.prec == prec; }));
+}
+
+// ---- the split pipeline (wf_kernels.h) ----
+typedef void (*WfStartFn)(Scene, RenderParams, float *, WfQueues);
+struct WfStartVariant { bool prec; WfStartFn fn; };
+static const WfStartVariant WF_START_VARIANTS[] = {HR_VARIANT(wf_start_kernel, false), HR_VARIANT(wf_start_kernel, true)};
+static WfStartFn select_wf_start_kernel(bool precise) {
+    return fn_of(find_row(WF_START_VARIANTS, [&](const WfStartVariant &r) { return r.prec == precise; }));
+}
+
+typedef void (*WfTraverseFn)(Scene, RenderParams, WfQueues, uint32_t, Counters *);
+struct WfTraverseVariant { bool cnt, qn; WfTraverseFn fn; };
+static const WfTraverseVariant WF_TRAVERSE_VARIANTS[] = {HR_VARIANT(wf_traverse_kernel, false, true), HR_VARIANT(wf_traverse_kernel, false, false),
+                                                         HR_VARIANT(wf_traverse_kernel, true, true), HR_VARIANT(wf_traverse_kernel, true, false)};
+typedef void (*WfShadeFn)(Scene, RenderParams, float *, WfQueues, uint32_t, Counters *, uint32_t *);
+struct WfShadeVariant { bool cnt, prec, log; WfShadeFn fn; };
+static const WfShadeVariant WF_SHADE_VARIANTS[] = {HR_VARIANT(wf_shade_kernel, false, false, false), HR_VARIANT(wf_shade_kernel, false, true, false),
+                                                   HR_VARIANT(wf_shade_kernel, true, false, false),  HR_VARIANT(wf_shade_kernel, true, true, false),
+                                                   HR_VARIANT(wf_shade_kernel, false, false, true),  HR_VARIANT(wf_shade_kernel, false, true, true)};
+// log: the path log's launch — it does not count, in either kernel (the traversal kernel has no log form of its own)
+static WfTraverseFn select_wf_traverse_kernel(bool counters, bool qn, bool log) {
+    const bool cnt = counters && !log;
+    return fn_of(find_row(WF_TRAVERSE_VARIANTS, [&](const WfTraverseVariant &r) { return r.cnt == cnt && r.qn == qn; }));
+}
+static WfShadeFn select_wf_shade_kernel(bool counters, bool precise, bool log) {
+    const bool cnt = counters && !log;
+    return fn_of(find_row(WF_SHADE_VARIANTS, [&](const WfShadeVariant &r) { return r.cnt == cnt && r.prec == precise && r.log == log; }));
+}
+
+// ---- debug_render_kernel<CNT, QN> and trace_debug_kernel<QN, CNT> (trace_kernel.h): neither runs beside a seed kernel ----
+typedef void (*DebugRenderFn)(Scene, RenderParams, int, float *, Counters *);
+struct DebugRenderVariant { bool cnt, qn; DebugRenderFn fn; };
+static const DebugRenderVariant DEBUG_RENDER_VARIANTS[] = {HR_VARIANT(debug_render_kernel, false, true), HR_VARIANT(debug_render_kernel, false, false),
+                                                           HR_VARIANT(debug_render_kernel, true, true), HR_VARIANT(debug_render_kernel, true, false)};
+static DebugRenderFn select_debug_render_kernel(bool counters, bool qn) {
+    return fn_of(find_row(DEBUG_RENDER_VARIANTS, [&](const DebugRenderVariant &r) { return r.cnt == counters && r.qn == qn; }));
+}
+typedef void (*TraceDebugFn)(Scene, RenderParams, uint32_t, const float *, const float *, float *, int32_t *, Counters *);
+struct TraceDebugVariant { bool qn, cnt; TraceDebugFn fn; };
+static const TraceDebugVariant TRACE_DEBUG_VARIANTS[] = {HR_VARIANT(trace_debug_kernel, true, false), HR_VARIANT(trace_debug_kernel, false, false),
+                                                         HR_VARIANT(trace_debug_kernel, true, true), HR_VARIANT(trace_debug_kernel, false, true)};
+static TraceDebugFn select_trace_debug_kernel(bool counters, bool qn) {
+    return fn_of(find_row(TRACE_DEBUG_VARIANTS, [&](const TraceDebugVariant &r) { return r.cnt == counters && r.qn == qn; }));
+}
+
+// ---- the seed kernels (seed_kernels.h) ----
+// Every one takes (rp, lens_shape, [ring,] recs, ovf, win, counters) and SEED_LDS_BYTES of dynamic LDS; `ring`: it has the ring argument.
+// key: mode = option seed_mode; split = init blocks of the producer waves (seed_pc_kernel only, else 0); prof = the phase-timing build (a
+// number for seed_ps_kernel, else 0 / 1); lo = the launch writes the draws' residuals into the records' twin (seed_seg_kernel only).
+struct SeedVariant { int mode, split, prof; bool lo; const void *fn; uint32_t threads; bool ring; };
+static const SeedVariant SEED_VARIANTS[] = {
+    {0, 0, 0, false, (const void *)seed_isaac64_kernel, 64 * SEED_WAVES, false},
+    {1, 8, 0, false, (const void *)seed_pc_kernel<8>, 256, true},
+    {1, 12, 0, false, (const void *)seed_pc_kernel<12>, 256, true},
+    {1, 16, 0, false, (const void *)seed_pc_kernel<16>, 256, true},
+    {1, 20, 0, false, (const void *)seed_pc_kernel<20>, 256, true},
+    {1, 24, 0, false, (const void *)seed_pc_kernel<24>, 256, true},
+    {1, 28, 0, false, (const void *)seed_pc_kernel<28>, 256, true},
+    {1, 16, 1, false, (const void *)seed_pc_kernel<16, true>, 256, true},
+    {1, 20, 1, false, (const void *)seed_pc_kernel<20, true>, 256, true},
+    {2, 0, 0, false, (const void *)seed_seg_kernel<false, false>, 256, true},
+    {2, 0, 1, false, (const void *)seed_seg_kernel<true, false>, 256, true},
+    {2, 0, 0, true, (const void *)seed_seg_kernel<false, true>, 256, true},
+    {2, 0, 1, true, (const void *)seed_seg_kernel<true, true>, 256, true},
+#if defined(HR_EXPERIMENTS)
+    {3, 0, 0, false, (const void *)seed_ps_kernel<0>, 256, true},
+    {3, 0, 1, false, (const void *)seed_ps_kernel<1>, 256, true},
+    {3, 0, 2, false, (const void *)seed_ps_kernel<2>, 256, true},
+    {3, 0, 3, false, (const void *)seed_ps_kernel<3>, 256, true},
+    {4, 0, 0, false, (const void *)seed_w5_kernel<false>, 320, true},
+    {4, 0, 1, false, (const void *)seed_w5_kernel<true>, 320, true},
+#endif
+};
+// seed_mode / seed_split / seed_prof as the context has them; twin: the launch carries the residual twin (rp.rec_lo_off != 0).
+//   * only the three-run kernel (mode 2) writes the twin
+//   * the ring kernel (mode 1): its phase-timing build exists for splits 16 and 20 only and falls back to 16
+//   * seed_ps_kernel (mode 3) has timing builds 1 .. 3, any other seed_prof is its plain build; everywhere else seed_prof is on / off
+//   * the fused kernel (mode 0) has no timing build
+static const SeedVariant *select_seed_kernel(int seed_mode, int seed_split, int seed_prof, bool twin) {
+    int split = 0, prof = seed_prof ? 1 : 0;
+    bool lo = false;
+    if (seed_mode == 2) lo = twin;
+    else if (seed_mode == 1) split = prof ? (seed_split == 20 ? 20 : 16) : seed_split;
+    else if (seed_mode == 3) prof = seed_prof >= 1 && seed_prof <= 3 ? seed_prof : 0;
+    else if (seed_mode == 0) prof = 0;
+    return find_row(SEED_VARIANTS, [&](const SeedVariant &r) { return r.mode == seed_mode && r.split == split && r.prof == prof && r.lo == lo; });
+}
