@@ -277,6 +277,12 @@ struct RenderParams {
     // the region (hr_set_region): the window [org_x, org_x + reg_w) x [org_y, org_y + reg_h) of the frame.  The tiles, the accumulator and the
     // path log are the window's (region-local pixels); seeds and camera rays take frame pixels org + local.  reg_w = reg_h = 0: the whole frame.
     uint32_t org_x, org_y, reg_w, reg_h;
+    // the active-tile list (hr_set_tile_mask / hr_select_tiles; adapt_core.h): the launch's work items are the DENSE indices
+    // 0 .. tile_count - 1 — records, work units, the finer tail and the fix-up lists are addressed by them — and tile_list[dense] is the region's
+    // tile whose pixels the item renders (ascending).  nullptr / 0: every tile of the region, dense index == tile.  Only the LIST forms of the
+    // kernels read the two (kernel_variants.h); the other forms never look.
+    const uint32_t *tile_list;
+    uint32_t tile_count;
 };
 HD uint32_t rp_reg_w(const RenderParams &rp) { return rp.reg_w ? rp.reg_w : rp.width; }
 HD uint32_t rp_reg_h(const RenderParams &rp) { return rp.reg_h ? rp.reg_h : rp.height; }

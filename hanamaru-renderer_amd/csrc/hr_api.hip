@@ -60,6 +60,7 @@ static int fail(int code, const char *fmt, ...) {
 #include "wf_kernels.h"
 #include "post_kernels.h"
 #include "noise_core.h"
+#include "adapt_core.h"
 #include "kernel_variants.h"
 
 // ------------------------------------------------------------------------------------------ context
@@ -89,6 +90,19 @@ struct hr_ctx {
     bool moments_on = false;
     double *moments = nullptr, *noise_img = nullptr;
     uint64_t moments_n = 0;
+    // option "sample_counts" (DESIGN.md §4.8): the samplings every pixel of the region has received (accumulate_kernel<.., true>), region-local
+    bool counts_on = false;
+    uint32_t *counts = nullptr;
+    // the tile mask (hr_set_tile_mask / hr_select_tiles): which 4x4 tiles of the region hr_render covers.  On the device the compacted list of the
+    // active tiles' indices, ascending (RenderParams::tile_list), and the flags it was compacted from; on the host the same flags as bytes.
+    bool mask_on = false;
+    std::vector<uint8_t> mask;               // [tiles_y * tiles_x] 0 / 1
+    uint32_t mask_active = 0;                // entries of the list
+    uint64_t mask_pixels = 0;                // in-region pixels of the active tiles (hr_stats.paths)
+    uint32_t *d_tile_list = nullptr, *d_tile_flags = nullptr;   // [tiles] each
+    uint32_t *d_select_out = nullptr;        // [3]: hipcub's count of selected tiles, the smallest and the largest count of a pixel (counts_min_kernel)
+    void *select_tmp = nullptr;              // hipcub's scratch for the compaction
+    size_t select_tmp_bytes = 0;
     // multi-GPU: RCCL communicator of this rank, and the all-reduced accumulator (valid until the next render / clear / write)
     hrcomm::Comm comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -460,6 +474,8 @@ int hr_destroy(hr_ctx *c) {
     if (c->accum_total) (void)hipFree(c->accum_total);
     if (c->moments) (void)hipFree(c->moments);
     if (c->noise_img) (void)hipFree(c->noise_img);
+    if (c->counts) (void)hipFree(c->counts);
+    for (void *p : {(void *)c->d_tile_list, (void *)c->d_tile_flags, (void *)c->d_select_out, c->select_tmp}) if (p) (void)hipFree(p);
     if (c->comm && hrcomm::api().CommDestroy) (void)hrcomm::api().CommDestroy(c->comm);
     for (hr_ctx *p : c->same_device_peers) if (p != c) { p->same_device_peers.clear(); p->comm_world = 0; p->total_valid = false; p->comm_path = HR_COMM_NONE; p->allreduces = 0; }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -754,6 +770,33 @@ static int alloc_moments(hr_ctx *c, uint32_t w, uint32_t h) {
     return HR_OK;
 }
 
+// The counts buffer (option "sample_counts") follows the accumulator like the moments do.
+static int free_counts(hr_ctx *c) {
+    if (c->counts) { HIP_TRY(hipFree(c->counts)); c->counts = nullptr; }
+    return HR_OK;
+}
+static int alloc_counts(hr_ctx *c, uint32_t w, uint32_t h) {
+    int rc = free_counts(c);
+    if (rc) return rc;
+    const size_t bytes = (size_t)w * h * sizeof(uint32_t);
+    HIP_TRY(hipMalloc((void **)&c->counts, bytes));
+    HIP_TRY(hipMemset(c->counts, 0, bytes));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // (the render streams do not wait for the null stream)
+    return HR_OK;
+}
+// No tile mask: hr_render covers every tile of the region again.  The mask's buffers are sized by the region's tiles and go with it.
+// (Callers have synchronised the context: no kernel is reading the list.)
+static int remove_mask(hr_ctx *c) {
+    c->mask_on = false;
+    c->mask.clear();
+    c->mask_active = 0; c->mask_pixels = 0;
+    if (c->d_tile_list) { HIP_TRY(hipFree(c->d_tile_list)); c->d_tile_list = nullptr; }
+    if (c->d_tile_flags) { HIP_TRY(hipFree(c->d_tile_flags)); c->d_tile_flags = nullptr; }
+    if (c->select_tmp) { HIP_TRY(hipFree(c->select_tmp)); c->select_tmp = nullptr; }
+    c->select_tmp_bytes = 0;
+    return HR_OK;
+}
+
 // The target: the W x H frame and the window of it that is rendered (the whole frame, or hr_set_region's).  The accumulator and the resolve's
 // buffers are (re)allocated for the window and zeroed.
 static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
@@ -769,6 +812,8 @@ static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y
     if (c->d_rgb8) { HIP_TRY(hipFree(c->d_rgb8)); c->d_rgb8 = nullptr; }
     if (c->accum_total) { HIP_TRY(hipFree(c->accum_total)); c->accum_total = nullptr; }
     if (c->moments_on) { int mrc = alloc_moments(c, w, h); if (mrc) return mrc; }
+    if ((rc = remove_mask(c))) return rc;   // the mask is over the old region's tiles
+    if (c->counts_on && (rc = alloc_counts(c, w, h))) return rc;
     size_t n = (size_t)w * h * 3;
     HIP_TRY(hipMalloc((void **)&c->accum_own, n * sizeof(float)));
     HIP_TRY(hipMemset(c->accum_own, 0, n * sizeof(float)));
@@ -867,6 +912,7 @@ int hr_clear(hr_ctx *c) {
     HIP_TRY(hipMemsetAsync(c->accum, 0, (size_t)c->RW * c->RH * 3 * sizeof(float), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
     if (c->moments) HIP_TRY(hipMemsetAsync(c->moments, 0, (size_t)c->RW * c->RH * 6 * sizeof(double), c->stream));
+    if (c->counts) HIP_TRY(hipMemsetAsync(c->counts, 0, (size_t)c->RW * c->RH * sizeof(uint32_t), c->stream));   // (the tile mask stays: a setting, like the region)
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->moments_n = 0;
     c->seed_ms = c->trace_ms = c->post_ms = c->debug_ms = 0;
@@ -950,7 +996,7 @@ static int launch_split(hr_ctx *c, const RenderParams &rp, int slot, std::vector
     hipStream_t st = c->stream;
     auto mark = [&]() -> hipError_t { if (!marks) return hipSuccess; hipEvent_t e; hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; marks->push_back(e); return hipEventRecord(e, st); };
     const bool log = plog != nullptr;
-    const WfStartFn start = select_wf_start_kernel(c->precise);
+    const WfStartFn start = select_wf_start_kernel(c->precise, rp.tile_list != nullptr);
     const WfTraverseFn traverse = select_wf_traverse_kernel(c->counters, c->dsc.qnodes != nullptr, log);
     const WfShadeFn shade = select_wf_shade_kernel(c->counters, c->precise, log);
     if (!start || !traverse || !shade) return fail(HR_ERR_UNSUPPORTED, "split pipeline: no kernel instantiation for these options (kernel_variants.h)");
@@ -974,10 +1020,11 @@ static int launch_split(hr_ctx *c, const RenderParams &rp, int slot, std::vector
 }
 
 static int launch_seed(hr_ctx *c, const RenderParams &rp, int slot, hipStream_t st) {
-    uint64_t paths = (uint64_t)rp.tiles_x * rp.tiles_y * rp.num_k * 64u;
+    const bool list = rp.tile_list != nullptr;
+    uint64_t paths = (uint64_t)(list ? rp.tile_count : rp.tiles_x * rp.tiles_y) * rp.num_k * 64u;
     uint32_t grid = (uint32_t)std::min<uint64_t>((paths + SEED_COLS - 1) / SEED_COLS, (uint64_t)c->num_cus);
-    const SeedVariant *v = select_seed_kernel(c->seed_mode, c->seed_split, c->seed_prof, rp.rec_lo_off != 0);
-    if (!v) return fail(HR_ERR_UNSUPPORTED, "no seed kernel instantiation for seed_mode %d, seed_split %d, seed_prof %d (kernel_variants.h)", c->seed_mode, c->seed_split, c->seed_prof);
+    const SeedVariant *v = select_seed_kernel(c->seed_mode, c->seed_split, c->seed_prof, rp.rec_lo_off != 0, list);
+    if (!v) return fail(HR_ERR_UNSUPPORTED, "no seed kernel instantiation for seed_mode %d, seed_split %d, seed_prof %d%s (kernel_variants.h)", c->seed_mode, c->seed_split, c->seed_prof, list ? " under a tile mask" : "");
     const bool skip = (c->debug_skip & 2) != 0;
     if (!skip && v->ring && !c->ring) HIP_TRY(hipMalloc((void **)&c->ring, (size_t)c->num_cus * SEED_RING_WORDS_MAX * sizeof(u64)));
     EventPair ev;
@@ -1034,7 +1081,7 @@ enum TraceSide { TRACE_NONE, TRACE_IN_FORCE, TRACE_SPLIT };
 // after the first, and the governor's fields (left at none: the queries launch with the chip to themselves).
 struct LaunchPlan {
     RenderParams rp;
-    uint32_t tiles;   // 4x4-pixel tiles of the target
+    uint32_t tiles;   // 4x4-pixel tiles the launch covers: the region's, or under a tile mask the active ones
     uint32_t batch;   // samplings per launch
     bool split;       // the split pipeline traces (the roulette estimator lives in the megakernel only)
 };
@@ -1046,6 +1093,7 @@ static int plan_launch(hr_ctx *c, uint32_t begin, uint32_t stride, uint32_t batc
     rp.sampling_begin = begin; rp.stride = stride; rp.num_k = batch;
     rp.pad[0] = c->seed_prio;
     p.tiles = rp.tiles_x * rp.tiles_y;
+    if (c->mask_on) { rp.tile_list = c->d_tile_list; rp.tile_count = c->mask_active; p.tiles = c->mask_active; }   // (never with 0 active tiles: hr_render returns before it plans)
     p.split = side == TRACE_SPLIT || (side == TRACE_IN_FORCE && c->trace_mode == 1 && !c->rr_start);
     p.batch = batch ? batch : render_batch(c, p.tiles, p.split);
     int rc = ensure_draws(c, (size_t)p.tiles * p.batch);
@@ -1073,6 +1121,17 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     invalidate_totals(c);
     if (c->precise_opt == 1 && c->rr_start) return fail(HR_ERR_UNSUPPORTED, "hr_render: russian_roulette and precise_shading exclude each other (the roulette estimator has no f64 instantiation)");
     const uint32_t total_k = (s_end - s_begin + stride - 1) / stride;
+    const bool list = c->mask_on;
+    if (list) {
+        // the list forms are rows of their own (kernel_variants.h) and exist for what a product host runs: anything else is refused, as a missing row is
+        const char *what = c->counters ? "option counters" : c->rr_start ? "option russian_roulette" : c->min_waves != 5 ? "debug option min_waves" :
+                           c->seed_mode != 2 ? "a seed_mode other than 2" : c->seed_prof ? "debug option seed_prof" : nullptr;
+        if (what) return fail(HR_ERR_UNSUPPORTED, "hr_render: %s has no kernel form for a tile mask (hr_set_tile_mask(NULL) removes the mask)", what);
+        if (!c->mask_active) {   // nothing is active: nothing to enqueue; the samplings count as issued (hr_noise.samplings), like those of any masked launch
+            if (c->moments) c->moments_n += total_k;
+            return HR_OK;
+        }
+    }
     LaunchPlan plan;
     int rc = plan_launch(c, s_begin, stride, 0, TRACE_IN_FORCE, plan);
     if (rc) return rc;
@@ -1083,8 +1142,10 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     rp.tail_div = c->tail_div;
     rp.pad[2] = (uint32_t)c->debug_skip;
     rp.wg_budget = c->trace_budget;
-    const TraceFn trace = select_trace_kernel(c->counters, c->dsc.qnodes != nullptr, c->rr_start != 0, c->precise, c->min_waves, false);
-    if (!trace) return fail(HR_ERR_UNSUPPORTED, "hr_render: no trace kernel instantiation for these options (kernel_variants.h)");
+    const TraceFn trace = select_trace_kernel(c->counters, c->dsc.qnodes != nullptr, c->rr_start != 0, c->precise, c->min_waves, false, list);
+    if (!trace) return fail(HR_ERR_UNSUPPORTED, "hr_render: no trace kernel instantiation for these options%s (kernel_variants.h)", list ? " under a tile mask" : "");
+    const AccumulateFn accumulate = select_accumulate_kernel(c->moments != nullptr, c->counts != nullptr, list);
+    if (!accumulate) return fail(HR_ERR_UNSUPPORTED, "hr_render: no accumulate kernel instantiation for these options (kernel_variants.h)");
     for (uint32_t done = 0; done < total_k; done += batch) {
         uint32_t nk = std::min(batch, total_k - done);
         rp.sampling_begin = s_begin + done * stride;
@@ -1115,8 +1176,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         // the launch's radiance into the accumulator (the trace kernel left every path's in its record), in the gap in which this
         // stream waits for the next seed kernel anyway
         if (!(c->debug_skip & 16)) {
-            if (c->moments) hipLaunchKernelGGL(accumulate_kernel<true>, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->accum, c->moments);
-            else hipLaunchKernelGGL(accumulate_kernel<false>, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->accum, (double *)nullptr);
+            hipLaunchKernelGGL(accumulate, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->accum, c->moments, c->counts);
             HIP_TRY(hipGetLastError());
             if (c->moments) c->moments_n += nk;
         }
@@ -1126,7 +1186,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->trace_done[slot], c->stream));
         c->trace_pending[slot] = true;
-        c->paths_rendered += (uint64_t)c->RW * c->RH * 4 * nk;
+        c->paths_rendered += (list ? c->mask_pixels : (uint64_t)c->RW * c->RH) * 4 * nk;
         if (c->trace_events.size() >= 64 && c->seed_events.size() == c->trace_events.size()) retire_finished_launches(c);
         if (c->trace_events.size() > 4096) {  // (never reached while launches finish: the host would have to be 4,096 launches ahead)
             if ((rc = sync_all(c))) return rc;
@@ -1140,6 +1200,8 @@ int hr_render_debug(hr_ctx *c, int mode) {
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_render_debug: no scene uploaded");
     if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_render_debug: hr_set_resolution not called");
     if (c->moments_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option moments on (a debug sampling goes into the accumulator without per-sampling values)");
+    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not while a tile mask is set (hr_set_tile_mask)");
+    if (c->counts_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option sample_counts on (a debug sampling goes into the accumulator without being counted)");
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
     RenderParams rp{};
@@ -1449,14 +1511,17 @@ int hr_write_moments(hr_ctx *c, const double *host, uint64_t samplings) {
 // e of every pixel into `img`, and its summary, reduced in a fixed order (the scheme of accumulator_sum_kernel: a fixed grid, every thread its
 // strided pixels in order, lanes and waves in order, the host adds the blocks' partial sums in index order): reproducible run to run.
 // out[block] = {sum of e, max of e, pixels with e > threshold}.
+// CNTS (option "sample_counts" on): n is the PIXEL's own count (every one >= 2: noise_run has checked), not the samplings issued.
 static const unsigned NOISE_BLOCKS = 1024;
+extern "C++" {   // (a template inside the C ABI's block)
+template <bool CNTS>
 __global__ __launch_bounds__(256) void noise_kernel(const double *__restrict__ moments, size_t pixels, uint64_t samplings, double floor, double threshold,
-                                                    double *__restrict__ img, double *__restrict__ out) {
+                                                    double *__restrict__ img, double *__restrict__ out, const uint32_t *__restrict__ counts) {
     double sum = 0.0, mx = 0.0, above = 0.0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
         double m[6];
         for (int k = 0; k < 6; k++) m[k] = moments[i * 6 + k];
-        const double e = hr::noise_pixel_error(m, samplings, floor);
+        const double e = hr::noise_pixel_error(m, CNTS ? (uint64_t)counts[i] : samplings, floor);
         img[i] = e;
         sum += e;
         mx = e > mx ? e : mx;
@@ -1478,20 +1543,55 @@ __global__ __launch_bounds__(256) void noise_kernel(const double *__restrict__ m
         o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
     }
 }
+}  // extern "C++"
+// the smallest and the largest count of a pixel of the region (option "sample_counts") into out[0], out[1]: an estimate needs 2 samplings behind
+// EVERY pixel, and no pixel can have received more samplings than the moments have seen issued
+__global__ __launch_bounds__(256) void counts_min_kernel(const uint32_t *__restrict__ counts, size_t pixels, uint32_t *__restrict__ out) {
+    uint32_t mn = 0xffffffffu, mx = 0u;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t v = counts[i];
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_down((int)mn, off), p = (uint32_t)__shfl_down((int)mx, off);
+        mn = o < mn ? o : mn;
+        mx = p > mx ? p : mx;
+    }
+    if ((threadIdx.x & 63u) == 0u) { atomicMin(out, mn); atomicMax(out + 1, mx); }
+}
+static int counts_cover_an_estimate(hr_ctx *c, const char *who) {
+    const size_t pixels = (size_t)c->RW * c->RH;
+    if (!c->d_select_out) HIP_TRY(hipMalloc((void **)&c->d_select_out, 3 * sizeof(uint32_t)));
+    uint32_t mm[2] = {0xffffffffu, 0u};
+    HIP_TRY(hipMemcpyAsync(c->d_select_out + 1, mm, sizeof mm, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (mm is on the stack)
+    hipLaunchKernelGGL(counts_min_kernel, dim3((unsigned)std::min<size_t>((pixels + 255) / 256, 1024)), dim3(256), 0, c->stream, c->counts, pixels, c->d_select_out + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(mm, c->d_select_out + 1, sizeof mm, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (mm[0] < 2) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), a variance needs 2", who, mm[0]);
+    // counts and moments that do not cover the same samplings (written apart, or one of them replaced by the host): n would be wrong, silently
+    if ((uint64_t)mm[1] > c->moments_n)
+        return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the moments cover %llu (the counts and the moments must cover the same samplings)", who, mm[1], (unsigned long long)c->moments_n);
+    return HR_OK;
+}
 // host_img: the image as well (or NULL); est: the summary (or NULL)
 static int noise_run(hr_ctx *c, const char *who, double floor, double threshold, double *host_img, hr_noise *est) {
     int rc = moments_ready(c, who);
     if (rc) return rc;
     if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "%s: floor must be a positive finite radiance", who);
     if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
-    if (c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
+    if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
     if ((rc = hr_synchronize(c))) return rc;
+    if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;
     const size_t pixels = (size_t)c->RW * c->RH;
     if (!c->noise_img) HIP_TRY(hipMalloc((void **)&c->noise_img, pixels * sizeof(double)));
     double *d = nullptr;
     std::vector<double> h(NOISE_BLOCKS * 3);
     HIP_TRY(hipMalloc((void **)&d, h.size() * sizeof(double)));
-    hipLaunchKernelGGL(noise_kernel, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d);
+    if (c->counts) hipLaunchKernelGGL(noise_kernel<true>, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d, c->counts);
+    else hipLaunchKernelGGL(noise_kernel<false>, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d, (const uint32_t *)nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && host_img) e = hipMemcpyAsync(host_img, c->noise_img, pixels * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -1516,6 +1616,155 @@ int hr_noise_estimate(hr_ctx *c, double floor, double threshold, hr_noise *out) 
 int hr_read_noise_image(hr_ctx *c, double floor, double *host) {
     if (c && !host) return fail(HR_ERR_INVALID, "hr_read_noise_image: null argument");
     return noise_run(c, "hr_read_noise_image", floor, 0.0, host, nullptr);
+}
+
+// ---- option "sample_counts", the tile mask and the selection of tiles (adapt_core.h) ----
+static int counts_ready(hr_ctx *c, const char *who) {
+    if (!c) return fail(HR_ERR_INVALID, "%s: null ctx", who);
+    if (!c->counts_on || !c->counts) return fail(HR_ERR_INVALID, "%s: option sample_counts is off", who);
+    return HR_OK;
+}
+int hr_read_sample_counts(hr_ctx *c, uint32_t *host) {
+    int rc = counts_ready(c, "hr_read_sample_counts");
+    if (rc) return rc;
+    if (!host) return fail(HR_ERR_INVALID, "hr_read_sample_counts: null argument");
+    if ((rc = hr_synchronize(c))) return rc;
+    HIP_TRY(hipMemcpy(host, c->counts, (size_t)c->RW * c->RH * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HR_OK;
+}
+int hr_write_sample_counts(hr_ctx *c, const uint32_t *host) {
+    int rc = counts_ready(c, "hr_write_sample_counts");
+    if (rc) return rc;
+    if (!host) return fail(HR_ERR_INVALID, "hr_write_sample_counts: null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = sync_all(c))) return rc;
+    HIP_TRY(hipMemcpy(c->counts, host, (size_t)c->RW * c->RH * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return HR_OK;
+}
+
+// hr_resolve's first kernel with every pixel's own count: the scale is hr_resolve's expression 1.0f / (float)(count * 4u), which hr_resolve works
+// out on the host, i.e. correctly rounded.  The device's fp32 division is not (the Makefile trades that for speed), so the quotient is taken in
+// f64 and rounded to fp32: the same float as the host's for every count whose odd part is below 2^28 (a quotient 1 / n lies at least
+// 1 / (odd(n) 2^25) of its value away from the midpoint of two floats, and rounding twice can only differ from rounding once within 2^-53).
+// A pixel without samplings is radiance 0, whatever the accumulator holds.
+__global__ void tonemap_gamma_counted_kernel(const float *__restrict__ acc, const uint32_t *__restrict__ counts, float *__restrict__ out, uint32_t n) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = counts[i];
+    if (k) tonemap_gamma(acc[i * 3], acc[i * 3 + 1], acc[i * 3 + 2], (float)(1.0 / (double)(float)(k * 4u)), &out[i * 3]);
+    else tonemap_gamma(0.0f, 0.0f, 0.0f, 0.0f, &out[i * 3]);
+}
+int hr_resolve_counted(hr_ctx *c, uint8_t *host_rgb8) {
+    int rc = counts_ready(c, "hr_resolve_counted");
+    if (rc) return rc;
+    if (!host_rgb8) return fail(HR_ERR_INVALID, "hr_resolve_counted: null argument");
+    if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_resolve_counted: no accumulator");
+    if ((rc = hr_synchronize(c))) return rc;
+    const uint32_t n = c->RW * c->RH;
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    hipLaunchKernelGGL(tonemap_gamma_counted_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->total_valid ? c->accum_total : c->accum, c->counts, c->post_tmp, n);
+    hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->RW, c->RH);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY(hipMemcpyAsync(host_rgb8, c->d_rgb8, (size_t)n * 3, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return drain_events(c);
+}
+
+// the mask's host side from its flags: the count of active tiles and of their in-region pixels
+static void mask_totals(hr_ctx *c) {
+    const uint32_t tx = (c->RW + 3) / 4, ty = (c->RH + 3) / 4;
+    c->mask_active = 0; c->mask_pixels = 0;
+    for (uint32_t y = 0; y < ty; y++)
+        for (uint32_t x = 0; x < tx; x++)
+            if (c->mask[(size_t)y * tx + x]) {
+                c->mask_active++;
+                c->mask_pixels += (uint64_t)std::min(4u, c->RW - 4u * x) * std::min(4u, c->RH - 4u * y);
+            }
+}
+static int mask_buffers(hr_ctx *c, uint32_t tiles) {
+    if (!c->d_tile_list) HIP_TRY(hipMalloc((void **)&c->d_tile_list, (size_t)tiles * sizeof(uint32_t)));
+    if (!c->d_tile_flags) HIP_TRY(hipMalloc((void **)&c->d_tile_flags, (size_t)tiles * sizeof(uint32_t)));
+    if (!c->d_select_out) HIP_TRY(hipMalloc((void **)&c->d_select_out, 3 * sizeof(uint32_t)));
+    return HR_OK;
+}
+int hr_set_tile_mask(hr_ctx *c, const uint8_t *mask) {
+    if (!c) return fail(HR_ERR_INVALID, "hr_set_tile_mask: null ctx");
+    if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_set_tile_mask: hr_set_resolution not called");
+    if (!c->counts_on) return fail(HR_ERR_INVALID, "hr_set_tile_mask: option sample_counts is off (an image whose pixels have unequal counts cannot be resolved without them)");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);   // kernels of an earlier hr_render may still be reading the list
+    if (rc) return rc;
+    if (!mask) return remove_mask(c);
+    const uint32_t tiles = ((c->RW + 3) / 4) * ((c->RH + 3) / 4);
+    if ((rc = mask_buffers(c, tiles))) return rc;
+    std::vector<uint32_t> flags(tiles), list;
+    c->mask.assign(tiles, 0);
+    for (uint32_t t = 0; t < tiles; t++)
+        if (mask[t]) { c->mask[t] = 1; flags[t] = 1u; list.push_back(t); }   // ascending
+    mask_totals(c);
+    HIP_TRY(hipMemcpy(c->d_tile_flags, flags.data(), (size_t)tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!list.empty()) HIP_TRY(hipMemcpy(c->d_tile_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->mask_on = true;
+    return HR_OK;
+}
+int hr_get_tile_mask(hr_ctx *c, uint8_t *mask, uint32_t *active) {
+    if (!c) return fail(HR_ERR_INVALID, "hr_get_tile_mask: null ctx");
+    if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_get_tile_mask: hr_set_resolution not called");
+    const uint32_t tiles = ((c->RW + 3) / 4) * ((c->RH + 3) / 4);
+    if (mask) { if (c->mask_on) memcpy(mask, c->mask.data(), tiles); else memset(mask, 1, tiles); }
+    if (active) *active = c->mask_on ? c->mask_active : tiles;
+    return HR_OK;
+}
+
+// The tile rule on the device: 16 lanes per tile (one per pixel), four tiles per wave; the ballot of a tile's lanes is its flag, ANDed with the
+// flag it had (have_prev: a mask is in force — a tile that went inactive stays inactive).  The ascending compaction of the flags into the list
+// is hipcub's DeviceSelect::Flagged over the tile indices: deterministic, two calls give identical lists.
+__global__ __launch_bounds__(256) void select_tiles_kernel(RenderParams rp, const double *__restrict__ moments, const uint32_t *__restrict__ counts, double floor, double threshold,
+                                                           int have_prev, uint32_t *__restrict__ flags) {
+    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
+    const bool hot = tile < tiles && hr::adapt_pixel_active(rp, tile, pix, moments, counts, floor, threshold);
+    const unsigned long long m = wave_ballot(hot);
+    const bool any = ((m >> (((threadIdx.x & 63u) >> 4) * 16u)) & 0xffffull) != 0ull;
+    if (pix == 0u && tile < tiles) flags[tile] = any && (!have_prev || flags[tile] != 0u) ? 1u : 0u;
+}
+int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active) {
+    int rc = moments_ready(c, "hr_select_tiles");
+    if (rc) return rc;
+    if ((rc = counts_ready(c, "hr_select_tiles"))) return rc;
+    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "hr_select_tiles: floor must be a positive finite radiance");
+    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "hr_select_tiles: threshold must not be negative");
+    if ((rc = hr_synchronize(c))) return rc;   // (also: no kernel is reading the list that is about to be rewritten)
+    if ((rc = counts_cover_an_estimate(c, "hr_select_tiles"))) return rc;
+    RenderParams rp{};
+    target_params(c, rp);
+    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
+    if ((rc = mask_buffers(c, tiles))) return rc;
+    const hipcub::CountingInputIterator<uint32_t> indices(0u);
+    size_t need = 0;
+    HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, need, indices, c->d_tile_flags, c->d_tile_list, c->d_select_out, (int)tiles, c->stream));
+    if (need > c->select_tmp_bytes) {
+        if (c->select_tmp) { HIP_TRY(hipFree(c->select_tmp)); c->select_tmp = nullptr; }
+        c->select_tmp_bytes = 0;
+        HIP_TRY(hipMalloc(&c->select_tmp, std::max<size_t>(need, 16)));
+        c->select_tmp_bytes = std::max<size_t>(need, 16);
+    }
+    hipLaunchKernelGGL(select_tiles_kernel, dim3((tiles + 15) / 16), dim3(256), 0, c->stream, rp, c->moments, c->counts, floor, threshold, c->mask_on ? 1 : 0, c->d_tile_flags);
+    HIP_TRY(hipGetLastError());
+    size_t bytes = c->select_tmp_bytes;
+    HIP_TRY(hipcub::DeviceSelect::Flagged(c->select_tmp, bytes, indices, c->d_tile_flags, c->d_tile_list, c->d_select_out, (int)tiles, c->stream));
+    std::vector<uint32_t> flags(tiles);
+    uint32_t selected = 0;
+    HIP_TRY(hipMemcpyAsync(flags.data(), c->d_tile_flags, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&selected, c->d_select_out, sizeof selected, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->mask.assign(tiles, 0);
+    for (uint32_t t = 0; t < tiles; t++) c->mask[t] = flags[t] ? 1 : 0;
+    mask_totals(c);
+    c->mask_on = true;
+    if (selected != c->mask_active) return fail(HR_ERR_DEVICE, "hr_select_tiles: the compaction kept %u tiles, the flags say %u", selected, c->mask_active);
+    if (active) *active = c->mask_active;
+    return HR_OK;
 }
 
 int hr_get_stats(hr_ctx *c, hr_stats *out) {
@@ -1630,6 +1879,21 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
         if (c->moments_on) return HR_OK;   // already on: the moments gathered so far stay
         if ((rc = alloc_moments(c, c->RW, c->RH))) { (void)free_moments(c); return rc; }
         c->moments_on = true;
+        // the counts are the moments' n: they cover the same samplings, so counts that are already running start over with the moments
+        if (c->counts) { HIP_TRY(hipMemset(c->counts, 0, (size_t)c->RW * c->RH * sizeof(uint32_t))); HIP_TRY(hipStreamSynchronize(nullptr)); }
+        return HR_OK;
+    }
+    if (k == "sample_counts") {   // how many samplings every pixel has received: what a tile mask (hr_set_tile_mask) needs
+        if (value != 0 && value != 1) return fail(HR_ERR_INVALID, "sample_counts must be 0 or 1");
+        if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "sample_counts: hr_set_resolution not called");
+        int rc = sync_all(c);
+        if (rc) return rc;
+        if (value == 0) { c->counts_on = false; if ((rc = remove_mask(c))) return rc; return free_counts(c); }
+        if (c->counts_on) return HR_OK;   // already on: the counts gathered so far stay
+        if ((rc = alloc_counts(c, c->RW, c->RH))) { (void)free_counts(c); return rc; }
+        c->counts_on = true;
+        // ... and moments that are already running start over with the counts (the accumulator stays, as it does when the moments are switched on)
+        if (c->moments) { HIP_TRY(hipMemset(c->moments, 0, (size_t)c->RW * c->RH * 6 * sizeof(double))); HIP_TRY(hipStreamSynchronize(nullptr)); c->moments_n = 0; }
         return HR_OK;
     }
     if (k == "max_tail_gib") {
@@ -1679,6 +1943,7 @@ int hr_set_debug_option(hr_ctx *c, const char *key, double value) {
 int hr_debug_draws(hr_ctx *c, uint32_t sampling, uint32_t first_path, uint32_t num_paths, uint32_t window, uint64_t *host_out) {
     if (!c || !host_out || !num_paths) return fail(HR_ERR_INVALID, "hr_debug_draws: bad argument");
     if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_draws: not while a region is set (hr_set_region)");
+    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_draws: not while a tile mask is set (hr_set_tile_mask)");
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_draws: hr_set_resolution not called");
     if (window == 0 || window > (uint32_t)ISAAC_TAIL) return fail(HR_ERR_INVALID, "window must be in [1,%d]", ISAAC_TAIL);
     if ((uint64_t)first_path + num_paths > (uint64_t)c->W * c->H * 4) return fail(HR_ERR_INVALID, "path range outside the image");
@@ -1700,6 +1965,7 @@ static int path_draws_out(hr_ctx *c, uint32_t sampling, float *host_out, bool re
     // records' twin), re-ordered to pixel-major paths: out[((y*W + x)*4 + sub) * 20 + d]
     if (!c || !host_out) return fail(HR_ERR_INVALID, "%s: bad argument", who);
     if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "%s: not while a region is set (hr_set_region)", who);
+    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "%s: not while a tile mask is set (hr_set_tile_mask)", who);
     if (!c->W) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", who);
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "%s: no scene (lens shape needed)", who);
     if (residuals && !draws_twin(c)) return fail(HR_ERR_UNSUPPORTED, "%s: no residuals are written (needs precise shading in force, seed_mode 2, draw_residuals 1)", who);
@@ -1748,6 +2014,7 @@ int hr_debug_path_log(hr_ctx *c, uint32_t sampling, uint32_t *host_out) {
     // path_advance) — with every path's radiance, ray count and event log written out instead of being accumulated
     if (!c || !host_out) return fail(HR_ERR_INVALID, "hr_debug_path_log: bad argument");
     if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_path_log: not while a region is set (hr_set_region)");
+    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_path_log: not while a tile mask is set (hr_set_tile_mask)");
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_path_log: hr_set_resolution not called");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_path_log: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
@@ -1797,6 +2064,7 @@ int hr_debug_wf_profile(hr_ctx *c, uint32_t sampling, uint32_t num_k, double *ms
     // ms_out[2 s - 1] / ms_out[2 s] = traversal / shading kernel of step s = 1 .. WF_STEPS; counts_out[2 s] / [2 s + 1] = rays / live paths of step s
     if (!c || !ms_out || !counts_out || !num_k) return fail(HR_ERR_INVALID, "hr_debug_wf_profile: bad argument");
     if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_wf_profile: not while a region is set (hr_set_region)");
+    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_wf_profile: not while a tile mask is set (hr_set_tile_mask)");
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_wf_profile: hr_set_resolution not called");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_wf_profile: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
@@ -1828,6 +2096,7 @@ int hr_debug_wf_profile(hr_ctx *c, uint32_t sampling, uint32_t num_k, double *ms
 int hr_debug_intersect(hr_ctx *c, uint32_t n, const float *rays, float *out, int32_t *out_element) {
     if (!c || !rays || !out || !out_element || !n) return fail(HR_ERR_INVALID, "hr_debug_intersect: bad argument");
     if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_intersect: not while a region is set (hr_set_region)");
+    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_intersect: not while a tile mask is set (hr_set_tile_mask)");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_intersect: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
     float *d_rays = nullptr, *d_out = nullptr;
@@ -1851,6 +2120,7 @@ int hr_debug_intersect(hr_ctx *c, uint32_t n, const float *rays, float *out, int
 int hr_debug_trace(hr_ctx *c, uint32_t n, const float *rays, const float *shadow_len, float *out, int32_t *out_element) {
     if (!c || !rays || !out || !out_element || !n) return fail(HR_ERR_INVALID, "hr_debug_trace: bad argument");
     if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: not while a region is set (hr_set_region)");
+    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: not while a tile mask is set (hr_set_tile_mask)");
     if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_trace: no scene uploaded");
     HIP_TRY(hipSetDevice(c->device));
     const TraceDebugFn fn = select_trace_debug_kernel(c->counters, c->dsc.qnodes != nullptr);

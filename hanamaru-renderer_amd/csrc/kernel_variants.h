@@ -19,24 +19,27 @@ static const Row *find_row(const Row (&table)[N], Match match) {
 template <class Row>
 static auto fn_of(const Row *r) -> decltype(r->fn) { return r ? r->fn : nullptr; }   // nullptr: no such row
 
-// ---- trace_kernel<CNT, MINW, QN, RR, LOG, PREC> (trace_kernel.h) ----
+// ---- trace_kernel<CNT, MINW, QN, RR, LOG, PREC, LIST> (trace_kernel.h) ----
 typedef void (*TraceFn)(Scene, RenderParams, float *, Counters *, uint32_t *, uint32_t *);
-struct TraceVariant { bool cnt; int minw; bool qn, rr, log, prec; TraceFn fn; };
+struct TraceVariant { bool cnt; int minw; bool qn, rr, log, prec, list; TraceFn fn; };
 static const TraceVariant TRACE_VARIANTS[] = {
     // fp32 shading: the default (5 waves), the tree of 32-byte nodes, debug option min_waves 4 / 6, the counters build
-    HR_VARIANT(trace_kernel, false, 5, true, false, false, false), HR_VARIANT(trace_kernel, false, 5, false, false, false, false),
-    HR_VARIANT(trace_kernel, false, 4, true, false, false, false), HR_VARIANT(trace_kernel, false, 6, true, false, false, false),
-    HR_VARIANT(trace_kernel, true, 3, true, false, false, false), HR_VARIANT(trace_kernel, true, 3, false, false, false, false),
+    HR_VARIANT(trace_kernel, false, 5, true, false, false, false, false), HR_VARIANT(trace_kernel, false, 5, false, false, false, false, false),
+    HR_VARIANT(trace_kernel, false, 4, true, false, false, false, false), HR_VARIANT(trace_kernel, false, 6, true, false, false, false, false),
+    HR_VARIANT(trace_kernel, true, 3, true, false, false, false, false), HR_VARIANT(trace_kernel, true, 3, false, false, false, false, false),
     // the roulette estimator (option russian_roulette)
-    HR_VARIANT(trace_kernel, false, 5, true, true, false, false), HR_VARIANT(trace_kernel, false, 5, false, true, false, false),
-    HR_VARIANT(trace_kernel, true, 3, true, true, false, false), HR_VARIANT(trace_kernel, true, 3, false, true, false, false),
+    HR_VARIANT(trace_kernel, false, 5, true, true, false, false, false), HR_VARIANT(trace_kernel, false, 5, false, true, false, false, false),
+    HR_VARIANT(trace_kernel, true, 3, true, true, false, false, false), HR_VARIANT(trace_kernel, true, 3, false, true, false, false, false),
     // precise shading (path_advance<.., PREC>): 128 VGPRs, debug option min_waves 6 -> the 96-VGPR form, 4 -> the 168-VGPR form, the counters build
-    HR_VARIANT(trace_kernel, false, 4, true, false, false, true), HR_VARIANT(trace_kernel, false, 4, false, false, false, true),
-    HR_VARIANT(trace_kernel, false, 5, true, false, false, true), HR_VARIANT(trace_kernel, false, 3, true, false, false, true),
-    HR_VARIANT(trace_kernel, true, 3, true, false, false, true), HR_VARIANT(trace_kernel, true, 3, false, false, false, true),
+    HR_VARIANT(trace_kernel, false, 4, true, false, false, true, false), HR_VARIANT(trace_kernel, false, 4, false, false, false, true, false),
+    HR_VARIANT(trace_kernel, false, 5, true, false, false, true, false), HR_VARIANT(trace_kernel, false, 3, true, false, false, true, false),
+    HR_VARIANT(trace_kernel, true, 3, true, false, false, true, false), HR_VARIANT(trace_kernel, true, 3, false, false, false, true, false),
     // the path log (hr_debug_path_log)
-    HR_VARIANT(trace_kernel, false, 3, true, false, true, false), HR_VARIANT(trace_kernel, false, 3, false, false, true, false),
-    HR_VARIANT(trace_kernel, false, 3, true, false, true, true), HR_VARIANT(trace_kernel, false, 3, false, false, true, true),
+    HR_VARIANT(trace_kernel, false, 3, true, false, true, false, false), HR_VARIANT(trace_kernel, false, 3, false, false, true, false, false),
+    HR_VARIANT(trace_kernel, false, 3, true, false, true, true, false), HR_VARIANT(trace_kernel, false, 3, false, false, true, true, false),
+    // a tile mask is in force (hr_set_tile_mask / hr_select_tiles, adapt_core.h): the default fp32 and precise forms over the active-tile list
+    HR_VARIANT(trace_kernel, false, 5, true, false, false, false, true), HR_VARIANT(trace_kernel, false, 5, false, false, false, false, true),
+    HR_VARIANT(trace_kernel, false, 4, true, false, false, true, true), HR_VARIANT(trace_kernel, false, 4, false, false, false, true, true),
 };
 // counters / qn (the scene has quantised nodes) / rr (rr_start != 0) / precise / min_waves as the context has them; log: the path log's launch.
 //   * the log builds are one occupancy form (MINW 3) and know neither counters nor roulette
@@ -44,7 +47,8 @@ static const TraceVariant TRACE_VARIANTS[] = {
 //   * counters builds are MINW 3 whatever min_waves says
 //   * precise: min_waves 6 -> MINW 5, 4 -> MINW 3, otherwise MINW 4 — with quantised nodes only; without them MINW 4
 //   * fp32: min_waves is MINW — with quantised nodes only; without them <false, 5, false>
-static TraceFn select_trace_kernel(bool counters, bool qn, bool rr, bool precise, int min_waves, bool log) {
+//   * list (a tile mask is in force): the default occupancy forms only — no counters, roulette, path log, or min_waves other than 5
+static TraceFn select_trace_kernel(bool counters, bool qn, bool rr, bool precise, int min_waves, bool log, bool list = false) {
     bool cnt = counters, prec = precise;
     int minw;
     if (log) { cnt = false; rr = false; minw = 3; }
@@ -52,15 +56,17 @@ static TraceFn select_trace_kernel(bool counters, bool qn, bool rr, bool precise
     else if (cnt) minw = 3;
     else if (prec) minw = !qn ? 4 : min_waves == 6 ? 5 : min_waves == 4 ? 3 : 4;
     else minw = !qn ? 5 : min_waves == 4 ? 4 : min_waves == 6 ? 6 : 5;
-    return fn_of(find_row(TRACE_VARIANTS, [&](const TraceVariant &r) { return r.cnt == cnt && r.minw == minw && r.qn == qn && r.rr == rr && r.log == log && r.prec == prec; }));
+    if (list && (cnt || rr || log || min_waves != 5)) return nullptr;
+    return fn_of(find_row(TRACE_VARIANTS, [&](const TraceVariant &r) { return r.cnt == cnt && r.minw == minw && r.qn == qn && r.rr == rr && r.log == log && r.prec == prec && r.list == list; }));
 }
 
 // ---- the split pipeline (wf_kernels.h) ----
 typedef void (*WfStartFn)(Scene, RenderParams, float *, WfQueues);
-struct WfStartVariant { bool prec; WfStartFn fn; };
-static const WfStartVariant WF_START_VARIANTS[] = {HR_VARIANT(wf_start_kernel, false), HR_VARIANT(wf_start_kernel, true)};
-static WfStartFn select_wf_start_kernel(bool precise) {
-    return fn_of(find_row(WF_START_VARIANTS, [&](const WfStartVariant &r) { return r.prec == precise; }));
+struct WfStartVariant { bool prec, list; WfStartFn fn; };   // list: a tile mask is in force (adapt_core.h)
+static const WfStartVariant WF_START_VARIANTS[] = {HR_VARIANT(wf_start_kernel, false, false), HR_VARIANT(wf_start_kernel, true, false),
+                                                   HR_VARIANT(wf_start_kernel, false, true), HR_VARIANT(wf_start_kernel, true, true)};
+static WfStartFn select_wf_start_kernel(bool precise, bool list = false) {
+    return fn_of(find_row(WF_START_VARIANTS, [&](const WfStartVariant &r) { return r.prec == precise && r.list == list; }));
 }
 
 typedef void (*WfTraverseFn)(Scene, RenderParams, WfQueues, uint32_t, Counters *);
@@ -101,8 +107,9 @@ static TraceDebugFn select_trace_debug_kernel(bool counters, bool qn) {
 // ---- the seed kernels (seed_kernels.h) ----
 // Every one takes (rp, lens_shape, [ring,] recs, ovf, win, counters) and SEED_LDS_BYTES of dynamic LDS; `ring`: it has the ring argument.
 // key: mode = option seed_mode; split = init blocks of the producer waves (seed_pc_kernel only, else 0); prof = the phase-timing build (a
-// number for seed_ps_kernel, else 0 / 1); lo = the launch writes the draws' residuals into the records' twin (seed_seg_kernel only).
-struct SeedVariant { int mode, split, prof; bool lo; const void *fn; uint32_t threads; bool ring; };
+// number for seed_ps_kernel, else 0 / 1); lo = the launch writes the draws' residuals into the records' twin (seed_seg_kernel only);
+// list = a tile mask is in force (adapt_core.h; the last member: seed_seg_kernel without its timing build only).
+struct SeedVariant { int mode, split, prof; bool lo; const void *fn; uint32_t threads; bool ring; bool list = false; };
 static const SeedVariant SEED_VARIANTS[] = {
     {0, 0, 0, false, (const void *)seed_isaac64_kernel, 64 * SEED_WAVES, false},
     {1, 8, 0, false, (const void *)seed_pc_kernel<8>, 256, true},
@@ -117,6 +124,8 @@ static const SeedVariant SEED_VARIANTS[] = {
     {2, 0, 1, false, (const void *)seed_seg_kernel<true, false>, 256, true},
     {2, 0, 0, true, (const void *)seed_seg_kernel<false, true>, 256, true},
     {2, 0, 1, true, (const void *)seed_seg_kernel<true, true>, 256, true},
+    {2, 0, 0, false, (const void *)seed_seg_kernel<false, false, true>, 256, true, true},
+    {2, 0, 0, true, (const void *)seed_seg_kernel<false, true, true>, 256, true, true},
 #if defined(HR_EXPERIMENTS)
     {3, 0, 0, false, (const void *)seed_ps_kernel<0>, 256, true},
     {3, 0, 1, false, (const void *)seed_ps_kernel<1>, 256, true},
@@ -131,12 +140,24 @@ static const SeedVariant SEED_VARIANTS[] = {
 //   * the ring kernel (mode 1): its phase-timing build exists for splits 16 and 20 only and falls back to 16
 //   * seed_ps_kernel (mode 3) has timing builds 1 .. 3, any other seed_prof is its plain build; everywhere else seed_prof is on / off
 //   * the fused kernel (mode 0) has no timing build
-static const SeedVariant *select_seed_kernel(int seed_mode, int seed_split, int seed_prof, bool twin) {
+//   * list (a tile mask is in force): the three-run kernel (mode 2) without phase timing, nothing else
+static const SeedVariant *select_seed_kernel(int seed_mode, int seed_split, int seed_prof, bool twin, bool list = false) {
     int split = 0, prof = seed_prof ? 1 : 0;
     bool lo = false;
     if (seed_mode == 2) lo = twin;
     else if (seed_mode == 1) split = prof ? (seed_split == 20 ? 20 : 16) : seed_split;
     else if (seed_mode == 3) prof = seed_prof >= 1 && seed_prof <= 3 ? seed_prof : 0;
     else if (seed_mode == 0) prof = 0;
-    return find_row(SEED_VARIANTS, [&](const SeedVariant &r) { return r.mode == seed_mode && r.split == split && r.prof == prof && r.lo == lo; });
+    return find_row(SEED_VARIANTS, [&](const SeedVariant &r) { return r.mode == seed_mode && r.split == split && r.prof == prof && r.lo == lo && r.list == list; });
+}
+
+// ---- accumulate_kernel<MOM, CNTS, LIST> (trace_kernel.h): a launch's radiance into the accumulator ----
+typedef void (*AccumulateFn)(RenderParams, const float *, float *, double *, uint32_t *);
+struct AccumulateVariant { bool mom, cnts, list; AccumulateFn fn; };
+static const AccumulateVariant ACCUMULATE_VARIANTS[] = {HR_VARIANT(accumulate_kernel, false, false, false), HR_VARIANT(accumulate_kernel, true, false, false),
+                                                        HR_VARIANT(accumulate_kernel, false, true, false),  HR_VARIANT(accumulate_kernel, true, true, false),
+                                                        HR_VARIANT(accumulate_kernel, false, true, true),   HR_VARIANT(accumulate_kernel, true, true, true)};
+// moments / sample_counts as the options have them; list: a tile mask is in force (it needs the counts: no <.., false, true> row)
+static AccumulateFn select_accumulate_kernel(bool moments, bool counts, bool list) {
+    return fn_of(find_row(ACCUMULATE_VARIANTS, [&](const AccumulateVariant &r) { return r.mom == moments && r.cnts == counts && r.list == list; }));
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "adapt_core.h"
 #include "device_scene.h"
 #include "isaac_core.h"
 
@@ -82,7 +83,7 @@ struct GlobalWindow {
     __device__ __forceinline__ void put(int step, u64 v) { col[(255 - step) * 40] = v; }
     __device__ __forceinline__ u64 ld(int k) const { return __hip_atomic_load(col + k * 40, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
-template <class Mem, bool LO = false>
+template <class Mem, bool LO = false, bool LIST = false>
 __device__ __forceinline__ void seed_fixup_wave(const RenderParams &rp, int lens_shape, Mem m, uint32_t lane40, bool lane_on, const uint32_t *list, uint32_t count,
                                                 u64 *win, float *recs, Counters *cnt) {
     if (count > rp.ovf_cap) {
@@ -100,7 +101,7 @@ __device__ __forceinline__ void seed_fixup_wave(const RenderParams &rp, int lens
         const uint32_t item = pid >> 6, j = pid & 63u;
         const uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, launch_tile<LIST>(rp, tile), j, px, py, sub);
         u64 s, t;
         path_seed_words(rp.width, rp.height, px, py, sub, s, t);
         if (lane_on) {
@@ -477,7 +478,7 @@ struct SegRegs {
         if (l.on) isaac_init_run<SEG_NBLK>(m, st16);
     }
 };
-template <bool PROF, bool LO>
+template <bool PROF, bool LO, bool LIST>
 __device__ __forceinline__ void seed_seg_consumer(const RenderParams &rp, int lens_shape, const PcRange &r, unsigned char *smem, uint32_t lane, uint32_t half,
                                                   float *__restrict__ recs, uint32_t *__restrict__ ovf, u64 *__restrict__ win, Counters *cnt) {
     uint32_t *ovf_list = ovf + (size_t)(blockIdx.x * 2u + half) * rp.ovf_cap;
@@ -500,7 +501,7 @@ __device__ __forceinline__ void seed_seg_consumer(const RenderParams &rp, int le
         const uint32_t item = (uint32_t)((in_range ? pid : r.paths - 1) >> 6), j = (uint32_t)((in_range ? pid : r.paths - 1) & 63u);
         uint32_t tile = item / rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_frame_pixel(rp, tile, j, px, py, sub);
+        tile_lane_frame_pixel(rp, launch_tile<LIST>(rp, tile), j, px, py, sub);
         const bool valid = in_range && px < rp.width && py < rp.height;
         HR_STAMP(0);
         if (PROF) { __builtin_amdgcn_s_waitcnt(0x0F70); HR_STAMP(1); }   // vmcnt(0)
@@ -526,8 +527,9 @@ __device__ __forceinline__ void seed_seg_consumer(const RenderParams &rp, int le
     if (PROF && lane == 0)
         for (int i = 0; i < 8; i++) atomicAdd(&cnt->seed_phase[i], pc[i]);
     const bool lane_on = lane < (uint32_t)SEED_LANES;
-    seed_fixup_wave<LdsHalfMem, LO>(rp, lens_shape, m, colr, lane_on, ovf_list, ovf_count, win + (size_t)(blockIdx.x * 2u + half) * SEED_WIN_WORDS, recs, cnt);
+    seed_fixup_wave<LdsHalfMem, LO, LIST>(rp, lens_shape, m, colr, lane_on, ovf_list, ovf_count, win + (size_t)(blockIdx.x * 2u + half) * SEED_WIN_WORDS, recs, cnt);
 }
+template <bool LIST>
 __device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const PcRange &r, unsigned char *smem, uint32_t lane, uint32_t half, const uint32_t pprio) {
     const IsaacWarm warm = isaac_warm();
     const SegLane sl = seg_lane(false, lane);
@@ -547,7 +549,7 @@ __device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const 
             const uint32_t item = (uint32_t)(ppid >> 6), j = (uint32_t)(ppid & 63u);
             uint32_t tile = item / rp.num_k, k = item - tile * rp.num_k;
             uint32_t px, py, sub;
-            tile_lane_frame_pixel(rp, tile, j, px, py, sub);
+            tile_lane_frame_pixel(rp, launch_tile<LIST>(rp, tile), j, px, py, sub);
             bool pvalid = px < rp.width && py < rp.height;
             u64 s, t;
             path_seed_words(rp.width, rp.height, pvalid ? px : 0u, pvalid ? py : 0u, sub, s, t);
@@ -577,7 +579,9 @@ __device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const 
     }
 }
 // LO: the records' twin with the draws' residuals is written too (precise shading, RenderParams::rec_lo_off)
-template <bool PROF = false, bool LO = false>
+// LIST: a tile mask is in force (adapt_core.h) — the launch's paths are those of the active tiles (pid = (dense tile * num_k + k) * 64 + j, as ever);
+// a lane's pixel, i.e. its seed, comes from the region's tile behind the dense index, one lookup where tile_lane_frame_pixel is fed
+template <bool PROF = false, bool LO = false, bool LIST = false>
 __global__ __launch_bounds__(256) void seed_seg_kernel(RenderParams rp, int lens_shape, u64 *__restrict__ ring, float *__restrict__ recs,
                                                        uint32_t *__restrict__ ovf, u64 *__restrict__ win, Counters *cnt) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -592,14 +596,14 @@ __global__ __launch_bounds__(256) void seed_seg_kernel(RenderParams rp, int lens
         default: __builtin_amdgcn_s_setprio(3); break;
     }
     PcRange r;
-    r.paths = (uint64_t)rp.tiles_x * rp.tiles_y * rp.num_k * 64u;
+    r.paths = (uint64_t)launch_tiles<LIST>(rp) * rp.num_k * 64u;
     const uint64_t groups = (r.paths + SEED_COLS - 1) / SEED_COLS;
     r.G0 = groups * blockIdx.x / gridDim.x; r.G1 = groups * (blockIdx.x + 1) / gridDim.x;
     r.first_path = r.G0 * SEED_COLS; r.end_path = r.G1 * SEED_COLS < r.paths ? r.G1 * SEED_COLS : r.paths;
     r.ring_wg = ring + (size_t)blockIdx.x * SEED_RING_WORDS_MAX;
-    if (consumer) seed_seg_consumer<PROF, LO>(rp, lens_shape, r, smem, lane, half, recs, ovf, win, cnt);
+    if (consumer) seed_seg_consumer<PROF, LO, LIST>(rp, lens_shape, r, smem, lane, half, recs, ovf, win, cnt);
     else {
-        seed_seg_producer(rp, r, smem, lane, half, pprio);
+        seed_seg_producer<LIST>(rp, r, smem, lane, half, pprio);
         seed_gov_end(rp, wave == 2u && lane == 0u);
     }
 }

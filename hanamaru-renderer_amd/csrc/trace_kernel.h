@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "adapt_core.h"
 #include "device_scene.h"
 #include "isaac_core.h"
 #include "pt_core.h"
@@ -119,7 +120,9 @@ __device__ __forceinline__ void flush_counters(Counters *cnt, uint32_t lane, uin
 // words per path, indexed ((y * W + x) * 4 + sub-sample) for the launch's first sampling: {r, g, b (float bits), rays, ev low, ev high, ev9, hash}.
 // The same kernel, the same path_advance: what is logged is what hr_render computes.
 // PREC (option precise_shading): path_advance shades in f64 (prec_core.h); instantiated for 128 VGPRs (MINW 4).
-template <bool CNT, int MINW, bool QN, bool RR = false, bool LOG = false, bool PREC = false>
+// LIST (a tile mask is in force, adapt_core.h): the launch's tiles are the dense indices of RenderParams::tile_list; `cur_tile` / `p.tile` stay dense
+// (records, work units, the finer tail), the region's tile is looked up once per work unit and only feeds the lanes' pixels.
+template <bool CNT, int MINW, bool QN, bool RR = false, bool LOG = false, bool PREC = false, bool LIST = false>
 __global__ __launch_bounds__(64 * TRACE_WAVES, MINW) void trace_kernel(Scene sc, RenderParams rp, float *recs, Counters *cnt, uint32_t *tile_counter, uint32_t *plog = nullptr) {
     // the wave budget (device_scene.h GovDev::budget; debug option trace_budget pins it): surplus workgroups leave before they touch anything
     // ONE budget per launch: the governor of the launch before may store a new one while this launch's workgroups are still starting, so the
@@ -138,8 +141,9 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, MINW) void trace_kernel(Scene sc,
         }
         if (budget && blockIdx.x >= budget) return;
     }
+    static_assert(!(LIST && (LOG || RR)), "the path log and the roulette hash take a path's pixel from its tile index: no list form");
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
+    const uint32_t tiles = launch_tiles<LIST>(rp);
     LaneCounters lc = {0, 0, 0, 0, 0, 0};
     uint32_t npaths = 0;
     WaveStats ws = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}, 0};
@@ -151,6 +155,7 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, MINW) void trace_kernel(Scene sc,
     uint32_t total = 0, cur_k0 = 0;          // wave-uniform: paths in the current unit (slot q = (k - cur_k0) * 64 + j), its first sampling
     const size_t tile_stride = (size_t)rp.num_k * REC_ITEM_FLOATS;   // floats of hand-off records per tile
     uint32_t cur_tile = 0, next = 0;          // wave-uniform: the tile of the unit being handed out and its queue head
+    uint32_t cur_ptile = 0;                   // LIST: the region's tile behind cur_tile (wave-uniform; the other forms never touch it)
     bool exhausted = false;
     Path p;
     p.q = PATH_IDLE;
@@ -222,12 +227,13 @@ __global__ __launch_bounds__(64 * TRACE_WAVES, MINW) void trace_kernel(Scene sc,
                     total = 64u;
                     next = 0;
                 }
+                if (LIST && !exhausted) cur_ptile = launch_tile<true>(rp, cur_tile);
             }
             if (next < total) {
                 uint32_t q = next + lane_rank(idle);
                 if (p.q == PATH_IDLE && q < total) {
                     uint32_t k = cur_k0 + (q >> 6), j = q & 63u, px, py, sub;
-                    tile_lane_frame_pixel(rp, cur_tile, j, px, py, sub);
+                    tile_lane_frame_pixel(rp, LIST ? cur_ptile : cur_tile, j, px, py, sub);
                     if (px < rp.width && py < rp.height) {
                         p.q = (k << 6) | j;   // slot inside the tile's batch (bits 0-5: lane of the tile -> pixel, sub-sample)
                         p.tile = cur_tile;
@@ -267,12 +273,16 @@ __device__ __forceinline__ float path_radiance_in(float x) { return x == x ? fmi
 // pixel), S1 += (double)x_k, S2 += (double)x_k^2 (the product of two fp32 values is exact in f64), one sampling at a time in the order rendered,
 // from the values in the buffer: the lane of sub-sample 0 loads the pixel's six doubles, runs the loop, stores them — the moments do not depend
 // on how samplings are cut into launches.  moments[reg_h][reg_w][6] = {S1r, S1g, S1b, S2r, S2g, S2b}.  No clamp: |v| <= 1e30, x^2 <= 1.6e61.
-template <bool MOM>
-__global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const float *__restrict__ recs, float *__restrict__ accum, double *__restrict__ moments) {
+// CNTS (option "sample_counts"): the lane that adds a pixel's sum also adds the launch's samplings to the pixel's count,
+// counts[reg_h][reg_w] — accumulator and moments come out bit for bit.  LIST (a tile mask, adapt_core.h): one wave per ACTIVE tile; `tile` is the
+// dense index the records are addressed by, the pixels are those of the region's tile behind it — no other pixel is touched.
+template <bool MOM, bool CNTS = false, bool LIST = false>
+__global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const float *__restrict__ recs, float *__restrict__ accum, double *__restrict__ moments,
+                                                             uint32_t *__restrict__ counts) {
     const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (tile >= rp.tiles_x * rp.tiles_y) return;
+    if (tile >= launch_tiles<LIST>(rp)) return;
     uint32_t px, py, sub;
-    tile_lane_pixel(rp, tile, lane, px, py, sub);
+    tile_lane_pixel(rp, launch_tile<LIST>(rp, tile), lane, px, py, sub);
     const bool valid = rp_in_region(rp, px, py);      // (lanes beyond the region's edge: their records hold nothing of the region)
     const f4 *src = reinterpret_cast<const f4 *>(recs + (size_t)tile * rp.num_k * REC_ITEM_FLOATS) + lane;
     float r = 0.0f, g = 0.0f, b = 0.0f;
@@ -300,6 +310,7 @@ __global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const 
         float *dst = accum + ((size_t)py * rp_reg_w(rp) + px) * 3;
         dst[0] += r; dst[1] += g; dst[2] += b;
         if (MOM) for (int i = 0; i < 6; i++) mom[i] = m[i];
+        if (CNTS) counts[(size_t)py * rp_reg_w(rp) + px] += rp.num_k;
     }
 }
 

@@ -57,7 +57,8 @@ __device__ __forceinline__ uint32_t wave_scan_inclusive(uint32_t v, uint32_t lan
 
 // one wave per item (tile x sampling of the launch = 64 paths), lane j = (pixel of the tile, sub-sample); the waves of sub-queue k take its
 // items k, k + 64, ... in turn
-template <bool PREC>
+// LIST (a tile mask, adapt_core.h): the items are those of the ACTIVE tiles; `tile` (records, path ids) stays the dense index, the pixel comes from the list
+template <bool PREC, bool LIST = false>
 __global__ __launch_bounds__(256) void wf_start_kernel(Scene sc, RenderParams rp, float *recs, WfQueues q) {
     const uint32_t lane = threadIdx.x & 63u;
     // the governor (device_scene.h GovDev): the launch's trace side starts here — its first thread stamps the start, records the level and
@@ -67,14 +68,14 @@ __global__ __launch_bounds__(256) void wf_start_kernel(Scene sc, RenderParams rp
         rp.gov->lvl[1][rp.gov_slot] = (uint32_t)__hip_atomic_load(&rp.gov->level, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         rp.gov->bud[rp.gov_slot] = (rp.wg_budget ? rp.wg_budget : __hip_atomic_load(&rp.gov->budget, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u;
     }
-    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u, items = rp.tiles_x * rp.tiles_y * rp.num_k;
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u, items = launch_tiles<LIST>(rp) * rp.num_k;
     const uint32_t k = w % WF_SUBQ, per = waves / WF_SUBQ;     // (the grid is a multiple of WF_SUBQ waves)
     WfCounts *cn = q.counts + (size_t)1 * WF_SUBQ + k;
     const uint32_t rbase0 = k * q.cap_rays, pbase0 = k * q.cap_paths;
     for (uint32_t item = k + (w / WF_SUBQ) * WF_SUBQ; item < items; item += per * WF_SUBQ) {
         const uint32_t tile = item / rp.num_k, ks = item - tile * rp.num_k;
         uint32_t px, py, sub;
-        tile_lane_frame_pixel(rp, tile, lane, px, py, sub);
+        tile_lane_frame_pixel(rp, launch_tile<LIST>(rp, tile), lane, px, py, sub);
         const bool valid = px < rp.width && py < rp.height;
         Path p;
         p.q = (ks << 6) | lane;

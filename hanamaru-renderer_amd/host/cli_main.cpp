@@ -7,7 +7,9 @@
 // the samplings that are missing — SURVEY.md §8f rank 3; the reference has no resumable state), --region X,Y,W,H (render the
 // window [X, X+W) x [Y, Y+H) of the -w x -h frame, bit for bit the frame's pixels there: hr_set_region; the images are W x H),
 // --noise-target E / --noise-floor F / --noise-check N / --noise-image FILE (option "moments": stop when the mean relative standard error of
-// the pixels is <= E; hr_noise_estimate — the reference stops on a sampling count or the clock only).
+// the pixels is <= E; hr_noise_estimate — the reference stops on a sampling count or the clock only),
+// --adaptive E / --sample-image FILE (options "moments" + "sample_counts": after a uniform first phase only the 4x4 tiles that still hold a pixel
+// with a relative standard error above E are rendered on; hr_select_tiles, hr_resolve_counted).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -77,6 +79,14 @@ static void usage(const char *prog) {
            "        --noise-floor F radiance below which a pixel's error is judged absolutely instead of relatively (default 0.01; > 0)\n"
            "        --noise-check N ask every N samplings (default 64, rounded up to whole launches): the question waits for the launches\n"
            "                        in flight, so it is asked rarely\n"
+           "        --adaptive E    adaptive sampling: render uniformly until the first check (--noise-check, default 64 samplings), then at every\n"
+           "                        check keep only the 4x4-pixel tiles that hold a pixel whose relative standard error e is above E, and stop\n"
+           "                        when no tile is left, or at -s / -t, whichever comes first.  Every check prints a line \"adaptive: samplings=\n"
+           "                        active= tiles=\".  The images are resolved with every pixel's own sampling count.  Choosing the tiles by the\n"
+           "                        samples that form the estimate biases the image slightly; the uniform first phase keeps that small.\n"
+           "                        One device only; not together with --noise-target (two stop rules).\n"
+           "        --sample-image FILE.png\n"
+           "                        write the per-pixel sampling counts as 8-bit grey, count / largest count (one device only)\n"
            "        --noise-image FILE.png\n"
            "                        write an 8-bit grey map of min(1, e / E) at the end of the render (E = the target, or 0.05 without one)\n",
            prog);
@@ -92,7 +102,9 @@ int main(int argc, char **argv) {
     int inflight = 8;   // launches enqueued ahead of the one being reported
     bool debug = false;
     int precise = -1;    // option precise_shading: -1 = the library's automatic choice
-    std::string region_arg, noise_png;
+    std::string region_arg, noise_png, sample_png;
+    bool have_adaptive = false;
+    double adaptive_e = 0.0;
     bool have_target = false;
     double noise_target = 0.0, noise_floor = 0.01;
     long long noise_check = 64;
@@ -141,6 +153,11 @@ int main(int argc, char **argv) {
             noise_check = strtoll(t, &e, 10);
             if (e == t || *e || noise_check < 1 || noise_check > 0x7fffffffll) { fprintf(stderr, "--noise-check must be a whole number of samplings, at least 1, not '%s'.\n", t); return 1; }
         } else if (a == "--noise-image") noise_png = val("noise-image");
+        else if (a == "--adaptive") {
+            if (!number("--adaptive", val("adaptive"), &adaptive_e)) return 1;
+            if (!(adaptive_e > 0.0)) { fprintf(stderr, "--adaptive must be positive.\n"); return 1; }
+            have_adaptive = true;
+        } else if (a == "--sample-image") sample_png = val("sample-image");
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -148,9 +165,20 @@ int main(int argc, char **argv) {
     if (inflight < 1) { fprintf(stderr, "--inflight must be at least 1.\n"); return 1; }
     if (width == 0 || height == 0) { fprintf(stderr, "width and height must be positive.\n"); return 1; }
     if (gpus < 1) { fprintf(stderr, "--gpus must be at least 1.\n"); return 1; }
-    const bool moments = have_target || !noise_png.empty();   // hr_set_option "moments"
+    const bool counts = have_adaptive || !sample_png.empty();   // hr_set_option "sample_counts"
+    if (counts) {
+        size_t ids = gpu_ids.empty() ? 0 : 1;
+        for (char ch : gpu_ids) ids += ch == ',';
+        if (gpus > 1 || ids > 1) {
+            fprintf(stderr, "--adaptive / --sample-image render on one device: the library can shard an adaptive render (masks and additive counts), this program's device loop does not.\n");
+            return 1;
+        }
+        if (have_adaptive && have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
+        if (debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
+    }
+    const bool moments = have_target || !noise_png.empty() || have_adaptive;   // hr_set_option "moments"
     if (moments && debug) { fprintf(stderr, "--noise-target / --noise-image cannot be combined with --debug (the debug renderer has no samplings to measure).\n"); return 1; }
-    const double noise_e = have_target && noise_target > 0.0 ? noise_target : (have_target ? 0.0 : 0.05);   // the threshold of "above" and of the grey map
+    const double noise_e = have_adaptive ? adaptive_e : have_target && noise_target > 0.0 ? noise_target : (have_target ? 0.0 : 0.05);   // the threshold of "above" and of the grey map
     // --region X,Y,W,H: four unsigned integers, a non-empty window inside the frame (hr_set_region's rule, checked before any device is opened)
     uint32_t region[4] = {0, 0, width, height};
     bool has_region = false;
@@ -214,6 +242,7 @@ int main(int argc, char **argv) {
         if (has_region) CHECK_HR(hr_set_region(ctxs[r], region[0], region[1], out_w, out_h));
         if (precise >= 0) CHECK_HR(hr_set_option(ctxs[r], "precise_shading", (double)precise));
         if (moments) CHECK_HR(hr_set_option(ctxs[r], "moments", 1.0));
+        if (counts) CHECK_HR(hr_set_option(ctxs[r], "sample_counts", 1.0));
     }
     hr_ctx *ctx = ctxs[0];
     if (ndev > 1) tee("devices: %u.", ndev);
@@ -244,6 +273,7 @@ int main(int argc, char **argv) {
     };
     // host-side sum: device 0 resolves the total from its accumulator, then gets its own partial sums back
     auto resolve = [&](uint32_t s, uint8_t *out) -> int {
+        if (have_adaptive) return hr_resolve_counted(ctx, out);   // every pixel with its own count (one device: checked with the flags)
         if (!host_sum) return hr_resolve(ctx, s, out);
         if (hr_read_accumulator(ctx, part.data()) != 0 || hr_write_accumulator(ctx, sum_acc.data()) != 0) return 1;
         int rc = hr_resolve(ctx, s, out);
@@ -312,6 +342,8 @@ int main(int argc, char **argv) {
     const uint32_t CKPT_MAGIC = 0x32415248u;          // "HRA2"
     const uint32_t CKPT_REGION_MAGIC = 0x32525248u;   // "HRR2"
     const uint32_t CKPT_MOMENTS_MAGIC = 0x534d5248u;  // "HRMS": the trailer behind the accumulator of a render with moments on
+    const uint32_t CKPT_COUNTS_MAGIC = 0x43535248u;   // "HRSC": the trailer behind that of a render with sample counts on — w*h uint32
+    bool resumed_counts = false;                      // --resume restored per-pixel counts: the tiles are chosen again before anything is rendered
     uint32_t scene_hash = 2166136261u;
     for (char ch : scene_name) scene_hash = (scene_hash ^ (uint8_t)ch) * 16777619u;
     if (!ckpt_in.empty()) {
@@ -339,18 +371,40 @@ int main(int argc, char **argv) {
         uint64_t mom_n = 0;
         std::vector<double> mom;
         bool have_mom = false;
-        if (ok && moments && fread(&mmagic, 4, 1, f) == 1 && mmagic == CKPT_MOMENTS_MAGIC) {
+        std::vector<uint32_t> cnt;
+        if (ok && (moments || counts) && fread(&mmagic, 4, 1, f) == 1 && mmagic == CKPT_MOMENTS_MAGIC) {
             mom.resize((size_t)out_w * out_h * 6);
             have_mom = fread(&mom_n, 8, 1, f) == 1 && fread(mom.data(), sizeof(double), mom.size(), f) == mom.size();
+            if (have_mom && fread(&mmagic, 4, 1, f) != 1) mmagic = 0;   // what follows the moments
+            have_mom = have_mom && moments;
+        }
+        if (ok && counts) {
+            // {"HRSC", w*h uint32}; a file without it was rendered uniformly: every pixel has received all of its samplings
+            cnt.assign((size_t)out_w * out_h, hdr[3]);
+            if (mmagic == CKPT_COUNTS_MAGIC) {
+                resumed_counts = fread(cnt.data(), sizeof(uint32_t), cnt.size(), f) == cnt.size();
+                ok = resumed_counts;
+            }
         }
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot resume from %s (missing, wrong magic, resolution or scene)\n", ckpt_in.c_str()); return 1; }
+        if (have_adaptive && !have_mom) {
+            fprintf(stderr, "--resume %s with --adaptive: the checkpoint holds no sample moments (it was written without --adaptive / --noise-target / --noise-image), "
+                            "so the noise of its %u samplings cannot be known; resume without --adaptive, or render again with it.\n", ckpt_in.c_str(), hdr[3]);
+            return 1;
+        }
+        if (have_adaptive && !resumed_counts && mom_n != hdr[3]) {
+            fprintf(stderr, "--resume %s with --adaptive: its sample moments cover %llu of its %u samplings and it holds no per-pixel counts, "
+                            "so the noise of its pixels cannot be known; resume without --adaptive, or render again with it.\n", ckpt_in.c_str(), (unsigned long long)mom_n, hdr[3]);
+            return 1;
+        }
         if (have_target && !have_mom) {
             fprintf(stderr, "--resume %s with --noise-target: the checkpoint holds no sample moments (it was written without --noise-target / --noise-image), "
                             "so the noise of its %u samplings cannot be known; resume without --noise-target, or render again with it.\n", ckpt_in.c_str(), hdr[3]);
             return 1;
         }
         CHECK_HR(hr_write_accumulator(ctx, acc.data()));
+        if (counts) CHECK_HR(hr_write_sample_counts(ctx, cnt.data()));
         if (have_mom) CHECK_HR(hr_write_moments(ctx, mom.data(), mom_n));
         else if (moments) printf("the checkpoint holds no sample moments: the noise image covers the samplings rendered from here on\n");
         first = hdr[3] + 1;
@@ -451,11 +505,17 @@ int main(int argc, char **argv) {
     const size_t depth = interval <= 0.0 ? 1 : (size_t)inflight;
     // --noise-target: nothing is issued beyond the sampling at which the next question is due (whole launches: the launch that
     // reaches it is not cut), so that a render that has reached its target stops there and not a pipeline's depth later
-    uint64_t check_at = (uint64_t)first - 1 + (uint64_t)noise_check;
+    // --adaptive asks at the same points: the tiles are chosen again, and the render ends when none is left.  Resumed with per-pixel counts it
+    // asks before it renders anything: a tile that was done when the checkpoint was written is still done (its moments have not moved).
+    const bool checks = have_target || have_adaptive;
+    uint64_t check_at = (uint64_t)first - 1 + (resumed_counts && have_adaptive ? 0u : (uint64_t)noise_check);
+    const uint32_t all_tiles = ((out_w + 3) / 4) * ((out_h + 3) / 4);
     auto may_issue = [&]() -> uint32_t {
         if (next_s > sampling || q.size() >= depth) return 0;
-        if (have_target && (uint64_t)next_s > check_at) return 0;
-        const uint32_t n = std::min<uint32_t>(lrep, reports_of(next_s, sampling + 1));
+        if (checks && (uint64_t)next_s > check_at) return 0;
+        uint32_t n = std::min<uint32_t>(lrep, reports_of(next_s, sampling + 1));
+        // --adaptive: a launch ends where the tiles are chosen again (the uniform first phase is --noise-check samplings long, not a launch)
+        if (have_adaptive) n = std::min<uint32_t>(n, std::max<uint32_t>(1, reports_of(next_s, (uint32_t)std::min<uint64_t>(check_at, sampling) + 1)));
         if (!measured) return n;   // nothing measured yet: fill the pipeline
         const double room = time_limit - (now_sec() - begin);
         const double fit = last > 0.0 ? room / (1.1 * last) - (double)in_flight : (room >= 0.0 ? (double)n : 0.0);
@@ -469,6 +529,17 @@ int main(int argc, char **argv) {
     bool running = first <= sampling;
     while (running) {
         for (uint32_t n; (n = may_issue()) != 0;) if (issue(n)) return 1;
+        if (q.empty() && have_adaptive && next_s <= sampling && (uint64_t)next_s > check_at) {   // the tiles are chosen again, and nothing is in flight
+            uint32_t active = all_tiles;
+            const int rc = hr_select_tiles(ctx, noise_floor, adaptive_e, &active);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings — no estimate yet, go on as before)
+            if (rc != 0 && rc != HR_ERR_INVALID) { fprintf(stderr, "hr_select_tiles: %s\n", hr_last_error()); return 1; }
+            if (rc == 0) {
+                printf("adaptive: samplings=%u active=%u tiles=%u\n", next_s - 1, active, all_tiles);
+                if (!active) { if (finish("no tile is active")) return 1; break; }
+            }
+            check_at = (uint64_t)next_s - 1 + (uint64_t)noise_check;
+            continue;
+        }
         if (q.empty() && have_target && next_s <= sampling && (uint64_t)next_s > check_at) {   // the question is due, and nothing is in flight
             if (noise_check_now()) return 1;
             if (noise_known && noise_last.mean_error <= noise_target) { if (finish("reached noise target")) return 1; break; }
@@ -510,6 +581,11 @@ int main(int argc, char **argv) {
             if (noise_query(&est, nullptr, &mom, &mom_n) == 1) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
             ok = fwrite(&CKPT_MOMENTS_MAGIC, 4, 1, f) == 1 && fwrite(&mom_n, 8, 1, f) == 1 && fwrite(mom.data(), sizeof(double), mom.size(), f) == mom.size();
         }
+        if (ok && counts) {   // behind the moments trailer (a render without moments: behind the accumulator)
+            std::vector<uint32_t> cnt((size_t)out_w * out_h);
+            if (hr_read_sample_counts(ctx, cnt.data()) != 0) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
+            ok = fwrite(&CKPT_COUNTS_MAGIC, 4, 1, f) == 1 && fwrite(cnt.data(), sizeof(uint32_t), cnt.size(), f) == cnt.size();
+        }
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot write checkpoint %s\n", ckpt_out.c_str()); return 1; }
     }
@@ -545,6 +621,19 @@ int main(int argc, char **argv) {
                 grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = v;
             }
             if (hh_write_png_rgb8(noise_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        }
+    }
+    if (counts) {   // how the samplings were spent
+        std::vector<uint32_t> cnt((size_t)out_w * out_h);
+        CHECK_HR(hr_read_sample_counts(ctx, cnt.data()));
+        uint32_t lo = ~0u, hi = 0;
+        uint64_t sum = 0;
+        for (uint32_t v : cnt) { lo = std::min(lo, v); hi = std::max(hi, v); sum += v; }
+        tee("samplings per pixel: min=%u max=%u mean=%.3f", lo, hi, (double)sum / (double)cnt.size());
+        if (!sample_png.empty()) {   // grey map of count / largest count
+            std::vector<uint8_t> grey(cnt.size() * 3);
+            for (size_t i = 0; i < cnt.size(); i++) grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = hi ? (uint8_t)((double)cnt[i] / (double)hi * 255.0 + 0.5) : 0;
+            if (hh_write_png_rgb8(sample_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
         }
     }
     tee("sampled: %ux%u spp.", sampled, 4u);

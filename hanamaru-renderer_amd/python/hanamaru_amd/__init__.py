@@ -187,6 +187,12 @@ def hip_lib():
         L.hr_write_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.hr_noise_estimate.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(Noise)]
         L.hr_read_noise_image.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.hr_read_sample_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_write_sample_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_resolve_counted.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_set_tile_mask.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_get_tile_mask.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.hr_select_tiles.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint32)]
         _hip = L
     return _hip
 
@@ -461,6 +467,50 @@ class Renderer:
         out = np.empty(self._acc_hw(), dtype=np.float64)
         self._check(self.L.hr_read_noise_image(self._h, float(floor), out.ctypes.data))
         return out
+
+    # ---- adaptive sampling: option "sample_counts", the tile mask, the selection of tiles (include/hanamaru_hip.h)
+    def _tiles_hw(self):
+        h, w = self._acc_hw()
+        return ((h + 3) // 4, (w + 3) // 4)
+
+    def read_sample_counts(self):
+        """hr_read_sample_counts: (h, w) uint32, the samplings every pixel has received."""
+        out = np.empty(self._acc_hw(), dtype=np.uint32)
+        self._check(self.L.hr_read_sample_counts(self._h, out.ctypes.data))
+        return out
+
+    def write_sample_counts(self, counts):
+        a = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert a.shape == self._acc_hw()
+        self._check(self.L.hr_write_sample_counts(self._h, a.ctypes.data))
+
+    def resolve_counted(self):
+        """hr_resolve_counted: resolve() with every pixel's own count."""
+        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
+        self._check(self.L.hr_resolve_counted(self._h, out.ctypes.data))
+        return out
+
+    def set_tile_mask(self, mask):
+        """hr_set_tile_mask: (tiles_y, tiles_x) array over the region's 4x4 tiles, nonzero = render; None removes the mask."""
+        if mask is None:
+            self._check(self.L.hr_set_tile_mask(self._h, None))
+            return
+        a = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert a.shape == self._tiles_hw()
+        self._check(self.L.hr_set_tile_mask(self._h, a.ctypes.data))
+
+    def tile_mask(self):
+        """hr_get_tile_mask: ((tiles_y, tiles_x) uint8 mask in force — all ones without one —, active tiles)."""
+        out = np.empty(self._tiles_hw(), dtype=np.uint8)
+        n = C.c_uint32()
+        self._check(self.L.hr_get_tile_mask(self._h, out.ctypes.data, C.byref(n)))
+        return out, int(n.value)
+
+    def select_tiles(self, floor=0.01, threshold=0.05):
+        """hr_select_tiles: keep the tiles with a pixel whose e > threshold (ANDed with the mask in force); returns the active tiles left."""
+        n = C.c_uint32()
+        self._check(self.L.hr_select_tiles(self._h, float(floor), float(threshold), C.byref(n)))
+        return int(n.value)
 
     def debug_draws(self, sampling, first_path, num_paths, window):
         out = np.empty((num_paths, window), dtype=np.uint64)

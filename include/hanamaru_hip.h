@@ -293,6 +293,55 @@ int hr_write_moments(hr_ctx *ctx, const double *host, uint64_t samplings);   /* 
 int hr_noise_estimate(hr_ctx *ctx, double floor, double threshold, hr_noise *out);
 int hr_read_noise_image(hr_ctx *ctx, double floor, double *host /* w*h */);
 
+/* ---- adaptive sampling: per-pixel sample counts and the active-tile mask (option "sample_counts", off by default) ----------
+ * "Stop rendering what is done."  A frame converges unevenly; with a tile mask in force hr_render covers only the ACTIVE 4x4-pixel tiles of the
+ * region, and with option "sample_counts" = 1 every pixel knows how many samplings it has received.
+ *   - The contract: a path's seed and camera ray depend only on its frame pixel, its sub-sample and its sampling index.  Under a mask
+ *     hr_render(b, e, stride) adds to every pixel of an active tile exactly the per-sampling values x_s a render without the mask adds, and
+ *     nothing to any other pixel.  A pixel that has received samplings 1 .. n holds the accumulator contributions and the moments of a uniform
+ *     render of samplings 1 .. n (the moments bit for bit; the fp32 accumulator as far as the launches are cut alike, see option "batch").
+ *   - hr_set_option "sample_counts" 1 needs hr_set_resolution first (HR_ERR_NO_TARGET), allocates and zeroes counts[h][w] (uint32, region-local
+ *     like the accumulator; set again while on: nothing happens); 0 frees it and removes the mask.  Every hr_render launch adds its samplings to
+ *     the count of each pixel it adds radiance to.  The counts are zeroed by hr_clear, reallocated and zeroed by hr_set_resolution and
+ *     hr_set_region, replaced by hr_write_sample_counts, and not touched by hr_write_accumulator / hr_write_moments (a host that resumes writes
+ *     all three).  The accumulator and the moments are bit-identical with the option on or off.  hr_render_debug returns HR_ERR_UNSUPPORTED
+ *     while it is on.  With the option off the functions below return HR_ERR_INVALID (hr_get_tile_mask excepted).
+ *   - hr_read_sample_counts / hr_write_sample_counts: w*h uint32, row-major, top row first — resume, tile stitching, shards.  Counts are
+ *     additive like moments: a host adds the ranks' counts (there is no library-side collective).
+ *   - With "sample_counts" and "moments" both on, hr_noise_estimate and hr_read_noise_image take the PIXEL's count as n, and return
+ *     HR_ERR_INVALID if any pixel of the region has a count below 2.  hr_noise.samplings keeps its meaning (samplings issued since the
+ *     moments were zeroed).  With "sample_counts" off nothing about the two changes.  The counts are the moments' n, so the two cover the
+ *     same samplings: switching either option on while the other is on zeroes the other as well (the accumulator stays), and the estimate
+ *     and hr_select_tiles return HR_ERR_INVALID when a pixel's count exceeds the samplings behind the moments (a host that writes one of
+ *     them writes both).
+ *   - hr_resolve_counted: hr_resolve with the scale 1.0f / (float)(counts[p] * 4u) per pixel — equal counts S give the bytes of
+ *     hr_resolve(ctx, S, ..).  A count of 0 resolves as radiance 0.  Like hr_resolve it reads the all-reduced total while that is valid: the
+ *     caller must then have written the summed counts.
+ *   - hr_set_tile_mask: mask = tiles_y * tiles_x bytes over the region's 4x4 tiles, row-major, top row first, tiles_x = (w + 3) / 4,
+ *     tiles_y = (h + 3) / 4, nonzero = render the tile; NULL removes the mask.  Needs "sample_counts" on (HR_ERR_INVALID: an image whose pixels
+ *     have unequal counts cannot be resolved without them).  The mask is a setting, like the region: hr_clear keeps it; hr_set_resolution,
+ *     hr_set_region and switching "sample_counts" off remove it.  With no tile active hr_render enqueues nothing and returns HR_OK.
+ *     hr_stats.paths counts 4 x (in-region pixels of the active tiles) per sampling.  A sparse mask gets more samplings per launch (up to 64),
+ *     as a small region does.
+ *   - hr_get_tile_mask: the mask in force into `mask` (may be NULL) and the number of active tiles into `active` (may be NULL); without a mask
+ *     every byte is 1 and *active is the region's tile count.
+ *   - hr_select_tiles (needs "moments" and "sample_counts"; every count >= 2, else HR_ERR_INVALID): a tile is active iff e > threshold for at
+ *     least one of its in-region pixels, e being exactly the value hr_read_noise_image(floor) returns for the pixel.  The result is ANDed
+ *     with the mask in force and becomes the mask: a tile that went inactive stays inactive until hr_set_tile_mask(NULL) starts over, so a
+ *     pixel's samplings are always a prefix 1 .. n of those issued.  Decided and compacted on the device, deterministically: two calls give
+ *     the same mask.  *active (may be NULL): tiles left.
+ *   - While a mask is set: hr_render_debug and the unit-level hr_debug_* entry points return HR_ERR_UNSUPPORTED, and so does hr_render with
+ *     "counters", "russian_roulette", or the debug options min_waves, seed_mode (other than 2) or seed_prof changed — the kernels over a tile
+ *     list exist for fp32 and precise shading, both trace pipelines and both node formats.
+ *   - What it is not: selecting tiles by the same samples that form the estimate biases the image slightly (a pixel that looks converged by
+ *     luck stops early).  A uniform first phase keeps that small; the library does not dilate the mask and has no held-out estimate. */
+int hr_read_sample_counts(hr_ctx *ctx, uint32_t *host /* w*h */);
+int hr_write_sample_counts(hr_ctx *ctx, const uint32_t *host);
+int hr_resolve_counted(hr_ctx *ctx, uint8_t *host_rgb8);
+int hr_set_tile_mask(hr_ctx *ctx, const uint8_t *mask /* tiles_y*tiles_x, NULL = none */);
+int hr_get_tile_mask(hr_ctx *ctx, uint8_t *mask /* may be NULL */, uint32_t *active /* may be NULL */);
+int hr_select_tiles(hr_ctx *ctx, double floor, double threshold, uint32_t *active /* may be NULL */);
+
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):
  *   "counters"      0 / 1: instrumented build of the trace kernel (fills the counter fields of hr_stats)
@@ -319,6 +368,8 @@ int hr_get_stats(hr_ctx *ctx, hr_stats *out);
  *                   what runs.  (1 excludes "russian_roulette"; -1 stands back when the roulette is on.)
  *   "moments"       0 (default) / 1: keep per-pixel first and second moments of the per-sampling values for hr_noise_estimate (see there);
  *                   the image does not change by a bit
+ *   "sample_counts" 0 (default) / 1: keep per-pixel counts of the samplings received, for hr_set_tile_mask / hr_select_tiles /
+ *                   hr_resolve_counted (see there); the image does not change by a bit
  *   next hr_upload_scene:
  *   "bvh_builder"   -1 = by scene size (default): the host's binned-SAH build below 200,000 primitives (the best tree; one host thread,
  *                   < 1 s), the device PLOC build from there on (0.97 - 0.99 of that tree's quality; 4 x 10^6 triangles in 38 ms instead of

@@ -77,6 +77,13 @@ extern "C" {
     pub fn hr_write_moments(ctx: *mut HrCtx, host: *const f64, samplings: u64) -> c_int;
     pub fn hr_noise_estimate(ctx: *mut HrCtx, floor: f64, threshold: f64, out: *mut HrNoise) -> c_int;
     pub fn hr_read_noise_image(ctx: *mut HrCtx, floor: f64, host: *mut f64 /* w*h */) -> c_int;
+    // adaptive sampling: option "sample_counts", the tile mask, the selection of tiles
+    pub fn hr_read_sample_counts(ctx: *mut HrCtx, host: *mut u32 /* w*h */) -> c_int;
+    pub fn hr_write_sample_counts(ctx: *mut HrCtx, host: *const u32) -> c_int;
+    pub fn hr_resolve_counted(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
+    pub fn hr_set_tile_mask(ctx: *mut HrCtx, mask: *const u8 /* tiles_y*tiles_x, null = none */) -> c_int;
+    pub fn hr_get_tile_mask(ctx: *mut HrCtx, mask: *mut u8, active: *mut u32) -> c_int;
+    pub fn hr_select_tiles(ctx: *mut HrCtx, floor: f64, threshold: f64, active: *mut u32) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----
