@@ -13,6 +13,8 @@
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
+// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts) are rows of one
+// table, PLANES, with one set of routines for their bytes, life cycle, zeroing and host copies; scratch a call needs lives in a CallScratch.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -54,6 +56,30 @@ static int fail(int code, const char *fmt, ...) {
         hipError_t e_ = (expr);                                                                               \
         if (e_ != hipSuccess) return fail(HR_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+// the same for the entry points whose callers have always been told "<entry point>: <HIP's text>"
+#define HIP_TRY_AS(who, expr)                                                                                 \
+    do {                                                                                                      \
+        hipError_t e_ = (expr);                                                                               \
+        if (e_ != hipSuccess) return fail(HR_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e_));               \
+    } while (0)
+template <class T>
+static int free_device(T *&p) {
+    if (p) { HIP_TRY(hipFree(p)); p = nullptr; }
+    return HR_OK;
+}
+// Device memory for the duration of one call: every block is freed when the holder goes out of scope, on every path out of the call.
+struct CallScratch {
+    std::vector<void *> blocks;
+    CallScratch() = default;
+    CallScratch(const CallScratch &) = delete;
+    CallScratch &operator=(const CallScratch &) = delete;
+    ~CallScratch() { for (void *q : blocks) (void)hipFree(q); }
+    hipError_t alloc(void **out, size_t bytes) {
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e == hipSuccess) blocks.push_back(*out);
+        return e;
+    }
+};
 
 #include "seed_kernels.h"
 #include "trace_kernel.h"
@@ -384,6 +410,112 @@ static hipError_t timed_end(hipError_t launched, EventPair &ev, hipStream_t st, 
     if (launches) ++*launches;
     return hipSuccess;
 }
+// an event pair for the duration of one call (the device BVH build's)
+struct CallEvents : EventPair {
+    CallEvents() : EventPair{nullptr, nullptr} {}
+    CallEvents(const CallEvents &) = delete;
+    CallEvents &operator=(const CallEvents &) = delete;
+    ~CallEvents() { drop_pair(*this); }
+};
+
+// `c` leaves its same-device group (hr_comm_init_local over one device): the group is over for its peers too
+static void reset_same_device_peers(hr_ctx *c) {
+    for (hr_ctx *p : c->same_device_peers) if (p != c) { p->same_device_peers.clear(); p->comm_world = 0; p->total_valid = false; p->comm_path = HR_COMM_NONE; p->allreduces = 0; }
+}
+// The tile mask's device buffers and what the selection and the counts' check work in.  All four are allocated by whoever needs them first
+// (mask_buffers, select_out_buffer, hr_select_tiles) and released here, by remove_mask and hr_destroy.
+static int free_mask_buffers(hr_ctx *c) {
+    c->select_tmp_bytes = 0;
+    for (uint32_t **p : {&c->d_tile_list, &c->d_tile_flags, &c->d_select_out}) { int rc = free_device(*p); if (rc) return rc; }
+    return free_device(c->select_tmp);
+}
+
+// ------------------------------------------------------------------------------------------ region planes
+// A plane is a device buffer of RW x RH x comps elements of one type: the accumulator and everything that has its shape.  This table is the one
+// place that says what each plane holds; the routines below are the one place that turns it into bytes, and set_target / hr_clear / hr_destroy
+// walk it.  Life cycles:
+//   WITH_TARGET   allocated by set_target for every target
+//   WITH_OPTION   allocated while the option `on` is on: when it is switched on, and by set_target while it is on; gone when it is switched off
+//   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate), freed by
+//                 set_target — noise_img also with the moments it is made of
+// at_alloc: zeroed when allocated.  at_clear: zeroed by hr_clear.  n: the count that belongs to the plane's contents and is zeroed with them.
+enum PlaneLife { WITH_TARGET, WITH_OPTION, ON_FIRST_USE };
+struct Plane {
+    void **(*slot)(hr_ctx *);
+    size_t elem;
+    uint32_t comps;
+    PlaneLife life;
+    bool at_alloc, at_clear;
+    const char *option = nullptr;       // WITH_OPTION: the key of hr_set_option
+    bool hr_ctx::*on = nullptr;
+    uint64_t hr_ctx::*n = nullptr;
+};
+#define PLANE_SLOT(member) [](hr_ctx *c) -> void ** { return (void **)&c->member; }
+static const Plane ACCUM_OWN{PLANE_SLOT(accum_own), sizeof(float), 3, WITH_TARGET, true, true};   // hr_clear zeroes c->accum: this plane, or the caller's bound buffer of its size
+static const Plane POST_TMP{PLANE_SLOT(post_tmp), sizeof(float), 3, WITH_TARGET, false, false};
+static const Plane RGB8{PLANE_SLOT(d_rgb8), sizeof(uint8_t), 3, WITH_TARGET, false, false};
+static const Plane ACCUM_TOTAL{PLANE_SLOT(accum_total), sizeof(float), 3, ON_FIRST_USE, false, false};
+static const Plane MOMENTS{PLANE_SLOT(moments), sizeof(double), 6, WITH_OPTION, true, true, "moments", &hr_ctx::moments_on, &hr_ctx::moments_n};
+static const Plane NOISE_IMG{PLANE_SLOT(noise_img), sizeof(double), 1, ON_FIRST_USE, false, false};
+static const Plane COUNTS{PLANE_SLOT(counts), sizeof(uint32_t), 1, WITH_OPTION, true, true, "sample_counts", &hr_ctx::counts_on};
+#undef PLANE_SLOT
+static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS};
+
+static size_t region_pixels(const hr_ctx *c) { return (size_t)c->RW * c->RH; }
+static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps; }
+static size_t plane_bytes(const hr_ctx *c, const Plane &p) { return plane_elems(c, p) * p.elem; }
+static int plane_free(hr_ctx *c, const Plane &p) {
+    if (p.n) c->*p.n = 0;
+    return free_device(*p.slot(c));
+}
+// The plane's contents start over: `dev` (a buffer of the plane's size; default: the plane's own, if there is one) is zeroed on `st`, the count
+// that belongs to them with it.  Outside a render that is the null stream, which is waited for: the render streams do not wait for it.
+static int plane_zero(hr_ctx *c, const Plane &p, hipStream_t st = nullptr, void *dev = nullptr) {
+    if (!dev && !(dev = *p.slot(c))) return HR_OK;
+    HIP_TRY(hipMemsetAsync(dev, 0, plane_bytes(c, p), st));
+    if (!st) HIP_TRY(hipStreamSynchronize(nullptr));
+    if (p.n) c->*p.n = 0;
+    return HR_OK;
+}
+// (re)allocate the plane for the region in force
+static int plane_alloc(hr_ctx *c, const Plane &p) {
+    int rc = plane_free(c, p);
+    if (rc) return rc;
+    HIP_TRY(hipMalloc(p.slot(c), plane_bytes(c, p)));
+    return p.at_alloc ? plane_zero(c, p) : HR_OK;
+}
+// Host copies of a buffer of the plane's size.  A read goes through hr_synchronize (which can return the RNG-window error); a write through
+// sync_all, and one into the accumulator makes the totals that include it stale.
+static int plane_read(hr_ctx *c, const Plane &p, const void *dev, void *host) {
+    int rc = hr_synchronize(c);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(host, dev, plane_bytes(c, p), hipMemcpyDeviceToHost));
+    return HR_OK;
+}
+static int plane_write(hr_ctx *c, const Plane &p, void *dev, const void *host) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    if (dev == c->accum) invalidate_totals(c);
+    HIP_TRY(hipMemcpy(dev, host, plane_bytes(c, p), hipMemcpyHostToDevice));
+    return HR_OK;
+}
+// the plane of an option: refused while the option is off (`who`: the entry point); its host copies ask that first, then for the host's pointer
+static int plane_ready(hr_ctx *c, const Plane &p, const char *who) {
+    if (!c) return fail(HR_ERR_INVALID, "%s: null ctx", who);
+    if (!(c->*p.on) || !*p.slot(c)) return fail(HR_ERR_INVALID, "%s: option %s is off", who, p.option);
+    return HR_OK;
+}
+static int option_plane_read(hr_ctx *c, const Plane &p, const char *who, void *host) {
+    int rc = plane_ready(c, p, who);
+    if (!rc && !host) rc = fail(HR_ERR_INVALID, "%s: null argument", who);
+    return rc ? rc : plane_read(c, p, *p.slot(c), host);
+}
+static int option_plane_write(hr_ctx *c, const Plane &p, const char *who, const void *host) {
+    int rc = plane_ready(c, p, who);
+    if (!rc && !host) rc = fail(HR_ERR_INVALID, "%s: null argument", who);
+    return rc ? rc : plane_write(c, p, *p.slot(c), host);
+}
 
 // ------------------------------------------------------------------------------------------ C ABI
 
@@ -456,28 +588,16 @@ int hr_destroy(hr_ctx *c) {
     for (auto *ev : {&c->seed_events, &c->trace_events, &c->post_events, &c->debug_events})
         for (auto &e : *ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &m : c->markers) (void)hipEventDestroy(m.second);
-    if (c->accum_own) (void)hipFree(c->accum_own);
+    for (const Plane *p : PLANES) (void)plane_free(c, *p);
+    (void)free_mask_buffers(c);
     for (int i = 0; i < 2; i++) {
-        if (c->recs[i]) (void)hipFree(c->recs[i]);
         if (c->seed_done[i]) (void)hipEventDestroy(c->seed_done[i]);
         if (c->trace_done[i]) (void)hipEventDestroy(c->trace_done[i]);
     }
-    if (c->ring) (void)hipFree(c->ring);
-    if (c->wf_block) (void)hipFree(c->wf_block);
-    if (c->ovf) (void)hipFree(c->ovf);
-    if (c->ovf_win) (void)hipFree(c->ovf_win);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    if (c->d_tile_counter) (void)hipFree(c->d_tile_counter);
-    if (c->gov) (void)hipFree(c->gov);
-    if (c->post_tmp) (void)hipFree(c->post_tmp);
-    if (c->d_rgb8) (void)hipFree(c->d_rgb8);
-    if (c->accum_total) (void)hipFree(c->accum_total);
-    if (c->moments) (void)hipFree(c->moments);
-    if (c->noise_img) (void)hipFree(c->noise_img);
-    if (c->counts) (void)hipFree(c->counts);
-    for (void *p : {(void *)c->d_tile_list, (void *)c->d_tile_flags, (void *)c->d_select_out, c->select_tmp}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->recs[0], (void *)c->recs[1], (void *)c->ring, c->wf_block, (void *)c->ovf, (void *)c->ovf_win, (void *)c->d_counters, (void *)c->d_tile_counter, (void *)c->gov})
+        if (p) (void)hipFree(p);
     if (c->comm && hrcomm::api().CommDestroy) (void)hrcomm::api().CommDestroy(c->comm);
-    for (hr_ctx *p : c->same_device_peers) if (p != c) { p->same_device_peers.clear(); p->comm_world = 0; p->total_valid = false; p->comm_path = HR_COMM_NONE; p->allreduces = 0; }
+    reset_same_device_peers(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->seed_stream) (void)hipStreamDestroy(c->seed_stream);
     delete c;
@@ -487,7 +607,7 @@ int hr_destroy(hr_ctx *c) {
 // Device builders (option bvh_builder = 1 LBVH, 2 PLOC; gpu_bvh.h): the primitive arrays were uploaded in input order; split long
 // thin triangles into references (early split clipping), build the tree over them, emit it in both record formats (16-byte quantised
 // records in per-octant near-first preorder — what the trace kernel walks — and the 32-byte fp32 records), re-store the primitives
-// in leaf order and point the scene at the results.  Scratch is freed before returning.
+// in leaf order and point the scene at the results.  The scratch and the event pair live for the call (CallScratch, CallEvents).
 static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_in) {
     using namespace lbvh;
     Scene &d = c->dsc;
@@ -504,25 +624,18 @@ static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_i
         const double e0 = hs.scene_max[0] - hs.scene_min[0], e1 = hs.scene_max[1] - hs.scene_min[1], e2 = hs.scene_max[2] - hs.scene_min[2];
         if (e0 >= 0 && e1 >= 0 && e2 >= 0) scene_sa = 2.0 * (e0 * e1 + e1 * e2 + e2 * e0);
     }
-    std::vector<void *> scratch;
-    hipEvent_t ea = nullptr, eb = nullptr;   // around everything the build puts on the stream
-    auto cleanup = [&]() {
-        for (void *q : scratch) (void)hipFree(q);
-        scratch.clear();
-        if (ea) { (void)hipEventDestroy(ea); ea = nullptr; }
-        if (eb) { (void)hipEventDestroy(eb); eb = nullptr; }
-    };
+    CallScratch scratch;
+    CallEvents ev;   // around everything the build puts on the stream
     auto alloc = [&](size_t bytes, bool keep) -> void * {
         void *q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        (keep ? c->scene_allocs : scratch).push_back(q);
+        if (keep) { if (hipMalloc(&q, std::max<size_t>(bytes, 16)) == hipSuccess) c->scene_allocs.push_back(q); }
+        else (void)scratch.alloc(&q, std::max<size_t>(bytes, 16));
         return q;
     };
 #define LBVH_ALLOC(var, type, count, keep)                                                                        \
     type *var = (type *)alloc(sizeof(type) * (size_t)(count), keep);                                                \
-    if (!var) { cleanup(); return fail(HR_ERR_DEVICE, "hr_upload_scene: out of device memory in the BVH build"); }
-    (void)hipEventCreate(&ea); (void)hipEventCreate(&eb);
-    (void)hipEventRecord(ea, c->stream);
+    if (!var) return fail(HR_ERR_DEVICE, "hr_upload_scene: out of device memory in the BVH build");
+    (void)timed_begin(ev, c->stream);   // (best effort: without the pair the build goes on and reports 0 ms)
     // Early split clipping on the device (option split_ratio: -1 = on with the host builder's automatic ratio of 2, 0 = off, > 0 = that
     // ratio; the host builder's automatic mode also builds the unsplit tree and keeps the better one, the device always keeps the split):
     // pieces per triangle, a scan, then the pieces' boxes and owners.  The builders below then see one primitive per piece.
@@ -532,15 +645,14 @@ static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_i
         LBVH_ALLOC(split_counts, uint32_t, nt, false)
         LBVH_ALLOC(split_offsets, uint32_t, nt, false)
         size_t sbytes = 0;
-        hipError_t se = hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, split_counts, split_offsets, (int)nt, c->stream);
+        HIP_TRY_AS("device split clipping", hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, split_counts, split_offsets, (int)nt, c->stream));
         LBVH_ALLOC(split_tmp, unsigned char, sbytes, false)
         split_count_kernel<<<(nt + 127) / 128, 128, 0, c->stream>>>(tris_in, nt, sp, split_counts);
-        if (se == hipSuccess) se = hipcub::DeviceScan::ExclusiveSum(split_tmp, sbytes, split_counts, split_offsets, (int)nt, c->stream);
+        HIP_TRY_AS("device split clipping", hipcub::DeviceScan::ExclusiveSum(split_tmp, sbytes, split_counts, split_offsets, (int)nt, c->stream));
         uint32_t last[2] = {0, 0};
-        if (se == hipSuccess) se = hipMemcpyAsync(&last[0], split_offsets + (nt - 1), 4, hipMemcpyDeviceToHost, c->stream);
-        if (se == hipSuccess) se = hipMemcpyAsync(&last[1], split_counts + (nt - 1), 4, hipMemcpyDeviceToHost, c->stream);
-        if (se == hipSuccess) se = hipStreamSynchronize(c->stream);
-        if (se != hipSuccess) { cleanup(); return fail(HR_ERR_DEVICE, "device split clipping: %s", hipGetErrorString(se)); }
+        HIP_TRY_AS("device split clipping", hipMemcpyAsync(&last[0], split_offsets + (nt - 1), 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY_AS("device split clipping", hipMemcpyAsync(&last[1], split_counts + (nt - 1), 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY_AS("device split clipping", hipStreamSynchronize(c->stream));
         const uint64_t refs = (uint64_t)last[0] + last[1];
         // (bounded together with the spheres and cuboids: the builder's n = refs + spheres + cuboids indexes its sort keys and INFO_COUNT with
         // 24 bits; beyond that the split references are dropped and the triangles go in as they are)
@@ -553,7 +665,7 @@ static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_i
     }
     const int n = (int)(p.num_tris + p.num_spheres + p.num_cuboids);
     p.index_bits = key_index_bits_for((uint64_t)n);
-    if (n <= 0 || (uint64_t)n >= (1ull << p.index_bits)) { cleanup(); return fail(HR_ERR_UNSUPPORTED, "device BVH build: %d primitives do not fit the %d index bits of the sort keys", n, p.index_bits); }
+    if (n <= 0 || (uint64_t)n >= (1ull << p.index_bits)) return fail(HR_ERR_UNSUPPORTED, "device BVH build: %d primitives do not fit the %d index bits of the sort keys", n, p.index_bits);
     const int N = 2 * n - 1;
     LBVH_ALLOC(keys_in, mkey_t, n, false)
     LBVH_ALLOC(keys, mkey_t, n, false)
@@ -578,16 +690,12 @@ static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_i
     LBVH_ALLOC(sphere_lo, f4, d.num_spheres, true)
     LBVH_ALLOC(cuboids, f4, 2 * (size_t)d.num_cuboids, true)
     size_t sort_bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, keys_in, keys, n, 0, 64, c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(HR_ERR_DEVICE, "hipcub sort (size query): %s", hipGetErrorString(e)); }
+    HIP_TRY_AS("hipcub sort (size query)", hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, keys_in, keys, n, 0, 64, c->stream));
     LBVH_ALLOC(sort_tmp, unsigned char, sort_bytes, false)
     // multi-workgroup PLOC: packed role counters, their scan, the two-slot iteration state
     const bool ploc_multi = c->builder_in_use == 2 && n > 1;
     size_t scan_bytes = 0;
-    if (ploc_multi) {
-        e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (u64t *)nullptr, (u64t *)nullptr, n, c->stream);
-        if (e != hipSuccess) { cleanup(); return fail(HR_ERR_DEVICE, "hipcub scan (size query): %s", hipGetErrorString(e)); }
-    }
+    if (ploc_multi) HIP_TRY_AS("hipcub scan (size query)", hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (u64t *)nullptr, (u64t *)nullptr, n, c->stream));
     LBVH_ALLOC(ploc_flags, u64t, ploc_multi ? n : 1, false)
     LBVH_ALLOC(ploc_pos, u64t, ploc_multi ? n : 1, false)
     LBVH_ALLOC(scan_tmp, unsigned char, scan_bytes, false)
@@ -600,73 +708,63 @@ static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_i
 #undef LBVH_ALLOC
     const int T = 256;
     hipStream_t st = c->stream;
-    e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)n, st);
-    if (e == hipSuccess) e = hipMemsetAsync(parent, 0xff, sizeof(uint32_t) * (size_t)N, st);   // n == 1: the lone leaf is the root
-    if (e == hipSuccess) {
-        key_kernel<<<(n + T - 1) / T, T, 0, st>>>(p, n, keys_in);
-        e = hipcub::DeviceRadixSort::SortKeys(sort_tmp, sort_bytes, keys_in, keys, n, 0, 64, st);
-    }
-    if (e == hipSuccess) {
-        leaf_kernel<<<(n + T - 1) / T, T, 0, st>>>(p, keys, n, w);
-        if (n > 1 && c->builder_in_use == 1) hierarchy_kernel<<<(n - 1 + T - 1) / T, T, 0, st>>>(keys, n, w);
-        if (ploc_multi) {
-            ploc_init_kernel<<<(n + T - 1) / T, T, 0, st>>>(n, cl_a, ploc_state);
-            uint32_t *cur = cl_a, *nxt = cl_b;
-            uint32_t m_known = (uint32_t)n;   // the host's upper bound of the cluster count (refreshed every few iterations)
-            int it = 0;
-            for (; it < 4096 && m_known > c->ploc_top && e == hipSuccess; it++) {
-                const uint32_t g = (m_known + T - 1) / T;
-                const PlocState *sin = ploc_state + (it & 1);
-                ploc_nn_kernel<<<g, T, 0, st>>>(w, cur, nn, sin);
-                ploc_role_kernel<<<g, T, 0, st>>>(nn, ploc_flags, m_known, sin);
-                e = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, ploc_flags, ploc_pos, (int)m_known, st);
-                ploc_merge_kernel<<<g, T, 0, st>>>(w, cur, nxt, nn, ploc_flags, ploc_pos, sin, ploc_state + ((it + 1) & 1));
-                std::swap(cur, nxt);
-                if ((it & 3) == 3 || m_known <= 4u * c->ploc_top) {   // every fourth iteration (every one near the end): how many are left?
-                    PlocState hs{};
-                    if (e == hipSuccess) e = hipMemcpyAsync(&hs, ploc_state + ((it + 1) & 1), sizeof hs, hipMemcpyDeviceToHost, st);
-                    if (e == hipSuccess) e = hipStreamSynchronize(st);
-                    if (e == hipSuccess) m_known = hs.m;
-                }
-            }
-            if (e == hipSuccess && m_known > top_cap) e = hipErrorUnknown;   // (the loop ends at <= ploc_top clusters, the size of the top buffers)
-            // the top of the tree: binned SAH over the clusters that are left, on the host (a few thousand boxes)
-            if (e == hipSuccess && m_known > 1u) {
-                const uint32_t m = m_known;
-                std::vector<float> hb(6 * (size_t)m);
-                std::vector<uint32_t> hc(m);
-                ploc_top_gather_kernel<<<(m + T - 1) / T, T, 0, st>>>(w, cur, m, top_boxes, top_counts);
-                e = hipMemcpyAsync(hb.data(), top_boxes, hb.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(hc.data(), top_counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-                std::vector<int32_t> tl, tr;
-                if (e == hipSuccess) {
-                    build_top_tree(hb.data(), hc.data(), m, tl, tr);
-                    if (tl.size() != (size_t)m - 1) e = hipErrorUnknown;
-                }
-                if (e == hipSuccess) e = hipMemcpyAsync(top_left, tl.data(), tl.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(top_right, tr.data(), tr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) {
-                    ploc_top_apply_kernel<<<(m - 1 + T - 1) / T, T, 0, st>>>(w, m - 1, top_left, top_right, cur);
-                    e = hipStreamSynchronize(st);   // tl / tr are host vectors about to go out of scope
-                }
+    static const char *const who = "device BVH build";
+    HIP_TRY_AS(who, hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)n, st));
+    HIP_TRY_AS(who, hipMemsetAsync(parent, 0xff, sizeof(uint32_t) * (size_t)N, st));   // n == 1: the lone leaf is the root
+    key_kernel<<<(n + T - 1) / T, T, 0, st>>>(p, n, keys_in);
+    HIP_TRY_AS(who, hipcub::DeviceRadixSort::SortKeys(sort_tmp, sort_bytes, keys_in, keys, n, 0, 64, st));
+    leaf_kernel<<<(n + T - 1) / T, T, 0, st>>>(p, keys, n, w);
+    if (n > 1 && c->builder_in_use == 1) hierarchy_kernel<<<(n - 1 + T - 1) / T, T, 0, st>>>(keys, n, w);
+    if (ploc_multi) {
+        ploc_init_kernel<<<(n + T - 1) / T, T, 0, st>>>(n, cl_a, ploc_state);
+        uint32_t *cur = cl_a, *nxt = cl_b;
+        uint32_t m_known = (uint32_t)n;   // the host's upper bound of the cluster count (refreshed every few iterations)
+        for (int it = 0; it < 4096 && m_known > c->ploc_top; it++) {
+            const uint32_t g = (m_known + T - 1) / T;
+            const PlocState *sin = ploc_state + (it & 1);
+            ploc_nn_kernel<<<g, T, 0, st>>>(w, cur, nn, sin);
+            ploc_role_kernel<<<g, T, 0, st>>>(nn, ploc_flags, m_known, sin);
+            HIP_TRY_AS(who, hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, ploc_flags, ploc_pos, (int)m_known, st));
+            ploc_merge_kernel<<<g, T, 0, st>>>(w, cur, nxt, nn, ploc_flags, ploc_pos, sin, ploc_state + ((it + 1) & 1));
+            std::swap(cur, nxt);
+            if ((it & 3) == 3 || m_known <= 4u * c->ploc_top) {   // every fourth iteration (every one near the end): how many are left?
+                PlocState hs{};
+                HIP_TRY_AS(who, hipMemcpyAsync(&hs, ploc_state + ((it + 1) & 1), sizeof hs, hipMemcpyDeviceToHost, st));
+                HIP_TRY_AS(who, hipStreamSynchronize(st));
+                m_known = hs.m;
             }
         }
-        fit_kernel<<<(n + T - 1) / T, T, 0, st>>>(n, (uint32_t)c->max_leaf, w);
-        finish_kernel<<<(N + T - 1) / T, T, 0, st>>>(p, n, w, prim_pos);
-        frame_kernel<<<1, 64, 0, st>>>(w, frame);
-        emit_kernel<<<(8 * N + T - 1) / T, T, 0, st>>>(n, w, frame, nodes, qnodes);
-        gather_kernel<<<(n + T - 1) / T, T, 0, st>>>(p, keys, prim_pos, n, tris, tri_shade, tri_face, spheres, sphere_elem, d.sphere_elem, sphere_lo, d.sphere_lo, cuboids);
-        e = hipGetLastError();
+        HIP_TRY_AS(who, m_known > top_cap ? hipErrorUnknown : hipSuccess);   // (the loop ends at <= ploc_top clusters, the size of the top buffers)
+        // the top of the tree: binned SAH over the clusters that are left, on the host (a few thousand boxes)
+        if (m_known > 1u) {
+            const uint32_t m = m_known;
+            std::vector<float> hb(6 * (size_t)m);
+            std::vector<uint32_t> hc(m);
+            ploc_top_gather_kernel<<<(m + T - 1) / T, T, 0, st>>>(w, cur, m, top_boxes, top_counts);
+            HIP_TRY_AS(who, hipMemcpyAsync(hb.data(), top_boxes, hb.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY_AS(who, hipMemcpyAsync(hc.data(), top_counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY_AS(who, hipStreamSynchronize(st));
+            std::vector<int32_t> tl, tr;
+            build_top_tree(hb.data(), hc.data(), m, tl, tr);
+            HIP_TRY_AS(who, tl.size() != (size_t)m - 1 ? hipErrorUnknown : hipSuccess);
+            HIP_TRY_AS(who, hipMemcpyAsync(top_left, tl.data(), tl.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY_AS(who, hipMemcpyAsync(top_right, tr.data(), tr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            ploc_top_apply_kernel<<<(m - 1 + T - 1) / T, T, 0, st>>>(w, m - 1, top_left, top_right, cur);
+            HIP_TRY_AS(who, hipStreamSynchronize(st));   // tl / tr are host vectors about to go out of scope
+        }
     }
-    (void)hipEventRecord(eb, st);
+    fit_kernel<<<(n + T - 1) / T, T, 0, st>>>(n, (uint32_t)c->max_leaf, w);
+    finish_kernel<<<(N + T - 1) / T, T, 0, st>>>(p, n, w, prim_pos);
+    frame_kernel<<<1, 64, 0, st>>>(w, frame);
+    emit_kernel<<<(8 * N + T - 1) / T, T, 0, st>>>(n, w, frame, nodes, qnodes);
+    gather_kernel<<<(n + T - 1) / T, T, 0, st>>>(p, keys, prim_pos, n, tris, tri_shade, tri_face, spheres, sphere_elem, d.sphere_elem, sphere_lo, d.sphere_lo, cuboids);
+    HIP_TRY_AS(who, hipGetLastError());
+    if (ev.b) (void)hipEventRecord(ev.b, st);
     float hframe[8] = {0, 0, 0, 1, 1, 1, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(hframe, frame, sizeof hframe, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    HIP_TRY_AS(who, hipMemcpyAsync(hframe, frame, sizeof hframe, hipMemcpyDeviceToHost, st));
+    HIP_TRY_AS(who, hipStreamSynchronize(st));
     float ms = 0;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ea, eb);
-    cleanup();
-    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "device BVH build: %s", hipGetErrorString(e));
+    if (ev.b) (void)hipEventElapsedTime(&ms, ev.a, ev.b);
     uint32_t total = 0;
     memcpy(&total, &hframe[6], sizeof total);
     if (total == 0 || total > (uint32_t)N) return fail(HR_ERR_DEVICE, "device BVH build: implausible record count %u for %d primitives", total, n);
@@ -753,52 +851,17 @@ int hr_upload_scene(hr_ctx *c, const hr_scene_desc *sd) {
     return HR_OK;
 }
 
-// The moments buffer (option "moments") follows the accumulator: the window's size, zeroed together with the count.
-static int free_moments(hr_ctx *c) {
-    c->moments_n = 0;
-    if (c->moments) { HIP_TRY(hipFree(c->moments)); c->moments = nullptr; }
-    if (c->noise_img) { HIP_TRY(hipFree(c->noise_img)); c->noise_img = nullptr; }
-    return HR_OK;
-}
-static int alloc_moments(hr_ctx *c, uint32_t w, uint32_t h) {
-    int rc = free_moments(c);
-    if (rc) return rc;
-    const size_t bytes = (size_t)w * h * 6 * sizeof(double);
-    HIP_TRY(hipMalloc((void **)&c->moments, bytes));
-    HIP_TRY(hipMemset(c->moments, 0, bytes));
-    HIP_TRY(hipStreamSynchronize(nullptr));   // (the render streams do not wait for the null stream)
-    return HR_OK;
-}
-
-// The counts buffer (option "sample_counts") follows the accumulator like the moments do.
-static int free_counts(hr_ctx *c) {
-    if (c->counts) { HIP_TRY(hipFree(c->counts)); c->counts = nullptr; }
-    return HR_OK;
-}
-static int alloc_counts(hr_ctx *c, uint32_t w, uint32_t h) {
-    int rc = free_counts(c);
-    if (rc) return rc;
-    const size_t bytes = (size_t)w * h * sizeof(uint32_t);
-    HIP_TRY(hipMalloc((void **)&c->counts, bytes));
-    HIP_TRY(hipMemset(c->counts, 0, bytes));
-    HIP_TRY(hipStreamSynchronize(nullptr));   // (the render streams do not wait for the null stream)
-    return HR_OK;
-}
 // No tile mask: hr_render covers every tile of the region again.  The mask's buffers are sized by the region's tiles and go with it.
 // (Callers have synchronised the context: no kernel is reading the list.)
 static int remove_mask(hr_ctx *c) {
     c->mask_on = false;
     c->mask.clear();
     c->mask_active = 0; c->mask_pixels = 0;
-    if (c->d_tile_list) { HIP_TRY(hipFree(c->d_tile_list)); c->d_tile_list = nullptr; }
-    if (c->d_tile_flags) { HIP_TRY(hipFree(c->d_tile_flags)); c->d_tile_flags = nullptr; }
-    if (c->select_tmp) { HIP_TRY(hipFree(c->select_tmp)); c->select_tmp = nullptr; }
-    c->select_tmp_bytes = 0;
-    return HR_OK;
+    return free_mask_buffers(c);
 }
 
-// The target: the W x H frame and the window of it that is rendered (the whole frame, or hr_set_region's).  The accumulator and the resolve's
-// buffers are (re)allocated for the window and zeroed.
+// The target: the W x H frame and the window of it that is rendered (the whole frame, or hr_set_region's).  Every plane is freed, and those that
+// live with the target, or with an option that is on, are allocated again for the window (zeroed where the table says so).
 static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
@@ -807,24 +870,27 @@ static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y
     // pointers); a caller-bound accumulator was sized for the old target: it is unbound, the caller rebinds
     c->accum = nullptr; c->W = c->H = 0; c->RX = c->RY = c->RW = c->RH = 0; c->total_valid = false;
     unbind_accumulator(c);
-    if (c->accum_own) { HIP_TRY(hipFree(c->accum_own)); c->accum_own = nullptr; }
-    if (c->post_tmp) { HIP_TRY(hipFree(c->post_tmp)); c->post_tmp = nullptr; }
-    if (c->d_rgb8) { HIP_TRY(hipFree(c->d_rgb8)); c->d_rgb8 = nullptr; }
-    if (c->accum_total) { HIP_TRY(hipFree(c->accum_total)); c->accum_total = nullptr; }
-    if (c->moments_on) { int mrc = alloc_moments(c, w, h); if (mrc) return mrc; }
+    for (const Plane *p : PLANES) if ((rc = plane_free(c, *p))) return rc;
     if ((rc = remove_mask(c))) return rc;   // the mask is over the old region's tiles
-    if (c->counts_on && (rc = alloc_counts(c, w, h))) return rc;
-    size_t n = (size_t)w * h * 3;
-    HIP_TRY(hipMalloc((void **)&c->accum_own, n * sizeof(float)));
-    HIP_TRY(hipMemset(c->accum_own, 0, n * sizeof(float)));
-    HIP_TRY(hipMalloc((void **)&c->post_tmp, n * sizeof(float)));
-    HIP_TRY(hipMalloc((void **)&c->d_rgb8, n));
+    c->RW = w; c->RH = h;   // what sizes a plane; W stays 0 — no target — until every plane is there
+    for (const Plane *p : PLANES)
+        if ((p->life == WITH_TARGET || (p->life == WITH_OPTION && c->*p->on)) && (rc = plane_alloc(c, *p))) { c->RW = c->RH = 0; return rc; }
     c->W = W; c->H = H;
-    c->RX = x0; c->RY = y0; c->RW = w; c->RH = h;
+    c->RX = x0; c->RY = y0;
     c->accum = c->accum_own;
     return govern_reset(c);
 }
 static bool has_region(const hr_ctx *c) { return c->RW != c->W || c->RH != c->H; }
+// What the debug entry points refuse, after their own argument check, in this order: a region, a tile mask, no target, no scene.  `needs` says
+// which of the four an entry point asks for.
+enum { NO_REGION = 1, NO_MASK = 2, A_TARGET = 4, A_SCENE = 8 };
+static int debug_refusal(const hr_ctx *c, const char *who, int needs) {
+    if ((needs & NO_REGION) && has_region(c)) return fail(HR_ERR_UNSUPPORTED, "%s: not while a region is set (hr_set_region)", who);
+    if ((needs & NO_MASK) && c->mask_on) return fail(HR_ERR_UNSUPPORTED, "%s: not while a tile mask is set (hr_set_tile_mask)", who);
+    if ((needs & A_TARGET) && (!c->accum || !c->W)) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", who);
+    if ((needs & A_SCENE) && !c->have_scene) return fail(HR_ERR_NO_SCENE, "%s: no scene uploaded", who);
+    return HR_OK;
+}
 
 int hr_set_resolution(hr_ctx *c, uint32_t w, uint32_t h) {
     if (!c || !w || !h) return fail(HR_ERR_INVALID, "hr_set_resolution: bad argument");
@@ -851,10 +917,10 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
     if (!c) return fail(HR_ERR_INVALID, "hr_bind_accumulator: null ctx");
     if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_bind_accumulator: hr_set_resolution not called");
     HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = plane_bytes(c, ACCUM_OWN);
     if (device_rgb) {
         // what can be checked of a caller's pointer is checked: device memory, of this context's device, float-aligned, and w x h x 3 floats
         // (the region's) inside the allocation it points into (a tensor of another shape or dtype would otherwise be overrun by plain stores, silently)
-        const size_t need = (size_t)c->RW * c->RH * 3 * sizeof(float);
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, device_rgb) != hipSuccess || at.type != hipMemoryTypeDevice) {
             (void)hipGetLastError();
@@ -865,9 +931,9 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
         void *base = nullptr;
         size_t size = 0;
         if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)device_rgb) == hipSuccess) {
-            if ((const char *)device_rgb + need > (const char *)base + size)
+            if ((const char *)device_rgb + bytes > (const char *)base + size)
                 return fail(HR_ERR_INVALID, "hr_bind_accumulator: the buffer is too small (%zu bytes from this address to the end of its allocation, %u x %u x 3 floats = %zu needed)",
-                            (size_t)((const char *)base + size - (const char *)device_rgb), c->RW, c->RH, need);
+                            (size_t)((const char *)base + size - (const char *)device_rgb), c->RW, c->RH, bytes);
         } else (void)hipGetLastError();
     }
     int rc = sync_all(c);
@@ -877,7 +943,6 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
         // cannot both pass.  The registry holds byte ranges: a buffer that overlaps another context's is refused like an equal one.
         // (The caller binds NULL before it frees a bound buffer: an entry left behind would refuse whoever is handed the address next.)
         std::lock_guard<std::mutex> lk(g_bound_mu);
-        const size_t bytes = (size_t)c->RW * c->RH * 3 * sizeof(float);
         if (device_rgb)
             for (const auto &kv : g_bound) {
                 const char *a = (const char *)kv.first, *b = (const char *)device_rgb;
@@ -909,12 +974,11 @@ int hr_clear(hr_ctx *c) {
     int rc = sync_all(c);
     if (rc) return rc;
     invalidate_totals(c);
-    HIP_TRY(hipMemsetAsync(c->accum, 0, (size_t)c->RW * c->RH * 3 * sizeof(float), c->stream));
+    // the planes the table marks, the accumulator through c->accum (it may be the caller's bound buffer); the tile mask stays: a setting, like the region
+    for (const Plane *p : PLANES)
+        if (p->at_clear && (rc = plane_zero(c, *p, c->stream, p == &ACCUM_OWN ? c->accum : nullptr))) return rc;
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
-    if (c->moments) HIP_TRY(hipMemsetAsync(c->moments, 0, (size_t)c->RW * c->RH * 6 * sizeof(double), c->stream));
-    if (c->counts) HIP_TRY(hipMemsetAsync(c->counts, 0, (size_t)c->RW * c->RH * sizeof(uint32_t), c->stream));   // (the tile mask stays: a setting, like the region)
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->moments_n = 0;
     c->seed_ms = c->trace_ms = c->post_ms = c->debug_ms = 0;
     c->seed_launches = c->trace_launches = c->debug_launches = 0;
     c->paths_rendered = 0;
@@ -1186,7 +1250,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->trace_done[slot], c->stream));
         c->trace_pending[slot] = true;
-        c->paths_rendered += (list ? c->mask_pixels : (uint64_t)c->RW * c->RH) * 4 * nk;
+        c->paths_rendered += (list ? c->mask_pixels : (uint64_t)region_pixels(c)) * 4 * nk;
         if (c->trace_events.size() >= 64 && c->seed_events.size() == c->trace_events.size()) retire_finished_launches(c);
         if (c->trace_events.size() > 4096) {  // (never reached while launches finish: the host would have to be 4,096 launches ahead)
             if ((rc = sync_all(c))) return rc;
@@ -1197,10 +1261,11 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
 
 int hr_render_debug(hr_ctx *c, int mode) {
     if (!c || mode < 0 || mode > 3) return fail(HR_ERR_INVALID, "hr_render_debug: mode must be 0..3");
-    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_render_debug: no scene uploaded");
-    if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_render_debug: hr_set_resolution not called");
+    // (this entry point has always asked in an order of its own — scene, target, moments, mask, counts — and renders a region: one need at a time)
+    int rc;
+    if ((rc = debug_refusal(c, "hr_render_debug", A_SCENE)) || (rc = debug_refusal(c, "hr_render_debug", A_TARGET))) return rc;
     if (c->moments_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option moments on (a debug sampling goes into the accumulator without per-sampling values)");
-    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not while a tile mask is set (hr_set_tile_mask)");
+    if ((rc = debug_refusal(c, "hr_render_debug", NO_MASK))) return rc;
     if (c->counts_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option sample_counts on (a debug sampling goes into the accumulator without being counted)");
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
@@ -1255,38 +1320,12 @@ int hr_wait(hr_ctx *c, uint64_t ticket) {
 int hr_read_accumulator(hr_ctx *c, float *host) {
     if (!c || !host) return fail(HR_ERR_INVALID, "hr_read_accumulator: null argument");
     if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_read_accumulator: no accumulator");
-    int rc = hr_synchronize(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(host, c->total_valid ? c->accum_total : c->accum, (size_t)c->RW * c->RH * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return HR_OK;
+    return plane_read(c, ACCUM_OWN, c->total_valid ? c->accum_total : c->accum, host);
 }
 int hr_write_accumulator(hr_ctx *c, const float *host) {
     if (!c || !host) return fail(HR_ERR_INVALID, "hr_write_accumulator: null argument");
     if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_write_accumulator: no accumulator");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    invalidate_totals(c);
-    HIP_TRY(hipMemcpy(c->accum, host, (size_t)c->RW * c->RH * 3 * sizeof(float), hipMemcpyHostToDevice));
-    return HR_OK;
-}
-
-int hr_resolve(hr_ctx *c, uint32_t samplings, uint8_t *host_rgb8) {
-    if (!c || !host_rgb8 || !samplings) return fail(HR_ERR_INVALID, "hr_resolve: bad argument");
-    if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_resolve: no accumulator");
-    int rc = hr_synchronize(c);
-    if (rc) return rc;
-    // the region's accumulator is resolved as an image of its own: the bilateral filter's clamp and wrap act at the region's edges
-    uint32_t n = c->RW * c->RH;
-    float scale = 1.0f / (float)(samplings * 4u);
-    EventPair ev;
-    HIP_TRY(timed_begin(ev, c->stream));
-    hipLaunchKernelGGL(tonemap_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->total_valid ? c->accum_total : c->accum, c->post_tmp, n, scale);
-    hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->RW, c->RH);
-    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
-    HIP_TRY(hipMemcpyAsync(host_rgb8, c->d_rgb8, (size_t)n * 3, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return drain_events(c);
+    return plane_write(c, ACCUM_OWN, c->accum, host);
 }
 
 // ---- multi-GPU: one all-reduce of the accumulators over RCCL (hr_comm.h) ------------------------------------------------------
@@ -1310,7 +1349,7 @@ __global__ void add_accumulator_kernel(float *__restrict__ total, const float *_
 }
 static int comm_release(hr_ctx *c) {
     if (c->comm) { NCCL_TRY(hrcomm::api().CommDestroy(c->comm)); c->comm = nullptr; }
-    for (hr_ctx *p : c->same_device_peers) if (p != c) { p->same_device_peers.clear(); p->comm_world = 0; p->total_valid = false; p->comm_path = HR_COMM_NONE; p->allreduces = 0; }
+    reset_same_device_peers(c);
     c->same_device_peers.clear();
     c->comm_world = 0; c->comm_rank = 0; c->total_valid = false;
     c->comm_path = HR_COMM_NONE; c->allreduces = 0;
@@ -1367,8 +1406,8 @@ static int allreduce_enqueue(hr_ctx *c) {
     if (!c->comm && c->same_device_peers.empty()) return fail(HR_ERR_INVALID, "hr_allreduce_accumulator: no communicator (hr_comm_init_rank / hr_comm_init_local)");
     if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_allreduce_accumulator: no accumulator");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)c->RW * c->RH * 3;
-    if (!c->accum_total) HIP_TRY(hipMalloc((void **)&c->accum_total, n * sizeof(float)));
+    const size_t n = plane_elems(c, ACCUM_OWN);
+    if (!c->accum_total) { int rc = plane_alloc(c, ACCUM_TOTAL); if (rc) return rc; }
     if (!c->same_device_peers.empty()) {
         for (hr_ctx *p : c->same_device_peers) {
             if (p->W != c->W || p->H != c->H || p->RX != c->RX || p->RY != c->RY || p->RW != c->RW || p->RH != c->RH || !p->accum)
@@ -1378,7 +1417,7 @@ static int allreduce_enqueue(hr_ctx *c) {
         // rank order, so that every context of the group gets bit-identical totals (as an all-reduce delivers them)
         int rc = sync_all(c);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(c->accum_total, c->same_device_peers[0]->accum, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->accum_total, c->same_device_peers[0]->accum, plane_bytes(c, ACCUM_OWN), hipMemcpyDeviceToDevice, c->stream));
         for (size_t k = 1; k < c->same_device_peers.size(); k++)
             hipLaunchKernelGGL(add_accumulator_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->accum_total, c->same_device_peers[k]->accum, n);
         HIP_TRY(hipGetLastError());
@@ -1468,42 +1507,29 @@ int hr_accumulator_sum(hr_ctx *c, int which, double out_rgb[3]) {
     if (which == 1 && !c->total_valid) return fail(HR_ERR_INVALID, "hr_accumulator_sum: no all-reduced total (hr_allreduce_accumulator first)");
     int rc = hr_synchronize(c);
     if (rc) return rc;
+    CallScratch scratch;
     double *d = nullptr;
     std::vector<double> h(ACC_SUM_BLOCKS * 3);
-    HIP_TRY(hipMalloc((void **)&d, h.size() * sizeof(double)));
-    hipLaunchKernelGGL(accumulator_sum_kernel, dim3(ACC_SUM_BLOCKS), dim3(256), 0, c->stream, which ? c->accum_total : c->accum, (size_t)c->RW * c->RH, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "hr_accumulator_sum: %s", hipGetErrorString(e));
+    HIP_TRY(scratch.alloc((void **)&d, h.size() * sizeof(double)));
+    hipLaunchKernelGGL(accumulator_sum_kernel, dim3(ACC_SUM_BLOCKS), dim3(256), 0, c->stream, which ? c->accum_total : c->accum, region_pixels(c), d);
+    HIP_TRY_AS("hr_accumulator_sum", hipGetLastError());
+    HIP_TRY_AS("hr_accumulator_sum", hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY_AS("hr_accumulator_sum", hipStreamSynchronize(c->stream));
     out_rgb[0] = out_rgb[1] = out_rgb[2] = 0.0;
     for (unsigned b = 0; b < ACC_SUM_BLOCKS; b++) for (int k = 0; k < 3; k++) out_rgb[k] += h[b * 3 + k];
     return HR_OK;
 }
 
 // ---- option "moments": the moments, and the noise estimate made of them (noise_core.h) ----
-static int moments_ready(hr_ctx *c, const char *who) {
-    if (!c) return fail(HR_ERR_INVALID, "%s: null ctx", who);
-    if (!c->moments_on || !c->moments) return fail(HR_ERR_INVALID, "%s: option moments is off", who);
-    return HR_OK;
-}
 int hr_read_moments(hr_ctx *c, double *host, uint64_t *samplings) {
-    int rc = moments_ready(c, "hr_read_moments");
+    int rc = option_plane_read(c, MOMENTS, "hr_read_moments", host);
     if (rc) return rc;
-    if (!host) return fail(HR_ERR_INVALID, "hr_read_moments: null argument");
-    if ((rc = hr_synchronize(c))) return rc;
-    HIP_TRY(hipMemcpy(host, c->moments, (size_t)c->RW * c->RH * 6 * sizeof(double), hipMemcpyDeviceToHost));
     if (samplings) *samplings = c->moments_n;
     return HR_OK;
 }
 int hr_write_moments(hr_ctx *c, const double *host, uint64_t samplings) {
-    int rc = moments_ready(c, "hr_write_moments");
+    int rc = option_plane_write(c, MOMENTS, "hr_write_moments", host);
     if (rc) return rc;
-    if (!host) return fail(HR_ERR_INVALID, "hr_write_moments: null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = sync_all(c))) return rc;
-    HIP_TRY(hipMemcpy(c->moments, host, (size_t)c->RW * c->RH * 6 * sizeof(double), hipMemcpyHostToDevice));
     c->moments_n = samplings;
     return HR_OK;
 }
@@ -1560,9 +1586,14 @@ __global__ __launch_bounds__(256) void counts_min_kernel(const uint32_t *__restr
     }
     if ((threadIdx.x & 63u) == 0u) { atomicMin(out, mn); atomicMax(out + 1, mx); }
 }
-static int counts_cover_an_estimate(hr_ctx *c, const char *who) {
-    const size_t pixels = (size_t)c->RW * c->RH;
+static int select_out_buffer(hr_ctx *c) {
     if (!c->d_select_out) HIP_TRY(hipMalloc((void **)&c->d_select_out, 3 * sizeof(uint32_t)));
+    return HR_OK;
+}
+static int counts_cover_an_estimate(hr_ctx *c, const char *who) {
+    const size_t pixels = region_pixels(c);
+    int rc = select_out_buffer(c);
+    if (rc) return rc;
     uint32_t mm[2] = {0xffffffffu, 0u};
     HIP_TRY(hipMemcpyAsync(c->d_select_out + 1, mm, sizeof mm, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));   // (mm is on the stack)
@@ -1578,26 +1609,25 @@ static int counts_cover_an_estimate(hr_ctx *c, const char *who) {
 }
 // host_img: the image as well (or NULL); est: the summary (or NULL)
 static int noise_run(hr_ctx *c, const char *who, double floor, double threshold, double *host_img, hr_noise *est) {
-    int rc = moments_ready(c, who);
+    int rc = plane_ready(c, MOMENTS, who);
     if (rc) return rc;
     if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "%s: floor must be a positive finite radiance", who);
     if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
     if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
     if ((rc = hr_synchronize(c))) return rc;
     if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;
-    const size_t pixels = (size_t)c->RW * c->RH;
-    if (!c->noise_img) HIP_TRY(hipMalloc((void **)&c->noise_img, pixels * sizeof(double)));
+    const size_t pixels = region_pixels(c);
+    if (!c->noise_img && (rc = plane_alloc(c, NOISE_IMG))) return rc;
+    CallScratch scratch;
     double *d = nullptr;
     std::vector<double> h(NOISE_BLOCKS * 3);
-    HIP_TRY(hipMalloc((void **)&d, h.size() * sizeof(double)));
+    HIP_TRY(scratch.alloc((void **)&d, h.size() * sizeof(double)));
     if (c->counts) hipLaunchKernelGGL(noise_kernel<true>, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d, c->counts);
     else hipLaunchKernelGGL(noise_kernel<false>, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d, (const uint32_t *)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && host_img) e = hipMemcpyAsync(host_img, c->noise_img, pixels * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    HIP_TRY_AS(who, hipGetLastError());
+    HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (host_img) HIP_TRY_AS(who, hipMemcpyAsync(host_img, c->noise_img, plane_bytes(c, NOISE_IMG), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
     if (est) {
         double sum = 0.0, mx = 0.0, above = 0.0;
         for (unsigned b = 0; b < NOISE_BLOCKS; b++) { sum += h[b * 3]; mx = h[b * 3 + 1] > mx ? h[b * 3 + 1] : mx; above += h[b * 3 + 2]; }
@@ -1619,28 +1649,8 @@ int hr_read_noise_image(hr_ctx *c, double floor, double *host) {
 }
 
 // ---- option "sample_counts", the tile mask and the selection of tiles (adapt_core.h) ----
-static int counts_ready(hr_ctx *c, const char *who) {
-    if (!c) return fail(HR_ERR_INVALID, "%s: null ctx", who);
-    if (!c->counts_on || !c->counts) return fail(HR_ERR_INVALID, "%s: option sample_counts is off", who);
-    return HR_OK;
-}
-int hr_read_sample_counts(hr_ctx *c, uint32_t *host) {
-    int rc = counts_ready(c, "hr_read_sample_counts");
-    if (rc) return rc;
-    if (!host) return fail(HR_ERR_INVALID, "hr_read_sample_counts: null argument");
-    if ((rc = hr_synchronize(c))) return rc;
-    HIP_TRY(hipMemcpy(host, c->counts, (size_t)c->RW * c->RH * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return HR_OK;
-}
-int hr_write_sample_counts(hr_ctx *c, const uint32_t *host) {
-    int rc = counts_ready(c, "hr_write_sample_counts");
-    if (rc) return rc;
-    if (!host) return fail(HR_ERR_INVALID, "hr_write_sample_counts: null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = sync_all(c))) return rc;
-    HIP_TRY(hipMemcpy(c->counts, host, (size_t)c->RW * c->RH * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return HR_OK;
-}
+int hr_read_sample_counts(hr_ctx *c, uint32_t *host) { return option_plane_read(c, COUNTS, "hr_read_sample_counts", host); }
+int hr_write_sample_counts(hr_ctx *c, const uint32_t *host) { return option_plane_write(c, COUNTS, "hr_write_sample_counts", host); }
 
 // hr_resolve's first kernel with every pixel's own count: the scale is hr_resolve's expression 1.0f / (float)(count * 4u), which hr_resolve works
 // out on the host, i.e. correctly rounded.  The device's fp32 division is not (the Makefile trades that for speed), so the quotient is taken in
@@ -1654,21 +1664,35 @@ __global__ void tonemap_gamma_counted_kernel(const float *__restrict__ acc, cons
     if (k) tonemap_gamma(acc[i * 3], acc[i * 3 + 1], acc[i * 3 + 2], (float)(1.0 / (double)(float)(k * 4u)), &out[i * 3]);
     else tonemap_gamma(0.0f, 0.0f, 0.0f, 0.0f, &out[i * 3]);
 }
+// The resolve behind hr_resolve (every pixel scaled by 1 / (4 samplings)) and hr_resolve_counted (samplings == 0: by its own count): the first
+// kernel differs, the rest is one.  The region's accumulator is resolved as an image of its own: the bilateral filter's clamp and wrap act at
+// the region's edges.
+static int resolve_region(hr_ctx *c, uint32_t samplings, uint8_t *host_rgb8) {
+    int rc = hr_synchronize(c);
+    if (rc) return rc;
+    const uint32_t n = (uint32_t)region_pixels(c);
+    const float *acc = c->total_valid ? c->accum_total : c->accum;
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    if (samplings) hipLaunchKernelGGL(tonemap_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, acc, c->post_tmp, n, 1.0f / (float)(samplings * 4u));
+    else hipLaunchKernelGGL(tonemap_gamma_counted_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, acc, c->counts, c->post_tmp, n);
+    hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->RW, c->RH);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY(hipMemcpyAsync(host_rgb8, c->d_rgb8, plane_bytes(c, RGB8), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return drain_events(c);
+}
+int hr_resolve(hr_ctx *c, uint32_t samplings, uint8_t *host_rgb8) {
+    if (!c || !host_rgb8 || !samplings) return fail(HR_ERR_INVALID, "hr_resolve: bad argument");
+    if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_resolve: no accumulator");
+    return resolve_region(c, samplings, host_rgb8);
+}
 int hr_resolve_counted(hr_ctx *c, uint8_t *host_rgb8) {
-    int rc = counts_ready(c, "hr_resolve_counted");
+    int rc = plane_ready(c, COUNTS, "hr_resolve_counted");
     if (rc) return rc;
     if (!host_rgb8) return fail(HR_ERR_INVALID, "hr_resolve_counted: null argument");
     if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_resolve_counted: no accumulator");
-    if ((rc = hr_synchronize(c))) return rc;
-    const uint32_t n = c->RW * c->RH;
-    EventPair ev;
-    HIP_TRY(timed_begin(ev, c->stream));
-    hipLaunchKernelGGL(tonemap_gamma_counted_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->total_valid ? c->accum_total : c->accum, c->counts, c->post_tmp, n);
-    hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->RW, c->RH);
-    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
-    HIP_TRY(hipMemcpyAsync(host_rgb8, c->d_rgb8, (size_t)n * 3, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return drain_events(c);
+    return resolve_region(c, 0, host_rgb8);
 }
 
 // the mask's host side from its flags: the count of active tiles and of their in-region pixels
@@ -1685,8 +1709,7 @@ static void mask_totals(hr_ctx *c) {
 static int mask_buffers(hr_ctx *c, uint32_t tiles) {
     if (!c->d_tile_list) HIP_TRY(hipMalloc((void **)&c->d_tile_list, (size_t)tiles * sizeof(uint32_t)));
     if (!c->d_tile_flags) HIP_TRY(hipMalloc((void **)&c->d_tile_flags, (size_t)tiles * sizeof(uint32_t)));
-    if (!c->d_select_out) HIP_TRY(hipMalloc((void **)&c->d_select_out, 3 * sizeof(uint32_t)));
-    return HR_OK;
+    return select_out_buffer(c);
 }
 int hr_set_tile_mask(hr_ctx *c, const uint8_t *mask) {
     if (!c) return fail(HR_ERR_INVALID, "hr_set_tile_mask: null ctx");
@@ -1729,9 +1752,9 @@ __global__ __launch_bounds__(256) void select_tiles_kernel(RenderParams rp, cons
     if (pix == 0u && tile < tiles) flags[tile] = any && (!have_prev || flags[tile] != 0u) ? 1u : 0u;
 }
 int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active) {
-    int rc = moments_ready(c, "hr_select_tiles");
+    int rc = plane_ready(c, MOMENTS, "hr_select_tiles");
     if (rc) return rc;
-    if ((rc = counts_ready(c, "hr_select_tiles"))) return rc;
+    if ((rc = plane_ready(c, COUNTS, "hr_select_tiles"))) return rc;
     if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "hr_select_tiles: floor must be a positive finite radiance");
     if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "hr_select_tiles: threshold must not be negative");
     if ((rc = hr_synchronize(c))) return rc;   // (also: no kernel is reading the list that is about to be rewritten)
@@ -1744,7 +1767,7 @@ int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active)
     size_t need = 0;
     HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, need, indices, c->d_tile_flags, c->d_tile_list, c->d_select_out, (int)tiles, c->stream));
     if (need > c->select_tmp_bytes) {
-        if (c->select_tmp) { HIP_TRY(hipFree(c->select_tmp)); c->select_tmp = nullptr; }
+        if ((rc = free_device(c->select_tmp))) return rc;
         c->select_tmp_bytes = 0;
         HIP_TRY(hipMalloc(&c->select_tmp, std::max<size_t>(need, 16)));
         c->select_tmp_bytes = std::max<size_t>(need, 16);
@@ -1865,37 +1888,34 @@ static int apply_option(hr_ctx *c, const OptionRow &r, double value) {
     return r.flags & OPT_GOVERN ? govern_reset(c) : HR_OK;
 }
 
+// An option that owns a plane (`p.option`, `p.on`).  Off: `off_first`, then the plane goes.  On: the plane is allocated, zeroed — a failed
+// allocation leaves the option off —, and `other`, when it is already running, starts over with it: the counts are the moments' n, the two
+// must cover the same samplings (the accumulator stays).  Set on while on: what has been gathered stays.
+static int set_plane_option(hr_ctx *c, double value, const Plane &p, const Plane &other, int (*off_first)(hr_ctx *)) {
+    if (value != 0 && value != 1) return fail(HR_ERR_INVALID, "%s must be 0 or 1", p.option);
+    if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", p.option);
+    int rc = sync_all(c);
+    if (rc) return rc;
+    if (value == 0) {
+        c->*p.on = false;
+        if ((rc = off_first(c))) return rc;
+        return plane_free(c, p);
+    }
+    if (c->*p.on) return HR_OK;
+    if ((rc = plane_alloc(c, p))) { (void)plane_free(c, p); return rc; }
+    c->*p.on = true;
+    return plane_zero(c, other);
+}
+
 int hr_set_option(hr_ctx *c, const char *key, double value) {
     if (!c || !key) return fail(HR_ERR_INVALID, "hr_set_option: null argument");
     HIP_TRY(hipSetDevice(c->device));
     std::string k = key;
     if (const OptionRow *row = find_row(PRODUCT_OPTIONS, [&](const OptionRow &r) { return k == r.key; })) return apply_option(c, *row, value);
-    if (k == "moments") {   // per-pixel first and second moments of the per-sampling values, for the noise estimate
-        if (value != 0 && value != 1) return fail(HR_ERR_INVALID, "moments must be 0 or 1");
-        if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "moments: hr_set_resolution not called");
-        int rc = sync_all(c);
-        if (rc) return rc;
-        if (value == 0) { c->moments_on = false; return free_moments(c); }
-        if (c->moments_on) return HR_OK;   // already on: the moments gathered so far stay
-        if ((rc = alloc_moments(c, c->RW, c->RH))) { (void)free_moments(c); return rc; }
-        c->moments_on = true;
-        // the counts are the moments' n: they cover the same samplings, so counts that are already running start over with the moments
-        if (c->counts) { HIP_TRY(hipMemset(c->counts, 0, (size_t)c->RW * c->RH * sizeof(uint32_t))); HIP_TRY(hipStreamSynchronize(nullptr)); }
-        return HR_OK;
-    }
-    if (k == "sample_counts") {   // how many samplings every pixel has received: what a tile mask (hr_set_tile_mask) needs
-        if (value != 0 && value != 1) return fail(HR_ERR_INVALID, "sample_counts must be 0 or 1");
-        if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "sample_counts: hr_set_resolution not called");
-        int rc = sync_all(c);
-        if (rc) return rc;
-        if (value == 0) { c->counts_on = false; if ((rc = remove_mask(c))) return rc; return free_counts(c); }
-        if (c->counts_on) return HR_OK;   // already on: the counts gathered so far stay
-        if ((rc = alloc_counts(c, c->RW, c->RH))) { (void)free_counts(c); return rc; }
-        c->counts_on = true;
-        // ... and moments that are already running start over with the counts (the accumulator stays, as it does when the moments are switched on)
-        if (c->moments) { HIP_TRY(hipMemset(c->moments, 0, (size_t)c->RW * c->RH * 6 * sizeof(double))); HIP_TRY(hipStreamSynchronize(nullptr)); c->moments_n = 0; }
-        return HR_OK;
-    }
+    // per-pixel first and second moments of the per-sampling values, for the noise estimate, and how many samplings every pixel
+    // has received: what a tile mask (hr_set_tile_mask) needs — the mask goes when the counts go
+    if (k == "moments") return set_plane_option(c, value, MOMENTS, COUNTS, [](hr_ctx *x) { return plane_free(x, NOISE_IMG); });
+    if (k == "sample_counts") return set_plane_option(c, value, COUNTS, MOMENTS, remove_mask);
     if (k == "max_tail_gib") {
         if (value < 1 || value > 128) return fail(HR_ERR_INVALID, "max_tail_gib must be in [1,128]");
         c->max_tail_bytes = (uint64_t)value << 30;
@@ -1942,21 +1962,19 @@ int hr_set_debug_option(hr_ctx *c, const char *key, double value) {
 
 int hr_debug_draws(hr_ctx *c, uint32_t sampling, uint32_t first_path, uint32_t num_paths, uint32_t window, uint64_t *host_out) {
     if (!c || !host_out || !num_paths) return fail(HR_ERR_INVALID, "hr_debug_draws: bad argument");
-    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_draws: not while a region is set (hr_set_region)");
-    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_draws: not while a tile mask is set (hr_set_tile_mask)");
-    if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_draws: hr_set_resolution not called");
+    int rc = debug_refusal(c, "hr_debug_draws", NO_REGION | NO_MASK | A_TARGET);
+    if (rc) return rc;
     if (window == 0 || window > (uint32_t)ISAAC_TAIL) return fail(HR_ERR_INVALID, "window must be in [1,%d]", ISAAC_TAIL);
     if ((uint64_t)first_path + num_paths > (uint64_t)c->W * c->H * 4) return fail(HR_ERR_INVALID, "path range outside the image");
     HIP_TRY(hipSetDevice(c->device));
+    CallScratch scratch;
     u64 *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, (size_t)num_paths * window * 8));
+    HIP_TRY(scratch.alloc((void **)&d, (size_t)num_paths * window * 8));
     hipLaunchKernelGGL(seed_debug_kernel, dim3((num_paths + 63) / 64), dim3(64), 256 * 64 * 8, c->stream, c->W, c->H, sampling, first_path, num_paths,
                        (int)window, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(host_out, d, (size_t)num_paths * window * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "hr_debug_draws: %s", hipGetErrorString(e));
+    HIP_TRY_AS("hr_debug_draws", hipGetLastError());
+    HIP_TRY_AS("hr_debug_draws", hipStreamSynchronize(c->stream));
+    HIP_TRY_AS("hr_debug_draws", hipMemcpy(host_out, d, (size_t)num_paths * window * 8, hipMemcpyDeviceToHost));
     return HR_OK;
 }
 
@@ -1964,14 +1982,12 @@ static int path_draws_out(hr_ctx *c, uint32_t sampling, float *host_out, bool re
     // the 20 fp32 draws per path exactly as the production seed kernel hands them to the trace kernel (residuals: the same slots of the
     // records' twin), re-ordered to pixel-major paths: out[((y*W + x)*4 + sub) * 20 + d]
     if (!c || !host_out) return fail(HR_ERR_INVALID, "%s: bad argument", who);
-    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "%s: not while a region is set (hr_set_region)", who);
-    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "%s: not while a tile mask is set (hr_set_tile_mask)", who);
-    if (!c->W) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", who);
-    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "%s: no scene (lens shape needed)", who);
+    int rc = debug_refusal(c, who, NO_REGION | NO_MASK | A_TARGET);
+    if (rc) return rc;
+    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "%s: no scene (lens shape needed)", who);   // (a text of its own)
     if (residuals && !draws_twin(c)) return fail(HR_ERR_UNSUPPORTED, "%s: no residuals are written (needs precise shading in force, seed_mode 2, draw_residuals 1)", who);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
+    if ((rc = sync_all(c))) return rc;
     LaunchPlan plan;
     if ((rc = plan_launch(c, sampling, 1, 1, TRACE_NONE, plan))) return rc;   // (no region: refused above)
     RenderParams &rp = plan.rp;
@@ -2013,13 +2029,10 @@ int hr_debug_path_log(hr_ctx *c, uint32_t sampling, uint32_t *host_out) {
     // one sampling through the production pipeline — the seed kernel, then the LOG instantiation of trace_kernel (same traversal, same
     // path_advance) — with every path's radiance, ray count and event log written out instead of being accumulated
     if (!c || !host_out) return fail(HR_ERR_INVALID, "hr_debug_path_log: bad argument");
-    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_path_log: not while a region is set (hr_set_region)");
-    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_path_log: not while a tile mask is set (hr_set_tile_mask)");
-    if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_path_log: hr_set_resolution not called");
-    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_path_log: no scene uploaded");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
+    int rc = debug_refusal(c, "hr_debug_path_log", NO_REGION | NO_MASK | A_TARGET | A_SCENE);
     if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = sync_all(c))) return rc;
     LaunchPlan plan;
     if ((rc = plan_launch(c, sampling, 1, 1, TRACE_IN_FORCE, plan))) return rc;   // (no region: refused above)
     const RenderParams &rp = plan.rp;
@@ -2028,34 +2041,26 @@ int hr_debug_path_log(hr_ctx *c, uint32_t sampling, uint32_t *host_out) {
     if (!split && !trace) return fail(HR_ERR_UNSUPPORTED, "hr_debug_path_log: no trace kernel instantiation for these options (kernel_variants.h)");
     if ((rc = launch_seed(c, rp, 0, c->stream))) return rc;   // on the main stream, slot 0: nothing else is in flight
     const size_t words = (size_t)c->W * c->H * 4u * 8u;
+    CallScratch scratch;
     uint32_t *d_log = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_log, words * sizeof(uint32_t)));
-    hipError_t e = hipMemsetAsync(d_log, 0, words * sizeof(uint32_t), c->stream);
-    void *log_block = nullptr;
-    if (e == hipSuccess && split) {
+    HIP_TRY(scratch.alloc((void **)&d_log, words * sizeof(uint32_t)));
+    HIP_TRY_AS("hr_debug_path_log", hipMemsetAsync(d_log, 0, words * sizeof(uint32_t), c->stream));
+    if (split) {
         // the split pipeline's LOG instantiation: the event log rides in two more state quads and a tag per ray slot, allocated for this call only
         WfQueues wq = c->wf;
         const size_t st_q = (size_t)wq.cap_paths * WF_SUBQ * sizeof(f4), tg_q = (size_t)wq.cap_rays * WF_SUBQ * sizeof(uint32_t);
-        e = hipMalloc(&log_block, 2 * st_q + 2 * tg_q);
-        if (e == hipSuccess) {
-            char *b = (char *)log_block;
-            for (int i = 0; i < 2; i++) { wq.st_f[i] = (f4 *)b; b += st_q; }
-            for (int i = 0; i < 2; i++) { wq.tag[i] = (uint32_t *)b; b += tg_q; }
-            rc = launch_split(c, rp, 0, nullptr, d_log, &wq);
-            if (rc) { (void)hipFree(log_block); (void)hipFree(d_log); return rc; }
-        }
-    } else if (e == hipSuccess) {
-        e = hipMemsetAsync(c->d_tile_counter, 0, sizeof(uint32_t), c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(trace, dim3(trace_grid_size(c, plan.tiles, 1, 0)), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, c->recs[0], c->d_counters, c->d_tile_counter, d_log);
-            e = hipGetLastError();
-        }
+        char *b = nullptr;
+        HIP_TRY_AS("hr_debug_path_log", scratch.alloc((void **)&b, 2 * st_q + 2 * tg_q));
+        for (int i = 0; i < 2; i++) { wq.st_f[i] = (f4 *)b; b += st_q; }
+        for (int i = 0; i < 2; i++) { wq.tag[i] = (uint32_t *)b; b += tg_q; }
+        if ((rc = launch_split(c, rp, 0, nullptr, d_log, &wq))) return rc;
+    } else {
+        HIP_TRY_AS("hr_debug_path_log", hipMemsetAsync(c->d_tile_counter, 0, sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(trace, dim3(trace_grid_size(c, plan.tiles, 1, 0)), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, c->recs[0], c->d_counters, c->d_tile_counter, d_log);
+        HIP_TRY_AS("hr_debug_path_log", hipGetLastError());
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(host_out, d_log, words * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d_log);
-    if (log_block) (void)hipFree(log_block);
-    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "hr_debug_path_log: %s", hipGetErrorString(e));
+    HIP_TRY_AS("hr_debug_path_log", hipStreamSynchronize(c->stream));
+    HIP_TRY_AS("hr_debug_path_log", hipMemcpy(host_out, d_log, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return drain_events(c);
 }
 
@@ -2063,13 +2068,10 @@ int hr_debug_wf_profile(hr_ctx *c, uint32_t sampling, uint32_t num_k, double *ms
     // one launch of the split pipeline with the chip to itself, an event between every two kernels: ms_out[0] = wf_start_kernel,
     // ms_out[2 s - 1] / ms_out[2 s] = traversal / shading kernel of step s = 1 .. WF_STEPS; counts_out[2 s] / [2 s + 1] = rays / live paths of step s
     if (!c || !ms_out || !counts_out || !num_k) return fail(HR_ERR_INVALID, "hr_debug_wf_profile: bad argument");
-    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_wf_profile: not while a region is set (hr_set_region)");
-    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_wf_profile: not while a tile mask is set (hr_set_tile_mask)");
-    if (!c->W) return fail(HR_ERR_NO_TARGET, "hr_debug_wf_profile: hr_set_resolution not called");
-    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_wf_profile: no scene uploaded");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
+    int rc = debug_refusal(c, "hr_debug_wf_profile", NO_REGION | NO_MASK | A_TARGET | A_SCENE);
     if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = sync_all(c))) return rc;
     LaunchPlan plan;
     if ((rc = plan_launch(c, sampling, 1, num_k, TRACE_SPLIT, plan))) return rc;   // (no region: refused above); the split pipeline whatever is in force
     RenderParams &rp = plan.rp;
@@ -2095,61 +2097,54 @@ int hr_debug_wf_profile(hr_ctx *c, uint32_t sampling, uint32_t num_k, double *ms
 
 int hr_debug_intersect(hr_ctx *c, uint32_t n, const float *rays, float *out, int32_t *out_element) {
     if (!c || !rays || !out || !out_element || !n) return fail(HR_ERR_INVALID, "hr_debug_intersect: bad argument");
-    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_intersect: not while a region is set (hr_set_region)");
-    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_intersect: not while a tile mask is set (hr_set_tile_mask)");
-    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_intersect: no scene uploaded");
+    int rc = debug_refusal(c, "hr_debug_intersect", NO_REGION | NO_MASK | A_SCENE);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    CallScratch scratch;
     float *d_rays = nullptr, *d_out = nullptr;
     int32_t *d_el = nullptr;
-    hipError_t e = hipMalloc((void **)&d_rays, (size_t)n * 6 * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)n * 8 * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_el, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, (size_t)n * 6 * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(intersect_debug_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, n, d_rays, d_out, d_el);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 8 * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_element, d_el, (size_t)n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_rays); (void)hipFree(d_out); (void)hipFree(d_el);
-    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "hr_debug_intersect: %s", hipGetErrorString(e));
+    HIP_TRY_AS("hr_debug_intersect", scratch.alloc((void **)&d_rays, (size_t)n * 6 * 4));
+    HIP_TRY_AS("hr_debug_intersect", scratch.alloc((void **)&d_out, (size_t)n * 8 * 4));
+    HIP_TRY_AS("hr_debug_intersect", scratch.alloc((void **)&d_el, (size_t)n * 4));
+    HIP_TRY_AS("hr_debug_intersect", hipMemcpy(d_rays, rays, (size_t)n * 6 * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(intersect_debug_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, n, d_rays, d_out, d_el);
+    HIP_TRY_AS("hr_debug_intersect", hipGetLastError());
+    HIP_TRY_AS("hr_debug_intersect", hipStreamSynchronize(c->stream));
+    HIP_TRY_AS("hr_debug_intersect", hipMemcpy(out, d_out, (size_t)n * 8 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY_AS("hr_debug_intersect", hipMemcpy(out_element, d_el, (size_t)n * 4, hipMemcpyDeviceToHost));
     return HR_OK;
 }
 
 int hr_debug_trace(hr_ctx *c, uint32_t n, const float *rays, const float *shadow_len, float *out, int32_t *out_element) {
     if (!c || !rays || !out || !out_element || !n) return fail(HR_ERR_INVALID, "hr_debug_trace: bad argument");
-    if (has_region(c)) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: not while a region is set (hr_set_region)");
-    if (c->mask_on) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: not while a tile mask is set (hr_set_tile_mask)");
-    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_debug_trace: no scene uploaded");
+    int rc = debug_refusal(c, "hr_debug_trace", NO_REGION | NO_MASK | A_SCENE);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const TraceDebugFn fn = select_trace_debug_kernel(c->counters, c->dsc.qnodes != nullptr);
     if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_debug_trace: no kernel instantiation for these options (kernel_variants.h)");
+    CallScratch scratch;
     float *d_rays = nullptr, *d_out = nullptr, *d_sl = nullptr;
     int32_t *d_el = nullptr;
-    hipError_t e = hipMalloc((void **)&d_rays, (size_t)n * 6 * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)n * 8 * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_el, (size_t)n * 4);
-    if (e == hipSuccess && shadow_len) e = hipMalloc((void **)&d_sl, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, (size_t)n * 6 * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && shadow_len) e = hipMemcpy(d_sl, shadow_len, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        RenderParams rp{};
-        knob_params(c, rp);   // (no geometry: the rays are the caller's)
-        // the record format hr_render walks on this scene; timed with HIP events (hr_stats.debug_kernel_ms), counted with option "counters".
-        // The timing is best effort: the launch goes out without it if an event cannot be made, and only a pair that was really recorded
-        // is ever queried (timed_end)
-        EventPair ev;
-        (void)timed_begin(ev, c->stream);
-        hipLaunchKernelGGL(fn, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, rp, n, d_rays, d_sl, d_out, d_el, c->counters ? c->d_counters : (Counters *)nullptr);
-        e = hipGetLastError();
-        (void)timed_end(e, ev, c->stream, c->debug_events, &c->debug_launches);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 8 * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_element, d_el, (size_t)n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_rays); (void)hipFree(d_out); (void)hipFree(d_el); (void)hipFree(d_sl);
-    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "hr_debug_trace: %s", hipGetErrorString(e));
+    HIP_TRY_AS("hr_debug_trace", scratch.alloc((void **)&d_rays, (size_t)n * 6 * 4));
+    HIP_TRY_AS("hr_debug_trace", scratch.alloc((void **)&d_out, (size_t)n * 8 * 4));
+    HIP_TRY_AS("hr_debug_trace", scratch.alloc((void **)&d_el, (size_t)n * 4));
+    if (shadow_len) HIP_TRY_AS("hr_debug_trace", scratch.alloc((void **)&d_sl, (size_t)n * 4));
+    HIP_TRY_AS("hr_debug_trace", hipMemcpy(d_rays, rays, (size_t)n * 6 * 4, hipMemcpyHostToDevice));
+    if (shadow_len) HIP_TRY_AS("hr_debug_trace", hipMemcpy(d_sl, shadow_len, (size_t)n * 4, hipMemcpyHostToDevice));
+    RenderParams rp{};
+    knob_params(c, rp);   // (no geometry: the rays are the caller's)
+    // the record format hr_render walks on this scene; timed with HIP events (hr_stats.debug_kernel_ms), counted with option "counters".
+    // The timing is best effort: the launch goes out without it if an event cannot be made, and only a pair that was really recorded
+    // is ever queried (timed_end)
+    EventPair ev;
+    (void)timed_begin(ev, c->stream);
+    hipLaunchKernelGGL(fn, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, rp, n, d_rays, d_sl, d_out, d_el, c->counters ? c->d_counters : (Counters *)nullptr);
+    const hipError_t launched = hipGetLastError();
+    (void)timed_end(launched, ev, c->stream, c->debug_events, &c->debug_launches);
+    HIP_TRY_AS("hr_debug_trace", launched);
+    HIP_TRY_AS("hr_debug_trace", hipStreamSynchronize(c->stream));
+    HIP_TRY_AS("hr_debug_trace", hipMemcpy(out, d_out, (size_t)n * 8 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY_AS("hr_debug_trace", hipMemcpy(out_element, d_el, (size_t)n * 4, hipMemcpyDeviceToHost));
     return drain_events(c);
 }
 

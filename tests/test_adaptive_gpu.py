@@ -361,6 +361,85 @@ def test_refusals(ha, scenes):
         r.close()
 
 
+def test_options_start_each_other_over(ha, scenes):
+    """Switching "moments" or "sample_counts" on zeroes the other one's buffer (the two cover the same samplings) and leaves the accumulator; set
+    on again while on it keeps what has been gathered.  On the frame and on the region of the same size (sides that are no multiples of 4)."""
+    sc, _ = scenes("cornell_mini")
+    r = ha.Renderer(0)
+    try:
+        r.upload_scene(sc)
+        for target in sorted(TARGETS):
+            _retarget(r, target, moments=True, counts=False)
+            r.render(1, 3)
+            acc, (mom, n) = r.read_accumulator(), r.read_moments()
+            assert n == 2 and mom.shape == (RH, RW, 6) and mom.any() and acc.any(), target
+            r.set_option("sample_counts", 1)
+            mom, n = r.read_moments()
+            assert n == 0 and not mom.any(), target
+            assert _same(r.read_accumulator(), acc), target
+            counts = r.read_sample_counts()
+            assert counts.shape == (RH, RW) and not counts.any(), target
+            r.render(3, 5)
+            acc, (mom, n), counts = r.read_accumulator(), r.read_moments(), r.read_sample_counts()
+            assert (counts == 2).all() and n == 2 and mom.any(), target
+            r.set_option("sample_counts", 1)                  # already on: nothing changes
+            assert _same(r.read_accumulator(), acc) and _same(r.read_moments()[0], mom) and r.read_moments()[1] == 2, target
+            assert np.array_equal(r.read_sample_counts(), counts), target
+            r.set_option("moments", 0)
+            r.set_option("moments", 1)
+            assert not r.read_sample_counts().any() and _same(r.read_accumulator(), acc), target
+            mom, n = r.read_moments()
+            assert n == 0 and not mom.any(), target
+    finally:
+        r.close()
+
+
+def test_debug_refusal_precedence(ha, scenes):
+    """What a debug entry point refuses first: a region, then a tile mask, then a missing target, then a missing scene.  Nothing is rendered."""
+    HR_ERR_NO_SCENE = -3
+    rays = np.array([[0, 0, 5, 0, 0, -1]], dtype=np.float32)
+
+    def path_draws(r):
+        out = np.empty((max(r.height, 1), max(r.width, 1), 4, 20), dtype=np.float32)
+        r._check(r.L.hr_debug_path_draws(r._h, 1, out.ctypes.data))
+
+    def four(r):
+        return [(r.debug_path_log, (1,)), (r.debug_wf_profile, (1, 1)), (r.debug_intersect, (rays,)), (r.debug_trace, (rays,))]
+
+    (fw, fh), region = TARGETS["region"]
+    r = ha.Renderer(0)                                      # a resolution and a region, no scene
+    try:
+        r.set_resolution(fw, fh)
+        r.set_region(*region)
+        for fn, args in four(r):
+            code, text = _code(ha, fn, *args)
+            assert code == HR_ERR_UNSUPPORTED and "region" in text, fn
+        r.set_resolution(fw, fh)                            # full frame again
+        for fn, args in four(r):
+            assert _code(ha, fn, *args)[0] == HR_ERR_NO_SCENE, fn
+    finally:
+        r.close()
+    sc, _ = scenes("cornell_mini")
+    r = ha.Renderer(0)                                      # a scene, no resolution
+    try:
+        r.upload_scene(sc)
+        assert _code(ha, r.debug_draws, 1, 0, 64, 8)[0] == HR_ERR_NO_TARGET
+        assert _code(ha, r.debug_path_log, 1)[0] == HR_ERR_NO_TARGET
+    finally:
+        r.close()
+    r = ha.Renderer(0)                                      # a region, counts and a mask: the region is what is named
+    try:
+        r.set_resolution(fw, fh)
+        r.set_region(*region)
+        r.set_option("sample_counts", 1)
+        r.set_tile_mask(MASKS["checker"])
+        for fn, args in four(r) + [(r.debug_draws, (1, 0, 64, 8)), (path_draws, (r,))]:
+            code, text = _code(ha, fn, *args)
+            assert code == HR_ERR_UNSUPPORTED and "region" in text, fn
+    finally:
+        r.close()
+
+
 def _cli(args, cwd):
     import os
     import subprocess
