@@ -700,12 +700,6 @@ static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_i
     LBVH_ALLOC(ploc_pos, u64t, ploc_multi ? n : 1, false)
     LBVH_ALLOC(scan_tmp, unsigned char, scan_bytes, false)
     LBVH_ALLOC(ploc_state, PlocState, 2, false)
-    const uint32_t top_cap = ploc_multi ? std::min<uint32_t>((uint32_t)n, c->ploc_top) : 1u;   // clusters the top-down build may be handed
-    LBVH_ALLOC(top_boxes, float, 6 * (size_t)top_cap, false)
-    LBVH_ALLOC(top_counts, uint32_t, top_cap, false)
-    LBVH_ALLOC(top_left, int32_t, top_cap, false)
-    LBVH_ALLOC(top_right, int32_t, top_cap, false)
-#undef LBVH_ALLOC
     const int T = 256;
     hipStream_t st = c->stream;
     static const char *const who = "device BVH build";
@@ -718,41 +712,49 @@ static int build_bvh_on_device(hr_ctx *c, const HostScene &hs, const Tri *tris_i
     if (ploc_multi) {
         ploc_init_kernel<<<(n + T - 1) / T, T, 0, st>>>(n, cl_a, ploc_state);
         uint32_t *cur = cl_a, *nxt = cl_b;
-        uint32_t m_known = (uint32_t)n;   // the host's upper bound of the cluster count (refreshed every few iterations)
-        for (int it = 0; it < 4096 && m_known > c->ploc_top; it++) {
-            const uint32_t g = (m_known + T - 1) / T;
+        // (the loop's control — the read-back cadence, the end, the stall rule — is lbvh_core.h's PlocLoop, shared with the emulation)
+        PlocLoop loop = ploc_loop_begin((uint32_t)n, c->ploc_top);
+        while (ploc_loop_more(loop)) {
+            const uint32_t g = (loop.m_known + T - 1) / T, it = loop.its;
             const PlocState *sin = ploc_state + (it & 1);
             ploc_nn_kernel<<<g, T, 0, st>>>(w, cur, nn, sin);
-            ploc_role_kernel<<<g, T, 0, st>>>(nn, ploc_flags, m_known, sin);
-            HIP_TRY_AS(who, hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, ploc_flags, ploc_pos, (int)m_known, st));
+            ploc_role_kernel<<<g, T, 0, st>>>(nn, ploc_flags, loop.m_known, sin);
+            HIP_TRY_AS(who, hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, ploc_flags, ploc_pos, (int)loop.m_known, st));
             ploc_merge_kernel<<<g, T, 0, st>>>(w, cur, nxt, nn, ploc_flags, ploc_pos, sin, ploc_state + ((it + 1) & 1));
             std::swap(cur, nxt);
-            if ((it & 3) == 3 || m_known <= 4u * c->ploc_top) {   // every fourth iteration (every one near the end): how many are left?
+            if (ploc_loop_launched(loop)) {   // how many are left?
                 PlocState hs{};
                 HIP_TRY_AS(who, hipMemcpyAsync(&hs, ploc_state + ((it + 1) & 1), sizeof hs, hipMemcpyDeviceToHost, st));
                 HIP_TRY_AS(who, hipStreamSynchronize(st));
-                m_known = hs.m;
+                if (hs.m == 0u || hs.m > loop.m_known) return fail(HR_ERR_DEVICE, "device BVH build: implausible cluster count %u after %u of %d", hs.m, loop.m_known, n);
+                ploc_loop_read(loop, hs.m);
             }
         }
-        HIP_TRY_AS(who, m_known > top_cap ? hipErrorUnknown : hipSuccess);   // (the loop ends at <= ploc_top clusters, the size of the top buffers)
+        const uint32_t m_known = loop.m_known;   // exact: the loop ends on a read-back
         // the top of the tree: binned SAH over the clusters that are left, on the host (a few thousand boxes)
         if (m_known > 1u) {
             const uint32_t m = m_known;
             std::vector<float> hb(6 * (size_t)m);
             std::vector<uint32_t> hc(m);
+            // (sized here, by what is left: <= ploc_top clusters as a rule, up to n of them when the merges stalled)
+            LBVH_ALLOC(top_boxes, float, 6 * (size_t)m, false)
+            LBVH_ALLOC(top_counts, uint32_t, m, false)
+            LBVH_ALLOC(top_left, int32_t, m, false)
+            LBVH_ALLOC(top_right, int32_t, m, false)
             ploc_top_gather_kernel<<<(m + T - 1) / T, T, 0, st>>>(w, cur, m, top_boxes, top_counts);
             HIP_TRY_AS(who, hipMemcpyAsync(hb.data(), top_boxes, hb.size() * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_TRY_AS(who, hipMemcpyAsync(hc.data(), top_counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY_AS(who, hipStreamSynchronize(st));
             std::vector<int32_t> tl, tr;
             build_top_tree(hb.data(), hc.data(), m, tl, tr);
-            HIP_TRY_AS(who, tl.size() != (size_t)m - 1 ? hipErrorUnknown : hipSuccess);
+            if (tl.size() != (size_t)m - 1) return fail(HR_ERR_DEVICE, "device BVH build: the top-down build made %zu inner nodes over %u clusters", tl.size(), m);
             HIP_TRY_AS(who, hipMemcpyAsync(top_left, tl.data(), tl.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
             HIP_TRY_AS(who, hipMemcpyAsync(top_right, tr.data(), tr.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
             ploc_top_apply_kernel<<<(m - 1 + T - 1) / T, T, 0, st>>>(w, m - 1, top_left, top_right, cur);
             HIP_TRY_AS(who, hipStreamSynchronize(st));   // tl / tr are host vectors about to go out of scope
         }
     }
+#undef LBVH_ALLOC
     fit_kernel<<<(n + T - 1) / T, T, 0, st>>>(n, (uint32_t)c->max_leaf, w);
     finish_kernel<<<(N + T - 1) / T, T, 0, st>>>(p, n, w, prim_pos);
     frame_kernel<<<1, 64, 0, st>>>(w, frame);

@@ -318,6 +318,37 @@ HD int ploc_role(const uint32_t *nn, uint32_t i) {
     return i < j ? 1 : 2;
 }
 static const uint32_t PLOC_TOP_CLUSTERS = 8192;   // the merges stop at <= this many clusters; bvh_build.cpp's build_top_tree joins them top-down
+
+// The merge loop's control, one copy for build_bvh_on_device (hr_api.hip) and for the emulation (tests/emu).  The cluster count lives
+// with the kernels; the host knows an upper bound, m_known, that it reads back every fourth iteration (every iteration near the
+// end) and that sizes the grids.  The loop ends when m_known <= top, or when it STALLS: the iterations since the last read-back
+// merged fewer than 1/64 of the clusters each (at least one each).  The clusters that are left, however many, then go to the
+// top-down build.  Some mutual pair exists in every iteration — the pair of smallest union area — but no more than that is
+// promised: when every pair of the search window has the same union area (copies of one primitive, boxes of zero area on a line),
+// or when the boxes are nested in Morton order (concentric spheres), every cluster but one points at the same neighbour and an
+// iteration makes ONE merge.  Real scenes merge a fifth to a half of their clusters per iteration and never come near the bound,
+// which also limits the loop to 64 ln(n) + 128 iterations.
+static const uint32_t PLOC_READ_EVERY = 4, PLOC_STALL_SHIFT = 6;
+struct PlocLoop {
+    uint32_t m_known;   // clusters, as far as the host knows: exact after a read-back
+    uint32_t top;       // the merges stop at <= top clusters
+    uint32_t since;     // iterations launched since the last read-back
+    uint32_t its;       // iterations launched
+    bool stalled;
+};
+HD PlocLoop ploc_loop_begin(uint32_t n, uint32_t top) { return PlocLoop{n, top, 0u, 0u, false}; }
+HD bool ploc_loop_more(const PlocLoop &l) { return !l.stalled && l.m_known > l.top; }
+// an iteration has been launched: is the cluster count read back now?
+HD bool ploc_loop_launched(PlocLoop &l) {
+    l.its++; l.since++;
+    return l.since == PLOC_READ_EVERY || l.m_known <= 4u * l.top;
+}
+// the count that was read back
+HD void ploc_loop_read(PlocLoop &l, uint32_t m) {
+    const uint32_t per_iteration = l.m_known >> PLOC_STALL_SHIFT;
+    l.stalled = m > l.top && l.m_known - m < l.since * (per_iteration > 1u ? per_iteration : 1u);
+    l.m_known = m; l.since = 0u;
+}
 HD void ploc_make_node(const Work &w, uint32_t id, uint32_t l, uint32_t r) {
     w.left[id] = l; w.right[id] = r;
     w.parent[l] = id; w.parent[r] = id;

@@ -135,13 +135,17 @@ extern "C" {
 static int g_max_leaf = 4;
 static double g_split_ratio = -1.0;   // automatic, as the library
 static int g_builder = 0;   // 0 = host SAH (bvh_build.cpp), 1 = LBVH, 2 = PLOC (lbvh_core.h, the device builders' per-thread code run sequentially)
-void emu_set_build_options(int max_leaf, double split_ratio) { g_max_leaf = max_leaf; g_split_ratio = split_ratio; }
+static uint32_t g_ploc_top = hr::lbvh::PLOC_TOP_CLUSTERS;   // the library's debug option ploc_top (builder 2)
+static uint32_t g_ploc_iterations = 0, g_ploc_top_clusters = 0;   // of the last PLOC build: merge iterations, clusters handed to the top-down build
+void emu_set_build_options(int max_leaf, double split_ratio, uint32_t ploc_top) { g_max_leaf = max_leaf; g_split_ratio = split_ratio; g_ploc_top = ploc_top; }
+void emu_last_ploc_loop(uint32_t *out2) { out2[0] = g_ploc_iterations; out2[1] = g_ploc_top_clusters; }
 void emu_set_builder(int builder) { g_builder = builder; }
 
 // what build_bvh_on_device (hr_api.hip) does, with std::sort for the radix sort and loops for the kernels.
 // builder 1 = LBVH hierarchy (Karras), 2 = PLOC (the single-workgroup kernel's phases, run by one "thread")
 static void device_build_host(HostScene &hs, int max_leaf, int builder, double split_ratio) {
     using namespace lbvh;
+    g_ploc_iterations = g_ploc_top_clusters = 0;
     Prims p{};
     p.tris = hs.tris.data(); p.num_tris = (uint32_t)hs.tris.size();
     // early split clipping as build_bvh_on_device does it: count, scan, emit
@@ -186,19 +190,25 @@ static void device_build_host(HostScene &hs, int max_leaf, int builder, double s
         std::vector<uint32_t> cl(n), nxt(n), nn(n);
         for (int k = 0; k < n; k++) cl[k] = (uint32_t)(n - 1 + k);
         uint32_t m = (uint32_t)n, next_node = (uint32_t)(n - 1);   // internal ids are handed out downwards: the last merge makes node 0, the root
-        while (m > PLOC_TOP_CLUSTERS) {   // the merges stop at a few thousand clusters ...
-            for (uint32_t i = 0; i < m; i++) nn[i] = ploc_nearest(w, cl.data(), m, i);
-            uint32_t pos = 0, made = 0;
-            for (uint32_t i = 0; i < m; i++) {
-                int role = ploc_role(nn.data(), i);
-                if (role == 2) continue;
-                if (role == 1) { uint32_t id = next_node - 1u - made++; ploc_make_node(w, id, cl[i], cl[nn[i]]); nxt[pos++] = id; }
-                else nxt[pos++] = cl[i];
+        // the device's loop (build_bvh_on_device): m is the count the kernels keep, loop.m_known what the host has read back of it
+        PlocLoop loop = ploc_loop_begin((uint32_t)n, g_ploc_top);
+        while (ploc_loop_more(loop)) {   // the merges stop at a few thousand clusters, or when they stall ...
+            if (m > 1u) {   // (the kernels do nothing at one cluster)
+                for (uint32_t i = 0; i < m; i++) nn[i] = ploc_nearest(w, cl.data(), m, i);
+                uint32_t pos = 0, made = 0;
+                for (uint32_t i = 0; i < m; i++) {
+                    int role = ploc_role(nn.data(), i);
+                    if (role == 2) continue;
+                    if (role == 1) { uint32_t id = next_node - 1u - made++; ploc_make_node(w, id, cl[i], cl[nn[i]]); nxt[pos++] = id; }
+                    else nxt[pos++] = cl[i];
+                }
+                next_node -= made;
+                m = pos;
+                cl.swap(nxt);
             }
-            next_node -= made;
-            m = pos;
-            cl.swap(nxt);
+            if (ploc_loop_launched(loop)) ploc_loop_read(loop, m);
         }
+        g_ploc_iterations = loop.its; g_ploc_top_clusters = m;
         if (m > 1) {   // ... and the host builder's binned SAH joins them top-down (as build_bvh_on_device does)
             std::vector<float> boxes(6 * (size_t)m);
             std::vector<uint32_t> counts(m);

@@ -15,7 +15,8 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.emu_scene_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.emu_scene_destroy.argtypes = [C.c_void_p]
-        L.emu_set_build_options.argtypes = [C.c_int, C.c_double]
+        L.emu_set_build_options.argtypes = [C.c_int, C.c_double, C.c_uint32]
+        L.emu_last_ploc_loop.argtypes = [C.c_void_p]
         L.emu_set_builder.argtypes = [C.c_int]
         L.emu_set_walk_mode.argtypes = [C.c_int]
         L.emu_scene_stats.argtypes = [C.c_void_p, C.c_void_p]
@@ -106,10 +107,21 @@ class EmuScene:
         return out, el
 
 
-def set_build_options(max_leaf=4, split_ratio=-1.0, builder=0):
-    """builder: 0 = host SAH, 1 = LBVH, 2 = PLOC (the device builders' per-thread code, run sequentially)."""
-    lib().emu_set_build_options(max_leaf, split_ratio)
+PLOC_TOP_DEFAULT = 8192   # lbvh_core.h PLOC_TOP_CLUSTERS
+
+
+def set_build_options(max_leaf=4, split_ratio=-1.0, builder=0, ploc_top=PLOC_TOP_DEFAULT):
+    """builder: 0 = host SAH, 1 = LBVH, 2 = PLOC (the device builders' per-thread code, run sequentially); ploc_top: the library's
+    debug option of that name (builder 2: the merges stop at <= ploc_top clusters, 1 = merge to the root)."""
+    lib().emu_set_build_options(max_leaf, split_ratio, ploc_top)
     lib().emu_set_builder(builder)
+
+
+def last_ploc_loop():
+    """(merge iterations, clusters handed to the top-down build) of the last PLOC build"""
+    out = (C.c_uint32 * 2)()
+    lib().emu_last_ploc_loop(out)
+    return int(out[0]), int(out[1])
 
 
 def set_walk_mode(mode):
