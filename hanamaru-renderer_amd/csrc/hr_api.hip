@@ -9,11 +9,11 @@
 //                    and debug_render_kernel (renderer.rs:101-146)
 //   wf_kernels.h     the split pipeline (option trace_mode 1): wf_start_kernel, wf_traverse_kernel (the same traversal at <= 64 VGPRs),
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
-//   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel
+//   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
-// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts) are rows of one
+// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image) are rows of one
 // table, PLANES, with one set of routines for their bytes, life cycle, zeroing and host copies; scratch a call needs lives in a CallScratch.
 #include <hip/hip_runtime.h>
 
@@ -119,6 +119,10 @@ struct hr_ctx {
     // option "sample_counts" (DESIGN.md §4.8): the samplings every pixel of the region has received (accumulate_kernel<.., true>), region-local
     bool counts_on = false;
     uint32_t *counts = nullptr;
+    // the denoiser: the guide planes {albedo rgb, normal xyz, depth, coverage} of the region — rendered by hr_render_guides or written
+    // by the host — and the denoised radiance D of the last hr_denoise, valid until anything it was made of changes (invalidate_denoised)
+    float *guides = nullptr, *denoised = nullptr;
+    bool guides_valid = false, denoised_valid = false;
     // the tile mask (hr_set_tile_mask / hr_select_tiles): which 4x4 tiles of the region hr_render covers.  On the device the compacted list of the
     // active tiles' indices, ascending (RenderParams::tile_list), and the flags it was compacted from; on the host the same flags as bytes.
     bool mask_on = false;
@@ -338,6 +342,8 @@ static void invalidate_totals(hr_ctx *c) {
     c->total_valid = false;
     for (hr_ctx *p : c->same_device_peers) p->total_valid = false;
 }
+// the accumulator, the moments, the counts or the guides of `c` are about to change, or its target: the denoised image is no longer theirs
+static void invalidate_denoised(hr_ctx *c) { c->denoised_valid = false; }
 static int drain_events(hr_ctx *c) {
     auto sum = [](std::vector<EventPair> &ev, double &acc) -> hipError_t {
         // a pair whose query fails is dropped with the rest (left in the list it would fail every later drain, i.e. every later API call)
@@ -436,8 +442,9 @@ static int free_mask_buffers(hr_ctx *c) {
 // walk it.  Life cycles:
 //   WITH_TARGET   allocated by set_target for every target
 //   WITH_OPTION   allocated while the option `on` is on: when it is switched on, and by set_target while it is on; gone when it is switched off
-//   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate), freed by
-//                 set_target — noise_img also with the moments it is made of
+//   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate; guides: the first
+//                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise), freed by set_target — noise_img also with the moments it
+//                 is made of, guides also by hr_upload_scene (they show the scene)
 // at_alloc: zeroed when allocated.  at_clear: zeroed by hr_clear.  n: the count that belongs to the plane's contents and is zeroed with them.
 enum PlaneLife { WITH_TARGET, WITH_OPTION, ON_FIRST_USE };
 struct Plane {
@@ -458,8 +465,10 @@ static const Plane ACCUM_TOTAL{PLANE_SLOT(accum_total), sizeof(float), 3, ON_FIR
 static const Plane MOMENTS{PLANE_SLOT(moments), sizeof(double), 6, WITH_OPTION, true, true, "moments", &hr_ctx::moments_on, &hr_ctx::moments_n};
 static const Plane NOISE_IMG{PLANE_SLOT(noise_img), sizeof(double), 1, ON_FIRST_USE, false, false};
 static const Plane COUNTS{PLANE_SLOT(counts), sizeof(uint32_t), 1, WITH_OPTION, true, true, "sample_counts", &hr_ctx::counts_on};
+static const Plane GUIDES{PLANE_SLOT(guides), sizeof(float), 8, ON_FIRST_USE, false, false};
+static const Plane DENOISED{PLANE_SLOT(denoised), sizeof(float), 3, ON_FIRST_USE, false, false};
 #undef PLANE_SLOT
-static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS};
+static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED};
 
 static size_t region_pixels(const hr_ctx *c) { return (size_t)c->RW * c->RH; }
 static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps; }
@@ -497,6 +506,7 @@ static int plane_write(hr_ctx *c, const Plane &p, void *dev, const void *host) {
     int rc = sync_all(c);
     if (rc) return rc;
     if (dev == c->accum) invalidate_totals(c);
+    invalidate_denoised(c);   // every plane a host can write is one the denoised image is made of
     HIP_TRY(hipMemcpy(dev, host, plane_bytes(c, p), hipMemcpyHostToDevice));
     return HR_OK;
 }
@@ -805,6 +815,9 @@ int hr_upload_scene(hr_ctx *c, const hr_scene_desc *sd) {
     rc = flatten_scene(sd, hs, ferr, c->max_leaf, gpu_build ? 0.0 : c->split_ratio, !gpu_build);
     if (rc) return fail(rc, "hr_upload_scene: %s", ferr.c_str());   // a description that is refused leaves the scene in place
     free_scene(c);
+    c->guides_valid = false;   // the guide planes show the scene that goes
+    invalidate_denoised(c);
+    if ((rc = plane_free(c, GUIDES))) return rc;
     Scene &d = c->dsc;
     d = hs.view();
     int r;
@@ -871,6 +884,8 @@ static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y
     // no target while the buffers are being replaced (a failed allocation leaves the context without one, not with dangling
     // pointers); a caller-bound accumulator was sized for the old target: it is unbound, the caller rebinds
     c->accum = nullptr; c->W = c->H = 0; c->RX = c->RY = c->RW = c->RH = 0; c->total_valid = false;
+    c->guides_valid = false;
+    invalidate_denoised(c);
     unbind_accumulator(c);
     for (const Plane *p : PLANES) if ((rc = plane_free(c, *p))) return rc;
     if ((rc = remove_mask(c))) return rc;   // the mask is over the old region's tiles
@@ -956,6 +971,7 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
     }
     c->accum = device_rgb ? device_rgb : c->accum_own;
     invalidate_totals(c);
+    invalidate_denoised(c);
     return HR_OK;
 }
 void *hr_accumulator_device_ptr(hr_ctx *c) { return c ? c->accum : nullptr; }
@@ -976,6 +992,7 @@ int hr_clear(hr_ctx *c) {
     int rc = sync_all(c);
     if (rc) return rc;
     invalidate_totals(c);
+    invalidate_denoised(c);
     // the planes the table marks, the accumulator through c->accum (it may be the caller's bound buffer); the tile mask stays: a setting, like the region
     for (const Plane *p : PLANES)
         if (p->at_clear && (rc = plane_zero(c, *p, c->stream, p == &ACCUM_OWN ? c->accum : nullptr))) return rc;
@@ -1185,6 +1202,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     if (s_end <= s_begin) return HR_OK;
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
+    invalidate_denoised(c);
     if (c->precise_opt == 1 && c->rr_start) return fail(HR_ERR_UNSUPPORTED, "hr_render: russian_roulette and precise_shading exclude each other (the roulette estimator has no f64 instantiation)");
     const uint32_t total_k = (s_end - s_begin + stride - 1) / stride;
     const bool list = c->mask_on;
@@ -1271,6 +1289,7 @@ int hr_render_debug(hr_ctx *c, int mode) {
     if (c->counts_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option sample_counts on (a debug sampling goes into the accumulator without being counted)");
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
+    invalidate_denoised(c);
     RenderParams rp{};
     target_params(c, rp);
     knob_params(c, rp);   // (the debug kernels read leaf_den and node_unroll of them)
@@ -1669,14 +1688,16 @@ __global__ void tonemap_gamma_counted_kernel(const float *__restrict__ acc, cons
 // The resolve behind hr_resolve (every pixel scaled by 1 / (4 samplings)) and hr_resolve_counted (samplings == 0: by its own count): the first
 // kernel differs, the rest is one.  The region's accumulator is resolved as an image of its own: the bilateral filter's clamp and wrap act at
 // the region's edges.
-static int resolve_region(hr_ctx *c, uint32_t samplings, uint8_t *host_rgb8) {
+// `radiance` (hr_resolve_denoised): that image instead of an accumulator, with the scale 1.0f.
+static int resolve_region(hr_ctx *c, uint32_t samplings, uint8_t *host_rgb8, const float *radiance = nullptr) {
     int rc = hr_synchronize(c);
     if (rc) return rc;
     const uint32_t n = (uint32_t)region_pixels(c);
     const float *acc = c->total_valid ? c->accum_total : c->accum;
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
-    if (samplings) hipLaunchKernelGGL(tonemap_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, acc, c->post_tmp, n, 1.0f / (float)(samplings * 4u));
+    if (radiance) hipLaunchKernelGGL(tonemap_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, radiance, c->post_tmp, n, 1.0f);
+    else if (samplings) hipLaunchKernelGGL(tonemap_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, acc, c->post_tmp, n, 1.0f / (float)(samplings * 4u));
     else hipLaunchKernelGGL(tonemap_gamma_counted_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, acc, c->counts, c->post_tmp, n);
     hipLaunchKernelGGL(bilateral_quantise_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->post_tmp, c->d_rgb8, c->RW, c->RH);
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
@@ -1695,6 +1716,102 @@ int hr_resolve_counted(hr_ctx *c, uint8_t *host_rgb8) {
     if (!host_rgb8) return fail(HR_ERR_INVALID, "hr_resolve_counted: null argument");
     if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_resolve_counted: no accumulator");
     return resolve_region(c, 0, host_rgb8);
+}
+
+// ---- the denoiser: guide planes, the à-trous filter and its resolve (denoise_core.h) ----
+int hr_denoise_default_params(hr_denoise_params *out) {
+    if (!out) return fail(HR_ERR_INVALID, "hr_denoise_default_params: null argument");
+    memset(out, 0, sizeof *out);
+    out->levels = 4; out->demodulate = 1;
+    out->sigma_color = 3.0; out->sigma_normal = 0.5; out->sigma_albedo = 0.25; out->sigma_depth = 0.1;
+    return HR_OK;
+}
+// One pinhole pass over the whole region, whatever tile mask is set, into the guide planes (stored, not added).  Nothing else is touched: not the
+// accumulator, the moments, the counts or hr_stats.paths; its time goes to debug_kernel_ms / debug_launches.
+int hr_render_guides(hr_ctx *c) {
+    if (!c) return fail(HR_ERR_INVALID, "hr_render_guides: null ctx");
+    int rc;
+    if ((rc = debug_refusal(c, "hr_render_guides", A_SCENE)) || (rc = debug_refusal(c, "hr_render_guides", A_TARGET))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    invalidate_denoised(c);
+    c->guides_valid = false;
+    if (!c->guides && (rc = plane_alloc(c, GUIDES))) return rc;
+    RenderParams rp{};
+    target_params(c, rp);
+    knob_params(c, rp);   // (leaf_den and node_unroll, as hr_render_debug)
+    const GuideRenderFn fn = select_guide_render_kernel(c->dsc.qnodes != nullptr);
+    if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_guides: no kernel instantiation for this node format (kernel_variants.h)");
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
+    hipLaunchKernelGGL(fn, dim3((tiles + TRACE_WAVES - 1) / TRACE_WAVES), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, c->guides);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->debug_events, &c->debug_launches));
+    c->guides_valid = true;
+    return HR_OK;
+}
+int hr_read_guides(hr_ctx *c, float *host) {
+    if (!c || !host) return fail(HR_ERR_INVALID, "hr_read_guides: null argument");
+    if (!c->guides || !c->guides_valid) return fail(HR_ERR_INVALID, "hr_read_guides: no guide planes (hr_render_guides or hr_write_guides first)");
+    return plane_read(c, GUIDES, c->guides, host);
+}
+int hr_write_guides(hr_ctx *c, const float *host) {
+    if (!c || !host) return fail(HR_ERR_INVALID, "hr_write_guides: null argument");
+    if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_write_guides: hr_set_resolution not called");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if (!c->guides && (rc = plane_alloc(c, GUIDES))) return rc;
+    c->guides_valid = false;
+    if ((rc = plane_write(c, GUIDES, c->guides, host))) return rc;
+    c->guides_valid = true;
+    return HR_OK;
+}
+int hr_denoise(hr_ctx *c, const hr_denoise_params *params) {
+    static const char *const who = "hr_denoise";
+    int rc = plane_ready(c, MOMENTS, who);
+    if (rc) return rc;
+    hr_denoise_params p;
+    if (params) p = *params;
+    else (void)hr_denoise_default_params(&p);
+    // what is refused is refused before anything is touched: the denoised image of an earlier call stays
+    if (p.levels > DENOISE_MAX_LEVELS) return fail(HR_ERR_INVALID, "%s: levels must be in [0,%u]", who, DENOISE_MAX_LEVELS);
+    if (p.demodulate > 1u) return fail(HR_ERR_INVALID, "%s: demodulate must be 0 or 1", who);
+    for (double s : {p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth})
+        if (!(s > 0.0) || !(s < INFINITY)) return fail(HR_ERR_INVALID, "%s: every sigma must be positive and finite", who);
+    if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
+    if (c->moments_n >= (1ull << 30)) return fail(HR_ERR_INVALID, "%s: %llu samplings do not fit the resolve's 32-bit scale", who, (unsigned long long)c->moments_n);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = hr_synchronize(c))) return rc;
+    if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;
+    if (!c->guides_valid && (rc = hr_render_guides(c))) return rc;
+    const uint32_t pixels = (uint32_t)region_pixels(c);
+    if (!c->denoised && (rc = plane_alloc(c, DENOISED))) return rc;
+    CallScratch scratch;
+    double *cv[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++) HIP_TRY_AS(who, scratch.alloc((void **)&cv[k], (size_t)pixels * 6 * sizeof(double)));
+    invalidate_denoised(c);
+    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
+    const int demodulate = p.demodulate && p.levels ? 1 : 0;   // without a level there is nothing to filter: D = (float)C0, as the header says
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const dim3 flat((pixels + 255) / 256), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
+    hipLaunchKernelGGL(denoise_init_kernel, flat, dim3(256), 0, c->stream, c->accum, c->moments, c->counts, (uint32_t)c->moments_n, c->guides, cv[0], pixels, demodulate);
+    for (uint32_t l = 0; l < p.levels; l++)
+        hipLaunchKernelGGL(atrous_kernel, tiles2d, dim3(32, 8), 0, c->stream, cv[l & 1u], c->guides, cv[(l + 1u) & 1u], c->RW, c->RH, 1u << l, sg);
+    hipLaunchKernelGGL(denoise_final_kernel, flat, dim3(256), 0, c->stream, cv[p.levels & 1u], c->guides, c->denoised, pixels, demodulate);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
+    c->denoised_valid = true;
+    return drain_events(c);
+}
+int hr_read_denoised(hr_ctx *c, float *host) {
+    if (!c || !host) return fail(HR_ERR_INVALID, "hr_read_denoised: null argument");
+    if (!c->denoised || !c->denoised_valid) return fail(HR_ERR_INVALID, "hr_read_denoised: no denoised image (hr_denoise first; anything that changes its inputs invalidates it)");
+    return plane_read(c, DENOISED, c->denoised, host);
+}
+int hr_resolve_denoised(hr_ctx *c, uint8_t *host_rgb8) {
+    if (!c || !host_rgb8) return fail(HR_ERR_INVALID, "hr_resolve_denoised: null argument");
+    if (!c->denoised || !c->denoised_valid) return fail(HR_ERR_INVALID, "hr_resolve_denoised: no denoised image (hr_denoise first; anything that changes its inputs invalidates it)");
+    return resolve_region(c, 0, host_rgb8, c->denoised);
 }
 
 // the mask's host side from its flags: the count of active tiles and of their in-region pixels
@@ -1898,6 +2015,7 @@ static int set_plane_option(hr_ctx *c, double value, const Plane &p, const Plane
     if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", p.option);
     int rc = sync_all(c);
     if (rc) return rc;
+    if (value == 0 || !(c->*p.on)) invalidate_denoised(c);   // the moments or the counts go, or start over
     if (value == 0) {
         c->*p.on = false;
         if ((rc = off_first(c))) return rc;

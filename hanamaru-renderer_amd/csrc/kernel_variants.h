@@ -96,6 +96,13 @@ static const DebugRenderVariant DEBUG_RENDER_VARIANTS[] = {HR_VARIANT(debug_rend
 static DebugRenderFn select_debug_render_kernel(bool counters, bool qn) {
     return fn_of(find_row(DEBUG_RENDER_VARIANTS, [&](const DebugRenderVariant &r) { return r.cnt == counters && r.qn == qn; }));
 }
+// ---- guide_render_kernel<QN> (trace_kernel.h): the denoiser's guide planes, one row per node format; runs beside nothing ----
+typedef void (*GuideRenderFn)(Scene, RenderParams, float *);
+struct GuideRenderVariant { bool qn; GuideRenderFn fn; };
+static const GuideRenderVariant GUIDE_RENDER_VARIANTS[] = {HR_VARIANT(guide_render_kernel, true), HR_VARIANT(guide_render_kernel, false)};
+static GuideRenderFn select_guide_render_kernel(bool qn) {
+    return fn_of(find_row(GUIDE_RENDER_VARIANTS, [&](const GuideRenderVariant &r) { return r.qn == qn; }));
+}
 typedef void (*TraceDebugFn)(Scene, RenderParams, uint32_t, const float *, const float *, float *, int32_t *, Counters *);
 struct TraceDebugVariant { bool qn, cnt; TraceDebugFn fn; };
 static const TraceDebugVariant TRACE_DEBUG_VARIANTS[] = {HR_VARIANT(trace_debug_kernel, true, false), HR_VARIANT(trace_debug_kernel, false, false),

@@ -934,6 +934,20 @@ HD bool debug_primary(const Scene &sc, const Ray &ray, const TraceState &ts, int
     lit = pm.albedo * fmaxf(dot(s.n, light), 0.0f);
     return true;
 }
+// The guide values of the primary ray's hit, for the denoiser (denoise_core.h; guide_render_kernel in trace_kernel.h walks the production
+// traversal as the debug renderer does): g[8] = {albedo rgb (texture x tint, PointMat::albedo), normal xyz (what mode 1 shows), the hit distance
+// along the pinhole ray, coverage 1}.  A miss is eight zeros.
+HD void guide_primary(const Scene &sc, const Ray &ray, const TraceState &ts, float *g) {
+    if (ts.prim < 0) { for (int k = 0; k < 8; k++) g[k] = 0.0f; return; }
+    Surf s;
+    hit_surface(sc, ray, ts, material_needs_uv(sc, hit_element(sc, ts)), s);
+    PointMat pm;
+    material_at(sc, s.elem, s.u, s.v, pm);
+    g[0] = pm.albedo.x; g[1] = pm.albedo.y; g[2] = pm.albedo.z;
+    g[3] = s.n.x; g[4] = s.n.y; g[5] = s.n.z;
+    g[6] = ts.t;
+    g[7] = 1.0f;
+}
 // scalar form (host emulation): one node + its leaf per step
 template <bool CNT>
 HD V3f debug_pixel(const Scene &sc, const RenderParams &rp, uint32_t px, uint32_t py, uint32_t sub, int mode, LaneCounters *cn) {

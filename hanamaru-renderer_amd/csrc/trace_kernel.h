@@ -423,3 +423,36 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void debug_render_kernel(Scene sc
     }
     flush_counters<CNT>(cnt, lane, (uint32_t)active, lc, ws);
 }
+
+// The denoiser's guide planes: debug_render_kernel's tile / lane mapping, pinhole ray and walk, with guide_primary in place of
+// the visualisers — no shadow ray, no counters build.  The four sub-samples of a pixel are summed with the same two lane exchanges, and the
+// sub-sample 0 lane STORES the mean (sum x 0.25f, exact) into guides[reg_h][reg_w][8]: a pass replaces the planes, it does not add to them.
+template <bool QN>
+__global__ __launch_bounds__(64 * TRACE_WAVES) void guide_render_kernel(Scene sc, RenderParams rp, float *__restrict__ guides) {
+    const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * TRACE_WAVES + (threadIdx.x >> 6);
+    if (tile >= rp.tiles_x * rp.tiles_y) return;
+    uint32_t px, py, sub;
+    tile_lane_pixel(rp, tile, lane, px, py, sub);
+    const bool active = rp_in_region(rp, px, py);
+    LaneCounters lc = {0, 0, 0, 0, 0, 0};
+    WaveStats ws = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}, 0};
+    Path p;
+    p.q = active ? lane : PATH_IDLE;
+    p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
+    debug_camera_ray(sc, rp, rp.org_x + (active ? px : 0u), rp.org_y + (active ? py : 0u), sub, p.ray);
+    ray_quantise(sc, p.ray);
+    trace_begin(p.ts, T_INF, p.ray.start);
+    if (!active) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
+    const uint32_t n_active = (uint32_t)__popcll(wave_ballot(active));
+    const uint32_t leaf_den = rp.leaf_den ? rp.leaf_den : 2u;
+    uint32_t tick = 0;
+    traverse_wave<false, QN>(sc, rp, p, active, n_active, 0u, leaf_den, lc, ws, tick, rp.trace_boost);
+    float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (active) guide_primary(sc, p.ray, p.ts, g);
+    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 1);
+    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 2);
+    if (active && sub == 0u) {
+        float *o = guides + ((size_t)py * rp_reg_w(rp) + px) * 8;
+        for (int k = 0; k < 8; k++) o[k] = g[k] * 0.25f;
+    }
+}

@@ -9,7 +9,9 @@
 // --noise-target E / --noise-floor F / --noise-check N / --noise-image FILE (option "moments": stop when the mean relative standard error of
 // the pixels is <= E; hr_noise_estimate — the reference stops on a sampling count or the clock only),
 // --adaptive E / --sample-image FILE (options "moments" + "sample_counts": after a uniform first phase only the 4x4 tiles that still hold a pixel
-// with a relative standard error above E are rendered on; hr_select_tiles, hr_resolve_counted).
+// with a relative standard error above E are rendered on; hr_select_tiles, hr_resolve_counted),
+// --denoise / --denoise-levels N / --guide-image PREFIX (option "moments": the final image is the variance-guided a-trous filter's, hr_denoise +
+// hr_resolve_denoised; the first-hit guide planes as images of their own, hr_render_guides + hr_read_guides).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -88,7 +90,15 @@ static void usage(const char *prog) {
            "        --sample-image FILE.png\n"
            "                        write the per-pixel sampling counts as 8-bit grey, count / largest count (one device only)\n"
            "        --noise-image FILE.png\n"
-           "                        write an 8-bit grey map of min(1, e / E) at the end of the render (E = the target, or 0.05 without one)\n",
+           "                        write an 8-bit grey map of min(1, e / E) at the end of the render (E = the target, or 0.05 without one)\n"
+           "        --denoise       keep per-pixel sample moments and write the FINAL image through the variance-guided edge-avoiding a-trous filter\n"
+           "                        (hr_denoise: guided by first-hit albedo, normal and depth; progress images stay as they are).  With --adaptive\n"
+           "                        every pixel's own sampling count is its n.  One device only; not with --debug.\n"
+           "        --denoise-levels N\n"
+           "                        filter levels, 0 .. 5 (default 4; the taps of level l are 2^l pixels apart)\n"
+           "        --guide-image PREFIX\n"
+           "                        write the guide planes as PREFIX_albedo.png, PREFIX_normal.png ((n + 1) / 2) and PREFIX_depth.png (depth / largest\n"
+           "                        depth, grey).  One device only; not with --debug.\n",
            prog);
 }
 
@@ -108,6 +118,9 @@ int main(int argc, char **argv) {
     bool have_target = false;
     double noise_target = 0.0, noise_floor = 0.01;
     long long noise_check = 64;
+    bool denoise = false;
+    long long denoise_levels = -1;   // -1: the library's default
+    std::string guide_prefix;
     // a number, the whole argument, not NaN; what is wrong with it is said with the flag's name, before any device is opened
     auto number = [](const char *flag, const char *text, double *out) -> bool {
         char *e = nullptr;
@@ -158,6 +171,13 @@ int main(int argc, char **argv) {
             if (!(adaptive_e > 0.0)) { fprintf(stderr, "--adaptive must be positive.\n"); return 1; }
             have_adaptive = true;
         } else if (a == "--sample-image") sample_png = val("sample-image");
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-levels") {
+            const char *t = val("denoise-levels");
+            char *e = nullptr;
+            denoise_levels = strtoll(t, &e, 10);
+            if (e == t || *e || denoise_levels < 0 || denoise_levels > 5) { fprintf(stderr, "--denoise-levels must be a whole number in 0 .. 5, not '%s'.\n", t); return 1; }
+        } else if (a == "--guide-image") guide_prefix = val("guide-image");
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -176,7 +196,17 @@ int main(int argc, char **argv) {
         if (have_adaptive && have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
         if (debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
     }
-    const bool moments = have_target || !noise_png.empty() || have_adaptive;   // hr_set_option "moments"
+    if (denoise_levels >= 0 && !denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
+    if (denoise || !guide_prefix.empty()) {
+        size_t ids = gpu_ids.empty() ? 0 : 1;
+        for (char ch : gpu_ids) ids += ch == ',';
+        if (gpus > 1 || ids > 1) {
+            fprintf(stderr, "--denoise / --guide-image render on one device: the library denoises one context's accumulator, moments and counts (a sharded host sums them into one), this program's device loop does not.\n");
+            return 1;
+        }
+        if (debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
+    }
+    const bool moments = have_target || !noise_png.empty() || have_adaptive || denoise;   // hr_set_option "moments"
     if (moments && debug) { fprintf(stderr, "--noise-target / --noise-image cannot be combined with --debug (the debug renderer has no samplings to measure).\n"); return 1; }
     const double noise_e = have_adaptive ? adaptive_e : have_target && noise_target > 0.0 ? noise_target : (have_target ? 0.0 : 0.05);   // the threshold of "above" and of the grey map
     // --region X,Y,W,H: four unsigned integers, a non-empty window inside the frame (hr_set_region's rule, checked before any device is opened)
@@ -272,7 +302,18 @@ int main(int argc, char **argv) {
         return 0;
     };
     // host-side sum: device 0 resolves the total from its accumulator, then gets its own partial sums back
+    bool have_guides = false;   // the context holds guide planes (for --guide-image)
+    bool final_image = false;   // set by whoever writes the render's last image: --denoise filters that one only
     auto resolve = [&](uint32_t s, uint8_t *out) -> int {
+        if (denoise && final_image) {
+            hr_denoise_params dp;
+            if (hr_denoise_default_params(&dp) != 0) return 1;
+            if (denoise_levels >= 0) dp.levels = (uint32_t)denoise_levels;
+            const int rc = hr_denoise(ctx, &dp);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings — the flags' values were checked when they were read)
+            if (rc == 0) { have_guides = true; return hr_resolve_denoised(ctx, out); }   // (hr_denoise rendered the guide planes, nothing has dropped them since)
+            if (rc != HR_ERR_INVALID) return rc;
+            tee("denoise: fewer than 2 samplings behind a pixel, the image is not denoised.");
+        }
         if (have_adaptive) return hr_resolve_counted(ctx, out);   // every pixel with its own count (one device: checked with the flags)
         if (!host_sum) return hr_resolve(ctx, s, out);
         if (hr_read_accumulator(ctx, part.data()) != 0 || hr_write_accumulator(ctx, sum_acc.data()) != 0) return 1;
@@ -398,6 +439,14 @@ int main(int argc, char **argv) {
                             "so the noise of its pixels cannot be known; resume without --adaptive, or render again with it.\n", ckpt_in.c_str(), (unsigned long long)mom_n, hdr[3]);
             return 1;
         }
+        if (denoise && !(have_mom && (resumed_counts || mom_n == hdr[3]))) {
+            // the filter's mean is accumulator / (4 n) with n the samplings behind the moments (or the pixel's count): moments that do not cover
+            // every sampling of the accumulator would give an image of the wrong brightness
+            fprintf(stderr, "--resume %s with --denoise: the checkpoint's sample moments %s, so the variance of its %u samplings cannot be known; "
+                            "resume without --denoise, or render again with it.\n", ckpt_in.c_str(),
+                    have_mom ? "do not cover all of its samplings" : "are missing (it was written without --denoise / --adaptive / --noise-target / --noise-image)", hdr[3]);
+            return 1;
+        }
         if (have_target && !have_mom) {
             fprintf(stderr, "--resume %s with --noise-target: the checkpoint holds no sample moments (it was written without --noise-target / --noise-image), "
                             "so the noise of its %u samplings cannot be known; resume without --noise-target, or render again with it.\n", ckpt_in.c_str(), hdr[3]);
@@ -499,6 +548,7 @@ int main(int argc, char **argv) {
         printf("%s\n", why);
         printf("output final image: %03u.png\n", counter);
         printf("remain: %.3f sec.\n", time_limit - used);
+        final_image = true;
         return save(sampled);
     };
     // how many reports may be enqueued now?  (samplings left, room in the pipeline, and the time-limit rule asked for the moment they would finish)
@@ -524,6 +574,7 @@ int main(int argc, char **argv) {
     };
     if (first > sampling && !debug && sampled > 0) {   // resumed from a checkpoint that already holds every requested sampling: just resolve it
         printf("reached max sampling\n");
+        final_image = true;
         if (save(sampled)) return 1;
     }
     bool running = first <= sampling;
@@ -622,6 +673,22 @@ int main(int argc, char **argv) {
             }
             if (hh_write_png_rgb8(noise_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
         }
+    }
+    if (!guide_prefix.empty()) {   // the guide planes as images of their own (the planes of --denoise's filter, or a pass of their own)
+        std::vector<float> g((size_t)out_w * out_h * 8);
+        if (!have_guides) CHECK_HR(hr_render_guides(ctx));
+        CHECK_HR(hr_read_guides(ctx, g.data()));
+        const size_t pixels = (size_t)out_w * out_h;
+        float zmax = 0.0f;
+        for (size_t i = 0; i < pixels; i++) zmax = std::max(zmax, g[i * 8 + 6]);
+        auto byte = [](float v) { return (uint8_t)(std::min(1.0f, std::max(0.0f, v)) * 255.0f + 0.5f); };
+        std::vector<uint8_t> img(pixels * 3);
+        for (size_t i = 0; i < pixels; i++) for (int k = 0; k < 3; k++) img[i * 3 + k] = byte(powf(std::max(0.0f, g[i * 8 + k]), 1.0f / 2.2f));
+        if (hh_write_png_rgb8((guide_prefix + "_albedo.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        for (size_t i = 0; i < pixels; i++) for (int k = 0; k < 3; k++) img[i * 3 + k] = byte(0.5f * g[i * 8 + 3 + k] + 0.5f * g[i * 8 + 7]);
+        if (hh_write_png_rgb8((guide_prefix + "_normal.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        for (size_t i = 0; i < pixels; i++) img[i * 3] = img[i * 3 + 1] = img[i * 3 + 2] = byte(zmax > 0.0f ? g[i * 8 + 6] / zmax : 0.0f);
+        if (hh_write_png_rgb8((guide_prefix + "_depth.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
     }
     if (counts) {   // how the samplings were spent
         std::vector<uint32_t> cnt((size_t)out_w * out_h);

@@ -80,6 +80,11 @@ class Noise(C.Structure):
                 ("mean_error", C.c_double), ("max_error", C.c_double)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("demodulate", C.c_uint32),
+                ("sigma_color", C.c_double), ("sigma_normal", C.c_double), ("sigma_albedo", C.c_double), ("sigma_depth", C.c_double)]
+
+
 COMM_PATHS = {0: "none", 1: "rccl-rank", 2: "rccl-group", 3: "same-device-fallback"}
 
 
@@ -193,8 +198,25 @@ def hip_lib():
         L.hr_set_tile_mask.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_get_tile_mask.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.hr_select_tiles.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint32)]
+        L.hr_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+        L.hr_render_guides.argtypes = [C.c_void_p]
+        L.hr_read_guides.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_write_guides.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)]
+        L.hr_read_denoised.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_resolve_denoised.argtypes = [C.c_void_p, C.c_void_p]
         _hip = L
     return _hip
+
+
+def denoise_default_params():
+    """hr_denoise_default_params: the documented defaults as a DenoiseParams (needs no device)."""
+    L = hip_lib()
+    p = DenoiseParams()
+    rc = L.hr_denoise_default_params(C.byref(p))
+    if rc != 0:
+        raise HipError(rc, L.hr_last_error().decode())
+    return p
 
 
 COMM_ID_BYTES = 128
@@ -511,6 +533,43 @@ class Renderer:
         n = C.c_uint32()
         self._check(self.L.hr_select_tiles(self._h, float(floor), float(threshold), C.byref(n)))
         return int(n.value)
+
+    # ---- guide planes and the denoiser (include/hanamaru_hip.h)
+    def render_guides(self):
+        """hr_render_guides: one pinhole pass into the guide planes."""
+        self._check(self.L.hr_render_guides(self._h))
+
+    def read_guides(self):
+        """hr_read_guides: (h, w, 8) float32 {albedo rgb, normal xyz, depth, coverage}."""
+        out = np.empty(self._acc_hw() + (8,), dtype=np.float32)
+        self._check(self.L.hr_read_guides(self._h, out.ctypes.data))
+        return out
+
+    def write_guides(self, guides):
+        a = np.ascontiguousarray(guides, dtype=np.float32)
+        assert a.shape == self._acc_hw() + (8,)
+        self._check(self.L.hr_write_guides(self._h, a.ctypes.data))
+
+    def denoise(self, **params):
+        """hr_denoise: the defaults, with any of levels, demodulate, sigma_color, sigma_normal, sigma_albedo, sigma_depth replaced."""
+        p = denoise_default_params()
+        for k, v in params.items():
+            if k not in dict(DenoiseParams._fields_):
+                raise TypeError("denoise() has no parameter %r" % k)
+            setattr(p, k, v)
+        self._check(self.L.hr_denoise(self._h, C.byref(p)))
+
+    def read_denoised(self):
+        """hr_read_denoised: (h, w, 3) float32 radiance."""
+        out = np.empty(self._acc_hw() + (3,), dtype=np.float32)
+        self._check(self.L.hr_read_denoised(self._h, out.ctypes.data))
+        return out
+
+    def resolve_denoised(self):
+        """hr_resolve_denoised: resolve() of the denoised radiance."""
+        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
+        self._check(self.L.hr_resolve_denoised(self._h, out.ctypes.data))
+        return out
 
     def debug_draws(self, sampling, first_path, num_paths, window):
         out = np.empty((num_paths, window), dtype=np.uint64)

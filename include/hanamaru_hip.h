@@ -342,6 +342,62 @@ int hr_set_tile_mask(hr_ctx *ctx, const uint8_t *mask /* tiles_y*tiles_x, NULL =
 int hr_get_tile_mask(hr_ctx *ctx, uint8_t *mask /* may be NULL */, uint32_t *active /* may be NULL */);
 int hr_select_tiles(hr_ctx *ctx, double floor, double threshold, uint32_t *active /* may be NULL */);
 
+/* ---- guide planes and the variance-guided denoiser ---------------------------------------------------------------------------
+ * "Do something about the noise that is left."  An edge-avoiding a-trous filter over the mean radiance, steered by the per-pixel variance the
+ * moments give and by first-hit guide planes.  hr_resolve's 3x3 bilateral filter is part of the reference's look and stays what it is.
+ *   - The guide planes: h x w x 8 floats per pixel {albedo r, g, b (texture x tint), normal x, y, z, depth (hit distance along the pinhole ray),
+ *     coverage}, row-major, top row first: the mean over the pixel's 2x2 sub-samples of the primary PINHOLE ray's hit (no lens, no RNG: the
+ *     rays of hr_render_debug); a sub-sample that misses contributes eight zeros, so coverage is the fraction that hit.  hr_render_guides is one
+ *     pass of the production traversal over the whole region — whatever tile mask is set — that STORES the planes.  A guide pixel depends on its
+ *     frame pixel only: a region's guides are bit-identical to that window of a full-frame pass.  The pass touches neither the accumulator nor the
+ *     moments, the counts or hr_stats.paths; its time goes to hr_stats.debug_kernel_ms / debug_launches.  hr_read_guides returns the planes as
+ *     outputs in their own right (AOVs; HR_ERR_INVALID while there are none); hr_write_guides replaces them (resume, stitching, synthetic inputs).
+ *     The buffer is allocated on first use, dropped by hr_set_resolution, hr_set_region and hr_upload_scene, and kept by hr_clear.
+ *   - hr_denoise computes D, w x h x 3 floats of radiance (what accumulator x 1 / (4 n) is), from this context's OWN accumulator — never the
+ *     all-reduced total: a sharded host writes the summed accumulator, moments and counts into one context, as it does for the estimate —,
+ *     the moments and the guides.  The definition is csrc/denoise_core.h, to the bit (f64, + - x / max only, one IEEE operation per step, no FMA):
+ *         C0_c = accumulator_c x fp32(1 / (4 n))      V0_c = var_c / n / 16   (var_c as in the noise estimate: the variance of the mean)
+ *         demodulate = 1 and levels > 0: C / (A + eps) and V / (A + eps)^2 are filtered and the result is multiplied by (A + eps), eps = 1e-3
+ *         level l = 0 .. levels - 1, step s = 2^l, taps q = p + s (i, j), i, j in -2 .. 2 (a tap outside the region is skipped, not clamped),
+ *         h = k[|i|] k[|j|], k = {3/8, 1/4, 1/16},  K(x) = max(0, 1 - x)^2,  tiny = 1e-30
+ *             x_n = |N_p - N_q|^2 / sigma_normal^2        x_a = |A_p - A_q|^2 / sigma_albedo^2        x_h = (H_p - H_q)^2
+ *             x_z = (Z_p - Z_q)^2 / (sigma_depth^2 (Z_p^2 + Z_q^2) + tiny)
+ *             x_c = |C_p - C_q|^2 / (sigma_color^2 (sumV_p + sumV_q) + tiny)          (C, V of the level's input)
+ *             w = h K(x_n) K(x_a) K(x_z) K(x_h) K(x_c)      C'(p) = sum w C(q) / sum w      V'_c(p) = sum w^2 V_c(q) / (sum w)^2
+ *         D = (float)C of the last level; levels = 0: D = (float)C0, the radiance the resolve tone-maps.
+ *     n is the samplings behind the moments, or with option "sample_counts" on the pixel's own count.
+ *   - hr_denoise returns HR_ERR_INVALID with option "moments" off; when a pixel has n < 2 (like the noise estimate); with "sample_counts" on when
+ *     a count exceeds the samplings behind the moments (like hr_select_tiles); for levels > 5, demodulate > 1 or a sigma that is not finite and
+ *     > 0.  In all of these D stays as it was.  params = NULL: hr_denoise_default_params' (levels 4, demodulate 1, sigma_color 3, sigma_normal 0.5,
+ *     sigma_albedo 0.25, sigma_depth 0.1; it needs no device).  Without guide planes (none rendered or written since they were last dropped)
+ *     hr_denoise runs hr_render_guides itself.
+ *   - D is valid until anything it was made of changes: hr_render, hr_render_debug, hr_clear, hr_write_accumulator / _moments / _sample_counts /
+ *     _guides, hr_render_guides, hr_upload_scene, hr_bind_accumulator, switching "moments" or "sample_counts", hr_set_resolution, hr_set_region.
+ *     hr_read_denoised and hr_resolve_denoised return HR_ERR_INVALID without a valid D.  hr_resolve_denoised is renderer.rs:64-90 on D with
+ *     the scale 1.0f: with levels = 0 the bytes of hr_resolve(ctx, n, ..) — of hr_resolve_counted with "sample_counts" on.
+ *   - Nothing changes for a caller that never calls these functions (same kernels), and none of them writes the accumulator, moments or counts.
+ *   - With a region the taps stop at the region's edge: the last level reaches 2 x 2^(levels - 1) pixels, and through the levels before it a
+ *     pixel depends on inputs up to 2 x (2^levels - 1) pixels away, so pixels within that distance of the edge differ from the full-frame
+ *     result and those further inside equal it.  As with the bilateral filter, exact tiles of a frame come from stitching the tiles'
+ *     accumulators, moments, counts and guides into one full-frame context.
+ *   - What it is not: there is no temporal part, and the guides are the FIRST hit's — what is seen through or in glass and mirrors is guided
+ *     by the glass surface.  The sigmas are design parameters: the defaults are the best row of a small host-side sweep
+ *     (DESIGN.md 4.9 has the table), which also shows the filter RAISING the error of a 64-sampling rtcamp6_v3_1 render: it is for short renders.
+ *   - Cost at 1920x1080: not yet measured on the device (hr_stats.post_kernel_ms of one hr_denoise, debug_kernel_ms of one hr_render_guides);
+ *     hr_denoise holds 2 x w x h x 6 doubles of scratch for the call (199 MB).  All of these synchronise except hr_render_guides. */
+typedef struct hr_denoise_params {
+    uint32_t levels;       /* 0..5 */
+    uint32_t demodulate;   /* 0 | 1 */
+    double sigma_color, sigma_normal, sigma_albedo, sigma_depth;
+} hr_denoise_params;
+int hr_denoise_default_params(hr_denoise_params *out);
+int hr_render_guides(hr_ctx *ctx);                         /* one pinhole pass into the guide buffer */
+int hr_read_guides(hr_ctx *ctx, float *host /* w*h*8 */);  /* the planes as outputs in their own right (AOVs) */
+int hr_write_guides(hr_ctx *ctx, const float *host);       /* resume, stitching, synthetic inputs */
+int hr_denoise(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */);
+int hr_read_denoised(hr_ctx *ctx, float *host /* w*h*3 radiance */);
+int hr_resolve_denoised(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on D with scale 1.0f */
+
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):
  *   "counters"      0 / 1: instrumented build of the trace kernel (fills the counter fields of hr_stats)

@@ -30,6 +30,9 @@ pub const HR_MESH: i32 = 2;
 /// hr_noise: summary of the per-pixel relative standard error e (option "moments")
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrNoise { pub samplings: u64, pub pixels: u64, pub pixels_above: u64,
                                                                  pub mean_error: f64, pub max_error: f64 }
+/// hr_denoise_params: the a-trous denoiser's parameters (hr_denoise_default_params fills in the defaults)
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrDenoiseParams { pub levels: u32, pub demodulate: u32, pub sigma_color: f64, pub sigma_normal: f64,
+                                                                         pub sigma_albedo: f64, pub sigma_depth: f64 }
 pub enum HrCtx {}
 
 extern "C" {
@@ -84,6 +87,14 @@ extern "C" {
     pub fn hr_set_tile_mask(ctx: *mut HrCtx, mask: *const u8 /* tiles_y*tiles_x, null = none */) -> c_int;
     pub fn hr_get_tile_mask(ctx: *mut HrCtx, mask: *mut u8, active: *mut u32) -> c_int;
     pub fn hr_select_tiles(ctx: *mut HrCtx, floor: f64, threshold: f64, active: *mut u32) -> c_int;
+    // guide planes {albedo rgb, normal xyz, depth, coverage} (w*h*8 floats) and the variance-guided a-trous denoiser (needs option "moments")
+    pub fn hr_denoise_default_params(out: *mut HrDenoiseParams) -> c_int;
+    pub fn hr_render_guides(ctx: *mut HrCtx) -> c_int;
+    pub fn hr_read_guides(ctx: *mut HrCtx, host: *mut f32 /* w*h*8 */) -> c_int;
+    pub fn hr_write_guides(ctx: *mut HrCtx, host: *const f32) -> c_int;
+    pub fn hr_denoise(ctx: *mut HrCtx, p: *const HrDenoiseParams /* null = defaults */) -> c_int;
+    pub fn hr_read_denoised(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 radiance */) -> c_int;
+    pub fn hr_resolve_denoised(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----
@@ -98,6 +109,7 @@ const _: () = assert!(std::mem::size_of::<HrSkybox>() == 48 && std::mem::align_o
 const _: () = assert!(std::mem::size_of::<HrSceneDesc>() == 248 && std::mem::align_of::<HrSceneDesc>() == 8);   // hr_scene_desc
 const _: () = assert!(std::mem::size_of::<HrCommInfo>() == 32 && std::mem::align_of::<HrCommInfo>() == 8);   // hr_comm_info_t
 const _: () = assert!(std::mem::size_of::<HrNoise>() == 40 && std::mem::align_of::<HrNoise>() == 8);   // hr_noise
+const _: () = assert!(std::mem::size_of::<HrDenoiseParams>() == 40 && std::mem::align_of::<HrDenoiseParams>() == 8);   // hr_denoise_params
 const _: () = assert!(std::mem::size_of::<Vector3>() == 24);   // hr_vec3
 #[cfg(test)]
 mod layout {
@@ -154,6 +166,12 @@ mod layout {
         assert_eq!(off!(HrNoise, pixels_above), 16);
         assert_eq!(off!(HrNoise, mean_error), 24);
         assert_eq!(off!(HrNoise, max_error), 32);
+        assert_eq!(off!(HrDenoiseParams, levels), 0);
+        assert_eq!(off!(HrDenoiseParams, demodulate), 4);
+        assert_eq!(off!(HrDenoiseParams, sigma_color), 8);
+        assert_eq!(off!(HrDenoiseParams, sigma_normal), 16);
+        assert_eq!(off!(HrDenoiseParams, sigma_albedo), 24);
+        assert_eq!(off!(HrDenoiseParams, sigma_depth), 32);
     }
 }
 // ---- END GENERATED ----
