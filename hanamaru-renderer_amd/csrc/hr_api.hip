@@ -123,6 +123,7 @@ struct hr_ctx {
     // by the host — and the denoised radiance D of the last hr_denoise, valid until anything it was made of changes (invalidate_denoised)
     float *guides = nullptr, *denoised = nullptr;
     bool guides_valid = false, denoised_valid = false;
+    uint32_t guide_bounces = 0;   // option "guide_bounces": mirrors and glass the guide rays follow to the first non-delta hit (0: the first hit's planes)
     // the tile mask (hr_set_tile_mask / hr_select_tiles): which 4x4 tiles of the region hr_render covers.  On the device the compacted list of the
     // active tiles' indices, ascending (RenderParams::tile_list), and the flags it was compacted from; on the host the same flags as bytes.
     bool mask_on = false;
@@ -1727,7 +1728,8 @@ int hr_denoise_default_params(hr_denoise_params *out) {
     return HR_OK;
 }
 // One pinhole pass over the whole region, whatever tile mask is set, into the guide planes (stored, not added).  Nothing else is touched: not the
-// accumulator, the moments, the counts or hr_stats.paths; its time goes to debug_kernel_ms / debug_launches.
+// accumulator, the moments, the counts or hr_stats.paths; its time goes to debug_kernel_ms / debug_launches.  Option "guide_bounces" = K > 0:
+// guide_chain_kernel follows mirrors and glass for up to K bounces; 0 is guide_render_kernel, the first hit's planes.
 int hr_render_guides(hr_ctx *c) {
     if (!c) return fail(HR_ERR_INVALID, "hr_render_guides: null ctx");
     int rc;
@@ -1740,11 +1742,14 @@ int hr_render_guides(hr_ctx *c) {
     target_params(c, rp);
     knob_params(c, rp);   // (leaf_den and node_unroll, as hr_render_debug)
     const GuideRenderFn fn = select_guide_render_kernel(c->dsc.qnodes != nullptr);
-    if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_guides: no kernel instantiation for this node format (kernel_variants.h)");
+    const GuideChainFn chain = select_guide_chain_kernel(c->dsc.qnodes != nullptr);
+    if (c->guide_bounces ? !chain : !fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_guides: no kernel instantiation for this node format (kernel_variants.h)");
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
     const uint32_t tiles = rp.tiles_x * rp.tiles_y;
-    hipLaunchKernelGGL(fn, dim3((tiles + TRACE_WAVES - 1) / TRACE_WAVES), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, c->guides);
+    const dim3 grid((tiles + TRACE_WAVES - 1) / TRACE_WAVES), block(64 * TRACE_WAVES);
+    if (c->guide_bounces) hipLaunchKernelGGL(chain, grid, block, 0, c->stream, c->dsc, rp, c->guide_bounces, c->guides);
+    else hipLaunchKernelGGL(fn, grid, block, 0, c->stream, c->dsc, rp, c->guides);
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->debug_events, &c->debug_launches));
     c->guides_valid = true;
     return HR_OK;
@@ -2036,6 +2041,14 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
     // has received: what a tile mask (hr_set_tile_mask) needs — the mask goes when the counts go
     if (k == "moments") return set_plane_option(c, value, MOMENTS, COUNTS, [](hr_ctx *x) { return plane_free(x, NOISE_IMG); });
     if (k == "sample_counts") return set_plane_option(c, value, COUNTS, MOMENTS, remove_mask);
+    if (k == "guide_bounces") {  // next hr_render_guides; a new value drops the planes it would no longer describe, and the image filtered with them
+        if (!(value >= 0 && value <= 8) || value != std::floor(value)) return fail(HR_ERR_INVALID, "guide_bounces must be a whole number in [0,8]");
+        if ((uint32_t)value == c->guide_bounces) return HR_OK;
+        c->guide_bounces = (uint32_t)value;
+        c->guides_valid = false;
+        invalidate_denoised(c);
+        return HR_OK;
+    }
     if (k == "max_tail_gib") {
         if (value < 1 || value > 128) return fail(HR_ERR_INVALID, "max_tail_gib must be in [1,128]");
         c->max_tail_bytes = (uint64_t)value << 30;

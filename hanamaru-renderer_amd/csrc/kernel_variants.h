@@ -103,6 +103,13 @@ static const GuideRenderVariant GUIDE_RENDER_VARIANTS[] = {HR_VARIANT(guide_rend
 static GuideRenderFn select_guide_render_kernel(bool qn) {
     return fn_of(find_row(GUIDE_RENDER_VARIANTS, [&](const GuideRenderVariant &r) { return r.qn == qn; }));
 }
+// ---- guide_chain_kernel<QN> (trace_kernel.h): the guide planes at the first non-delta hit (option guide_bounces > 0); 0 bounces is the kernel above ----
+typedef void (*GuideChainFn)(Scene, RenderParams, uint32_t, float *);
+struct GuideChainVariant { bool qn; GuideChainFn fn; };
+static const GuideChainVariant GUIDE_CHAIN_VARIANTS[] = {HR_VARIANT(guide_chain_kernel, true), HR_VARIANT(guide_chain_kernel, false)};
+static GuideChainFn select_guide_chain_kernel(bool qn) {
+    return fn_of(find_row(GUIDE_CHAIN_VARIANTS, [&](const GuideChainVariant &r) { return r.qn == qn; }));
+}
 typedef void (*TraceDebugFn)(Scene, RenderParams, uint32_t, const float *, const float *, float *, int32_t *, Counters *);
 struct TraceDebugVariant { bool qn, cnt; TraceDebugFn fn; };
 static const TraceDebugVariant TRACE_DEBUG_VARIANTS[] = {HR_VARIANT(trace_debug_kernel, true, false), HR_VARIANT(trace_debug_kernel, false, false),

@@ -948,6 +948,39 @@ HD void guide_primary(const Scene &sc, const Ray &ray, const TraceState &ts, flo
     g[6] = ts.t;
     g[7] = 1.0f;
 }
+// The guide values at the first NON-DELTA hit (option "guide_bounces" = K > 0; guide_chain_kernel in trace_kernel.h): the pinhole
+// ray is followed through Specular (1) and Refraction (2) surfaces — a deterministic chain: the mirror direction, and for glass the branch
+// sample_refraction takes for the draw r0 = 1 (transmission; the reflection on total internal reflection and on its degenerate cases) — for at
+// most K bounces.  g[8] = {product of the albedos along the chain (the sampled-bounce scalar `refl` is not part of it), the terminal hit's world
+// normal, the path length summed over the segments, coverage 1}.  A primary miss is eight zeros; a chain that leaves the scene after a bounce ends
+// at its last hit (a mirror that shows sky is guided like the mirror).  With K = 0 it is guide_primary bit for bit: 1.0f x a and 0 + t are exact.
+struct GuideChain { V3f a; float z; };   // the albedo product and the path length so far
+HD void guide_chain_begin(GuideChain &gc, float *g) {
+    gc.a = v3(1.0f, 1.0f, 1.0f); gc.z = 0.0f;
+    for (int k = 0; k < 8; k++) g[k] = 0.0f;
+}
+// One link, per lane: the closest hit `ts` of `ray` into g.  `last`: this was walk K.  True when the chain goes on — `ray` is then the bounce ray
+// (ray_set only: the caller quantises it and begins the walk); false when g is final.  No RayFix, as guide_primary.
+HD bool guide_chain_link(const Scene &sc, Ray &ray, const TraceState &ts, bool last, GuideChain &gc, float *g) {
+    if (ts.prim < 0) return false;   // the primary ray: g is still eight zeros; after a bounce: g holds the last hit
+    Surf s;
+    hit_surface(sc, ray, ts, material_needs_uv(sc, hit_element(sc, ts)), s);
+    PointMat pm;
+    material_at(sc, s.elem, s.u, s.v, pm);
+    gc.z += ts.t;
+    gc.a = gc.a * pm.albedo;
+    g[0] = gc.a.x; g[1] = gc.a.y; g[2] = gc.a.z;
+    g[3] = s.n.x; g[4] = s.n.y; g[5] = s.n.z;
+    g[6] = gc.z;
+    g[7] = 1.0f;
+    if (last || (pm.surface != 1 && pm.surface != 2)) return false;
+    V3f no, nd;
+    float refl;
+    bool transmitted;
+    bsdf_sample(pm, 1.0f, 0.0f, s.pos, -ray.d, s.n, no, nd, refl, transmitted);
+    ray_set(ray, no, nd);
+    return true;
+}
 // scalar form (host emulation): one node + its leaf per step
 template <bool CNT>
 HD V3f debug_pixel(const Scene &sc, const RenderParams &rp, uint32_t px, uint32_t py, uint32_t sub, int mode, LaneCounters *cn) {

@@ -456,3 +456,42 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void guide_render_kernel(Scene sc
         for (int k = 0; k < 8; k++) o[k] = g[k] * 0.25f;
     }
 }
+
+// The guide planes at the first non-delta hit (option "guide_bounces" = K > 0): guide_render_kernel with guide_chain_link
+// (pt_core.h) after every walk.  A lane whose hit is a mirror or glass and whose chain has bounces left sets its next ray; the others are parked,
+// as the lanes without a shadow ray are in debug_render_kernel.  The wave walks again while any lane has a ray: at most K more walks.  The sums
+// and the store are guide_render_kernel's.
+template <bool QN>
+__global__ __launch_bounds__(64 * TRACE_WAVES) void guide_chain_kernel(Scene sc, RenderParams rp, uint32_t bounces, float *__restrict__ guides) {
+    const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * TRACE_WAVES + (threadIdx.x >> 6);
+    if (tile >= rp.tiles_x * rp.tiles_y) return;
+    uint32_t px, py, sub;
+    tile_lane_pixel(rp, tile, lane, px, py, sub);
+    const bool active = rp_in_region(rp, px, py);
+    LaneCounters lc = {0, 0, 0, 0, 0, 0};
+    WaveStats ws = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}, 0};
+    Path p;
+    p.q = active ? lane : PATH_IDLE;
+    p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
+    debug_camera_ray(sc, rp, rp.org_x + (active ? px : 0u), rp.org_y + (active ? py : 0u), sub, p.ray);
+    const uint32_t leaf_den = rp.leaf_den ? rp.leaf_den : 2u;
+    uint32_t tick = 0;
+    float g[8];
+    GuideChain gc;
+    guide_chain_begin(gc, g);
+    bool more = active;
+    for (uint32_t j = 0;; j++) {
+        ray_quantise(sc, p.ray);
+        trace_begin(p.ts, T_INF, p.ray.start);
+        if (!more) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
+        traverse_wave<false, QN>(sc, rp, p, more, (uint32_t)__popcll(wave_ballot(more)), 0u, leaf_den, lc, ws, tick, rp.trace_boost);
+        more = more && guide_chain_link(sc, p.ray, p.ts, j >= bounces, gc, g);
+        if (!wave_ballot(more)) break;
+    }
+    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 1);
+    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 2);
+    if (active && sub == 0u) {
+        float *o = guides + ((size_t)py * rp_reg_w(rp) + px) * 8;
+        for (int k = 0; k < 8; k++) o[k] = g[k] * 0.25f;
+    }
+}

@@ -11,7 +11,8 @@
 // --adaptive E / --sample-image FILE (options "moments" + "sample_counts": after a uniform first phase only the 4x4 tiles that still hold a pixel
 // with a relative standard error above E are rendered on; hr_select_tiles, hr_resolve_counted),
 // --denoise / --denoise-levels N / --guide-image PREFIX (option "moments": the final image is the variance-guided a-trous filter's, hr_denoise +
-// hr_resolve_denoised; the first-hit guide planes as images of their own, hr_render_guides + hr_read_guides).
+// hr_resolve_denoised; the guide planes as images of their own, hr_render_guides + hr_read_guides), --guide-bounces K (option "guide_bounces":
+// the guide rays follow mirrors and glass for up to K bounces to the first rough hit; 0, the default, is the first hit).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -98,7 +99,11 @@ static void usage(const char *prog) {
            "                        filter levels, 0 .. 5 (default 4; the taps of level l are 2^l pixels apart)\n"
            "        --guide-image PREFIX\n"
            "                        write the guide planes as PREFIX_albedo.png, PREFIX_normal.png ((n + 1) / 2) and PREFIX_depth.png (depth / largest\n"
-           "                        depth, grey).  One device only; not with --debug.\n",
+           "                        depth, grey).  One device only; not with --debug.\n"
+           "        --guide-bounces K\n"
+           "                        the guide planes follow mirrors and glass (Specular and Refraction surfaces) for up to K bounces, 0 .. 8, to the\n"
+           "                        first rough hit: albedo is the product along the chain, the normal the last hit's, depth the path length.\n"
+           "                        Default 0: the first hit.  Needs --denoise or --guide-image.\n",
            prog);
 }
 
@@ -121,6 +126,7 @@ int main(int argc, char **argv) {
     bool denoise = false;
     long long denoise_levels = -1;   // -1: the library's default
     std::string guide_prefix;
+    long long guide_bounces = -1;    // -1: not given (the library's default, 0)
     // a number, the whole argument, not NaN; what is wrong with it is said with the flag's name, before any device is opened
     auto number = [](const char *flag, const char *text, double *out) -> bool {
         char *e = nullptr;
@@ -178,6 +184,12 @@ int main(int argc, char **argv) {
             denoise_levels = strtoll(t, &e, 10);
             if (e == t || *e || denoise_levels < 0 || denoise_levels > 5) { fprintf(stderr, "--denoise-levels must be a whole number in 0 .. 5, not '%s'.\n", t); return 1; }
         } else if (a == "--guide-image") guide_prefix = val("guide-image");
+        else if (a == "--guide-bounces") {
+            const char *t = val("guide-bounces");
+            char *e = nullptr;
+            guide_bounces = strtoll(t, &e, 10);
+            if (e == t || *e || guide_bounces < 0 || guide_bounces > 8) { fprintf(stderr, "--guide-bounces must be a whole number in 0 .. 8, not '%s'.\n", t); return 1; }
+        }
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -197,6 +209,7 @@ int main(int argc, char **argv) {
         if (debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
     }
     if (denoise_levels >= 0 && !denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
+    if (guide_bounces >= 0 && !denoise && guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
     if (denoise || !guide_prefix.empty()) {
         size_t ids = gpu_ids.empty() ? 0 : 1;
         for (char ch : gpu_ids) ids += ch == ',';
@@ -273,6 +286,7 @@ int main(int argc, char **argv) {
         if (precise >= 0) CHECK_HR(hr_set_option(ctxs[r], "precise_shading", (double)precise));
         if (moments) CHECK_HR(hr_set_option(ctxs[r], "moments", 1.0));
         if (counts) CHECK_HR(hr_set_option(ctxs[r], "sample_counts", 1.0));
+        if (guide_bounces >= 0) CHECK_HR(hr_set_option(ctxs[r], "guide_bounces", (double)guide_bounces));
     }
     hr_ctx *ctx = ctxs[0];
     if (ndev > 1) tee("devices: %u.", ndev);

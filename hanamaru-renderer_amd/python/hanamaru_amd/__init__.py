@@ -536,7 +536,8 @@ class Renderer:
 
     # ---- guide planes and the denoiser (include/hanamaru_hip.h)
     def render_guides(self):
-        """hr_render_guides: one pinhole pass into the guide planes."""
+        """hr_render_guides: one pinhole pass into the guide planes (set_option("guide_bounces", K), K in 0 .. 8: through up to K mirrors and
+        glass surfaces to the first rough hit; default 0, the first hit)."""
         self._check(self.L.hr_render_guides(self._h))
 
     def read_guides(self):

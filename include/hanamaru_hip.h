@@ -353,6 +353,14 @@ int hr_select_tiles(hr_ctx *ctx, double floor, double threshold, uint32_t *activ
  *     moments, the counts or hr_stats.paths; its time goes to hr_stats.debug_kernel_ms / debug_launches.  hr_read_guides returns the planes as
  *     outputs in their own right (AOVs; HR_ERR_INVALID while there are none); hr_write_guides replaces them (resume, stitching, synthetic inputs).
  *     The buffer is allocated on first use, dropped by hr_set_resolution, hr_set_region and hr_upload_scene, and kept by hr_clear.
+ *   - Option "guide_bounces" = K, 1 .. 8 (default 0: the planes above): the guide ray follows mirrors and glass — the Specular and Refraction
+ *     surface types, whose bounce is deterministic — for up to K bounces, and the planes hold the first hit that is neither.  A mirror is
+ *     followed along its mirror direction; glass along the branch the sampler takes for the draw r0 = 1: transmission, or the reflection on total
+ *     internal reflection.  GGX, GGXRefraction and Diffuse end the chain; a chain that leaves the scene after a bounce ends at its last hit (a
+ *     mirror that shows sky is guided like the mirror); a primary miss is eight zeros as before.  Albedo is then the PRODUCT of the albedos along
+ *     the chain, the normal the terminal hit's world normal, depth the path length summed over the segments; coverage, the 2x2 mean, the layout,
+ *     the region contract, the ignored tile mask and the accounting are as above.  The definition is guide_chain_link in csrc/pt_core.h; with
+ *     K = 0 it is the first hit's values bit for bit.  Setting a new value drops the guide planes (rendered or written) and invalidates D.
  *   - hr_denoise computes D, w x h x 3 floats of radiance (what accumulator x 1 / (4 n) is), from this context's OWN accumulator — never the
  *     all-reduced total: a sharded host writes the summed accumulator, moments and counts into one context, as it does for the estimate —,
  *     the moments and the guides.  The definition is csrc/denoise_core.h, to the bit (f64, + - x / max only, one IEEE operation per step, no FMA):
@@ -380,9 +388,11 @@ int hr_select_tiles(hr_ctx *ctx, double floor, double threshold, uint32_t *activ
  *     pixel depends on inputs up to 2 x (2^levels - 1) pixels away, so pixels within that distance of the edge differ from the full-frame
  *     result and those further inside equal it.  As with the bilateral filter, exact tiles of a frame come from stitching the tiles'
  *     accumulators, moments, counts and guides into one full-frame context.
- *   - What it is not: there is no temporal part, and the guides are the FIRST hit's — what is seen through or in glass and mirrors is guided
- *     by the glass surface.  The sigmas are design parameters: the defaults are the best row of a small host-side sweep
- *     (DESIGN.md 4.9 has the table), which also shows the filter RAISING the error of a 64-sampling rtcamp6_v3_1 render: it is for short renders.
+ *   - What it is not: there is no temporal part.  By default the guides are the FIRST hit's — what is seen through or in glass and mirrors is
+ *     guided by the glass surface; "guide_bounces" follows mirrors and glass to the first rough hit, but not low-roughness GGX, only one branch
+ *     at glass (no separate reflect / transmit planes), and the normal is not reflected into a mirror's virtual space.  The sigmas are design
+ *     parameters: the defaults are the best row of a small host-side sweep (DESIGN.md 4.9 has the tables).  With first-hit guides that sweep
+ *     shows the filter RAISING the error of a 64-sampling rtcamp6_v3_1 render (ratio 1.50); with "guide_bounces" 2 the same figure is 0.60.
  *   - Cost at 1920x1080: not yet measured on the device (hr_stats.post_kernel_ms of one hr_denoise, debug_kernel_ms of one hr_render_guides);
  *     hr_denoise holds 2 x w x h x 6 doubles of scratch for the call (199 MB).  All of these synchronise except hr_render_guides. */
 typedef struct hr_denoise_params {
@@ -391,7 +401,7 @@ typedef struct hr_denoise_params {
     double sigma_color, sigma_normal, sigma_albedo, sigma_depth;
 } hr_denoise_params;
 int hr_denoise_default_params(hr_denoise_params *out);
-int hr_render_guides(hr_ctx *ctx);                         /* one pinhole pass into the guide buffer */
+int hr_render_guides(hr_ctx *ctx);                         /* one pinhole pass into the guide buffer ("guide_bounces": through mirrors and glass) */
 int hr_read_guides(hr_ctx *ctx, float *host /* w*h*8 */);  /* the planes as outputs in their own right (AOVs) */
 int hr_write_guides(hr_ctx *ctx, const float *host);       /* resume, stitching, synthetic inputs */
 int hr_denoise(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */);
@@ -426,6 +436,10 @@ int hr_get_stats(hr_ctx *ctx, hr_stats *out);
  *                   the image does not change by a bit
  *   "sample_counts" 0 (default) / 1: keep per-pixel counts of the samplings received, for hr_set_tile_mask / hr_select_tiles /
  *                   hr_resolve_counted (see there); the image does not change by a bit
+ *   next hr_render_guides:
+ *   "guide_bounces" 0 (default) .. 8, a whole number: how many mirrors and glass surfaces the guide rays follow to the first rough hit (see
+ *                   "guide planes" above).  A new value drops the guide planes and the denoised image; the value it already has changes
+ *                   nothing; anything else is HR_ERR_INVALID and changes nothing.  No rendered image depends on it.
  *   next hr_upload_scene:
  *   "bvh_builder"   -1 = by scene size (default): the host's binned-SAH build below 200,000 primitives (the best tree; one host thread,
  *                   < 1 s), the device PLOC build from there on (0.97 - 0.99 of that tree's quality; 4 x 10^6 triangles in 38 ms instead of
