@@ -1280,6 +1280,24 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     return HR_OK;
 }
 
+// One pass of a single-ray tile kernel (trace_kernel.h: the debug renderer, the guide kernels) over the region: one wave per 4x4-pixel tile, the
+// trace side's knobs (the kernels read leaf_den and node_unroll of them), timed into debug_kernel_ms / debug_launches.  `args`: what the kernel
+// takes behind (Scene, RenderParams).
+extern "C++" {   // (a template inside the C ABI's block)
+template <class Fn, class... Args>
+static int launch_tile_pass(hr_ctx *c, Fn fn, Args... args) {
+    RenderParams rp{};
+    target_params(c, rp);
+    knob_params(c, rp);
+    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    hipLaunchKernelGGL(fn, dim3((tiles + TRACE_WAVES - 1) / TRACE_WAVES), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, args...);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->debug_events, &c->debug_launches));
+    return HR_OK;
+}
+}  // extern "C++"
+
 int hr_render_debug(hr_ctx *c, int mode) {
     if (!c || mode < 0 || mode > 3) return fail(HR_ERR_INVALID, "hr_render_debug: mode must be 0..3");
     // (this entry point has always asked in an order of its own — scene, target, moments, mask, counts — and renders a region: one need at a time)
@@ -1291,17 +1309,9 @@ int hr_render_debug(hr_ctx *c, int mode) {
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
     invalidate_denoised(c);
-    RenderParams rp{};
-    target_params(c, rp);
-    knob_params(c, rp);   // (the debug kernels read leaf_den and node_unroll of them)
     const DebugRenderFn fn = select_debug_render_kernel(c->counters, c->dsc.qnodes != nullptr);
     if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: no kernel instantiation for these options (kernel_variants.h)");
-    EventPair ev;
-    HIP_TRY(timed_begin(ev, c->stream));
-    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
-    hipLaunchKernelGGL(fn, dim3((tiles + TRACE_WAVES - 1) / TRACE_WAVES), dim3(64 * TRACE_WAVES), 0, c->stream, c->dsc, rp, mode, c->accum, c->d_counters);
-    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->debug_events, &c->debug_launches));
-    return HR_OK;
+    return launch_tile_pass(c, fn, mode, c->accum, c->d_counters);
 }
 
 int hr_synchronize(hr_ctx *c) {
@@ -1738,19 +1748,10 @@ int hr_render_guides(hr_ctx *c) {
     invalidate_denoised(c);
     c->guides_valid = false;
     if (!c->guides && (rc = plane_alloc(c, GUIDES))) return rc;
-    RenderParams rp{};
-    target_params(c, rp);
-    knob_params(c, rp);   // (leaf_den and node_unroll, as hr_render_debug)
     const GuideRenderFn fn = select_guide_render_kernel(c->dsc.qnodes != nullptr);
     const GuideChainFn chain = select_guide_chain_kernel(c->dsc.qnodes != nullptr);
     if (c->guide_bounces ? !chain : !fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_guides: no kernel instantiation for this node format (kernel_variants.h)");
-    EventPair ev;
-    HIP_TRY(timed_begin(ev, c->stream));
-    const uint32_t tiles = rp.tiles_x * rp.tiles_y;
-    const dim3 grid((tiles + TRACE_WAVES - 1) / TRACE_WAVES), block(64 * TRACE_WAVES);
-    if (c->guide_bounces) hipLaunchKernelGGL(chain, grid, block, 0, c->stream, c->dsc, rp, c->guide_bounces, c->guides);
-    else hipLaunchKernelGGL(fn, grid, block, 0, c->stream, c->dsc, rp, c->guides);
-    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->debug_events, &c->debug_launches));
+    if ((rc = c->guide_bounces ? launch_tile_pass(c, chain, c->guide_bounces, c->guides) : launch_tile_pass(c, fn, c->guides))) return rc;
     c->guides_valid = true;
     return HR_OK;
 }

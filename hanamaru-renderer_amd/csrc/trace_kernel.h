@@ -1,4 +1,6 @@
-// The path-tracing megakernel and the two small debug kernels that share its per-lane code — included by hr_api.hip only (one translation unit: the kernels and the C ABI that launches them).
+// The path-tracing megakernel, the pass that sums its records into the accumulator, and the single-ray kernels that send one ray per lane
+// through its traversal (the ray queries, the debug renderer, the denoiser's guide planes) — included by hr_api.hip only (one translation unit: the kernels
+// and the C ABI that launches them).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -314,6 +316,51 @@ __global__ __launch_bounds__(256) void accumulate_kernel(RenderParams rp, const 
     }
 }
 
+// ---- the single-ray wave: one ray per lane through traverse_wave, then the lane reads its hit ----
+// What the query kernels (trace_debug_kernel, intersect_debug_kernel), the debug renderer and the guide kernels share, written once.
+
+// One walk of the wave: the lanes with `has_ray` send p.ray through the production traversal, closest hit within `limit`; the others are parked
+// (a parked lane is trace_done: traverse_wave never touches it).  The ray is quantised BEFORE the walk begins, which starts at the node the
+// quantisation chose.  No lane waits for a phase A here (adv_den 0).  `tick` runs on across a kernel's walks; CNT counts the ray.
+template <bool CNT, bool QN>
+__device__ __forceinline__ void walk_wave(const Scene &sc, const RenderParams &rp, Path &p, const bool has_ray, const float limit, LaneCounters &lc, WaveStats &ws, uint32_t &tick) {
+    ray_quantise(sc, p.ray);
+    trace_begin(p.ts, limit, p.ray.start);
+    if (!has_ray) { p.ts.cur = NODE_END; p.ts.leaf = 0; p.ts.leaf2 = 0; }
+    traverse_wave<CNT, QN>(sc, rp, p, has_ray, (uint32_t)__popcll(wave_ballot(has_ray)), 0u, rp.leaf_den ? rp.leaf_den : 2u, lc, ws, tick, rp.trace_boost);
+    if (CNT && has_ray) lc.rays++;
+}
+
+// The four sub-samples of a pixel sit in neighbouring lanes: every lane of the quad gets their sum, by two lane exchanges (renderer.rs:48-60
+// adds them in order; the fp32 sum differs from that order by an ulp at most).  Every lane of the wave is here.
+__device__ __forceinline__ float quad_sum(float v) {
+    v += __shfl_xor(v, 1);
+    return v + __shfl_xor(v, 2);
+}
+// the guide kernels' store: the sub-sample 0 lane STORES the mean (sum x 0.25f, exact) into guides[reg_h][reg_w][8] — a pass replaces the planes
+__device__ __forceinline__ void guide_store(const RenderParams &rp, const bool active, uint32_t px, uint32_t py, uint32_t sub, float *g, float *__restrict__ guides) {
+    for (int k = 0; k < 8; k++) g[k] = quad_sum(g[k]);
+    if (active && sub == 0u) {
+        float *o = guides + ((size_t)py * rp_reg_w(rp) + px) * 8;
+        for (int k = 0; k < 8; k++) o[k] = g[k] * 0.25f;
+    }
+}
+// a query's answer: out[i][8] = {hit, t, pos xyz, normal xyz} (a miss: 0, the search limit, six zeros) and the element, -1 for a miss
+__device__ __forceinline__ void write_hit_record(const Scene &sc, const Ray &ray, const TraceState &ts, uint32_t i, float *__restrict__ out, int32_t *__restrict__ out_elem) {
+    float *o = out + (size_t)i * 8;
+    int32_t elem = -1;
+    if (ts.prim >= 0) {
+        Surf s;
+        hit_surface(sc, ray, ts, true, s);
+        elem = s.elem;
+        o[0] = 1.0f; o[1] = ts.t; o[2] = s.pos.x; o[3] = s.pos.y; o[4] = s.pos.z; o[5] = s.n.x; o[6] = s.n.y; o[7] = s.n.z;
+    } else {
+        o[0] = 0.0f; o[1] = ts.t;
+        for (int k = 2; k < 8; k++) o[k] = 0.0f;
+    }
+    out_elem[i] = elem;
+}
+
 // hr_debug_trace: closest-hit / shadow queries through the PRODUCTION traversal — traverse_wave on the record format the renderer
 // walks, box and leaf phases, two parked leaves, closest-hit culling, and for shadow queries (shadow_len > 0) the search limit of
 // nee_setup and shadow_early_out.  One wave = 64 rays; lanes whose walk is done idle, as lanes waiting for phase A do in the megakernel.
@@ -328,31 +375,15 @@ __global__ __launch_bounds__(64) void trace_debug_kernel(Scene sc, RenderParams 
     p.q = active ? 0u : PATH_IDLE;
     p.tile = 0; p.st = 1u;
     ray_set(p.ray, v3(rays[j * 6], rays[j * 6 + 1], rays[j * 6 + 2]), v3(rays[j * 6 + 3], rays[j * 6 + 4], rays[j * 6 + 5]));
-    ray_quantise(sc, p.ray);
     const float sl = shadow_len ? shadow_len[j] : 0.0f;
     p.shadow_len = sl;
-    if (sl > 0.0f) { trace_begin(p.ts, sl + 0.03f, p.ray.start); p.st |= 16u; }   // nee_setup's search limit, shadow phase
-    else trace_begin(p.ts, T_INF, p.ray.start);
-    if (!active) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
+    if (sl > 0.0f) p.st |= 16u;   // shadow phase, with nee_setup's search limit
     LaneCounters lc = {0, 0, 0, 0, 0, 0};
     WaveStats ws = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}, 0};
-    const uint32_t n_active = (uint32_t)__popcll(wave_ballot(active));
     uint32_t tick = 0;
-    traverse_wave<CNT, QN>(sc, rp, p, active, n_active, 0u, rp.leaf_den ? rp.leaf_den : 2u, lc, ws, tick, rp.trace_boost);
-    if (CNT) { if (active) lc.rays++; flush_counters<CNT>(cnt, threadIdx.x & 63u, active ? 1u : 0u, lc, ws); }
-    if (!active) return;
-    float *o = out + (size_t)i * 8;
-    int32_t elem = -1;
-    if (p.ts.prim >= 0) {
-        Surf s;
-        hit_surface(sc, p.ray, p.ts, true, s);
-        elem = s.elem;
-        o[0] = 1.0f; o[1] = p.ts.t; o[2] = s.pos.x; o[3] = s.pos.y; o[4] = s.pos.z; o[5] = s.n.x; o[6] = s.n.y; o[7] = s.n.z;
-    } else {
-        o[0] = 0.0f; o[1] = p.ts.t;
-        for (int k = 2; k < 8; k++) o[k] = 0.0f;
-    }
-    out_elem[i] = elem;
+    walk_wave<CNT, QN>(sc, rp, p, active, sl > 0.0f ? sl + 0.03f : T_INF, lc, ws, tick);
+    flush_counters<CNT>(cnt, threadIdx.x & 63u, active ? 1u : 0u, lc, ws);
+    if (active) write_hit_record(sc, p.ray, p.ts, i, out, out_elem);
 }
 
 __global__ void intersect_debug_kernel(Scene sc, uint32_t n, const float *__restrict__ rays, float *__restrict__ out, int32_t *__restrict__ out_elem) {
@@ -364,24 +395,12 @@ __global__ void intersect_debug_kernel(Scene sc, uint32_t n, const float *__rest
     trace_begin(ts, T_INF);
     LaneCounters lc;
     while (ts.cur != NODE_END) trace_step<false>(sc, r, ts, &lc);
-    float *o = out + (size_t)i * 8;
-    int32_t elem = -1;
-    if (ts.prim >= 0) {
-        Surf s;
-        hit_surface(sc, r, ts, true, s);
-        elem = s.elem;
-        o[0] = 1.0f; o[1] = ts.t; o[2] = s.pos.x; o[3] = s.pos.y; o[4] = s.pos.z; o[5] = s.n.x; o[6] = s.n.y; o[7] = s.n.z;
-    } else {
-        o[0] = 0.0f; o[1] = ts.t;
-        for (int k = 2; k < 8; k++) o[k] = 0.0f;
-    }
-    out_elem[i] = elem;
+    write_hit_record(sc, r, ts, i, out, out_elem);
 }
 
-// DebugRenderer (renderer.rs:101-146) through the production traversal: one wave per 4x4-pixel tile, one lane per (pixel, sub-sample)
-// as in the megakernel, pinhole rays, no RNG, no seed kernel next to it.  Depth mode (2) is the traversal-only workload of bench.py:
-// camera rays, closest hits, nothing shaded.  The four sub-samples of a pixel sit in neighbouring lanes and are summed with two
-// lane exchanges (renderer.rs:48-60 adds them in order; the fp32 sum differs from that order by an ulp at most).
+// DebugRenderer (renderer.rs:101-146) through the production traversal: one wave per 4x4-pixel tile, one lane per (pixel, sub-sample) as in the
+// megakernel, pinhole rays, no RNG, no seed kernel next to it.  Depth mode (2) is
+// the traversal-only workload of bench.py: camera rays, closest hits, nothing shaded.  The pixel's sum is ADDED to the accumulator.
 template <bool CNT, bool QN>
 __global__ __launch_bounds__(64 * TRACE_WAVES) void debug_render_kernel(Scene sc, RenderParams rp, int mode, float *__restrict__ accum, Counters *cnt) {
     const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * TRACE_WAVES + (threadIdx.x >> 6);
@@ -395,28 +414,17 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void debug_render_kernel(Scene sc
     p.q = active ? lane : PATH_IDLE;
     p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
     debug_camera_ray(sc, rp, rp.org_x + (active ? px : 0u), rp.org_y + (active ? py : 0u), sub, p.ray);
-    ray_quantise(sc, p.ray);
-    trace_begin(p.ts, T_INF, p.ray.start);
-    if (!active) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
-    const uint32_t n_active = (uint32_t)__popcll(wave_ballot(active));
-    const uint32_t leaf_den = rp.leaf_den ? rp.leaf_den : 2u;
     uint32_t tick = 0;
-    traverse_wave<CNT, QN>(sc, rp, p, active, n_active, 0u, leaf_den, lc, ws, tick, rp.trace_boost);
-    if (CNT && active) lc.rays++;
+    walk_wave<CNT, QN>(sc, rp, p, active, T_INF, lc, ws, tick);
     V3f val = v3(0, 0, 0), lit = v3(0, 0, 0);
     Ray sh = p.ray;
     const bool more = active && debug_primary(sc, p.ray, p.ts, mode, val, lit, sh);
     if (wave_ballot(more)) {   // Shading mode: the shadow ray towards the fixed light, any closest hit darkens
         p.ray = sh;
-        ray_quantise(sc, p.ray);
-        trace_begin(p.ts, T_INF, p.ray.start);
-        if (!more) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
-        traverse_wave<CNT, QN>(sc, rp, p, more, (uint32_t)__popcll(wave_ballot(more)), 0u, leaf_den, lc, ws, tick, rp.trace_boost);
-        if (CNT && more) lc.rays++;
+        walk_wave<CNT, QN>(sc, rp, p, more, T_INF, lc, ws, tick);
         if (more) val = val + lit * (p.ts.prim >= 0 ? 0.5f : 1.0f);
     }
-    val.x += __shfl_xor(val.x, 1); val.y += __shfl_xor(val.y, 1); val.z += __shfl_xor(val.z, 1);
-    val.x += __shfl_xor(val.x, 2); val.y += __shfl_xor(val.y, 2); val.z += __shfl_xor(val.z, 2);
+    val.x = quad_sum(val.x); val.y = quad_sum(val.y); val.z = quad_sum(val.z);
     if (active && sub == 0u) {
         float *o = accum + ((size_t)py * rp_reg_w(rp) + px) * 3;
         o[0] += val.x; o[1] += val.y; o[2] += val.z;
@@ -424,9 +432,8 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void debug_render_kernel(Scene sc
     flush_counters<CNT>(cnt, lane, (uint32_t)active, lc, ws);
 }
 
-// The denoiser's guide planes: debug_render_kernel's tile / lane mapping, pinhole ray and walk, with guide_primary in place of
-// the visualisers — no shadow ray, no counters build.  The four sub-samples of a pixel are summed with the same two lane exchanges, and the
-// sub-sample 0 lane STORES the mean (sum x 0.25f, exact) into guides[reg_h][reg_w][8]: a pass replaces the planes, it does not add to them.
+// The denoiser's guide planes: debug_render_kernel's tile / lane mapping and pinhole ray, the first hit's guide_primary — no shadow
+// ray, no counters build.
 template <bool QN>
 __global__ __launch_bounds__(64 * TRACE_WAVES) void guide_render_kernel(Scene sc, RenderParams rp, float *__restrict__ guides) {
     const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * TRACE_WAVES + (threadIdx.x >> 6);
@@ -440,27 +447,16 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void guide_render_kernel(Scene sc
     p.q = active ? lane : PATH_IDLE;
     p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
     debug_camera_ray(sc, rp, rp.org_x + (active ? px : 0u), rp.org_y + (active ? py : 0u), sub, p.ray);
-    ray_quantise(sc, p.ray);
-    trace_begin(p.ts, T_INF, p.ray.start);
-    if (!active) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
-    const uint32_t n_active = (uint32_t)__popcll(wave_ballot(active));
-    const uint32_t leaf_den = rp.leaf_den ? rp.leaf_den : 2u;
     uint32_t tick = 0;
-    traverse_wave<false, QN>(sc, rp, p, active, n_active, 0u, leaf_den, lc, ws, tick, rp.trace_boost);
+    walk_wave<false, QN>(sc, rp, p, active, T_INF, lc, ws, tick);
     float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (active) guide_primary(sc, p.ray, p.ts, g);
-    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 1);
-    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 2);
-    if (active && sub == 0u) {
-        float *o = guides + ((size_t)py * rp_reg_w(rp) + px) * 8;
-        for (int k = 0; k < 8; k++) o[k] = g[k] * 0.25f;
-    }
+    guide_store(rp, active, px, py, sub, g, guides);
 }
 
-// The guide planes at the first non-delta hit (option "guide_bounces" = K > 0): guide_render_kernel with guide_chain_link
-// (pt_core.h) after every walk.  A lane whose hit is a mirror or glass and whose chain has bounces left sets its next ray; the others are parked,
-// as the lanes without a shadow ray are in debug_render_kernel.  The wave walks again while any lane has a ray: at most K more walks.  The sums
-// and the store are guide_render_kernel's.
+// The guide planes at the first non-delta hit (option "guide_bounces" = K > 0): guide_chain_link (pt_core.h) after every walk.
+// A lane whose hit is a mirror or glass and whose chain has bounces left sets its next ray; the others are parked.  The wave walks again while
+// any lane has a ray: at most K more walks.
 template <bool QN>
 __global__ __launch_bounds__(64 * TRACE_WAVES) void guide_chain_kernel(Scene sc, RenderParams rp, uint32_t bounces, float *__restrict__ guides) {
     const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * TRACE_WAVES + (threadIdx.x >> 6);
@@ -474,24 +470,15 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void guide_chain_kernel(Scene sc,
     p.q = active ? lane : PATH_IDLE;
     p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
     debug_camera_ray(sc, rp, rp.org_x + (active ? px : 0u), rp.org_y + (active ? py : 0u), sub, p.ray);
-    const uint32_t leaf_den = rp.leaf_den ? rp.leaf_den : 2u;
     uint32_t tick = 0;
     float g[8];
     GuideChain gc;
     guide_chain_begin(gc, g);
     bool more = active;
     for (uint32_t j = 0;; j++) {
-        ray_quantise(sc, p.ray);
-        trace_begin(p.ts, T_INF, p.ray.start);
-        if (!more) { p.ts.cur = NODE_END; p.ts.leaf = 0; }
-        traverse_wave<false, QN>(sc, rp, p, more, (uint32_t)__popcll(wave_ballot(more)), 0u, leaf_den, lc, ws, tick, rp.trace_boost);
+        walk_wave<false, QN>(sc, rp, p, more, T_INF, lc, ws, tick);
         more = more && guide_chain_link(sc, p.ray, p.ts, j >= bounces, gc, g);
         if (!wave_ballot(more)) break;
     }
-    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 1);
-    for (int k = 0; k < 8; k++) g[k] += __shfl_xor(g[k], 2);
-    if (active && sub == 0u) {
-        float *o = guides + ((size_t)py * rp_reg_w(rp) + px) * 8;
-        for (int k = 0; k < 8; k++) o[k] = g[k] * 0.25f;
-    }
+    guide_store(rp, active, px, py, sub, g, guides);
 }

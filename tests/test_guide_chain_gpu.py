@@ -295,6 +295,55 @@ def test_quality_ratios_with_and_without_the_chain(ha, scenes, scene):
         assert ratios[(64, 4)] < ratios[(64, 0)]
 
 
+# ---------------------------------------------------------------------------------------------------------------- partial tiles, lanes outside a region
+
+TINY_W, TINY_H, TINY_REGION = 10, 6, (3, 2, 5, 3)
+
+
+@pytest.fixture(scope="module")
+def tiny_host(scenes, harness):  # noqa: F811
+    """rtcamp6_v3_1 at 10 x 6 on the host form: (pixels all four of whose sub-samples hit, those whose K = 8 chain ends at its first hit)."""
+    hc = gc.HostChain(harness, scenes("rtcamp6_v3_1")[0].desc_ptr)
+    full = hc.primary(TINY_W, TINY_H)[1][..., 7] == 1.0
+    ends = full & (hc.chain(TINY_W, TINY_H, 8)[1][..., 0] == 1).all(-1)
+    hc.close()
+    return full, ends
+
+
+@pytest.mark.parametrize("qn", [1, 0])
+def test_partial_tiles_and_lanes_outside_a_region(ha, scenes, tiny_host, qn):
+    """A 10 x 6 frame is 3 x 2 tiles, every one of the right column and the bottom row partial; the region (3, 2, 5, 3) starts and ends inside
+    tiles.  Where all four sub-samples hit (coverage 1.0: at least half of the region's pixels, the host form says 0.8), the debug renderer's Normal
+    mode into a cleared accumulator x 0.25f IS guide planes 3 - 5 — the same hits, summed by the same two exchanges — and with guide_bounces = 8
+    the pixels whose chain ends at the first hit keep those bits.  A region has planes of its own: they are the whole frame's crop, bit for bit."""
+    sc = scenes("rtcamp6_v3_1")[0]
+    host_full, host_ends = tiny_host
+    x0, y0, w, h = TINY_REGION
+    whole = {}
+    for region in (None, TINY_REGION):
+        crop = (lambda a: a) if region is None else (lambda a: np.ascontiguousarray(a[y0:y0 + h, x0:x0 + w]))
+        r = _renderer(ha, sc, 0, qn=qn, region=region, w=TINY_W, h=TINY_H)
+        r.clear()
+        r.render_debug(1)
+        normal = r.read_accumulator() * np.float32(0.25)
+        r.render_guides()
+        g0 = r.read_guides()
+        r.set_option("guide_bounces", 8)
+        r.render_guides()
+        g8 = r.read_guides()
+        r.close()
+        full = g0[..., 7] == 1.0
+        assert full.mean() >= 0.5 and np.array_equal(full, crop(host_full)), region
+        assert _same(normal[full], g0[full][:, 3:6]), region
+        ends = full & crop(host_ends)
+        assert ends.sum() >= 4 and _same(g8[ends], g0[ends]), region
+        if region is None:
+            whole = dict(normal=normal, g0=g0, g8=g8)
+        else:
+            for name, a in (("normal", normal), ("g0", g0), ("g8", g8)):
+                assert _same(a, crop(whole[name])), name
+
+
 # ---------------------------------------------------------------------------------------------------------------- the CLI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

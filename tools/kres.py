@@ -16,7 +16,7 @@ def parse(f):
             out[cur] = {}
             continue
         for k, short in keys.items():
-            m = re.search(r"remark:\s+" + re.escape(k) + r": (\d+)", l)
+            m = re.search(r"remark:(?:\s+\S+:\d+:\d+:)?\s+" + re.escape(k) + r": (\d+)", l)   # (the location before or behind "remark:")
             if m and cur:
                 out[cur][short] = int(m.group(1))
     return out
