@@ -329,6 +329,25 @@ static const uint32_t REC_ITEM_FLOATS = 64u * REC_FLOATS;   // one item = 8 KiB
 // seed_seg_kernel: the init sweep of 32 blocks as three runs of SEG_NBLK blocks starting at blocks 0, SEG_B1, SEG_B2 (the last two
 // overlap by one block, which both write with the same values: every run has the same length, no lane is masked)
 static const int SEG_B1 = 11, SEG_B2 = 21, SEG_NBLK = 11;
+// seed_seg_kernel's pre-run form (debug option seed_prerun, seed_kernels.h): every lane of a half's two waves has a run, none overlap.
+// The 40 generators of a half come in two classes.  Columns < SEGP_XCOLS: two producer runs of SEGP_PNBLK blocks (from blocks 0 and 12,
+// their first SEGP_PRE blocks computed BEFORE the window and kept in registers) and one consumer run of SEGP_NBLK blocks (from block 24);
+// the other columns: four consumer runs of SEGP_NBLK blocks (from 0, 8, 16, 24).  A slot is wave * 64 + lane of the half's window
+// (wave 0 = its producer wave, 1 = its consumer wave): 64 + 64 runs, one per lane, 32 * 32 + 8 * 32 blocks in all.
+static const int SEGP_NBLK = 8, SEGP_PNBLK = 12, SEGP_PRE = 4, SEGP_XCOLS = 32, SEGP_AHEAD_END = 24;
+// (the ahead pass hands out states at blocks 0, 8, 12, 16 and 24, each only in the lanes whose class has a run there)
+HD bool segp_wants(uint32_t col, int block) {     // does generator `col` have a run that starts at `block`?
+    return block == 0 || block == 24 || (col < (uint32_t)SEGP_XCOLS ? block == 12 : block == 8 || block == 16);
+}
+HD uint32_t segp_slot(uint32_t col, int block) {  // the slot whose run starts there (segp_wants(col, block))
+    if (col < (uint32_t)SEGP_XCOLS) return block == 0 ? col : block == 12 ? 32u + col : 64u + col;
+    return 96u + (uint32_t)(block >> 3) * 8u + (col - (uint32_t)SEGP_XCOLS);
+}
+HD void segp_run(uint32_t slot, uint32_t &col, uint32_t &first, uint32_t &nblk) {   // the inverse: column, first block and length of a slot's run
+    if (slot < 64u) { col = slot & 31u; first = (slot >> 5) * (uint32_t)SEGP_PNBLK; nblk = (uint32_t)SEGP_PNBLK; }
+    else if (slot < 96u) { col = slot - 64u; first = 24u; nblk = (uint32_t)SEGP_NBLK; }
+    else { col = (uint32_t)SEGP_XCOLS + ((slot - 96u) & 7u); first = ((slot - 96u) >> 3) * (uint32_t)SEGP_NBLK; nblk = (uint32_t)SEGP_NBLK; }
+}
 HD uint32_t rec_slot(uint32_t lane_base, uint32_t slot) { return lane_base + (slot >> 2) * 256u + (slot & 3u); }
 
 struct Counters {

@@ -178,7 +178,8 @@ struct hr_ctx {
     double bvh_build_ms = 0;                 // device builder: key + sort + hierarchy + fit + emit + gather kernels
     uint64_t max_tail_bytes = 20ull << 30;   // cap of each hand-off buffer
     int seed_mode = 2;                       // 2 = three-run seed kernel (default), 1 = producer / consumer kernel with the state ring, 0 = fused seed kernel
-    int seed_prof = 0;                       // phase timing build of the seed kernel (three-run kernel; ring kernel: splits 16 and 20)
+    int seed_prof = 0;                       // phase timing build of the seed kernel (three-run kernel: 1 = consumer waves, 2 = producer waves; ring kernel: splits 16 and 20)
+    int seed_prerun = 1;                     // three-run seed kernel: 1 = the pre-run form of its window (seed_kernels.h), 0 = three equal runs
     uint32_t seed_prio = 3;                  // s_setprio of the seed / round kernel's waves
     uint32_t nee_cull = 7;                   // debug option nee_cull: mask of nee_setup's shortcuts in force (1 far side | 2 GGX below the horizon; bit 2 reserved); 0 = trace every NEE shadow ray (bit-identical image, more rays)
     uint32_t rr_start = 0;                   // Russian roulette from this path iteration on (0 = off: the reference has none; NOT image-preserving)
@@ -1107,7 +1108,7 @@ static int launch_seed(hr_ctx *c, const RenderParams &rp, int slot, hipStream_t 
     const bool list = rp.tile_list != nullptr;
     uint64_t paths = (uint64_t)(list ? rp.tile_count : rp.tiles_x * rp.tiles_y) * rp.num_k * 64u;
     uint32_t grid = (uint32_t)std::min<uint64_t>((paths + SEED_COLS - 1) / SEED_COLS, (uint64_t)c->num_cus);
-    const SeedVariant *v = select_seed_kernel(c->seed_mode, c->seed_split, c->seed_prof, rp.rec_lo_off != 0, list);
+    const SeedVariant *v = select_seed_kernel(c->seed_mode, c->seed_split, c->seed_prof, rp.rec_lo_off != 0, list, c->seed_prerun != 0);
     if (!v) return fail(HR_ERR_UNSUPPORTED, "no seed kernel instantiation for seed_mode %d, seed_split %d, seed_prof %d%s (kernel_variants.h)", c->seed_mode, c->seed_split, c->seed_prof, list ? " under a tile mask" : "");
     const bool skip = (c->debug_skip & 2) != 0;
     if (!skip && v->ring && !c->ring) HIP_TRY(hipMalloc((void **)&c->ring, (size_t)c->num_cus * SEED_RING_WORDS_MAX * sizeof(u64)));
@@ -1992,6 +1993,7 @@ static const OptionRow DEBUG_OPTIONS[] = {
     {"init_prio", &hr_ctx::init_prio, 0, 3, 0, "init_prio must be in [0,3]", 0},
     {"seed_split", &hr_ctx::seed_split, 8, 28, 4, "seed_split must be 8, 12, 16, 20, 24 or 28", 0},
     {"seed_prof", &hr_ctx::seed_prof, 1, 0, 0, "", 0},
+    {"seed_prerun", &hr_ctx::seed_prerun, 0, 1, 1, "seed_prerun must be 1 (pre-run window of the three-run seed kernel) or 0 (its three equal runs)", OPT_SYNC},
     {"ploc_top", &hr_ctx::ploc_top, 1, 1 << 16, 0, "ploc_top must be in [1,65536]", 0},
     {"trace_mode", &hr_ctx::trace_mode_opt, -1, 1, 1, "trace_mode must be -1 (automatic), 0 (megakernel) or 1 (split: traversal kernel + shading kernel)", OPT_SYNC | OPT_GOVERN},
     {"draw_residuals", &hr_ctx::draw_residuals, 0, 1, 1, "draw_residuals must be 0 or 1", 0},

@@ -123,7 +123,8 @@ static TraceDebugFn select_trace_debug_kernel(bool counters, bool qn) {
 // key: mode = option seed_mode; split = init blocks of the producer waves (seed_pc_kernel only, else 0); prof = the phase-timing build (a
 // number for seed_ps_kernel, else 0 / 1); lo = the launch writes the draws' residuals into the records' twin (seed_seg_kernel only);
 // list = a tile mask is in force (adapt_core.h; the last member: seed_seg_kernel without its timing build only).
-struct SeedVariant { int mode, split, prof; bool lo; const void *fn; uint32_t threads; bool ring; bool list = false; };
+// pre = the pre-run form of seed_seg_kernel's window (debug option seed_prerun, the default; false everywhere else).
+struct SeedVariant { int mode, split, prof; bool lo; const void *fn; uint32_t threads; bool ring; bool list = false; bool pre = false; };
 static const SeedVariant SEED_VARIANTS[] = {
     {0, 0, 0, false, (const void *)seed_isaac64_kernel, 64 * SEED_WAVES, false},
     {1, 8, 0, false, (const void *)seed_pc_kernel<8>, 256, true},
@@ -140,6 +141,15 @@ static const SeedVariant SEED_VARIANTS[] = {
     {2, 0, 1, true, (const void *)seed_seg_kernel<true, true>, 256, true},
     {2, 0, 0, false, (const void *)seed_seg_kernel<false, false, true>, 256, true, true},
     {2, 0, 0, true, (const void *)seed_seg_kernel<false, true, true>, 256, true, true},
+    {2, 0, 2, false, (const void *)seed_seg_kernel<2, false>, 256, true},                           // seed_prof 2: the producer waves' timing
+    // the same rows in the pre-run form
+    {2, 0, 0, false, (const void *)seed_seg_kernel<false, false, false, true>, 256, true, false, true},
+    {2, 0, 1, false, (const void *)seed_seg_kernel<true, false, false, true>, 256, true, false, true},
+    {2, 0, 0, true, (const void *)seed_seg_kernel<false, true, false, true>, 256, true, false, true},
+    {2, 0, 1, true, (const void *)seed_seg_kernel<true, true, false, true>, 256, true, false, true},
+    {2, 0, 0, false, (const void *)seed_seg_kernel<false, false, true, true>, 256, true, true, true},
+    {2, 0, 0, true, (const void *)seed_seg_kernel<false, true, true, true>, 256, true, true, true},
+    {2, 0, 2, false, (const void *)seed_seg_kernel<2, false, false, true>, 256, true, false, true},
 #if defined(HR_EXPERIMENTS)
     {3, 0, 0, false, (const void *)seed_ps_kernel<0>, 256, true},
     {3, 0, 1, false, (const void *)seed_ps_kernel<1>, 256, true},
@@ -155,14 +165,15 @@ static const SeedVariant SEED_VARIANTS[] = {
 //   * seed_ps_kernel (mode 3) has timing builds 1 .. 3, any other seed_prof is its plain build; everywhere else seed_prof is on / off
 //   * the fused kernel (mode 0) has no timing build
 //   * list (a tile mask is in force): the three-run kernel (mode 2) without phase timing, nothing else
-static const SeedVariant *select_seed_kernel(int seed_mode, int seed_split, int seed_prof, bool twin, bool list = false) {
+//   * the three-run kernel (mode 2) alone has the pre-run form (seed_prerun) and a timing build of its producer waves (seed_prof 2, without the twin)
+static const SeedVariant *select_seed_kernel(int seed_mode, int seed_split, int seed_prof, bool twin, bool list = false, bool prerun = false) {
     int split = 0, prof = seed_prof ? 1 : 0;
-    bool lo = false;
-    if (seed_mode == 2) lo = twin;
+    bool lo = false, pre = false;
+    if (seed_mode == 2) { lo = twin; pre = prerun; if (seed_prof == 2) prof = 2; }
     else if (seed_mode == 1) split = prof ? (seed_split == 20 ? 20 : 16) : seed_split;
     else if (seed_mode == 3) prof = seed_prof >= 1 && seed_prof <= 3 ? seed_prof : 0;
     else if (seed_mode == 0) prof = 0;
-    return find_row(SEED_VARIANTS, [&](const SeedVariant &r) { return r.mode == seed_mode && r.split == split && r.prof == prof && r.lo == lo && r.list == list; });
+    return find_row(SEED_VARIANTS, [&](const SeedVariant &r) { return r.mode == seed_mode && r.split == split && r.prof == prof && r.lo == lo && r.list == list && r.pre == pre; });
 }
 
 // ---- accumulate_kernel<MOM, CNTS, LIST> (trace_kernel.h): a launch's radiance into the accumulator ----

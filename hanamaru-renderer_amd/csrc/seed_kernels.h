@@ -478,19 +478,100 @@ struct SegRegs {
         if (l.on) isaac_init_run<SEG_NBLK>(m, st16);
     }
 };
-template <bool PROF, bool LO, bool LIST>
+// ---- the pre-run form of the window (the default; debug option seed_prerun = 0: the three equal runs above) ------------------------------
+// The three-run window leaves two things idle: 8 of a half's 128 lanes (and a block computed twice), and the producer waves, which finish
+// their ahead pass well before barrier A and need about half of the registers the kernel is allocated for the consumer's round.  Here
+// every lane of both waves has a run and no block is computed twice (device_scene.h SEGP_*: columns 0-31 are cut 12 + 12 + 8, columns
+// 32-39 are cut 8 + 8 + 8 + 8; the 12-block runs belong to the producer lanes), and a producer lane computes the first SEGP_PRE blocks of
+// its next run right after its ahead pass, BEFORE barrier A, into registers (SEGP_PRE x 16 VGPRs): in the window it writes those out and
+// continues.  The window is 8 blocks long on both waves instead of 11.  Still no generator word travels through memory; the ring holds 128
+// entry states per half and group (16 KiB) instead of 120, as [wave][8 pairs][64 lanes][2] u64: a lane's eight 16-byte loads are coalesced.
+struct SegpLayout {
+    static const size_t WAVE_WORDS = (size_t)16 * 64;        // the entry states of one wave's 64 lanes: [8 pairs][64 lanes][2] u64
+    static const size_t HALF_WORDS = 2 * WAVE_WORDS;         // slots 0-63: the producer wave's, 64-127: the consumer wave's
+    static const size_t GROUP_WORDS = 2 * HALF_WORDS;
+};
+static_assert(SEED_RING_GROUPS * SegpLayout::GROUP_WORDS <= SEED_RING_WORDS_MAX, "the ring allocation of the producer / consumer kernel holds it");
+static_assert(2 * SEGP_XCOLS == 64 && SEGP_XCOLS + 4 * (SEED_LANES - SEGP_XCOLS) == 64, "64 producer runs and 64 consumer runs per half");
+static_assert(SEGP_PNBLK == SEGP_PRE + SEGP_NBLK && 2 * SEGP_PNBLK + SEGP_NBLK == 32 && 4 * SEGP_NBLK == 32 && SEGP_AHEAD_END == 32 - SEGP_NBLK, "the runs tile the sweep");
+struct SegpStateOut {
+    u64 *half;      // the states of the path's group and half
+    uint32_t col;   // its column there
+    __device__ __forceinline__ bool wants(int block) const { return segp_wants(col, block); }
+    __device__ __forceinline__ void state(int block, u64 a, u64 b, u64 c, u64 d, u64 e, u64 f, u64 g, u64 h, u64 A, u64 B, u64 C, u64 D, u64 E, u64 F, u64 G, u64 H) {
+        typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+        const uint32_t s = segp_slot(col, block);
+        u64x2 *dst = reinterpret_cast<u64x2 *>(half + (size_t)(s >> 6) * SegpLayout::WAVE_WORDS + (size_t)(s & 63u) * 2u);
+        const u64x2 q[8] = {{a, b}, {c, d}, {e, f}, {g, h}, {A, B}, {C, D}, {E, F}, {G, H}};
+#pragma unroll
+        for (int j = 0; j < 8; j++) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst + j * 64), "v"(q[j]) : "memory");   // (see SegStateOut)
+    }
+};
+struct SegpLane {
+    uint32_t slot, col, first;   // the run of this lane: segp_run(slot)
+};
+__device__ __forceinline__ SegpLane segp_lane(bool consumer, uint32_t lane) {
+    SegpLane l;
+    uint32_t nblk;
+    l.slot = (consumer ? 64u : 0u) + lane;
+    segp_run(l.slot, l.col, l.first, nblk);
+    return l;
+}
+struct SegpRegs {
+    typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
+    u64x2_t v[8];
+    __device__ __forceinline__ void load(const u64 *ring_wg, uint64_t g, uint32_t half, const SegpLane &l) {
+        const u64 *regs = ring_wg + (g & (SEED_RING_GROUPS - 1)) * SegpLayout::GROUP_WORDS + half * SegpLayout::HALF_WORDS + (size_t)(l.slot >> 6) * SegpLayout::WAVE_WORDS + (size_t)(l.slot & 63u) * 2u;
+#pragma unroll
+        for (int q = 0; q < 8; q++) v[q] = __builtin_nontemporal_load(reinterpret_cast<const u64x2_t *>(regs + q * 128));
+    }
+    // a consumer lane's window: its run of SEGP_NBLK blocks
+    __device__ __forceinline__ void run(unsigned char *lds_half, const SegpLane &l) const {
+        u64 st16[16];
+#pragma unroll
+        for (int q = 0; q < 8; q++) { st16[2 * q] = v[q].x; st16[2 * q + 1] = v[q].y; }
+        LdsHalfMem m{reinterpret_cast<u64 *>(lds_half) + l.col + (size_t)l.first * 8u * SEED_LANES};
+        isaac_init_run<SEGP_NBLK>(m, st16);
+    }
+    // a producer lane, before the window: the first SEGP_PRE blocks of its run, kept in registers; v moves on to the state behind them
+    __device__ __forceinline__ void prerun(u64 (*kept)[8]) {
+        u64 st16[16];
+#pragma unroll
+        for (int q = 0; q < 8; q++) { st16[2 * q] = v[q].x; st16[2 * q + 1] = v[q].y; }
+        isaac_init_prerun<SEGP_PRE>(st16, kept);
+#pragma unroll
+        for (int q = 0; q < 8; q++) { v[q].x = st16[2 * q]; v[q].y = st16[2 * q + 1]; }
+    }
+    // a producer lane's window: the kept blocks go out, the run continues for SEGP_NBLK blocks
+    __device__ __forceinline__ void finish(unsigned char *lds_half, const SegpLane &l, const u64 (*kept)[8]) const {
+        LdsHalfMem k{reinterpret_cast<u64 *>(lds_half) + l.col + (size_t)l.first * 8u * SEED_LANES};
+#pragma unroll
+        for (int p = 0; p < SEGP_PRE; p++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) k.st(p * 8 + j, kept[p][j]);
+        u64 st16[16];
+#pragma unroll
+        for (int q = 0; q < 8; q++) { st16[2 * q] = v[q].x; st16[2 * q + 1] = v[q].y; }
+        LdsHalfMem m{k.col + (size_t)SEGP_PRE * 8u * SEED_LANES};
+        isaac_init_run<SEGP_NBLK>(m, st16);
+    }
+};
+template <bool PRE> struct SegForm { typedef SegLane Lane; typedef SegRegs Regs; static __device__ __forceinline__ Lane lane(bool consumer, uint32_t l) { return seg_lane(consumer, l); } };
+template <> struct SegForm<true> { typedef SegpLane Lane; typedef SegpRegs Regs; static __device__ __forceinline__ Lane lane(bool consumer, uint32_t l) { return segp_lane(consumer, l); } };
+template <bool PROF, bool LO, bool LIST, bool PRE>
 __device__ __forceinline__ void seed_seg_consumer(const RenderParams &rp, int lens_shape, const PcRange &r, unsigned char *smem, uint32_t lane, uint32_t half,
                                                   float *__restrict__ recs, uint32_t *__restrict__ ovf, u64 *__restrict__ win, Counters *cnt) {
     uint32_t *ovf_list = ovf + (size_t)(blockIdx.x * 2u + half) * rp.ovf_cap;
     uint32_t ovf_count = 0;
     unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tm = 0;
 #define HR_STAMP(i) do { if (PROF) { unsigned long long now_ = __builtin_readcyclecounter(); pc[i] += now_ - tm; tm = now_; } } while (0)
-    const SegLane sl = seg_lane(true, lane);
-    SegRegs regs;
+    const typename SegForm<PRE>::Lane sl = SegForm<PRE>::lane(true, lane);
+    typename SegForm<PRE>::Regs regs;
     const uint32_t colr = lane < (uint32_t)SEED_LANES ? lane : 0u;
     unsigned char *lds_half = smem + (size_t)half * SEED_LDS_HALF_BYTES;
     LdsHalfMem m{reinterpret_cast<u64 *>(lds_half) + colr};
     const uint64_t n_groups = r.G1 - r.G0;
+    if (PRE) __syncthreads();   // the pre-run form: the producers pre-run their first window between this barrier and the next
     __syncthreads();   // A of iteration 0: the states of groups G0 and G0 + 1 are in the ring
     for (uint64_t it = 1; it <= n_groups; it++) {
         if (PROF) tm = __builtin_readcyclecounter();
@@ -529,11 +610,20 @@ __device__ __forceinline__ void seed_seg_consumer(const RenderParams &rp, int le
     const bool lane_on = lane < (uint32_t)SEED_LANES;
     seed_fixup_wave<LdsHalfMem, LO, LIST>(rp, lens_shape, m, colr, lane_on, ovf_list, ovf_count, win + (size_t)(blockIdx.x * 2u + half) * SEED_WIN_WORDS, recs, cnt);
 }
-template <bool LIST>
-__device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const PcRange &r, unsigned char *smem, uint32_t lane, uint32_t half, const uint32_t pprio) {
+// PROF (option seed_prof = 2): the producer wave's side of a group, summed per wave into Counters::seed_phase
+//   0 window   1 barrier B   2 register loads + ahead pass (+ pre-run)   3 barrier A in groups with a chunk of the ahead pass   4 barrier A in groups without
+//   5 groups with a chunk   6 of those, groups whose wait at barrier A was shorter than SEGP_PRE uncontended init blocks (SEG_PROF_FIT cycles)   7 groups
+static const uint32_t SEG_PROF_FIT = 563u * SEGP_PRE;
+template <bool LIST, bool PRE, bool PROF>
+__device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const PcRange &r, unsigned char *smem, uint32_t lane, uint32_t half, const uint32_t pprio, Counters *cnt) {
     const IsaacWarm warm = isaac_warm();
-    const SegLane sl = seg_lane(false, lane);
-    SegRegs regs;
+    const typename SegForm<PRE>::Lane sl = SegForm<PRE>::lane(false, lane);
+    typename SegForm<PRE>::Regs regs;
+    u64 kept[PRE ? SEGP_PRE : 1][8];   // the pre-run form: the first blocks of the next window's run
+    // (32-bit sums, pinned to scalar registers: a wave's launch is ~6e7 cycles, and as vector registers the eight sums took the kernel past 128)
+    uint32_t pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tm = 0, chunks = 0;
+#define HR_NOW() __builtin_amdgcn_readfirstlane((uint32_t)__builtin_readcyclecounter())
+#define HR_STAMP(i) do { if (PROF) { const uint32_t now_ = HR_NOW(); pc[i] = __builtin_amdgcn_readfirstlane(pc[i] + (now_ - tm)); tm = now_; } } while (0)
     unsigned char *lds_half = smem + (size_t)half * SEED_LDS_HALF_BYTES;
     const uint64_t n_groups = r.G1 - r.G0;
     uint64_t frontier = r.first_path & ~63ull;               // first path whose states are not in the ring yet (chunks of 64 paths)
@@ -555,18 +645,36 @@ __device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const 
             path_seed_words(rp.width, rp.height, pvalid ? px : 0u, pvalid ? py : 0u, sub, s, t);
             const uint64_t g = ppid / SEED_COLS;
             const uint32_t c80 = (uint32_t)(ppid - g * SEED_COLS), hh = c80 >= (uint32_t)SEED_LANES ? 1u : 0u;
-            SegStateOut out{r.ring_wg + (g & (SEED_RING_GROUPS - 1)) * SegLayout::GROUP_WORDS + hh * SegLayout::HALF_WORDS + (size_t)(c80 - hh * (uint32_t)SEED_LANES) * 2u};
-            if (on) isaac_init_ahead<SEG_B1, SEG_B2>(out, warm, 8700304ULL, (u64)(rp.sampling_begin + k * rp.stride), s, t);
+            if constexpr (PRE) {
+                SegpStateOut out{r.ring_wg + (g & (SEED_RING_GROUPS - 1)) * SegpLayout::GROUP_WORDS + hh * SegpLayout::HALF_WORDS, c80 - hh * (uint32_t)SEED_LANES};
+                if (on) isaac_init_ahead_pre(out, warm, 8700304ULL, (u64)(rp.sampling_begin + k * rp.stride), s, t);
+            } else {
+                SegStateOut out{r.ring_wg + (g & (SEED_RING_GROUPS - 1)) * SegLayout::GROUP_WORDS + hh * SegLayout::HALF_WORDS + (size_t)(c80 - hh * (uint32_t)SEED_LANES) * 2u};
+                if (on) isaac_init_ahead<SEG_B1, SEG_B2>(out, warm, 8700304ULL, (u64)(rp.sampling_begin + k * rp.stride), s, t);
+            }
+            if (PROF) chunks = __builtin_amdgcn_readfirstlane(chunks + 1u);
         }
         __builtin_amdgcn_s_waitcnt(0);   // the state stores are hand-written: the compiler does not wait for them at the barrier by itself
     };
     // iteration 0: the states of groups G0 and G0 + 1 (one group of slack, as in the producer / consumer kernel)
     ahead(r.G0 + 2);
-    __syncthreads();   // A
-    if (n_groups >= 1) regs.load(r.ring_wg, r.G0, half, sl);
+    if constexpr (PRE) {
+        // the first window has no earlier slack: its pre-run goes between two barriers of its own (the other producer wave's states must be in)
+        __syncthreads();
+        regs.load(r.ring_wg, r.G0, half, sl);   // (a workgroup has at least one group: the grid is at most the number of groups)
+        regs.prerun(kept);
+        __syncthreads();   // A
+    } else {
+        __syncthreads();   // A
+        if (n_groups >= 1) regs.load(r.ring_wg, r.G0, half, sl);
+    }
     for (uint64_t it = 1; it <= n_groups; it++) {
-        regs.run(lds_half, sl);          // the window
+        if (PROF) { tm = HR_NOW(); chunks = 0; }
+        if constexpr (PRE) regs.finish(lds_half, sl, kept);   // the window: the pre-run blocks go out, the run continues
+        else regs.run(lds_half, sl);                          // the window
+        HR_STAMP(0);
         __syncthreads();   // B
+        HR_STAMP(1);
         if (it < n_groups) regs.load(r.ring_wg, r.G0 + it, half, sl);   // for the next window; complete in the ring since the last barrier A
         // the ahead pass's priority may alternate between groups (pprio bits 2-3: the priority of the odd groups): the priority
         // governor balances the two kernels with it, and the balance point usually lies between two whole levels
@@ -575,13 +683,32 @@ __device__ __forceinline__ void seed_seg_producer(const RenderParams &rp, const 
             if (pr == 0u) __builtin_amdgcn_s_setprio(0); else if (pr == 1u) __builtin_amdgcn_s_setprio(1); else if (pr == 2u) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3);
         }
         ahead(r.G0 + it + 2);
+        // in the time this wave would otherwise wait at barrier A.  (Unconditional: behind the last group it works on the state the last
+        // window left, for nothing — a branch here would make the compiler keep two sets of the kept blocks' 64 registers.)
+        if constexpr (PRE) regs.prerun(kept);
+        HR_STAMP(2);
         __syncthreads();   // A
+        if (PROF) {
+            const uint32_t now_ = HR_NOW(), wait = now_ - tm;
+            tm = now_;
+            const bool busy = chunks != 0;
+            pc[3] = __builtin_amdgcn_readfirstlane(pc[3] + (busy ? wait : 0u));
+            pc[4] = __builtin_amdgcn_readfirstlane(pc[4] + (busy ? 0u : wait));
+            pc[5] = __builtin_amdgcn_readfirstlane(pc[5] + (busy ? 1u : 0u));
+            pc[6] = __builtin_amdgcn_readfirstlane(pc[6] + (busy && wait < SEG_PROF_FIT ? 1u : 0u));
+            pc[7] = __builtin_amdgcn_readfirstlane(pc[7] + 1u);
+        }
     }
+#undef HR_STAMP
+#undef HR_NOW
+    if (PROF && lane == 0)
+        for (int i = 0; i < 8; i++) atomicAdd(&cnt->seed_phase[i], (unsigned long long)pc[i]);
 }
 // LO: the records' twin with the draws' residuals is written too (precise shading, RenderParams::rec_lo_off)
 // LIST: a tile mask is in force (adapt_core.h) — the launch's paths are those of the active tiles (pid = (dense tile * num_k + k) * 64 + j, as ever);
 // a lane's pixel, i.e. its seed, comes from the region's tile behind the dense index, one lookup where tile_lane_frame_pixel is fed
-template <bool PROF = false, bool LO = false, bool LIST = false>
+// PRE: the pre-run form of the window (above); PROF: 1 = the consumer waves' phase timing, 2 = the producer waves'
+template <int PROF = 0, bool LO = false, bool LIST = false, bool PRE = false>
 __global__ __launch_bounds__(256) void seed_seg_kernel(RenderParams rp, int lens_shape, u64 *__restrict__ ring, float *__restrict__ recs,
                                                        uint32_t *__restrict__ ovf, u64 *__restrict__ win, Counters *cnt) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -601,9 +728,9 @@ __global__ __launch_bounds__(256) void seed_seg_kernel(RenderParams rp, int lens
     r.G0 = groups * blockIdx.x / gridDim.x; r.G1 = groups * (blockIdx.x + 1) / gridDim.x;
     r.first_path = r.G0 * SEED_COLS; r.end_path = r.G1 * SEED_COLS < r.paths ? r.G1 * SEED_COLS : r.paths;
     r.ring_wg = ring + (size_t)blockIdx.x * SEED_RING_WORDS_MAX;
-    if (consumer) seed_seg_consumer<PROF, LO, LIST>(rp, lens_shape, r, smem, lane, half, recs, ovf, win, cnt);
+    if (consumer) seed_seg_consumer<PROF == 1, LO, LIST, PRE>(rp, lens_shape, r, smem, lane, half, recs, ovf, win, cnt);
     else {
-        seed_seg_producer<LIST>(rp, r, smem, lane, half, pprio);
+        seed_seg_producer<LIST, PRE, PROF == 2>(rp, r, smem, lane, half, pprio, cnt);
         seed_gov_end(rp, wave == 2u && lane == 0u);
     }
 }

@@ -19,8 +19,11 @@ extern "C" {
  * "seed_mode" (2 = three-run seed kernel, default; 3 = its phase-shifted four-run form and 4 = its five-wave four-run form, both
  * slower, kept as measured experiments; 1 = producer / consumer kernel with a
  * ring of generator words; 0 = fused),
+ * "seed_prerun" (seed_mode 2 only: 1 = the pre-run form of its window, default — all 128 lanes of a half's two waves have a run of the init
+ * sweep and the producer lanes compute the first blocks of theirs ahead of the window, in registers; 0 = the three equal runs; same draws, bit for bit),
  * "seed_split" (seed_mode 1), "seed_prio" / "init_prio" (s_setprio of the seed kernel's consumer / producer waves), "seed_prof"
- * (phase timing build of the seed kernel -> hr_stats.seed_phase_cycles; seed_mode 3: 1 | 2 | 3 = consumer 0, consumer 1, producer 0), "ploc_top" (bvh_builder 2: clusters the bottom-up merges
+ * (phase timing build of the seed kernel -> hr_stats.seed_phase_cycles; seed_mode 2: 1 = the consumer waves' phases, 2 = the producer waves' — window,
+ * barrier B, ahead pass, barrier A in groups with / without a chunk of the ahead pass, see seed_kernels.h; seed_mode 3: 1 | 2 | 3 = consumer 0, consumer 1, producer 0), "ploc_top" (bvh_builder 2: clusters the bottom-up merges
  * leave for the top-down build over them; 1 = merge to the root; takes effect at the next hr_upload_scene), "debug_skip" (bit mask that drops parts of the pipeline
  * for timing experiments: THE IMAGE IS GARBAGE), "nee_cull" (mask of pt_core.h nee_setup's shortcuts in force: 1 = far side of the emitter, 2 = GGX below the
  * horizon; bit 2 is reserved — a third shortcut was measured and dropped, DESIGN.md §4.2 —; default 7; 0 = trace every NEE shadow ray — the bit-identical A/B of the shortcuts). */
