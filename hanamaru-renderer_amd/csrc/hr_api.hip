@@ -9,11 +9,12 @@
 //                    and debug_render_kernel (renderer.rs:101-146)
 //   wf_kernels.h     the split pipeline (option trace_mode 1): wf_start_kernel, wf_traverse_kernel (the same traversal at <= 64 VGPRs),
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
-//   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h)
+//   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
+//                    robust_kernel (robust_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
-// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image) are rows of one
+// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane) are rows of one
 // table, PLANES, with one set of routines for their bytes, life cycle, zeroing and host copies; scratch a call needs lives in a CallScratch.
 #include <hip/hip_runtime.h>
 
@@ -124,6 +125,16 @@ struct hr_ctx {
     float *guides = nullptr, *denoised = nullptr;
     bool guides_valid = false, denoised_valid = false;
     uint32_t guide_bounces = 0;   // option "guide_bounces": mirrors and glass the guide rays follow to the first non-delta hit (0: the first hit's planes)
+    // option "robust_buckets" = K: per pixel K x 3 sums of the per-sampling values, sampling j of a pixel in bucket j mod K
+    // (bucket_kernel), the samplings behind them, and the robust radiance R with its trim plane of the last hr_robust, valid until anything it was
+    // made of changes (invalidate_robust)
+    bool robust_on = false;
+    uint32_t robust_k = 0;
+    double *buckets = nullptr;
+    uint64_t buckets_n = 0;
+    float *robust = nullptr;
+    uint8_t *robust_trim = nullptr;
+    bool robust_valid = false;
     // the tile mask (hr_set_tile_mask / hr_select_tiles): which 4x4 tiles of the region hr_render covers.  On the device the compacted list of the
     // active tiles' indices, ascending (RenderParams::tile_list), and the flags it was compacted from; on the host the same flags as bytes.
     bool mask_on = false;
@@ -346,6 +357,8 @@ static void invalidate_totals(hr_ctx *c) {
 }
 // the accumulator, the moments, the counts or the guides of `c` are about to change, or its target: the denoised image is no longer theirs
 static void invalidate_denoised(hr_ctx *c) { c->denoised_valid = false; }
+// the same for the robust radiance: the buckets or the counts of `c` are about to change, its accumulator or its target
+static void invalidate_robust(hr_ctx *c) { c->robust_valid = false; }
 static int drain_events(hr_ctx *c) {
     auto sum = [](std::vector<EventPair> &ev, double &acc) -> hipError_t {
         // a pair whose query fails is dropped with the rest (left in the list it would fail every later drain, i.e. every later API call)
@@ -445,9 +458,11 @@ static int free_mask_buffers(hr_ctx *c) {
 //   WITH_TARGET   allocated by set_target for every target
 //   WITH_OPTION   allocated while the option `on` is on: when it is switched on, and by set_target while it is on; gone when it is switched off
 //   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate; guides: the first
-//                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise), freed by set_target — noise_img also with the moments it
-//                 is made of, guides also by hr_upload_scene (they show the scene)
+//                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise; robust, robust_trim: the first hr_robust), freed by set_target —
+//                 noise_img also with the moments it is made of, guides also by hr_upload_scene (they show the scene), robust and robust_trim also
+//                 with the buckets they are made of
 // at_alloc: zeroed when allocated.  at_clear: zeroed by hr_clear.  n: the count that belongs to the plane's contents and is zeroed with them.
+// per: a plane whose components are `comps` times a number the context holds (the sample buckets: 3 per bucket, K buckets).
 enum PlaneLife { WITH_TARGET, WITH_OPTION, ON_FIRST_USE };
 struct Plane {
     void **(*slot)(hr_ctx *);
@@ -458,6 +473,7 @@ struct Plane {
     const char *option = nullptr;       // WITH_OPTION: the key of hr_set_option
     bool hr_ctx::*on = nullptr;
     uint64_t hr_ctx::*n = nullptr;
+    uint32_t hr_ctx::*per = nullptr;
 };
 #define PLANE_SLOT(member) [](hr_ctx *c) -> void ** { return (void **)&c->member; }
 static const Plane ACCUM_OWN{PLANE_SLOT(accum_own), sizeof(float), 3, WITH_TARGET, true, true};   // hr_clear zeroes c->accum: this plane, or the caller's bound buffer of its size
@@ -469,11 +485,14 @@ static const Plane NOISE_IMG{PLANE_SLOT(noise_img), sizeof(double), 1, ON_FIRST_
 static const Plane COUNTS{PLANE_SLOT(counts), sizeof(uint32_t), 1, WITH_OPTION, true, true, "sample_counts", &hr_ctx::counts_on};
 static const Plane GUIDES{PLANE_SLOT(guides), sizeof(float), 8, ON_FIRST_USE, false, false};
 static const Plane DENOISED{PLANE_SLOT(denoised), sizeof(float), 3, ON_FIRST_USE, false, false};
+static const Plane BUCKETS{PLANE_SLOT(buckets), sizeof(double), 3, WITH_OPTION, true, true, "robust_buckets", &hr_ctx::robust_on, &hr_ctx::buckets_n, &hr_ctx::robust_k};
+static const Plane ROBUST{PLANE_SLOT(robust), sizeof(float), 3, ON_FIRST_USE, false, false};
+static const Plane ROBUST_TRIM{PLANE_SLOT(robust_trim), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
 #undef PLANE_SLOT
-static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED};
+static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM};
 
 static size_t region_pixels(const hr_ctx *c) { return (size_t)c->RW * c->RH; }
-static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps; }
+static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps * (p.per ? c->*p.per : 1u); }
 static size_t plane_bytes(const hr_ctx *c, const Plane &p) { return plane_elems(c, p) * p.elem; }
 static int plane_free(hr_ctx *c, const Plane &p) {
     if (p.n) c->*p.n = 0;
@@ -509,6 +528,7 @@ static int plane_write(hr_ctx *c, const Plane &p, void *dev, const void *host) {
     if (rc) return rc;
     if (dev == c->accum) invalidate_totals(c);
     invalidate_denoised(c);   // every plane a host can write is one the denoised image is made of
+    if (dev != c->guides) invalidate_robust(c);   // (the guide planes are none of the robust radiance's inputs)
     HIP_TRY(hipMemcpy(dev, host, plane_bytes(c, p), hipMemcpyHostToDevice));
     return HR_OK;
 }
@@ -888,6 +908,7 @@ static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y
     c->accum = nullptr; c->W = c->H = 0; c->RX = c->RY = c->RW = c->RH = 0; c->total_valid = false;
     c->guides_valid = false;
     invalidate_denoised(c);
+    invalidate_robust(c);
     unbind_accumulator(c);
     for (const Plane *p : PLANES) if ((rc = plane_free(c, *p))) return rc;
     if ((rc = remove_mask(c))) return rc;   // the mask is over the old region's tiles
@@ -974,6 +995,7 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
     c->accum = device_rgb ? device_rgb : c->accum_own;
     invalidate_totals(c);
     invalidate_denoised(c);
+    invalidate_robust(c);
     return HR_OK;
 }
 void *hr_accumulator_device_ptr(hr_ctx *c) { return c ? c->accum : nullptr; }
@@ -995,6 +1017,7 @@ int hr_clear(hr_ctx *c) {
     if (rc) return rc;
     invalidate_totals(c);
     invalidate_denoised(c);
+    invalidate_robust(c);
     // the planes the table marks, the accumulator through c->accum (it may be the caller's bound buffer); the tile mask stays: a setting, like the region
     for (const Plane *p : PLANES)
         if (p->at_clear && (rc = plane_zero(c, *p, c->stream, p == &ACCUM_OWN ? c->accum : nullptr))) return rc;
@@ -1205,6 +1228,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
     invalidate_denoised(c);
+    invalidate_robust(c);
     if (c->precise_opt == 1 && c->rr_start) return fail(HR_ERR_UNSUPPORTED, "hr_render: russian_roulette and precise_shading exclude each other (the roulette estimator has no f64 instantiation)");
     const uint32_t total_k = (s_end - s_begin + stride - 1) / stride;
     const bool list = c->mask_on;
@@ -1215,6 +1239,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         if (what) return fail(HR_ERR_UNSUPPORTED, "hr_render: %s has no kernel form for a tile mask (hr_set_tile_mask(NULL) removes the mask)", what);
         if (!c->mask_active) {   // nothing is active: nothing to enqueue; the samplings count as issued (hr_noise.samplings), like those of any masked launch
             if (c->moments) c->moments_n += total_k;
+            if (c->buckets) c->buckets_n += total_k;
             return HR_OK;
         }
     }
@@ -1232,6 +1257,8 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     if (!trace) return fail(HR_ERR_UNSUPPORTED, "hr_render: no trace kernel instantiation for these options%s (kernel_variants.h)", list ? " under a tile mask" : "");
     const AccumulateFn accumulate = select_accumulate_kernel(c->moments != nullptr, c->counts != nullptr, list);
     if (!accumulate) return fail(HR_ERR_UNSUPPORTED, "hr_render: no accumulate kernel instantiation for these options (kernel_variants.h)");
+    const BucketFn bucket = c->buckets ? select_bucket_kernel(c->counts != nullptr, list) : nullptr;   // option robust_buckets off: nothing more is launched
+    if (c->buckets && !bucket) return fail(HR_ERR_UNSUPPORTED, "hr_render: no bucket kernel instantiation for these options (kernel_variants.h)");
     for (uint32_t done = 0; done < total_k; done += batch) {
         uint32_t nk = std::min(batch, total_k - done);
         rp.sampling_begin = s_begin + done * stride;
@@ -1262,6 +1289,11 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         // the launch's radiance into the accumulator (the trace kernel left every path's in its record), in the gap in which this
         // stream waits for the next seed kernel anyway
         if (!(c->debug_skip & 16)) {
+            if (bucket) {   // in front of accumulate_kernel: a pixel's ordinal under sample_counts is its count BEFORE this launch
+                hipLaunchKernelGGL(bucket, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->buckets, c->counts, c->robust_k, (unsigned long long)c->buckets_n);
+                HIP_TRY(hipGetLastError());
+                c->buckets_n += nk;
+            }
             hipLaunchKernelGGL(accumulate, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->accum, c->moments, c->counts);
             HIP_TRY(hipGetLastError());
             if (c->moments) c->moments_n += nk;
@@ -1307,6 +1339,7 @@ int hr_render_debug(hr_ctx *c, int mode) {
     if (c->moments_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option moments on (a debug sampling goes into the accumulator without per-sampling values)");
     if ((rc = debug_refusal(c, "hr_render_debug", NO_MASK))) return rc;
     if (c->counts_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option sample_counts on (a debug sampling goes into the accumulator without being counted)");
+    if (c->robust_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option robust_buckets on (a debug sampling goes into the accumulator without per-sampling values)");
     HIP_TRY(hipSetDevice(c->device));
     invalidate_totals(c);
     invalidate_denoised(c);
@@ -1821,6 +1854,58 @@ int hr_resolve_denoised(hr_ctx *c, uint8_t *host_rgb8) {
     return resolve_region(c, 0, host_rgb8, c->denoised);
 }
 
+// ---- option "robust_buckets": the sample buckets and the firefly-robust resolve made of them (robust_core.h) ----
+int hr_read_buckets(hr_ctx *c, double *host, uint64_t *samplings) {
+    int rc = option_plane_read(c, BUCKETS, "hr_read_buckets", host);
+    if (rc) return rc;
+    if (samplings) *samplings = c->buckets_n;
+    return HR_OK;
+}
+int hr_write_buckets(hr_ctx *c, const double *host, uint64_t samplings) {
+    int rc = option_plane_write(c, BUCKETS, "hr_write_buckets", host);
+    if (rc) return rc;
+    c->buckets_n = samplings;
+    return HR_OK;
+}
+int hr_robust(hr_ctx *c) {
+    static const char *const who = "hr_robust";
+    int rc = plane_ready(c, BUCKETS, who);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = hr_synchronize(c))) return rc;
+    if (!c->robust && (rc = plane_alloc(c, ROBUST))) return rc;
+    if (!c->robust_trim && (rc = plane_alloc(c, ROBUST_TRIM))) return rc;
+    invalidate_robust(c);
+    const uint32_t pixels = (uint32_t)region_pixels(c);
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    hipLaunchKernelGGL(robust_kernel, dim3((pixels + 255) / 256), dim3(256), 0, c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->robust_k, c->robust, c->robust_trim, pixels);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
+    c->robust_valid = true;
+    return drain_events(c);
+}
+// R of the last hr_robust, while nothing it was made of has changed (`who`: the entry point)
+static int robust_ready(hr_ctx *c, const char *who, const void *host) {
+    int rc = plane_ready(c, BUCKETS, who);
+    if (rc) return rc;
+    if (!host) return fail(HR_ERR_INVALID, "%s: null argument", who);
+    if (!c->robust || !c->robust_trim || !c->robust_valid) return fail(HR_ERR_INVALID, "%s: no robust image (hr_robust first; anything that changes its inputs invalidates it)", who);
+    return HR_OK;
+}
+int hr_read_robust(hr_ctx *c, float *host) {
+    int rc = robust_ready(c, "hr_read_robust", host);
+    return rc ? rc : plane_read(c, ROBUST, c->robust, host);
+}
+int hr_read_robust_trim(hr_ctx *c, uint8_t *host) {
+    int rc = robust_ready(c, "hr_read_robust_trim", host);
+    return rc ? rc : plane_read(c, ROBUST_TRIM, c->robust_trim, host);
+}
+int hr_resolve_robust(hr_ctx *c, uint8_t *host_rgb8) {
+    int rc = robust_ready(c, "hr_resolve_robust", host_rgb8);
+    return rc ? rc : resolve_region(c, 0, host_rgb8, c->robust);
+}
+
 // the mask's host side from its flags: the count of active tiles and of their in-region pixels
 static void mask_totals(hr_ctx *c) {
     const uint32_t tx = (c->RW + 3) / 4, ty = (c->RH + 3) / 4;
@@ -2023,7 +2108,7 @@ static int set_plane_option(hr_ctx *c, double value, const Plane &p, const Plane
     if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", p.option);
     int rc = sync_all(c);
     if (rc) return rc;
-    if (value == 0 || !(c->*p.on)) invalidate_denoised(c);   // the moments or the counts go, or start over
+    if (value == 0 || !(c->*p.on)) { invalidate_denoised(c); invalidate_robust(c); }   // the moments or the counts go, or start over
     if (value == 0) {
         c->*p.on = false;
         if ((rc = off_first(c))) return rc;
@@ -2035,6 +2120,27 @@ static int set_plane_option(hr_ctx *c, double value, const Plane &p, const Plane
     return plane_zero(c, other);
 }
 
+// Option "robust_buckets" = K.  0: the buckets go, and R with them.  K in {3, 5, .., 15}: K buckets per pixel, zeroed — set again
+// with the value it has: what has been gathered stays; with another K they start over.  Buckets that start (over) while option "sample_counts"
+// runs start the counts over too: a pixel's count is the ordinal of its next sampling.  The counts are the moments' n, so the moments go with them.
+static int set_robust_buckets(hr_ctx *c, double value) {
+    if (value != 0 && !robust_valid_k(value)) return fail(HR_ERR_INVALID, "robust_buckets must be 0 (off) or an odd number of buckets in [3,15]");
+    if (value != 0 && !c->W) return fail(HR_ERR_NO_TARGET, "robust_buckets: hr_set_resolution not called");
+    if (c->robust_on && (uint32_t)value == c->robust_k) return HR_OK;
+    int rc = sync_all(c);
+    if (rc) return rc;
+    invalidate_robust(c);
+    c->robust_on = false;
+    c->robust_k = 0;
+    if ((rc = plane_free(c, BUCKETS)) || (rc = plane_free(c, ROBUST)) || (rc = plane_free(c, ROBUST_TRIM))) return rc;
+    if (value == 0) return HR_OK;
+    c->robust_k = (uint32_t)value;
+    if ((rc = plane_alloc(c, BUCKETS))) { (void)plane_free(c, BUCKETS); c->robust_k = 0; return rc; }
+    c->robust_on = true;
+    if (c->counts_on) { invalidate_denoised(c); if ((rc = plane_zero(c, COUNTS)) || (rc = plane_zero(c, MOMENTS))) return rc; }
+    return HR_OK;
+}
+
 int hr_set_option(hr_ctx *c, const char *key, double value) {
     if (!c || !key) return fail(HR_ERR_INVALID, "hr_set_option: null argument");
     HIP_TRY(hipSetDevice(c->device));
@@ -2042,8 +2148,17 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
     if (const OptionRow *row = find_row(PRODUCT_OPTIONS, [&](const OptionRow &r) { return k == r.key; })) return apply_option(c, *row, value);
     // per-pixel first and second moments of the per-sampling values, for the noise estimate, and how many samplings every pixel
     // has received: what a tile mask (hr_set_tile_mask) needs — the mask goes when the counts go
-    if (k == "moments") return set_plane_option(c, value, MOMENTS, COUNTS, [](hr_ctx *x) { return plane_free(x, NOISE_IMG); });
-    if (k == "sample_counts") return set_plane_option(c, value, COUNTS, MOMENTS, remove_mask);
+    if (k == "moments") {   // (moments that start zero the counts, and the counts are the buckets' ordinals: the buckets start over with them)
+        const bool was_on = c->moments_on;
+        const int rc = set_plane_option(c, value, MOMENTS, COUNTS, [](hr_ctx *x) { return plane_free(x, NOISE_IMG); });
+        return !rc && value == 1 && !was_on && c->counts_on ? plane_zero(c, BUCKETS) : rc;
+    }
+    if (k == "sample_counts") {   // (the counts are the buckets' ordinals as well as the moments' n: both start over with them)
+        const bool was_on = c->counts_on;
+        const int rc = set_plane_option(c, value, COUNTS, MOMENTS, remove_mask);
+        return !rc && value == 1 && !was_on ? plane_zero(c, BUCKETS) : rc;
+    }
+    if (k == "robust_buckets") return set_robust_buckets(c, value);
     if (k == "guide_bounces") {  // next hr_render_guides; a new value drops the planes it would no longer describe, and the image filtered with them
         if (!(value >= 0 && value <= 8) || value != std::floor(value)) return fail(HR_ERR_INVALID, "guide_bounces must be a whole number in [0,8]");
         if ((uint32_t)value == c->guide_bounces) return HR_OK;

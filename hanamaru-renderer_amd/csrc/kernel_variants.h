@@ -186,3 +186,12 @@ static const AccumulateVariant ACCUMULATE_VARIANTS[] = {HR_VARIANT(accumulate_ke
 static AccumulateFn select_accumulate_kernel(bool moments, bool counts, bool list) {
     return fn_of(find_row(ACCUMULATE_VARIANTS, [&](const AccumulateVariant &r) { return r.mom == moments && r.cnts == counts && r.list == list; }));
 }
+
+// ---- bucket_kernel<CNTS, LIST> (trace_kernel.h): a launch's per-sampling pixel values into the sample buckets (option robust_buckets) ----
+typedef void (*BucketFn)(RenderParams, const float *, double *, const uint32_t *, uint32_t, unsigned long long);
+struct BucketVariant { bool cnts, list; BucketFn fn; };
+static const BucketVariant BUCKET_VARIANTS[] = {HR_VARIANT(bucket_kernel, false, false), HR_VARIANT(bucket_kernel, true, false), HR_VARIANT(bucket_kernel, true, true)};
+// sample_counts as the option has it; list: a tile mask is in force (it needs the counts: no <false, true> row)
+static BucketFn select_bucket_kernel(bool counts, bool list) {
+    return fn_of(find_row(BUCKET_VARIANTS, [&](const BucketVariant &r) { return r.cnts == counts && r.list == list; }));
+}

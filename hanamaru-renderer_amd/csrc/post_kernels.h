@@ -5,6 +5,7 @@
 #include "denoise_core.h"
 #include "device_scene.h"
 #include "post_core.h"
+#include "robust_core.h"
 
 using namespace hr;
 
@@ -38,4 +39,13 @@ __global__ __launch_bounds__(256) void denoise_final_kernel(const double *__rest
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pixels) return;
     denoise_final(cv + (size_t)i * 6, guides + (size_t)i * 8, demodulate, d + (size_t)i * 3);
+}
+
+// The firefly-robust resolve (robust_core.h): one thread per pixel, R and the trim plane from the pixel's K buckets.  The kernel carries
+// no arithmetic of its own.  counts == nullptr: every pixel has n_all samplings (option "sample_counts" off).
+__global__ __launch_bounds__(256) void robust_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all, uint32_t K,
+                                                     float *__restrict__ out, uint8_t *__restrict__ trim, uint32_t pixels) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    robust_pixel(buckets + (size_t)i * K * 3, K, counts ? (uint64_t)counts[i] : (uint64_t)n_all, out + (size_t)i * 3, trim + i);
 }

@@ -337,6 +337,35 @@ __device__ __forceinline__ float quad_sum(float v) {
     v += __shfl_xor(v, 1);
     return v + __shfl_xor(v, 2);
 }
+// The sample buckets (option "robust_buckets" = K): accumulate_kernel's mapping — one wave per (active) tile, lane j = (pixel of the
+// tile, sub-sample) — over the same records, launched in front of it.  The per-sampling pixel value x_k is the moments' to the bit (path_radiance_in,
+// quad_sum); the j-th sampling a pixel receives goes into its bucket j mod K: the lane of sub-sample 0 adds (double)x_k per channel to
+// buckets[reg_h][reg_w][K][3], one sampling at a time from the value in the buffer — the buckets do not depend on how samplings are cut into launches.
+// j starts at `start`, the samplings behind the buckets before this launch; CNTS (option "sample_counts"): at the pixel's own count, which
+// accumulate_kernel bumps behind this kernel.  LIST (a tile mask): one wave per ACTIVE tile, no other pixel is touched.
+template <bool CNTS, bool LIST = false>
+__global__ __launch_bounds__(256) void bucket_kernel(RenderParams rp, const float *__restrict__ recs, double *__restrict__ buckets, const uint32_t *__restrict__ counts, uint32_t K,
+                                                      unsigned long long start) {
+    const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= launch_tiles<LIST>(rp)) return;
+    uint32_t px, py, sub;
+    tile_lane_pixel(rp, launch_tile<LIST>(rp, tile), lane, px, py, sub);
+    const bool valid = rp_in_region(rp, px, py);      // (lanes beyond the region's edge: their records hold nothing of the region)
+    const bool adds = valid && sub == 0u;
+    const f4 *src = reinterpret_cast<const f4 *>(recs + (size_t)tile * rp.num_k * REC_ITEM_FLOATS) + lane;
+    const size_t pixel = adds ? (size_t)py * rp_reg_w(rp) + px : 0;
+    double *bk = buckets + pixel * K * 3;
+    uint32_t b = adds ? (uint32_t)((CNTS ? (unsigned long long)counts[pixel] : start) % K) : 0u;
+    for (uint32_t k = 0; k < rp.num_k; k++) {   // (every lane of the wave is here: the trip count is the launch's)
+        const f4 v = valid ? src[(size_t)k * (REC_ITEM_FLOATS / 4u)] : f4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float xr = quad_sum(path_radiance_in(v.x)), xg = quad_sum(path_radiance_in(v.y)), xb = quad_sum(path_radiance_in(v.z));
+        if (adds) {
+            double *o = bk + b * 3u;
+            o[0] += (double)xr; o[1] += (double)xg; o[2] += (double)xb;
+            b = b + 1u == K ? 0u : b + 1u;
+        }
+    }
+}
 // the guide kernels' store: the sub-sample 0 lane STORES the mean (sum x 0.25f, exact) into guides[reg_h][reg_w][8] — a pass replaces the planes
 __device__ __forceinline__ void guide_store(const RenderParams &rp, const bool active, uint32_t px, uint32_t py, uint32_t sub, float *g, float *__restrict__ guides) {
     for (int k = 0; k < 8; k++) g[k] = quad_sum(g[k]);

@@ -12,7 +12,9 @@
 // with a relative standard error above E are rendered on; hr_select_tiles, hr_resolve_counted),
 // --denoise / --denoise-levels N / --guide-image PREFIX (option "moments": the final image is the variance-guided a-trous filter's, hr_denoise +
 // hr_resolve_denoised; the guide planes as images of their own, hr_render_guides + hr_read_guides), --guide-bounces K (option "guide_bounces":
-// the guide rays follow mirrors and glass for up to K bounces to the first rough hit; 0, the default, is the first hit).
+// the guide rays follow mirrors and glass for up to K bounces to the first rough hit; 0, the default, is the first hit),
+// --robust K / --robust-image FILE (option "robust_buckets": every image is the firefly-robust resolve of K sample buckets per pixel, hr_robust +
+// hr_resolve_robust; the buckets ride in the checkpoint behind the other trailers).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -103,7 +105,14 @@ static void usage(const char *prog) {
            "        --guide-bounces K\n"
            "                        the guide planes follow mirrors and glass (Specular and Refraction surfaces) for up to K bounces, 0 .. 8, to the\n"
            "                        first rough hit: albedo is the product along the chain, the normal the last hit's, depth the path length.\n"
-           "                        Default 0: the first hit.  Needs --denoise or --guide-image.\n",
+           "                        Default 0: the first hit.  Needs --denoise or --guide-image.\n"
+           "        --robust K      keep K sample buckets per pixel (K odd, 3 .. 15; 3 K doubles per pixel) and write every image, progress and final,\n"
+           "                        through the firefly-robust resolve (hr_robust + hr_resolve_robust: an adaptive median of the K bucket means, which\n"
+           "                        drops the buckets a few very bright paths landed in; biased dark where it trims).  Works with --region,\n"
+           "                        --noise-target and --adaptive (every pixel's own sampling count).  --checkpoint appends the buckets, --resume\n"
+           "                        restores them and refuses a file without them or with another K.  One device only; not with --denoise or --debug.\n"
+           "        --robust-image FILE.png\n"
+           "                        write an 8-bit grey map of trim / ((K - 1) / 2), the buckets dropped at either end (needs --robust)\n",
            prog);
 }
 
@@ -127,6 +136,8 @@ int main(int argc, char **argv) {
     long long denoise_levels = -1;   // -1: the library's default
     std::string guide_prefix;
     long long guide_bounces = -1;    // -1: not given (the library's default, 0)
+    long long robust_k = 0;          // --robust K: option "robust_buckets" (0: off)
+    std::string robust_png;
     // a number, the whole argument, not NaN; what is wrong with it is said with the flag's name, before any device is opened
     auto number = [](const char *flag, const char *text, double *out) -> bool {
         char *e = nullptr;
@@ -190,6 +201,12 @@ int main(int argc, char **argv) {
             guide_bounces = strtoll(t, &e, 10);
             if (e == t || *e || guide_bounces < 0 || guide_bounces > 8) { fprintf(stderr, "--guide-bounces must be a whole number in 0 .. 8, not '%s'.\n", t); return 1; }
         }
+        else if (a == "--robust") {
+            const char *t = val("robust");
+            char *e = nullptr;
+            robust_k = strtoll(t, &e, 10);
+            if (e == t || *e || robust_k < 3 || robust_k > 15 || !(robust_k & 1)) { fprintf(stderr, "--robust must be an odd number of buckets in 3 .. 15, not '%s'.\n", t); return 1; }
+        } else if (a == "--robust-image") robust_png = val("robust-image");
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -218,6 +235,17 @@ int main(int argc, char **argv) {
             return 1;
         }
         if (debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
+    }
+    if (!robust_png.empty() && !robust_k) { fprintf(stderr, "--robust-image needs --robust.\n"); return 1; }
+    if (robust_k) {
+        size_t ids = gpu_ids.empty() ? 0 : 1;
+        for (char ch : gpu_ids) ids += ch == ',';
+        if (gpus > 1 || ids > 1) {
+            fprintf(stderr, "--robust renders on one device: buckets of several devices add up only when each rendered a multiple of K samplings, and this program's device loop does not see to that.\n");
+            return 1;
+        }
+        if (denoise) { fprintf(stderr, "--robust cannot be combined with --denoise (the filter reads the raw moments, not the robust radiance: two final images).\n"); return 1; }
+        if (debug) { fprintf(stderr, "--robust cannot be combined with --debug (the debug renderer has no samplings to put into buckets).\n"); return 1; }
     }
     const bool moments = have_target || !noise_png.empty() || have_adaptive || denoise;   // hr_set_option "moments"
     if (moments && debug) { fprintf(stderr, "--noise-target / --noise-image cannot be combined with --debug (the debug renderer has no samplings to measure).\n"); return 1; }
@@ -287,6 +315,7 @@ int main(int argc, char **argv) {
         if (moments) CHECK_HR(hr_set_option(ctxs[r], "moments", 1.0));
         if (counts) CHECK_HR(hr_set_option(ctxs[r], "sample_counts", 1.0));
         if (guide_bounces >= 0) CHECK_HR(hr_set_option(ctxs[r], "guide_bounces", (double)guide_bounces));
+        if (robust_k) CHECK_HR(hr_set_option(ctxs[r], "robust_buckets", (double)robust_k));
     }
     hr_ctx *ctx = ctxs[0];
     if (ndev > 1) tee("devices: %u.", ndev);
@@ -319,6 +348,7 @@ int main(int argc, char **argv) {
     bool have_guides = false;   // the context holds guide planes (for --guide-image)
     bool final_image = false;   // set by whoever writes the render's last image: --denoise filters that one only
     auto resolve = [&](uint32_t s, uint8_t *out) -> int {
+        if (robust_k) return hr_robust(ctx) != 0 ? 1 : hr_resolve_robust(ctx, out);   // (one device, no --denoise: checked with the flags)
         if (denoise && final_image) {
             hr_denoise_params dp;
             if (hr_denoise_default_params(&dp) != 0) return 1;
@@ -398,6 +428,7 @@ int main(int argc, char **argv) {
     const uint32_t CKPT_REGION_MAGIC = 0x32525248u;   // "HRR2"
     const uint32_t CKPT_MOMENTS_MAGIC = 0x534d5248u;  // "HRMS": the trailer behind the accumulator of a render with moments on
     const uint32_t CKPT_COUNTS_MAGIC = 0x43535248u;   // "HRSC": the trailer behind that of a render with sample counts on — w*h uint32
+    const uint32_t CKPT_BUCKETS_MAGIC = 0x4b425248u;  // "HRBK": the trailer behind those of a render with --robust — K (uint32), samplings (uint64), w*h*3K doubles
     bool resumed_counts = false;                      // --resume restored per-pixel counts: the tiles are chosen again before anything is rendered
     uint32_t scene_hash = 2166136261u;
     for (char ch : scene_name) scene_hash = (scene_hash ^ (uint8_t)ch) * 16777619u;
@@ -427,7 +458,7 @@ int main(int argc, char **argv) {
         std::vector<double> mom;
         bool have_mom = false;
         std::vector<uint32_t> cnt;
-        if (ok && (moments || counts) && fread(&mmagic, 4, 1, f) == 1 && mmagic == CKPT_MOMENTS_MAGIC) {
+        if (ok && (moments || counts || robust_k) && fread(&mmagic, 4, 1, f) == 1 && mmagic == CKPT_MOMENTS_MAGIC) {
             mom.resize((size_t)out_w * out_h * 6);
             have_mom = fread(&mom_n, 8, 1, f) == 1 && fread(mom.data(), sizeof(double), mom.size(), f) == mom.size();
             if (have_mom && fread(&mmagic, 4, 1, f) != 1) mmagic = 0;   // what follows the moments
@@ -439,10 +470,29 @@ int main(int argc, char **argv) {
             if (mmagic == CKPT_COUNTS_MAGIC) {
                 resumed_counts = fread(cnt.data(), sizeof(uint32_t), cnt.size(), f) == cnt.size();
                 ok = resumed_counts;
+                if (ok && fread(&mmagic, 4, 1, f) != 1) mmagic = 0;   // what follows the counts
+            }
+        }
+        // {"HRBK", K, samplings behind the buckets, w*h*3K doubles}
+        std::vector<double> bkt;
+        uint32_t bkt_k = 0;
+        uint64_t bkt_n = 0;
+        const char *bkt_why = nullptr;
+        if (ok && robust_k) {
+            if (!counts && mmagic == CKPT_COUNTS_MAGIC) bkt_why = "its buckets were filled by per-pixel sampling counts (resume with --adaptive or --sample-image as well)";
+            else if (mmagic != CKPT_BUCKETS_MAGIC || fread(&bkt_k, 4, 1, f) != 1 || fread(&bkt_n, 8, 1, f) != 1) bkt_why = "it holds no sample buckets (it was written without --robust)";
+            else if (bkt_k != (uint32_t)robust_k) bkt_why = "its sample buckets were kept with another K";
+            else {
+                bkt.resize((size_t)out_w * out_h * 3 * bkt_k);
+                ok = fread(bkt.data(), sizeof(double), bkt.size(), f) == bkt.size();
             }
         }
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot resume from %s (missing, wrong magic, resolution or scene)\n", ckpt_in.c_str()); return 1; }
+        if (bkt_why) {
+            fprintf(stderr, "--resume %s with --robust %lld: %s; resume without --robust, or render again with it.\n", ckpt_in.c_str(), robust_k, bkt_why);
+            return 1;
+        }
         if (have_adaptive && !have_mom) {
             fprintf(stderr, "--resume %s with --adaptive: the checkpoint holds no sample moments (it was written without --adaptive / --noise-target / --noise-image), "
                             "so the noise of its %u samplings cannot be known; resume without --adaptive, or render again with it.\n", ckpt_in.c_str(), hdr[3]);
@@ -470,6 +520,7 @@ int main(int argc, char **argv) {
         if (counts) CHECK_HR(hr_write_sample_counts(ctx, cnt.data()));
         if (have_mom) CHECK_HR(hr_write_moments(ctx, mom.data(), mom_n));
         else if (moments) printf("the checkpoint holds no sample moments: the noise image covers the samplings rendered from here on\n");
+        if (robust_k) CHECK_HR(hr_write_buckets(ctx, bkt.data(), bkt_n));
         first = hdr[3] + 1;
         sampled = hdr[3];
         printf("resumed at %ux4 sampled\n", hdr[3]);
@@ -651,6 +702,13 @@ int main(int argc, char **argv) {
             if (hr_read_sample_counts(ctx, cnt.data()) != 0) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
             ok = fwrite(&CKPT_COUNTS_MAGIC, 4, 1, f) == 1 && fwrite(cnt.data(), sizeof(uint32_t), cnt.size(), f) == cnt.size();
         }
+        if (ok && robust_k) {   // behind every other trailer; a file written without --robust keeps the bytes it always had
+            std::vector<double> bkt((size_t)out_w * out_h * 3 * (size_t)robust_k);
+            uint64_t bkt_n = 0;
+            const uint32_t k32 = (uint32_t)robust_k;
+            if (hr_read_buckets(ctx, bkt.data(), &bkt_n) != 0) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
+            ok = fwrite(&CKPT_BUCKETS_MAGIC, 4, 1, f) == 1 && fwrite(&k32, 4, 1, f) == 1 && fwrite(&bkt_n, 8, 1, f) == 1 && fwrite(bkt.data(), sizeof(double), bkt.size(), f) == bkt.size();
+        }
         if (f) fclose(f);
         if (!ok) { fprintf(stderr, "cannot write checkpoint %s\n", ckpt_out.c_str()); return 1; }
     }
@@ -703,6 +761,20 @@ int main(int argc, char **argv) {
         if (hh_write_png_rgb8((guide_prefix + "_normal.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
         for (size_t i = 0; i < pixels; i++) img[i * 3] = img[i * 3 + 1] = img[i * 3 + 2] = byte(zmax > 0.0f ? g[i * 8 + 6] / zmax : 0.0f);
         if (hh_write_png_rgb8((guide_prefix + "_depth.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+    }
+    if (robust_k) {   // how much the robust resolve dropped; and its map
+        std::vector<uint8_t> trim((size_t)out_w * out_h);
+        CHECK_HR(hr_robust(ctx));
+        CHECK_HR(hr_read_robust_trim(ctx, trim.data()));
+        const uint32_t most = (uint32_t)(robust_k - 1) / 2;
+        size_t trimmed = 0;
+        for (uint8_t v : trim) trimmed += v != 0;
+        tee("robust: buckets=%lld trimmed pixels=%.4f", robust_k, (double)trimmed / (double)trim.size());
+        if (!robust_png.empty()) {   // grey map of trim / ((K - 1) / 2)
+            std::vector<uint8_t> grey(trim.size() * 3);
+            for (size_t i = 0; i < trim.size(); i++) grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = (uint8_t)((double)trim[i] / (double)most * 255.0 + 0.5);
+            if (hh_write_png_rgb8(robust_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        }
     }
     if (counts) {   // how the samplings were spent
         std::vector<uint32_t> cnt((size_t)out_w * out_h);

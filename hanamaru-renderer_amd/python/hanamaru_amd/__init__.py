@@ -205,6 +205,12 @@ def hip_lib():
         L.hr_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)]
         L.hr_read_denoised.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_resolve_denoised.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_read_buckets.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.hr_write_buckets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.hr_robust.argtypes = [C.c_void_p]
+        L.hr_read_robust.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_read_robust_trim.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_resolve_robust.argtypes = [C.c_void_p, C.c_void_p]
         _hip = L
     return _hip
 
@@ -345,6 +351,7 @@ class Renderer:
         self._h = h
         self.width = self.height = 0
         self._region = None   # (x0, y0, w, h) set by set_region; None = the whole frame
+        self._robust_k = 0    # option "robust_buckets" as last accepted
 
     def _check(self, rc):
         if rc != 0:
@@ -393,6 +400,8 @@ class Renderer:
 
     def set_option(self, key, value):
         self._check(self.L.hr_set_option(self._h, key.encode(), float(value)))
+        if key == "robust_buckets":   # the K the library accepted sizes read_buckets / write_buckets
+            self._robust_k = int(value)
 
     def set_debug_option(self, key, value):
         """Measurement knobs (include/hanamaru_hip.h: hr_set_debug_option) — not for product code."""
@@ -570,6 +579,42 @@ class Renderer:
         """hr_resolve_denoised: resolve() of the denoised radiance."""
         out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
         self._check(self.L.hr_resolve_denoised(self._h, out.ctypes.data))
+        return out
+
+    # ---- option "robust_buckets": the sample buckets and the firefly-robust resolve (include/hanamaru_hip.h)
+    def read_buckets(self):
+        """hr_read_buckets: ((h, w, K, 3) float64 bucket sums — K from the size the library reports for the option —, samplings behind them)."""
+        k = self._robust_k
+        out = np.empty(self._acc_hw() + (max(k, 1), 3), dtype=np.float64)
+        n = C.c_uint64()
+        self._check(self.L.hr_read_buckets(self._h, out.ctypes.data, C.byref(n)))
+        return out, int(n.value)
+
+    def write_buckets(self, buckets, samplings):
+        a = np.ascontiguousarray(buckets, dtype=np.float64)
+        assert a.shape == self._acc_hw() + (self._robust_k, 3)
+        self._check(self.L.hr_write_buckets(self._h, a.ctypes.data, C.c_uint64(samplings)))
+
+    def robust(self):
+        """hr_robust: the robust radiance R and its trim plane from the buckets."""
+        self._check(self.L.hr_robust(self._h))
+
+    def read_robust(self):
+        """hr_read_robust: (h, w, 3) float32 radiance."""
+        out = np.empty(self._acc_hw() + (3,), dtype=np.float32)
+        self._check(self.L.hr_read_robust(self._h, out.ctypes.data))
+        return out
+
+    def read_robust_trim(self):
+        """hr_read_robust_trim: (h, w) uint8, the buckets dropped at either end."""
+        out = np.empty(self._acc_hw(), dtype=np.uint8)
+        self._check(self.L.hr_read_robust_trim(self._h, out.ctypes.data))
+        return out
+
+    def resolve_robust(self):
+        """hr_resolve_robust: resolve() of the robust radiance."""
+        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
+        self._check(self.L.hr_resolve_robust(self._h, out.ctypes.data))
         return out
 
     def debug_draws(self, sampling, first_path, num_paths, window):

@@ -408,6 +408,49 @@ int hr_denoise(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */);
 int hr_read_denoised(hr_ctx *ctx, float *host /* w*h*3 radiance */);
 int hr_resolve_denoised(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on D with scale 1.0f */
 
+/* ---- sample buckets and the firefly-robust resolve (option "robust_buckets", off by default) -------------------------------------
+ * The estimator has next-event estimation to small emitters and no MIS: a short render is dominated by a few paths that carry hundreds of times
+ * their pixel's mean, and the plain mean of the samplings shows them as fireflies.  With option "robust_buckets" = K (K odd, 3 .. 15) the context
+ * keeps, per pixel, K x 3 f64 sums of the per-sampling values x_s of "moments" above: the j-th sampling a pixel receives (j = 0, 1, .. per pixel,
+ * in the order rendered) adds (double)x_s per channel to bucket j mod K, one sampling at a time from the value in the buffer.  hr_robust turns
+ * them into R, an adaptive median of the bucket means (after Buisine et al. 2021): no extra path is traced.
+ *   - buckets[h][w][K][3] f64, region-local.  Memory: 3 K doubles per pixel — 448 MB at 1920x1080 with K = 9, 747 MB with K = 15.
+ *   - With "sample_counts" on, j starts at the pixel's own count; without it at the samplings behind the buckets (the count hr_read_buckets
+ *     returns).  The buckets therefore do not depend on how samplings are cut into launches, and under a tile mask a pixel that has received
+ *     samplings 1 .. n holds the buckets of a uniform render of samplings 1 .. n.
+ *   - hr_set_option "robust_buckets" K needs hr_set_resolution first (HR_ERR_NO_TARGET), allocates and zeroes the buckets and their count; the
+ *     value it already has changes nothing; another K starts them over; 0 frees them; any other value is HR_ERR_INVALID and changes nothing.
+ *     hr_clear, hr_set_resolution and hr_set_region zero them (the last two at the new size).  Buckets that start (over) while "sample_counts"
+ *     is on zero the counts — a pixel's count is the ordinal of its next sampling — and with the counts the moments whose n they are; switching
+ *     "sample_counts" on (or "moments" on while the counts run, which zeroes the counts) zeroes the buckets.  hr_write_accumulator / _moments /
+ *     _sample_counts do not touch them: a host that resumes writes all of them.  hr_render_debug returns HR_ERR_UNSUPPORTED while the option is
+ *     on.  The option does not need "moments".  The accumulator, the moments and the counts are bit-identical with the option on or off, and
+ *     with it off nothing more is launched.
+ *   - hr_read_buckets / hr_write_buckets: w*h*K*3 doubles and the samplings behind them — resume, tile stitching.  Buckets of several ranks can
+ *     be added only when every rank rendered a multiple of K samplings (bucket b of every rank then holds the same share); there is no
+ *     library-side collective.
+ *   - hr_robust computes R (w x h x 3 floats of radiance) and the trim plane (w x h bytes) — both allocated on first use; its time goes to
+ *     hr_stats.post_kernel_ms.  The definition is csrc/robust_core.h, to the bit (f64; + - x /, comparisons and one truncation; one IEEE
+ *     operation per step, no FMA).  For a pixel with n samplings (its own count with "sample_counts" on, else the count behind the buckets) and
+ *     bucket sums B[b][c]:
+ *         n == 0   R = 0;      n < K   R_c = ((B[0][c] + B[1][c]) + .. + B[K-1][c]) / n / 4 (the plain mean), trim = 0;       otherwise
+ *         n_b = (n - b + K - 1) / K (integer);   m_b,c = B[b][c] / n_b / 4;   y_b = (m_b,r + m_b,g) + m_b,b;   buckets ascending by (y_b, b);
+ *         T = sum_i y_(i);   Gn = sum_i (2 i - K - 1) y_(i), i = 1 .. K;   trim = 0 if T <= 0, else G = Gn / (K T) (the Gini coefficient of the
+ *         bucket means), trim = G > 0 ? min((K - 1) / 2, (int)(G K / 2)) : 0;   R_c = (sum_{i = trim + 1 .. K - trim} m_(i),c) / (K - 2 trim).
+ *     Equal buckets give trim 0 (the mean of the bucket means), one bucket holding everything gives (K - 1) / 2 (the median bucket).  R is biased
+ *     dark where it trims; the bias shrinks as the bucket means converge (DESIGN.md 4.10 has the measured figures).
+ *   - R is valid until anything it was made of changes: hr_render, hr_clear, hr_write_accumulator / _moments / _sample_counts / _buckets,
+ *     hr_bind_accumulator, switching "robust_buckets", "moments" or "sample_counts", hr_set_resolution, hr_set_region.  hr_read_robust,
+ *     hr_read_robust_trim and hr_resolve_robust return HR_ERR_INVALID without a valid R; all six functions return HR_ERR_INVALID with the option
+ *     off; in both cases R stays as it was.  hr_resolve_robust is renderer.rs:64-90 on R with the scale 1.0f, as hr_resolve_denoised is on D.
+ *   - The noise estimate and the denoiser still read the raw moments.  All of these synchronise. */
+int hr_read_buckets(hr_ctx *ctx, double *host /* w*h*K*3 */, uint64_t *samplings /* may be NULL */);
+int hr_write_buckets(hr_ctx *ctx, const double *host, uint64_t samplings);   /* resume, tile stitching */
+int hr_robust(hr_ctx *ctx);
+int hr_read_robust(hr_ctx *ctx, float *host /* w*h*3 radiance */);
+int hr_read_robust_trim(hr_ctx *ctx, uint8_t *host /* w*h: buckets dropped at either end */);
+int hr_resolve_robust(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on R with scale 1.0f */
+
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):
  *   "counters"      0 / 1: instrumented build of the trace kernel (fills the counter fields of hr_stats)
@@ -436,6 +479,8 @@ int hr_get_stats(hr_ctx *ctx, hr_stats *out);
  *                   the image does not change by a bit
  *   "sample_counts" 0 (default) / 1: keep per-pixel counts of the samplings received, for hr_set_tile_mask / hr_select_tiles /
  *                   hr_resolve_counted (see there); the image does not change by a bit
+ *   "robust_buckets" 0 (default) / K in {3, 5, .., 15}: keep K sample buckets per pixel for hr_robust (see there; 3 K doubles per pixel); the
+ *                   image does not change by a bit
  *   next hr_render_guides:
  *   "guide_bounces" 0 (default) .. 8, a whole number: how many mirrors and glass surfaces the guide rays follow to the first rough hit (see
  *                   "guide planes" above).  A new value drops the guide planes and the denoised image; the value it already has changes

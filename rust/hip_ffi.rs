@@ -95,6 +95,14 @@ extern "C" {
     pub fn hr_denoise(ctx: *mut HrCtx, p: *const HrDenoiseParams /* null = defaults */) -> c_int;
     pub fn hr_read_denoised(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 radiance */) -> c_int;
     pub fn hr_resolve_denoised(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
+    // option "robust_buckets" = K (hr_set_option): per pixel K x 3 f64 sums of the per-sampling values (w*h*K*3 doubles) and the firefly-robust
+    // radiance made of them; HR_ERR_INVALID while the option is off
+    pub fn hr_read_buckets(ctx: *mut HrCtx, host: *mut f64 /* w*h*K*3 */, samplings: *mut u64) -> c_int;
+    pub fn hr_write_buckets(ctx: *mut HrCtx, host: *const f64, samplings: u64) -> c_int;
+    pub fn hr_robust(ctx: *mut HrCtx) -> c_int;
+    pub fn hr_read_robust(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 radiance */) -> c_int;
+    pub fn hr_read_robust_trim(ctx: *mut HrCtx, host: *mut u8 /* w*h */) -> c_int;
+    pub fn hr_resolve_robust(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----

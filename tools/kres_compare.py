@@ -12,8 +12,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kres  # noqa: E402
 
-PARENT_ARITY = {"trace_kernel": 7, "accumulate_kernel": 3, "wf_start_kernel": 2, "seed_seg_kernel": 3, "noise_kernel": 1}
-PATTERN = re.compile(r"trace_kernel|seed_seg_kernel|accumulate_kernel|wf_|tonemap|bilateral|noise_kernel|governor|select_tiles|counts_min|seed_isaac64|seed_pc|debug_render|trace_debug|guide_|atrous|denoise_")
+PARENT_ARITY = {"trace_kernel": 7, "accumulate_kernel": 3, "wf_start_kernel": 2, "seed_seg_kernel": 4, "noise_kernel": 1}
+PATTERN = re.compile(r"trace_kernel|seed_seg_kernel|accumulate_kernel|wf_|tonemap|bilateral|noise_kernel|governor|select_tiles|counts_min|seed_isaac64|seed_pc|debug_render|trace_debug|guide_|atrous|denoise_|bucket_kernel|robust_kernel")
 KEYS = ["vgpr", "sgpr", "vspill", "sspill", "scratch", "lds", "occ"]
 
 
