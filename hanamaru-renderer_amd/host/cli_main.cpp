@@ -15,6 +15,8 @@
 // the guide rays follow mirrors and glass for up to K bounces to the first rough hit; 0, the default, is the first hit),
 // --robust K / --robust-image FILE (option "robust_buckets": every image is the firefly-robust resolve of K sample buckets per pixel, hr_robust +
 // hr_resolve_robust; the buckets ride in the checkpoint behind the other trailers).
+// The file is in main's order: Options and parse_options (everything that can be refused before a device is opened), then Run, whose members
+// are main's steps.  The checkpoint's format is host/checkpoint.h's; what a render demands of a file is said in Run::resume.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -25,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "checkpoint.h"
 #include "hanamaru_hip.h"
 #include "hanamaru_host.h"
 
@@ -116,7 +119,7 @@ static void usage(const char *prog) {
            prog);
 }
 
-int main(int argc, char **argv) {
+struct Options {
     uint32_t width = 1920, height = 1080, sampling = 1000;  // main.rs:1249-1251
     double time_limit = 123.0, interval = 15.0;              // main.rs:1255-1256
     std::string scene_name = "rtcamp6_v3_1", assets, ckpt_out, ckpt_in, gpu_ids;
@@ -138,13 +141,59 @@ int main(int argc, char **argv) {
     long long guide_bounces = -1;    // -1: not given (the library's default, 0)
     long long robust_k = 0;          // --robust K: option "robust_buckets" (0: off)
     std::string robust_png;
-    // a number, the whole argument, not NaN; what is wrong with it is said with the flag's name, before any device is opened
-    auto number = [](const char *flag, const char *text, double *out) -> bool {
+    // what the flags add up to:
+    bool counts = false, moments = false;   // hr_set_option "sample_counts", "moments"
+    double noise_e = 0.05;                  // the threshold of "above" and of the grey map
+    uint32_t region[4] = {0, 0, 0, 0};      // --region, or the whole frame
+    bool has_region = false;
+    uint32_t out_w = 0, out_h = 0;          // the accumulator and the images: the region's
+};
+
+// a number, the whole argument, not NaN; what is wrong with it is said with the flag's name, before any device is opened
+static bool number(const char *flag, const char *text, double *out) {
+    char *e = nullptr;
+    *out = strtod(text, &e);
+    if (e == text || *e || std::isnan(*out) || std::isinf(*out)) { fprintf(stderr, "%s: '%s' is not a number.\n", flag, text); return false; }
+    return true;
+}
+// a whole number, the whole argument, one of lo, lo + step, .. up to hi; `what` is the flag's own word for that
+static bool whole(const char *flag, const char *text, long long lo, long long hi, long long step, const char *what, long long *out) {
+    char *e = nullptr;
+    *out = strtoll(text, &e, 10);
+    if (e == text || *e || *out < lo || *out > hi || (*out - lo) % step) { fprintf(stderr, "%s must be %s, not '%s'.\n", flag, what, text); return false; }
+    return true;
+}
+// a feature that this program renders on one device only: its sentence, when --gpus / --gpu-ids name more
+static bool one_device(const Options &o, const char *sentence) {
+    size_t ids = o.gpu_ids.empty() ? 0 : 1;
+    for (char ch : o.gpu_ids) ids += ch == ',';
+    if (o.gpus > 1 || ids > 1) fprintf(stderr, "%s\n", sentence);
+    return !(o.gpus > 1 || ids > 1);
+}
+// --region X,Y,W,H: four unsigned integers, a non-empty window inside the frame (hr_set_region's rule, checked before any device is opened)
+static bool parse_region(const char *text, uint32_t width, uint32_t height, uint32_t region[4]) {
+    uint64_t v[4];
+    int n = 0;
+    for (const char *p = text; n < 4; n++) {
+        if (*p < '0' || *p > '9') break;
         char *e = nullptr;
-        *out = strtod(text, &e);
-        if (e == text || *e || std::isnan(*out) || std::isinf(*out)) { fprintf(stderr, "%s: '%s' is not a number.\n", flag, text); return false; }
-        return true;
-    };
+        v[n] = strtoull(p, &e, 10);
+        if (v[n] > 0xffffffffull) break;
+        p = e;
+        if (n < 3 && *p++ != ',') break;
+        if (n == 3 && *p) break;
+    }
+    if (n != 4) { fprintf(stderr, "--region must be X,Y,W,H (four unsigned integers), not '%s'.\n", text); return false; }
+    if (!v[2] || !v[3] || v[0] > width || v[2] > width - v[0] || v[1] > height || v[3] > height - v[1]) {
+        fprintf(stderr, "--region %s: the window must be non-empty and lie inside the %ux%u frame.\n", text, width, height);
+        return false;
+    }
+    for (int k = 0; k < 4; k++) region[k] = (uint32_t)v[k];
+    return true;
+}
+
+// argv into Options, with every refusal that needs no device.  Returns the exit status, or -1: go on and render.
+static int parse_options(int argc, char **argv, Options &o) {
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -152,172 +201,186 @@ int main(int argc, char **argv) {
             return argv[++i];
         };
         if (a == "--help") { usage(argv[0]); return 0; }
-        else if (a == "-d" || a == "--debug") debug = true;
-        else if (a == "-w" || a == "--width") width = (uint32_t)strtoul(val("w"), nullptr, 10);
-        else if (a == "-h" || a == "--height") height = (uint32_t)strtoul(val("h"), nullptr, 10);
-        else if (a == "-s" || a == "--sampling") sampling = (uint32_t)strtoul(val("s"), nullptr, 10);
-        else if (a == "-t" || a == "--time") time_limit = strtod(val("t"), nullptr);
-        else if (a == "-i" || a == "--interval") interval = strtod(val("i"), nullptr);
-        else if (a == "--scene") scene_name = val("scene");
-        else if (a == "--assets") assets = val("assets");
-        else if (a == "--batch") batch = atoi(val("batch"));
-        else if (a == "--launch") launch = atoi(val("launch"));
-        else if (a == "--inflight") inflight = atoi(val("inflight"));
-        else if (a == "--precise") precise = 1;
-        else if (a == "--no-precise") precise = 0;
-        else if (a == "--gpus") gpus = atoi(val("gpus"));
-        else if (a == "--gpu-ids") gpu_ids = val("gpu-ids");
-        else if (a == "--checkpoint") ckpt_out = val("checkpoint");
-        else if (a == "--resume") ckpt_in = val("resume");
-        else if (a == "--region") region_arg = val("region");
+        else if (a == "-d" || a == "--debug") o.debug = true;
+        else if (a == "-w" || a == "--width") o.width = (uint32_t)strtoul(val("w"), nullptr, 10);
+        else if (a == "-h" || a == "--height") o.height = (uint32_t)strtoul(val("h"), nullptr, 10);
+        else if (a == "-s" || a == "--sampling") o.sampling = (uint32_t)strtoul(val("s"), nullptr, 10);
+        else if (a == "-t" || a == "--time") o.time_limit = strtod(val("t"), nullptr);
+        else if (a == "-i" || a == "--interval") o.interval = strtod(val("i"), nullptr);
+        else if (a == "--scene") o.scene_name = val("scene");
+        else if (a == "--assets") o.assets = val("assets");
+        else if (a == "--batch") o.batch = atoi(val("batch"));
+        else if (a == "--launch") o.launch = atoi(val("launch"));
+        else if (a == "--inflight") o.inflight = atoi(val("inflight"));
+        else if (a == "--precise") o.precise = 1;
+        else if (a == "--no-precise") o.precise = 0;
+        else if (a == "--gpus") o.gpus = atoi(val("gpus"));
+        else if (a == "--gpu-ids") o.gpu_ids = val("gpu-ids");
+        else if (a == "--checkpoint") o.ckpt_out = val("checkpoint");
+        else if (a == "--resume") o.ckpt_in = val("resume");
+        else if (a == "--region") o.region_arg = val("region");
         else if (a == "--noise-target") {
-            if (!number("--noise-target", val("noise-target"), &noise_target)) return 1;
-            if (noise_target < 0.0) { fprintf(stderr, "--noise-target must not be negative.\n"); return 1; }
-            have_target = true;
+            if (!number("--noise-target", val("noise-target"), &o.noise_target)) return 1;
+            if (o.noise_target < 0.0) { fprintf(stderr, "--noise-target must not be negative.\n"); return 1; }
+            o.have_target = true;
         } else if (a == "--noise-floor") {
-            if (!number("--noise-floor", val("noise-floor"), &noise_floor)) return 1;
-            if (!(noise_floor > 0.0)) { fprintf(stderr, "--noise-floor must be positive.\n"); return 1; }
+            if (!number("--noise-floor", val("noise-floor"), &o.noise_floor)) return 1;
+            if (!(o.noise_floor > 0.0)) { fprintf(stderr, "--noise-floor must be positive.\n"); return 1; }
         } else if (a == "--noise-check") {
-            const char *t = val("noise-check");
-            char *e = nullptr;
-            noise_check = strtoll(t, &e, 10);
-            if (e == t || *e || noise_check < 1 || noise_check > 0x7fffffffll) { fprintf(stderr, "--noise-check must be a whole number of samplings, at least 1, not '%s'.\n", t); return 1; }
-        } else if (a == "--noise-image") noise_png = val("noise-image");
+            if (!whole("--noise-check", val("noise-check"), 1, 0x7fffffffll, 1, "a whole number of samplings, at least 1", &o.noise_check)) return 1;
+        } else if (a == "--noise-image") o.noise_png = val("noise-image");
         else if (a == "--adaptive") {
-            if (!number("--adaptive", val("adaptive"), &adaptive_e)) return 1;
-            if (!(adaptive_e > 0.0)) { fprintf(stderr, "--adaptive must be positive.\n"); return 1; }
-            have_adaptive = true;
-        } else if (a == "--sample-image") sample_png = val("sample-image");
-        else if (a == "--denoise") denoise = true;
+            if (!number("--adaptive", val("adaptive"), &o.adaptive_e)) return 1;
+            if (!(o.adaptive_e > 0.0)) { fprintf(stderr, "--adaptive must be positive.\n"); return 1; }
+            o.have_adaptive = true;
+        } else if (a == "--sample-image") o.sample_png = val("sample-image");
+        else if (a == "--denoise") o.denoise = true;
         else if (a == "--denoise-levels") {
-            const char *t = val("denoise-levels");
-            char *e = nullptr;
-            denoise_levels = strtoll(t, &e, 10);
-            if (e == t || *e || denoise_levels < 0 || denoise_levels > 5) { fprintf(stderr, "--denoise-levels must be a whole number in 0 .. 5, not '%s'.\n", t); return 1; }
-        } else if (a == "--guide-image") guide_prefix = val("guide-image");
+            if (!whole("--denoise-levels", val("denoise-levels"), 0, 5, 1, "a whole number in 0 .. 5", &o.denoise_levels)) return 1;
+        } else if (a == "--guide-image") o.guide_prefix = val("guide-image");
         else if (a == "--guide-bounces") {
-            const char *t = val("guide-bounces");
-            char *e = nullptr;
-            guide_bounces = strtoll(t, &e, 10);
-            if (e == t || *e || guide_bounces < 0 || guide_bounces > 8) { fprintf(stderr, "--guide-bounces must be a whole number in 0 .. 8, not '%s'.\n", t); return 1; }
-        }
-        else if (a == "--robust") {
-            const char *t = val("robust");
-            char *e = nullptr;
-            robust_k = strtoll(t, &e, 10);
-            if (e == t || *e || robust_k < 3 || robust_k > 15 || !(robust_k & 1)) { fprintf(stderr, "--robust must be an odd number of buckets in 3 .. 15, not '%s'.\n", t); return 1; }
-        } else if (a == "--robust-image") robust_png = val("robust-image");
+            if (!whole("--guide-bounces", val("guide-bounces"), 0, 8, 1, "a whole number in 0 .. 8", &o.guide_bounces)) return 1;
+        } else if (a == "--robust") {
+            if (!whole("--robust", val("robust"), 3, 15, 2, "an odd number of buckets in 3 .. 15", &o.robust_k)) return 1;
+        } else if (a == "--robust-image") o.robust_png = val("robust-image");
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
-    if (batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
-    if (launch < 0) { fprintf(stderr, "--launch must be at least 1 (or 0: automatic).\n"); return 1; }
-    if (inflight < 1) { fprintf(stderr, "--inflight must be at least 1.\n"); return 1; }
-    if (width == 0 || height == 0) { fprintf(stderr, "width and height must be positive.\n"); return 1; }
-    if (gpus < 1) { fprintf(stderr, "--gpus must be at least 1.\n"); return 1; }
-    const bool counts = have_adaptive || !sample_png.empty();   // hr_set_option "sample_counts"
-    if (counts) {
-        size_t ids = gpu_ids.empty() ? 0 : 1;
-        for (char ch : gpu_ids) ids += ch == ',';
-        if (gpus > 1 || ids > 1) {
-            fprintf(stderr, "--adaptive / --sample-image render on one device: the library can shard an adaptive render (masks and additive counts), this program's device loop does not.\n");
-            return 1;
-        }
-        if (have_adaptive && have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
-        if (debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
+    if (o.batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
+    if (o.launch < 0) { fprintf(stderr, "--launch must be at least 1 (or 0: automatic).\n"); return 1; }
+    if (o.inflight < 1) { fprintf(stderr, "--inflight must be at least 1.\n"); return 1; }
+    if (o.width == 0 || o.height == 0) { fprintf(stderr, "width and height must be positive.\n"); return 1; }
+    if (o.gpus < 1) { fprintf(stderr, "--gpus must be at least 1.\n"); return 1; }
+    o.counts = o.have_adaptive || !o.sample_png.empty();
+    if (o.counts) {
+        if (!one_device(o, "--adaptive / --sample-image render on one device: the library can shard an adaptive render (masks and additive counts), this program's device loop does not.")) return 1;
+        if (o.have_adaptive && o.have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
+        if (o.debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
     }
-    if (denoise_levels >= 0 && !denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
-    if (guide_bounces >= 0 && !denoise && guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
-    if (denoise || !guide_prefix.empty()) {
-        size_t ids = gpu_ids.empty() ? 0 : 1;
-        for (char ch : gpu_ids) ids += ch == ',';
-        if (gpus > 1 || ids > 1) {
-            fprintf(stderr, "--denoise / --guide-image render on one device: the library denoises one context's accumulator, moments and counts (a sharded host sums them into one), this program's device loop does not.\n");
-            return 1;
-        }
-        if (debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
+    if (o.denoise_levels >= 0 && !o.denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
+    if (o.guide_bounces >= 0 && !o.denoise && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
+    if (o.denoise || !o.guide_prefix.empty()) {
+        if (!one_device(o, "--denoise / --guide-image render on one device: the library denoises one context's accumulator, moments and counts (a sharded host sums them into one), this program's device loop does not.")) return 1;
+        if (o.debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
     }
-    if (!robust_png.empty() && !robust_k) { fprintf(stderr, "--robust-image needs --robust.\n"); return 1; }
-    if (robust_k) {
-        size_t ids = gpu_ids.empty() ? 0 : 1;
-        for (char ch : gpu_ids) ids += ch == ',';
-        if (gpus > 1 || ids > 1) {
-            fprintf(stderr, "--robust renders on one device: buckets of several devices add up only when each rendered a multiple of K samplings, and this program's device loop does not see to that.\n");
-            return 1;
-        }
-        if (denoise) { fprintf(stderr, "--robust cannot be combined with --denoise (the filter reads the raw moments, not the robust radiance: two final images).\n"); return 1; }
-        if (debug) { fprintf(stderr, "--robust cannot be combined with --debug (the debug renderer has no samplings to put into buckets).\n"); return 1; }
+    if (!o.robust_png.empty() && !o.robust_k) { fprintf(stderr, "--robust-image needs --robust.\n"); return 1; }
+    if (o.robust_k) {
+        if (!one_device(o, "--robust renders on one device: buckets of several devices add up only when each rendered a multiple of K samplings, and this program's device loop does not see to that.")) return 1;
+        if (o.denoise) { fprintf(stderr, "--robust cannot be combined with --denoise (the filter reads the raw moments, not the robust radiance: two final images).\n"); return 1; }
+        if (o.debug) { fprintf(stderr, "--robust cannot be combined with --debug (the debug renderer has no samplings to put into buckets).\n"); return 1; }
     }
-    const bool moments = have_target || !noise_png.empty() || have_adaptive || denoise;   // hr_set_option "moments"
-    if (moments && debug) { fprintf(stderr, "--noise-target / --noise-image cannot be combined with --debug (the debug renderer has no samplings to measure).\n"); return 1; }
-    const double noise_e = have_adaptive ? adaptive_e : have_target && noise_target > 0.0 ? noise_target : (have_target ? 0.0 : 0.05);   // the threshold of "above" and of the grey map
-    // --region X,Y,W,H: four unsigned integers, a non-empty window inside the frame (hr_set_region's rule, checked before any device is opened)
-    uint32_t region[4] = {0, 0, width, height};
-    bool has_region = false;
-    if (!region_arg.empty()) {
-        uint64_t v[4];
-        int n = 0;
-        for (const char *p = region_arg.c_str(); n < 4; n++) {
-            if (*p < '0' || *p > '9') break;
-            char *e = nullptr;
-            v[n] = strtoull(p, &e, 10);
-            if (v[n] > 0xffffffffull) break;
-            p = e;
-            if (n < 3 && *p++ != ',') break;
-            if (n == 3 && *p) break;
-        }
-        if (n != 4) { fprintf(stderr, "--region must be X,Y,W,H (four unsigned integers), not '%s'.\n", region_arg.c_str()); return 1; }
-        if (!v[2] || !v[3] || v[0] > width || v[2] > width - v[0] || v[1] > height || v[3] > height - v[1]) {
-            fprintf(stderr, "--region %s: the window must be non-empty and lie inside the %ux%u frame.\n", region_arg.c_str(), width, height);
-            return 1;
-        }
-        for (int k = 0; k < 4; k++) region[k] = (uint32_t)v[k];
-        has_region = region[2] != width || region[3] != height;   // the whole frame as a region is no region
+    o.moments = o.have_target || !o.noise_png.empty() || o.have_adaptive || o.denoise;
+    if (o.moments && o.debug) { fprintf(stderr, "--noise-target / --noise-image cannot be combined with --debug (the debug renderer has no samplings to measure).\n"); return 1; }
+    o.noise_e = o.have_adaptive ? o.adaptive_e : o.have_target && o.noise_target > 0.0 ? o.noise_target : (o.have_target ? 0.0 : 0.05);
+    o.region[2] = o.width, o.region[3] = o.height;
+    if (!o.region_arg.empty()) {
+        if (!parse_region(o.region_arg.c_str(), o.width, o.height, o.region)) return 1;
+        o.has_region = o.region[2] != o.width || o.region[3] != o.height;   // the whole frame as a region is no region
     }
-    const uint32_t out_w = region[2], out_h = region[3];   // the accumulator and the images: the region's
-    if (assets.empty()) {
+    o.out_w = o.region[2], o.out_h = o.region[3];
+    if (o.assets.empty()) {
         FILE *probe = fopen("assets/models/box.obj", "rb");
-        if (probe) { fclose(probe); assets = "assets"; } else assets = ".";
+        if (probe) { fclose(probe); o.assets = "assets"; } else o.assets = ".";
     }
-    setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);   // dmabuf IPC (RCCL on this driver), unless the caller says otherwise; before the HIP runtime starts
-    g_log = fopen("result.txt", "w");
-    double total_begin = now_sec();
-    tee("num threads: %d.", 1);  // main.rs:1261 prints rayon's pool size; here: one host thread drives one GPU
-    tee("resolution: %ux%u.", width, height);
-    if (has_region) tee("region: %u,%u %ux%u.", region[0], region[1], out_w, out_h);
-    tee("max sampling: %ux%u spp.", sampling, 4u);
-    tee("time limit: %.2f sec.", time_limit);
-    tee("report interval: %.2f sec.", interval);
+    return -1;
+}
 
-    double init_begin = now_sec();
+static int write_png(const std::string &path, const uint8_t *rgb, uint32_t w, uint32_t h) {
+    if (hh_write_png_rgb8(path.c_str(), rgb, w, h) == 0) return 0;
+    fprintf(stderr, "png: %s\n", hh_last_error());
+    return 1;
+}
+// One value per pixel, in 0 .. 1 (the caller clamps where its values can leave that range), as an 8-bit grey PNG: v * 255 + 0.5, cut off, in
+// the arithmetic of the values' own type (the depth plane's are floats, the others doubles).
+template <class F> static int write_grey(const std::string &path, uint32_t w, uint32_t h, F value) {
+    using T = decltype(value((size_t)0));
+    std::vector<uint8_t> grey((size_t)w * h * 3);
+    for (size_t i = 0; i < (size_t)w * h; i++) grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = (uint8_t)(value(i) * (T)255.0 + (T)0.5);
+    return write_png(path, grey.data(), w, h);
+}
+
+// One render: the devices, what has been rendered so far, and main's steps in their order.  Every step returns 0 or the exit status.
+struct Run {
+    const Options &o;
+    uint32_t sampling;          // the render loop's limit: -s (0 once --debug has rendered its one image)
+    uint32_t scene_hash = 2166136261u;   // FNV-1a of the scene name, for the checkpoint's header
+    double total_begin = now_sec();
     hh_scene *scene = nullptr;
-    if (hh_scene_create(scene_name.c_str(), assets.c_str(), &scene) != 0) { fprintf(stderr, "scene: %s\n", hh_last_error()); return 1; }
+    std::vector<hr_ctx *> ctxs;
+    hr_ctx *ctx = nullptr;      // device 0: it resolves the images
+    uint32_t ndev = 0;
+    bool host_sum = false;
+    std::vector<float> sum_acc, part;
+    bool have_guides = false;   // the context holds guide planes (for --guide-image)
+    bool final_image = false;   // set by whoever writes the render's last image: --denoise filters that one only
+    std::vector<double> mom_tot, mom_part, mom_own;
+    hr_noise noise_last;
+    bool noise_known = false;
+    std::vector<uint8_t> rgb;
+    double begin = 0.0, last_progress = 0.0, last_image = 0.0;
+    uint32_t counter = 0, sampled = 0;
+    std::string last_png;       // the image file save() wrote last: result.png is a copy of the final one (one PNG encode, not two)
+    uint32_t first = 1;
+    bool resumed_counts = false;   // --resume restored per-pixel counts: the tiles are chosen again before anything is rendered
+
+    explicit Run(const Options &opt) : o(opt), sampling(opt.sampling) {
+        for (char ch : o.scene_name) scene_hash = (scene_hash ^ (uint8_t)ch) * 16777619u;
+    }
+    // main's steps, in its order
+    void print_settings() const;
+    int open_devices();
+    int resume();
+    int render();
+    int write_checkpoint();
+    int write_result_png();
+    int write_reports();
+    void close();
+    // what the steps share
+    int combine();
+    int resolve(uint32_t s, uint8_t *out);
+    int noise_query(hr_noise *est, double *img, std::vector<double> *tot_out, uint64_t *n_out);
+    int noise_check_now();
+    int save(uint32_t s);
+};
+
+void Run::print_settings() const {
+    tee("num threads: %d.", 1);  // main.rs:1261 prints rayon's pool size; here: one host thread drives one GPU
+    tee("resolution: %ux%u.", o.width, o.height);
+    if (o.has_region) tee("region: %u,%u %ux%u.", o.region[0], o.region[1], o.out_w, o.out_h);
+    tee("max sampling: %ux%u spp.", o.sampling, 4u);
+    tee("time limit: %.2f sec.", o.time_limit);
+    tee("report interval: %.2f sec.", o.interval);
+}
+
+int Run::open_devices() {
+    double init_begin = now_sec();
+    if (hh_scene_create(o.scene_name.c_str(), o.assets.c_str(), &scene) != 0) { fprintf(stderr, "scene: %s\n", hh_last_error()); return 1; }
     // devices: samplings are independent and seeded by index, so device r of N renders samplings first + r, first + r + N, ...
     // (bench.py does the same with one process per GPU and an RCCL all-reduce)
     std::vector<int> devices;
-    if (!gpu_ids.empty()) {
-        for (size_t p = 0; p < gpu_ids.size();) {
-            size_t q = gpu_ids.find(',', p);
-            devices.push_back(atoi(gpu_ids.substr(p, q == std::string::npos ? std::string::npos : q - p).c_str()));
+    if (!o.gpu_ids.empty()) {
+        for (size_t p = 0; p < o.gpu_ids.size();) {
+            size_t q = o.gpu_ids.find(',', p);
+            devices.push_back(atoi(o.gpu_ids.substr(p, q == std::string::npos ? std::string::npos : q - p).c_str()));
             if (q == std::string::npos) break;
             p = q + 1;
         }
     } else {
-        for (int d = 0; d < (gpus > 0 ? gpus : 1); d++) devices.push_back(d);
+        for (int d = 0; d < (o.gpus > 0 ? o.gpus : 1); d++) devices.push_back(d);
     }
-    const uint32_t ndev = (uint32_t)devices.size();
-    std::vector<hr_ctx *> ctxs(ndev, nullptr);
+    ndev = (uint32_t)devices.size();
+    ctxs.assign(ndev, nullptr);
     for (uint32_t r = 0; r < ndev; r++) {
         CHECK_HR(hr_create(devices[r], &ctxs[r]));
         CHECK_HR(hr_upload_scene(ctxs[r], hh_scene_desc(scene)));
-        CHECK_HR(hr_set_resolution(ctxs[r], width, height));
-        if (has_region) CHECK_HR(hr_set_region(ctxs[r], region[0], region[1], out_w, out_h));
-        if (precise >= 0) CHECK_HR(hr_set_option(ctxs[r], "precise_shading", (double)precise));
-        if (moments) CHECK_HR(hr_set_option(ctxs[r], "moments", 1.0));
-        if (counts) CHECK_HR(hr_set_option(ctxs[r], "sample_counts", 1.0));
-        if (guide_bounces >= 0) CHECK_HR(hr_set_option(ctxs[r], "guide_bounces", (double)guide_bounces));
-        if (robust_k) CHECK_HR(hr_set_option(ctxs[r], "robust_buckets", (double)robust_k));
+        CHECK_HR(hr_set_resolution(ctxs[r], o.width, o.height));
+        if (o.has_region) CHECK_HR(hr_set_region(ctxs[r], o.region[0], o.region[1], o.out_w, o.out_h));
+        if (o.precise >= 0) CHECK_HR(hr_set_option(ctxs[r], "precise_shading", (double)o.precise));
+        if (o.moments) CHECK_HR(hr_set_option(ctxs[r], "moments", 1.0));
+        if (o.counts) CHECK_HR(hr_set_option(ctxs[r], "sample_counts", 1.0));
+        if (o.guide_bounces >= 0) CHECK_HR(hr_set_option(ctxs[r], "guide_bounces", (double)o.guide_bounces));
+        if (o.robust_k) CHECK_HR(hr_set_option(ctxs[r], "robust_buckets", (double)o.robust_k));
     }
-    hr_ctx *ctx = ctxs[0];
+    ctx = ctxs[0];
     if (ndev > 1) tee("devices: %u.", ndev);
     tee("init scene: %.2f sec.", now_sec() - init_begin);
     // The image needs the sum of all devices' accumulators: ONE all-reduce over RCCL (hr_allreduce_accumulators — the sum lands
@@ -325,206 +388,177 @@ int main(int argc, char **argv) {
     // hr_read_accumulator on device 0 then see the total (renderer.rs:64-90 runs after the sum).
     // A multi-GPU box whose RCCL cannot be loaded (hr_comm_init_local: HR_ERR_UNSUPPORTED) still renders: the host then sums the
     // devices' accumulators itself when an image or a checkpoint is written (`sum_acc` below) — slower, same result.
-    bool host_sum = false;
     if (ndev > 1) {
         int rc = hr_comm_init_local(ctxs.data(), (int)ndev);
         if (rc == HR_ERR_UNSUPPORTED) { host_sum = true; tee("no RCCL (%s): accumulators are summed on the host.", hr_last_error()); }
         else if (rc != 0) { fprintf(stderr, "hr_comm_init_local: %s\n", hr_last_error()); return 1; }
     }
-    std::vector<float> sum_acc, part;
-    auto combine = [&]() -> int {
-        if (ndev == 1) return 0;
-        if (!host_sum) return hr_allreduce_accumulators(ctxs.data(), (int)ndev) != 0;
-        sum_acc.resize((size_t)out_w * out_h * 3);
-        part.resize(sum_acc.size());
-        if (hr_read_accumulator(ctxs[0], sum_acc.data()) != 0) return 1;
-        for (uint32_t r = 1; r < ndev; r++) {
-            if (hr_read_accumulator(ctxs[r], part.data()) != 0) return 1;
-            for (size_t i = 0; i < sum_acc.size(); i++) sum_acc[i] += part[i];
-        }
-        return 0;
-    };
-    // host-side sum: device 0 resolves the total from its accumulator, then gets its own partial sums back
-    bool have_guides = false;   // the context holds guide planes (for --guide-image)
-    bool final_image = false;   // set by whoever writes the render's last image: --denoise filters that one only
-    auto resolve = [&](uint32_t s, uint8_t *out) -> int {
-        if (robust_k) return hr_robust(ctx) != 0 ? 1 : hr_resolve_robust(ctx, out);   // (one device, no --denoise: checked with the flags)
-        if (denoise && final_image) {
-            hr_denoise_params dp;
-            if (hr_denoise_default_params(&dp) != 0) return 1;
-            if (denoise_levels >= 0) dp.levels = (uint32_t)denoise_levels;
-            const int rc = hr_denoise(ctx, &dp);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings — the flags' values were checked when they were read)
-            if (rc == 0) { have_guides = true; return hr_resolve_denoised(ctx, out); }   // (hr_denoise rendered the guide planes, nothing has dropped them since)
-            if (rc != HR_ERR_INVALID) return rc;
-            tee("denoise: fewer than 2 samplings behind a pixel, the image is not denoised.");
-        }
-        if (have_adaptive) return hr_resolve_counted(ctx, out);   // every pixel with its own count (one device: checked with the flags)
-        if (!host_sum) return hr_resolve(ctx, s, out);
-        if (hr_read_accumulator(ctx, part.data()) != 0 || hr_write_accumulator(ctx, sum_acc.data()) != 0) return 1;
-        int rc = hr_resolve(ctx, s, out);
-        return hr_write_accumulator(ctx, part.data()) != 0 ? 1 : rc;
-    };
+    rgb.resize((size_t)o.out_w * o.out_h * 3);
+    begin = last_progress = last_image = now_sec();
+    return 0;
+}
 
-    // The noise estimate of everything rendered so far.  Several devices: every device holds the moments of its own samplings; they are
-    // additive, so the host adds them in rank order (as sum_acc does for accumulators without RCCL), device 0 estimates the total and gets
-    // its own moments back.  tot_out / n_out: the summed moments and their count as well (for the checkpoint).
-    // Returns 0, 1 = error, 2 = fewer than two samplings behind the moments (no variance yet).
-    std::vector<double> mom_tot, mom_part, mom_own;
-    auto noise_query = [&](hr_noise *est, double *img, std::vector<double> *tot_out, uint64_t *n_out) -> int {
-        uint64_t n_own = 0, n_tot = 0;
-        const size_t len = (size_t)out_w * out_h * 6;
-        if (ndev > 1 || tot_out) {
-            mom_tot.resize(len);
-            if (hr_read_moments(ctx, mom_tot.data(), &n_own) != 0) return 1;
-            n_tot = n_own;
-        }
-        if (ndev > 1) {
-            mom_own = mom_tot;
-            mom_part.resize(len);
-            for (uint32_t r = 1; r < ndev; r++) {
-                uint64_t n_r = 0;
-                if (hr_read_moments(ctxs[r], mom_part.data(), &n_r) != 0) return 1;
-                for (size_t i = 0; i < len; i++) mom_tot[i] += mom_part[i];
-                n_tot += n_r;
-            }
-            if (hr_write_moments(ctx, mom_tot.data(), n_tot) != 0) return 1;
-        }
-        memset(est, 0, sizeof *est);
-        int rc = hr_noise_estimate(ctx, noise_floor, noise_e, est);   // (HR_ERR_INVALID: n < 2 — floor and threshold were checked with the flags)
-        if (rc == 0 && img) rc = hr_read_noise_image(ctx, noise_floor, img);
-        if (ndev > 1 && hr_write_moments(ctx, mom_own.data(), n_own) != 0) return 1;
-        if (tot_out) *tot_out = mom_tot;
-        if (n_out) *n_out = n_tot;
-        return rc == 0 ? 0 : (rc == HR_ERR_INVALID ? 2 : 1);
-    };
-    hr_noise noise_last;
-    bool noise_known = false;
-    // one "noise:" line per check, after the "rendering:" lines of the samplings it covers
-    auto noise_check_now = [&]() -> int {
-        int rc = noise_query(&noise_last, nullptr, nullptr, nullptr);
-        if (rc == 1) { fprintf(stderr, "hr_noise_estimate: %s\n", hr_last_error()); return 1; }
-        noise_known = rc == 0;
-        if (noise_known) printf("noise: samplings=%llu mean=%.9g max=%.9g above=%llu\n", (unsigned long long)noise_last.samplings, noise_last.mean_error, noise_last.max_error,
-                                (unsigned long long)noise_last.pixels_above);
-        return 0;
-    };
-    std::vector<uint8_t> rgb((size_t)out_w * out_h * 3);
-    double begin = now_sec(), last_progress = begin, last_image = begin;
-    uint32_t counter = 0, sampled = 0;
-    std::string last_png;     // the image file save() wrote last: result.png is a copy of the final one (one PNG encode, not two)
-    auto save = [&](uint32_t s) -> int {
-        char path[32];
-        snprintf(path, sizeof path, "%03u.png", counter);
-        double t0 = now_sec();
-        if (combine() || resolve(s, rgb.data()) != 0) { fprintf(stderr, "hr_resolve: %s\n", hr_last_error()); return 1; }
-        printf("update_imgbuf: %.3f sec\n", now_sec() - t0);
-        last_png = path;
-        return hh_write_png_rgb8(path, rgb.data(), out_w, out_h);
-    };
-    uint32_t first = 1;
-    // checkpoint = {magic, width, height, samplings done, FNV-1a of the scene name} + the fp32 accumulator; with a region the magic is
-    // "HRR2" and the header goes on with {x0, y0, w, h}, the accumulator is the region's (a full-frame checkpoint keeps the "HRA2" format)
-    const uint32_t CKPT_MAGIC = 0x32415248u;          // "HRA2"
-    const uint32_t CKPT_REGION_MAGIC = 0x32525248u;   // "HRR2"
-    const uint32_t CKPT_MOMENTS_MAGIC = 0x534d5248u;  // "HRMS": the trailer behind the accumulator of a render with moments on
-    const uint32_t CKPT_COUNTS_MAGIC = 0x43535248u;   // "HRSC": the trailer behind that of a render with sample counts on — w*h uint32
-    const uint32_t CKPT_BUCKETS_MAGIC = 0x4b425248u;  // "HRBK": the trailer behind those of a render with --robust — K (uint32), samplings (uint64), w*h*3K doubles
-    bool resumed_counts = false;                      // --resume restored per-pixel counts: the tiles are chosen again before anything is rendered
-    uint32_t scene_hash = 2166136261u;
-    for (char ch : scene_name) scene_hash = (scene_hash ^ (uint8_t)ch) * 16777619u;
-    if (!ckpt_in.empty()) {
-        FILE *f = fopen(ckpt_in.c_str(), "rb");
-        uint32_t hdr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        std::vector<float> acc((size_t)out_w * out_h * 3);
-        bool ok = f && fread(hdr, 4, 5, f) == 5 && (hdr[0] == CKPT_MAGIC || hdr[0] == CKPT_REGION_MAGIC);
-        if (ok && (hdr[0] == CKPT_REGION_MAGIC) != has_region) {
-            if (f) fclose(f);
-            fprintf(stderr, "cannot resume from %s: %s\n", ckpt_in.c_str(), has_region ? "it is a full-frame checkpoint and --region is given" : "it is a region checkpoint and no --region is given");
-            return 1;
-        }
-        if (ok && has_region) {
-            ok = fread(hdr + 5, 4, 4, f) == 4;
-            if (ok && (hdr[5] != region[0] || hdr[6] != region[1] || hdr[7] != out_w || hdr[8] != out_h)) {
-                fclose(f);
-                fprintf(stderr, "cannot resume from %s: its region is %u,%u,%u,%u, --region is %u,%u,%u,%u\n", ckpt_in.c_str(), hdr[5], hdr[6], hdr[7], hdr[8],
-                        region[0], region[1], out_w, out_h);
-                return 1;
-            }
-        }
-        ok = ok && hdr[1] == width && hdr[2] == height && hdr[4] == scene_hash && fread(acc.data(), sizeof(float), acc.size(), f) == acc.size();
-        // a checkpoint written with moments on goes on with the trailer {"HRMS", samplings behind the moments, w*h*6 doubles}
-        uint32_t mmagic = 0;
-        uint64_t mom_n = 0;
-        std::vector<double> mom;
-        bool have_mom = false;
-        std::vector<uint32_t> cnt;
-        if (ok && (moments || counts || robust_k) && fread(&mmagic, 4, 1, f) == 1 && mmagic == CKPT_MOMENTS_MAGIC) {
-            mom.resize((size_t)out_w * out_h * 6);
-            have_mom = fread(&mom_n, 8, 1, f) == 1 && fread(mom.data(), sizeof(double), mom.size(), f) == mom.size();
-            if (have_mom && fread(&mmagic, 4, 1, f) != 1) mmagic = 0;   // what follows the moments
-            have_mom = have_mom && moments;
-        }
-        if (ok && counts) {
-            // {"HRSC", w*h uint32}; a file without it was rendered uniformly: every pixel has received all of its samplings
-            cnt.assign((size_t)out_w * out_h, hdr[3]);
-            if (mmagic == CKPT_COUNTS_MAGIC) {
-                resumed_counts = fread(cnt.data(), sizeof(uint32_t), cnt.size(), f) == cnt.size();
-                ok = resumed_counts;
-                if (ok && fread(&mmagic, 4, 1, f) != 1) mmagic = 0;   // what follows the counts
-            }
-        }
-        // {"HRBK", K, samplings behind the buckets, w*h*3K doubles}
-        std::vector<double> bkt;
-        uint32_t bkt_k = 0;
-        uint64_t bkt_n = 0;
-        const char *bkt_why = nullptr;
-        if (ok && robust_k) {
-            if (!counts && mmagic == CKPT_COUNTS_MAGIC) bkt_why = "its buckets were filled by per-pixel sampling counts (resume with --adaptive or --sample-image as well)";
-            else if (mmagic != CKPT_BUCKETS_MAGIC || fread(&bkt_k, 4, 1, f) != 1 || fread(&bkt_n, 8, 1, f) != 1) bkt_why = "it holds no sample buckets (it was written without --robust)";
-            else if (bkt_k != (uint32_t)robust_k) bkt_why = "its sample buckets were kept with another K";
-            else {
-                bkt.resize((size_t)out_w * out_h * 3 * bkt_k);
-                ok = fread(bkt.data(), sizeof(double), bkt.size(), f) == bkt.size();
-            }
-        }
-        if (f) fclose(f);
-        if (!ok) { fprintf(stderr, "cannot resume from %s (missing, wrong magic, resolution or scene)\n", ckpt_in.c_str()); return 1; }
-        if (bkt_why) {
-            fprintf(stderr, "--resume %s with --robust %lld: %s; resume without --robust, or render again with it.\n", ckpt_in.c_str(), robust_k, bkt_why);
-            return 1;
-        }
-        if (have_adaptive && !have_mom) {
-            fprintf(stderr, "--resume %s with --adaptive: the checkpoint holds no sample moments (it was written without --adaptive / --noise-target / --noise-image), "
-                            "so the noise of its %u samplings cannot be known; resume without --adaptive, or render again with it.\n", ckpt_in.c_str(), hdr[3]);
-            return 1;
-        }
-        if (have_adaptive && !resumed_counts && mom_n != hdr[3]) {
-            fprintf(stderr, "--resume %s with --adaptive: its sample moments cover %llu of its %u samplings and it holds no per-pixel counts, "
-                            "so the noise of its pixels cannot be known; resume without --adaptive, or render again with it.\n", ckpt_in.c_str(), (unsigned long long)mom_n, hdr[3]);
-            return 1;
-        }
-        if (denoise && !(have_mom && (resumed_counts || mom_n == hdr[3]))) {
-            // the filter's mean is accumulator / (4 n) with n the samplings behind the moments (or the pixel's count): moments that do not cover
-            // every sampling of the accumulator would give an image of the wrong brightness
-            fprintf(stderr, "--resume %s with --denoise: the checkpoint's sample moments %s, so the variance of its %u samplings cannot be known; "
-                            "resume without --denoise, or render again with it.\n", ckpt_in.c_str(),
-                    have_mom ? "do not cover all of its samplings" : "are missing (it was written without --denoise / --adaptive / --noise-target / --noise-image)", hdr[3]);
-            return 1;
-        }
-        if (have_target && !have_mom) {
-            fprintf(stderr, "--resume %s with --noise-target: the checkpoint holds no sample moments (it was written without --noise-target / --noise-image), "
-                            "so the noise of its %u samplings cannot be known; resume without --noise-target, or render again with it.\n", ckpt_in.c_str(), hdr[3]);
-            return 1;
-        }
-        CHECK_HR(hr_write_accumulator(ctx, acc.data()));
-        if (counts) CHECK_HR(hr_write_sample_counts(ctx, cnt.data()));
-        if (have_mom) CHECK_HR(hr_write_moments(ctx, mom.data(), mom_n));
-        else if (moments) printf("the checkpoint holds no sample moments: the noise image covers the samplings rendered from here on\n");
-        if (robust_k) CHECK_HR(hr_write_buckets(ctx, bkt.data(), bkt_n));
-        first = hdr[3] + 1;
-        sampled = hdr[3];
-        printf("resumed at %ux4 sampled\n", hdr[3]);
+int Run::combine() {
+    if (ndev == 1) return 0;
+    if (!host_sum) return hr_allreduce_accumulators(ctxs.data(), (int)ndev) != 0;
+    sum_acc.resize((size_t)o.out_w * o.out_h * 3);
+    part.resize(sum_acc.size());
+    if (hr_read_accumulator(ctxs[0], sum_acc.data()) != 0) return 1;
+    for (uint32_t r = 1; r < ndev; r++) {
+        if (hr_read_accumulator(ctxs[r], part.data()) != 0) return 1;
+        for (size_t i = 0; i < sum_acc.size(); i++) sum_acc[i] += part[i];
     }
+    return 0;
+}
+// host-side sum: device 0 resolves the total from its accumulator, then gets its own partial sums back
+int Run::resolve(uint32_t s, uint8_t *out) {
+    if (o.robust_k) return hr_robust(ctx) != 0 ? 1 : hr_resolve_robust(ctx, out);   // (one device, no --denoise: checked with the flags)
+    if (o.denoise && final_image) {
+        hr_denoise_params dp;
+        if (hr_denoise_default_params(&dp) != 0) return 1;
+        if (o.denoise_levels >= 0) dp.levels = (uint32_t)o.denoise_levels;
+        const int rc = hr_denoise(ctx, &dp);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings — the flags' values were checked when they were read)
+        if (rc == 0) { have_guides = true; return hr_resolve_denoised(ctx, out); }   // (hr_denoise rendered the guide planes, nothing has dropped them since)
+        if (rc != HR_ERR_INVALID) return rc;
+        tee("denoise: fewer than 2 samplings behind a pixel, the image is not denoised.");
+    }
+    if (o.have_adaptive) return hr_resolve_counted(ctx, out);   // every pixel with its own count (one device: checked with the flags)
+    if (!host_sum) return hr_resolve(ctx, s, out);
+    if (hr_read_accumulator(ctx, part.data()) != 0 || hr_write_accumulator(ctx, sum_acc.data()) != 0) return 1;
+    int rc = hr_resolve(ctx, s, out);
+    return hr_write_accumulator(ctx, part.data()) != 0 ? 1 : rc;
+}
+
+// The noise estimate of everything rendered so far.  Several devices: every device holds the moments of its own samplings; they are
+// additive, so the host adds them in rank order (as sum_acc does for accumulators without RCCL), device 0 estimates the total and gets
+// its own moments back.  tot_out / n_out: the summed moments and their count as well (for the checkpoint).
+// Returns 0, 1 = error, 2 = fewer than two samplings behind the moments (no variance yet).
+int Run::noise_query(hr_noise *est, double *img, std::vector<double> *tot_out, uint64_t *n_out) {
+    uint64_t n_own = 0, n_tot = 0;
+    const size_t len = (size_t)o.out_w * o.out_h * 6;
+    if (ndev > 1 || tot_out) {
+        mom_tot.resize(len);
+        if (hr_read_moments(ctx, mom_tot.data(), &n_own) != 0) return 1;
+        n_tot = n_own;
+    }
+    if (ndev > 1) {
+        mom_own = mom_tot;
+        mom_part.resize(len);
+        for (uint32_t r = 1; r < ndev; r++) {
+            uint64_t n_r = 0;
+            if (hr_read_moments(ctxs[r], mom_part.data(), &n_r) != 0) return 1;
+            for (size_t i = 0; i < len; i++) mom_tot[i] += mom_part[i];
+            n_tot += n_r;
+        }
+        if (hr_write_moments(ctx, mom_tot.data(), n_tot) != 0) return 1;
+    }
+    memset(est, 0, sizeof *est);
+    int rc = hr_noise_estimate(ctx, o.noise_floor, o.noise_e, est);   // (HR_ERR_INVALID: n < 2 — floor and threshold were checked with the flags)
+    if (rc == 0 && img) rc = hr_read_noise_image(ctx, o.noise_floor, img);
+    if (ndev > 1 && hr_write_moments(ctx, mom_own.data(), n_own) != 0) return 1;
+    if (tot_out) *tot_out = mom_tot;
+    if (n_out) *n_out = n_tot;
+    return rc == 0 ? 0 : (rc == HR_ERR_INVALID ? 2 : 1);
+}
+// one "noise:" line per check, after the "rendering:" lines of the samplings it covers
+int Run::noise_check_now() {
+    int rc = noise_query(&noise_last, nullptr, nullptr, nullptr);
+    if (rc == 1) { fprintf(stderr, "hr_noise_estimate: %s\n", hr_last_error()); return 1; }
+    noise_known = rc == 0;
+    if (noise_known) printf("noise: samplings=%llu mean=%.9g max=%.9g above=%llu\n", (unsigned long long)noise_last.samplings, noise_last.mean_error, noise_last.max_error,
+                            (unsigned long long)noise_last.pixels_above);
+    return 0;
+}
+int Run::save(uint32_t s) {
+    char path[32];
+    snprintf(path, sizeof path, "%03u.png", counter);
+    double t0 = now_sec();
+    if (combine() || resolve(s, rgb.data()) != 0) { fprintf(stderr, "hr_resolve: %s\n", hr_last_error()); return 1; }
+    printf("update_imgbuf: %.3f sec\n", now_sec() - t0);
+    last_png = path;
+    return hh_write_png_rgb8(path, rgb.data(), o.out_w, o.out_h);
+}
+
+// --resume: what this render demands of the file, and what it says when the file falls short (the sections themselves: checkpoint.h)
+int Run::resume() {
+    if (o.ckpt_in.empty()) return 0;
+    const char *path = o.ckpt_in.c_str();
+    const ckpt::File c = ckpt::read(path);
+    bool ok = c.magic == ckpt::FRAME || c.magic == ckpt::REGION;
+    if (ok && (c.magic == ckpt::REGION) != o.has_region) {
+        fprintf(stderr, "cannot resume from %s: %s\n", path, o.has_region ? "it is a full-frame checkpoint and --region is given" : "it is a region checkpoint and no --region is given");
+        return 1;
+    }
+    if (ok && o.has_region) {
+        ok = c.complete >= ckpt::S_HEADER;
+        if (ok && (c.region[0] != o.region[0] || c.region[1] != o.region[1] || c.region[2] != o.out_w || c.region[3] != o.out_h)) {
+            fprintf(stderr, "cannot resume from %s: its region is %u,%u,%u,%u, --region is %u,%u,%u,%u\n", path, c.region[0], c.region[1], c.region[2], c.region[3],
+                    o.region[0], o.region[1], o.out_w, o.out_h);
+            return 1;
+        }
+    }
+    ok = ok && c.width == o.width && c.height == o.height && c.scene_hash == scene_hash && c.complete >= ckpt::S_ACCUMULATOR;
+    // The trailers count only for a render that keeps what they hold; a trailer that is cut short hides whatever is behind it.
+    const bool have_mom = c.has_moments && o.moments;   // (moments that are cut short: as a file without them)
+    const uint64_t mom_n = c.moments_n;
+    std::vector<uint32_t> uniform;
+    if (ok && o.counts) {
+        // a file without counts was rendered uniformly: every pixel has received all of its samplings
+        resumed_counts = c.has_counts;
+        if (!resumed_counts) uniform.assign((size_t)o.out_w * o.out_h, c.samplings);
+        ok = c.cut != ckpt::S_COUNTS;
+    }
+    const char *bkt_why = nullptr;
+    if (ok && o.robust_k) {
+        if (!o.counts && (c.has_counts || c.cut == ckpt::S_COUNTS)) bkt_why = "its buckets were filled by per-pixel sampling counts (resume with --adaptive or --sample-image as well)";
+        else if (!c.buckets_head) bkt_why = "it holds no sample buckets (it was written without --robust)";
+        else if (c.buckets_k != (uint32_t)o.robust_k) bkt_why = "its sample buckets were kept with another K";
+        else ok = c.has_buckets;
+    }
+    if (!ok) { fprintf(stderr, "cannot resume from %s (missing, wrong magic, resolution or scene)\n", path); return 1; }
+    if (bkt_why) {
+        fprintf(stderr, "--resume %s with --robust %lld: %s; resume without --robust, or render again with it.\n", path, o.robust_k, bkt_why);
+        return 1;
+    }
+    if (o.have_adaptive && !have_mom) {
+        fprintf(stderr, "--resume %s with --adaptive: the checkpoint holds no sample moments (it was written without --adaptive / --noise-target / --noise-image), "
+                        "so the noise of its %u samplings cannot be known; resume without --adaptive, or render again with it.\n", path, c.samplings);
+        return 1;
+    }
+    if (o.have_adaptive && !resumed_counts && mom_n != c.samplings) {
+        fprintf(stderr, "--resume %s with --adaptive: its sample moments cover %llu of its %u samplings and it holds no per-pixel counts, "
+                        "so the noise of its pixels cannot be known; resume without --adaptive, or render again with it.\n", path, (unsigned long long)mom_n, c.samplings);
+        return 1;
+    }
+    if (o.denoise && !(have_mom && (resumed_counts || mom_n == c.samplings))) {
+        // the filter's mean is accumulator / (4 n) with n the samplings behind the moments (or the pixel's count): moments that do not cover
+        // every sampling of the accumulator would give an image of the wrong brightness
+        fprintf(stderr, "--resume %s with --denoise: the checkpoint's sample moments %s, so the variance of its %u samplings cannot be known; "
+                        "resume without --denoise, or render again with it.\n", path,
+                have_mom ? "do not cover all of its samplings" : "are missing (it was written without --denoise / --adaptive / --noise-target / --noise-image)", c.samplings);
+        return 1;
+    }
+    if (o.have_target && !have_mom) {
+        fprintf(stderr, "--resume %s with --noise-target: the checkpoint holds no sample moments (it was written without --noise-target / --noise-image), "
+                        "so the noise of its %u samplings cannot be known; resume without --noise-target, or render again with it.\n", path, c.samplings);
+        return 1;
+    }
+    CHECK_HR(hr_write_accumulator(ctx, c.acc.data()));
+    if (o.counts) CHECK_HR(hr_write_sample_counts(ctx, resumed_counts ? c.counts.data() : uniform.data()));
+    if (have_mom) CHECK_HR(hr_write_moments(ctx, c.moments.data(), mom_n));
+    else if (o.moments) printf("the checkpoint holds no sample moments: the noise image covers the samplings rendered from here on\n");
+    if (o.robust_k) CHECK_HR(hr_write_buckets(ctx, c.buckets.data(), c.buckets_n));
+    first = c.samplings + 1;
+    sampled = c.samplings;
+    printf("resumed at %ux4 sampled\n", c.samplings);
+    return 0;
+}
+
+int Run::render() {
+    const bool debug = o.debug, have_target = o.have_target, have_adaptive = o.have_adaptive;
+    const double time_limit = o.time_limit, interval = o.interval, noise_floor = o.noise_floor, noise_target = o.noise_target, adaptive_e = o.adaptive_e;
+    const uint32_t out_w = o.out_w, out_h = o.out_h;
+    const long long noise_check = o.noise_check;
     if (debug) {  // main.rs:1279-1281: DebugRenderer { mode: FocalPlane }, max_sampling 1, report_progress = update_imgbuf + stop
         CHECK_HR(hr_render_debug(ctx, 3));
         CHECK_HR(hr_synchronize(ctx));
@@ -553,8 +587,8 @@ int main(int argc, char **argv) {
     struct Launch { uint32_t begin, end; double issued; std::vector<uint64_t> ticket; };
     std::vector<Launch> q;     // issued, not yet reported; oldest first
     uint32_t next_s = first;
-    const uint32_t B = (uint32_t)batch;
-    uint32_t lrep = launch > 0 ? (uint32_t)launch : 0;   // reports per launch
+    const uint32_t B = (uint32_t)o.batch;
+    uint32_t lrep = o.launch > 0 ? (uint32_t)o.launch : 0;   // reports per launch
     if (!lrep) {   // as many reports as make the library's own automatic launch size (hanamaru_hip.h "batch": about 33 M paths) on every device
         const uint64_t per_sampling = ((uint64_t)(out_w + 3) / 4) * ((out_h + 3) / 4) * 64u;
         const uint64_t lsize = std::min<uint64_t>(64, std::max<uint64_t>(4, (33177600ull + per_sampling - 1) / per_sampling));
@@ -617,7 +651,7 @@ int main(int argc, char **argv) {
         return save(sampled);
     };
     // how many reports may be enqueued now?  (samplings left, room in the pipeline, and the time-limit rule asked for the moment they would finish)
-    const size_t depth = interval <= 0.0 ? 1 : (size_t)inflight;
+    const size_t depth = interval <= 0.0 ? 1 : (size_t)o.inflight;
     // --noise-target: nothing is issued beyond the sampling at which the next question is due (whole launches: the launch that
     // reaches it is not cut), so that a render that has reached its target stops there and not a pipeline's depth later
     // --adaptive asks at the same points: the tiles are chosen again, and the render ends when none is left.  Resumed with per-pixel counts it
@@ -681,129 +715,136 @@ int main(int argc, char **argv) {
         }
     }
     for (uint32_t r = 0; r < ndev; r++) CHECK_HR(hr_synchronize(ctxs[r]));
-    if (!ckpt_out.empty()) {
-        std::vector<float> acc((size_t)out_w * out_h * 3);
-        if (combine()) { fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
-        if (host_sum) acc = sum_acc;
-        else CHECK_HR(hr_read_accumulator(ctx, acc.data()));
-        uint32_t hdr[9] = {has_region ? CKPT_REGION_MAGIC : CKPT_MAGIC, width, height, sampled, scene_hash, region[0], region[1], out_w, out_h};
-        const size_t nhdr = has_region ? 9 : 5;
-        FILE *f = fopen(ckpt_out.c_str(), "wb");
-        bool ok = f && fwrite(hdr, 4, nhdr, f) == nhdr && fwrite(acc.data(), sizeof(float), acc.size(), f) == acc.size();
-        if (ok && moments) {   // the trailer; a file written without moments keeps the bytes it always had
-            hr_noise est;
-            std::vector<double> mom;
-            uint64_t mom_n = 0;
-            if (noise_query(&est, nullptr, &mom, &mom_n) == 1) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
-            ok = fwrite(&CKPT_MOMENTS_MAGIC, 4, 1, f) == 1 && fwrite(&mom_n, 8, 1, f) == 1 && fwrite(mom.data(), sizeof(double), mom.size(), f) == mom.size();
-        }
-        if (ok && counts) {   // behind the moments trailer (a render without moments: behind the accumulator)
-            std::vector<uint32_t> cnt((size_t)out_w * out_h);
-            if (hr_read_sample_counts(ctx, cnt.data()) != 0) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
-            ok = fwrite(&CKPT_COUNTS_MAGIC, 4, 1, f) == 1 && fwrite(cnt.data(), sizeof(uint32_t), cnt.size(), f) == cnt.size();
-        }
-        if (ok && robust_k) {   // behind every other trailer; a file written without --robust keeps the bytes it always had
-            std::vector<double> bkt((size_t)out_w * out_h * 3 * (size_t)robust_k);
-            uint64_t bkt_n = 0;
-            const uint32_t k32 = (uint32_t)robust_k;
-            if (hr_read_buckets(ctx, bkt.data(), &bkt_n) != 0) { fclose(f); fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
-            ok = fwrite(&CKPT_BUCKETS_MAGIC, 4, 1, f) == 1 && fwrite(&k32, 4, 1, f) == 1 && fwrite(&bkt_n, 8, 1, f) == 1 && fwrite(bkt.data(), sizeof(double), bkt.size(), f) == bkt.size();
-        }
-        if (f) fclose(f);
-        if (!ok) { fprintf(stderr, "cannot write checkpoint %s\n", ckpt_out.c_str()); return 1; }
+    return 0;
+}
+
+// --checkpoint: everything is read from the devices first, then written in one go; a file keeps the bytes it always had: the trailers
+// of what this render did not keep are not there
+int Run::write_checkpoint() {
+    if (o.ckpt_out.empty()) return 0;
+    ckpt::File c;
+    c.magic = o.has_region ? ckpt::REGION : ckpt::FRAME, c.width = o.width, c.height = o.height, c.samplings = sampled, c.scene_hash = scene_hash;
+    std::copy(o.region, o.region + 4, c.region);
+    c.has_moments = o.moments, c.has_counts = o.counts, c.has_buckets = o.robust_k != 0;
+    c.acc.resize((size_t)o.out_w * o.out_h * 3);
+    if (combine()) { fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
+    if (host_sum) c.acc = sum_acc;
+    else CHECK_HR(hr_read_accumulator(ctx, c.acc.data()));
+    if (c.has_moments) {
+        hr_noise est;
+        if (noise_query(&est, nullptr, &c.moments, &c.moments_n) == 1) { fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
     }
-    {   // main.rs:1217: result.png = the final image — the bytes finish() has just written as NNN.png
-        bool copied = false;
-        if (!last_png.empty()) {
-            FILE *in = fopen(last_png.c_str(), "rb"), *out = in ? fopen("result.png", "wb") : nullptr;
-            if (in && out) {
-                std::vector<char> buf(1 << 20);
-                size_t n;
-                copied = true;
-                while ((n = fread(buf.data(), 1, buf.size(), in)) > 0) copied = copied && fwrite(buf.data(), 1, n, out) == n;
-                copied = copied && !ferror(in);
-            }
-            if (in) fclose(in);
-            if (out) copied = (fclose(out) == 0) && copied;
-        }
-        if (!copied && hh_write_png_rgb8("result.png", rgb.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+    if (c.has_counts) {
+        c.counts.resize((size_t)o.out_w * o.out_h);
+        if (hr_read_sample_counts(ctx, c.counts.data()) != 0) { fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
     }
-    if (moments) {   // the estimate of the final image, to result.txt as well; and its map
-        std::vector<double> e_img(noise_png.empty() ? 0 : (size_t)out_w * out_h);
+    if (c.has_buckets) {
+        c.buckets_k = (uint32_t)o.robust_k;
+        c.buckets.resize((size_t)o.out_w * o.out_h * 3 * c.buckets_k);
+        if (hr_read_buckets(ctx, c.buckets.data(), &c.buckets_n) != 0) { fprintf(stderr, "checkpoint: %s\n", hr_last_error()); return 1; }
+    }
+    if (!ckpt::write(o.ckpt_out.c_str(), c)) { fprintf(stderr, "cannot write checkpoint %s\n", o.ckpt_out.c_str()); return 1; }
+    return 0;
+}
+
+// main.rs:1217: result.png = the final image — the bytes finish() has just written as NNN.png
+int Run::write_result_png() {
+    bool copied = false;
+    if (!last_png.empty()) {
+        FILE *in = fopen(last_png.c_str(), "rb"), *out = in ? fopen("result.png", "wb") : nullptr;
+        if (in && out) {
+            std::vector<char> buf(1 << 20);
+            size_t n;
+            copied = true;
+            while ((n = fread(buf.data(), 1, buf.size(), in)) > 0) copied = copied && fwrite(buf.data(), 1, n, out) == n;
+            copied = copied && !ferror(in);
+        }
+        if (in) fclose(in);
+        if (out) copied = (fclose(out) == 0) && copied;
+    }
+    return copied ? 0 : write_png("result.png", rgb.data(), o.out_w, o.out_h);
+}
+
+// what the render came to, to result.txt as well, and the maps of it that were asked for
+int Run::write_reports() {
+    const uint32_t out_w = o.out_w, out_h = o.out_h;
+    const size_t pixels = (size_t)out_w * out_h;
+    if (o.moments) {   // the estimate of the final image; and its map
+        std::vector<double> e_img(o.noise_png.empty() ? 0 : pixels);
         int rc = noise_query(&noise_last, e_img.empty() ? nullptr : e_img.data(), nullptr, nullptr);
         if (rc == 1) { fprintf(stderr, "hr_noise_estimate: %s\n", hr_last_error()); return 1; }
         if (rc == 2) tee("noise: fewer than 2 samplings, no estimate.");
         else tee("noise: samplings=%llu mean=%.9g max=%.9g above=%llu", (unsigned long long)noise_last.samplings, noise_last.mean_error, noise_last.max_error,
                  (unsigned long long)noise_last.pixels_above);
-        if (!noise_png.empty() && rc == 0) {   // grey map of min(1, e / E)
-            const double E = noise_e > 0.0 ? noise_e : 0.05;
-            std::vector<uint8_t> grey((size_t)out_w * out_h * 3);
-            for (size_t i = 0; i < e_img.size(); i++) {
-                const double t = e_img[i] / E;
-                const uint8_t v = (uint8_t)((t >= 1.0 ? 1.0 : (t > 0.0 ? t : 0.0)) * 255.0 + 0.5);
-                grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = v;
-            }
-            if (hh_write_png_rgb8(noise_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
-        }
+        const double E = o.noise_e > 0.0 ? o.noise_e : 0.05;   // grey map of min(1, e / E)
+        if (!o.noise_png.empty() && rc == 0 && write_grey(o.noise_png, out_w, out_h, [&](size_t i) { const double t = e_img[i] / E; return t >= 1.0 ? 1.0 : (t > 0.0 ? t : 0.0); })) return 1;
     }
-    if (!guide_prefix.empty()) {   // the guide planes as images of their own (the planes of --denoise's filter, or a pass of their own)
-        std::vector<float> g((size_t)out_w * out_h * 8);
+    if (!o.guide_prefix.empty()) {   // the guide planes as images of their own (the planes of --denoise's filter, or a pass of their own)
+        std::vector<float> g(pixels * 8);
         if (!have_guides) CHECK_HR(hr_render_guides(ctx));
         CHECK_HR(hr_read_guides(ctx, g.data()));
-        const size_t pixels = (size_t)out_w * out_h;
         float zmax = 0.0f;
         for (size_t i = 0; i < pixels; i++) zmax = std::max(zmax, g[i * 8 + 6]);
         auto byte = [](float v) { return (uint8_t)(std::min(1.0f, std::max(0.0f, v)) * 255.0f + 0.5f); };
         std::vector<uint8_t> img(pixels * 3);
         for (size_t i = 0; i < pixels; i++) for (int k = 0; k < 3; k++) img[i * 3 + k] = byte(powf(std::max(0.0f, g[i * 8 + k]), 1.0f / 2.2f));
-        if (hh_write_png_rgb8((guide_prefix + "_albedo.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        if (write_png(o.guide_prefix + "_albedo.png", img.data(), out_w, out_h)) return 1;
         for (size_t i = 0; i < pixels; i++) for (int k = 0; k < 3; k++) img[i * 3 + k] = byte(0.5f * g[i * 8 + 3 + k] + 0.5f * g[i * 8 + 7]);
-        if (hh_write_png_rgb8((guide_prefix + "_normal.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
-        for (size_t i = 0; i < pixels; i++) img[i * 3] = img[i * 3 + 1] = img[i * 3 + 2] = byte(zmax > 0.0f ? g[i * 8 + 6] / zmax : 0.0f);
-        if (hh_write_png_rgb8((guide_prefix + "_depth.png").c_str(), img.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
+        if (write_png(o.guide_prefix + "_normal.png", img.data(), out_w, out_h)) return 1;
+        if (write_grey(o.guide_prefix + "_depth.png", out_w, out_h, [&](size_t i) { return std::min(1.0f, std::max(0.0f, zmax > 0.0f ? g[i * 8 + 6] / zmax : 0.0f)); })) return 1;
     }
-    if (robust_k) {   // how much the robust resolve dropped; and its map
-        std::vector<uint8_t> trim((size_t)out_w * out_h);
+    if (o.robust_k) {   // how much the robust resolve dropped; and its map
+        std::vector<uint8_t> trim(pixels);
         CHECK_HR(hr_robust(ctx));
         CHECK_HR(hr_read_robust_trim(ctx, trim.data()));
-        const uint32_t most = (uint32_t)(robust_k - 1) / 2;
+        const uint32_t most = (uint32_t)(o.robust_k - 1) / 2;
         size_t trimmed = 0;
         for (uint8_t v : trim) trimmed += v != 0;
-        tee("robust: buckets=%lld trimmed pixels=%.4f", robust_k, (double)trimmed / (double)trim.size());
-        if (!robust_png.empty()) {   // grey map of trim / ((K - 1) / 2)
-            std::vector<uint8_t> grey(trim.size() * 3);
-            for (size_t i = 0; i < trim.size(); i++) grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = (uint8_t)((double)trim[i] / (double)most * 255.0 + 0.5);
-            if (hh_write_png_rgb8(robust_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
-        }
+        tee("robust: buckets=%lld trimmed pixels=%.4f", o.robust_k, (double)trimmed / (double)trim.size());
+        // grey map of trim / ((K - 1) / 2)
+        if (!o.robust_png.empty() && write_grey(o.robust_png, out_w, out_h, [&](size_t i) { return (double)trim[i] / (double)most; })) return 1;
     }
-    if (counts) {   // how the samplings were spent
-        std::vector<uint32_t> cnt((size_t)out_w * out_h);
+    if (o.counts) {   // how the samplings were spent
+        std::vector<uint32_t> cnt(pixels);
         CHECK_HR(hr_read_sample_counts(ctx, cnt.data()));
         uint32_t lo = ~0u, hi = 0;
         uint64_t sum = 0;
         for (uint32_t v : cnt) { lo = std::min(lo, v); hi = std::max(hi, v); sum += v; }
         tee("samplings per pixel: min=%u max=%u mean=%.3f", lo, hi, (double)sum / (double)cnt.size());
-        if (!sample_png.empty()) {   // grey map of count / largest count
-            std::vector<uint8_t> grey(cnt.size() * 3);
-            for (size_t i = 0; i < cnt.size(); i++) grey[i * 3] = grey[i * 3 + 1] = grey[i * 3 + 2] = hi ? (uint8_t)((double)cnt[i] / (double)hi * 255.0 + 0.5) : 0;
-            if (hh_write_png_rgb8(sample_png.c_str(), grey.data(), out_w, out_h) != 0) { fprintf(stderr, "png: %s\n", hh_last_error()); return 1; }
-        }
+        // grey map of count / largest count
+        if (!o.sample_png.empty() && write_grey(o.sample_png, out_w, out_h, [&](size_t i) { return hi ? (double)cnt[i] / (double)hi : 0.0; })) return 1;
     }
     tee("sampled: %ux%u spp.", sampled, 4u);
     hr_stats st;
     if (hr_get_stats(ctx, &st) == 0) {
         double sec = st.trace_kernel_ms * 1e-3;
         uint64_t paths = st.paths;
-        for (uint32_t r = 1; r < ndev; r++) { hr_stats o; if (hr_get_stats(ctxs[r], &o) == 0) paths += o.paths; }
+        for (uint32_t r = 1; r < ndev; r++) { hr_stats other; if (hr_get_stats(ctxs[r], &other) == 0) paths += other.paths; }
         // two clocks: until the last sampling was reported (the render itself), and until here (+ the final hr_resolve and the PNG encoder)
         tee("gpu: %.3f Mpaths/s wall (%.3f incl. the final image), trace kernel %.3f s, seed kernel %.3f s.", (double)paths / std::max(1e-9, last_progress - begin) * 1e-6,
             (double)paths / (now_sec() - begin) * 1e-6, sec, st.seed_kernel_ms * 1e-3);
     }
     double total = now_sec() - total_begin;
-    double used_percent = total / time_limit * 100.0;
+    double used_percent = total / o.time_limit * 100.0;
     tee("total %g sec. used %.2f %% (x %.2f)", total, used_percent, 100.0 / used_percent);
+    return 0;
+}
+
+void Run::close() {
     for (hr_ctx *c : ctxs) hr_destroy(c);
     hh_scene_destroy(scene);
     if (g_log) fclose(g_log);
+}
+
+int main(int argc, char **argv) {
+    Options o;
+    const int status = parse_options(argc, argv, o);
+    if (status >= 0) return status;
+    setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);   // dmabuf IPC (RCCL on this driver), unless the caller says otherwise; before the HIP runtime starts
+    g_log = fopen("result.txt", "w");
+    Run run(o);
+    run.print_settings();
+    if (run.open_devices() || run.resume() || run.render() || run.write_checkpoint() || run.write_result_png() || run.write_reports()) return 1;
+    run.close();
     return 0;
 }

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli import run_cli
 from test_moments_cpu import ulp_distance
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -187,16 +188,8 @@ def test_list_forms_are_rows_of_the_variant_tables():
         assert row in kv, row
 
 
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-
-
-def _cli(args, cwd):
-    assert os.path.exists(CLI), "the CLI is not built (__graft_entry__.build() makes it with libhanamaru_hip.so)"
-    return subprocess.run([CLI] + args, cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-
-
 def test_cli_help_lists_the_adaptive_flags(tmp_path):
-    r = _cli(["--help"], tmp_path)
+    r = run_cli(["--help"], tmp_path)
     assert r.returncode == 0
     for flag in ("--adaptive E", "--sample-image FILE.png"):
         assert flag in r.stdout, flag
@@ -207,7 +200,7 @@ def test_cli_help_lists_the_adaptive_flags(tmp_path):
                                        (["--adaptive", "-0.5"], "--adaptive"), (["--adaptive", "nan"], "--adaptive"), (["--adaptive", "soon"], "--adaptive"),
                                        (["--sample-image", "s.png", "--gpus", "2"], "one device"), (["--adaptive", "0.1", "--debug"], "--debug")])
 def test_cli_refuses_before_any_device(tmp_path, args, word):
-    r = _cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
+    r = run_cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
     assert r.returncode == 1, r.stdout
     assert word in r.stdout
     assert not (tmp_path / "result.txt").exists()

@@ -5,6 +5,8 @@ noise image against its numpy restatement (4 ulp, the bar of §4.7)."""
 import numpy as np
 import pytest
 
+import ckpt
+from cli import ASSETS, run_cli
 from test_moments_cpu import ulp_distance
 
 pytestmark = pytest.mark.gpu
@@ -440,22 +442,12 @@ def test_debug_refusal_precedence(ha, scenes):
         r.close()
 
 
-def _cli(args, cwd):
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    return subprocess.run([os.path.join(root, "hanamaru-renderer_amd", "hanamaru-hip"), "--assets", os.path.join(root, "assets")] + args, cwd=str(cwd),
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-
-
 def _checkpoint_counts(path, w, h):
     """{"HRA2" header, accumulator, "HRMS" trailer, "HRSC" trailer}: the per-pixel counts of a checkpoint written with --adaptive."""
-    raw = open(path, "rb").read()
-    off = 5 * 4 + w * h * 3 * 4
-    assert raw[off:off + 4] == b"HRMS"
-    off += 4 + 8 + w * h * 6 * 8
-    assert raw[off:off + 4] == b"HRSC" and len(raw) == off + 4 + w * h * 4
-    return np.frombuffer(raw, dtype=np.uint32, offset=off + 4).reshape(h, w)
+    c = ckpt.read(path)
+    assert c.magic == ckpt.FRAME and c.has_moments and c.has_counts and c.complete == ckpt.S_COUNTS
+    assert c.used == c.size == 5 * 4 + w * h * 3 * 4 + (4 + 8 + w * h * 6 * 8) + (4 + w * h * 4) and c.counts.shape == (h, w)
+    return c.counts
 
 
 def test_cli_adaptive(tmp_path, ha, scenes):
@@ -472,8 +464,9 @@ def test_cli_adaptive(tmp_path, ha, scenes):
     finally:
         r.close()
     thr = float(np.median(img.reshape(h // 4, 4, w // 4, 4).max(axis=(1, 3))))
-    base = ["-w", str(w), "-h", str(h), "--scene", "cornell_mini", "-t", "600", "--noise-check", "8", "--adaptive", repr(thr)]
-    run = _cli(base + ["-s", "24", "--sample-image", "samples.png", "--checkpoint", "a.ckpt"], tmp_path)
+    plain = ["--assets", ASSETS, "-w", str(w), "-h", str(h), "--scene", "cornell_mini", "-t", "600"]
+    base = plain + ["--noise-check", "8", "--adaptive", repr(thr)]
+    run = run_cli(base + ["-s", "24", "--sample-image", "samples.png", "--checkpoint", "a.ckpt"], tmp_path, timeout=120)
     assert run.returncode == 0, run.stdout
     checks = re.findall(r"adaptive: samplings=(\d+) active=(\d+) tiles=(\d+)", run.stdout)
     assert checks and checks[0][0] == "8" and 0 < int(checks[0][1]) < int(checks[0][2]) == (w // 4) * (h // 4)
@@ -487,7 +480,7 @@ def test_cli_adaptive(tmp_path, ha, scenes):
     counts = _checkpoint_counts(str(tmp_path / "a.ckpt"), w, h)
     assert len(np.unique(counts)) >= 2 and counts.min() >= 8 and np.array_equal(grey[..., 0], np.floor(counts / counts.max() * 255.0 + 0.5).astype(np.uint8))
     # resume: the counts come back, the tiles are chosen again before anything is rendered, and every pixel only ever gains samplings
-    again = _cli(base + ["-s", "40", "--resume", "a.ckpt", "--checkpoint", "b.ckpt"], tmp_path)
+    again = run_cli(base + ["-s", "40", "--resume", "a.ckpt", "--checkpoint", "b.ckpt"], tmp_path, timeout=120)
     assert again.returncode == 0, again.stdout
     assert "holds no sample moments" not in again.stdout        # the moments were found and restored
     first = re.search(r"adaptive: samplings=(\d+) active=(\d+)", again.stdout)
@@ -496,16 +489,15 @@ def test_cli_adaptive(tmp_path, ha, scenes):
     after = _checkpoint_counts(str(tmp_path / "b.ckpt"), w, h)
     assert (after >= counts).all() and (after[counts < counts.max()] == counts[counts < counts.max()]).all()
     # resumed with nothing left to render: the counts round-trip unchanged
-    same = _cli(base + ["-s", str(sampled), "--resume", "a.ckpt", "--checkpoint", "c.ckpt"], tmp_path)
+    same = run_cli(base + ["-s", str(sampled), "--resume", "a.ckpt", "--checkpoint", "c.ckpt"], tmp_path, timeout=120)
     assert same.returncode == 0 and np.array_equal(_checkpoint_counts(str(tmp_path / "c.ckpt"), w, h), counts)
     # without the new flags: a checkpoint with moments resumes silently, one without says that its samplings are not covered
-    plain = ["-w", str(w), "-h", str(h), "--scene", "cornell_mini", "-t", "600"]
-    assert _cli(plain + ["-s", "4", "--noise-image", "n.png", "--checkpoint", "m.ckpt"], tmp_path).returncode == 0
-    assert _cli(plain + ["-s", "4", "--checkpoint", "p.ckpt"], tmp_path).returncode == 0
-    with_mom = _cli(plain + ["-s", "6", "--noise-image", "n.png", "--resume", "m.ckpt"], tmp_path)
-    without = _cli(plain + ["-s", "6", "--noise-image", "n.png", "--sample-image", "s.png", "--resume", "p.ckpt"], tmp_path)
+    assert run_cli(plain + ["-s", "4", "--noise-image", "n.png", "--checkpoint", "m.ckpt"], tmp_path, timeout=120).returncode == 0
+    assert run_cli(plain + ["-s", "4", "--checkpoint", "p.ckpt"], tmp_path, timeout=120).returncode == 0
+    with_mom = run_cli(plain + ["-s", "6", "--noise-image", "n.png", "--resume", "m.ckpt"], tmp_path, timeout=120)
+    without = run_cli(plain + ["-s", "6", "--noise-image", "n.png", "--sample-image", "s.png", "--resume", "p.ckpt"], tmp_path, timeout=120)
     assert with_mom.returncode == 0 and "holds no sample moments" not in with_mom.stdout
     assert without.returncode == 0 and "holds no sample moments" in without.stdout
     for args, word in [(["--gpus", "2"], "one device"), (["--noise-target", "0.1"], "two stop rules")]:
-        bad = _cli(base + ["-s", "8"] + args, tmp_path)
+        bad = run_cli(base + ["-s", "8"] + args, tmp_path, timeout=120)
         assert bad.returncode == 1 and word in bad.stdout

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli import run_cli
 from test_moments_cpu import ulp_distance
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -332,16 +333,8 @@ def test_guide_kernel_has_a_row_per_node_format():
         assert row in kv, row
 
 
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-
-
-def _cli(args, cwd):
-    assert os.path.exists(CLI), "the CLI is not built (__graft_entry__.build() makes it with libhanamaru_hip.so)"
-    return subprocess.run([CLI] + args, cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-
-
 def test_cli_help_lists_the_denoise_flags(tmp_path):
-    r = _cli(["--help"], tmp_path)
+    r = run_cli(["--help"], tmp_path)
     assert r.returncode == 0
     for flag in ("--denoise ", "--denoise-levels N", "--guide-image PREFIX"):
         assert flag in r.stdout, flag
@@ -352,7 +345,7 @@ def test_cli_help_lists_the_denoise_flags(tmp_path):
                                        (["--guide-image", "g", "--debug"], "--debug"), (["--denoise", "--denoise-levels", "6"], "--denoise-levels"),
                                        (["--denoise", "--denoise-levels", "two"], "--denoise-levels"), (["--denoise-levels", "2"], "--denoise")])
 def test_cli_refuses_before_any_device(tmp_path, args, word):
-    r = _cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
+    r = run_cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
     assert r.returncode == 1, r.stdout
     assert word in r.stdout
     assert not (tmp_path / "result.txt").exists()

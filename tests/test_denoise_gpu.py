@@ -3,13 +3,12 @@ and node-format contracts bit for bit; hr_denoise against csrc/denoise_core.h co
 + - x / max, no contraction); its resolve against hr_resolve / hr_resolve_counted byte for byte; the state rules; and that the default
 parameters lower the error of a 16-sampling render."""
 import ctypes as C
-import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import ckpt
+from cli import ASSETS, run_cli
 from test_denoise_cpu import DEFAULTS, bits, core, core_denoise, synthetic_inputs  # noqa: F401  (core: the g++-built harness, a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -351,31 +350,22 @@ def test_default_parameters_lower_the_error_of_a_short_render(ha, scenes, scene)
 
 # ---------------------------------------------------------------------------------------------------------------- the CLI
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-
-
-def _cli(args, cwd):
-    return subprocess.run([CLI, "--assets", os.path.join(ROOT, "assets"), "--scene", "spheres", "-w", "32", "-h", "16"] + args, cwd=str(cwd),
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+CLI_ARGS = ["--assets", ASSETS, "--scene", "spheres", "-w", "32", "-h", "16"]
 
 
 def test_cli_denoise_guide_images_and_resume(tmp_path):
     """--denoise end to end, and its resume rule: the filter's mean is accumulator / (4 n) with n the samplings behind the moments, so a
     checkpoint whose moments do not cover every sampling of its accumulator is refused (as --adaptive refuses it), not resolved too bright."""
-    r = _cli(["-s", "4", "--denoise", "--denoise-levels", "2", "--guide-image", "g", "--checkpoint", "with.ckpt"], tmp_path)
+    r = run_cli(CLI_ARGS + ["-s", "4", "--denoise", "--denoise-levels", "2", "--guide-image", "g", "--checkpoint", "with.ckpt"], tmp_path, timeout=120)
     assert r.returncode == 0, r.stdout
     for name in ("result.png", "g_albedo.png", "g_normal.png", "g_depth.png", "with.ckpt"):
         assert (tmp_path / name).stat().st_size > 0, name
     assert "is not denoised" not in r.stdout
     # a checkpoint written without moments: {"HRA2", w, h, samplings, FNV-1a of the scene name} + the accumulator
-    fnv = 2166136261
-    for ch in b"spheres":
-        fnv = ((fnv ^ ch) * 16777619) & 0xffffffff
-    (tmp_path / "plain.ckpt").write_bytes(struct.pack("<5I", 0x32415248, 32, 16, 3, fnv) + np.ones((16, 32, 3), np.float32).tobytes())
-    r = _cli(["-s", "6", "--denoise", "--resume", "plain.ckpt"], tmp_path)
+    (tmp_path / "plain.ckpt").write_bytes(ckpt.pack(ckpt.new(32, 16, 3, "spheres", np.ones((16, 32, 3), np.float32))))
+    r = run_cli(CLI_ARGS + ["-s", "6", "--denoise", "--resume", "plain.ckpt"], tmp_path, timeout=120)
     assert r.returncode == 1 and "--denoise" in r.stdout and "moments" in r.stdout, r.stdout
-    r = _cli(["-s", "6", "--resume", "plain.ckpt"], tmp_path)                   # without --denoise the file is fine
+    r = run_cli(CLI_ARGS + ["-s", "6", "--resume", "plain.ckpt"], tmp_path, timeout=120)                   # without --denoise the file is fine
     assert r.returncode == 0, r.stdout
-    r = _cli(["-s", "6", "--denoise", "--resume", "with.ckpt"], tmp_path)         # moments that cover its 4 samplings: goes on to 6
+    r = run_cli(CLI_ARGS + ["-s", "6", "--denoise", "--resume", "with.ckpt"], tmp_path, timeout=120)         # moments that cover its 4 samplings: goes on to 6
     assert r.returncode == 0 and "resumed at 4x4 sampled" in r.stdout and "is not denoised" not in r.stdout, r.stdout

@@ -2,12 +2,12 @@
 csrc/pt_core.h guide_chain_link (tests/guide_chain_harness.cpp, built here with g++) against guide_primary, against the same chain in f64 over the
 oracle, and each rule of the definition on a tiny hand-built scene; the variant rows and the CLI's refusals, without a device."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import guide_chain as gc
+from cli import run_cli
 from test_denoise_cpu import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,23 +165,15 @@ def test_variant_table_has_the_chain_rows_and_keeps_the_old_ones():
     assert '"guide_bounces"' in open(os.path.join(ROOT, "include", "hanamaru_hip.h")).read()
 
 
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-
-
-def _cli(args, cwd):
-    assert os.path.exists(CLI), "the CLI is not built (__graft_entry__.build() makes it with libhanamaru_hip.so)"
-    return subprocess.run([CLI] + args, cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-
-
 def test_cli_help_lists_guide_bounces(tmp_path):
-    r = _cli(["--help"], tmp_path)
+    r = run_cli(["--help"], tmp_path)
     assert r.returncode == 0 and "--guide-bounces K" in r.stdout
 
 
 @pytest.mark.parametrize("args,word", [(["--denoise", "--guide-bounces", "9"], "--guide-bounces must be"), (["--guide-image", "g", "--guide-bounces", "-1"], "--guide-bounces must be"),
                                        (["--denoise", "--guide-bounces", "two"], "--guide-bounces must be"), (["--guide-bounces", "2"], "--guide-bounces needs")])
 def test_cli_refuses_guide_bounces_before_any_device(tmp_path, args, word):
-    r = _cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
+    r = run_cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
     assert r.returncode == 1, r.stdout
     assert word in r.stdout
     assert not (tmp_path / "result.txt").exists()

@@ -3,13 +3,12 @@ against the parent's planes (K = 0), its exact identities (node formats, regions
 oracle's first hits, against the host form of the same per-lane function (tests/guide_chain_harness.cpp), the option's state rules, hr_denoise
 over chain guides against the host filter core bit for bit, the quality figures, and the CLI flag."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import guide_chain as gc
+from cli import ASSETS, run_cli
 from test_denoise_cpu import bits, core, core_denoise  # noqa: F401  (core: the g++-built filter harness, a fixture)
 from test_guide_chain_cpu import harness  # noqa: F401  (the g++-built host form, a fixture)
 
@@ -346,14 +345,9 @@ def test_partial_tiles_and_lanes_outside_a_region(ha, scenes, tiny_host, qn):
 
 # ---------------------------------------------------------------------------------------------------------------- the CLI
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-
-
 def test_cli_guide_bounces_writes_the_chains_planes(tmp_path):
     def run(extra, prefix):
-        return subprocess.run([CLI, "--assets", os.path.join(ROOT, "assets"), "--scene", "cornell_mini", "-w", "32", "-h", "16", "-s", "4", "--denoise", "--guide-image", prefix] + extra,
-                              cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+        return run_cli(["--assets", ASSETS, "--scene", "cornell_mini", "-w", "32", "-h", "16", "-s", "4", "--denoise", "--guide-image", prefix] + extra, tmp_path, timeout=120)
     r = run(["--guide-bounces", "4"], "P")
     assert r.returncode == 0, r.stdout
     for name in ("P_albedo.png", "P_normal.png", "P_depth.png"):

@@ -9,8 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli import run_cli
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
 
 
 def noise_reference(moments, n, floor):
@@ -126,14 +127,8 @@ def test_noise_core_matches_the_definition(tmp_path):
     assert ulp_distance(run(mixed, 24, 0.01), [noise_reference(mixed, 24, 0.01)])[0] <= 4 and run(mixed, 24, 0.01)[0] > 0
 
 
-def _cli(args, cwd):
-    if not os.path.exists(CLI):
-        pytest.skip("CLI not built (needs libhanamaru_hip.so: __graft_entry__.build())")
-    return subprocess.run([CLI] + args, cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-
-
 def test_cli_help_lists_the_noise_flags(tmp_path):
-    r = _cli(["--help"], tmp_path)
+    r = run_cli(["--help"], tmp_path, missing="skip")
     assert r.returncode == 0
     for flag in ("--noise-target E", "--noise-floor F", "--noise-check N", "--noise-image FILE.png"):
         assert flag in r.stdout, flag
@@ -148,7 +143,7 @@ def test_cli_help_lists_the_noise_flags(tmp_path):
                                        (["--noise-check", "1.5"], "--noise-check")])
 def test_cli_rejects_bad_noise_values_before_any_device(tmp_path, args, flag):
     """Argument errors: exit status 1 and a message naming the flag, before the log file is opened or a device is touched."""
-    r = _cli(["-w", "96", "-h", "54", "-s", "4"] + args, tmp_path)
+    r = run_cli(["-w", "96", "-h", "54", "-s", "4"] + args, tmp_path, missing="skip")
     assert r.returncode == 1, r.stdout
     assert flag in r.stdout
     assert not (tmp_path / "result.txt").exists()

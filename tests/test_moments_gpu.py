@@ -1,18 +1,17 @@
 """Per-pixel sample moments and the noise estimate (option "moments") on the MI355X.  The definition is exact: x_s, a sampling's
 contribution to a pixel, is what `clear; render(s, s + 1); read_accumulator` returns today, S1 / S2 are their sums in f64 in the order rendered —
 so the moments are checked to the bit against the library's own per-sampling renders, whatever the launch cuts, shading mode and pipeline."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import ckpt
+from cli import ASSETS, run_cli
 from test_moments_cpu import noise_reference, ulp_distance
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, S = 96, 54, 24
 REGION = (29, 17, 40, 24)
 SCENES = ["spheres", "rtcamp6_v3_1"]    # no meshes (precise shading in the megakernel by default) / a mesh scene
@@ -276,13 +275,6 @@ def test_the_estimate_means_something(ha, scenes, name, oracle_rms):
     assert k.sum() > 5000 and 0.6 <= rms <= 1.6, rms
 
 
-def _cli(tmp_path, args):
-    exe = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-    assert os.path.exists(exe), "hanamaru-hip not built (run __graft_entry__.build())"
-    return subprocess.run([exe] + [str(a) for a in args] + ["--assets", os.path.join(ROOT, "assets")], cwd=str(tmp_path), stdout=subprocess.PIPE,
-                          stderr=subprocess.STDOUT, text=True, timeout=300)
-
-
 def _noise_lines(text):
     return [(int(m.group(1)), float(m.group(2)), float(m.group(3)), int(m.group(4)))
             for m in re.finditer(r"^noise: samplings=(\d+) mean=(\S+) max=(\S+) above=(\d+)$", text, re.M)]
@@ -293,10 +285,10 @@ def test_cli_noise_target(tmp_path, ha, scenes):
     what 64 samplings reach; the moments do not depend on launch cuts, so the 256-sampling run meets the same value at its first check):
     E = 1.05 x that mean, so the run with `-s 256` has to stop at 64."""
     from PIL import Image
-    base = ["-w", W, "-h", H, "-t", 1000, "-i", 1000]
+    base = ["--assets", ASSETS, "-w", W, "-h", H, "-t", 1000, "-i", 1000]
     d0 = tmp_path / "trial"
     d0.mkdir()
-    p = _cli(d0, base + ["-s", 64, "--noise-target", 0])
+    p = run_cli(base + ["-s", 64, "--noise-target", 0], d0, timeout=300)
     assert p.returncode == 0, p.stdout
     trial = _noise_lines(p.stdout)
     print("trial:", trial)
@@ -304,7 +296,7 @@ def test_cli_noise_target(tmp_path, ha, scenes):
     CLI_TARGET = float("%.6g" % (1.05 * trial[0][1]))
     d1 = tmp_path / "a"
     d1.mkdir()
-    p = _cli(d1, base + ["-s", 256, "--noise-target", CLI_TARGET, "--noise-image", "noise.png"])
+    p = run_cli(base + ["-s", 256, "--noise-target", CLI_TARGET, "--noise-image", "noise.png"], d1, timeout=300)
     assert p.returncode == 0, p.stdout
     lines = _noise_lines(p.stdout)
     done = int(re.search(r"^sampled: (\d+)x4 spp\.$", p.stdout, re.M).group(1))
@@ -335,33 +327,33 @@ def test_cli_noise_target(tmp_path, ha, scenes):
     # a target of 0 is never reached: all 8 samplings, one estimate at the end
     d2 = tmp_path / "b"
     d2.mkdir()
-    p = _cli(d2, base + ["-s", 8, "--noise-target", 0, "--checkpoint", "ck8"])
+    p = run_cli(base + ["-s", 8, "--noise-target", 0, "--checkpoint", "ck8"], d2, timeout=300)
     assert p.returncode == 0 and "sampled: 8x4 spp." in p.stdout and "reached max sampling" in p.stdout, p.stdout
     assert [l[0] for l in _noise_lines(p.stdout)] == [8]
     # checkpoint -> resume continues the count: 8 + 8 samplings leave the moments of a straight 16 (they do not depend on launch cuts)
-    p = _cli(d2, base + ["-s", 16, "--noise-target", 0, "--resume", "ck8", "--checkpoint", "ck16"])
+    p = run_cli(base + ["-s", 16, "--noise-target", 0, "--resume", "ck8", "--checkpoint", "ck16"], d2, timeout=300)
     assert p.returncode == 0 and "resumed at 8x4 sampled" in p.stdout, p.stdout
     assert [l[0] for l in _noise_lines(p.stdout)] == [16]
     d3 = tmp_path / "c"
     d3.mkdir()
-    p = _cli(d3, base + ["-s", 16, "--noise-target", 0, "--checkpoint", "ck16"])
+    p = run_cli(base + ["-s", 16, "--noise-target", 0, "--checkpoint", "ck16"], d3, timeout=300)
     assert p.returncode == 0, p.stdout
     acc_bytes = 20 + W * H * 12
 
     def trailer(path):
-        raw = open(path, "rb").read()
-        assert len(raw) == acc_bytes + 12 + W * H * 48 and raw[acc_bytes:acc_bytes + 4] == b"HRMS"
-        return int(np.frombuffer(raw[acc_bytes + 4:acc_bytes + 12], dtype=np.uint64)[0]), raw[acc_bytes + 12:]
+        c = ckpt.read(path)
+        assert c.used == c.size == acc_bytes + 12 + W * H * 48 and c.has_moments and c.complete == ckpt.S_MOMENTS   # "HRMS" behind the accumulator, nothing else
+        return c.moments_n, c.moments.tobytes()
     (n_a, mom_a), (n_b, mom_b) = trailer(d2 / "ck16"), trailer(d3 / "ck16")
     assert n_a == n_b == 16 and mom_a == mom_b
     assert trailer(d2 / "ck8")[0] == 8
     # a file written without moments keeps today's bytes, and cannot be resumed with a noise target
-    p = _cli(d3, base + ["-s", 4, "--checkpoint", "plain"])
+    p = run_cli(base + ["-s", 4, "--checkpoint", "plain"], d3, timeout=300)
     assert p.returncode == 0 and not _noise_lines(p.stdout), p.stdout
     assert len(open(d3 / "plain", "rb").read()) == acc_bytes
-    p = _cli(d3, base + ["-s", 8, "--resume", "plain", "--noise-target", 0.05])
+    p = run_cli(base + ["-s", 8, "--resume", "plain", "--noise-target", 0.05], d3, timeout=300)
     assert p.returncode == 1 and "--noise-target" in p.stdout and "moments" in p.stdout, p.stdout
     # only the image asked for: E = 0.05, no early stop
-    p = _cli(d3, base + ["-s", 4, "--noise-image", "n.png"])
+    p = run_cli(base + ["-s", 4, "--noise-image", "n.png"], d3, timeout=300)
     assert p.returncode == 0 and "sampled: 4x4 spp." in p.stdout and [l[0] for l in _noise_lines(p.stdout)] == [4], p.stdout
     assert np.asarray(Image.open(d3 / "n.png")).shape[:2] == (H, W)

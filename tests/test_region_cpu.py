@@ -3,12 +3,12 @@ CLI's --region is documented and checked before any device is opened."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+from cli import run_cli
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
 
 
 def _product_header():
@@ -39,14 +39,8 @@ def test_python_renderer_has_set_region(ha):
     assert L.hr_set_region.argtypes is not None and len(L.hr_set_region.argtypes) == 5
 
 
-def _cli(args, cwd):
-    if not os.path.exists(CLI):
-        pytest.skip("CLI not built (needs libhanamaru_hip.so: __graft_entry__.build())")
-    return subprocess.run([CLI] + args, cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-
-
 def test_cli_help_lists_region(tmp_path):
-    r = _cli(["--help"], tmp_path)
+    r = run_cli(["--help"], tmp_path, missing="skip")
     assert r.returncode == 0 and "--region X,Y,W,H" in r.stdout
 
 
@@ -56,7 +50,7 @@ def test_cli_help_lists_region(tmp_path):
 def test_cli_rejects_a_bad_region_before_any_device(tmp_path, args):
     """Malformed or out-of-frame windows are argument errors: exit status 1 and a message naming --region, before the log file is opened
     or a device is touched (no result.txt; on a machine without a GPU no device error either)."""
-    r = _cli(args, tmp_path)
+    r = run_cli(args, tmp_path, missing="skip")
     assert r.returncode == 1, r.stdout
     assert "--region" in r.stdout
     assert not (tmp_path / "result.txt").exists()

@@ -2,15 +2,14 @@
 FRAME coordinates, so pixel (i, j) of a region accumulator is bit-identical to pixel (x0+i, y0+j) of the full-frame render with the same
 hr_render calls and options — checked to the bit here for both shading modes, the split pipeline, the debug renderer, tiles stitched from
 separate contexts, extreme frames and the CLI."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import ckpt
+from cli import ASSETS, run_cli
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 480, 270
 REGIONS = [(37, 21, 101, 63), (0, 0, 1, 1), (0, 100, 480, 5), (467, 263, 13, 7), (0, 0, 480, 270)]
 SAMPLINGS = [(1, 9, 1), (3, 16, 3)]
@@ -232,27 +231,16 @@ def test_region_same_device_exchange(ha, scenes):
             r.close()
 
 
-def _cli(tmp_path, args):
-    exe = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-    assert os.path.exists(exe), "hanamaru-hip not built (run __graft_entry__.build())"
-    return subprocess.run([exe] + [str(a) for a in args] + ["--assets", os.path.join(ROOT, "assets")], cwd=str(tmp_path), stdout=subprocess.PIPE,
-                          stderr=subprocess.STDOUT, text=True, timeout=300)
-
-
-def _ckpt(path):
-    raw = open(path, "rb").read()
-    return np.frombuffer(raw[:20], dtype=np.uint32), raw
-
-
 def test_cli_region(tmp_path, ha, scenes):
     from PIL import Image
     reg = (37, 21, 101, 63)
     rarg = "%d,%d,%d,%d" % reg
-    base = ["-w", W, "-h", H, "-t", 1000, "-i", 1000, "--launch", 1]
+    small = ["--assets", ASSETS, "-w", 96, "-h", 54, "-t", 1000, "-i", 1000]
+    base = ["--assets", ASSETS, "-w", W, "-h", H, "-t", 1000, "-i", 1000, "--launch", 1]
     # the PNG of a region run: w x h, hr_resolve of a region context (one sampling per launch, as --launch 1 renders them)
     d1 = tmp_path / "a"
     d1.mkdir()
-    p = _cli(d1, base + ["-s", 4, "--region", rarg, "--checkpoint", "ck"])
+    p = run_cli(base + ["-s", 4, "--region", rarg, "--checkpoint", "ck"], d1, timeout=300)
     assert p.returncode == 0, p.stdout
     assert "region: 37,21 101x63." in p.stdout
     img = np.asarray(Image.open(d1 / "result.png"))
@@ -267,28 +255,28 @@ def test_cli_region(tmp_path, ha, scenes):
     finally:
         r.close()
     assert img.shape == (63, 101, 3) and np.array_equal(img, exp)
-    hdr, raw = _ckpt(d1 / "ck")
-    assert raw[:4] == b"HRR2" and list(np.frombuffer(raw[20:36], dtype=np.uint32)) == list(reg) and len(raw) == 36 + 101 * 63 * 12
+    c = ckpt.read(d1 / "ck")
+    assert c.magic == ckpt.REGION and c.region == reg and c.complete == ckpt.S_ACCUMULATOR and c.used == c.size == 36 + 101 * 63 * 12
     # checkpoint / resume round trip: 2 + 2 samplings == the uninterrupted 4 (accumulator and image)
     d2 = tmp_path / "b"
     d2.mkdir()
-    p = _cli(d2, base + ["-s", 2, "--region", rarg, "--checkpoint", "ck2"])
+    p = run_cli(base + ["-s", 2, "--region", rarg, "--checkpoint", "ck2"], d2, timeout=300)
     assert p.returncode == 0, p.stdout
-    p = _cli(d2, base + ["-s", 4, "--region", rarg, "--resume", "ck2", "--checkpoint", "ck4"])
+    p = run_cli(base + ["-s", 4, "--region", rarg, "--resume", "ck2", "--checkpoint", "ck4"], d2, timeout=300)
     assert p.returncode == 0 and "resumed at 2x4 sampled" in p.stdout, p.stdout
-    assert _ckpt(d2 / "ck4")[1] == raw
+    assert (d2 / "ck4").read_bytes() == (d1 / "ck").read_bytes()
     assert np.array_equal(np.asarray(Image.open(d2 / "result.png")), img)
     # a region checkpoint resumed with another region, or without one, is refused
-    p = _cli(d2, base + ["-s", 4, "--region", "36,21,101,63", "--resume", "ck2"])
+    p = run_cli(base + ["-s", 4, "--region", "36,21,101,63", "--resume", "ck2"], d2, timeout=300)
     assert p.returncode != 0 and "region" in p.stdout, p.stdout
-    p = _cli(d2, base + ["-s", 4, "--resume", "ck2"])
+    p = run_cli(base + ["-s", 4, "--resume", "ck2"], d2, timeout=300)
     assert p.returncode != 0 and "region" in p.stdout, p.stdout
     # a full-frame checkpoint keeps its format ("HRA2", five words, W x H x 3 floats) and is refused under --region
     d3 = tmp_path / "c"
     d3.mkdir()
-    p = _cli(d3, ["-w", 96, "-h", 54, "-s", 1, "-t", 1000, "-i", 1000, "--checkpoint", "ckf"])
+    p = run_cli(small + ["-s", 1, "--checkpoint", "ckf"], d3, timeout=300)
     assert p.returncode == 0, p.stdout
-    hdr, raw = _ckpt(d3 / "ckf")
-    assert raw[:4] == b"HRA2" and list(hdr[1:4]) == [96, 54, 1] and len(raw) == 20 + 96 * 54 * 12
-    p = _cli(d3, ["-w", 96, "-h", 54, "-s", 2, "-t", 1000, "-i", 1000, "--region", "0,0,8,8", "--resume", "ckf"])
+    c = ckpt.read(d3 / "ckf")
+    assert c.magic == ckpt.FRAME and (c.width, c.height, c.samplings) == (96, 54, 1) and c.complete == ckpt.S_ACCUMULATOR and c.used == c.size == 20 + 96 * 54 * 12
+    p = run_cli(small + ["-s", 2, "--region", "0,0,8,8", "--resume", "ckf"], d3, timeout=300)
     assert p.returncode != 0, p.stdout

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli import run_cli
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("hr_read_buckets", "hr_write_buckets", "hr_robust", "hr_read_robust", "hr_read_robust_trim", "hr_resolve_robust")
 
@@ -284,16 +286,8 @@ def test_bucket_kernel_rows():
         assert row in kv, row
 
 
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
-
-
-def _cli(args, cwd):
-    assert os.path.exists(CLI), "the CLI is not built (__graft_entry__.build() makes it with libhanamaru_hip.so)"
-    return subprocess.run([CLI] + args, cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-
-
 def test_cli_help_lists_the_robust_flags(tmp_path):
-    r = _cli(["--help"], tmp_path)
+    r = run_cli(["--help"], tmp_path)
     assert r.returncode == 0
     for flag in ("--robust K", "--robust-image FILE.png"):
         assert flag in r.stdout, flag
@@ -306,7 +300,7 @@ def test_cli_help_lists_the_robust_flags(tmp_path):
                                        (["--robust", "9", "--gpus", "2"], "one device"), (["--robust", "9", "--gpu-ids", "0,1"], "one device"),
                                        (["--robust", "9", "--debug"], "--debug"), (["--robust-image", "t.png"], "--robust")])
 def test_cli_refuses_before_any_device(tmp_path, args, word):
-    r = _cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
+    r = run_cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
     assert r.returncode == 1, r.stdout
     assert word in r.stdout
     assert not (tmp_path / "result.txt").exists()

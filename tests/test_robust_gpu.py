@@ -1,14 +1,12 @@
 """Sample buckets and the firefly-robust resolve on the MI355X: the buckets bucket_kernel keeps against a sequential f64 loop over
 the library's own per-sampling renders, under launch cuts, strides, pipelines, regions and tile masks — bit for bit —, hr_robust against the host
 build of csrc/robust_core.h — bit for bit —, the state rules of R, the quality figure on the device, and the CLI."""
-import os
-import struct
-import subprocess
-
 import numpy as np
 import pytest
 
+import ckpt
 import test_robust_cpu as rc
+from cli import ASSETS, run_cli
 from test_adaptive_gpu import MASKS, MODES, RH, RW, SCENES, TARGETS, _bits, _code, _pixels, _same
 
 pytestmark = pytest.mark.gpu
@@ -350,37 +348,28 @@ def test_quality_ratio_on_the_device(ha, scenes, core, name):
 
 # ---------------------------------------------------------------------------------------------------------------- the CLI
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "hanamaru-renderer_amd", "hanamaru-hip")
 CW, CH = 32, 16
-
-
-def _cli(args, cwd):
-    os.makedirs(str(cwd), exist_ok=True)
-    return subprocess.run([CLI, "--assets", os.path.join(ROOT, "assets"), "--scene", "cornell_mini", "-w", str(CW), "-h", str(CH), "-t", "1000", "-i", "1000"] + args,
-                          cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+CLI_ARGS = ["--assets", ASSETS, "--scene", "cornell_mini", "-w", str(CW), "-h", str(CH), "-t", "1000", "-i", "1000"]
 
 
 def _checkpoint_buckets(path, K):
     """The last trailer of a checkpoint written with --robust K: {"HRBK", K, samplings, w*h*3K doubles}."""
-    raw = open(path, "rb").read()
-    size = 16 + CW * CH * 3 * K * 8
-    magic, k, n = struct.unpack("<IIQ", raw[-size:-size + 16])
-    assert magic == 0x4b425248 and k == K
-    return np.frombuffer(raw[-size + 16:], dtype=np.float64).reshape(CH, CW, K, 3), n, len(raw) - size
+    c = ckpt.read(path)
+    assert c.has_buckets and c.buckets_k == K and c.complete == ckpt.S_BUCKETS and c.used == c.size and c.buckets.shape == (CH, CW, K, 3)
+    return c.buckets, c.buckets_n, c.size - (16 + CW * CH * 3 * K * 8)
 
 
 def test_cli_robust_images_and_resume(tmp_path):
     one, two = tmp_path / "one", tmp_path / "two"
-    r = _cli(["-s", "16", "--robust", "9", "--robust-image", "trim.png", "--checkpoint", "c.ckpt"], one)
+    r = run_cli(CLI_ARGS + ["-s", "16", "--robust", "9", "--robust-image", "trim.png", "--checkpoint", "c.ckpt"], one, timeout=120)
     assert r.returncode == 0, r.stdout
     for f in ("result.png", "trim.png", "c.ckpt"):
         assert (one / f).stat().st_size > 0, f
     assert "robust: buckets=9" in r.stdout
     # 8 + 8 samplings across a checkpoint: the bytes of the unsplit 16
-    r = _cli(["-s", "8", "--robust", "9", "--checkpoint", "a.ckpt"], two)
+    r = run_cli(CLI_ARGS + ["-s", "8", "--robust", "9", "--checkpoint", "a.ckpt"], two, timeout=120)
     assert r.returncode == 0, r.stdout
-    r = _cli(["-s", "16", "--robust", "9", "--robust-image", "trim.png", "--resume", "a.ckpt", "--checkpoint", "b.ckpt"], two)
+    r = run_cli(CLI_ARGS + ["-s", "16", "--robust", "9", "--robust-image", "trim.png", "--resume", "a.ckpt", "--checkpoint", "b.ckpt"], two, timeout=120)
     assert r.returncode == 0 and "resumed at 8x4 sampled" in r.stdout, r.stdout
     for f in ("result.png", "trim.png"):
         assert (one / f).read_bytes() == (two / f).read_bytes(), f
@@ -389,16 +378,16 @@ def test_cli_robust_images_and_resume(tmp_path):
     assert n_one == n_two == 16 and b_one.any() and np.array_equal(_bits(b_one), _bits(b_two))
     assert head_one == 20 + CW * CH * 12                                             # no other trailer: the header and the accumulator
     # another K, or a file without buckets, is refused together with --robust; without the flag the file keeps the bytes it always had
-    r = _cli(["-s", "20", "--robust", "5", "--resume", "a.ckpt"], two)
+    r = run_cli(CLI_ARGS + ["-s", "20", "--robust", "5", "--resume", "a.ckpt"], two, timeout=120)
     assert r.returncode == 1 and "another K" in r.stdout, r.stdout
-    r = _cli(["-s", "4", "--checkpoint", "plain.ckpt"], two)
+    r = run_cli(CLI_ARGS + ["-s", "4", "--checkpoint", "plain.ckpt"], two, timeout=120)
     assert r.returncode == 0 and (two / "plain.ckpt").stat().st_size == 20 + CW * CH * 12, r.stdout
-    r = _cli(["-s", "8", "--robust", "9", "--resume", "plain.ckpt"], two)
+    r = run_cli(CLI_ARGS + ["-s", "8", "--robust", "9", "--resume", "plain.ckpt"], two, timeout=120)
     assert r.returncode == 1 and "no sample buckets" in r.stdout, r.stdout
     # with --adaptive the buckets follow every pixel's own count, through the checkpoint as well
-    r = _cli(["-s", "24", "--robust", "9", "--adaptive", "0.05", "--noise-check", "8", "--checkpoint", "ad.ckpt"], two)
+    r = run_cli(CLI_ARGS + ["-s", "24", "--robust", "9", "--adaptive", "0.05", "--noise-check", "8", "--checkpoint", "ad.ckpt"], two, timeout=120)
     assert r.returncode == 0 and "adaptive:" in r.stdout, r.stdout
-    r = _cli(["-s", "32", "--robust", "9", "--adaptive", "0.05", "--noise-check", "8", "--resume", "ad.ckpt"], two)
+    r = run_cli(CLI_ARGS + ["-s", "32", "--robust", "9", "--adaptive", "0.05", "--noise-check", "8", "--resume", "ad.ckpt"], two, timeout=120)
     assert r.returncode == 0, r.stdout
-    r = _cli(["-s", "32", "--robust", "9", "--resume", "ad.ckpt"], two)             # per-pixel ordinals need the counts
+    r = run_cli(CLI_ARGS + ["-s", "32", "--robust", "9", "--resume", "ad.ckpt"], two, timeout=120)             # per-pixel ordinals need the counts
     assert r.returncode == 1 and "per-pixel" in r.stdout, r.stdout
