@@ -342,7 +342,7 @@ static int govern_reset(hr_ctx *c) {
     // the wave budget is governed with the level (a fixed level pins it at "all"): 2.5 .. 3.5 workgroups per CU in steps of a quarter
     if (c->trace_boost < 0) { h.budget_step = (uint32_t)c->num_cus / 4u; h.budget_lo = (uint32_t)c->num_cus * 5u / 2u; h.budget_hi = (uint32_t)c->num_cus * 7u / 2u; }
     h.thr_down = 0.88f; h.thr_up = 0.97f;
-    if (c->trace_mode == 1 && c->trace_boost < 0) {
+    if (c->trace_mode == 1 && !c->rr_start && c->trace_boost < 0) {   // (the roulette estimator lives in the megakernel: plan_launch)
         // the split pipeline's traversal kernel: 3 .. 7 workgroups of four 64-VGPR waves per CU in steps of a half, "all" = 8 (device_scene.h gov_budget_next)
         h.budget_step = (uint32_t)c->num_cus / 2u; h.budget_lo = (uint32_t)c->num_cus * 3u; h.budget_hi = (uint32_t)c->num_cus * 7u;
         h.thr_down = 0.96f; h.thr_up = 1.02f;
@@ -2070,9 +2070,10 @@ static const OptionRow DEBUG_OPTIONS[] = {
     {"min_waves", &hr_ctx::min_waves, 4, 6, 0, "min_waves must be in [4,6]", 0},
     {"kchunk", &hr_ctx::kchunk, 0, 64, 0, "kchunk must be in [1,64], or 0 for the default", 0},
     {"node_unroll", &hr_ctx::node_unroll, 1, 2, 1, "node_unroll must be 1 or 2", 0},
-    {"tail_div", &hr_ctx::tail_div, 1, 0, 0, "", 0},
-    {"trace_grid", &hr_ctx::trace_grid, 1, 0, 0, "", 0},
-    {"trace_budget", &hr_ctx::trace_budget, 1, 0, 0, "", 0},
+    // (the three go into uint32_t fields, and the budget is handed on as budget + 1: nothing negative, not a number or beyond 2^31)
+    {"tail_div", &hr_ctx::tail_div, 0, 2147483648.0, 0, "tail_div must be in [0,2^31] (0 = no finer tail)", 0},
+    {"trace_grid", &hr_ctx::trace_grid, 0, 2147483648.0, 0, "trace_grid must be in [0,2^31] (0 = trace_wgs per CU)", 0},
+    {"trace_budget", &hr_ctx::trace_budget, 0, 2147483648.0, 0, "trace_budget must be in [0,2^31] (0 = every workgroup stays)", 0},
     {"trace_wgs", &hr_ctx::trace_wgs, 1, 8, 0, "trace_wgs must be in [1,8]", 0},
     {"seed_prio", &hr_ctx::seed_prio, 0, 3, 0, "seed_prio must be in [0,3]", 0},
     {"init_prio", &hr_ctx::init_prio, 0, 3, 0, "init_prio must be in [0,3]", 0},
@@ -2089,7 +2090,7 @@ static const OptionRow DEBUG_OPTIONS[] = {
 };
 static int apply_option(hr_ctx *c, const OptionRow &r, double value) {
     if (r.lo <= r.hi) {
-        bool ok = !(value < r.lo || value > r.hi);
+        bool ok = value >= r.lo && value <= r.hi;   // (false for a NaN)
         if (ok && r.step > 0) ok = std::fmod(value - r.lo, r.step) == 0.0;
         if (!ok) return fail(HR_ERR_INVALID, "%s", r.error);
     }
@@ -2141,10 +2142,13 @@ static int set_robust_buckets(hr_ctx *c, double value) {
     return HR_OK;
 }
 
+static const char *const RR_EXCLUDES_PRECISE = "russian_roulette and precise_shading 1 exclude each other (the roulette estimator has no f64 instantiation)";
 int hr_set_option(hr_ctx *c, const char *key, double value) {
     if (!c || !key) return fail(HR_ERR_INVALID, "hr_set_option: null argument");
     HIP_TRY(hipSetDevice(c->device));
     std::string k = key;
+    // the pair is refused where it is asked for, whichever comes second, and what was in force stays (hr_render keeps its own check)
+    if (k == "precise_shading" && value == 1 && c->rr_start) return fail(HR_ERR_UNSUPPORTED, "%s", RR_EXCLUDES_PRECISE);
     if (const OptionRow *row = find_row(PRODUCT_OPTIONS, [&](const OptionRow &r) { return k == r.key; })) return apply_option(c, *row, value);
     // per-pixel first and second moments of the per-sampling values, for the noise estimate, and how many samplings every pixel
     // has received: what a tile mask (hr_set_tile_mask) needs — the mask goes when the counts go
@@ -2183,9 +2187,13 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
     }
     if (k == "russian_roulette") {  // NOT image-preserving (see the header): 0 = off, else the first path iteration that plays
         if (value != 0 && (value < 2 || value > 9)) return fail(HR_ERR_INVALID, "russian_roulette must be 0 (off) or the first iteration that plays, in [2,9]");
+        if (value != 0 && c->precise_opt == 1) return fail(HR_ERR_UNSUPPORTED, "%s", RR_EXCLUDES_PRECISE);
+        int rc = sync_all(c);
+        if (rc) return rc;
         c->rr_start = (uint32_t)value;
-        resolve_modes(c);     // (automatic precise shading stands back: the roulette estimator has no f64 instantiation)
-        return HR_OK;
+        // automatic precise shading stands back (the roulette estimator has no f64 instantiation), so shading and pipeline in force may change
+        // here as they do under precise_shading and trace_mode: the governor starts over with the thresholds and the budget range of what runs
+        return govern_reset(c);
     }
     return fail(HR_ERR_INVALID, "unknown option '%s' (measurement knobs live behind hr_set_debug_option)", key);
 }

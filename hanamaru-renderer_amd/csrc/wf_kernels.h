@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256, 8) void wf_traverse_kernel(Scene sc, RenderPar
     uint32_t blocks = gridDim.x, boost_mask = rp.trace_boost;
     if (rp.gov) {
         const uint32_t b = rp.gov->bud[rp.gov_slot];
-        if (b > 1u && b - 1u < blocks) blocks = (b - 1u) / 16u * 16u;      // whole multiples of WF_SUBQ waves
+        if (b > 1u && b - 1u < blocks) blocks = max(16u, (b - 1u) / 16u * 16u);      // whole multiples of WF_SUBQ waves, never fewer than one per sub-queue
         if (blockIdx.x >= blocks) return;
         boost_mask = gov_trace_mask((int32_t)rp.gov->lvl[1][rp.gov_slot]);
     }

@@ -474,7 +474,8 @@ int hr_get_stats(hr_ctx *ctx, hr_stats *out);
  *                   (7 - 30 % on mesh scenes); the library takes the faster one for the scene.
  *                   -1 (default) = automatic: ON for scenes without triangle meshes (BASELINE config 2: small spheres are what multiplies an
  *                   fp32 ray's error, and there it costs little), OFF for the others; 0 = off; 1 = on.  hr_stats.shading_in_force says
- *                   what runs.  (1 excludes "russian_roulette"; -1 stands back when the roulette is on.)
+ *                   what runs.  (1 excludes "russian_roulette": whichever of the two is asked for second is refused with HR_ERR_UNSUPPORTED and
+ *                   what was in force stays; -1 stands back when the roulette is on.)
  *   "moments"       0 (default) / 1: keep per-pixel first and second moments of the per-sampling values for hr_noise_estimate (see there);
  *                   the image does not change by a bit
  *   "sample_counts" 0 (default) / 1: keep per-pixel counts of the samplings received, for hr_set_tile_mask / hr_select_tiles /

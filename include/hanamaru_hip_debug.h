@@ -16,6 +16,10 @@ extern "C" {
 /* Measurement / experiment knobs, kept out of hr_set_option so that a host cannot change the kernels' schedule — or produce a
  * garbage image — by a key string meant for a product option: "adv_den" / "leaf_den" (trace-kernel phase thresholds), "min_waves"
  * (4..6, occupancy variant of the trace kernel; only with quant_nodes = 1), "kchunk", "node_unroll" (1 | 2), "trace_wgs",
+ * "tail_div" (the last 1 / tail_div of a launch's tiles go out one sampling at a time; 0 = no finer tail; default 16), "trace_grid" (workgroups of the
+ * trace kernel's grid; 0 = trace_wgs per CU, default) and "trace_budget" (workgroups that stay, the governor's wave budget pinned; 0 = not pinned,
+ * default; the split pipeline's traversal kernel takes whole multiples of 16 workgroups, and a budget below 16 means 16) — each of the three a value
+ * in [0, 2^31]: negative values, NaN and anything larger are HR_ERR_INVALID and change nothing —,
  * "seed_mode" (2 = three-run seed kernel, default; 3 = its phase-shifted four-run form and 4 = its five-wave four-run form, both
  * slower, kept as measured experiments; 1 = producer / consumer kernel with a
  * ring of generator words; 0 = fused),

@@ -629,6 +629,16 @@ def test_error_paths(ha):
     for key, bad in [("adv_den", 0), ("leaf_den", 100), ("min_waves", 9), ("seed_mode", 5), ("seed_split", 10), ("nonsense", 1)]:
         with pytest.raises(ha.HipError):
             r.set_debug_option(key, bad)
+    # the three knobs that go into uint32_t fields unclamped: nothing negative, not a number or beyond 2^31 (the budget travels as budget + 1)
+    for key in ("tail_div", "trace_grid", "trace_budget"):
+        for bad in (-1, float("nan"), 2.0 ** 32, 2.0 ** 31 + 1, float("inf")):
+            with pytest.raises(ha.HipError) as e:
+                r.set_debug_option(key, bad)
+            assert e.value.code == -1 and key in str(e.value), (key, bad)
+        r.set_debug_option(key, 2.0 ** 31)
+        r.set_debug_option(key, {"tail_div": 16, "trace_grid": 0, "trace_budget": 0}[key])
+    with pytest.raises(ha.HipError):
+        r.set_debug_option("adv_den", float("nan"))      # (a NaN is inside no range)
     # the measurement knobs are not reachable through the product call: a host cannot ship a garbage image by key string
     for key in ("debug_skip", "seed_prof", "seed_mode", "seed_split", "seed_prio", "init_prio", "adv_den", "kchunk", "trace_wgs", "node_unroll"):
         with pytest.raises(ha.HipError):
