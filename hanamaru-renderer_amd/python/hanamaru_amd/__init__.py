@@ -340,6 +340,15 @@ def load_obj(path, matrix=None):
     return verts, faces
 
 
+# The planes a context hands out or takes in, per pixel of the region (hr_api.hip: PLANES): name -> (trailing shape, dtype).  "rgb8" is what
+# every hr_resolve* writes; the buckets' trailing shape starts with the K in force and is passed by the caller.
+_PLANES = {
+    "accumulator": ((3,), np.float32), "rgb8": ((3,), np.uint8), "moments": ((6,), np.float64), "noise": ((), np.float64),
+    "sample_counts": ((), np.uint32), "guides": ((8,), np.float32), "denoised": ((3,), np.float32), "buckets": ((3,), np.float64),
+    "robust": ((3,), np.float32), "robust_trim": ((), np.uint8),
+}
+
+
 class Renderer:
     """Thin wrapper over hr_ctx — mirrors the reference's Renderer trait usage (renderer.rs:20-99):
     render() accumulates samplings, resolve() is update_imgbuf."""
@@ -368,6 +377,12 @@ class Renderer:
         except Exception:
             pass
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
     def upload_scene(self, scene):
         self._scene = scene  # keep host memory alive during the call
         self._check(self.L.hr_upload_scene(self._h, scene.desc_ptr))
@@ -391,6 +406,24 @@ class Renderer:
 
     def _acc_hw(self):
         return (self._region[3], self._region[2]) if self._region else (self.height, self.width)
+
+    def _read_plane(self, fn, plane, *args, samplings=False, tail=None):
+        """fn(ctx, *args, out[, &samplings]) into a fresh array of the plane's shape; with `samplings` the pair (array, samplings word)."""
+        shape, dtype = _PLANES[plane]
+        out = np.empty(self._acc_hw() + (shape if tail is None else tail), dtype=dtype)
+        if not samplings:
+            self._check(fn(self._h, *args, out.ctypes.data))
+            return out
+        n = C.c_uint64()
+        self._check(fn(self._h, *args, out.ctypes.data, C.byref(n)))
+        return out, int(n.value)
+
+    def _write_plane(self, fn, plane, array, *args, tail=None):
+        """fn(ctx, array, *args) of an array that must have the plane's shape."""
+        shape, dtype = _PLANES[plane]
+        a = np.ascontiguousarray(array, dtype=dtype)
+        assert a.shape == self._acc_hw() + (shape if tail is None else tail)
+        self._check(fn(self._h, a.ctypes.data, *args))
 
     def bind_accumulator(self, device_ptr):
         self._check(self.L.hr_bind_accumulator(self._h, device_ptr))
@@ -428,19 +461,13 @@ class Renderer:
         self._check(self.L.hr_synchronize(self._h))
 
     def read_accumulator(self):
-        out = np.empty(self._acc_hw() + (3,), dtype=np.float32)
-        self._check(self.L.hr_read_accumulator(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_read_accumulator, "accumulator")
 
     def write_accumulator(self, acc):
-        a = np.ascontiguousarray(acc, dtype=np.float32)
-        assert a.shape == self._acc_hw() + (3,)
-        self._check(self.L.hr_write_accumulator(self._h, a.ctypes.data))
+        self._write_plane(self.L.hr_write_accumulator, "accumulator", acc)
 
     def resolve(self, samplings_done):
-        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
-        self._check(self.L.hr_resolve(self._h, samplings_done, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_resolve, "rgb8", samplings_done)
 
     def stats(self):
         s = Stats()
@@ -477,15 +504,10 @@ class Renderer:
     # ---- option "moments": per-pixel sample moments and the noise estimate (include/hanamaru_hip.h)
     def read_moments(self):
         """hr_read_moments: ((h, w, 6) float64 array {S1r, S1g, S1b, S2r, S2g, S2b}, samplings behind them)."""
-        out = np.empty(self._acc_hw() + (6,), dtype=np.float64)
-        n = C.c_uint64()
-        self._check(self.L.hr_read_moments(self._h, out.ctypes.data, C.byref(n)))
-        return out, int(n.value)
+        return self._read_plane(self.L.hr_read_moments, "moments", samplings=True)
 
     def write_moments(self, moments, samplings):
-        a = np.ascontiguousarray(moments, dtype=np.float64)
-        assert a.shape == self._acc_hw() + (6,)
-        self._check(self.L.hr_write_moments(self._h, a.ctypes.data, C.c_uint64(samplings)))
+        self._write_plane(self.L.hr_write_moments, "moments", moments, C.c_uint64(samplings))
 
     def noise_estimate(self, floor=0.01, threshold=0.05):
         """hr_noise_estimate: {samplings, pixels, pixels_above, mean_error, max_error} of the per-pixel relative standard error e."""
@@ -495,9 +517,7 @@ class Renderer:
 
     def noise_image(self, floor=0.01):
         """hr_read_noise_image: e of every pixel, (h, w) float64."""
-        out = np.empty(self._acc_hw(), dtype=np.float64)
-        self._check(self.L.hr_read_noise_image(self._h, float(floor), out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_read_noise_image, "noise", float(floor))
 
     # ---- adaptive sampling: option "sample_counts", the tile mask, the selection of tiles (include/hanamaru_hip.h)
     def _tiles_hw(self):
@@ -506,20 +526,14 @@ class Renderer:
 
     def read_sample_counts(self):
         """hr_read_sample_counts: (h, w) uint32, the samplings every pixel has received."""
-        out = np.empty(self._acc_hw(), dtype=np.uint32)
-        self._check(self.L.hr_read_sample_counts(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_read_sample_counts, "sample_counts")
 
     def write_sample_counts(self, counts):
-        a = np.ascontiguousarray(counts, dtype=np.uint32)
-        assert a.shape == self._acc_hw()
-        self._check(self.L.hr_write_sample_counts(self._h, a.ctypes.data))
+        self._write_plane(self.L.hr_write_sample_counts, "sample_counts", counts)
 
     def resolve_counted(self):
         """hr_resolve_counted: resolve() with every pixel's own count."""
-        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
-        self._check(self.L.hr_resolve_counted(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_resolve_counted, "rgb8")
 
     def set_tile_mask(self, mask):
         """hr_set_tile_mask: (tiles_y, tiles_x) array over the region's 4x4 tiles, nonzero = render; None removes the mask."""
@@ -551,14 +565,10 @@ class Renderer:
 
     def read_guides(self):
         """hr_read_guides: (h, w, 8) float32 {albedo rgb, normal xyz, depth, coverage}."""
-        out = np.empty(self._acc_hw() + (8,), dtype=np.float32)
-        self._check(self.L.hr_read_guides(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_read_guides, "guides")
 
     def write_guides(self, guides):
-        a = np.ascontiguousarray(guides, dtype=np.float32)
-        assert a.shape == self._acc_hw() + (8,)
-        self._check(self.L.hr_write_guides(self._h, a.ctypes.data))
+        self._write_plane(self.L.hr_write_guides, "guides", guides)
 
     def denoise(self, **params):
         """hr_denoise: the defaults, with any of levels, demodulate, sigma_color, sigma_normal, sigma_albedo, sigma_depth replaced."""
@@ -571,29 +581,19 @@ class Renderer:
 
     def read_denoised(self):
         """hr_read_denoised: (h, w, 3) float32 radiance."""
-        out = np.empty(self._acc_hw() + (3,), dtype=np.float32)
-        self._check(self.L.hr_read_denoised(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_read_denoised, "denoised")
 
     def resolve_denoised(self):
         """hr_resolve_denoised: resolve() of the denoised radiance."""
-        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
-        self._check(self.L.hr_resolve_denoised(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_resolve_denoised, "rgb8")
 
     # ---- option "robust_buckets": the sample buckets and the firefly-robust resolve (include/hanamaru_hip.h)
     def read_buckets(self):
         """hr_read_buckets: ((h, w, K, 3) float64 bucket sums — K from the size the library reports for the option —, samplings behind them)."""
-        k = self._robust_k
-        out = np.empty(self._acc_hw() + (max(k, 1), 3), dtype=np.float64)
-        n = C.c_uint64()
-        self._check(self.L.hr_read_buckets(self._h, out.ctypes.data, C.byref(n)))
-        return out, int(n.value)
+        return self._read_plane(self.L.hr_read_buckets, "buckets", samplings=True, tail=(max(self._robust_k, 1), 3))
 
     def write_buckets(self, buckets, samplings):
-        a = np.ascontiguousarray(buckets, dtype=np.float64)
-        assert a.shape == self._acc_hw() + (self._robust_k, 3)
-        self._check(self.L.hr_write_buckets(self._h, a.ctypes.data, C.c_uint64(samplings)))
+        self._write_plane(self.L.hr_write_buckets, "buckets", buckets, C.c_uint64(samplings), tail=(self._robust_k, 3))
 
     def robust(self):
         """hr_robust: the robust radiance R and its trim plane from the buckets."""
@@ -601,21 +601,15 @@ class Renderer:
 
     def read_robust(self):
         """hr_read_robust: (h, w, 3) float32 radiance."""
-        out = np.empty(self._acc_hw() + (3,), dtype=np.float32)
-        self._check(self.L.hr_read_robust(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_read_robust, "robust")
 
     def read_robust_trim(self):
         """hr_read_robust_trim: (h, w) uint8, the buckets dropped at either end."""
-        out = np.empty(self._acc_hw(), dtype=np.uint8)
-        self._check(self.L.hr_read_robust_trim(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_read_robust_trim, "robust_trim")
 
     def resolve_robust(self):
         """hr_resolve_robust: resolve() of the robust radiance."""
-        out = np.empty(self._acc_hw() + (3,), dtype=np.uint8)
-        self._check(self.L.hr_resolve_robust(self._h, out.ctypes.data))
-        return out
+        return self._read_plane(self.L.hr_resolve_robust, "rgb8")
 
     def debug_draws(self, sampling, first_path, num_paths, window):
         out = np.empty((num_paths, window), dtype=np.uint64)

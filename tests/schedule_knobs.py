@@ -4,7 +4,8 @@ How work is handed out never changes the image: every path leaves its radiance i
 records in a fixed order, so work-unit size, grid size, wave budget, priorities and queue layout are free to move.  KNOBS lists
 every option that may only move those — tests/test_schedule_gpu.py renders each value of each row and compares with the render at the defaults,
 bit for bit — and OTHER_OPTIONS lists every other key hr_set_option / hr_set_debug_option know, with the reason it is no row and the test that
-covers it.  tests/test_schedule_cpu.py reads the keys out of hr_api.hip: a new option fails there until it is in one of the two.
+covers it.  Both carry every key's setter and default (ALL_DEFAULTS, SETTERS: what tests/gpu_helpers.py's options() restores to).
+tests/test_schedule_cpu.py reads the keys and the defaults out of hr_api.hip: a new option fails there until it is in one of the two.
 
 No GPU in this module."""
 from collections import namedtuple, OrderedDict
@@ -71,43 +72,47 @@ def settings(pipeline, full=True, keys=None, combined=True):
     return out
 
 
-def apply(renderer, setting):
-    for key, value in setting.items():
-        getattr(renderer, KNOBS[key].setter)(key, value)
-
-
-def restore(renderer):
-    apply(renderer, DEFAULTS)
-
-
-# Every other key of hr_set_option / hr_set_debug_option: why it is no row above, and the test that covers it.
+# Every other key of hr_set_option / hr_set_debug_option: why it is no row above, the test that covers it, its setter and its default (hr_ctx's
+# initialiser again; rng_window is fixed at the library's ISAAC_TAIL, the only value it takes).
 #   axis     tests/test_schedule_gpu.py sets it itself: the sweeps run under both of its values (or with it on and off)
 #   image    it changes the image, the tree or a plane, or what a later call does
 #   variant  another instruction stream or another seed kernel for the same bits, pinned at full size by a test of its own
-OTHER_OPTIONS = {
-    "trace_mode": ("axis", "tests/test_schedule_gpu.py (every sweep, both values); test_gpu_parity.py::test_kernel_variants_render_the_same_bits"),
-    "precise_shading": ("axis", "tests/test_schedule_gpu.py (every sweep, 0 and 1); test_gpu_parity.py::test_precise_shading_defaults_and_finite_radiance"),
-    "counters": ("axis", "tests/test_schedule_gpu.py::test_accounting_sweep; test_gpu_parity.py::test_kernel_variants_render_the_same_bits"),
-    "batch": ("image", "the fp32 accumulator depends on the launch cuts: test_gpu_parity.py::test_sharding_and_batching_are_exact_partitions"),
-    "sample_counts": ("image", "a plane: tests/test_adaptive_gpu.py::test_counts"),
-    "moments": ("image", "a plane: tests/test_moments_gpu.py"),
-    "robust_buckets": ("image", "a plane: tests/test_robust_gpu.py"),
-    "guide_bounces": ("image", "the guide planes: tests/test_guide_chain_gpu.py"),
+Other = namedtuple("Other", "kind covered_by setter default")
+P, D = "set_option", "set_debug_option"
+
+OTHER_OPTIONS = {key: Other(*row) for key, row in {
+    "trace_mode": ("axis", "tests/test_schedule_gpu.py (every sweep, both values); test_gpu_parity.py::test_kernel_variants_render_the_same_bits", D, -1),
+    "precise_shading": ("axis", "tests/test_schedule_gpu.py (every sweep, 0 and 1); test_gpu_parity.py::test_precise_shading_defaults_and_finite_radiance", P, -1),
+    "counters": ("axis", "tests/test_schedule_gpu.py::test_accounting_sweep; test_gpu_parity.py::test_kernel_variants_render_the_same_bits", P, 0),
+    "batch": ("image", "the fp32 accumulator depends on the launch cuts: test_gpu_parity.py::test_sharding_and_batching_are_exact_partitions", P, 0),
+    "sample_counts": ("image", "a plane: tests/test_adaptive_gpu.py::test_counts", P, 0),
+    "moments": ("image", "a plane: tests/test_moments_gpu.py", P, 0),
+    "robust_buckets": ("image", "a plane: tests/test_robust_gpu.py", P, 0),
+    "guide_bounces": ("image", "the guide planes: tests/test_guide_chain_gpu.py", P, 0),
     "russian_roulette": ("image", "another estimator: test_gpu_parity.py::test_russian_roulette_is_unbiased_and_off_by_default; "
-                                  "tests/test_schedule_gpu.py::test_roulette_and_precise_shading_refuse_each_other"),
-    "quant_nodes": ("image", "the tree's record format, next upload: test_gpu_parity.py::test_kernel_variants_render_the_same_bits"),
-    "bvh_builder": ("image", "the tree: test_gpu_parity.py::test_device_bvh_build_is_interchangeable"),
-    "max_leaf": ("image", "the tree: test_gpu_parity.py::test_device_bvh_build_is_interchangeable"),
-    "split_ratio": ("image", "the tree: tests/test_bvh_edges_gpu.py"),
-    "ploc_top": ("image", "the tree: tests/test_bvh_edges_gpu.py"),
-    "max_tail_gib": ("image", "caps the samplings per launch, i.e. the launch cuts: test_gpu_parity.py::test_config5_4k_crops"),
-    "rng_window": ("image", "fixed in this build: test_gpu_parity.py::test_error_paths"),
-    "nee_cull": ("image", "which shadow rays are traced (same accumulator, other ray counts): test_gpu_parity.py::test_nee_culls_do_not_change_a_bit"),
-    "draw_residuals": ("image", "precise shading without the draws' residuals is another image: tests/test_seed_prerun.py"),
-    "debug_skip": ("image", "a garbage image on purpose (timing experiments): test_gpu_parity.py::test_error_paths"),
-    "seed_prof": ("image", "the seed kernel's timing build fills hr_stats.seed_phase_cycles: tests/test_adaptive_gpu.py (refused under a tile mask)"),
-    "min_waves": ("variant", "test_gpu_parity.py::test_kernel_variants_render_the_same_bits"),
-    "seed_mode": ("variant", "test_gpu_parity.py::test_seed_kernels_are_bit_identical, ::test_seed_kernels_agree_on_odd_shapes"),
-    "seed_split": ("variant", "test_gpu_parity.py::test_seed_kernels_are_bit_identical"),
-    "seed_prerun": ("variant", "tests/test_seed_prerun.py"),
-}
+                                  "tests/test_schedule_gpu.py::test_roulette_and_precise_shading_refuse_each_other", P, 0),
+    "quant_nodes": ("image", "the tree's record format, next upload: test_gpu_parity.py::test_kernel_variants_render_the_same_bits", P, 1),
+    "bvh_builder": ("image", "the tree: test_gpu_parity.py::test_device_bvh_build_is_interchangeable", P, -1),
+    "max_leaf": ("image", "the tree: test_gpu_parity.py::test_device_bvh_build_is_interchangeable", P, 4),
+    "split_ratio": ("image", "the tree: tests/test_bvh_edges_gpu.py", P, -1.0),
+    "ploc_top": ("image", "the tree: tests/test_bvh_edges_gpu.py", D, 8192),
+    "max_tail_gib": ("image", "caps the samplings per launch, i.e. the launch cuts: test_gpu_parity.py::test_config5_4k_crops", P, 20),
+    "rng_window": ("image", "fixed in this build: test_gpu_parity.py::test_error_paths", P, 64),
+    "nee_cull": ("image", "which shadow rays are traced (same accumulator, other ray counts): test_gpu_parity.py::test_nee_culls_do_not_change_a_bit", D, 7),
+    "draw_residuals": ("image", "precise shading without the draws' residuals is another image: tests/test_seed_prerun.py", D, 1),
+    "debug_skip": ("image", "a garbage image on purpose (timing experiments): test_gpu_parity.py::test_error_paths", D, 0),
+    "seed_prof": ("image", "the seed kernel's timing build fills hr_stats.seed_phase_cycles: tests/test_adaptive_gpu.py (refused under a tile mask)", D, 0),
+    "min_waves": ("variant", "test_gpu_parity.py::test_kernel_variants_render_the_same_bits", D, 5),
+    "seed_mode": ("variant", "test_gpu_parity.py::test_seed_kernels_are_bit_identical, ::test_seed_kernels_agree_on_odd_shapes", D, 2),
+    "seed_split": ("variant", "test_gpu_parity.py::test_seed_kernels_are_bit_identical", D, 16),
+    "seed_prerun": ("variant", "tests/test_seed_prerun.py", D, 1),
+}.items()}
+
+def split(setting):
+    """(options, debug options) of a setting: what gpu_helpers.options takes"""
+    return tuple({k: v for k, v in setting.items() if SETTERS[k] == setter} for setter in (P, D))
+
+
+# every option's default and setter, the knobs and the others together: what tests/gpu_helpers.py's options() restores to, and through what
+ALL_DEFAULTS = dict(DEFAULTS, **{key: o.default for key, o in OTHER_OPTIONS.items()})
+SETTERS = dict({k.key: k.setter for k in KNOBS.values()}, **{key: o.setter for key, o in OTHER_OPTIONS.items()})

@@ -7,6 +7,7 @@ import pytest
 
 import ckpt
 from cli import ASSETS, run_cli
+from gpu_helpers import error_of, renderer, retarget, same
 from test_moments_cpu import ulp_distance
 
 pytestmark = pytest.mark.gpu
@@ -45,39 +46,12 @@ def _pixels(mask):
     return np.kron(np.asarray(mask) != 0, np.ones((4, 4), bool))[:RH, :RW]
 
 
-def _renderer(ha, sc, opts=None, dbg=None, target="frame", moments=True, counts=True):
-    r = ha.Renderer(0)
-    for k, v in (opts or {}).items():
-        r.set_option(k, v)
-    for k, v in (dbg or {}).items():
-        r.set_debug_option(k, v)
-    r.upload_scene(sc)
-    _retarget(r, target, moments, counts)
-    return r
+def _make(ha, sc, opts=None, dbg=None, target="frame", moments=True, counts=True):
+    return renderer(ha, sc, opts, dbg, *TARGETS[target], moments=moments, counts=counts)
 
 
-def _retarget(r, target, moments=True, counts=True):
-    frame, region = TARGETS[target]
-    r.set_resolution(*frame)
-    if region is not None:
-        r.set_region(*region)
-    r.set_option("moments", 1 if moments else 0)
-    r.set_option("sample_counts", 1 if counts else 0)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _code(ha, fn, *a):
-    with pytest.raises(ha.HipError) as e:
-        fn(*a)
-    return e.value.code, str(e.value)
+def _aim(r, target, moments=True, counts=True):
+    retarget(r, *TARGETS[target], moments=moments, counts=counts)
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -85,11 +59,11 @@ def _code(ha, fn, *a):
 def test_masked_render_is_the_unmasked_render_on_its_tiles(ha, scenes, name, mode):
     sc, _ = scenes(name)
     opts, dbg = MODES[mode]
-    full, masked = _renderer(ha, sc, opts, dbg, counts=False), _renderer(ha, sc, opts, dbg)
+    full, masked = _make(ha, sc, opts, dbg, counts=False), _make(ha, sc, opts, dbg)
     try:
         for target in sorted(TARGETS):
-            _retarget(full, target, counts=False)    # (the reference runs the kernels without counts: the counting forms change neither buffer)
-            _retarget(masked, target)
+            _aim(full, target, counts=False)    # (the reference runs the kernels without counts: the counting forms change neither buffer)
+            _aim(masked, target)
             for batch in (1, 5, 0):
                 full.set_option("batch", batch)
                 masked.set_option("batch", batch)
@@ -106,15 +80,15 @@ def test_masked_render_is_the_unmasked_render_on_its_tiles(ha, scenes, name, mod
                         masked.render(*args)
                         macc, (mmom, mn) = masked.read_accumulator(), masked.read_moments()
                         assert mn == n, what
-                        assert _same(mmom, np.where(pix[..., None], mom, 0.0)), what
+                        assert same(mmom, np.where(pix[..., None], mom, 0.0)), what
                         if batch:    # (automatic: a sparse mask takes more samplings per launch, and the fp32 accumulator depends on the launch cuts)
-                            assert _same(macc, np.where(pix[..., None], acc, np.float32(0))), what
+                            assert same(macc, np.where(pix[..., None], acc, np.float32(0))), what
                         assert np.array_equal(masked.read_sample_counts(), np.where(pix, n, 0).astype(np.uint32)), what
                     # all tiles == no mask
                     masked.clear()
                     masked.set_tile_mask(None)
                     masked.render(*args)
-                    assert _same(masked.read_accumulator(), acc) and _same(masked.read_moments()[0], mom), (name, mode, target, batch, args)
+                    assert same(masked.read_accumulator(), acc) and same(masked.read_moments()[0], mom), (name, mode, target, batch, args)
     finally:
         full.close()
         masked.close()
@@ -122,23 +96,19 @@ def test_masked_render_is_the_unmasked_render_on_its_tiles(ha, scenes, name, mod
 
 def test_none_active_leaves_the_accumulator(ha, scenes):
     sc, _ = scenes("cornell_mini")
-    r = _renderer(ha, sc)
-    try:
+    with _make(ha, sc) as r:
         r.render(1, 4)
         before, launches = r.read_accumulator(), r.stats()["trace_launches"]
         r.set_tile_mask(MASKS["none"])
         r.render(4, 9)                        # HR_OK, nothing enqueued
-        assert _same(r.read_accumulator(), before) and r.stats()["trace_launches"] == launches
+        assert same(r.read_accumulator(), before) and r.stats()["trace_launches"] == launches
         assert r.tile_mask()[1] == 0 and (r.read_sample_counts() == 3).all()
-    finally:
-        r.close()
 
 
 @pytest.mark.parametrize("target", sorted(TARGETS))
 def test_counts(ha, scenes, target):
     sc, _ = scenes("rtcamp6_v3_1")
-    r = _renderer(ha, sc, target=target)
-    try:
+    with _make(ha, sc, target=target) as r:
         assert not r.read_sample_counts().any()
         expect = np.zeros((RH, RW), np.int64)
         for mask, args in [(None, (1, 5, 1)), (MASKS["checker"], (5, 9, 1)), (MASKS["scattered"], (9, 20, 2)), (MASKS["none"], (20, 25, 1)), (MASKS["last"], (20, 23, 1))]:
@@ -154,7 +124,7 @@ def test_counts(ha, scenes, target):
         data = rng.integers(0, 2 ** 32, (RH, RW), dtype=np.uint64).astype(np.uint32)
         acc = r.read_accumulator()
         r.write_sample_counts(data)
-        assert np.array_equal(r.read_sample_counts(), data) and _same(r.read_accumulator(), acc)
+        assert np.array_equal(r.read_sample_counts(), data) and same(r.read_accumulator(), acc)
         r.write_accumulator(acc * 2)                                    # does not touch the counts
         assert np.array_equal(r.read_sample_counts(), data)
         # hr_clear zeroes the counts and keeps the mask
@@ -176,16 +146,13 @@ def test_counts(ha, scenes, target):
         r.set_tile_mask(np.eye(2, 3, dtype=np.uint8))
         assert r.tile_mask()[1] == 2
         r.set_option("sample_counts", 0)
-        assert r.tile_mask()[1] == 6 and _code(ha, r.read_sample_counts)[0] == HR_ERR_INVALID
-    finally:
-        r.close()
+        assert r.tile_mask()[1] == 6 and error_of(ha, r.read_sample_counts)[0] == HR_ERR_INVALID
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_resolve_counted(ha, scenes, name):
     sc, _ = scenes(name)
-    r = _renderer(ha, sc)
-    try:
+    with _make(ha, sc) as r:
         for S in (6, 24):     # 1 / 24 and 1 / 96: not powers of two
             r.clear()
             r.render(1, S + 1)
@@ -205,8 +172,6 @@ def test_resolve_counted(ha, scenes, name):
             got = r.resolve_counted()
             r.write_sample_counts(np.full((RH, RW), S))
             assert np.array_equal(got, r.resolve(S)) and np.array_equal(got, r.resolve_counted())
-    finally:
-        r.close()
 
 
 def _noise_reference(mom, n, floor):
@@ -230,16 +195,15 @@ def _tile_max(img):
 @pytest.mark.parametrize("name", SCENES)
 def test_estimate_with_per_pixel_counts(ha, scenes, name):
     sc, _ = scenes(name)
-    r = _renderer(ha, sc)
-    try:
+    with _make(ha, sc) as r:
         r.render(1, 2)
-        assert _code(ha, r.noise_image, 0.01)[0] == HR_ERR_INVALID            # every count is 1
+        assert error_of(ha, r.noise_image, 0.01)[0] == HR_ERR_INVALID            # every count is 1
         r.clear()
         r.set_tile_mask(MASKS["first"])
         r.render(1, 9)
-        code, text = _code(ha, r.noise_estimate, 0.01, 0.05)                  # 8 samplings issued, but most pixels have none
+        code, text = error_of(ha, r.noise_estimate, 0.01, 0.05)                  # 8 samplings issued, but most pixels have none
         assert code == HR_ERR_INVALID and "0 samplings" in text
-        assert _code(ha, r.select_tiles, 0.01, 0.05)[0] == HR_ERR_INVALID
+        assert error_of(ha, r.select_tiles, 0.01, 0.05)[0] == HR_ERR_INVALID
         r.set_tile_mask(None)
         r.clear()
         r.render(1, 9)
@@ -254,16 +218,13 @@ def test_estimate_with_per_pixel_counts(ha, scenes, name):
             assert d.max() <= 4
             est = r.noise_estimate(floor, 0.05)
             assert est["samplings"] == 20 and est["pixels"] == RW * RH and est["max_error"] == img.max() and est["pixels_above"] == int((img > 0.05).sum())
-    finally:
-        r.close()
 
 
 @pytest.mark.parametrize("name", SCENES)
 @pytest.mark.parametrize("target", sorted(TARGETS))
 def test_select_tiles(ha, scenes, name, target):
     sc, _ = scenes(name)
-    r = _renderer(ha, sc, target=target)
-    try:
+    with _make(ha, sc, target=target) as r:
         r.render(1, 17)
         floor = 0.01
         tmax = _tile_max(r.noise_image(floor))
@@ -287,15 +248,13 @@ def test_select_tiles(ha, scenes, name, target):
         r.set_tile_mask(None)
         tmax2 = _tile_max(r.noise_image(floor))
         assert r.select_tiles(floor, thr) == int((tmax2 > thr).sum())
-    finally:
-        r.close()
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_end_to_end_prefix_property(ha, scenes, name):
     """16 uniform samplings, then four rounds of select / 16 more: every pixel holds the moments of a uniform render of samplings 1 .. its count."""
     sc, _ = scenes(name)
-    a, u = _renderer(ha, sc), _renderer(ha, sc, counts=False)
+    a, u = _make(ha, sc), _make(ha, sc, counts=False)
     try:
         snaps = {}
         for k in range(1, 6):
@@ -312,7 +271,7 @@ def test_end_to_end_prefix_property(ha, scenes, name):
         assert n == 80 and len(values) >= 2 and set(values) <= set(snaps)
         for v in values:
             sel = counts == v
-            assert _same(mom[sel], snaps[v][sel]), (name, v)
+            assert same(mom[sel], snaps[v][sel]), (name, v)
         assert a.stats()["paths"] == 4 * int(counts.sum())
     finally:
         a.close()
@@ -321,34 +280,33 @@ def test_end_to_end_prefix_property(ha, scenes, name):
 
 def test_refusals(ha, scenes):
     sc, _ = scenes("cornell_mini")
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         r.upload_scene(sc)
-        assert _code(ha, r.set_option, "sample_counts", 1)[0] == HR_ERR_NO_TARGET
+        assert error_of(ha, r.set_option, "sample_counts", 1)[0] == HR_ERR_NO_TARGET
         r.set_resolution(RW, RH)
-        code, text = _code(ha, r.set_tile_mask, MASKS["checker"])
+        code, text = error_of(ha, r.set_tile_mask, MASKS["checker"])
         assert code == HR_ERR_INVALID and "sample_counts" in text
-        assert _code(ha, r.read_sample_counts)[0] == HR_ERR_INVALID and _code(ha, r.resolve_counted)[0] == HR_ERR_INVALID
-        assert _code(ha, r.select_tiles, 0.01, 0.05)[0] == HR_ERR_INVALID
-        assert _code(ha, r.set_option, "sample_counts", 2)[0] == HR_ERR_INVALID
+        assert error_of(ha, r.read_sample_counts)[0] == HR_ERR_INVALID and error_of(ha, r.resolve_counted)[0] == HR_ERR_INVALID
+        assert error_of(ha, r.select_tiles, 0.01, 0.05)[0] == HR_ERR_INVALID
+        assert error_of(ha, r.set_option, "sample_counts", 2)[0] == HR_ERR_INVALID
         r.render_debug(2)                                # allowed while the option is off
         r.clear()
         r.set_option("sample_counts", 1)
-        assert _code(ha, r.select_tiles, 0.01, 0.05)[0] == HR_ERR_INVALID     # needs the moments too
-        assert _code(ha, r.render_debug, 2)[0] == HR_ERR_UNSUPPORTED
+        assert error_of(ha, r.select_tiles, 0.01, 0.05)[0] == HR_ERR_INVALID     # needs the moments too
+        assert error_of(ha, r.render_debug, 2)[0] == HR_ERR_UNSUPPORTED
         r.set_tile_mask(MASKS["checker"])
-        code, text = _code(ha, r.render_debug, 2)
+        code, text = error_of(ha, r.render_debug, 2)
         assert code == HR_ERR_UNSUPPORTED and "tile mask" in text
         rays = np.array([[0, 0, 5, 0, 0, -1]], dtype=np.float32)
         for fn, args in [(r.debug_intersect, (rays,)), (r.debug_trace, (rays,)), (r.debug_path_log, (1,)), (r.debug_draws, (1, 0, 64, 8)), (r.debug_wf_profile, (1, 1))]:
-            code, text = _code(ha, fn, *args)
+            code, text = error_of(ha, fn, *args)
             assert code == HR_ERR_UNSUPPORTED and "tile mask" in text, fn
         # option combinations that have no kernel over a tile list
         for setter, key, on, off, word in [(r.set_option, "counters", 1, 0, "counters"), (r.set_option, "russian_roulette", 3, 0, "russian_roulette"),
                                            (r.set_debug_option, "min_waves", 4, 5, "min_waves"), (r.set_debug_option, "seed_mode", 1, 2, "seed_mode"),
                                            (r.set_debug_option, "seed_prof", 1, 0, "seed_prof")]:
             setter(key, on)
-            code, text = _code(ha, r.render, 1, 3)
+            code, text = error_of(ha, r.render, 1, 3)
             assert code == HR_ERR_UNSUPPORTED and word in text and "tile mask" in text, key
             setter(key, off)
         assert not r.read_sample_counts().any()          # nothing of the refused renders arrived
@@ -359,41 +317,36 @@ def test_refusals(ha, scenes):
         r.set_option("counters", 1)
         r.render(3, 4)
         r.synchronize()
-    finally:
-        r.close()
 
 
 def test_options_start_each_other_over(ha, scenes):
     """Switching "moments" or "sample_counts" on zeroes the other one's buffer (the two cover the same samplings) and leaves the accumulator; set
     on again while on it keeps what has been gathered.  On the frame and on the region of the same size (sides that are no multiples of 4)."""
     sc, _ = scenes("cornell_mini")
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         r.upload_scene(sc)
         for target in sorted(TARGETS):
-            _retarget(r, target, moments=True, counts=False)
+            _aim(r, target, moments=True, counts=False)
             r.render(1, 3)
             acc, (mom, n) = r.read_accumulator(), r.read_moments()
             assert n == 2 and mom.shape == (RH, RW, 6) and mom.any() and acc.any(), target
             r.set_option("sample_counts", 1)
             mom, n = r.read_moments()
             assert n == 0 and not mom.any(), target
-            assert _same(r.read_accumulator(), acc), target
+            assert same(r.read_accumulator(), acc), target
             counts = r.read_sample_counts()
             assert counts.shape == (RH, RW) and not counts.any(), target
             r.render(3, 5)
             acc, (mom, n), counts = r.read_accumulator(), r.read_moments(), r.read_sample_counts()
             assert (counts == 2).all() and n == 2 and mom.any(), target
             r.set_option("sample_counts", 1)                  # already on: nothing changes
-            assert _same(r.read_accumulator(), acc) and _same(r.read_moments()[0], mom) and r.read_moments()[1] == 2, target
+            assert same(r.read_accumulator(), acc) and same(r.read_moments()[0], mom) and r.read_moments()[1] == 2, target
             assert np.array_equal(r.read_sample_counts(), counts), target
             r.set_option("moments", 0)
             r.set_option("moments", 1)
-            assert not r.read_sample_counts().any() and _same(r.read_accumulator(), acc), target
+            assert not r.read_sample_counts().any() and same(r.read_accumulator(), acc), target
             mom, n = r.read_moments()
             assert n == 0 and not mom.any(), target
-    finally:
-        r.close()
 
 
 def test_debug_refusal_precedence(ha, scenes):
@@ -409,37 +362,28 @@ def test_debug_refusal_precedence(ha, scenes):
         return [(r.debug_path_log, (1,)), (r.debug_wf_profile, (1, 1)), (r.debug_intersect, (rays,)), (r.debug_trace, (rays,))]
 
     (fw, fh), region = TARGETS["region"]
-    r = ha.Renderer(0)                                      # a resolution and a region, no scene
-    try:
+    with ha.Renderer(0) as r:                                      # a resolution and a region, no scene
         r.set_resolution(fw, fh)
         r.set_region(*region)
         for fn, args in four(r):
-            code, text = _code(ha, fn, *args)
+            code, text = error_of(ha, fn, *args)
             assert code == HR_ERR_UNSUPPORTED and "region" in text, fn
         r.set_resolution(fw, fh)                            # full frame again
         for fn, args in four(r):
-            assert _code(ha, fn, *args)[0] == HR_ERR_NO_SCENE, fn
-    finally:
-        r.close()
+            assert error_of(ha, fn, *args)[0] == HR_ERR_NO_SCENE, fn
     sc, _ = scenes("cornell_mini")
-    r = ha.Renderer(0)                                      # a scene, no resolution
-    try:
+    with ha.Renderer(0) as r:                                      # a scene, no resolution
         r.upload_scene(sc)
-        assert _code(ha, r.debug_draws, 1, 0, 64, 8)[0] == HR_ERR_NO_TARGET
-        assert _code(ha, r.debug_path_log, 1)[0] == HR_ERR_NO_TARGET
-    finally:
-        r.close()
-    r = ha.Renderer(0)                                      # a region, counts and a mask: the region is what is named
-    try:
+        assert error_of(ha, r.debug_draws, 1, 0, 64, 8)[0] == HR_ERR_NO_TARGET
+        assert error_of(ha, r.debug_path_log, 1)[0] == HR_ERR_NO_TARGET
+    with ha.Renderer(0) as r:                                      # a region, counts and a mask: the region is what is named
         r.set_resolution(fw, fh)
         r.set_region(*region)
         r.set_option("sample_counts", 1)
         r.set_tile_mask(MASKS["checker"])
         for fn, args in four(r) + [(r.debug_draws, (1, 0, 64, 8)), (path_draws, (r,))]:
-            code, text = _code(ha, fn, *args)
+            code, text = error_of(ha, fn, *args)
             assert code == HR_ERR_UNSUPPORTED and "region" in text, fn
-    finally:
-        r.close()
 
 
 def _checkpoint_counts(path, w, h):
@@ -455,14 +399,11 @@ def test_cli_adaptive(tmp_path, ha, scenes):
     w, h = 64, 48
     sc, _ = scenes("cornell_mini")
     # a threshold between the tile maxima after the first phase: some tiles stop at the first check, some go on
-    r = _renderer(ha, sc, counts=False)
-    try:
+    with _make(ha, sc, counts=False) as r:
         r.set_resolution(w, h)
         r.set_option("moments", 1)
         r.render(1, 9)
         img = r.noise_image(0.01)
-    finally:
-        r.close()
     thr = float(np.median(img.reshape(h // 4, 4, w // 4, 4).max(axis=(1, 3))))
     plain = ["--assets", ASSETS, "-w", str(w), "-h", str(h), "--scene", "cornell_mini", "-t", "600"]
     base = plain + ["--noise-check", "8", "--adaptive", repr(thr)]

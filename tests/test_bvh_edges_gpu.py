@@ -9,27 +9,16 @@ import numpy as np
 import pytest
 
 import bvh_edge_scenes as bes
+from gpu_helpers import options
+from schedule_knobs import ALL_DEFAULTS
 
 pytestmark = pytest.mark.gpu
 
-PLOC_TOP_DEFAULT = 8192
-DEFAULTS = {"bvh_builder": -1, "max_leaf": 4, "quant_nodes": 1, "split_ratio": -1.0}
 
-
-def _restore(gpu):
-    for k, v in DEFAULTS.items():
-        gpu.set_option(k, v)
-    gpu.set_debug_option("ploc_top", PLOC_TOP_DEFAULT)
-
-
-def _upload_and_query(gpu, ha, case, builder, max_leaf=4, quant=1, split_ratio=-1.0, ploc_top=PLOC_TOP_DEFAULT):
+def _upload_and_query(gpu, ha, case, builder, max_leaf=4, quant=1, split_ratio=-1.0, ploc_top=ALL_DEFAULTS["ploc_top"]):
     """upload under the options, check the stats and that the two walks agree to the bit; returns (hits, elements, stats)"""
-    gpu.set_option("bvh_builder", builder)
-    gpu.set_option("max_leaf", max_leaf)
-    gpu.set_option("quant_nodes", quant)
-    gpu.set_option("split_ratio", split_ratio)
-    gpu.set_debug_option("ploc_top", ploc_top)
-    gpu.upload_scene(case.scene_holder(ha))          # raises unless hr_upload_scene returns HR_OK
+    with options(gpu, {"bvh_builder": builder, "max_leaf": max_leaf, "quant_nodes": quant, "split_ratio": split_ratio}, {"ploc_top": ploc_top}):
+        gpu.upload_scene(case.scene_holder(ha))          # raises unless hr_upload_scene returns HR_OK
     st = gpu.stats()
     what = (case.name, "builder %d max_leaf %d quant %d split %g ploc_top %d" % (builder, max_leaf, quant, split_ratio, ploc_top))
     nt, ns, nc = case.g.counts
@@ -48,29 +37,26 @@ def test_edge_case_on_the_device(gpu, ha, name):
     case = bes.get(name)
     n = sum(case.g.counts)
     ms = {}
-    try:
-        base, base_el, _ = _upload_and_query(gpu, ha, case, 0)
-        bes.check_against_brute(case, base, base_el, "builder 0")
-        for max_leaf in (1, 4, 15):
+    base, base_el, _ = _upload_and_query(gpu, ha, case, 0)
+    bes.check_against_brute(case, base, base_el, "builder 0")
+    for max_leaf in (1, 4, 15):
+        for builder in (0, 1, 2):
+            got, gel, st = _upload_and_query(gpu, ha, case, builder, max_leaf=max_leaf)
+            bes.check_same_hits(case, got, gel, base, base_el, "builder %d max_leaf %d" % (builder, max_leaf))
+            if max_leaf == 4:
+                ms[builder] = st["bvh_build_ms"]
+    if bes.in_group(name, "ADE"):
+        for builder in (0, 1, 2):
+            got, gel, _ = _upload_and_query(gpu, ha, case, builder, quant=0)
+            bes.check_same_hits(case, got, gel, base, base_el, "builder %d, 32-byte records" % builder)
+    for top in [1, 2, 64] + ([n - 1, n] if bes.in_group(name, "A") and n > 2 else []):
+        got, gel, _ = _upload_and_query(gpu, ha, case, 2, ploc_top=top)
+        bes.check_same_hits(case, got, gel, base, base_el, "ploc_top %d" % top)
+    if bes.in_group(name, "DFG"):
+        for ratio in (0.0, 1.01, 1000.0):
             for builder in (0, 1, 2):
-                got, gel, st = _upload_and_query(gpu, ha, case, builder, max_leaf=max_leaf)
-                bes.check_same_hits(case, got, gel, base, base_el, "builder %d max_leaf %d" % (builder, max_leaf))
-                if max_leaf == 4:
-                    ms[builder] = st["bvh_build_ms"]
-        if bes.in_group(name, "ADE"):
-            for builder in (0, 1, 2):
-                got, gel, _ = _upload_and_query(gpu, ha, case, builder, quant=0)
-                bes.check_same_hits(case, got, gel, base, base_el, "builder %d, 32-byte records" % builder)
-        for top in [1, 2, 64] + ([n - 1, n] if bes.in_group(name, "A") and n > 2 else []):
-            got, gel, _ = _upload_and_query(gpu, ha, case, 2, ploc_top=top)
-            bes.check_same_hits(case, got, gel, base, base_el, "ploc_top %d" % top)
-        if bes.in_group(name, "DFG"):
-            for ratio in (0.0, 1.01, 1000.0):
-                for builder in (0, 1, 2):
-                    got, gel, _ = _upload_and_query(gpu, ha, case, builder, split_ratio=ratio)
-                    bes.check_same_hits(case, got, gel, base, base_el, "builder %d split_ratio %g" % (builder, ratio))
-    finally:
-        _restore(gpu)
+                got, gel, _ = _upload_and_query(gpu, ha, case, builder, split_ratio=ratio)
+                bes.check_same_hits(case, got, gel, base, base_el, "builder %d split_ratio %g" % (builder, ratio))
     print("%s: %d primitives, bvh_build_ms LBVH %.3f PLOC %.3f" % (case.name, n, ms[1], ms[2]))
 
 
@@ -78,17 +64,14 @@ def test_edge_case_on_the_device(gpu, ha, name):
 def test_edge_case_renders(gpu, ha, name):
     """one short render over the device-built trees: the accumulator is finite and not empty"""
     case = bes.get(name)
-    try:
-        for builder in (1, 2):
-            gpu.set_option("bvh_builder", builder)
+    for builder in (1, 2):
+        with options(gpu, {"bvh_builder": builder}):
             gpu.upload_scene(case.scene_holder(ha))
             gpu.set_resolution(32, 18)
             gpu.clear()
             gpu.render(1, 3)
             acc = gpu.read_accumulator()
             assert np.isfinite(acc).all() and (acc != 0).any(), (name, builder)
-    finally:
-        _restore(gpu)
 
 
 @pytest.mark.parametrize("name", sorted(bes.LOOP_CASES))
@@ -98,15 +81,12 @@ def test_merge_loop_that_makes_one_merge_per_iteration_on_the_device(gpu, ha, sc
     are left to the top-down build.  The upload succeeds, the hits are the host tree's and the brute force's, and the context goes on
     working: another scene uploads and renders."""
     case = bes.get(name)
-    try:
-        base, base_el, _ = _upload_and_query(gpu, ha, case, 0)
-        bes.check_against_brute(case, base, base_el, "builder 0")
-        for top in (1, PLOC_TOP_DEFAULT):
-            got, gel, st = _upload_and_query(gpu, ha, case, 2, ploc_top=top)
-            bes.check_same_hits(case, got, gel, base, base_el, "builder 2 ploc_top %d" % top)
-            print("%s ploc_top %d: bvh_build_ms %.3f, %d records" % (name, top, st["bvh_build_ms"], st["bvh_nodes"]))
-    finally:
-        _restore(gpu)
+    base, base_el, _ = _upload_and_query(gpu, ha, case, 0)
+    bes.check_against_brute(case, base, base_el, "builder 0")
+    for top in (1, ALL_DEFAULTS["ploc_top"]):
+        got, gel, st = _upload_and_query(gpu, ha, case, 2, ploc_top=top)
+        bes.check_same_hits(case, got, gel, base, base_el, "builder 2 ploc_top %d" % top)
+        print("%s ploc_top %d: bvh_build_ms %.3f, %d records" % (name, top, st["bvh_build_ms"], st["bvh_nodes"]))
     sc, _ = scenes("cornell_mini")
     gpu.upload_scene(sc)
     gpu.set_resolution(32, 18)

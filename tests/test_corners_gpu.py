@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import corner_scenes as cs
+from gpu_helpers import options
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +31,8 @@ def _log_and_render(gpu, s):
 def test_corner_scene_path_by_path(gpu, ha, orc, name, precise):
     s, ref = cs.get(ha, orc, name)
     gpu.upload_scene(s)
-    gpu.set_option("precise_shading", precise)
-    try:
+    with options(gpu, {"precise_shading": precise}):
         g = _log_and_render(gpu, s)
-    finally:
-        gpu.set_option("precise_shading", -1)
     cs.check(name, g, ref, "device, precise_shading %d" % precise)
     if name.startswith("sky_nonsquare"):
         assert (g[1] == 1).all() and ((g[2][..., 0] & 7) == 1).all()          # one ray, one sky lookup
@@ -45,14 +43,9 @@ def test_corner_scene_path_by_path(gpu, ha, orc, name, precise):
 def test_corner_scene_on_the_other_trees(gpu, ha, orc, name, option, value, default):
     """the 32-byte nodes and the device-built PLOC tree: the same limits"""
     s, ref = cs.get(ha, orc, name)
-    gpu.set_option(option, value)
-    gpu.set_option("precise_shading", 0)
-    try:
+    with options(gpu, {option: value, "precise_shading": 0}):
         gpu.upload_scene(s)
         g = _log_and_render(gpu, s)
-    finally:
-        gpu.set_option("precise_shading", -1)
-        gpu.set_option(option, default)
     cs.check(name, g, ref, "device, %s %d" % (option, value))
 
 
@@ -63,11 +56,8 @@ def test_camera_inside_a_glass_sphere_sees_through_it(gpu, ha, orc, precise):
     ref = orc.OracleScene(s.desc_ptr).path_log(s.w, s.h, 1)
     assert ((ref[2][..., 0] & 7) == 1).all() and (ref[1] == 1).all() and (ref[2][..., 9] == 0).all()
     gpu.upload_scene(s)
-    gpu.set_option("precise_shading", precise)
-    try:
+    with options(gpu, {"precise_shading": precise}):
         g = _log_and_render(gpu, s)
-    finally:
-        gpu.set_option("precise_shading", -1)
     cs.check_whole_frame(g, ref)
 
 
@@ -79,11 +69,8 @@ def test_the_ray_that_hits_a_pole_exactly(gpu, ha, orc, south, precise):
     s = cs.sphere_pole_exact(ha, south)
     ref = orc.OracleScene(s.desc_ptr).path_log(2, 2, 1)
     gpu.upload_scene(s)
-    gpu.set_option("precise_shading", precise)
-    try:
+    with options(gpu, {"precise_shading": precise}):
         g = _log_and_render(gpu, s)
-    finally:
-        gpu.set_option("precise_shading", -1)
     cs.check_pole_frame(g, ref, (1, 1, 3))
 
 
@@ -110,15 +97,12 @@ def test_albedo_guide_plane_of_the_imaged_cuboid(ha, orc, view):
     the four rays, to 1e-3 — the 7 x 3 albedo lookup on all six faces (u, v from 0 to 1, the flipped v of the Y faces) with no bounce after it."""
     s = cs.cuboid_edges(ha, view)
     o = orc.OracleScene(s.desc_ptr)
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         r.upload_scene(s)
         r.set_resolution(s.w, s.h)
         org, dirs = _sub_sample_rays(r, s.desc, s.w, s.h)
         r.render_guides()
         g = r.read_guides()
-    finally:
-        r.close()
     full = np.argwhere(g[..., 7] == 1.0)
     assert len(full) > 400                                   # the cuboid fills a fifth of the frame
     worst, normals = 0.0, set()

@@ -9,7 +9,8 @@ import pytest
 
 import ckpt
 from cli import ASSETS, run_cli
-from test_denoise_cpu import DEFAULTS, bits, core, core_denoise, synthetic_inputs  # noqa: F401  (core: the g++-built harness, a fixture)
+from gpu_helpers import error_of, renderer, same
+from test_denoise_cpu import DEFAULTS, core, core_denoise, synthetic_inputs  # noqa: F401  (core: the g++-built harness, a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,30 +20,12 @@ SCENES = ["spheres", "rtcamp6_v3_1"]
 REGIONS = {"frame": None, "window": (29, 17, 40, 24), "45x27": (13, 9, 45, 27)}
 
 
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+def _make(ha, sc, region=None, moments=True, counts=False, opts=None):
+    return renderer(ha, sc, opts, None, (W, H), region, moments=moments, counts=counts)
 
 
-def _code(ha, fn, *a, **kw):
-    with pytest.raises(ha.HipError) as e:
-        fn(*a, **kw)
-    return e.value.code
-
-
-def _renderer(ha, sc, region=None, moments=True, counts=False, opts=None):
-    r = ha.Renderer(0)
-    for k, v in (opts or {}).items():
-        r.set_option(k, v)
-    if sc is not None:
-        r.upload_scene(sc)
-    r.set_resolution(W, H)
-    if region is not None:
-        r.set_region(*region)
-    if moments:
-        r.set_option("moments", 1)
-    if counts:
-        r.set_option("sample_counts", 1)
-    return r
+def _err(ha, fn, *a, **kw):
+    return error_of(ha, fn, *a, **kw)[0]
 
 
 def _window(full, region):
@@ -61,7 +44,7 @@ def full_guides(ha, scenes):
 
     def get(name, qn):
         if (name, qn) not in cache:
-            r = _renderer(ha, scenes(name)[0], moments=False, opts={"quant_nodes": qn})
+            r = _make(ha, scenes(name)[0], moments=False, opts={"quant_nodes": qn})
             r.render_guides()
             cache[(name, qn)] = r.read_guides()
             r.close()
@@ -83,14 +66,14 @@ def test_guides_against_the_debug_renderer(ha, scenes, full_guides, scene, qn):
     assert set(np.unique(cov)) <= {0.0, 0.25, 0.5, 0.75, 1.0}
     hit = cov == 1.0
     assert hit.sum() > 500
-    r = _renderer(ha, scenes(scene)[0], moments=False, opts={"quant_nodes": qn})
+    r = _make(ha, scenes(scene)[0], moments=False, opts={"quant_nodes": qn})
     r.render_debug(1)
     normal = r.read_accumulator()
     r.clear()
     r.render_debug(2)
     depth = r.read_accumulator()
     r.close()
-    assert _same((g[..., 3:6] * np.float32(4.0))[hit], normal[hit])
+    assert same((g[..., 3:6] * np.float32(4.0))[hit], normal[hit])
     focus = np.float32(scenes(scene)[0].desc.camera.focus_distance)
     want = depth[..., 0].astype(np.float64) * 2.0 * float(focus) / 4.0
     rel = np.abs(g[..., 6].astype(np.float64) - want)[hit] / want[hit]
@@ -114,7 +97,7 @@ def _constant_albedo_scene(ha, colour):
 def test_albedo_plane_on_a_scene_of_one_colour(ha, qn):
     colour = (0.75, 0.5, 0.25)                                   # fp32 values: four of them sum exactly, x 0.25 gives them back
     sc = _constant_albedo_scene(ha, colour)
-    r = _renderer(ha, sc, moments=False, opts={"quant_nodes": qn})
+    r = _make(ha, sc, moments=False, opts={"quant_nodes": qn})
     r.render_guides()
     g = r.read_guides()
     r.close()
@@ -130,41 +113,41 @@ def test_albedo_plane_on_a_scene_of_one_colour(ha, qn):
 @pytest.mark.parametrize("region", ["window", "45x27"])
 @pytest.mark.parametrize("scene", SCENES)
 def test_region_guides_are_the_frames_window(ha, scenes, full_guides, scene, region, qn):
-    r = _renderer(ha, scenes(scene)[0], region=REGIONS[region], moments=False, opts={"quant_nodes": qn})
+    r = _make(ha, scenes(scene)[0], region=REGIONS[region], moments=False, opts={"quant_nodes": qn})
     r.render_guides()
     g = r.read_guides()
     r.close()
-    assert _same(g, _window(full_guides(scene, qn), REGIONS[region]))
+    assert same(g, _window(full_guides(scene, qn), REGIONS[region]))
 
 
 def test_guide_pass_touches_nothing_else_and_ignores_the_mask(ha, scenes, full_guides):
-    r = _renderer(ha, scenes("rtcamp6_v3_1")[0], counts=True)
+    r = _make(ha, scenes("rtcamp6_v3_1")[0], counts=True)
     r.render(1, 5)
     mask = np.zeros(((H + 3) // 4, (W + 3) // 4), np.uint8)
     mask[2:5, 3:9] = 1
     r.set_tile_mask(mask)
     r.render(5, 7)
     before = (r.read_accumulator(), r.read_moments(), r.read_sample_counts(), r.stats())
-    assert _code(ha, r.read_guides) == HR_ERR_INVALID            # none yet
+    assert _err(ha, r.read_guides) == HR_ERR_INVALID            # none yet
     r.render_guides()
     g = r.read_guides()
     after = (r.read_accumulator(), r.read_moments(), r.read_sample_counts(), r.stats())
-    assert _same(before[0], after[0]) and _same(before[1][0], after[1][0]) and before[1][1] == after[1][1] and np.array_equal(before[2], after[2])
+    assert same(before[0], after[0]) and same(before[1][0], after[1][0]) and before[1][1] == after[1][1] and np.array_equal(before[2], after[2])
     assert before[3]["paths"] == after[3]["paths"] and after[3]["debug_launches"] == before[3]["debug_launches"] + 1
     assert after[3]["trace_launches"] == before[3]["trace_launches"] and after[3]["debug_kernel_ms"] > before[3]["debug_kernel_ms"]
-    assert _same(g, full_guides("rtcamp6_v3_1", 1))              # the whole region, whatever the mask
+    assert same(g, full_guides("rtcamp6_v3_1", 1))              # the whole region, whatever the mask
     r.clear()
-    assert _same(r.read_guides(), g)                             # hr_clear keeps them
+    assert same(r.read_guides(), g)                             # hr_clear keeps them
     r.set_region(1, 1, 20, 10)
-    assert _code(ha, r.read_guides) == HR_ERR_INVALID            # the target went, they went
+    assert _err(ha, r.read_guides) == HR_ERR_INVALID            # the target went, they went
     r.close()
 
 
 def test_write_guides_round_trips(ha):
-    r = _renderer(ha, None, moments=False)
+    r = _make(ha, None, moments=False)
     g = np.random.default_rng(1).normal(size=(H, W, 8)).astype(np.float32)
     r.write_guides(g)
-    assert _same(r.read_guides(), g)
+    assert same(r.read_guides(), g)
     r.close()
 
 
@@ -177,7 +160,7 @@ CASES = [dict(levels=1, demodulate=1), dict(levels=4, demodulate=1), dict(levels
 @pytest.mark.parametrize("region", ["frame", "45x27"])
 @pytest.mark.parametrize("scene", SCENES)
 def test_denoise_equals_the_host_core(ha, scenes, core, scene, region):
-    r = _renderer(ha, scenes(scene)[0], region=REGIONS[region])
+    r = _make(ha, scenes(scene)[0], region=REGIONS[region])
     r.render(1, S + 1)
     r.denoise()                                                  # renders the guides itself
     acc, (mom, n), g = r.read_accumulator(), r.read_moments(), r.read_guides()
@@ -187,17 +170,17 @@ def test_denoise_equals_the_host_core(ha, scenes, core, scene, region):
         got = r.read_denoised()
         want = core_denoise(core, acc, mom, n, g, **case)
         assert np.isfinite(got).all()
-        assert _same(got, want), case
+        assert same(got, want), case
         r.denoise(**case)
-        assert _same(r.read_denoised(), got)                     # two calls, identical bits
+        assert same(r.read_denoised(), got)                     # two calls, identical bits
     raw = core_denoise(core, acc, mom, n, g, levels=0)
-    assert not _same(got, raw)
+    assert not same(got, raw)
     r.close()
 
 
 @pytest.mark.parametrize("scene", SCENES)
 def test_denoise_with_unequal_counts_equals_the_host_core(ha, scenes, core, scene):
-    r = _renderer(ha, scenes(scene)[0], counts=True)
+    r = _make(ha, scenes(scene)[0], counts=True)
     r.render(1, S // 2 + 1)
     e = r.noise_image()
     pad = np.full((((H + 3) // 4) * 4, ((W + 3) // 4) * 4), -np.inf)
@@ -212,7 +195,7 @@ def test_denoise_with_unequal_counts_equals_the_host_core(ha, scenes, core, scen
     g = r.read_guides()
     for case in (dict(levels=4, demodulate=1), dict(levels=5, demodulate=0)):
         r.denoise(**case)
-        assert _same(r.read_denoised(), core_denoise(core, acc, mom, cnt, g, **case)), case
+        assert same(r.read_denoised(), core_denoise(core, acc, mom, cnt, g, **case)), case
     r.denoise(levels=0)
     assert np.array_equal(r.resolve_denoised(), r.resolve_counted())
     r.close()
@@ -234,7 +217,7 @@ def test_denoise_of_written_inputs_equals_the_host_core(ha, core, w, h, unequal)
     r.write_guides(g)
     for case in (dict(levels=5, demodulate=1), dict(levels=5, demodulate=0), dict(levels=2, demodulate=1), dict(levels=0, demodulate=1)):
         r.denoise(**case)
-        assert _same(r.read_denoised(), core_denoise(core, acc, mom, n, g, **case)), case
+        assert same(r.read_denoised(), core_denoise(core, acc, mom, n, g, **case)), case
     r.close()
 
 
@@ -242,7 +225,7 @@ def test_denoise_of_written_inputs_equals_the_host_core(ha, core, w, h, unequal)
 
 @pytest.mark.parametrize("scene", SCENES)
 def test_resolve_of_level_zero_is_the_resolve(ha, scenes, scene):
-    r = _renderer(ha, scenes(scene)[0])
+    r = _make(ha, scenes(scene)[0])
     r.render(1, S + 1)
     for dem in (0, 1):
         r.denoise(levels=0, demodulate=dem)
@@ -255,25 +238,25 @@ def test_resolve_of_level_zero_is_the_resolve(ha, scenes, scene):
 
 def test_state_rules(ha, scenes):
     sc = scenes("spheres")[0]
-    r = _renderer(ha, sc, moments=False)
+    r = _make(ha, sc, moments=False)
     r.render(1, 5)
-    assert _code(ha, r.denoise) == HR_ERR_INVALID                # option moments is off
-    assert _code(ha, r.read_denoised) == HR_ERR_INVALID and _code(ha, r.resolve_denoised) == HR_ERR_INVALID
+    assert _err(ha, r.denoise) == HR_ERR_INVALID                # option moments is off
+    assert _err(ha, r.read_denoised) == HR_ERR_INVALID and _err(ha, r.resolve_denoised) == HR_ERR_INVALID
     r.set_option("moments", 1)
-    assert _code(ha, r.denoise) == HR_ERR_INVALID                # no sampling behind the moments
+    assert _err(ha, r.denoise) == HR_ERR_INVALID                # no sampling behind the moments
     r.render(1, 2)
-    assert _code(ha, r.denoise) == HR_ERR_INVALID                # one: a variance needs two
+    assert _err(ha, r.denoise) == HR_ERR_INVALID                # one: a variance needs two
     r.render(2, 5)
     r.denoise()
     d = r.read_denoised()
     acc, mom = r.read_accumulator(), r.read_moments()
     # refused parameters leave D as it was
     for bad in (dict(levels=6), dict(demodulate=2), dict(sigma_color=0.0), dict(sigma_normal=-1.0), dict(sigma_albedo=float("nan")), dict(sigma_depth=float("inf"))):
-        assert _code(ha, r.denoise, **bad) == HR_ERR_INVALID, bad
-        assert _same(r.read_denoised(), d)
+        assert _err(ha, r.denoise, **bad) == HR_ERR_INVALID, bad
+        assert same(r.read_denoised(), d)
     assert ha.hip_lib().hr_denoise(r._h, None) == 0              # NULL: the defaults
-    assert _same(r.read_denoised(), d)
-    assert _same(r.read_accumulator(), acc) and _same(r.read_moments()[0], mom[0])     # the denoiser writes none of its inputs
+    assert same(r.read_denoised(), d)
+    assert same(r.read_accumulator(), acc) and same(r.read_moments()[0], mom[0])     # the denoiser writes none of its inputs
     # whatever changes an input invalidates D
     g = r.read_guides()
     cnt = np.full((H, W), 4, np.uint32)
@@ -282,16 +265,16 @@ def test_state_rules(ha, scenes):
         r.denoise()
         r.read_denoised()
         step()
-        assert _code(ha, r.read_denoised) == HR_ERR_INVALID and _code(ha, r.resolve_denoised) == HR_ERR_INVALID
+        assert _err(ha, r.read_denoised) == HR_ERR_INVALID and _err(ha, r.resolve_denoised) == HR_ERR_INVALID
     r.render(1, 5)
     r.denoise()
     r.upload_scene(sc)
-    assert _code(ha, r.read_denoised) == HR_ERR_INVALID and _code(ha, r.read_guides) == HR_ERR_INVALID
+    assert _err(ha, r.read_denoised) == HR_ERR_INVALID and _err(ha, r.read_guides) == HR_ERR_INVALID
     r.denoise()
     r.set_region(3, 3, 40, 20)
-    assert _code(ha, r.read_denoised) == HR_ERR_INVALID
+    assert _err(ha, r.read_denoised) == HR_ERR_INVALID
     r.set_resolution(W, H)                                       # the options stay on, the planes start over
-    assert _code(ha, r.read_denoised) == HR_ERR_INVALID
+    assert _err(ha, r.read_denoised) == HR_ERR_INVALID
     # per-pixel counts: the pixel's own count is its n; a pixel below 2, or a count above the moments', is refused
     r.set_option("sample_counts", 1)
     r.render(1, 5)
@@ -300,24 +283,24 @@ def test_state_rules(ha, scenes):
     low = cnt.copy()
     low[7, 9] = 1
     r.write_sample_counts(low)
-    assert _code(ha, r.denoise) == HR_ERR_INVALID
+    assert _err(ha, r.denoise) == HR_ERR_INVALID
     high = cnt.copy()
     high[7, 9] = 5
     r.write_sample_counts(high)
-    assert _code(ha, r.denoise) == HR_ERR_INVALID
+    assert _err(ha, r.denoise) == HR_ERR_INVALID
     r.write_sample_counts(cnt)
     r.denoise()
-    assert _same(r.read_denoised(), d)
+    assert same(r.read_denoised(), d)
     r.write_sample_counts(cnt)
-    assert _code(ha, r.read_denoised) == HR_ERR_INVALID
+    assert _err(ha, r.read_denoised) == HR_ERR_INVALID
     r.close()
     # switching moments off invalidates too.  (hr_render_debug invalidates as well, but that cannot be observed: it refuses while moments is on, and
     # switching moments off has already invalidated D.)
-    r = _renderer(ha, sc)
+    r = _make(ha, sc)
     r.render(1, 5)
     r.denoise()
     r.set_option("moments", 0)
-    assert _code(ha, r.read_denoised) == HR_ERR_INVALID
+    assert _err(ha, r.read_denoised) == HR_ERR_INVALID
     r.close()
 
 
@@ -332,7 +315,7 @@ def _rel_sq_error(x, t):
 def test_default_parameters_lower_the_error_of_a_short_render(ha, scenes, scene):
     """Truth: 2,048 samplings of the 96x54 frame.  The relative squared error mean((x - t)^2 / (t^2 + 0.01^2)) of the denoised image at 16 samplings
     is lower than the raw mean's.  Only "lower" is asserted; the ratios printed here (16 and 64 samplings) are the ones in DESIGN.md §4.9."""
-    r = _renderer(ha, scenes(scene)[0])
+    r = _make(ha, scenes(scene)[0])
     r.render(1, 2049)
     truth = r.read_accumulator() / np.float32(2048 * 4)
     ratios = {}

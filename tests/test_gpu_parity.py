@@ -21,6 +21,8 @@ import os
 import numpy as np
 import pytest
 
+from gpu_helpers import options
+
 pytestmark = pytest.mark.gpu
 
 ATOL_REL = 1e-2
@@ -109,14 +111,11 @@ def test_path_draws_match_oracle_after_lens_rejection(gpu, scenes, orc):
     assert gpu.L.hr_debug_path_draw_residuals(gpu._h, sampling, C.c_void_p(out.ctypes.data)) != 0      # fp32 shading in force: no twin
     w, h = 320, 180
     gpu.set_resolution(w, h)
-    gpu.set_option("precise_shading", 1)
-    try:
+    with options(gpu, {"precise_shading": 1}):
         hi = np.empty((h, w, 4, 20), dtype=np.float32)
         lo = np.empty((h, w, 4, 20), dtype=np.float32)
         assert gpu.L.hr_debug_path_draws(gpu._h, sampling, C.c_void_p(hi.ctypes.data)) == 0, gpu.L.hr_last_error()
         assert gpu.L.hr_debug_path_draw_residuals(gpu._h, sampling, C.c_void_p(lo.ctypes.data)) == 0, gpu.L.hr_last_error()
-    finally:
-        gpu.set_option("precise_shading", -1)
     deep = 0
     for y in range(0, h, 3):
         for x in range(w):
@@ -180,17 +179,12 @@ def test_production_traversal_closest_hit_matches_oracle(gpu, scenes, name, buil
     tolerances of test_closest_hit_matches_oracle, and BIT-identical to the scalar walk of hr_debug_intersect: the order in which
     a wave visits nodes and tests leaves must not change what a ray hits."""
     sc, o = scenes(name)
-    gpu.set_option("bvh_builder", builder)
-    gpu.set_option("quant_nodes", quant)
-    try:
+    with options(gpu, {"bvh_builder": builder, "quant_nodes": quant}):
         gpu.upload_scene(sc)
         n = 6000 + 37   # not a multiple of 64: the last wave is ragged
         rays32 = _query_rays(sc, n, 11)
         got, gel = gpu.debug_trace(rays32)
         scalar, sel = gpu.debug_intersect(rays32)
-    finally:
-        gpu.set_option("bvh_builder", -1)
-        gpu.set_option("quant_nodes", 1)
     assert np.array_equal(gel, sel)
     assert np.array_equal(got.view(np.uint32), scalar.view(np.uint32))
     ref, rel = o.intersect(rays32.astype(np.float64))
@@ -221,13 +215,10 @@ def test_triangle_test_boundary_rules_on_the_gpu(gpu, ha, orc, builder):
     h.keep = keep
     o = orc.OracleScene(C.addressof(d))
     ref, rel = o.intersect(TRI_EDGE_RAYS.astype(np.float64))
-    gpu.set_option("bvh_builder", builder)
-    try:
+    with options(gpu, {"bvh_builder": builder}):
         gpu.upload_scene(h)
         got, gel = gpu.debug_trace(TRI_EDGE_RAYS)
         scalar, sel = gpu.debug_intersect(TRI_EDGE_RAYS)
-    finally:
-        gpu.set_option("bvh_builder", -1)
     assert np.array_equal(got.view(np.uint32), scalar.view(np.uint32)) and np.array_equal(gel, sel)
     assert np.array_equal(got[:, 0], ref[:, 0].astype(np.float32)), (got[:, 0], ref[:, 0])
     assert np.array_equal(got[:, 0], np.array([1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 0, 0, 0], dtype=np.float32))
@@ -251,13 +242,10 @@ def test_triangle_test_across_scales_on_the_gpu(gpu, ha, orc, builder):
     h.keep = keep
     o = orc.OracleScene(C.addressof(d))
     ref, rel = o.intersect(rays.astype(np.float64))
-    gpu.set_option("bvh_builder", builder)
-    try:
+    with options(gpu, {"bvh_builder": builder}):
         gpu.upload_scene(h)
         got, gel = gpu.debug_trace(rays)
         scalar, sel = gpu.debug_intersect(rays)
-    finally:
-        gpu.set_option("bvh_builder", -1)
     assert np.array_equal(got.view(np.uint32), scalar.view(np.uint32)) and np.array_equal(gel, sel)
     assert np.array_equal(got[:, 0], ref[:, 0].astype(np.float32))
     hit = ref[:, 0] == 1
@@ -317,14 +305,9 @@ def test_radiance_accumulator_matches_oracle(gpu, scenes, name, w, h, s, precise
     sc, o = scenes(name)
     gpu.upload_scene(sc)
     gpu.set_resolution(w, h)
-    gpu.set_option("batch", 3)
-    gpu.set_option("precise_shading", precise)      # (0 = fp32 shading pinned: the automatic choice turns precise shading on for scenes without meshes)
-    try:
+    with options(gpu, {"batch": 3, "precise_shading": precise}):      # (0 = fp32 shading pinned: the automatic choice turns precise shading on for scenes without meshes)
         gpu.render(1, s + 1)
         acc = gpu.read_accumulator()
-    finally:
-        gpu.set_option("batch", 0)   # back to automatic
-        gpu.set_option("precise_shading", -1)
     ref, _ = o.render(w, h, 1, s + 1, threads=0)
     _check_scene(name, acc, ref, "%dx%dx%d%s" % (w, h, s, " precise" if precise else ""), GATES_PRECISE if precise else GATES)
     m_gpu, m_ref = float(acc.mean()), float(ref.mean())
@@ -383,21 +366,15 @@ def test_per_path_parity_accounting_precise_shading(gpu, scenes, name):
     """test_per_path_parity_accounting with option precise_shading: the path log comes from the split pipeline's LOG instantiation (the
     event log rides in the path's state), its radiances are what hr_render accumulates in that mode, and the same-branch tail meets the
     tighter limits above."""
-    gpu.set_option("precise_shading", 1)
-    try:
+    with options(gpu, {"precise_shading": 1}):
         _per_path_accounting(gpu, scenes, name, PATH_LIMITS_PRECISE, "precise")
-    finally:
-        gpu.set_option("precise_shading", -1)
 
 
 @pytest.mark.parametrize("name", sorted(PATH_LIMITS))
 def test_per_path_parity_accounting(gpu, scenes, name):
     """fp32 shading (pinned: option precise_shading 0; the automatic choice would shade `spheres`, a scene without meshes, in f64)."""
-    gpu.set_option("precise_shading", 0)
-    try:
+    with options(gpu, {"precise_shading": 0}):
         _per_path_accounting(gpu, scenes, name, PATH_LIMITS, "fp32 shading")
-    finally:
-        gpu.set_option("precise_shading", -1)
 
 
 def _per_path_accounting(gpu, scenes, name, limits, label):
@@ -476,14 +453,11 @@ def test_random_scenes_path_by_path(gpu, ha, orc, seed, builder, precise):
     sc = random_scenes.build(ha, seed)
     o = orc.OracleScene(sc.desc_ptr)
     w, h = 160, 90
-    try:
-        gpu.set_option("bvh_builder", builder)
+    with options(gpu) as opt:
+        opt.set("bvh_builder", builder)
         gpu.upload_scene(sc)
-    finally:
-        gpu.set_option("bvh_builder", -1)
     gpu.set_resolution(w, h)
-    gpu.set_option("precise_shading", precise)
-    try:
+    with options(gpu, {"precise_shading": precise}):
         g = gpu.debug_path_log(1)
         gpu.clear()
         gpu.render(1, 2)
@@ -491,8 +465,6 @@ def test_random_scenes_path_by_path(gpu, ha, orc, seed, builder, precise):
         gpu.clear()
         gpu.render(1, 3)
         acc = gpu.read_accumulator().copy()
-    finally:
-        gpu.set_option("precise_shading", -1)
     rad = g[0]
     assert np.array_equal(acc1, ((rad[:, :, 0] + rad[:, :, 1]) + (rad[:, :, 2] + rad[:, :, 3])).astype(np.float32))
     a = path_parity.account(g, o.path_log(w, h, 1))
@@ -525,22 +497,21 @@ def test_sharding_and_batching_are_exact_partitions(gpu, scenes):
     sc, _ = scenes("rtcamp6_v3_1")
     gpu.upload_scene(sc)
     gpu.set_resolution(120, 68)
-    gpu.set_option("batch", 8)
-    gpu.render(1, 9)
-    whole = gpu.read_accumulator().astype(np.float64)
-    gpu.clear()
-    gpu.set_option("batch", 1)
-    for rank in range(4):
-        gpu.render(1 + rank, 9, 4)
-    parts = gpu.read_accumulator().astype(np.float64)
-    assert np.abs(whole - parts).max() <= 1e-4 * max(1.0, np.abs(whole).max())
-    # determinism of a repeat
-    gpu.clear()
-    gpu.set_option("batch", 8)
-    gpu.render(1, 9)
-    again = gpu.read_accumulator().astype(np.float64)
-    assert np.abs(whole - again).max() <= 1e-5 * max(1.0, np.abs(whole).max())
-    gpu.set_option("batch", 0)   # back to automatic
+    with options(gpu, {"batch": 8}) as opt:
+        gpu.render(1, 9)
+        whole = gpu.read_accumulator().astype(np.float64)
+        gpu.clear()
+        opt.set("batch", 1)
+        for rank in range(4):
+            gpu.render(1 + rank, 9, 4)
+        parts = gpu.read_accumulator().astype(np.float64)
+        assert np.abs(whole - parts).max() <= 1e-4 * max(1.0, np.abs(whole).max())
+        # determinism of a repeat
+        gpu.clear()
+        opt.set("batch", 8)
+        gpu.render(1, 9)
+        again = gpu.read_accumulator().astype(np.float64)
+        assert np.abs(whole - again).max() <= 1e-5 * max(1.0, np.abs(whole).max())
 
 
 def _crop_parity(gpu, o, name, W, H, S, crops, size=64, gates=None, crop_slack=None):
@@ -548,10 +519,10 @@ def _crop_parity(gpu, o, name, W, H, S, crops, size=64, gates=None, crop_slack=N
     at the SAME full-image coordinates (seeds depend on them): every crop must pass the scene's gates, and the union of the
     crops agrees in the mean to 5e-3."""
     gpu.set_resolution(W, H)
-    gpu.set_option("batch", 0)
-    gpu.clear()
-    gpu.render(1, S + 1)
-    acc = gpu.read_accumulator()
+    with options(gpu, {"batch": 0}):
+        gpu.clear()
+        gpu.render(1, S + 1)
+        acc = gpu.read_accumulator()
     assert np.isfinite(acc).all() and (acc >= 0).all()
     got_all, ref_all, fr = [], [], []
     for (x0, y0) in crops:
@@ -582,10 +553,9 @@ def test_config3_full_size_crops(gpu, scenes):
     against the sky (mirror), and the image's bottom-right corner."""
     sc, o = scenes("rtcamp6_v3_1")
     gpu.upload_scene(sc)
-    gpu.set_option("counters", 1)
-    acc = _crop_parity(gpu, o, "rtcamp6_v3_1", 1920, 1080, 8, [(160, 130), (800, 760), (700, 250), (1500, 300), (1856, 1016)])
-    st = gpu.stats()
-    gpu.set_option("counters", 0)
+    with options(gpu, {"counters": 1}):
+        acc = _crop_parity(gpu, o, "rtcamp6_v3_1", 1920, 1080, 8, [(160, 130), (800, 760), (700, 250), (1500, 300), (1856, 1016)])
+        st = gpu.stats()
     assert st["paths"] == 1920 * 1080 * 4 * 8 and st["rng_overflow"] == 0
     assert (acc.sum(axis=2) > 0).mean() > 0.9   # black floor texels (albedo 0) and dark sky stay exactly 0
     assert 2.5 < (st["rays"] + st["shadow_culled"]) / st["paths"] < 3.6          # SURVEY.md Appendix D: 3.05 rays per path (scene.intersect calls of the reference: traced + culled)
@@ -920,10 +890,9 @@ def test_no_systematic_bias_at_many_samplings(gpu, scenes):
     gpu.upload_scene(sc)
     w, h, s = 160, 90, 32
     gpu.set_resolution(w, h)
-    gpu.set_option("batch", 8)
-    gpu.render(1, s + 1)
-    acc = gpu.read_accumulator().astype(np.float64) / (4 * s)
-    gpu.set_option("batch", 0)   # back to automatic
+    with options(gpu, {"batch": 8}):
+        gpu.render(1, s + 1)
+        acc = gpu.read_accumulator().astype(np.float64) / (4 * s)
     ref, _ = o.render(w, h, 1, s + 1, threads=0)
     ref /= 4 * s
     assert abs(acc.mean() - ref.mean()) <= 5e-4 * ref.mean()
@@ -978,12 +947,12 @@ def test_cli_checkpoint_resume_and_debug(tmp_path):
     assert img.shape == (36, 64, 3) and img.std() > 5
 
 
-def _seed_mode_available(gpu, mode):
+def _seed_mode_available(opt, mode):
     """seed_mode 3 and 4 (measured experiments, slower than the default) are compiled only into `make EXPERIMENTS=1` builds; the
     product library answers HR_ERR_UNSUPPORTED (-6) for them."""
     import hanamaru_amd as ha
     try:
-        gpu.set_debug_option("seed_mode", mode)
+        opt.set("seed_mode", mode)
         return True
     except ha.HipError as e:
         assert e.code == -6 and mode >= 3, (mode, str(e))
@@ -999,15 +968,15 @@ def test_seed_kernels_are_bit_identical(gpu, scenes):
     sc, _ = scenes("rtcamp6_v3_1")
     gpu.upload_scene(sc)
     outs = []
-    try:
+    with options(gpu) as opt:
         for (w, h, s) in [(130, 71, 6), (640, 360, 9)]:   # ragged: tiles hang over the right and bottom edges; many groups per CU
             gpu.set_resolution(w, h)
             ref = None
             for mode, head in [(0, 16), (1, 16), (1, 8), (1, 12), (1, 24), (2, 16), (3, 16), (4, 16)]:   # 2: the three-run kernel (no state ring), 3: its phase-shifted four-run form
-                if not _seed_mode_available(gpu, mode):      # modes 3 and 4: only in `make EXPERIMENTS=1` builds
+                if not _seed_mode_available(opt, mode):      # modes 3 and 4: only in `make EXPERIMENTS=1` builds
                     continue
-                gpu.set_debug_option("seed_mode", mode)
-                gpu.set_debug_option("seed_split", head)
+                opt.set("seed_mode", mode)
+                opt.set("seed_split", head)
                 gpu.clear()
                 gpu.render(1, s + 1)
                 acc = gpu.read_accumulator().astype(np.float64)
@@ -1016,9 +985,6 @@ def test_seed_kernels_are_bit_identical(gpu, scenes):
                     assert ref.sum() > 0
                 else:
                     assert np.array_equal(ref, acc), (w, h, mode, head, np.abs(ref - acc).max())
-    finally:
-        gpu.set_debug_option("seed_mode", 2)
-        gpu.set_debug_option("seed_split", 16)
 
 
 def test_priority_governor_does_not_change_results(gpu, scenes):
@@ -1030,16 +996,14 @@ def test_priority_governor_does_not_change_results(gpu, scenes):
     gpu.upload_scene(sc)
     gpu.set_resolution(320, 180)
     outs = []
-    try:
+    with options(gpu) as opt:
         for boost in (0, 1, 2, 3, 4, -1, -1):
-            gpu.set_option("trace_boost", boost)
+            opt.set("trace_boost", boost)
             gpu.clear()
             gpu.render(1, 13)
             outs.append(gpu.read_accumulator().astype(np.float64))
         with pytest.raises(Exception):
-            gpu.set_option("trace_boost", 5)
-    finally:
-        gpu.set_option("trace_boost", -1)
+            opt.set("trace_boost", 5)
     assert outs[0].sum() > 0
     for o in outs[1:]:
         assert np.array_equal(outs[0], o), np.abs(outs[0] - o).max()
@@ -1051,7 +1015,7 @@ def test_nee_culls_do_not_change_a_bit(gpu, scenes):
     is GGX and the emitter below its horizon (material.rs:64-67 returns 0).  The reference traces
     those rays and discards them (renderer.rs:279-280); with debug option nee_cull 0 so does the kernel — same accumulator, bit for bit, on
     every scene type; and the path log still counts the reference's scene.intersect calls."""
-    try:
+    with options(gpu) as opt:
         for name, w, h, s in [("rtcamp6_v3_1", 400, 225, 4), ("rtcamp6_v2", 320, 180, 2), ("tbf3", 320, 180, 2), ("rtcamp5", 320, 180, 2), ("rtcamp6_v1", 256, 144, 2),
                               ("spheres", 320, 180, 2), ("cornell_mini", 200, 128, 4), ("material_examples", 256, 144, 2)]:
             sc, _ = scenes(name)
@@ -1059,12 +1023,12 @@ def test_nee_culls_do_not_change_a_bit(gpu, scenes):
             gpu.set_resolution(w, h)
             out = {}
             for cull in (7, 0):       # the mask of shortcuts in force: 7 = all (default), 0 = every shadow ray traced
-                gpu.set_debug_option("nee_cull", cull)
-                gpu.set_option("counters", 1)
+                opt.set("nee_cull", cull)
+                opt.set("counters", 1)
                 gpu.clear()
                 gpu.render(1, 1 + s)
                 st = gpu.stats()
-                gpu.set_option("counters", 0)
+                opt.set("counters", 0)
                 out[cull] = (gpu.read_accumulator().copy(), st, gpu.debug_path_log(1))
             (a, sa, la), (b, sb, lb) = out[7], out[0]
             assert a.sum() > 0 and np.array_equal(a, b), (name, np.abs(a - b).max())
@@ -1074,9 +1038,6 @@ def test_nee_culls_do_not_change_a_bit(gpu, scenes):
                 assert np.array_equal(x, y), name
             print("nee culls %s: %.3f of %.3f rays per path not traced (%.1f %% of the node tests)" %
                   (name, sa["shadow_culled"] / sa["paths"], sb["rays"] / sb["paths"], 100.0 * (1.0 - sa["node_tests"] / sb["node_tests"])))
-    finally:
-        gpu.set_debug_option("nee_cull", 7)
-        gpu.set_option("counters", 0)
 
 
 def test_kernel_variants_render_the_same_bits(gpu, scenes):
@@ -1094,55 +1055,48 @@ def test_kernel_variants_render_the_same_bits(gpu, scenes):
         return gpu.read_accumulator().copy()
     ref = render()
     assert ref.sum() > 0
-    try:
-        gpu.set_option("counters", 1)
+    with options(gpu) as opt:
+        opt.set("counters", 1)
         assert np.array_equal(ref, render()), "instrumented build"
-        gpu.set_option("counters", 0)
+        opt.set("counters", 0)
         for mw in (4, 6):
-            gpu.set_debug_option("min_waves", mw)
+            opt.set("min_waves", mw)
             assert np.array_equal(ref, render()), ("min_waves", mw)
-        gpu.set_debug_option("min_waves", 5)
+        opt.set("min_waves", 5)
         # the split pipeline (traversal kernel + shading kernel per path iteration, wf_kernels.h) is the megakernel cut at scene.intersect
         log_mega = gpu.debug_path_log(3)
-        gpu.set_debug_option("trace_mode", 1)
+        opt.set("trace_mode", 1)
         assert np.array_equal(ref, render()), "split pipeline"
         # ... and its LOG instantiation (the event log rides in the path's state) writes the megakernel's path log, word for word
         for a, b in zip(log_mega, gpu.debug_path_log(3)):
             assert np.array_equal(a, b), "split pipeline, path log"
-        gpu.set_option("counters", 1)
+        opt.set("counters", 1)
         assert np.array_equal(ref, render()), "split pipeline, instrumented build"
-        gpu.set_option("counters", 0)
+        opt.set("counters", 0)
         # option precise_shading has two homes too — path_advance<.., PREC> in the megakernel (the residuals parked in the path's record) and
         # the split pipeline's shading kernel (the residuals in the queued state): one function (prec_core.h shade_hit_f64), the same bits
-        gpu.set_option("precise_shading", 1)
+        opt.set("precise_shading", 1)
         prec_split = render()
         prec_split_log = gpu.debug_path_log(3)
-        gpu.set_debug_option("trace_mode", 0)
+        opt.set("trace_mode", 0)
         assert np.array_equal(prec_split, render()), "precise shading: megakernel vs split pipeline"
         assert not np.array_equal(prec_split, ref)
         for a, b in zip(prec_split_log, gpu.debug_path_log(3)):
             assert np.array_equal(a, b), "precise shading, path log"
-        gpu.set_option("counters", 1)
+        opt.set("counters", 1)
         assert np.array_equal(prec_split, render()), "precise shading, instrumented build"
-        gpu.set_option("counters", 0)
-        gpu.set_option("precise_shading", -1)
-        gpu.set_debug_option("trace_mode", 1)
-        gpu.set_option("quant_nodes", 0)
+        opt.set("counters", 0)
+        opt.set("precise_shading", -1)
+        opt.set("trace_mode", 1)
+        opt.set("quant_nodes", 0)
         gpu.upload_scene(sc)
         assert np.array_equal(ref, render()), "split pipeline, fp32 node records"
-        gpu.set_debug_option("trace_mode", 0)
+        opt.set("trace_mode", 0)
         assert np.array_equal(ref, render()), "fp32 node records"
-        gpu.set_option("quant_nodes", 1)
-        gpu.set_option("bvh_builder", 2)
+        opt.set("quant_nodes", 1)
+        opt.set("bvh_builder", 2)
         gpu.upload_scene(sc)
         assert np.array_equal(ref, render()), "device-built tree"
-    finally:
-        gpu.set_option("counters", 0)
-        gpu.set_option("precise_shading", -1)
-        gpu.set_debug_option("trace_mode", -1)
-        gpu.set_debug_option("min_waves", 5)
-        gpu.set_option("quant_nodes", 1)
-        gpu.set_option("bvh_builder", -1)
 
 
 def test_priority_governor_decides_on_the_device(gpu, scenes):
@@ -1152,8 +1106,8 @@ def test_priority_governor_decides_on_the_device(gpu, scenes):
     sc, _ = scenes("rtcamp6_v3_1")
     gpu.upload_scene(sc)
     gpu.set_resolution(1920, 1080)
-    try:
-        gpu.set_option("trace_boost", -1)
+    with options(gpu) as opt:
+        opt.set("trace_boost", -1)
         st0 = gpu.stats()
         assert st0["governor_decisions"] == 0 and st0["governor_level"] == 0      # a new balance starts at "seed kernel first"
         gpu.clear()
@@ -1164,14 +1118,12 @@ def test_priority_governor_decides_on_the_device(gpu, scenes):
         assert 16 <= st["governor_decisions"] <= 23, st["governor_decisions"]     # not the first, not the last
         assert 0 <= st["governor_level"] <= 4 and st["governor_moves"] <= st["governor_decisions"]
         for level in (3, 0):
-            gpu.set_option("trace_boost", level)
+            opt.set("trace_boost", level)
             gpu.clear()
             gpu.render(1, 9)
             gpu.synchronize()
             st = gpu.stats()
             assert st["governor_level"] == level and st["governor_decisions"] == 0 and st["governor_moves"] == 0
-    finally:
-        gpu.set_option("trace_boost", -1)
 
 
 def test_wave_budget_governor(gpu, scenes):
@@ -1182,9 +1134,8 @@ def test_wave_budget_governor(gpu, scenes):
     sc, _ = scenes("rtcamp6_v3_1")
     gpu.upload_scene(sc)
     gpu.set_resolution(1920, 1080)
-    gpu.set_option("batch", 4)
-    try:
-        gpu.set_option("trace_boost", -1)
+    with options(gpu, {"batch": 4}) as opt:
+        opt.set("trace_boost", -1)
         gpu.clear()
         gpu.render(1, 97)                 # 24 launches in ONE call: the host never waits, everything is decided on the device
         st = gpu.stats()
@@ -1193,18 +1144,18 @@ def test_wave_budget_governor(gpu, scenes):
         print("wave budget: headline settles at %d trace workgroups (%d moves, %d launches judged), level %d" % (st["governor_budget"], st["governor_budget_moves"], st["governor_decisions"], st["governor_level"]))
         assert st["governor_level"] == 0 and st["governor_budget_moves"] >= 2 and st["governor_decisions"] >= 12
         assert cus * 5 // 2 <= st["governor_budget"] <= cus * 7 // 2 and st["governor_budget"] % (cus // 4) == 0
-        gpu.set_option("trace_boost", 0)  # a fixed level: no budget
+        opt.set("trace_boost", 0)  # a fixed level: no budget
         gpu.clear()
         gpu.render(1, 97)
         st0 = gpu.stats()
         assert st0["governor_budget"] == 0 and st0["governor_budget_moves"] == 0
         assert np.array_equal(governed, gpu.read_accumulator())
-        gpu.set_option("trace_boost", -1)
-        gpu.set_debug_option("trace_budget", 512)      # pinned from the host: same bits again
+        opt.set("trace_boost", -1)
+        opt.set("trace_budget", 512)      # pinned from the host: same bits again
         gpu.clear()
         gpu.render(1, 97)
         assert np.array_equal(governed, gpu.read_accumulator())
-        gpu.set_debug_option("trace_budget", 0)
+        opt.set("trace_budget", 0)
         # a scene whose trace kernel is the slower one keeps every workgroup
         sc2, _ = scenes("rtcamp6_v2")
         gpu.upload_scene(sc2)
@@ -1213,10 +1164,6 @@ def test_wave_budget_governor(gpu, scenes):
         st2 = gpu.stats()
         print("wave budget: rtcamp6_v2 keeps %s workgroups, level %d" % ("all" if st2["governor_budget"] == 0 else st2["governor_budget"], st2["governor_level"]))
         assert st2["governor_budget"] == 0 and st2["governor_level"] >= 2
-    finally:
-        gpu.set_option("trace_boost", -1)
-        gpu.set_debug_option("trace_budget", 0)
-        gpu.set_option("batch", 0)
 
 
 def _run_bench(extra, env=None, launcher_ranks=0, port=29541, full=True):
@@ -1406,17 +1353,15 @@ def test_config5_4k_crops(gpu, scenes):
     BVH, refraction), the bunny's ear silhouette, the picture frame's edge against the sky, floor + armadillo, open sky."""
     sc, o = scenes("rtcamp6_dodeca")
     gpu.upload_scene(sc)
-    gpu.set_option("counters", 1)
-    W, H, S = 3840, 2160, 4
-    acc = _crop_parity(gpu, o, "rtcamp6_dodeca", W, H, S, [(1950, 150), (1850, 520), (3040, 640), (1620, 1560), (380, 320)])
-    st = gpu.stats()
-    assert st["paths"] == W * H * 4 * S and st["rng_overflow"] == 0 and st["trace_launches"] == 1
-    gpu.set_option("max_tail_gib", 4)                    # one 4K sampling of hand-off records is 4.25 GB: the cap shrinks the launch to 1
-    gpu.clear()
-    gpu.render(1, 3)
-    st = gpu.stats()
-    gpu.set_option("max_tail_gib", 20)
-    gpu.set_option("counters", 0)
+    with options(gpu, {"counters": 1}) as opt:
+        W, H, S = 3840, 2160, 4
+        acc = _crop_parity(gpu, o, "rtcamp6_dodeca", W, H, S, [(1950, 150), (1850, 520), (3040, 640), (1620, 1560), (380, 320)])
+        st = gpu.stats()
+        assert st["paths"] == W * H * 4 * S and st["rng_overflow"] == 0 and st["trace_launches"] == 1
+        opt.set("max_tail_gib", 4)                    # one 4K sampling of hand-off records is 4.25 GB: the cap shrinks the launch to 1
+        gpu.clear()
+        gpu.render(1, 3)
+        st = gpu.stats()
     assert st["paths"] == W * H * 4 * 2 and st["trace_launches"] == 2
     capped = gpu.read_accumulator()
     gpu.clear()
@@ -1432,23 +1377,16 @@ def test_config5_4k_crops_precise_shading(gpu, scenes):
     sc, o = scenes("rtcamp6_dodeca")
     gpu.upload_scene(sc)
     W, H, S = 3840, 2160, 2
-    gpu.set_option("precise_shading", 1)
-    gpu.set_option("counters", 1)
-    gpu.set_option("max_tail_gib", 8)                     # this scene's queues take 10.6 GB per 4K sampling (one emitter): a launch per sampling
-    try:
+    with options(gpu, {"precise_shading": 1, "counters": 1, "max_tail_gib": 8}) as opt:      # this scene's queues take 10.6 GB per 4K sampling (one emitter): a launch per sampling
         a = _crop_parity(gpu, o, "rtcamp6_dodeca", W, H, S, [(1950, 150), (1850, 520), (3040, 640)])
         st = gpu.stats()
         assert st["paths"] == W * H * 4 * S and st["rng_overflow"] == 0 and st["trace_launches"] == 2
-        gpu.set_option("counters", 0)
-        gpu.set_option("max_tail_gib", 64)                # room for both samplings in one launch
+        opt.set("counters", 0)
+        opt.set("max_tail_gib", 64)                # room for both samplings in one launch
         gpu.clear()
         gpu.render(1, S + 1)
         whole = gpu.read_accumulator()      # (another launch size is another summation order of a pixel's records: equal to fp32 rounding)
         assert np.abs(a.astype(np.float64) - whole).max() <= 1e-4 * max(1.0, float(np.abs(whole).max()))
-    finally:
-        gpu.set_option("max_tail_gib", 20)
-        gpu.set_option("counters", 0)
-        gpu.set_option("precise_shading", -1)
 
 
 def test_precise_shading_defaults_and_finite_radiance(gpu, scenes):
@@ -1459,34 +1397,28 @@ def test_precise_shading_defaults_and_finite_radiance(gpu, scenes):
     sc, _ = scenes("spheres")
     gpu.upload_scene(sc)
     assert gpu.stats()["shading_in_force"] == 1
-    gpu.set_option("russian_roulette", 3)
-    assert gpu.stats()["shading_in_force"] == 0          # the roulette estimator has no f64 instantiation: the automatic choice stands back
-    gpu.set_option("russian_roulette", 0)
+    with options(gpu, {"russian_roulette": 3}):
+        assert gpu.stats()["shading_in_force"] == 0          # the roulette estimator has no f64 instantiation: the automatic choice stands back
     sc, _ = scenes("rtcamp6_v3_1")
     gpu.upload_scene(sc)
     assert gpu.stats()["shading_in_force"] == 0
-    gpu.set_option("precise_shading", 1)
-    assert gpu.stats()["shading_in_force"] == 2          # a mesh scene: the split form is the faster one
-    gpu.set_option("precise_shading", -1)
+    with options(gpu, {"precise_shading": 1}):
+        assert gpu.stats()["shading_in_force"] == 2          # a mesh scene: the split form is the faster one
     sc, _ = scenes("rtcamp5")
     gpu.upload_scene(sc)
     assert gpu.stats()["shading_in_force"] == 0
-    gpu.set_option("precise_shading", 1)
-    try:
+    with options(gpu, {"precise_shading": 1}) as opt:
         assert gpu.stats()["shading_in_force"] == 2      # any mesh: the split form
         gpu.set_resolution(1920, 1080)
         gpu.clear()
         gpu.render(191, 194)
         split = gpu.read_accumulator().copy()
         assert np.isfinite(split).all()
-        gpu.set_debug_option("trace_mode", 0)
+        opt.set("trace_mode", 0)
         assert gpu.stats()["shading_in_force"] == 1      # pinned: the megakernel form, the same bits
         gpu.clear()
         gpu.render(191, 194)
         assert np.array_equal(split, gpu.read_accumulator())
-    finally:
-        gpu.set_debug_option("trace_mode", -1)
-        gpu.set_option("precise_shading", -1)
 
 
 @pytest.mark.parametrize("precise", [0, 1])
@@ -1497,13 +1429,10 @@ def test_ggx_nee_sample_exactly_at_the_horizon_adds_nothing(gpu, scenes, precise
     sc, o = scenes("cornell_mini")
     gpu.upload_scene(sc)
     gpu.set_resolution(1920, 1080)
-    gpu.set_option("precise_shading", precise)
-    try:
+    with options(gpu, {"precise_shading": precise}):
         gpu.clear()
         gpu.render(732, 733)
         acc = gpu.read_accumulator().copy()
-    finally:
-        gpu.set_option("precise_shading", -1)
     assert np.isfinite(acc).all()
     ref = o.render_region(1920, 1080, 1394, 371, 1, 1, 732, 733, threads=1)[0, 0]
     assert np.abs(acc[371, 1394].astype(np.float64) - ref).max() <= 1e-4, (acc[371, 1394], ref)
@@ -1518,20 +1447,14 @@ def test_random_scenes_rendered_long_stay_finite(gpu, ha, seed, precise):
     import random_scenes
     kw = dict(spheres=2, cuboids=1, meshes=1) if seed % 4 == 2 else dict(spheres=0, cuboids=6, meshes=2)
     sc = random_scenes.build(ha, seed, **kw)
-    gpu.set_option("bvh_builder", seed % 3)
-    try:
+    with options(gpu, {"bvh_builder": seed % 3}):
         gpu.upload_scene(sc)
-    finally:
-        gpu.set_option("bvh_builder", -1)
     gpu.set_resolution(640, 360)
-    gpu.set_option("precise_shading", precise)
-    try:
+    with options(gpu, {"precise_shading": precise}):
         gpu.clear()
         gpu.render(1, 257)
         acc = gpu.read_accumulator().copy()
         img = gpu.resolve(256)
-    finally:
-        gpu.set_option("precise_shading", -1)
     assert np.isfinite(acc).all() and acc.max() < 1e34
     assert img.shape == (360, 640, 3)
 
@@ -1616,12 +1539,11 @@ def test_config2_spheres_full_size_crops(gpu, scenes):
     the bottom-left image corner (spheres cut by the border), the inside of a sphere."""
     sc, o = scenes("spheres")
     gpu.upload_scene(sc)
-    gpu.set_option("counters", 1)
-    # 64 samplings = 256 paths per pixel: a pixel is off by more than 1e-3 as soon as ONE of them took another branch (grazing
-    # sphere rims), so the 1e-3 fraction falls with the sampling count while the 1e-2 fraction rises — gates for this count
-    _crop_parity(gpu, o, "spheres", 1920, 1080, 64, [(900, 190), (400, 160), (1150, 590), (0, 1016), (760, 900)], gates=(0.9996, 0.9985), crop_slack=(0.0008, 0.003))
-    st = gpu.stats()
-    gpu.set_option("counters", 0)
+    with options(gpu, {"counters": 1}):
+        # 64 samplings = 256 paths per pixel: a pixel is off by more than 1e-3 as soon as ONE of them took another branch (grazing
+        # sphere rims), so the 1e-3 fraction falls with the sampling count while the 1e-2 fraction rises — gates for this count
+        _crop_parity(gpu, o, "spheres", 1920, 1080, 64, [(900, 190), (400, 160), (1150, 590), (0, 1016), (760, 900)], gates=(0.9996, 0.9985), crop_slack=(0.0008, 0.003))
+        st = gpu.stats()
     assert st["paths"] == 1920 * 1080 * 4 * 64 and st["rng_overflow"] == 0 and st["tri_tests"] == 0 and st["sphere_tests"] > 0
 
 
@@ -1639,14 +1561,10 @@ def test_matches_the_reference_binarys_committed_render(gpu, scenes, precise):
     sc, _ = scenes("rtcamp6_v3_1")
     gpu.upload_scene(sc)
     gpu.set_resolution(1920, 1080)
-    gpu.set_option("batch", 0)
-    gpu.set_option("precise_shading", precise)      # (automatic = fp32 shading on this scene; 1: the split pipeline with f64 bounces)
-    try:
+    with options(gpu, {"batch": 0, "precise_shading": precise}):      # (automatic = fp32 shading on this scene; 1: the split pipeline with f64 bounces)
         gpu.clear()
         gpu.render(1, 1001)
         img = gpu.resolve(1000).astype(np.float64)
-    finally:
-        gpu.set_option("precise_shading", -1)
     d = np.abs(img - ref)
     psnr = 10 * np.log10(255.0 ** 2 / (d ** 2).mean())
     print("vs the reference binary's image, precise %d: PSNR %.2f dB, mean abs diff %.4f, exact channels %.5f, within 1 LSB %.6f, max %d" % (precise, psnr, d.mean(), (d == 0).mean(), (d <= 1).mean(), d.max()))
@@ -1676,10 +1594,10 @@ def test_device_bvh_build_is_interchangeable(gpu, scenes, name, max_leaf):
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     rays = np.concatenate([org, d], axis=1).astype(np.float32)
     res = {}
-    try:
+    with options(gpu) as opt:
         for builder in (0, 1, 2):
-            gpu.set_option("bvh_builder", builder)
-            gpu.set_option("max_leaf", max_leaf)
+            opt.set("bvh_builder", builder)
+            opt.set("max_leaf", max_leaf)
             gpu.upload_scene(sc)
             st = gpu.stats()
             if builder:
@@ -1689,17 +1607,13 @@ def test_device_bvh_build_is_interchangeable(gpu, scenes, name, max_leaf):
                 assert st["bvh_build_ms"] == 0
             hit, el = gpu.debug_intersect(rays)
             gpu.set_resolution(160, 90)
-            gpu.set_option("counters", 1)
+            opt.set("counters", 1)
             gpu.clear()
             gpu.render(1, 3)
             acc = gpu.read_accumulator().astype(np.float64)
             st = gpu.stats()
-            gpu.set_option("counters", 0)
+            opt.set("counters", 0)
             res[builder] = (hit, el, acc, st["node_tests"] / max(1, st["rays"]), st["bvh_build_ms"])
-    finally:
-        gpu.set_option("bvh_builder", -1)
-        gpu.set_option("max_leaf", 4)
-        gpu.set_option("counters", 0)
     h0, e0, a0, nt0, _ = res[0]
     ref, _ = o.render(160, 90, 1, 3, threads=0, counters=True)
     for builder in (1, 2):
@@ -1765,17 +1679,15 @@ def test_device_builders_at_a_million_primitives(gpu, ha):
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     rays = np.concatenate([org, d], axis=1).astype(np.float32)
     res = {}
-    try:
+    with options(gpu) as opt:
         for builder in (1, 2):
-            gpu.set_option("bvh_builder", builder)
+            opt.set("bvh_builder", builder)
             gpu.upload_scene(sc)
             gpu.upload_scene(sc)                      # second build: allocator and code caches warm
             st = gpu.stats()
             assert st["triangles"] == faces.shape[0]
             res[builder] = (gpu.debug_trace(rays), st["bvh_build_ms"], st["bvh_nodes"])
             print("device builder %d: %d triangles -> %d records in %.2f ms" % (builder, st["triangles"], st["bvh_nodes"], st["bvh_build_ms"]))
-    finally:
-        gpu.set_option("bvh_builder", -1)
     (h1, e1), ms1, _ = res[1]
     (h2, e2), ms2, _ = res[2]
     assert np.array_equal(h1.view(np.uint32), h2.view(np.uint32)) and np.array_equal(e1, e2)
@@ -1803,11 +1715,11 @@ def test_builders_at_four_million_triangles(gpu, ha, orc):
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     rays = np.concatenate([org, d], axis=1).astype(np.float32)
     res = {}
-    try:
+    with options(gpu) as opt:
         # the default (bvh_builder = -1) picks the device PLOC build for a scene of this size: the upload — flatten, copy, build — takes about a
         # second where the host's one-thread SAH build alone takes 25 (scenes below 200,000 primitives keep the host tree: checked on rtcamp6)
         import time
-        gpu.set_option("bvh_builder", -1)
+        opt.set("bvh_builder", -1)
         t0 = time.perf_counter()
         gpu.upload_scene(sc)
         t_auto = time.perf_counter() - t0
@@ -1819,7 +1731,7 @@ def test_builders_at_four_million_triangles(gpu, ha, orc):
         gpu.upload_scene(small)
         assert gpu.stats()["bvh_builder_used"] == 0
         for builder in (1, 2, 0):
-            gpu.set_option("bvh_builder", builder)
+            opt.set("bvh_builder", builder)
             gpu.upload_scene(sc)
             st = gpu.stats()
             assert st["triangles"] == faces.shape[0] and st["bvh_nodes"] > faces.shape[0] // 4 and st["bvh_builder_used"] == builder
@@ -1827,8 +1739,6 @@ def test_builders_at_four_million_triangles(gpu, ha, orc):
             print("builder %d: %d triangles -> %d records per octant (%.0f MB of 16-byte records), device build %.2f ms" % (
                 builder, st["triangles"], st["bvh_nodes"], (st["bvh_nodes"] + 1) * 8 * 16 / 1e6, st["bvh_build_ms"]))
             assert (st["bvh_nodes"] + 1) * 8 * 16 > (1 << 28)          # the quantised records' byte offsets pass the old 2^28 limit
-    finally:
-        gpu.set_option("bvh_builder", -1)
     (h0, e0), (s0, se0) = res[0]
     res[3] = auto_hits
     for b in (1, 2, 3):
@@ -1854,8 +1764,7 @@ def test_hundreds_of_launches_in_one_call(gpu, scenes):
     sc, _ = scenes("cornell_mini")
     gpu.upload_scene(sc)
     gpu.set_resolution(48, 32)
-    gpu.set_option("batch", 1)
-    try:
+    with options(gpu, {"batch": 1}):
         gpu.clear()
         gpu.render(1, 401)
         one = gpu.read_accumulator().astype(np.float64)
@@ -1865,8 +1774,6 @@ def test_hundreds_of_launches_in_one_call(gpu, scenes):
         for k in range(4):
             gpu.render(1 + 100 * k, 101 + 100 * k)
         four = gpu.read_accumulator().astype(np.float64)
-    finally:
-        gpu.set_option("batch", 0)
     assert np.abs(one - four).max() <= 1e-5 * max(1.0, np.abs(one).max())
 
 
@@ -1898,24 +1805,22 @@ def test_seed_kernels_agree_on_odd_shapes(gpu, scenes):
     gpu.upload_scene(sc)
     rng = np.random.default_rng(12)
     shapes = [(1, 1), (3, 2), (5, 17), (64, 1), (257, 3), (100, 100)] + [(int(rng.integers(1, 400)), int(rng.integers(1, 300))) for _ in range(4)]
-    try:
+    with options(gpu) as opt:
         for (w, h) in shapes:
             begin, stride = int(rng.integers(1, 50)), int(rng.integers(1, 4))
             end = begin + stride * int(rng.integers(1, 9))
             gpu.set_resolution(w, h)
             outs = []
             for mode in (0, 1, 2, 3, 4):
-                if not _seed_mode_available(gpu, mode):
+                if not _seed_mode_available(opt, mode):
                     continue
-                gpu.set_debug_option("seed_mode", mode)
+                opt.set("seed_mode", mode)
                 gpu.clear()
                 gpu.render(begin, end, stride)
                 outs.append(gpu.read_accumulator().astype(np.float64))
             for o in outs[1:]:
                 assert np.isfinite(o).all()
                 assert np.array_equal(outs[0], o), (w, h, begin, end, stride, np.abs(outs[0] - o).max())
-    finally:
-        gpu.set_debug_option("seed_mode", 2)
 
 
 def test_ragged_sizes_and_large_sampling_indices_path_by_path(gpu, scenes):
@@ -1983,14 +1888,11 @@ def test_russian_roulette_is_unbiased_and_off_by_default(gpu, scenes):
     gpu.set_resolution(w, h)
 
     def render(rr):
-        gpu.set_option("russian_roulette", rr)
-        gpu.set_option("counters", 1)
-        gpu.clear()
-        gpu.render(1, S + 1)
-        acc = gpu.read_accumulator().astype(np.float64)
-        st = gpu.stats()
-        gpu.set_option("counters", 0)
-        gpu.set_option("russian_roulette", 0)
+        with options(gpu, {"russian_roulette": rr, "counters": 1}):
+            gpu.clear()
+            gpu.render(1, S + 1)
+            acc = gpu.read_accumulator().astype(np.float64)
+            st = gpu.stats()
         return acc, st["rays"] / st["paths"]
 
     ref, rays_ref = render(0)

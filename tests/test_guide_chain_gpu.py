@@ -9,7 +9,8 @@ import pytest
 
 import guide_chain as gc
 from cli import ASSETS, run_cli
-from test_denoise_cpu import bits, core, core_denoise  # noqa: F401  (core: the g++-built filter harness, a fixture)
+from gpu_helpers import bits, error_of, renderer, same
+from test_denoise_cpu import core, core_denoise  # noqa: F401  (core: the g++-built filter harness, a fixture)
 from test_guide_chain_cpu import harness  # noqa: F401  (the g++-built host form, a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -28,34 +29,17 @@ REGIONS = [(29, 17, 40, 24), (13, 9, 45, 27)]
 TOL_DEV_NORMAL, TOL_DEV_LENGTH = 5.2e-5, 2.0e-5
 
 
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+def _make(ha, sc, bounces=None, qn=1, region=None, w=W, h=H, moments=False, counts=False):
+    opts = dict({"quant_nodes": qn}, **({} if bounces is None else {"guide_bounces": bounces}))
+    return renderer(ha, sc, opts, None, (w, h), region, moments=moments, counts=counts)
 
 
-def _code(ha, fn, *a, **kw):
-    with pytest.raises(ha.HipError) as e:
-        fn(*a, **kw)
-    return e.value.code
-
-
-def _renderer(ha, sc, bounces=None, qn=1, region=None, w=W, h=H, moments=False, counts=False):
-    r = ha.Renderer(0)
-    r.set_option("quant_nodes", qn)
-    r.upload_scene(sc)
-    r.set_resolution(w, h)
-    if region is not None:
-        r.set_region(*region)
-    if moments:
-        r.set_option("moments", 1)
-    if counts:
-        r.set_option("sample_counts", 1)
-    if bounces is not None:
-        r.set_option("guide_bounces", bounces)
-    return r
+def _err(ha, fn, *a, **kw):
+    return error_of(ha, fn, *a, **kw)[0]
 
 
 def _planes(ha, sc, bounces=None, **kw):
-    r = _renderer(ha, sc, bounces, **kw)
+    r = _make(ha, sc, bounces, **kw)
     r.render_guides()
     g = r.read_guides()
     r.close()
@@ -83,9 +67,9 @@ def test_default_is_zero_bounces(ha, scenes, scene, qn):
     same bits."""
     sc = scenes(scene)[0]
     default = _planes(ha, sc, None, qn=qn)
-    assert _same(_planes(ha, sc, 0, qn=qn), default)
+    assert same(_planes(ha, sc, 0, qn=qn), default)
     assert (default[..., 7] == 1.0).sum() > 500
-    assert not _same(_planes(ha, sc, 4, qn=qn), default)         # and the chain is not a no-op on these scenes
+    assert not same(_planes(ha, sc, 4, qn=qn), default)         # and the chain is not a no-op on these scenes
 
 
 def test_without_a_delta_surface_nothing_changes(ha):
@@ -97,7 +81,7 @@ def test_without_a_delta_surface_nothing_changes(ha):
     base = _planes(ha, sc, 0)
     assert (base[..., 7] == 1.0).sum() > 500
     for bounces in (1, 4, 8):
-        assert _same(_planes(ha, sc, bounces), base), bounces
+        assert same(_planes(ha, sc, bounces), base), bounces
 
 
 COLOURS = {"wall": (0.75, 0.5, 0.25), "left": (0.25, 0.75, 0.5), "right": (0.5, 0.25, 1.0), "floor": (0.125, 0.375, 0.625)}
@@ -117,7 +101,7 @@ def _mirror_scene(ha):
 def test_one_planar_mirror_with_dyadic_colours(ha, qn):
     sc = _mirror_scene(ha)
     g0, g1, g8 = (_planes(ha, sc, k, qn=qn) for k in (0, 1, 8))
-    assert _same(g1, g8)                                          # a planar mirror never sees itself: one bounce is all there is
+    assert same(g1, g8)                                          # a planar mirror never sees itself: one bounce is all there is
     differ = (bits(g1) != bits(g0)).any(-1)
     assert differ.sum() > 100
     full = differ & (g1[..., 7] == 1.0)
@@ -126,7 +110,7 @@ def test_one_planar_mirror_with_dyadic_colours(ha, qn):
     assert all(any((a == c).all() for c in half) for a in g1[full][:, 0:3])
     assert (g1[full][:, 0:3] == half[0]).all()                    # (the wall, by construction)
     assert (g1[full][:, 3:6] == np.float32([0.0, 0.0, -1.0])).all() and (g1[full][:, 6] > g0[full][:, 6] + 8.0).all()
-    assert _same(g1[~differ], g0[~differ])
+    assert same(g1[~differ], g0[~differ])
 
 
 # ---------------------------------------------------------------------------------------------------------------- exact identities, K = 4
@@ -135,8 +119,8 @@ def test_one_planar_mirror_with_dyadic_colours(ha, qn):
 def test_node_formats_repeat_calls_regions_and_the_mask(ha, scenes, chain_guides, scene):
     sc = scenes(scene)[0]
     full = chain_guides(scene, 4, 1)
-    assert _same(chain_guides(scene, 4, 0), full)                # 16-byte and 32-byte nodes: the same closest hits, the same chain
-    r = _renderer(ha, sc, 4, counts=True, moments=True)
+    assert same(chain_guides(scene, 4, 0), full)                # 16-byte and 32-byte nodes: the same closest hits, the same chain
+    r = _make(ha, sc, 4, counts=True, moments=True)
     r.render(1, 4)
     mask = np.zeros(((H + 3) // 4, (W + 3) // 4), np.uint8)
     mask[2:5, 3:9] = 1
@@ -146,16 +130,16 @@ def test_node_formats_repeat_calls_regions_and_the_mask(ha, scenes, chain_guides
     r.render_guides()
     g = r.read_guides()
     r.render_guides()
-    assert _same(r.read_guides(), g) and _same(g, full)          # two calls, and the whole region whatever the mask
+    assert same(r.read_guides(), g) and same(g, full)          # two calls, and the whole region whatever the mask
     after = (r.read_accumulator(), r.read_moments(), r.read_sample_counts(), r.stats())
-    assert _same(before[0], after[0]) and _same(before[1][0], after[1][0]) and before[1][1] == after[1][1] and np.array_equal(before[2], after[2])
+    assert same(before[0], after[0]) and same(before[1][0], after[1][0]) and before[1][1] == after[1][1] and np.array_equal(before[2], after[2])
     assert before[3]["paths"] == after[3]["paths"] and after[3]["trace_launches"] == before[3]["trace_launches"]
     assert after[3]["debug_launches"] == before[3]["debug_launches"] + 2 and after[3]["debug_kernel_ms"] > before[3]["debug_kernel_ms"]
     r.close()
     for region in REGIONS:
         for qn in (1, 0):
             x0, y0, w, h = region
-            assert _same(_planes(ha, sc, 4, qn=qn, region=region), np.ascontiguousarray(full[y0:y0 + h, x0:x0 + w])), (region, qn)
+            assert same(_planes(ha, sc, 4, qn=qn, region=region), np.ascontiguousarray(full[y0:y0 + h, x0:x0 + w])), (region, qn)
 
 
 @pytest.mark.parametrize("scene", SCENES)
@@ -168,7 +152,7 @@ def test_pixels_whose_first_hits_are_rough_keep_their_planes(ha, scenes, orc, ch
     g0, g4 = chain_guides(scene, 0), chain_guides(scene, 4)
     print("%s: %d of %d pixels decided rough by the oracle; %d pixels differ between K = 0 and K = 4" % (scene, rough.sum(), rough.size, (bits(g0) != bits(g4)).any(-1).sum()))
     assert rough.sum() > 500 and (g0[rough][:, 7] == 1.0).all()
-    assert _same(g4[rough], g0[rough])
+    assert same(g4[rough], g0[rough])
 
 
 # ---------------------------------------------------------------------------------------------------------------- against the host form
@@ -215,52 +199,52 @@ def test_device_against_the_host_form(ha, untextured, bounces, qn):
     print("K = %d, quant_nodes %d: %.4f of the pixels disagree in albedo; on the others: normal %.3g absolute, path length %.3g relative" % (bounces, qn, 1.0 - agree.mean(), e_nrm, e_len))
     assert (want[..., 7] == 1.0).sum() > 1000
     assert 1.0 - agree.mean() <= 0.01
-    assert _same(g[..., 7][agree], want[..., 7][agree])
+    assert same(g[..., 7][agree], want[..., 7][agree])
     assert e_nrm <= TOL_DEV_NORMAL and e_len <= TOL_DEV_LENGTH
 
 
 # ---------------------------------------------------------------------------------------------------------------- state
 
 def test_option_state_rules(ha, scenes):
-    r = _renderer(ha, scenes("rtcamp6_v3_1")[0], moments=True)
+    r = _make(ha, scenes("rtcamp6_v3_1")[0], moments=True)
     r.render(1, 5)
     r.denoise()
     g0, d0 = r.read_guides(), r.read_denoised()
     r.set_option("guide_bounces", 0)                             # the value it has: nothing changes
-    assert _same(r.read_guides(), g0) and _same(r.read_denoised(), d0)
+    assert same(r.read_guides(), g0) and same(r.read_denoised(), d0)
     for bad in (9, -1, 2.5, float("nan")):
-        assert _code(ha, r.set_option, "guide_bounces", bad) == HR_ERR_INVALID, bad
-        assert _same(r.read_guides(), g0) and _same(r.read_denoised(), d0)
+        assert _err(ha, r.set_option, "guide_bounces", bad) == HR_ERR_INVALID, bad
+        assert same(r.read_guides(), g0) and same(r.read_denoised(), d0)
     r.set_option("guide_bounces", 4)                             # a new value: the planes and the image filtered with them go
-    assert _code(ha, r.read_guides) == HR_ERR_INVALID and _code(ha, r.read_denoised) == HR_ERR_INVALID and _code(ha, r.resolve_denoised) == HR_ERR_INVALID
+    assert _err(ha, r.read_guides) == HR_ERR_INVALID and _err(ha, r.read_denoised) == HR_ERR_INVALID and _err(ha, r.resolve_denoised) == HR_ERR_INVALID
     r.denoise()                                                  # renders the chain's planes itself
     g4, d4 = r.read_guides(), r.read_denoised()
-    assert not _same(g4, g0) and not _same(d4, d0)
+    assert not same(g4, g0) and not same(d4, d0)
     r.set_option("guide_bounces", 4)
-    assert _same(r.read_guides(), g4) and _same(r.read_denoised(), d4)
+    assert same(r.read_guides(), g4) and same(r.read_denoised(), d4)
     r.render_guides()
-    assert _same(r.read_guides(), g4) and _code(ha, r.read_denoised) == HR_ERR_INVALID
+    assert same(r.read_guides(), g4) and _err(ha, r.read_denoised) == HR_ERR_INVALID
     r.write_guides(g0)                                           # written planes are whatever the host says, for any K
-    assert _same(r.read_guides(), g0)
+    assert same(r.read_guides(), g0)
     r.denoise()
-    assert _same(r.read_denoised(), d0)
+    assert same(r.read_denoised(), d0)
     r.set_option("guide_bounces", 0)                             # and a new value drops written planes too
-    assert _code(ha, r.read_guides) == HR_ERR_INVALID
+    assert _err(ha, r.read_guides) == HR_ERR_INVALID
     r.render_guides()
-    assert _same(r.read_guides(), g0)
+    assert same(r.read_guides(), g0)
     r.close()
 
 
 @pytest.mark.parametrize("scene", SCENES)
 def test_denoise_with_chain_guides_equals_the_host_core(ha, scenes, core, chain_guides, scene):  # noqa: F811
-    r = _renderer(ha, scenes(scene)[0], 4, moments=True)
+    r = _make(ha, scenes(scene)[0], 4, moments=True)
     r.render(1, 17)
     r.denoise()
     acc, (mom, n), g = r.read_accumulator(), r.read_moments(), r.read_guides()
-    assert n == 16 and _same(g, chain_guides(scene, 4))
+    assert n == 16 and same(g, chain_guides(scene, 4))
     for case in (dict(levels=4, demodulate=1), dict(levels=5, demodulate=0)):
         r.denoise(**case)
-        assert _same(r.read_denoised(), core_denoise(core, acc, mom, n, g, **case)), case
+        assert same(r.read_denoised(), core_denoise(core, acc, mom, n, g, **case)), case
     r.close()
 
 
@@ -273,7 +257,7 @@ def test_quality_ratios_with_and_without_the_chain(ha, scenes, scene):
     0.90 -> 0.91, rtcamp6_v3_1 0.47 -> 0.31 and 1.50 -> 0.60, cornell_mini 0.83 -> 0.60 and 0.78 -> 0.67.  ASSERTED: ratio(16 samplings, K = 4) < 1
     on rtcamp6_v3_1 and cornell_mini, where the host has it at 0.31 and 0.60 (spheres, 0.85 and no delta surface in view, is printed only); and at
     64 samplings only that on rtcamp6_v3_1 the chain's ratio is below the first hit's (host: 0.60 against 1.50) — nothing else at 64."""
-    r = _renderer(ha, scenes(scene)[0], moments=True)
+    r = _make(ha, scenes(scene)[0], moments=True)
     r.render(1, 2049)
     truth = r.read_accumulator() / np.float32(2048 * 4)
     ratios = {}
@@ -321,7 +305,7 @@ def test_partial_tiles_and_lanes_outside_a_region(ha, scenes, tiny_host, qn):
     whole = {}
     for region in (None, TINY_REGION):
         crop = (lambda a: a) if region is None else (lambda a: np.ascontiguousarray(a[y0:y0 + h, x0:x0 + w]))
-        r = _renderer(ha, sc, 0, qn=qn, region=region, w=TINY_W, h=TINY_H)
+        r = _make(ha, sc, 0, qn=qn, region=region, w=TINY_W, h=TINY_H)
         r.clear()
         r.render_debug(1)
         normal = r.read_accumulator() * np.float32(0.25)
@@ -333,14 +317,14 @@ def test_partial_tiles_and_lanes_outside_a_region(ha, scenes, tiny_host, qn):
         r.close()
         full = g0[..., 7] == 1.0
         assert full.mean() >= 0.5 and np.array_equal(full, crop(host_full)), region
-        assert _same(normal[full], g0[full][:, 3:6]), region
+        assert same(normal[full], g0[full][:, 3:6]), region
         ends = full & crop(host_ends)
-        assert ends.sum() >= 4 and _same(g8[ends], g0[ends]), region
+        assert ends.sum() >= 4 and same(g8[ends], g0[ends]), region
         if region is None:
             whole = dict(normal=normal, g0=g0, g8=g8)
         else:
             for name, a in (("normal", normal), ("g0", g0), ("g8", g8)):
-                assert _same(a, crop(whole[name])), name
+                assert same(a, crop(whole[name])), name
 
 
 # ---------------------------------------------------------------------------------------------------------------- the CLI

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import light_material_scenes as lm
+from gpu_helpers import options
 from test_corners_gpu import _log_and_render
 
 pytestmark = pytest.mark.gpu
@@ -19,11 +20,8 @@ LIGHT_CASES = sorted(lm.LIGHT_CASES)
 def test_light_material_scene_path_by_path(gpu, ha, orc, name, precise):
     s, ref = lm.get(ha, orc, name)
     gpu.upload_scene(s)
-    gpu.set_option("precise_shading", precise)
-    try:
+    with options(gpu, {"precise_shading": precise}):
         g = _log_and_render(gpu, s)
-    finally:
-        gpu.set_option("precise_shading", -1)
     assert np.isfinite(g[0]).all()
     lm.check(name, g, ref, "device, precise_shading %d" % precise)
 
@@ -37,21 +35,16 @@ def test_nee_culls_do_not_change_a_bit_here_either(gpu, ha, orc, name, precise):
     s, _ = lm.get(ha, orc, name)
     gpu.upload_scene(s)
     gpu.set_resolution(s.w, s.h)
-    gpu.set_option("precise_shading", precise)
     out = {}
-    try:
+    with options(gpu, {"precise_shading": precise}) as opt:
         for cull in (7, 0):
-            gpu.set_debug_option("nee_cull", cull)
-            gpu.set_option("counters", 1)
+            opt.set("nee_cull", cull)
+            opt.set("counters", 1)
             gpu.clear()
             gpu.render(1, 5)
             st = gpu.stats()
-            gpu.set_option("counters", 0)
+            opt.set("counters", 0)
             out[cull] = (gpu.read_accumulator().copy(), st, gpu.debug_path_log(1))
-    finally:
-        gpu.set_debug_option("nee_cull", 7)
-        gpu.set_option("counters", 0)
-        gpu.set_option("precise_shading", -1)
     (a, sa, la), (b, sb, lb) = out[7], out[0]
     assert a.sum() > 0 and np.isfinite(a).all() and np.array_equal(a, b), (name, np.abs(a - b).max())
     for x, y in zip(la, lb):
@@ -72,17 +65,13 @@ def test_split_pipeline_renders_the_same_bits(gpu, ha, orc, name, precise):
     s, _ = lm.get(ha, orc, name)
     gpu.upload_scene(s)
     gpu.set_resolution(s.w, s.h)
-    gpu.set_option("precise_shading", precise)
     out = []
-    try:
+    with options(gpu, {"precise_shading": precise}) as opt:
         for mode in (0, 1):
-            gpu.set_debug_option("trace_mode", mode)
+            opt.set("trace_mode", mode)
             gpu.clear()
             gpu.render(1, 3)
             out.append((gpu.read_accumulator().copy(), gpu.debug_path_log(1)))
-    finally:
-        gpu.set_debug_option("trace_mode", -1)
-        gpu.set_option("precise_shading", -1)
     (a, la), (b, lb) = out
     assert a.sum() > 0 and np.isfinite(a).all() and np.array_equal(a, b), (name, np.abs(a - b).max())
     for x, y in zip(la, lb):
@@ -94,12 +83,7 @@ def test_split_pipeline_renders_the_same_bits(gpu, ha, orc, name, precise):
 def test_light_material_scene_on_the_other_trees(gpu, ha, orc, name, option, value, default):
     """the 32-byte nodes and the device-built PLOC tree: the same limits"""
     s, ref = lm.get(ha, orc, name)
-    gpu.set_option(option, value)
-    gpu.set_option("precise_shading", 0)
-    try:
+    with options(gpu, {option: value, "precise_shading": 0}):
         gpu.upload_scene(s)
         g = _log_and_render(gpu, s)
-    finally:
-        gpu.set_option("precise_shading", -1)
-        gpu.set_option(option, default)
     lm.check(name, g, ref, "device, %s %d" % (option, value))

@@ -8,6 +8,7 @@ import pytest
 
 import ckpt
 from cli import ASSETS, run_cli
+from gpu_helpers import error_of, renderer, same
 from test_moments_cpu import noise_reference, ulp_distance
 
 pytestmark = pytest.mark.gpu
@@ -21,19 +22,12 @@ CONFIGS = {"default": ({}, {}), "fp32": ({"precise_shading": 0}, {}), "precise":
            "fp32-split": ({"precise_shading": 0}, {"trace_mode": 1}), "precise-mega": ({"precise_shading": 1}, {"trace_mode": 0})}
 
 
-def _renderer(ha, sc, opts=None, dbg=None, frame=(W, H), region=None, moments=True):
-    r = ha.Renderer(0)
-    r.upload_scene(sc)
-    for k, v in (opts or {}).items():
-        r.set_option(k, v)
-    for k, v in (dbg or {}).items():
-        r.set_debug_option(k, v)
-    r.set_resolution(*frame)
-    if region is not None:
-        r.set_region(*region)
-    if moments:
-        r.set_option("moments", 1)
-    return r
+def _make(ha, sc, opts=None, dbg=None, region=None, moments=True):
+    return renderer(ha, sc, opts, dbg, (W, H), region, moments=moments)
+
+
+def _err(ha, fn, *a):
+    return error_of(ha, fn, *a)[0]
 
 
 def _per_sampling(r, samplings):
@@ -52,17 +46,13 @@ def _moments_of(xs):
     return np.concatenate([np.cumsum(x, axis=0)[-1], np.cumsum(x * x, axis=0)[-1]], axis=-1)
 
 
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
-
-
 @pytest.mark.parametrize("name", SCENES)
 @pytest.mark.parametrize("config", sorted(CONFIGS))
 def test_moments_to_the_bit(ha, scenes, name, config):
     sc, _ = scenes(name)
     opts, dbg = CONFIGS[config]
-    ref_r = _renderer(ha, sc, opts, dbg, moments=False)
-    r = _renderer(ha, sc, opts, dbg)
+    ref_r = _make(ha, sc, opts, dbg, moments=False)
+    r = _make(ha, sc, opts, dbg)
     try:
         xs = _per_sampling(ref_r, range(1, S + 1))
         assert np.isfinite(xs).all() and xs.sum() > 0 and xs.std(axis=0).max() > 0
@@ -74,7 +64,7 @@ def test_moments_to_the_bit(ha, scenes, name, config):
                 r.render(a, b)
             mom, n = r.read_moments()
             assert n == S and mom.shape == (H, W, 6)
-            assert _same_bits(mom, ref), (name, config, batch, cuts, float(np.abs(mom - ref).max()))
+            assert same(mom, ref), (name, config, batch, cuts, float(np.abs(mom - ref).max()))
         # a stride-2 shard against its own samplings
         r.set_option("batch", 0)
         for first in (1, 2):
@@ -82,7 +72,7 @@ def test_moments_to_the_bit(ha, scenes, name, config):
             r.render(first, S + 1, 2)
             mom, n = r.read_moments()
             assert n == S // 2
-            assert _same_bits(mom, _moments_of(xs[first - 1::2])), (name, config, "stride 2 from", first)
+            assert same(mom, _moments_of(xs[first - 1::2])), (name, config, "stride 2 from", first)
     finally:
         r.close()
         ref_r.close()
@@ -95,16 +85,13 @@ def test_the_accumulator_does_not_move(ha, scenes, name, config):
     opts, dbg = CONFIGS[config]
     accs = []
     for on in (False, True):
-        r = _renderer(ha, sc, opts, dbg, moments=on)
-        try:
+        with _make(ha, sc, opts, dbg, moments=on) as r:
             r.render(1, 8)
             r.set_option("batch", 3)
             r.render(8, S + 1)
             r.render(2, S + 1, 3)
             accs.append(r.read_accumulator())
             img = r.resolve(S)
-        finally:
-            r.close()
         accs.append(img)
     assert np.array_equal(accs[0].view(np.uint32), accs[2].view(np.uint32)) and np.array_equal(accs[1], accs[3])
 
@@ -112,8 +99,8 @@ def test_the_accumulator_does_not_move(ha, scenes, name, config):
 @pytest.mark.parametrize("name", SCENES)
 def test_region_moments_are_the_frames_window(ha, scenes, name):
     sc, _ = scenes(name)
-    full = _renderer(ha, sc)
-    reg = _renderer(ha, sc, region=REGION)
+    full = _make(ha, sc)
+    reg = _make(ha, sc, region=REGION)
     try:
         full.render(1, S + 1)
         reg.render(1, S + 1)
@@ -121,19 +108,13 @@ def test_region_moments_are_the_frames_window(ha, scenes, name):
         mr, nr = reg.read_moments()
         x0, y0, w, h = REGION
         assert nf == nr == S and mr.shape == (h, w, 6)
-        assert _same_bits(mr, mf[y0:y0 + h, x0:x0 + w])
+        assert same(mr, mf[y0:y0 + h, x0:x0 + w])
         # the region's noise image is the estimate of the same moments
         assert np.array_equal(reg.noise_image(0.01), full.noise_image(0.01)[y0:y0 + h, x0:x0 + w])
         assert reg.noise_estimate(0.01, 0.05)["pixels"] == w * h
     finally:
         full.close()
         reg.close()
-
-
-def _code(ha, fn, *a):
-    with pytest.raises(ha.HipError) as e:
-        fn(*a)
-    return e.value.code
 
 
 def test_life_cycle(ha, scenes):
@@ -143,26 +124,26 @@ def test_life_cycle(ha, scenes):
     r2 = None
     try:
         r.upload_scene(sc)
-        assert _code(ha, r.set_option, "moments", 1) == HR_ERR_NO_TARGET      # before hr_set_resolution
+        assert _err(ha, r.set_option, "moments", 1) == HR_ERR_NO_TARGET      # before hr_set_resolution
         r.set_resolution(W, H)
         # off: the four functions refuse
-        assert _code(ha, r.read_moments) == HR_ERR_INVALID and _code(ha, r.write_moments, np.zeros((H, W, 6)), 3) == HR_ERR_INVALID
-        assert _code(ha, r.noise_estimate, 0.01, 0.05) == HR_ERR_INVALID and _code(ha, r.noise_image, 0.01) == HR_ERR_INVALID
-        assert _code(ha, r.set_option, "moments", 2) == HR_ERR_INVALID
+        assert _err(ha, r.read_moments) == HR_ERR_INVALID and _err(ha, r.write_moments, np.zeros((H, W, 6)), 3) == HR_ERR_INVALID
+        assert _err(ha, r.noise_estimate, 0.01, 0.05) == HR_ERR_INVALID and _err(ha, r.noise_image, 0.01) == HR_ERR_INVALID
+        assert _err(ha, r.set_option, "moments", 2) == HR_ERR_INVALID
         r.render_debug(2)                                                       # allowed while off
         r.clear()
         r.set_option("moments", 1)
         mom, n = r.read_moments()
         assert n == 0 and not mom.any()
-        assert _code(ha, r.render_debug, 2) == HR_ERR_UNSUPPORTED
+        assert _err(ha, r.render_debug, 2) == HR_ERR_UNSUPPORTED
         # n < 2: no variance
-        assert _code(ha, r.noise_estimate, 0.01, 0.05) == HR_ERR_INVALID
+        assert _err(ha, r.noise_estimate, 0.01, 0.05) == HR_ERR_INVALID
         r.render(1, 2)
-        assert r.read_moments()[1] == 1 and _code(ha, r.noise_estimate, 0.01, 0.05) == HR_ERR_INVALID and _code(ha, r.noise_image, 0.01) == HR_ERR_INVALID
+        assert r.read_moments()[1] == 1 and _err(ha, r.noise_estimate, 0.01, 0.05) == HR_ERR_INVALID and _err(ha, r.noise_image, 0.01) == HR_ERR_INVALID
         r.render(2, 3)
         assert r.noise_estimate(0.01, 0.05)["samplings"] == 2
-        assert _code(ha, r.noise_estimate, 0.0, 0.05) == HR_ERR_INVALID and _code(ha, r.noise_estimate, -1.0, 0.05) == HR_ERR_INVALID
-        assert _code(ha, r.noise_estimate, float("nan"), 0.05) == HR_ERR_INVALID
+        assert _err(ha, r.noise_estimate, 0.0, 0.05) == HR_ERR_INVALID and _err(ha, r.noise_estimate, -1.0, 0.05) == HR_ERR_INVALID
+        assert _err(ha, r.noise_estimate, float("nan"), 0.05) == HR_ERR_INVALID
         # hr_clear, hr_set_region, hr_set_resolution zero moments and count (the last two at the new size)
         r.clear()
         mom, n = r.read_moments()
@@ -181,28 +162,28 @@ def test_life_cycle(ha, scenes):
         before, n = r.read_moments()
         r.write_accumulator(np.ones((32, 64, 3), dtype=np.float32))
         after, n2 = r.read_moments()
-        assert n == n2 == 3 and _same_bits(before, after)
+        assert n == n2 == 3 and same(before, after)
         rng = np.random.default_rng(7)
         data = rng.standard_normal((32, 64, 6)) * 10.0 ** rng.integers(-300, 60, (32, 64, 6))
         r.write_moments(data, 123456789012)
         back, n = r.read_moments()
-        assert n == 123456789012 and _same_bits(back, data)
+        assert n == 123456789012 and same(back, data)
         # off frees, on again starts from zero
         r.set_option("moments", 0)
-        assert _code(ha, r.read_moments) == HR_ERR_INVALID
+        assert _err(ha, r.read_moments) == HR_ERR_INVALID
         r.set_option("moments", 1)
         mom, n = r.read_moments()
         assert n == 0 and not mom.any()
         # two shards: moments added on the host in rank order, written into one context -> the count S and the whole render's estimate
         r.set_resolution(W, H)
-        r2 = _renderer(ha, sc)
+        r2 = _make(ha, sc)
         r.render(1, S + 1, 2)
         r2.render(2, S + 1, 2)
         (m0, n0), (m1, n1) = r.read_moments(), r2.read_moments()
         assert n0 == n1 == S // 2
         r2.write_moments(m0 + m1, n0 + n1)
         tot, n = r2.read_moments()
-        assert n == S and _same_bits(tot, m0 + m1)
+        assert n == S and same(tot, m0 + m1)
         est = r2.noise_estimate(0.01, 0.05)
         assert est["samplings"] == S and est["pixels"] == W * H and 0 < est["mean_error"] < est["max_error"]
         # the same samplings rendered by one context: the same sums up to the order of the additions
@@ -219,8 +200,7 @@ def test_life_cycle(ha, scenes):
 @pytest.mark.parametrize("name", SCENES)
 def test_noise_map_and_summary(ha, scenes, name):
     sc, _ = scenes(name)
-    r = _renderer(ha, sc)
-    try:
+    with _make(ha, sc) as r:
         r.render(1, S + 1)
         mom, n = r.read_moments()
         for floor, thr in [(0.01, 0.05), (0.5, 0.01), (1e-6, 1.0)]:
@@ -239,8 +219,6 @@ def test_noise_map_and_summary(ha, scenes, name):
             assert again == est and np.float64(again["mean_error"]).tobytes() == np.float64(est["mean_error"]).tobytes()
             assert np.array_equal(r.noise_image(floor), img)
         assert 0 < r.noise_estimate(0.01, 0.05)["pixels_above"] <= W * H
-    finally:
-        r.close()
 
 
 @pytest.mark.parametrize("name,oracle_rms", [("rtcamp6_v3_1", 1.0040), ("cornell_mini", 1.0143)])
@@ -254,8 +232,7 @@ def test_the_estimate_means_something(ha, scenes, name, oracle_rms):
     used as a gate."""
     assert 0.8 <= oracle_rms <= 1.25
     sc, _ = scenes(name)
-    r = _renderer(ha, sc)
-    try:
+    with _make(ha, sc) as r:
         stats = []
         for first in (1, 65):
             r.clear()
@@ -265,8 +242,6 @@ def test_the_estimate_means_something(ha, scenes, name, oracle_rms):
             m = mom[..., :3] / n
             var = np.maximum(0.0, (mom[..., 3:] - mom[..., :3] * m) / (n - 1))
             stats.append((m / 4.0, np.sqrt(var / n) / 4.0))
-    finally:
-        r.close()
     (ma, sa), (mb, sb) = stats
     k = (sa > 0) & (sb > 0)
     z = (ma - mb)[k] / np.sqrt(sa[k] ** 2 + sb[k] ** 2)
@@ -310,14 +285,11 @@ def test_cli_noise_target(tmp_path, ha, scenes):
     assert np.asarray(Image.open(d1 / "result.png")).shape == (H, W, 3)
     # the final image is resolved with the samplings actually rendered
     sc, _ = scenes("rtcamp6_v3_1")
-    r = _renderer(ha, sc)
-    try:
+    with _make(ha, sc) as r:
         r.render(1, done + 1)
         exp = r.resolve(done)
         est = r.noise_estimate(0.01, CLI_TARGET)
         e_img = r.noise_image(0.01)
-    finally:
-        r.close()
     assert np.array_equal(np.asarray(Image.open(d1 / "result.png")), exp)
     assert lines[-1] == (done, float("%.9g" % est["mean_error"]), float("%.9g" % est["max_error"]), est["pixels_above"])
     grey = np.asarray(Image.open(d1 / "noise.png"))

@@ -7,6 +7,7 @@ import pytest
 
 import ckpt
 from cli import ASSETS, run_cli
+from gpu_helpers import renderer
 
 pytestmark = pytest.mark.gpu
 
@@ -18,16 +19,6 @@ MODES = {"fp32": ({"precise_shading": 0}, {}), "precise": ({"precise_shading": 1
 # the per-scene gates of tests/test_gpu_parity.py (fp32 shading / precise shading)
 GATES = {"rtcamp6_v3_1": (0.9998, 0.9995)}
 GATES_PRECISE = {"spheres": (0.9998, 0.9997)}
-
-
-def _renderer(ha, sc, opts=None, dbg=None):
-    r = ha.Renderer(0)
-    r.upload_scene(sc)
-    for k, v in (opts or {}).items():
-        r.set_option(k, v)
-    for k, v in (dbg or {}).items():
-        r.set_debug_option(k, v)
-    return r
 
 
 def _render(r, frame, region, s0, s1, stride=1):
@@ -47,8 +38,7 @@ def _crop(a, reg):
 @pytest.mark.parametrize("mode", sorted(MODES))
 def test_region_is_a_bit_exact_crop(ha, scenes, name, mode):
     sc, _ = scenes(name)
-    r = _renderer(ha, sc, *MODES[mode])
-    try:
+    with renderer(ha, sc, *MODES[mode]) as r:
         for (s0, s1, st) in SAMPLINGS:
             full = _render(r, (W, H), None, s0, s1, st)
             assert np.isfinite(full).all() and full.sum() > 0
@@ -56,19 +46,14 @@ def test_region_is_a_bit_exact_crop(ha, scenes, name, mode):
                 acc = _render(r, (W, H), reg, s0, s1, st)
                 assert acc.shape == (reg[3], reg[2], 3)
                 assert np.array_equal(acc, _crop(full, reg)), (name, mode, reg, s0, s1, st)
-    finally:
-        r.close()
 
 
 @pytest.mark.parametrize("name,precise", [("rtcamp6_v3_1", 0), ("spheres", 1)])
 def test_region_matches_oracle_region(ha, scenes, name, precise):
     sc, o = scenes(name)
     reg, s = (37, 21, 101, 63), 4
-    r = _renderer(ha, sc, {"precise_shading": precise})
-    try:
+    with renderer(ha, sc, {"precise_shading": precise}) as r:
         acc = _render(r, (W, H), reg, 1, s + 1).astype(np.float64)
-    finally:
-        r.close()
     ref = o.render_region(W, H, reg[0], reg[1], reg[2], reg[3], 1, s + 1, threads=0)
     rel = np.abs(acc - ref) / np.maximum(1.0, np.abs(ref))
     f2, f3 = float((rel <= 1e-2).mean()), float((rel <= 1e-3).mean())
@@ -82,8 +67,8 @@ def test_stitched_tiles_equal_the_frame(ha, scenes):
     full-frame context, that accumulator resolves to the full-frame image's bytes."""
     sc, _ = scenes("rtcamp6_v3_1")
     tiles = [(0, 0, 193, 101), (193, 0, W - 193, 101), (0, 101, 193, H - 101), (193, 101, W - 193, H - 101)]
-    rs = [_renderer(ha, sc) for _ in tiles]
-    full_r = _renderer(ha, sc)
+    rs = [renderer(ha, sc) for _ in tiles]
+    full_r = renderer(ha, sc)
     try:
         stitched = np.zeros((H, W, 3), dtype=np.float32)
         for r, t in zip(rs, tiles):
@@ -102,8 +87,7 @@ def test_region_resolve(ha, scenes, orc):
     """hr_resolve of a region is update_imgbuf of the region's accumulator as an image of its own (within 1 LSB of the oracle's post chain,
     > 99 % exact); one pixel in from its edges it is the full-frame image's bytes."""
     sc, _ = scenes("rtcamp6_v3_1")
-    r = _renderer(ha, sc)
-    try:
+    with renderer(ha, sc) as r:
         full = _render(r, (W, H), None, 1, 4)
         full_img = r.resolve(3)
         for reg in [(37, 21, 101, 63), (467, 263, 13, 7), (0, 100, 480, 5)]:
@@ -115,13 +99,11 @@ def test_region_resolve(ha, scenes, orc):
             d = np.abs(img.astype(int) - exp.astype(int))
             assert d.max() <= 1 and (d == 0).mean() > 0.99, (reg, d.max(), (d == 0).mean())
             assert np.array_equal(img[1:-1, 1:-1], _crop(full_img, reg)[1:-1, 1:-1]), reg
-    finally:
-        r.close()
 
 
 def test_region_debug_renderer(ha, scenes):
     sc, _ = scenes("rtcamp6_v3_1")
-    r = _renderer(ha, sc)
+    r = renderer(ha, sc)
     reg = (37, 21, 101, 63)
     try:
         for mode in range(4):
@@ -141,21 +123,17 @@ def test_region_debug_renderer(ha, scenes):
 def test_region_extreme_frames(ha, scenes, frame, regions, s):
     """The far corner of an 8K frame, and a 257 x 3 frame (aspect ratio beyond 4:1: the saturating seed word, isaac_core.h path_seed_words)."""
     sc, _ = scenes("rtcamp6_v3_1")
-    r = _renderer(ha, sc)
-    try:
+    with renderer(ha, sc) as r:
         full = _render(r, frame, None, *s)
         for reg in regions:
             acc = _render(r, frame, reg, *s)
             assert np.array_equal(acc, _crop(full, reg)), (frame, reg)
-    finally:
-        r.close()
 
 
 def test_region_lifecycle(ha, scenes):
     import torch
     sc, _ = scenes("cornell_mini")
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         with pytest.raises(ha.HipError) as e:
             r.set_region(0, 0, 1, 1)
         assert e.value.code == -4                                       # HR_ERR_NO_TARGET: hr_set_resolution first
@@ -201,8 +179,6 @@ def test_region_lifecycle(ha, scenes):
         assert r.read_accumulator().shape == (H, W, 3)
         r.set_region(0, 0, W, H)                                        # the whole frame as a region is no region
         r.debug_path_log(1)
-    finally:
-        r.close()
 
 
 def test_region_same_device_exchange(ha, scenes):
@@ -210,8 +186,8 @@ def test_region_same_device_exchange(ha, scenes):
     one-context region render (to the tolerance of test_same_device_group_sum)."""
     sc, _ = scenes("cornell_mini")
     reg = (37, 21, 101, 63)
-    rs = [_renderer(ha, sc) for _ in range(2)]
-    one = _renderer(ha, sc)
+    rs = [renderer(ha, sc) for _ in range(2)]
+    one = renderer(ha, sc)
     try:
         for r in rs:
             r.set_resolution(W, H)
@@ -245,15 +221,12 @@ def test_cli_region(tmp_path, ha, scenes):
     assert "region: 37,21 101x63." in p.stdout
     img = np.asarray(Image.open(d1 / "result.png"))
     sc, _ = scenes("rtcamp6_v3_1")
-    r = _renderer(ha, sc)
-    try:
+    with renderer(ha, sc) as r:
         r.set_resolution(W, H)
         r.set_region(*reg)
         for s in range(1, 5):
             r.render(s, s + 1)
         exp = r.resolve(4)
-    finally:
-        r.close()
     assert img.shape == (63, 101, 3) and np.array_equal(img, exp)
     c = ckpt.read(d1 / "ck")
     assert c.magic == ckpt.REGION and c.region == reg and c.complete == ckpt.S_ACCUMULATOR and c.used == c.size == 36 + 101 * 63 * 12

@@ -7,7 +7,8 @@ import pytest
 import ckpt
 import test_robust_cpu as rc
 from cli import ASSETS, run_cli
-from test_adaptive_gpu import MASKS, MODES, RH, RW, SCENES, TARGETS, _bits, _code, _pixels, _same
+from gpu_helpers import bits, error_of, renderer, retarget, same
+from test_adaptive_gpu import MASKS, MODES, RH, RW, SCENES, TARGETS, _pixels
 
 pytestmark = pytest.mark.gpu
 
@@ -16,26 +17,12 @@ BUCKET_MODES = ["fp32-mega", "precise-mega", "fp32-split"]
 N = 20                                                   # samplings of the rendered cases: 9 does not divide it, 3 does not either
 
 
-def _renderer(ha, sc, mode="fp32-mega", target="frame", K=0, moments=False, counts=False):
-    opts, dbg = MODES[mode]
-    r = ha.Renderer(0)
-    for k, v in opts.items():
-        r.set_option(k, v)
-    for k, v in dbg.items():
-        r.set_debug_option(k, v)
-    r.upload_scene(sc)
-    _retarget(r, target, K, moments, counts)
-    return r
+def _make(ha, sc, mode="fp32-mega", target="frame", K=0, moments=False, counts=False):
+    return renderer(ha, sc, *MODES[mode], *TARGETS[target], moments=moments, counts=counts, buckets=K)
 
 
-def _retarget(r, target, K=0, moments=False, counts=False):
-    frame, region = TARGETS[target]
-    r.set_resolution(*frame)
-    if region is not None:
-        r.set_region(*region)
-    r.set_option("moments", 1 if moments else 0)
-    r.set_option("sample_counts", 1 if counts else 0)
-    r.set_option("robust_buckets", K)
+def _aim(r, target, K=0, moments=False, counts=False):
+    retarget(r, *TARGETS[target], moments=moments, counts=counts, buckets=K)
 
 
 _x_cache = {}
@@ -46,15 +33,12 @@ def per_sampling(ha, scenes, name, mode, target, n=N):
     rendered once per (scene, mode, target) by a context without the option and shared."""
     key = (name, mode, target)
     if key not in _x_cache:
-        r = _renderer(ha, scenes(name)[0], mode, target)
-        try:
+        with _make(ha, scenes(name)[0], mode, target) as r:
             xs = []
             for s in range(1, n + 1):
                 r.clear()
                 r.render(s, s + 1)
                 xs.append(r.read_accumulator())
-        finally:
-            r.close()
         _x_cache[key] = np.stack(xs)
         assert np.isfinite(_x_cache[key]).all() and _x_cache[key].sum() > 0
     return _x_cache[key]
@@ -80,12 +64,11 @@ def core(tmp_path_factory):
 @pytest.mark.parametrize("name", SCENES)
 @pytest.mark.parametrize("mode", BUCKET_MODES)
 def test_buckets_equal_a_sequential_f64_loop(ha, scenes, name, mode):
-    r = _renderer(ha, scenes(name)[0], mode)
-    try:
+    with _make(ha, scenes(name)[0], mode) as r:
         for target in sorted(TARGETS):
             x = per_sampling(ha, scenes, name, mode, target)
             for K in (3, 9):
-                _retarget(r, target, K)
+                _aim(r, target, K)
                 assert r.read_buckets()[0].shape == (RH, RW, K, 3) and not r.read_buckets()[0].any()
                 for batch in (0, 1, 5):
                     r.set_option("batch", batch)
@@ -96,20 +79,18 @@ def test_buckets_equal_a_sequential_f64_loop(ha, scenes, name, mode):
                             r.render(*args)
                         got, n = r.read_buckets()
                         assert n == len(samplings), what
-                        assert _same(got, sequential_buckets(x, samplings, K)), what
+                        assert same(got, sequential_buckets(x, samplings, K)), what
                 r.set_option("batch", 0)
-    finally:
-        r.close()
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_the_option_changes_nothing_else(ha, scenes, name):
     sc = scenes(name)[0]
-    off, on = _renderer(ha, sc, moments=True, counts=True), _renderer(ha, sc, K=9, moments=True, counts=True)
+    off, on = _make(ha, sc, moments=True, counts=True), _make(ha, sc, K=9, moments=True, counts=True)
     try:
         for target in sorted(TARGETS):
-            _retarget(off, target, 0, True, True)
-            _retarget(on, target, 9, True, True)
+            _aim(off, target, 0, True, True)
+            _aim(on, target, 9, True, True)
             launches = []
             for r in (off, on):
                 r.set_tile_mask(None)
@@ -117,10 +98,10 @@ def test_the_option_changes_nothing_else(ha, scenes, name):
                 r.set_tile_mask(MASKS["checker"])
                 r.render(8, 13)
                 launches.append(r.stats()["trace_launches"])
-            assert _same(off.read_accumulator(), on.read_accumulator()) and _same(off.read_moments()[0], on.read_moments()[0])
+            assert same(off.read_accumulator(), on.read_accumulator()) and same(off.read_moments()[0], on.read_moments()[0])
             assert np.array_equal(off.read_sample_counts(), on.read_sample_counts()) and off.read_moments()[1] == on.read_moments()[1]
             assert launches[0] == launches[1]
-            assert _code(ha, off.read_buckets)[0] == HR_ERR_INVALID and on.read_buckets()[1] == 12
+            assert error_of(ha, off.read_buckets)[0] == HR_ERR_INVALID and on.read_buckets()[1] == 12
     finally:
         off.close()
         on.close()
@@ -131,11 +112,10 @@ def test_the_option_changes_nothing_else(ha, scenes, name):
 def test_tile_masks(ha, scenes, core, name, target):
     K = 9
     x = per_sampling(ha, scenes, name, "fp32-mega", target)
-    r = _renderer(ha, scenes(name)[0], "fp32-mega", target, K, counts=True)
-    try:
+    with _make(ha, scenes(name)[0], "fp32-mega", target, K, counts=True) as r:
         full = sequential_buckets(x, range(1, 13), K)
         r.render(1, 13)
-        assert _same(r.read_buckets()[0], full)
+        assert same(r.read_buckets()[0], full)
         for mname in ("first", "last", "scattered", "none"):
             pix = _pixels(MASKS[mname])
             r.clear()
@@ -143,7 +123,7 @@ def test_tile_masks(ha, scenes, core, name, target):
             r.render(1, 13)
             got, n = r.read_buckets()
             assert n == 12, mname
-            assert _same(got, np.where(pix[..., None, None], full, 0.0)), mname
+            assert same(got, np.where(pix[..., None, None], full, 0.0)), mname
             assert np.array_equal(r.read_sample_counts(), np.where(pix, 12, 0).astype(np.uint32)), mname
         # a second render under a smaller mask: every pixel holds the buckets of its own prefix 1 .. n_p
         wide = np.maximum(MASKS["checker"], MASKS["scattered"])
@@ -154,14 +134,12 @@ def test_tile_masks(ha, scenes, core, name, target):
         r.render(6, 13)
         counts = np.where(_pixels(MASKS["scattered"]), 12, np.where(_pixels(wide), 5, 0)).astype(np.uint32)
         assert np.array_equal(r.read_sample_counts(), counts)
-        assert _same(r.read_buckets()[0], sequential_buckets(x, range(1, 13), K, counts))
+        assert same(r.read_buckets()[0], sequential_buckets(x, range(1, 13), K, counts))
         # .. and the robust radiance takes every pixel's own count
         r.robust()
         R, trim = rc.core_robust(core, r.read_buckets()[0], counts)
-        assert _same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim)
+        assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim)
         assert (r.read_robust()[counts == 0] == 0).all()
-    finally:
-        r.close()
 
 
 def _resolve_of(r, R):
@@ -172,26 +150,25 @@ def _resolve_of(r, R):
 
 @pytest.mark.parametrize("name", SCENES)
 def test_robust_equals_the_host_core(ha, scenes, core, name):
-    r = _renderer(ha, scenes(name)[0])
-    try:
+    with _make(ha, scenes(name)[0]) as r:
         for target in sorted(TARGETS):
             for K in (9, 3):
                 # rendered buckets, equal counts
-                _retarget(r, target, K)
+                _aim(r, target, K)
                 r.render(1, N + 1)
                 B, n = r.read_buckets()
                 assert n == N
                 r.robust()
                 R, trim = rc.core_robust(core, B, N)
                 got = r.read_robust()
-                assert _same(got, R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
+                assert same(got, R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 assert np.isfinite(got).all() and got.sum() > 0
                 if K == 9 and name == "rtcamp6_v3_1":
                     assert trim.max() > 0                                           # the fireflies of this scene are trimmed somewhere
                 img = r.resolve_robust()
                 assert img.shape == (RH, RW, 3) and np.array_equal(img, _resolve_of(r, got)), (target, K)
                 # rendered buckets, per-pixel counts
-                _retarget(r, target, K, counts=True)
+                _aim(r, target, K, counts=True)
                 r.render(1, 8)
                 r.set_tile_mask(MASKS["checker"])
                 r.render(8, N + 1)
@@ -199,7 +176,7 @@ def test_robust_equals_the_host_core(ha, scenes, core, name):
                 assert set(np.unique(counts)) == {7, N}
                 r.robust()
                 R, trim = rc.core_robust(core, r.read_buckets()[0], counts)
-                assert _same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
+                assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 # written synthetic buckets and counts: n = 0, n < K, n = K, n > K side by side
                 rng = np.random.default_rng(K)
                 counts = rng.integers(0, 3 * K + 3, size=(RH, RW)).astype(np.uint32)
@@ -210,38 +187,35 @@ def test_robust_equals_the_host_core(ha, scenes, core, name):
                 r.write_buckets(B, 123)
                 r.write_sample_counts(counts)
                 back, n = r.read_buckets()
-                assert _same(back, B) and n == 123
+                assert same(back, B) and n == 123
                 r.robust()
                 R, trim = rc.core_robust(core, B, counts)
-                assert _same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
+                assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 assert np.array_equal(r.resolve_robust(), _resolve_of(r, R))
                 # without the counts every pixel has the samplings behind the buckets
-                _retarget(r, target, K)
+                _aim(r, target, K)
                 B = rc.fill_buckets(rc.heavy_tailed(rng, 2 * K + 1, (RH, RW)), K)
                 r.write_buckets(B, 2 * K + 1)
                 r.robust()
                 R, trim = rc.core_robust(core, B, 2 * K + 1)
-                assert _same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
+                assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 # every bucket equal: R is that mean, and the bytes are hr_resolve's of it
                 v = (rng.integers(1, 2 ** 12, size=(RH, RW, 3)) / 256.0).astype(np.float32)
                 r.write_buckets(np.repeat((v.astype(np.float64) * 8.0)[:, :, None, :], K, axis=2), 2 * K)
                 r.robust()
-                assert _same(r.read_robust(), v) and not r.read_robust_trim().any()
+                assert same(r.read_robust(), v) and not r.read_robust_trim().any()
                 assert np.array_equal(r.resolve_robust(), _resolve_of(r, v))
-    finally:
-        r.close()
 
 
 def test_state_rules(ha, scenes):
     sc = scenes("cornell_mini")[0]
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         r.upload_scene(sc)
-        assert _code(ha, r.set_option, "robust_buckets", 9)[0] == HR_ERR_NO_TARGET
+        assert error_of(ha, r.set_option, "robust_buckets", 9)[0] == HR_ERR_NO_TARGET
         r.set_resolution(RW, RH)
         # K = 0: every entry point is refused
         for fn in (r.read_buckets, r.robust, r.read_robust, r.read_robust_trim, r.resolve_robust):
-            assert _code(ha, fn)[0] == HR_ERR_INVALID
+            assert error_of(ha, fn)[0] == HR_ERR_INVALID
         assert r.L.hr_write_buckets(r._h, np.zeros(RH * RW * 27).ctypes.data, 0) == HR_ERR_INVALID
         r.set_option("robust_buckets", 9)
         r.render(1, 10)
@@ -249,14 +223,14 @@ def test_state_rules(ha, scenes):
         assert n == 9 and B.any()
         # bad values change nothing
         for bad in (4, 17, 1, 2, -3, 9.5, 16):
-            assert _code(ha, r.set_option, "robust_buckets", bad)[0] == HR_ERR_INVALID
-        assert _same(r.read_buckets()[0], B)
+            assert error_of(ha, r.set_option, "robust_buckets", bad)[0] == HR_ERR_INVALID
+        assert same(r.read_buckets()[0], B)
         r.set_option("robust_buckets", 9)                                           # the value it has: what was gathered stays
-        assert _same(r.read_buckets()[0], B) and r.read_buckets()[1] == 9
-        assert _code(ha, r.render_debug, 2)[0] == HR_ERR_UNSUPPORTED
+        assert same(r.read_buckets()[0], B) and r.read_buckets()[1] == 9
+        assert error_of(ha, r.render_debug, 2)[0] == HR_ERR_UNSUPPORTED
         # no R before hr_robust; stale after everything it was made of changes
         for fn in (r.read_robust, r.read_robust_trim, r.resolve_robust):
-            assert _code(ha, fn)[0] == HR_ERR_INVALID
+            assert error_of(ha, fn)[0] == HR_ERR_INVALID
         r.set_option("moments", 1)
         acc, mom = r.read_accumulator(), r.read_moments()[0]
 
@@ -267,7 +241,7 @@ def test_state_rules(ha, scenes):
 
         def stale(what):
             for fn in (r.read_robust, r.read_robust_trim, r.resolve_robust):
-                assert _code(ha, fn)[0] == HR_ERR_INVALID, what
+                assert error_of(ha, fn)[0] == HR_ERR_INVALID, what
 
         for what, call in [("render", lambda: r.render(10, 11)), ("clear", r.clear), ("write_accumulator", lambda: r.write_accumulator(acc)),
                            ("write_moments", lambda: r.write_moments(mom, 9)), ("write_buckets", lambda: r.write_buckets(B, 9)),
@@ -289,7 +263,7 @@ def test_state_rules(ha, scenes):
         data = np.random.default_rng(2).standard_normal((RH, RW, 5, 3)) * 1e3
         r.write_buckets(data, 2 ** 40 + 3)
         back, n = r.read_buckets()
-        assert _same(back, data) and n == 2 ** 40 + 3
+        assert same(back, data) and n == 2 ** 40 + 3
         # a new region or target zeroes them at the new size and drops R
         fresh()
         r.set_region(2, 1, 9, 6)
@@ -314,18 +288,15 @@ def test_state_rules(ha, scenes):
         fresh()
         r.set_option("robust_buckets", 0)
         for fn in (r.read_buckets, r.robust, r.read_robust, r.read_robust_trim, r.resolve_robust):
-            assert _code(ha, fn)[0] == HR_ERR_INVALID
+            assert error_of(ha, fn)[0] == HR_ERR_INVALID
         r.set_option("sample_counts", 0)
         r.render_debug(2)                                                            # allowed again
-    finally:
-        r.close()
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_quality_ratio_on_the_device(ha, scenes, core, name):
     w, h, n, K, truth_n = rc.QW, rc.QH, rc.QN, rc.QK, rc.QTRUTH
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         r.upload_scene(scenes(name)[0])
         r.set_resolution(w, h)
         r.set_option("robust_buckets", K)
@@ -333,7 +304,7 @@ def test_quality_ratio_on_the_device(ha, scenes, core, name):
         acc = r.read_accumulator()
         r.robust()
         R, trim = r.read_robust(), r.read_robust_trim()
-        assert _same(R, rc.core_robust(core, r.read_buckets()[0], n)[0])
+        assert same(R, rc.core_robust(core, r.read_buckets()[0], n)[0])
         r.set_option("robust_buckets", 0)
         r.clear()
         r.render(100001, 100001 + truth_n)                                           # the truth: 2,048 further samplings
@@ -342,8 +313,6 @@ def test_quality_ratio_on_the_device(ha, scenes, core, name):
         print("%s on the device: relMSE mean %.4g robust %.4g ratio %.3f, energy kept %.3f, pixels trimmed %.3f"
               % (name, e_mean, e_rob, e_rob / e_mean, R.astype(np.float64).sum() / (acc.astype(np.float64).sum() / (4 * n)), (trim > 0).mean()))
         assert e_rob / e_mean < 1.0
-    finally:
-        r.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the CLI
@@ -375,7 +344,7 @@ def test_cli_robust_images_and_resume(tmp_path):
         assert (one / f).read_bytes() == (two / f).read_bytes(), f
     b_one, n_one, head_one = _checkpoint_buckets(str(one / "c.ckpt"), 9)
     b_two, n_two, _ = _checkpoint_buckets(str(two / "b.ckpt"), 9)
-    assert n_one == n_two == 16 and b_one.any() and np.array_equal(_bits(b_one), _bits(b_two))
+    assert n_one == n_two == 16 and b_one.any() and np.array_equal(bits(b_one), bits(b_two))
     assert head_one == 20 + CW * CH * 12                                             # no other trailer: the header and the accumulator
     # another K, or a file without buckets, is refused together with --robust; without the flag the file keeps the bytes it always had
     r = run_cli(CLI_ARGS + ["-s", "20", "--robust", "5", "--resume", "a.ckpt"], two, timeout=120)

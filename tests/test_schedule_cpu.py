@@ -51,12 +51,52 @@ def _all_keys():
     return keys
 
 
+# the keys behind explicit code: the hr_ctx field each one sets (max_tail_gib is kept in bytes: `20ull << 30`)
+EXPLICIT_FIELDS = {"moments": "moments_on", "sample_counts": "counts_on", "robust_buckets": "robust_k", "guide_bounces": "guide_bounces",
+                   "russian_roulette": "rr_start", "seed_mode": "seed_mode", "nee_cull": "nee_cull", "split_ratio": "split_ratio",
+                   "max_tail_gib": "max_tail_bytes"}
+
+
+def _constant(name):
+    """the value of `static const <type> name = <number>;` somewhere under csrc/"""
+    csrc = os.path.dirname(API)
+    found = [m.group(1) for f in sorted(os.listdir(csrc)) if f.endswith(".h")
+             for m in re.finditer(r"^static const \w+ %s = (\d+);" % name, open(os.path.join(csrc, f)).read(), re.M)]
+    assert len(found) == 1, (name, found)
+    return int(found[0])
+
+
+def _initialiser(ctx, field):
+    """the default of hr_ctx::field as a number: an integer, false / true, -1.0, `20ull << 30` (returned in GiB) or a named constant"""
+    m = re.search(r"\b%s = ([^,;]+)[,;]" % field, ctx)
+    assert m, "no initialiser of hr_ctx::%s" % field
+    text = m.group(1).strip()
+    if text in ("false", "true"):
+        return int(text == "true")
+    if re.fullmatch(r"-?\d+", text):
+        return int(text)
+    if re.fullmatch(r"-?\d+\.\d+", text):
+        return float(text)
+    if re.fullmatch(r"\d+ull << 30", text):
+        return int(text.split("ull")[0])
+    if re.fullmatch(r"[\w:]+", text):
+        return _constant(text.split("::")[-1])
+    raise AssertionError("the initialiser of hr_ctx::%s does not parse: %r" % (field, text))
+
+
 def test_the_parser_sees_the_option_tables():
     t = _tables()
     assert {"counters", "batch", "trace_boost", "precise_shading"} <= set(t["PRODUCT_OPTIONS"])
     assert {"kchunk", "tail_div", "trace_grid", "trace_budget", "wf_trav_wgs", "debug_skip"} <= set(t["DEBUG_OPTIONS"])
     assert {"moments", "sample_counts", "russian_roulette", "seed_mode", "nee_cull"} <= set(_explicit_keys())
     assert t["DEBUG_OPTIONS"]["kchunk"] == ("kchunk", 0.0, 64.0, 0.0) and t["PRODUCT_OPTIONS"]["trace_boost"] == ("trace_boost", -1.0, 4.0, 1.0)
+    ctx = "bool a = false, b = true;\n    double r = -1.0;\n    uint64_t t = 20ull << 30;\n    uint32_t p = hr::lbvh::PLOC_TOP_CLUSTERS;\n    int n = -1;"
+    assert [_initialiser(ctx, f) for f in "abrtn"] == [0, 1, -1.0, 20, -1] and isinstance(_initialiser(ctx, "r"), float)
+    assert _initialiser(ctx, "p") == _constant("PLOC_TOP_CLUSTERS") == 8192
+    with pytest.raises(AssertionError):
+        _initialiser("int x = some(call);", "x")
+    with pytest.raises(AssertionError):
+        _initialiser(ctx, "missing")
 
 
 def test_every_option_is_in_the_table_or_in_the_list_of_the_others():
@@ -67,7 +107,7 @@ def test_every_option_is_in_the_table_or_in_the_list_of_the_others():
     assert not missing, "options neither in schedule_knobs.KNOBS (schedule-only: swept bit for bit) nor in OTHER_OPTIONS (with the test that covers them): %s" % missing
     gone = sorted((set(K.KNOBS) | set(K.OTHER_OPTIONS)) - set(keys))
     assert not gone, "schedule_knobs names options hr_api.hip does not have: %s" % gone
-    for key, (kind, covered_by) in K.OTHER_OPTIONS.items():
+    for key, (kind, covered_by, _, _) in K.OTHER_OPTIONS.items():
         assert kind in ("axis", "image", "variant") and "test" in covered_by, key
         for path in re.findall(r"(?:tests/)?(test_\w+\.py)", covered_by):
             assert os.path.exists(os.path.join(ROOT, "tests", path)), (key, path)
@@ -79,6 +119,17 @@ def test_setters_and_defaults_are_the_librarys():
     keys, t = _all_keys(), _tables()
     src = open(API).read()
     ctx = re.search(r"\nstruct hr_ctx \{\n(.*?)\n\};", src, re.S).group(1)
+    assert set(K.ALL_DEFAULTS) == set(K.SETTERS) == set(keys)
+    explicit = _explicit_keys()
+    for key, default in K.ALL_DEFAULTS.items():
+        assert keys[key] == K.SETTERS[key], key
+        rows = t["PRODUCT_OPTIONS" if K.SETTERS[key] == "set_option" else "DEBUG_OPTIONS"]
+        if key == "rng_window":      # no field: the one value the explicit code accepts
+            assert key in explicit and default == _constant("ISAAC_TAIL"), key
+            continue
+        assert (key in rows) != (key in EXPLICIT_FIELDS), key
+        got = _initialiser(ctx, rows[key][0] if key in rows else EXPLICIT_FIELDS[key])
+        assert got == default and type(got) is type(default), (key, got, default)
     for k in K.KNOBS.values():
         assert keys[k.key] == k.setter, k.key
         row = t["PRODUCT_OPTIONS" if k.setter == "set_option" else "DEBUG_OPTIONS"][k.key]

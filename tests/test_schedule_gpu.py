@@ -9,6 +9,7 @@ import pytest
 
 import light_material_scenes as lm
 import schedule_knobs as K
+from gpu_helpers import bits, error_of, options, renderer
 
 pytestmark = pytest.mark.gpu
 
@@ -34,17 +35,8 @@ def _scene(ha, scenes, name):
     return scenes(name)[0]
 
 
-def _renderer(ha, mode, precise, counters=0):
-    r = ha.Renderer(0)
-    r.set_option("batch", BATCH)
-    r.set_option("precise_shading", precise)
-    r.set_option("counters", counters)
-    r.set_debug_option("trace_mode", mode)
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+def _make(ha, mode, precise, counters=0):
+    return renderer(ha, None, {"batch": BATCH, "precise_shading": precise, "counters": counters}, {"trace_mode": mode})
 
 
 def _render(r):
@@ -56,7 +48,7 @@ def _render(r):
 def _reference(r, what):
     ref = _render(r)
     assert np.isfinite(ref).all() and ref.any(), what
-    assert np.array_equal(_bits(ref), _bits(_render(r))), ("the default render does not repeat", what)
+    assert np.array_equal(bits(ref), bits(_render(r))), ("the default render does not repeat", what)
     return ref
 
 
@@ -73,22 +65,15 @@ def _walk(ha, scenes, r, plan=PLAN):
 @pytest.mark.parametrize("mode", MODES)
 def test_single_knob_sweep(ha, scenes, mode, precise):
     """Every value of every row that acts on the pipeline in force, and the two combined settings: the accumulator of the defaults."""
-    r = _renderer(ha, mode, precise)
-    try:
+    with _make(ha, mode, precise) as r:
         for what, _, full in _walk(ha, scenes, r):
             ref = _reference(r, what)
             assert r.stats()["shading_in_force"] == {K.MEGA: (0, 1), K.SPLIT: (3, 2)}[mode][precise], what
             for label, setting in K.settings(mode, full):
-                try:
-                    K.apply(r, setting)
+                with options(r, *K.split(setting)):
                     got = _render(r)
-                finally:
-                    K.restore(r)
-                differ = int((_bits(got) != _bits(ref)).any(axis=-1).sum())
+                differ = int((bits(got) != bits(ref)).any(axis=-1).sum())
                 assert differ == 0, (what, mode, precise, label, "%d pixels differ" % differ)
-    finally:
-        K.restore(r)
-        r.close()
 
 
 @pytest.mark.parametrize("precise", [0, 1])
@@ -96,28 +81,20 @@ def test_single_knob_sweep(ha, scenes, mode, precise):
 def test_accounting_sweep(ha, scenes, mode, precise):
     """The same settings under option counters: every path of the frame is rendered exactly once (a path rendered twice writes the same record
     twice and stays invisible in the accumulator), the rays traced and the shadow rays culled are the default setting's, three launches."""
-    r = _renderer(ha, mode, precise, counters=1)
-    try:
+    with _make(ha, mode, precise, counters=1) as r:
         for what, (w, h), full in _walk(ha, scenes, r):
             ref = _reference(r, what)
             st0 = r.stats()
             assert st0["paths"] == w * h * 4 * SAMPLINGS and st0["trace_launches"] == LAUNCHES and st0["rays"] >= st0["paths"], (what, st0["paths"], st0["rays"])
             for label, setting in K.settings(mode, full):
-                try:
-                    K.apply(r, setting)
+                with options(r, *K.split(setting)):
                     got = _render(r)
                     st = r.stats()
-                finally:
-                    K.restore(r)
                 tag = (what, mode, precise, label)
                 assert st["paths"] == w * h * 4 * SAMPLINGS, tag + (st["paths"], w * h * 4 * SAMPLINGS)
                 assert st["rays"] == st0["rays"] and st["shadow_culled"] == st0["shadow_culled"], tag + (st["rays"], st0["rays"], st["shadow_culled"], st0["shadow_culled"])
                 assert st["trace_launches"] == LAUNCHES, tag
-                assert np.array_equal(_bits(got), _bits(ref)), tag
-    finally:
-        K.restore(r)
-        r.set_option("counters", 0)
-        r.close()
+                assert np.array_equal(bits(got), bits(ref)), tag
 
 
 def _mask():
@@ -137,8 +114,7 @@ def test_tile_mask_sweep(ha, scenes, mode, precise):
     w, h = RAGGED
     mask = _mask()
     pix = np.kron(mask != 0, np.ones((4, 4), bool))[:h, :w]
-    r = _renderer(ha, mode, precise)
-    try:
+    with _make(ha, mode, precise) as r:
         r.upload_scene(scenes(MESH_SCENE)[0])
         r.set_resolution(w, h)
         r.set_option("sample_counts", 1)
@@ -146,20 +122,14 @@ def test_tile_mask_sweep(ha, scenes, mode, precise):
         r.set_tile_mask(mask)
         assert r.tile_mask()[1] == int(mask.sum())
         ref = _render(r)
-        assert np.array_equal(_bits(ref), _bits(np.where(pix[..., None], full, np.float32(0)))), "the masked default render"
+        assert np.array_equal(bits(ref), bits(np.where(pix[..., None], full, np.float32(0)))), "the masked default render"
         for label, setting in K.settings(mode, True, keys=K.UNIT_KNOBS):
-            try:
-                K.apply(r, setting)
+            with options(r, *K.split(setting)):
                 got = _render(r)
                 counts = r.read_sample_counts()
-            finally:
-                K.restore(r)
-            assert not _bits(got)[~pix].any(), (mode, precise, label, "a pixel outside the active tiles was touched")
-            assert np.array_equal(_bits(got), _bits(ref)), (mode, precise, label)
+            assert not bits(got)[~pix].any(), (mode, precise, label, "a pixel outside the active tiles was touched")
+            assert np.array_equal(bits(got), bits(ref)), (mode, precise, label)
             assert np.array_equal(counts, np.where(pix, SAMPLINGS, 0).astype(np.uint32)), (mode, precise, label)
-    finally:
-        K.restore(r)
-        r.close()
 
 
 @pytest.mark.parametrize("precise", [0, 1])
@@ -167,24 +137,17 @@ def test_tile_mask_sweep(ha, scenes, mode, precise):
 def test_path_log_sweep(ha, scenes, mode, precise):
     """hr_debug_path_log plans its own launch (no tail, no budget): the knobs that still reach it leave the log of sampling 1 — radiance, ray
     counts, events and hashes of every path — word for word the default's."""
-    r = _renderer(ha, mode, precise)
-    try:
+    with _make(ha, mode, precise) as r:
         r.upload_scene(scenes(MESH_SCENE)[0])
         for w, h in (TINY, RAGGED):
             r.set_resolution(w, h)
             ref = r.debug_path_log(1)
             assert np.isfinite(ref[0]).all() and ref[0].any() and (ref[1] > 0).all(), (w, h)
             for label, setting in K.settings(mode, True, keys=K.PATH_LOG_KNOBS, combined=False):
-                try:
-                    K.apply(r, setting)
+                with options(r, *K.split(setting)):
                     got = r.debug_path_log(1)
-                finally:
-                    K.restore(r)
                 for a, b in zip(got, ref):
                     assert np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)), (w, h, mode, precise, label)
-    finally:
-        K.restore(r)
-        r.close()
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -192,42 +155,33 @@ def test_order_and_stickiness(ha, scenes, mode):
     """One context through both combined extremes and back to the defaults: nothing of a setting stays behind — the result is the reference
     again, and the result of a fresh context."""
     sc = scenes(MESH_SCENE)[0]
-    r, fresh = _renderer(ha, mode, 0), None
+    r, fresh = _make(ha, mode, 0), None
     try:
         r.upload_scene(sc)
         for frame in (RAGGED, TINY):
             r.set_resolution(*frame)
             ref = _reference(r, frame)
-            try:
+            with options(r) as opt:
                 for name in ("smallest", "largest", "smallest"):
-                    K.apply(r, K.COMBINED[name])
-                    assert np.array_equal(_bits(_render(r)), _bits(ref)), (frame, mode, name)
-            finally:
-                K.restore(r)
-            assert np.array_equal(_bits(_render(r)), _bits(ref)), (frame, mode, "back at the defaults")
+                    for key, value in K.COMBINED[name].items():
+                        opt.set(key, value)
+                    assert np.array_equal(bits(_render(r)), bits(ref)), (frame, mode, name)
+            assert np.array_equal(bits(_render(r)), bits(ref)), (frame, mode, "back at the defaults")
             if fresh is None:
-                fresh = _renderer(ha, mode, 0)
+                fresh = _make(ha, mode, 0)
                 fresh.upload_scene(sc)
             fresh.set_resolution(*frame)
-            assert np.array_equal(_bits(_render(fresh)), _bits(ref)), (frame, mode, "a fresh context")
+            assert np.array_equal(bits(_render(fresh)), bits(ref)), (frame, mode, "a fresh context")
     finally:
-        K.restore(r)
         r.close()
         if fresh is not None:
             fresh.close()
 
 
-def _code(ha, fn, *a):
-    with pytest.raises(ha.HipError) as e:
-        fn(*a)
-    return e.value.code, str(e.value)
-
-
 def test_roulette_and_precise_shading_refuse_each_other(ha, scenes):
     """The roulette estimator has no f64 instantiation: whichever of russian_roulette and precise_shading 1 is asked for second is refused with
     HR_ERR_UNSUPPORTED where it is asked for, what was in force stays, and the next render gives the bits it gave before the refused call."""
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         r.set_option("batch", BATCH)
         r.upload_scene(scenes(MESH_SCENE)[0])
         r.set_resolution(*RAGGED)
@@ -235,41 +189,36 @@ def test_roulette_and_precise_shading_refuse_each_other(ha, scenes):
         r.set_option("precise_shading", 1)
         before, shading = _render(r), r.stats()["shading_in_force"]
         assert shading == 2 and np.isfinite(before).all() and before.any()
-        code, text = _code(ha, r.set_option, "russian_roulette", 3)
+        code, text = error_of(ha, r.set_option, "russian_roulette", 3)
         assert code == HR_ERR_UNSUPPORTED and "precise_shading" in text
         assert r.stats()["shading_in_force"] == shading
-        assert np.array_equal(_bits(_render(r)), _bits(before))
+        assert np.array_equal(bits(_render(r)), bits(before))
         r.set_option("russian_roulette", 0)                  # off is no conflict
-        assert _code(ha, r.set_option, "russian_roulette", 1)[0] == HR_ERR_INVALID     # (a bad value is a bad value first)
+        assert error_of(ha, r.set_option, "russian_roulette", 1)[0] == HR_ERR_INVALID     # (a bad value is a bad value first)
         # the roulette first
         r.set_option("precise_shading", -1)
         plain = _render(r)
         r.set_option("russian_roulette", 3)
         before = _render(r)
-        assert np.isfinite(before).all() and not np.array_equal(_bits(before), _bits(plain))
-        code, text = _code(ha, r.set_option, "precise_shading", 1)
+        assert np.isfinite(before).all() and not np.array_equal(bits(before), bits(plain))
+        code, text = error_of(ha, r.set_option, "precise_shading", 1)
         assert code == HR_ERR_UNSUPPORTED and "russian_roulette" in text
         assert r.stats()["shading_in_force"] == 0
-        assert np.array_equal(_bits(_render(r)), _bits(before))
+        assert np.array_equal(bits(_render(r)), bits(before))
         r.set_option("precise_shading", 0)                   # the other values are no conflict
         r.set_option("precise_shading", -1)
         # the roulette off again: the image of before, and precise shading is accepted again
         r.set_option("russian_roulette", 0)
-        assert np.array_equal(_bits(_render(r)), _bits(plain))
+        assert np.array_equal(bits(_render(r)), bits(plain))
         r.set_option("precise_shading", 1)
         assert r.stats()["shading_in_force"] == 2
-    finally:
-        r.set_option("russian_roulette", 0)
-        r.set_option("precise_shading", -1)
-        r.close()
 
 
 def test_roulette_starts_the_governor_over(ha, scenes):
     """russian_roulette changes what runs (the estimator lives in the megakernel; automatic precise shading stands back): setting it synchronises
     and starts the governor over, as precise_shading and trace_mode do — what it had decided and the budget it had settled on are gone.  (The
     headline frame: only there do the kernels run beside each other long enough to be judged, test_wave_budget_governor.)"""
-    r = ha.Renderer(0)
-    try:
+    with ha.Renderer(0) as r:
         r.set_option("batch", 4)
         r.upload_scene(scenes(MESH_SCENE)[0])
         r.set_resolution(1920, 1080)
@@ -284,6 +233,3 @@ def test_roulette_starts_the_governor_over(ha, scenes):
         r.synchronize()
         r.set_option("russian_roulette", 0)
         assert r.stats()["governor_decisions"] == 0 and np.isfinite(r.read_accumulator()).all()
-    finally:
-        r.set_option("russian_roulette", 0)
-        r.close()

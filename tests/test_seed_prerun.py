@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_helpers import bits as _bits, options
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hanamaru-renderer_amd", "csrc")
 
@@ -37,10 +39,6 @@ def r(ha):
     rr.close()
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _render(r, args):
     r.clear()
     r.render(*args)
@@ -51,18 +49,15 @@ def _render(r, args):
 
 def _forms(r, args, fused=True):
     """The accumulator of render(*args) from the default, from seed_prerun = 0 and (fused) from seed_mode = 0; options restored."""
-    try:
+    with options(r) as opt:
         out = {"default": _render(r, args)}
-        r.set_debug_option("seed_prerun", 0)
+        opt.set("seed_prerun", 0)
         out["seed_prerun=0"] = _render(r, args)
-        r.set_debug_option("seed_prerun", 1)
+        opt.set("seed_prerun", 1)
         if fused:
-            r.set_debug_option("seed_mode", 0)
+            opt.set("seed_mode", 0)
             out["seed_mode=0"] = _render(r, args)
         return out
-    finally:
-        r.set_debug_option("seed_prerun", 1)
-        r.set_debug_option("seed_mode", 2)
 
 
 def _assert_same(out, what):
@@ -90,11 +85,8 @@ def test_every_workgroup_gets_exactly_one_group(r, scenes):
     sc, _ = scenes("rtcamp6_v3_1")
     r.upload_scene(sc)
     r.set_resolution(64, 20)
-    try:
-        r.set_option("batch", 4)
+    with options(r, {"batch": 4}):
         _assert_same(_forms(r, (1, 5)), "one group per workgroup")
-    finally:
-        r.set_option("batch", 0)
 
 
 @pytest.mark.gpu
@@ -110,21 +102,14 @@ def test_under_a_tile_mask(r, scenes):
     mask = (((xx * 7 + yy * 3) % 5) < 2).astype(np.uint8)     # 40 % of the tiles, the ragged last column and row among them
     mask[ty - 1, tx - 1] = 1
     pix = np.kron(mask != 0, np.ones((4, 4), bool))[:h, :w]
-    try:
-        r.set_option("sample_counts", 1)
-        r.set_option("batch", 1)
+    with options(r, {"sample_counts": 1, "batch": 1}) as opt:      # (the mask goes with the counts)
         r.set_tile_mask(mask)
         out = _forms(r, (1, 6), fused=False)
         _assert_same(out, "tile mask")
         r.set_tile_mask(None)
-        r.set_debug_option("seed_mode", 0)
+        opt.set("seed_mode", 0)
         full = _render(r, (1, 6))
         assert np.array_equal(_bits(out["default"]), _bits(np.where(pix[..., None], full, np.float32(0))))
-    finally:
-        r.set_debug_option("seed_mode", 2)
-        r.set_tile_mask(None)
-        r.set_option("batch", 0)
-        r.set_option("sample_counts", 0)
 
 
 @pytest.mark.gpu
@@ -134,11 +119,7 @@ def test_precise_shading_on_spheres(r, scenes):
     sc, _ = scenes("spheres")
     r.upload_scene(sc)
     r.set_resolution(130, 71)
-    try:
-        r.set_option("precise_shading", 1)
+    with options(r, {"precise_shading": 1}) as opt:
         _assert_same(_forms(r, (1, 7), fused=False), "precise shading, residual twin")
-        r.set_debug_option("draw_residuals", 0)
+        opt.set("draw_residuals", 0)
         _assert_same(_forms(r, (1, 7)), "precise shading, fp32 draws alone")
-    finally:
-        r.set_debug_option("draw_residuals", 1)
-        r.set_option("precise_shading", -1)
