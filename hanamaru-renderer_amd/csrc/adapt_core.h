@@ -33,6 +33,13 @@ HD bool adapt_pixel_active(const RenderParams &rp, uint32_t tile, uint32_t pix, 
     const size_t p = (size_t)py * rp_reg_w(rp) + px;
     return noise_pixel_error(moments + p * 6, (uint64_t)counts[p], floor) > threshold;
 }
+// The same question asked of an error image e_img[reg_h][reg_w] that is already there (hr_select_tiles_robust: e_R of the sample buckets)
+HD bool adapt_pixel_above(const RenderParams &rp, uint32_t tile, uint32_t pix, const double *e_img, double threshold) {
+    uint32_t px, py, sub;
+    tile_lane_pixel(rp, tile, pix * 4u, px, py, sub);
+    if (!rp_in_region(rp, px, py)) return false;
+    return e_img[(size_t)py * rp_reg_w(rp) + px] > threshold;
+}
 // the rule for a whole tile (the device asks one lane per pixel and takes the ballot: select_tiles_kernel, hr_api.hip)
 HD bool adapt_tile_active(const RenderParams &rp, uint32_t tile, const double *moments, const uint32_t *counts, double floor, double threshold) {
     bool any = false;

@@ -10,11 +10,11 @@
 //   wf_kernels.h     the split pipeline (option trace_mode 1): wf_start_kernel, wf_traverse_kernel (the same traversal at <= 64 VGPRs),
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
 //   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
-//                    robust_kernel (robust_core.h)
+//                    robust_kernel and robust_noise_kernel (robust_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
-// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane) are rows of one
+// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane, robust noise image and its trim plane) are rows of one
 // table, PLANES, with one set of routines for their bytes, life cycle, zeroing and host copies; scratch a call needs lives in a CallScratch.
 #include <hip/hip_runtime.h>
 
@@ -135,6 +135,10 @@ struct hr_ctx {
     float *robust = nullptr;
     uint8_t *robust_trim = nullptr;
     bool robust_valid = false;
+    // the robust noise estimate: e_R of every pixel and the trim behind it, as the last estimate or selection left them (allocated
+    // when one is first asked for; every call that reads them has just written them)
+    double *robust_noise_img = nullptr;
+    uint8_t *robust_noise_trim = nullptr;
     // the tile mask (hr_set_tile_mask / hr_select_tiles): which 4x4 tiles of the region hr_render covers.  On the device the compacted list of the
     // active tiles' indices, ascending (RenderParams::tile_list), and the flags it was compacted from; on the host the same flags as bytes.
     bool mask_on = false;
@@ -458,9 +462,10 @@ static int free_mask_buffers(hr_ctx *c) {
 //   WITH_TARGET   allocated by set_target for every target
 //   WITH_OPTION   allocated while the option `on` is on: when it is switched on, and by set_target while it is on; gone when it is switched off
 //   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate; guides: the first
-//                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise; robust, robust_trim: the first hr_robust), freed by set_target —
-//                 noise_img also with the moments it is made of, guides also by hr_upload_scene (they show the scene), robust and robust_trim also
-//                 with the buckets they are made of
+//                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise; robust, robust_trim: the first hr_robust; robust_noise_img,
+//                 robust_noise_trim: the first robust noise estimate), freed by set_target —
+//                 noise_img also with the moments it is made of, guides also by hr_upload_scene (they show the scene), robust, robust_trim
+//                 and the robust noise planes also with the buckets they are made of
 // at_alloc: zeroed when allocated.  at_clear: zeroed by hr_clear.  n: the count that belongs to the plane's contents and is zeroed with them.
 // per: a plane whose components are `comps` times a number the context holds (the sample buckets: 3 per bucket, K buckets).
 enum PlaneLife { WITH_TARGET, WITH_OPTION, ON_FIRST_USE };
@@ -488,8 +493,10 @@ static const Plane DENOISED{PLANE_SLOT(denoised), sizeof(float), 3, ON_FIRST_USE
 static const Plane BUCKETS{PLANE_SLOT(buckets), sizeof(double), 3, WITH_OPTION, true, true, "robust_buckets", &hr_ctx::robust_on, &hr_ctx::buckets_n, &hr_ctx::robust_k};
 static const Plane ROBUST{PLANE_SLOT(robust), sizeof(float), 3, ON_FIRST_USE, false, false};
 static const Plane ROBUST_TRIM{PLANE_SLOT(robust_trim), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
+static const Plane ROBUST_NOISE_IMG{PLANE_SLOT(robust_noise_img), sizeof(double), 1, ON_FIRST_USE, false, false};
+static const Plane ROBUST_NOISE_TRIM{PLANE_SLOT(robust_noise_trim), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
 #undef PLANE_SLOT
-static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM};
+static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM, &ROBUST_NOISE_IMG, &ROBUST_NOISE_TRIM};
 
 static size_t region_pixels(const hr_ctx *c) { return (size_t)c->RW * c->RH; }
 static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps * (p.per ? c->*p.per : 1u); }
@@ -590,6 +597,7 @@ static int create_resources(hr_ctx *c) {
     HIP_TRY(hipMalloc((void **)&c->gov, sizeof(GovDev)));
     { int grc = govern_reset(c); if (grc) return grc; }
     for (const SeedVariant &v : SEED_VARIANTS) HIP_TRY(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
+    for (const RobustNoiseVariant &v : ROBUST_NOISE_VARIANTS) if (v.lds()) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     HIP_TRY(hipFuncSetAttribute((const void *)seed_debug_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 8));
     // The seed kernel owns all 160 KiB of a CU's LDS and runs next to the trace side of the previous batch: a trace-side kernel that
     // uses ANY LDS (the compiler promotes small private arrays to LDS unless told not to, see the Makefile) could not share a CU
@@ -1656,17 +1664,24 @@ static int select_out_buffer(hr_ctx *c) {
     if (!c->d_select_out) HIP_TRY(hipMalloc((void **)&c->d_select_out, 3 * sizeof(uint32_t)));
     return HR_OK;
 }
-static int counts_cover_an_estimate(hr_ctx *c, const char *who) {
+// mm[0], mm[1]: the smallest and the largest count of the region
+static int counts_range(hr_ctx *c, uint32_t mm[2]) {
     const size_t pixels = region_pixels(c);
     int rc = select_out_buffer(c);
     if (rc) return rc;
-    uint32_t mm[2] = {0xffffffffu, 0u};
-    HIP_TRY(hipMemcpyAsync(c->d_select_out + 1, mm, sizeof mm, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));   // (mm is on the stack)
+    mm[0] = 0xffffffffu; mm[1] = 0u;
+    HIP_TRY(hipMemcpyAsync(c->d_select_out + 1, mm, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (mm is the caller's: on a stack)
     hipLaunchKernelGGL(counts_min_kernel, dim3((unsigned)std::min<size_t>((pixels + 255) / 256, 1024)), dim3(256), 0, c->stream, c->counts, pixels, c->d_select_out + 1);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(mm, c->d_select_out + 1, sizeof mm, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(mm, c->d_select_out + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return HR_OK;
+}
+static int counts_cover_an_estimate(hr_ctx *c, const char *who) {
+    uint32_t mm[2];
+    int rc = counts_range(c, mm);
+    if (rc) return rc;
     if (mm[0] < 2) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), a variance needs 2", who, mm[0]);
     // counts and moments that do not cover the same samplings (written apart, or one of them replaced by the host): n would be wrong, silently
     if ((uint64_t)mm[1] > c->moments_n)
@@ -1954,22 +1969,27 @@ int hr_get_tile_mask(hr_ctx *c, uint8_t *mask, uint32_t *active) {
 // The tile rule on the device: 16 lanes per tile (one per pixel), four tiles per wave; the ballot of a tile's lanes is its flag, ANDed with the
 // flag it had (have_prev: a mask is in force — a tile that went inactive stays inactive).  The ascending compaction of the flags into the list
 // is hipcub's DeviceSelect::Flagged over the tile indices: deterministic, two calls give identical lists.
-__global__ __launch_bounds__(256) void select_tiles_kernel(RenderParams rp, const double *__restrict__ moments, const uint32_t *__restrict__ counts, double floor, double threshold,
-                                                           int have_prev, uint32_t *__restrict__ flags) {
-    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
-    const bool hot = tile < tiles && hr::adapt_pixel_active(rp, tile, pix, moments, counts, floor, threshold);
+__device__ __forceinline__ void tile_flag_from_lanes(bool hot, uint32_t tile, uint32_t tiles, uint32_t pix, int have_prev, uint32_t *__restrict__ flags) {
     const unsigned long long m = wave_ballot(hot);
     const bool any = ((m >> (((threadIdx.x & 63u) >> 4) * 16u)) & 0xffffull) != 0ull;
     if (pix == 0u && tile < tiles) flags[tile] = any && (!have_prev || flags[tile] != 0u) ? 1u : 0u;
 }
-int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active) {
-    int rc = plane_ready(c, MOMENTS, "hr_select_tiles");
-    if (rc) return rc;
-    if ((rc = plane_ready(c, COUNTS, "hr_select_tiles"))) return rc;
-    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "hr_select_tiles: floor must be a positive finite radiance");
-    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "hr_select_tiles: threshold must not be negative");
-    if ((rc = hr_synchronize(c))) return rc;   // (also: no kernel is reading the list that is about to be rewritten)
-    if ((rc = counts_cover_an_estimate(c, "hr_select_tiles"))) return rc;
+__global__ __launch_bounds__(256) void select_tiles_kernel(RenderParams rp, const double *__restrict__ moments, const uint32_t *__restrict__ counts, double floor, double threshold,
+                                                           int have_prev, uint32_t *__restrict__ flags) {
+    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
+    const bool hot = tile < tiles && hr::adapt_pixel_active(rp, tile, pix, moments, counts, floor, threshold);
+    tile_flag_from_lanes(hot, tile, tiles, pix, have_prev, flags);
+}
+// the same with the rule of hr_select_tiles_robust: e_R (the image a robust noise estimate has just left) in place of e
+__global__ __launch_bounds__(256) void select_tiles_image_kernel(RenderParams rp, const double *__restrict__ e_img, double threshold, int have_prev, uint32_t *__restrict__ flags) {
+    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
+    const bool hot = tile < tiles && hr::adapt_pixel_above(rp, tile, pix, e_img, threshold);
+    tile_flag_from_lanes(hot, tile, tiles, pix, have_prev, flags);
+}
+// The selection behind hr_select_tiles and hr_select_tiles_robust (`who`), whose checks are done: the flags by the rule (e_img == nullptr: the
+// moments', else that image's), the compaction, the host's mask.
+static int select_tiles_run(hr_ctx *c, const char *who, const double *e_img, double floor, double threshold, uint32_t *active) {
+    int rc;
     RenderParams rp{};
     target_params(c, rp);
     const uint32_t tiles = rp.tiles_x * rp.tiles_y;
@@ -1983,7 +2003,8 @@ int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active)
         HIP_TRY(hipMalloc(&c->select_tmp, std::max<size_t>(need, 16)));
         c->select_tmp_bytes = std::max<size_t>(need, 16);
     }
-    hipLaunchKernelGGL(select_tiles_kernel, dim3((tiles + 15) / 16), dim3(256), 0, c->stream, rp, c->moments, c->counts, floor, threshold, c->mask_on ? 1 : 0, c->d_tile_flags);
+    if (e_img) hipLaunchKernelGGL(select_tiles_image_kernel, dim3((tiles + 15) / 16), dim3(256), 0, c->stream, rp, e_img, threshold, c->mask_on ? 1 : 0, c->d_tile_flags);
+    else hipLaunchKernelGGL(select_tiles_kernel, dim3((tiles + 15) / 16), dim3(256), 0, c->stream, rp, c->moments, c->counts, floor, threshold, c->mask_on ? 1 : 0, c->d_tile_flags);
     HIP_TRY(hipGetLastError());
     size_t bytes = c->select_tmp_bytes;
     HIP_TRY(hipcub::DeviceSelect::Flagged(c->select_tmp, bytes, indices, c->d_tile_flags, c->d_tile_list, c->d_select_out, (int)tiles, c->stream));
@@ -1996,9 +2017,85 @@ int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active)
     for (uint32_t t = 0; t < tiles; t++) c->mask[t] = flags[t] ? 1 : 0;
     mask_totals(c);
     c->mask_on = true;
-    if (selected != c->mask_active) return fail(HR_ERR_DEVICE, "hr_select_tiles: the compaction kept %u tiles, the flags say %u", selected, c->mask_active);
+    if (selected != c->mask_active) return fail(HR_ERR_DEVICE, "%s: the compaction kept %u tiles, the flags say %u", who, selected, c->mask_active);
     if (active) *active = c->mask_active;
     return HR_OK;
+}
+int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active) {
+    int rc = plane_ready(c, MOMENTS, "hr_select_tiles");
+    if (rc) return rc;
+    if ((rc = plane_ready(c, COUNTS, "hr_select_tiles"))) return rc;
+    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "hr_select_tiles: floor must be a positive finite radiance");
+    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "hr_select_tiles: threshold must not be negative");
+    if ((rc = hr_synchronize(c))) return rc;   // (also: no kernel is reading the list that is about to be rewritten)
+    if ((rc = counts_cover_an_estimate(c, "hr_select_tiles"))) return rc;
+    return select_tiles_run(c, "hr_select_tiles", nullptr, floor, threshold, active);
+}
+
+// ---- the robust noise estimate of the sample buckets, and the selection of tiles by it (robust_core.h) ----
+// e_R of every pixel of the region into the context's robust noise planes, and its summary.  Everything that is refused is refused before anything
+// is touched; nothing but those two planes is written.  need_counts: hr_select_tiles_robust (it also needs option sample_counts).
+static int robust_noise_run(hr_ctx *c, const char *who, bool need_counts, double floor, double threshold, hr_noise *est) {
+    int rc = plane_ready(c, BUCKETS, who);
+    if (rc) return rc;
+    if (need_counts && (rc = plane_ready(c, COUNTS, who))) return rc;
+    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "%s: floor must be a positive finite radiance", who);
+    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
+    const uint32_t K = c->robust_k;
+    if (!c->counts && c->buckets_n < K) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the %u buckets, the spread of the bucket means needs one in each", who, (unsigned long long)c->buckets_n, K);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = hr_synchronize(c))) return rc;   // (for the selection also: no kernel is reading the list that is about to be rewritten)
+    if (c->counts) {
+        uint32_t mm[2];
+        if ((rc = counts_range(c, mm))) return rc;
+        if (mm[0] < K) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), the spread of %u bucket means needs one in each", who, mm[0], K);
+        if ((uint64_t)mm[1] > c->buckets_n)
+            return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the buckets cover %llu (the counts and the buckets must cover the same samplings)", who, mm[1], (unsigned long long)c->buckets_n);
+    }
+    const RobustNoiseVariant *v = select_robust_noise_kernel(K, ROBUST_NOISE_STAGED);
+    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_noise_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
+    const size_t pixels = region_pixels(c);
+    if (!c->robust_noise_img && (rc = plane_alloc(c, ROBUST_NOISE_IMG))) return rc;
+    if (!c->robust_noise_trim && (rc = plane_alloc(c, ROBUST_NOISE_TRIM))) return rc;
+    CallScratch scratch;
+    double *d = nullptr;
+    std::vector<double> h(ROBUST_NOISE_BLOCKS * 3);
+    HIP_TRY(scratch.alloc((void **)&d, h.size() * sizeof(double)));
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    hipLaunchKernelGGL(v->fn, dim3(ROBUST_NOISE_BLOCKS), dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, pixels, floor, threshold,
+                       c->robust_noise_img, c->robust_noise_trim, d);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
+    if (est) {
+        double sum = 0.0, mx = 0.0, above = 0.0;
+        for (unsigned b = 0; b < ROBUST_NOISE_BLOCKS; b++) { sum += h[b * 3]; mx = h[b * 3 + 1] > mx ? h[b * 3 + 1] : mx; above += h[b * 3 + 2]; }
+        est->samplings = c->buckets_n;
+        est->pixels = (uint64_t)pixels;
+        est->pixels_above = (uint64_t)above;
+        est->mean_error = sum / (double)pixels;
+        est->max_error = mx;
+    }
+    return drain_events(c);
+}
+int hr_robust_noise_estimate(hr_ctx *c, double floor, double threshold, hr_noise *out) {
+    if (c && !out) return fail(HR_ERR_INVALID, "hr_robust_noise_estimate: null argument");
+    return robust_noise_run(c, "hr_robust_noise_estimate", false, floor, threshold, out);
+}
+int hr_read_robust_noise_image(hr_ctx *c, double floor, double *host) {
+    if (c && !host) return fail(HR_ERR_INVALID, "hr_read_robust_noise_image: null argument");
+    int rc = robust_noise_run(c, "hr_read_robust_noise_image", false, floor, 0.0, nullptr);
+    return rc ? rc : plane_read(c, ROBUST_NOISE_IMG, c->robust_noise_img, host);
+}
+int hr_read_robust_noise_trim(hr_ctx *c, double floor, uint8_t *host) {
+    if (c && !host) return fail(HR_ERR_INVALID, "hr_read_robust_noise_trim: null argument");
+    int rc = robust_noise_run(c, "hr_read_robust_noise_trim", false, floor, 0.0, nullptr);
+    return rc ? rc : plane_read(c, ROBUST_NOISE_TRIM, c->robust_noise_trim, host);
+}
+int hr_select_tiles_robust(hr_ctx *c, double floor, double threshold, uint32_t *active) {
+    int rc = robust_noise_run(c, "hr_select_tiles_robust", true, floor, threshold, nullptr);
+    return rc ? rc : select_tiles_run(c, "hr_select_tiles_robust", c->robust_noise_img, floor, threshold, active);
 }
 
 int hr_get_stats(hr_ctx *c, hr_stats *out) {
@@ -2133,7 +2230,7 @@ static int set_robust_buckets(hr_ctx *c, double value) {
     invalidate_robust(c);
     c->robust_on = false;
     c->robust_k = 0;
-    if ((rc = plane_free(c, BUCKETS)) || (rc = plane_free(c, ROBUST)) || (rc = plane_free(c, ROBUST_TRIM))) return rc;
+    if ((rc = plane_free(c, BUCKETS)) || (rc = plane_free(c, ROBUST)) || (rc = plane_free(c, ROBUST_TRIM)) || (rc = plane_free(c, ROBUST_NOISE_IMG)) || (rc = plane_free(c, ROBUST_NOISE_TRIM))) return rc;
     if (value == 0) return HR_OK;
     c->robust_k = (uint32_t)value;
     if ((rc = plane_alloc(c, BUCKETS))) { (void)plane_free(c, BUCKETS); c->robust_k = 0; return rc; }

@@ -195,3 +195,25 @@ static const BucketVariant BUCKET_VARIANTS[] = {HR_VARIANT(bucket_kernel, false,
 static BucketFn select_bucket_kernel(bool counts, bool list) {
     return fn_of(find_row(BUCKET_VARIANTS, [&](const BucketVariant &r) { return r.cnts == counts && r.list == list; }));
 }
+
+// ---- robust_noise_kernel<K, STAGE> (post_kernels.h): the robust noise estimate of the sample buckets, one row per K the option robust_buckets takes ----
+// stage: the workgroup's span goes through LDS (what the library runs) — its rows want `lds` bytes of dynamic LDS (create_resources raises the limit:
+// K = 11 and more is past 64 KiB); the per-lane form wants none and is kept for the comparison of DESIGN.md §4.11: a library built with
+// -DHR_ROBUST_NOISE_PER_LANE (`make EXPFLAGS=-DHR_ROBUST_NOISE_PER_LANE`) runs it instead — the same bits, another time.
+typedef void (*RobustNoiseFn)(const double *, const uint32_t *, unsigned long long, size_t, double, double, double *, uint8_t *, double *);
+struct RobustNoiseVariant { uint32_t k; bool stage; RobustNoiseFn fn; uint32_t lds() const { return stage ? 256u * 3u * k * (uint32_t)sizeof(double) : 0u; } };
+static const RobustNoiseVariant ROBUST_NOISE_VARIANTS[] = {
+    HR_VARIANT(robust_noise_kernel, 3, true),   HR_VARIANT(robust_noise_kernel, 5, true),   HR_VARIANT(robust_noise_kernel, 7, true),  HR_VARIANT(robust_noise_kernel, 9, true),
+    HR_VARIANT(robust_noise_kernel, 11, true),  HR_VARIANT(robust_noise_kernel, 13, true),  HR_VARIANT(robust_noise_kernel, 15, true),
+    HR_VARIANT(robust_noise_kernel, 3, false),  HR_VARIANT(robust_noise_kernel, 5, false),  HR_VARIANT(robust_noise_kernel, 7, false), HR_VARIANT(robust_noise_kernel, 9, false),
+    HR_VARIANT(robust_noise_kernel, 11, false), HR_VARIANT(robust_noise_kernel, 13, false), HR_VARIANT(robust_noise_kernel, 15, false),
+};
+#if defined(HR_ROBUST_NOISE_PER_LANE)
+static const bool ROBUST_NOISE_STAGED = false;
+#else
+static const bool ROBUST_NOISE_STAGED = true;
+#endif
+// K as option robust_buckets has it; stage: ROBUST_NOISE_STAGED
+static const RobustNoiseVariant *select_robust_noise_kernel(uint32_t k, bool stage) {
+    return find_row(ROBUST_NOISE_VARIANTS, [&](const RobustNoiseVariant &r) { return r.k == k && r.stage == stage; });
+}

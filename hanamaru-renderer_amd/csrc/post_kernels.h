@@ -49,3 +49,72 @@ __global__ __launch_bounds__(256) void robust_kernel(const double *__restrict__ 
     if (i >= pixels) return;
     robust_pixel(buckets + (size_t)i * K * 3, K, counts ? (uint64_t)counts[i] : (uint64_t)n_all, out + (size_t)i * 3, trim + i);
 }
+
+// The robust noise estimate (robust_pixel_error_k, robust_core.h): e_R of every pixel into `img`, the trim it took into `trim`
+// (or nullptr), and the summary out[block] = {sum of e_R, max of e_R, pixels with e_R > threshold}, reduced in a fixed order — a fixed grid,
+// every thread its strided pixels in order, lanes and waves in order, the host adds the blocks' partial sums in index order (the scheme of
+// noise_kernel, hr_api.hip): two calls return identical bits.  The kernel carries no arithmetic of its own.
+// K is a template parameter: the pixel's K keys live in registers, no array is indexed at run time, nothing goes to scratch (robust_kernel above
+// pays 72 VGPRs and 368 B of scratch per lane for its run-time K).  counts == nullptr: every pixel has n_all samplings.
+// STAGE: how the lanes come by their pixel's 3 K doubles — the arithmetic, and so every bit, is the same.
+//   true   a workgroup's 256 pixels are one contiguous span of 256 x 24 K bytes: its lanes load it as consecutive doubles (a wave's load is 512
+//          contiguous bytes), park it in 256 x 24 K bytes of dynamic LDS, and every lane reads its own pixel from there (stride 3 K doubles, 3 K odd:
+//          no bank conflict)
+//   false  every lane loads its own 24 K contiguous bytes from global memory: a wave's load touches 64 lines 24 K bytes apart
+// The loop runs the same number of times for every thread of a workgroup (the barriers), a lane past the last pixel computes nothing.
+constexpr unsigned ROBUST_NOISE_BLOCKS = 1024;
+template <uint32_t K>
+constexpr uint32_t robust_noise_lds_bytes() { return 256u * 3u * K * (uint32_t)sizeof(double); }
+template <uint32_t K, bool STAGE>
+__global__ __launch_bounds__(256) void robust_noise_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all, size_t pixels,
+                                                           double floor, double threshold, double *__restrict__ img, uint8_t *__restrict__ trim, double *__restrict__ out) {
+    extern __shared__ double robust_noise_stage[];
+    constexpr uint32_t D = 3u * K;   // doubles per pixel
+    double sum = 0.0, mx = 0.0, above = 0.0;
+    for (size_t base = (size_t)blockIdx.x * 256u; base < pixels; base += (size_t)gridDim.x * 256u) {
+        const size_t i = base + threadIdx.x;
+        const double *B = buckets + i * D;
+        if (STAGE) {
+            const double *span = buckets + base * D;
+            double v[D];
+            if (base + 256u <= pixels) {
+#pragma unroll
+                for (uint32_t j = 0; j < D; j++) v[j] = span[j * 256u + threadIdx.x];
+            } else {
+                const size_t have = (pixels - base) * D;   // doubles of the span that exist
+#pragma unroll
+                for (uint32_t j = 0; j < D; j++) v[j] = j * 256u + threadIdx.x < have ? span[j * 256u + threadIdx.x] : 0.0;
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < D; j++) robust_noise_stage[j * 256u + threadIdx.x] = v[j];
+            __syncthreads();
+            B = robust_noise_stage + threadIdx.x * D;
+        }
+        if (i < pixels) {
+            double e;
+            uint8_t t;
+            robust_pixel_error_k<K>(B, counts ? (uint64_t)counts[i] : (uint64_t)n_all, floor, &e, &t);
+            img[i] = e;
+            if (trim) trim[i] = t;
+            sum += e;
+            mx = e > mx ? e : mx;
+            above += e > threshold ? 1.0 : 0.0;
+        }
+        if (STAGE) __syncthreads();   // the next round overwrites the span
+    }
+    __shared__ double part[4][3];
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_down(sum, off);
+        const double o = __shfl_down(mx, off);
+        mx = o > mx ? o : mx;
+        above += __shfl_down(above, off);
+    }
+    if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][0] = sum; part[threadIdx.x >> 6][1] = mx; part[threadIdx.x >> 6][2] = above; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *o = out + (size_t)blockIdx.x * 3;
+        o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
+        o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
+        o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
+    }
+}

@@ -14,7 +14,9 @@
 // hr_resolve_denoised; the guide planes as images of their own, hr_render_guides + hr_read_guides), --guide-bounces K (option "guide_bounces":
 // the guide rays follow mirrors and glass for up to K bounces to the first rough hit; 0, the default, is the first hit),
 // --robust K / --robust-image FILE (option "robust_buckets": every image is the firefly-robust resolve of K sample buckets per pixel, hr_robust +
-// hr_resolve_robust; the buckets ride in the checkpoint behind the other trailers).
+// hr_resolve_robust; the buckets ride in the checkpoint behind the other trailers),
+// --robust-noise (with --robust: --noise-target, --adaptive and --noise-image judge the robust image by the spread of its bucket means,
+// hr_robust_noise_estimate / hr_select_tiles_robust / hr_read_robust_noise_image).
 // The file is in main's order: Options and parse_options (everything that can be refused before a device is opened), then Run, whose members
 // are main's steps.  The checkpoint's format is host/checkpoint.h's; what a render demands of a file is said in Run::resume.
 #include <algorithm>
@@ -115,7 +117,11 @@ static void usage(const char *prog) {
            "                        --noise-target and --adaptive (every pixel's own sampling count).  --checkpoint appends the buckets, --resume\n"
            "                        restores them and refuses a file without them or with another K.  One device only; not with --denoise or --debug.\n"
            "        --robust-image FILE.png\n"
-           "                        write an 8-bit grey map of trim / ((K - 1) / 2), the buckets dropped at either end (needs --robust)\n",
+           "                        write an 8-bit grey map of trim / ((K - 1) / 2), the buckets dropped at either end (needs --robust)\n"
+           "        --robust-noise  judge the noise of the image --robust shows, not of the plain mean: --noise-target asks hr_robust_noise_estimate,\n"
+           "                        --adaptive asks hr_select_tiles_robust (after --resume too) and --noise-image maps min(1, e_R / E), e_R the\n"
+           "                        winsorized standard error of the trimmed mean of the K bucket means over the channel sum + 3 F.  No estimate\n"
+           "                        before every pixel has K samplings.  Needs --robust; without this flag everything is judged as before.\n",
            prog);
 }
 
@@ -141,6 +147,7 @@ struct Options {
     long long guide_bounces = -1;    // -1: not given (the library's default, 0)
     long long robust_k = 0;          // --robust K: option "robust_buckets" (0: off)
     std::string robust_png;
+    bool robust_noise = false;       // --robust-noise: the noise questions are asked of the buckets (e_R), not of the moments
     // what the flags add up to:
     bool counts = false, moments = false;   // hr_set_option "sample_counts", "moments"
     double noise_e = 0.05;                  // the threshold of "above" and of the grey map
@@ -243,6 +250,7 @@ static int parse_options(int argc, char **argv, Options &o) {
         } else if (a == "--robust") {
             if (!whole("--robust", val("robust"), 3, 15, 2, "an odd number of buckets in 3 .. 15", &o.robust_k)) return 1;
         } else if (a == "--robust-image") o.robust_png = val("robust-image");
+        else if (a == "--robust-noise") o.robust_noise = true;
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (o.batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -263,6 +271,7 @@ static int parse_options(int argc, char **argv, Options &o) {
         if (o.debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
     }
     if (!o.robust_png.empty() && !o.robust_k) { fprintf(stderr, "--robust-image needs --robust.\n"); return 1; }
+    if (o.robust_noise && !o.robust_k) { fprintf(stderr, "--robust-noise needs --robust (it judges the noise by the sample buckets).\n"); return 1; }
     if (o.robust_k) {
         if (!one_device(o, "--robust renders on one device: buckets of several devices add up only when each rendered a multiple of K samplings, and this program's device loop does not see to that.")) return 1;
         if (o.denoise) { fprintf(stderr, "--robust cannot be combined with --denoise (the filter reads the raw moments, not the robust radiance: two final images).\n"); return 1; }
@@ -433,6 +442,7 @@ int Run::resolve(uint32_t s, uint8_t *out) {
 // additive, so the host adds them in rank order (as sum_acc does for accumulators without RCCL), device 0 estimates the total and gets
 // its own moments back.  tot_out / n_out: the summed moments and their count as well (for the checkpoint).
 // Returns 0, 1 = error, 2 = fewer than two samplings behind the moments (no variance yet).
+// --robust-noise (one device): the same questions asked of the sample buckets, e_R in place of e; 2 = a pixel with fewer than K samplings.
 int Run::noise_query(hr_noise *est, double *img, std::vector<double> *tot_out, uint64_t *n_out) {
     uint64_t n_own = 0, n_tot = 0;
     const size_t len = (size_t)o.out_w * o.out_h * 6;
@@ -453,8 +463,9 @@ int Run::noise_query(hr_noise *est, double *img, std::vector<double> *tot_out, u
         if (hr_write_moments(ctx, mom_tot.data(), n_tot) != 0) return 1;
     }
     memset(est, 0, sizeof *est);
-    int rc = hr_noise_estimate(ctx, o.noise_floor, o.noise_e, est);   // (HR_ERR_INVALID: n < 2 — floor and threshold were checked with the flags)
-    if (rc == 0 && img) rc = hr_read_noise_image(ctx, o.noise_floor, img);
+    // (HR_ERR_INVALID: n < 2, with --robust-noise n < K — floor and threshold were checked with the flags)
+    int rc = o.robust_noise ? hr_robust_noise_estimate(ctx, o.noise_floor, o.noise_e, est) : hr_noise_estimate(ctx, o.noise_floor, o.noise_e, est);
+    if (rc == 0 && img) rc = o.robust_noise ? hr_read_robust_noise_image(ctx, o.noise_floor, img) : hr_read_noise_image(ctx, o.noise_floor, img);
     if (ndev > 1 && hr_write_moments(ctx, mom_own.data(), n_own) != 0) return 1;
     if (tot_out) *tot_out = mom_tot;
     if (n_out) *n_out = n_tot;
@@ -681,7 +692,8 @@ int Run::render() {
         for (uint32_t n; (n = may_issue()) != 0;) if (issue(n)) return 1;
         if (q.empty() && have_adaptive && next_s <= sampling && (uint64_t)next_s > check_at) {   // the tiles are chosen again, and nothing is in flight
             uint32_t active = all_tiles;
-            const int rc = hr_select_tiles(ctx, noise_floor, adaptive_e, &active);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings — no estimate yet, go on as before)
+            // (HR_ERR_INVALID: a pixel with fewer than 2 samplings, with --robust-noise fewer than K — no estimate yet, go on as before)
+            const int rc = o.robust_noise ? hr_select_tiles_robust(ctx, noise_floor, adaptive_e, &active) : hr_select_tiles(ctx, noise_floor, adaptive_e, &active);
             if (rc != 0 && rc != HR_ERR_INVALID) { fprintf(stderr, "hr_select_tiles: %s\n", hr_last_error()); return 1; }
             if (rc == 0) {
                 printf("adaptive: samplings=%u active=%u tiles=%u\n", next_s - 1, active, all_tiles);

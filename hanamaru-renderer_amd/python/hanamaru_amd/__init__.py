@@ -211,6 +211,10 @@ def hip_lib():
         L.hr_read_robust.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_read_robust_trim.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_resolve_robust.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_robust_noise_estimate.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(Noise)]
+        L.hr_read_robust_noise_image.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.hr_read_robust_noise_trim.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.hr_select_tiles_robust.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint32)]
         _hip = L
     return _hip
 
@@ -610,6 +614,27 @@ class Renderer:
     def resolve_robust(self):
         """hr_resolve_robust: resolve() of the robust radiance."""
         return self._read_plane(self.L.hr_resolve_robust, "rgb8")
+
+    # ---- the robust noise estimate of the buckets, and the selection of tiles by it (include/hanamaru_hip.h)
+    def robust_noise_estimate(self, floor=0.01, threshold=0.05):
+        """hr_robust_noise_estimate: {samplings, pixels, pixels_above, mean_error, max_error} of e_R, the winsorized relative error of R's channel sum."""
+        n = Noise()
+        self._check(self.L.hr_robust_noise_estimate(self._h, float(floor), float(threshold), C.byref(n)))
+        return {k: getattr(n, k) for k, _ in n._fields_}
+
+    def robust_noise_image(self, floor=0.01):
+        """hr_read_robust_noise_image: e_R of every pixel, (h, w) float64."""
+        return self._read_plane(self.L.hr_read_robust_noise_image, "noise", float(floor))
+
+    def robust_noise_trim(self, floor=0.01):
+        """hr_read_robust_noise_trim: (h, w) uint8, the trim the estimate took (read_robust_trim()'s values without a robust())."""
+        return self._read_plane(self.L.hr_read_robust_noise_trim, "robust_trim", float(floor))
+
+    def select_tiles_robust(self, floor=0.01, threshold=0.05):
+        """hr_select_tiles_robust: select_tiles() with e_R in place of e; returns the active tiles left."""
+        n = C.c_uint32()
+        self._check(self.L.hr_select_tiles_robust(self._h, float(floor), float(threshold), C.byref(n)))
+        return int(n.value)
 
     def debug_draws(self, sampling, first_path, num_paths, window):
         out = np.empty((num_paths, window), dtype=np.uint64)

@@ -443,13 +443,38 @@ int hr_resolve_denoised(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 
  *     hr_bind_accumulator, switching "robust_buckets", "moments" or "sample_counts", hr_set_resolution, hr_set_region.  hr_read_robust,
  *     hr_read_robust_trim and hr_resolve_robust return HR_ERR_INVALID without a valid R; all six functions return HR_ERR_INVALID with the option
  *     off; in both cases R stays as it was.  hr_resolve_robust is renderer.rs:64-90 on R with the scale 1.0f, as hr_resolve_denoised is on D.
- *   - The noise estimate and the denoiser still read the raw moments.  All of these synchronise. */
+ *   - hr_noise_estimate, hr_select_tiles and the denoiser still read the raw moments; the robust noise estimate below reads the buckets.  All of
+ *     these synchronise. */
 int hr_read_buckets(hr_ctx *ctx, double *host /* w*h*K*3 */, uint64_t *samplings /* may be NULL */);
 int hr_write_buckets(hr_ctx *ctx, const double *host, uint64_t samplings);   /* resume, tile stitching */
 int hr_robust(hr_ctx *ctx);
 int hr_read_robust(hr_ctx *ctx, float *host /* w*h*3 radiance */);
 int hr_read_robust_trim(hr_ctx *ctx, uint8_t *host /* w*h: buckets dropped at either end */);
 int hr_resolve_robust(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on R with scale 1.0f */
+/* The robust noise estimate: how converged R is, from the spread of the pixel's own bucket means — not from the raw moments, which
+ * the few paths that R leaves out dominate.  e_R of a pixel is the Tukey-McLaughlin (winsorized) standard error of the trim-trimmed mean of its K
+ * bucket means, taken on the channel sum y, over that mean plus 3 floor.  The definition is robust_pixel_error in csrc/robust_core.h, to the bit but
+ * for the device's f64 sqrt (within 4 ulp; bit-identical where the spread is 0): with n_b, y_b, their ascending order and trim exactly as above,
+ *         kept = K - 2 trim;   Ry = (y_(trim+1) + .. + y_(K-trim)) / kept;   w_i = y_(i) clamped to [y_(trim+1), y_(K-trim)] by RANK, i = 1 .. K;
+ *         wbar = (sum_i w_i) / K;   ss = sum_i (w_i - wbar)^2;   se = sqrt(ss / (K - 1) / K) K / kept;   den = Ry + 3 floor;
+ *         e_R = den > 0 ? se / den : 0.
+ *   - It is an error of the channel SUM, not hr_noise_estimate's se_r + se_g + se_b; with trim = (K - 1) / 2 (the median bucket) se is 0 by
+ *     construction; and it is blind to R's dark bias, which is no noise.
+ *   - All of them need "robust_buckets" on ("moments" is not needed) and return HR_ERR_INVALID with it off, for floor <= 0 or not finite, for
+ *     threshold < 0, while any pixel of the region has fewer than K samplings (its own count with "sample_counts" on, else the count behind the
+ *     buckets), and with "sample_counts" on when a pixel's count exceeds the samplings behind the buckets.  What is refused touches nothing.
+ *   - hr_robust_noise_estimate: hr_noise of e_R (samplings: the count behind the buckets), reduced on the device in a fixed order — two calls
+ *     return identical bits.  hr_read_robust_noise_image: e_R of every pixel.  hr_read_robust_noise_trim: the trim that the estimate took, pixel by
+ *     pixel — hr_read_robust_trim's values without an hr_robust.
+ *   - hr_select_tiles_robust (needs "sample_counts" as well) is hr_select_tiles with e_R in place of e: a tile stays active iff e_R > threshold
+ *     for at least one of its in-region pixels — exactly the value hr_read_robust_noise_image returns — ANDed with the mask in force, compacted as
+ *     there.
+ *   - They work on the region, synchronise, put their time into hr_stats.post_kernel_ms, and touch neither R, the buckets, the moments nor the
+ *     counts (R stays valid). */
+int hr_robust_noise_estimate(hr_ctx *ctx, double floor, double threshold, hr_noise *out);
+int hr_read_robust_noise_image(hr_ctx *ctx, double floor, double *host /* w*h */);
+int hr_read_robust_noise_trim(hr_ctx *ctx, double floor, uint8_t *host /* w*h */);
+int hr_select_tiles_robust(hr_ctx *ctx, double floor, double threshold, uint32_t *active /* may be NULL */);
 
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):

@@ -103,6 +103,12 @@ extern "C" {
     pub fn hr_read_robust(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 radiance */) -> c_int;
     pub fn hr_read_robust_trim(ctx: *mut HrCtx, host: *mut u8 /* w*h */) -> c_int;
     pub fn hr_resolve_robust(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
+    // the robust noise estimate e_R of the buckets (the winsorized relative error of R's channel sum) and the selection of tiles by it;
+    // HR_ERR_INVALID while a pixel has fewer than K samplings (hr_select_tiles_robust also needs option "sample_counts")
+    pub fn hr_robust_noise_estimate(ctx: *mut HrCtx, floor: f64, threshold: f64, out: *mut HrNoise) -> c_int;
+    pub fn hr_read_robust_noise_image(ctx: *mut HrCtx, floor: f64, host: *mut f64 /* w*h */) -> c_int;
+    pub fn hr_read_robust_noise_trim(ctx: *mut HrCtx, floor: f64, host: *mut u8 /* w*h */) -> c_int;
+    pub fn hr_select_tiles_robust(ctx: *mut HrCtx, floor: f64, threshold: f64, active: *mut u32) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----
