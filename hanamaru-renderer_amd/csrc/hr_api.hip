@@ -10,7 +10,7 @@
 //   wf_kernels.h     the split pipeline (option trace_mode 1): wf_start_kernel, wf_traverse_kernel (the same traversal at <= 64 VGPRs),
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
 //   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
-//                    robust_kernel and robust_noise_kernel (robust_core.h)
+//                    robust_kernel, robust_denoise_init_kernel and robust_noise_kernel (robust_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
@@ -124,6 +124,7 @@ struct hr_ctx {
     // by the host — and the denoised radiance D of the last hr_denoise, valid until anything it was made of changes (invalidate_denoised)
     float *guides = nullptr, *denoised = nullptr;
     bool guides_valid = false, denoised_valid = false;
+    bool denoised_by_robust = false;   // D was made by hr_denoise_robust: switching robust_buckets invalidates it as well
     uint32_t guide_bounces = 0;   // option "guide_bounces": mirrors and glass the guide rays follow to the first non-delta hit (0: the first hit's planes)
     // option "robust_buckets" = K: per pixel K x 3 sums of the per-sampling values, sampling j of a pixel in bucket j mod K
     // (bucket_kernel), the samplings behind them, and the robust radiance R with its trim plane of the last hr_robust, valid until anything it was
@@ -598,6 +599,8 @@ static int create_resources(hr_ctx *c) {
     { int grc = govern_reset(c); if (grc) return grc; }
     for (const SeedVariant &v : SEED_VARIANTS) HIP_TRY(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEED_LDS_BYTES));
     for (const RobustNoiseVariant &v : ROBUST_NOISE_VARIANTS) if (v.lds()) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
+    for (const RobustVariant &v : ROBUST_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
+    for (const RobustDenoiseInitVariant &v : ROBUST_DENOISE_INIT_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     HIP_TRY(hipFuncSetAttribute((const void *)seed_debug_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 8));
     // The seed kernel owns all 160 KiB of a CU's LDS and runs next to the trace side of the previous batch: a trace-side kernel that
     // uses ANY LDS (the compiler promotes small private arrays to LDS unless told not to, see the Makefile) could not share a CU
@@ -1856,6 +1859,7 @@ int hr_denoise(hr_ctx *c, const hr_denoise_params *params) {
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
     c->denoised_valid = true;
+    c->denoised_by_robust = false;
     return drain_events(c);
 }
 int hr_read_denoised(hr_ctx *c, float *host) {
@@ -1888,13 +1892,15 @@ int hr_robust(hr_ctx *c) {
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = hr_synchronize(c))) return rc;
+    const RobustVariant *v = select_robust_kernel(c->robust_k);
+    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_kernel instantiation for %u buckets (kernel_variants.h)", who, c->robust_k);
     if (!c->robust && (rc = plane_alloc(c, ROBUST))) return rc;
     if (!c->robust_trim && (rc = plane_alloc(c, ROBUST_TRIM))) return rc;
     invalidate_robust(c);
-    const uint32_t pixels = (uint32_t)region_pixels(c);
+    const size_t pixels = region_pixels(c);
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
-    hipLaunchKernelGGL(robust_kernel, dim3((pixels + 255) / 256), dim3(256), 0, c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->robust_k, c->robust, c->robust_trim, pixels);
+    hipLaunchKernelGGL(v->fn, dim3((unsigned)((pixels + 255) / 256)), dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->robust, c->robust_trim, pixels);
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
     c->robust_valid = true;
@@ -2098,6 +2104,56 @@ int hr_select_tiles_robust(hr_ctx *c, double floor, double threshold, uint32_t *
     return rc ? rc : select_tiles_run(c, "hr_select_tiles_robust", c->robust_noise_img, floor, threshold, active);
 }
 
+// ---- the robust denoiser (robust_core.h, denoise_core.h): hr_denoise's levels on {C, V} of the sample buckets ----
+// Everything that is refused is refused before anything is touched: D of an earlier call stays.  Nothing but D (and, without guide planes, the
+// guides) is written: R, the buckets, the accumulator, the moments and the counts are read only or not at all.
+int hr_denoise_robust(hr_ctx *c, const hr_denoise_params *params) {
+    static const char *const who = "hr_denoise_robust";
+    int rc = plane_ready(c, BUCKETS, who);
+    if (rc) return rc;
+    hr_denoise_params p;
+    if (params) p = *params;
+    else (void)hr_denoise_default_params(&p);
+    if (p.levels > DENOISE_MAX_LEVELS) return fail(HR_ERR_INVALID, "%s: levels must be in [0,%u]", who, DENOISE_MAX_LEVELS);
+    if (p.demodulate > 1u) return fail(HR_ERR_INVALID, "%s: demodulate must be 0 or 1", who);
+    for (double s : {p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth})
+        if (!(s > 0.0) || !(s < INFINITY)) return fail(HR_ERR_INVALID, "%s: every sigma must be positive and finite", who);
+    const uint32_t K = c->robust_k;
+    if (!c->counts && c->buckets_n < K) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the %u buckets, the spread of the bucket means needs one in each", who, (unsigned long long)c->buckets_n, K);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = hr_synchronize(c))) return rc;
+    if (c->counts) {
+        uint32_t mm[2];
+        if ((rc = counts_range(c, mm))) return rc;
+        if (mm[0] < K) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), the spread of %u bucket means needs one in each", who, mm[0], K);
+        if ((uint64_t)mm[1] > c->buckets_n)
+            return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the buckets cover %llu (the counts and the buckets must cover the same samplings)", who, mm[1], (unsigned long long)c->buckets_n);
+    }
+    const RobustDenoiseInitVariant *v = select_robust_denoise_init_kernel(K);
+    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_denoise_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
+    if (!c->guides_valid && (rc = hr_render_guides(c))) return rc;
+    const size_t pixels = region_pixels(c);
+    if (!c->denoised && (rc = plane_alloc(c, DENOISED))) return rc;
+    CallScratch scratch;
+    double *cv[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++) HIP_TRY_AS(who, scratch.alloc((void **)&cv[k], pixels * 6 * sizeof(double)));
+    invalidate_denoised(c);
+    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
+    const int demodulate = p.demodulate && p.levels ? 1 : 0;   // without a level there is nothing to filter: D = (float)C = R
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
+    hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->guides, cv[0], pixels, demodulate);
+    for (uint32_t l = 0; l < p.levels; l++)
+        hipLaunchKernelGGL(atrous_kernel, tiles2d, dim3(32, 8), 0, c->stream, cv[l & 1u], c->guides, cv[(l + 1u) & 1u], c->RW, c->RH, 1u << l, sg);
+    hipLaunchKernelGGL(denoise_final_kernel, flat, dim3(256), 0, c->stream, cv[p.levels & 1u], c->guides, c->denoised, (uint32_t)pixels, demodulate);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
+    c->denoised_valid = true;
+    c->denoised_by_robust = true;
+    return drain_events(c);
+}
+
 int hr_get_stats(hr_ctx *c, hr_stats *out) {
     if (!c || !out) return fail(HR_ERR_INVALID, "hr_get_stats: null argument");
     HIP_TRY(hipSetDevice(c->device));
@@ -2225,6 +2281,7 @@ static int set_robust_buckets(hr_ctx *c, double value) {
     if (value != 0 && !robust_valid_k(value)) return fail(HR_ERR_INVALID, "robust_buckets must be 0 (off) or an odd number of buckets in [3,15]");
     if (value != 0 && !c->W) return fail(HR_ERR_NO_TARGET, "robust_buckets: hr_set_resolution not called");
     if (c->robust_on && (uint32_t)value == c->robust_k) return HR_OK;
+    if (c->denoised_by_robust) invalidate_denoised(c);   // a D of hr_denoise_robust is made of the buckets that go
     int rc = sync_all(c);
     if (rc) return rc;
     invalidate_robust(c);

@@ -217,3 +217,26 @@ static const bool ROBUST_NOISE_STAGED = true;
 static const RobustNoiseVariant *select_robust_noise_kernel(uint32_t k, bool stage) {
     return find_row(ROBUST_NOISE_VARIANTS, [&](const RobustNoiseVariant &r) { return r.k == k && r.stage == stage; });
 }
+
+// ---- robust_kernel<K> and robust_denoise_init_kernel<K> (post_kernels.h): hr_robust and the init pass of hr_denoise_robust, one row per K ----
+// Both stage a workgroup's span through lds() bytes of dynamic LDS (robust_stage_span; create_resources raises the limit).
+typedef void (*RobustFn)(const double *, const uint32_t *, unsigned long long, float *, uint8_t *, size_t);
+struct RobustVariant { uint32_t k; RobustFn fn; uint32_t lds() const { return 256u * 3u * k * (uint32_t)sizeof(double); } };
+static const RobustVariant ROBUST_VARIANTS[] = {
+    HR_VARIANT(robust_kernel, 3),  HR_VARIANT(robust_kernel, 5),  HR_VARIANT(robust_kernel, 7),  HR_VARIANT(robust_kernel, 9),
+    HR_VARIANT(robust_kernel, 11), HR_VARIANT(robust_kernel, 13), HR_VARIANT(robust_kernel, 15),
+};
+// K as option robust_buckets has it
+static const RobustVariant *select_robust_kernel(uint32_t k) {
+    return find_row(ROBUST_VARIANTS, [&](const RobustVariant &r) { return r.k == k; });
+}
+typedef void (*RobustDenoiseInitFn)(const double *, const uint32_t *, unsigned long long, const float *, double *, size_t, int);
+struct RobustDenoiseInitVariant { uint32_t k; RobustDenoiseInitFn fn; uint32_t lds() const { return 256u * 3u * k * (uint32_t)sizeof(double); } };
+static const RobustDenoiseInitVariant ROBUST_DENOISE_INIT_VARIANTS[] = {
+    HR_VARIANT(robust_denoise_init_kernel, 3),  HR_VARIANT(robust_denoise_init_kernel, 5),  HR_VARIANT(robust_denoise_init_kernel, 7),
+    HR_VARIANT(robust_denoise_init_kernel, 9),  HR_VARIANT(robust_denoise_init_kernel, 11), HR_VARIANT(robust_denoise_init_kernel, 13),
+    HR_VARIANT(robust_denoise_init_kernel, 15),
+};
+static const RobustDenoiseInitVariant *select_robust_denoise_init_kernel(uint32_t k) {
+    return find_row(ROBUST_DENOISE_INIT_VARIANTS, [&](const RobustDenoiseInitVariant &r) { return r.k == k; });
+}

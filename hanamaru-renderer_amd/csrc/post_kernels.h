@@ -41,21 +41,61 @@ __global__ __launch_bounds__(256) void denoise_final_kernel(const double *__rest
     denoise_final(cv + (size_t)i * 6, guides + (size_t)i * 8, demodulate, d + (size_t)i * 3);
 }
 
-// The firefly-robust resolve (robust_core.h): one thread per pixel, R and the trim plane from the pixel's K buckets.  The kernel carries
-// no arithmetic of its own.  counts == nullptr: every pixel has n_all samplings (option "sample_counts" off).
-__global__ __launch_bounds__(256) void robust_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all, uint32_t K,
-                                                     float *__restrict__ out, uint8_t *__restrict__ trim, uint32_t pixels) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+// A workgroup's 256 pixels through LDS, the staged form DESIGN.md §4.11 measured and kept (robust_noise_kernel below has it written out in its loop):
+// the pixels of workgroup `base / 256` are one contiguous span of 256 x 24 K bytes; the lanes load it as consecutive doubles (a wave's load is 512
+// contiguous bytes; past the last pixel of the image: zeros, nothing is read), park it in 256 x 24 K bytes of dynamic LDS, and every lane gets its own
+// pixel's 3 K doubles back (stride 3 K doubles, 3 K odd: no bank conflict).  Every thread of the workgroup calls it (the barrier).
+template <uint32_t K>
+constexpr uint32_t robust_stage_lds_bytes() { return 256u * 3u * K * (uint32_t)sizeof(double); }
+template <uint32_t K>
+__device__ __forceinline__ const double *robust_stage_span(const double *__restrict__ buckets, size_t base, size_t pixels) {
+    extern __shared__ double robust_stage[];
+    constexpr uint32_t D = 3u * K;   // doubles per pixel
+    const double *span = buckets + base * D;
+    double v[D];
+    if (base + 256u <= pixels) {
+#pragma unroll
+        for (uint32_t j = 0; j < D; j++) v[j] = span[j * 256u + threadIdx.x];
+    } else {
+        const size_t have = (pixels - base) * D;   // doubles of the span that exist
+#pragma unroll
+        for (uint32_t j = 0; j < D; j++) v[j] = j * 256u + threadIdx.x < have ? span[j * 256u + threadIdx.x] : 0.0;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < D; j++) robust_stage[j * 256u + threadIdx.x] = v[j];
+    __syncthreads();
+    return robust_stage + threadIdx.x * D;
+}
+
+// The firefly-robust resolve (robust_pixel_k, robust_core.h): one thread per pixel, one workgroup per span of 256 pixels, R and the
+// trim plane from the pixel's K buckets.  K is a template parameter: the bucket means live in registers, no array is indexed at run time, nothing
+// goes to scratch.  The kernel carries no arithmetic of its own.  counts == nullptr: every pixel has n_all samplings (option "sample_counts" off).
+template <uint32_t K>
+__global__ __launch_bounds__(256) void robust_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all,
+                                                     float *__restrict__ out, uint8_t *__restrict__ trim, size_t pixels) {
+    const size_t base = (size_t)blockIdx.x * 256u, i = base + threadIdx.x;
+    const double *B = robust_stage_span<K>(buckets, base, pixels);
     if (i >= pixels) return;
-    robust_pixel(buckets + (size_t)i * K * 3, K, counts ? (uint64_t)counts[i] : (uint64_t)n_all, out + (size_t)i * 3, trim + i);
+    robust_pixel_k<K>(B, counts ? (uint64_t)counts[i] : (uint64_t)n_all, out + i * 3, trim + i);
+}
+
+// The robust denoiser's init pass (robust_denoise_init_k, robust_core.h): the pixel's {C, V} from its K buckets into the
+// call-scoped plane of 6 doubles per pixel that denoise_init_kernel fills for hr_denoise; the levels and the final pass are atrous_kernel and
+// denoise_final_kernel above.  The same shape as robust_kernel; every pixel has n >= K samplings (hr_denoise_robust has checked).
+template <uint32_t K>
+__global__ __launch_bounds__(256) void robust_denoise_init_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all,
+                                                                  const float *__restrict__ guides, double *__restrict__ cv, size_t pixels, int demodulate) {
+    const size_t base = (size_t)blockIdx.x * 256u, i = base + threadIdx.x;
+    const double *B = robust_stage_span<K>(buckets, base, pixels);
+    if (i >= pixels) return;
+    robust_denoise_init_k<K>(B, counts ? (uint64_t)counts[i] : (uint64_t)n_all, guides + i * 8, demodulate, cv + i * 6);
 }
 
 // The robust noise estimate (robust_pixel_error_k, robust_core.h): e_R of every pixel into `img`, the trim it took into `trim`
 // (or nullptr), and the summary out[block] = {sum of e_R, max of e_R, pixels with e_R > threshold}, reduced in a fixed order — a fixed grid,
 // every thread its strided pixels in order, lanes and waves in order, the host adds the blocks' partial sums in index order (the scheme of
 // noise_kernel, hr_api.hip): two calls return identical bits.  The kernel carries no arithmetic of its own.
-// K is a template parameter: the pixel's K keys live in registers, no array is indexed at run time, nothing goes to scratch (robust_kernel above
-// pays 72 VGPRs and 368 B of scratch per lane for its run-time K).  counts == nullptr: every pixel has n_all samplings.
+// K is a template parameter: the pixel's K keys live in registers, no array is indexed at run time, nothing goes to scratch.  counts == nullptr: every pixel has n_all samplings.
 // STAGE: how the lanes come by their pixel's 3 K doubles — the arithmetic, and so every bit, is the same.
 //   true   a workgroup's 256 pixels are one contiguous span of 256 x 24 K bytes: its lanes load it as consecutive doubles (a wave's load is 512
 //          contiguous bytes), park it in 256 x 24 K bytes of dynamic LDS, and every lane reads its own pixel from there (stride 3 K doubles, 3 K odd:

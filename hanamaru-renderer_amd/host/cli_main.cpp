@@ -16,7 +16,8 @@
 // --robust K / --robust-image FILE (option "robust_buckets": every image is the firefly-robust resolve of K sample buckets per pixel, hr_robust +
 // hr_resolve_robust; the buckets ride in the checkpoint behind the other trailers),
 // --robust-noise (with --robust: --noise-target, --adaptive and --noise-image judge the robust image by the spread of its bucket means,
-// hr_robust_noise_estimate / hr_select_tiles_robust / hr_read_robust_noise_image).
+// hr_robust_noise_estimate / hr_select_tiles_robust / hr_read_robust_noise_image), --robust-denoise (with --robust: the FINAL
+// image is the a-trous filter's over the robust radiance and its bucket-spread variance, hr_denoise_robust + hr_resolve_denoised).
 // The file is in main's order: Options and parse_options (everything that can be refused before a device is opened), then Run, whose members
 // are main's steps.  The checkpoint's format is host/checkpoint.h's; what a render demands of a file is said in Run::resume.
 #include <algorithm>
@@ -121,7 +122,12 @@ static void usage(const char *prog) {
            "        --robust-noise  judge the noise of the image --robust shows, not of the plain mean: --noise-target asks hr_robust_noise_estimate,\n"
            "                        --adaptive asks hr_select_tiles_robust (after --resume too) and --noise-image maps min(1, e_R / E), e_R the\n"
            "                        winsorized standard error of the trimmed mean of the K bucket means over the channel sum + 3 F.  No estimate\n"
-           "                        before every pixel has K samplings.  Needs --robust; without this flag everything is judged as before.\n",
+           "                        before every pixel has K samplings.  Needs --robust; without this flag everything is judged as before.\n"
+           "        --robust-denoise\n"
+           "                        write the FINAL image through the a-trous filter on the robust radiance (hr_denoise_robust: --denoise's filter, fed\n"
+           "                        with the trimmed mean of the K bucket means and the winsorized variance of their spread instead of the raw moments;\n"
+           "                        progress images stay --robust's).  --denoise-levels, --guide-bounces and --guide-image work as with --denoise.  A\n"
+           "                        pixel with fewer than K samplings: the robust image is written unfiltered.  Needs --robust.\n",
            prog);
 }
 
@@ -148,6 +154,7 @@ struct Options {
     long long robust_k = 0;          // --robust K: option "robust_buckets" (0: off)
     std::string robust_png;
     bool robust_noise = false;       // --robust-noise: the noise questions are asked of the buckets (e_R), not of the moments
+    bool robust_denoise = false;     // --robust-denoise: the final image is hr_denoise_robust's
     // what the flags add up to:
     bool counts = false, moments = false;   // hr_set_option "sample_counts", "moments"
     double noise_e = 0.05;                  // the threshold of "above" and of the grey map
@@ -251,6 +258,7 @@ static int parse_options(int argc, char **argv, Options &o) {
             if (!whole("--robust", val("robust"), 3, 15, 2, "an odd number of buckets in 3 .. 15", &o.robust_k)) return 1;
         } else if (a == "--robust-image") o.robust_png = val("robust-image");
         else if (a == "--robust-noise") o.robust_noise = true;
+        else if (a == "--robust-denoise") o.robust_denoise = true;
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (o.batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -264,8 +272,9 @@ static int parse_options(int argc, char **argv, Options &o) {
         if (o.have_adaptive && o.have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
         if (o.debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
     }
-    if (o.denoise_levels >= 0 && !o.denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
-    if (o.guide_bounces >= 0 && !o.denoise && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
+    if (o.robust_denoise && !o.robust_k) { fprintf(stderr, "--robust-denoise needs --robust (it filters the robust radiance by the spread of the sample buckets).\n"); return 1; }
+    if (o.denoise_levels >= 0 && !o.denoise && !o.robust_denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
+    if (o.guide_bounces >= 0 && !o.denoise && !o.robust_denoise && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
     if (o.denoise || !o.guide_prefix.empty()) {
         if (!one_device(o, "--denoise / --guide-image render on one device: the library denoises one context's accumulator, moments and counts (a sharded host sums them into one), this program's device loop does not.")) return 1;
         if (o.debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
@@ -421,7 +430,18 @@ int Run::combine() {
 }
 // host-side sum: device 0 resolves the total from its accumulator, then gets its own partial sums back
 int Run::resolve(uint32_t s, uint8_t *out) {
-    if (o.robust_k) return hr_robust(ctx) != 0 ? 1 : hr_resolve_robust(ctx, out);   // (one device, no --denoise: checked with the flags)
+    if (o.robust_k) {   // (one device, no --denoise: checked with the flags)
+        if (o.robust_denoise && final_image) {
+            hr_denoise_params dp;
+            if (hr_denoise_default_params(&dp) != 0) return 1;
+            if (o.denoise_levels >= 0) dp.levels = (uint32_t)o.denoise_levels;
+            const int rc = hr_denoise_robust(ctx, &dp);   // (HR_ERR_INVALID: a pixel with fewer than K samplings — the flags' values were checked when they were read)
+            if (rc == 0) { have_guides = true; return hr_resolve_denoised(ctx, out); }   // (it rendered the guide planes, nothing has dropped them since)
+            if (rc != HR_ERR_INVALID) return rc;
+            tee("robust-denoise: fewer than K samplings behind a pixel, the robust image is not denoised.");
+        }
+        return hr_robust(ctx) != 0 ? 1 : hr_resolve_robust(ctx, out);
+    }
     if (o.denoise && final_image) {
         hr_denoise_params dp;
         if (hr_denoise_default_params(&dp) != 0) return 1;

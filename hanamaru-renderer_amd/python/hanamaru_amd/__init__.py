@@ -215,6 +215,7 @@ def hip_lib():
         L.hr_read_robust_noise_image.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.hr_read_robust_noise_trim.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.hr_select_tiles_robust.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint32)]
+        L.hr_denoise_robust.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)]
         _hip = L
     return _hip
 
@@ -582,6 +583,16 @@ class Renderer:
                 raise TypeError("denoise() has no parameter %r" % k)
             setattr(p, k, v)
         self._check(self.L.hr_denoise(self._h, C.byref(p)))
+
+    def denoise_robust(self, **params):
+        """hr_denoise_robust: denoise()'s filter on the robust radiance and its bucket-spread variance (option robust_buckets; no moments
+        needed); D is read with read_denoised / resolve_denoised."""
+        p = denoise_default_params()
+        for k, v in params.items():
+            if k not in dict(DenoiseParams._fields_):
+                raise TypeError("denoise_robust() has no parameter %r" % k)
+            setattr(p, k, v)
+        self._check(self.L.hr_denoise_robust(self._h, C.byref(p)))
 
     def read_denoised(self):
         """hr_read_denoised: (h, w, 3) float32 radiance."""

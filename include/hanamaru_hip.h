@@ -443,8 +443,8 @@ int hr_resolve_denoised(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 
  *     hr_bind_accumulator, switching "robust_buckets", "moments" or "sample_counts", hr_set_resolution, hr_set_region.  hr_read_robust,
  *     hr_read_robust_trim and hr_resolve_robust return HR_ERR_INVALID without a valid R; all six functions return HR_ERR_INVALID with the option
  *     off; in both cases R stays as it was.  hr_resolve_robust is renderer.rs:64-90 on R with the scale 1.0f, as hr_resolve_denoised is on D.
- *   - hr_noise_estimate, hr_select_tiles and the denoiser still read the raw moments; the robust noise estimate below reads the buckets.  All of
- *     these synchronise. */
+ *   - hr_noise_estimate, hr_select_tiles and hr_denoise still read the raw moments; the robust noise estimate and hr_denoise_robust below read
+ *     the buckets.  All of these synchronise. */
 int hr_read_buckets(hr_ctx *ctx, double *host /* w*h*K*3 */, uint64_t *samplings /* may be NULL */);
 int hr_write_buckets(hr_ctx *ctx, const double *host, uint64_t samplings);   /* resume, tile stitching */
 int hr_robust(hr_ctx *ctx);
@@ -475,6 +475,25 @@ int hr_robust_noise_estimate(hr_ctx *ctx, double floor, double threshold, hr_noi
 int hr_read_robust_noise_image(hr_ctx *ctx, double floor, double *host /* w*h */);
 int hr_read_robust_noise_trim(hr_ctx *ctx, double floor, uint8_t *host /* w*h */);
 int hr_select_tiles_robust(hr_ctx *ctx, double floor, double threshold, uint32_t *active /* may be NULL */);
+/* The robust denoiser: hr_denoise's filter on the robust radiance and a robust variance — not on the accumulator and the raw
+ * moments, which the few paths that R leaves out dominate.  Per pixel, with n_b, m_b,c, y_b, their ascending order (y_b, b) and trim exactly as
+ * hr_robust's (the definition is robust_pixel_cv_k in csrc/robust_core.h, to the bit: f64, + - x /, comparisons and one truncation, NO sqrt):
+ *         kept = K - 2 trim;   C_c = (m_(trim+1),c + .. + m_(K-trim),c) / kept                  (float)C_c is hr_robust's R_c
+ *         w_i,c = m_(i),c with i clamped to [trim + 1, K - trim]: winsorized by the RANK in y, per channel, i = 1 .. K
+ *         wbar_c = (sum_i w_i,c) / K;   ss_c = sum_i (w_i,c - wbar_c)^2;   f = K / kept;   V_c = ss_c / (K - 1) / K x f x f
+ *     V_c is the Tukey-McLaughlin variance of the trimmed mean, per channel; 0 by construction with trim = (K - 1) / 2.  {C, V} take the place of
+ *     hr_denoise's {C0, V0}; demodulation, the levels and the final pass are hr_denoise's (csrc/denoise_core.h), unchanged.
+ *   - It writes the same D as hr_denoise: hr_read_denoised and hr_resolve_denoised serve both, D is whichever call succeeded last.  With
+ *     levels = 0, D is R bit for bit and hr_resolve_denoised gives the bytes of hr_resolve_robust.
+ *   - It needs "robust_buckets" on ("moments" is not needed), works on the region, runs hr_render_guides itself when there are no guide planes,
+ *     synchronises, and puts its time into hr_stats.post_kernel_ms.  With "sample_counts" on every pixel has its own n.
+ *   - HR_ERR_INVALID — and D, R, the buckets, the counts and the mask stay exactly as they were — with the option off, while any pixel of the
+ *     region has fewer than K samplings, with "sample_counts" on when a count exceeds the samplings behind the buckets, and for the parameters
+ *     hr_denoise refuses.
+ *   - A D made by this call is valid until anything on hr_denoise's list changes, and also until "robust_buckets" is switched (every hr_write_*,
+ *     hr_write_buckets among them, is on that list already).  A D made by hr_denoise keeps its own rules.  The call touches neither R's validity,
+ *     the buckets, the accumulator, the moments nor the counts. */
+int hr_denoise_robust(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */);
 
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):

@@ -109,6 +109,8 @@ extern "C" {
     pub fn hr_read_robust_noise_image(ctx: *mut HrCtx, floor: f64, host: *mut f64 /* w*h */) -> c_int;
     pub fn hr_read_robust_noise_trim(ctx: *mut HrCtx, floor: f64, host: *mut u8 /* w*h */) -> c_int;
     pub fn hr_select_tiles_robust(ctx: *mut HrCtx, floor: f64, threshold: f64, active: *mut u32) -> c_int;
+    // hr_denoise's filter on the robust radiance and its bucket-spread variance; D is hr_read_denoised's / hr_resolve_denoised's
+    pub fn hr_denoise_robust(ctx: *mut HrCtx, p: *const HrDenoiseParams /* null = defaults */) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----

@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""tools/robust_denoise_rate.py [--buckets K] [--repeat N]: what one hr_denoise_robust costs.  Renders rtcamp6_v3_1 at 1920x1080
+with option robust_buckets K (default 9), 64 samplings, renders the guide planes, and then — after one warm-up call of each — times
+hr_denoise_robust with levels 0 (the init and final passes alone) and with levels 4, hr_robust_noise_estimate (which reads the same buckets) and
+hr_robust, N times alternating, by hr_stats.post_kernel_ms (the kernels' own event pair).  Prints every time, the medians, and for levels 0 the
+bytes moved (24 K read, 48 written, 48 read and 12 written per pixel) over the median.  --package: the python directory of another build of the
+package, as tools/robust_rate.py takes it; a build without hr_denoise_robust times hr_robust and the estimate only.  Not run by bench.py."""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", default="rtcamp6_v3_1")
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--samplings", type=int, default=64)
+    ap.add_argument("--buckets", type=int, default=9)
+    ap.add_argument("--repeat", type=int, default=10)
+    ap.add_argument("--package", default=os.path.join(ROOT, "hanamaru-renderer_amd", "python"))
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.package))
+    import hanamaru_amd as ha
+    W, H, K = a.width, a.height, a.buckets
+    r = ha.Renderer(0)
+    r.upload_scene(ha.Scene(a.scene, os.path.join(ROOT, "assets")))
+    r.set_resolution(W, H)
+    r.set_option("robust_buckets", K)
+    r.render(1, a.samplings + 1)
+    r.synchronize()
+    r.render_guides()
+
+    def timed(call):
+        before = r.stats()["post_kernel_ms"]
+        call()
+        return r.stats()["post_kernel_ms"] - before
+
+    cases = [("hr_robust", r.robust), ("hr_robust_noise_estimate", lambda: r.robust_noise_estimate(0.01, 0.08))]
+    if hasattr(r, "denoise_robust"):
+        cases += [("hr_denoise_robust levels 0", lambda: r.denoise_robust(levels=0)), ("hr_denoise_robust levels 4", lambda: r.denoise_robust(levels=4))]
+    for _, call in cases:
+        timed(call)
+    times = {name: [] for name, _ in cases}
+    for _ in range(a.repeat):
+        for name, call in cases:
+            times[name].append(timed(call))
+    print("library %s\nscene %s, %dx%d, K = %d, %d samplings" % (ha.HIP_LIB, a.scene, W, H, K, a.samplings))
+    for name, _ in cases:
+        print("%-27s ms: " % name + " ".join("%.3f" % t for t in times[name]) + "   median %.3f" % statistics.median(times[name]))
+    if "hr_denoise_robust levels 0" in times:
+        mbytes = W * H * (24 * K + 48 + 48 + 12) / 1e6
+        med = statistics.median(times["hr_denoise_robust levels 0"])
+        print("levels 0 moves %.0f MB: %.0f GB/s at the median; the buckets alone (%.0f MB) at 6.3 TB/s: %.3f ms" % (mbytes, mbytes / med, W * H * 24 * K / 1e6, W * H * 24 * K / 6.3e9))
+    r.close()
+
+
+if __name__ == "__main__":
+    main()
