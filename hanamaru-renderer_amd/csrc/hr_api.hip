@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -131,6 +132,7 @@ struct hr_ctx {
     // made of changes (invalidate_robust)
     bool robust_on = false;
     uint32_t robust_k = 0;
+    bool bucket_by_sampling = false;   // option "bucket_by_sampling" (DESIGN.md §4.13): sampling s in bucket (s - 1) mod K, so that shards add up (hr_fold_statistics)
     double *buckets = nullptr;
     uint64_t buckets_n = 0;
     float *robust = nullptr;
@@ -154,6 +156,7 @@ struct hr_ctx {
     hrcomm::Comm comm = nullptr;
     int comm_world = 0, comm_rank = 0;
     int comm_path = HR_COMM_NONE;              // how the group was formed (hr_comm_info)
+    uint64_t comm_group = 0;                   // hr_comm_init_local over distinct devices: the same number on every context of ONE call (hr_fold_statistics_group asks that its contexts are one group's), else 0
     uint64_t allreduces = 0;                   // collectives this context has enqueued since its communicator was made
     std::vector<hr_ctx *> same_device_peers;   // hr_comm_init_local over contexts that share ONE device: summed by a kernel, not by RCCL
     float *accum_total = nullptr;
@@ -1268,7 +1271,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     if (!trace) return fail(HR_ERR_UNSUPPORTED, "hr_render: no trace kernel instantiation for these options%s (kernel_variants.h)", list ? " under a tile mask" : "");
     const AccumulateFn accumulate = select_accumulate_kernel(c->moments != nullptr, c->counts != nullptr, list);
     if (!accumulate) return fail(HR_ERR_UNSUPPORTED, "hr_render: no accumulate kernel instantiation for these options (kernel_variants.h)");
-    const BucketFn bucket = c->buckets ? select_bucket_kernel(c->counts != nullptr, list) : nullptr;   // option robust_buckets off: nothing more is launched
+    const BucketFn bucket = c->buckets ? select_bucket_kernel(c->counts != nullptr, list, c->bucket_by_sampling) : nullptr;   // option robust_buckets off: nothing more is launched
     if (c->buckets && !bucket) return fail(HR_ERR_UNSUPPORTED, "hr_render: no bucket kernel instantiation for these options (kernel_variants.h)");
     for (uint32_t done = 0; done < total_k; done += batch) {
         uint32_t nk = std::min(batch, total_k - done);
@@ -1301,7 +1304,9 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
         // stream waits for the next seed kernel anyway
         if (!(c->debug_skip & 16)) {
             if (bucket) {   // in front of accumulate_kernel: a pixel's ordinal under sample_counts is its count BEFORE this launch
-                hipLaunchKernelGGL(bucket, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->buckets, c->counts, c->robust_k, (unsigned long long)c->buckets_n);
+                // by sampling: the launch's first bucket, (sampling_begin - 1) mod K, instead of the samplings behind the buckets
+                const unsigned long long start = c->bucket_by_sampling ? ((unsigned long long)rp.sampling_begin + c->robust_k - 1u) % c->robust_k : (unsigned long long)c->buckets_n;
+                hipLaunchKernelGGL(bucket, dim3((tiles + 3) / 4), dim3(256), 0, c->stream, rp, c->recs[slot], c->buckets, c->counts, c->robust_k, start);
                 HIP_TRY(hipGetLastError());
                 c->buckets_n += nk;
             }
@@ -1429,7 +1434,7 @@ static int comm_release(hr_ctx *c) {
     reset_same_device_peers(c);
     c->same_device_peers.clear();
     c->comm_world = 0; c->comm_rank = 0; c->total_valid = false;
-    c->comm_path = HR_COMM_NONE; c->allreduces = 0;
+    c->comm_path = HR_COMM_NONE; c->allreduces = 0; c->comm_group = 0;
     return HR_OK;
 }
 int hr_comm_init_rank(hr_ctx *c, const void *id, int world_size, int rank) {
@@ -1467,7 +1472,9 @@ int hr_comm_init_local(hr_ctx **ctxs, int n) {
         for (int j = 0; j < i; j++) if (devs[j] == devs[i]) return fail(HR_ERR_INVALID, "hr_comm_init_local: device %d appears twice (RCCL needs one rank per device)", devs[i]);
     }
     NCCL_TRY(hrcomm::api().CommInitAll(comms.data(), n, devs.data()));
-    for (int i = 0; i < n; i++) { ctxs[i]->comm = comms[i]; ctxs[i]->comm_world = n; ctxs[i]->comm_rank = i; ctxs[i]->comm_path = HR_COMM_RCCL_GROUP; }
+    static std::atomic<uint64_t> groups{0};
+    const uint64_t group = ++groups;
+    for (int i = 0; i < n; i++) { ctxs[i]->comm = comms[i]; ctxs[i]->comm_world = n; ctxs[i]->comm_rank = i; ctxs[i]->comm_path = HR_COMM_RCCL_GROUP; ctxs[i]->comm_group = group; }
     return HR_OK;
 }
 int hr_comm_destroy(hr_ctx *c) {
@@ -1533,6 +1540,188 @@ int hr_allreduce_accumulators(hr_ctx **ctxs, int n) {
     return HR_OK;
 }
 void *hr_total_device_ptr(hr_ctx *c) { return c && c->total_valid ? c->accum_total : nullptr; }
+
+// ---- hr_fold_statistics: every additive plane moves to rank 0 ------------------------------------------------
+// The planes a fold moves — the accumulator, and each option's plane while the option is on — in the order they are folded, with the RCCL type
+// of their elements.  FOLD_PLANES is the one list of them: the same-device kernel launches, the reduces and the non-roots' memsets walk it.
+struct FoldPlane { const Plane *plane; int dtype; };
+static const FoldPlane FOLD_PLANES[] = {{&ACCUM_OWN, hrcomm::kFloat}, {&MOMENTS, hrcomm::kDouble}, {&COUNTS, hrcomm::kUint32}, {&BUCKETS, hrcomm::kDouble}};
+static void *fold_plane_ptr(hr_ctx *c, const Plane &p) { return &p == &ACCUM_OWN ? (void *)c->accum : (p.on && !(c->*p.on)) ? nullptr : *p.slot(c); }
+
+extern "C++" {   // (templates inside the C ABI's block)
+__device__ __forceinline__ void fold_add(double2 &a, const double2 &b) { a.x += b.x; a.y += b.y; }
+__device__ __forceinline__ void fold_add(float4 &a, const float4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+__device__ __forceinline__ void fold_add(uint4 &a, const uint4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+template <class T> struct FoldVec;
+template <> struct FoldVec<double> { typedef double2 type; };
+template <> struct FoldVec<float> { typedef float4 type; };
+template <> struct FoldVec<uint32_t> { typedef uint4 type; };
+// root[i] += peer[i]; peer[i] = 0 over n elements: a stream of 16-byte loads and stores over the first `nvec` vectors (the host hands over
+// n / width, or 0 when one of the two buffers is not 16-byte aligned — a caller's bound accumulator may not be), a grid-stride loop under the
+// capped grid, then the elements behind the vectors one by one.  Every element is read and written by exactly one thread: no atomics.
+template <class T>
+__global__ __launch_bounds__(256) void fold_plane_kernel(T *__restrict__ root, T *__restrict__ peer, size_t n, size_t nvec) {
+    typedef typename FoldVec<T>::type V;
+    const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+    V *rv = reinterpret_cast<V *>(root), *pv = reinterpret_cast<V *>(peer);
+    for (size_t i = first; i < nvec; i += step) {
+        V a = rv[i];
+        const V b = pv[i];
+        fold_add(a, b);
+        rv[i] = a;
+        pv[i] = V{};
+    }
+    for (size_t i = nvec * (sizeof(V) / sizeof(T)) + first; i < n; i += step) {
+        root[i] += peer[i];
+        peer[i] = T(0);
+    }
+}
+template <class T>
+static hipError_t fold_plane_launch(void *root, void *peer, size_t n, hipStream_t st) {
+    const size_t width = 16 / sizeof(T);
+    const size_t nvec = ((uintptr_t)root | (uintptr_t)peer) % 16 ? 0 : n / width;
+    const size_t threads = nvec ? nvec + (n - nvec * width) : n;   // (a thread per vector; the tail is shorter than one vector)
+    const unsigned grid = (unsigned)std::min<size_t>(2048, std::max<size_t>(1, (threads + 255) / 256));
+    hipLaunchKernelGGL(fold_plane_kernel<T>, dim3(grid), dim3(256), 0, st, (T *)root, (T *)peer, n, nvec);
+    return hipGetLastError();
+}
+}  // extern "C++"
+
+// What a fold asks of one context, before anything is touched (`who`: the entry point).
+static int fold_refusal(hr_ctx *c, const char *who) {
+    if (!c) return fail(HR_ERR_INVALID, "%s: null ctx", who);
+    if (!c->comm && c->same_device_peers.empty()) return fail(HR_ERR_INVALID, "%s: no communicator (hr_comm_init_rank / hr_comm_init_local)", who);
+    if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "%s: no accumulator (hr_set_resolution not called)", who);
+    if (c->robust_on && !c->bucket_by_sampling)
+        return fail(HR_ERR_INVALID, "%s: robust_buckets is on with bucket_by_sampling 0 — buckets indexed by each pixel's ordinal do not add up across contexts "
+                    "(rank r's j-th sampling is not the j-th overall); set option bucket_by_sampling 1 on every context before it renders", who);
+    return HR_OK;
+}
+// ... and of the contexts of one group among each other: `ctxs` are the group's, all of them, in rank order
+static int fold_group_refusal(hr_ctx **ctxs, int n, const char *who) {
+    if (!ctxs || n < 1) return fail(HR_ERR_INVALID, "%s: bad argument", who);
+    for (int i = 0; i < n; i++) { int rc = fold_refusal(ctxs[i], who); if (rc) return rc; }
+    const hr_ctx *a = ctxs[0];
+    if (n != a->comm_world) return fail(HR_ERR_INVALID, "%s: %d contexts were given, the group has %d", who, n, a->comm_world);
+    for (int i = 0; i < n; i++) {
+        const hr_ctx *p = ctxs[i];
+        if (p->comm_world != n || p->comm_rank != i || p->comm_path != a->comm_path || p->comm_group != a->comm_group || (!a->same_device_peers.empty() && a->same_device_peers[i] != p))
+            return fail(HR_ERR_INVALID, "%s: context %d is not rank %d of the group of context 0 (the group's contexts, in the order hr_comm_init_local took them)", who, i, i);
+        if (p->W != a->W || p->H != a->H || p->RX != a->RX || p->RY != a->RY || p->RW != a->RW || p->RH != a->RH)
+            return fail(HR_ERR_INVALID, "%s: the contexts of the group differ in resolution or region", who);
+        if (p->moments_on != a->moments_on || p->counts_on != a->counts_on || p->robust_on != a->robust_on || p->robust_k != a->robust_k)
+            return fail(HR_ERR_INVALID, "%s: the contexts of the group differ in the options moments, sample_counts or robust_buckets (context %d: %d / %d / %u, context 0: %d / %d / %u)", who, i,
+                        (int)p->moments_on, (int)p->counts_on, p->robust_k, (int)a->moments_on, (int)a->counts_on, a->robust_k);
+    }
+    return HR_OK;
+}
+// what holds on every rank after a fold: the planes changed hands, so nothing made of them stands
+static void fold_invalidate(hr_ctx *c) {
+    invalidate_totals(c);
+    invalidate_denoised(c);
+    invalidate_robust(c);
+}
+// One device: for k = 1 .. n-1 in rank order root += peer_k, peer_k = 0, plane by plane — ((r0 + r1) + r2) .. to the bit.  Ordered as
+// allreduce_enqueue orders its sum: every context's render work is waited for, the kernels run on rank 0's stream, and they are finished
+// before the call returns (they write the PEERS' planes: a peer's next hr_render must not race with them).
+static int fold_same_device(hr_ctx **ctxs, int n) {
+    hr_ctx *root = ctxs[0];
+    HIP_TRY(hipSetDevice(root->device));
+    for (int i = n - 1; i >= 0; i--) { int rc = sync_all(ctxs[i]); if (rc) return rc; }
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, root->stream));
+    hipError_t e = hipSuccess;
+    for (int k = 1; k < n && e == hipSuccess; k++)
+        for (const FoldPlane &f : FOLD_PLANES) {
+            void *to = fold_plane_ptr(root, *f.plane), *from = fold_plane_ptr(ctxs[k], *f.plane);
+            if (!to || !from || e != hipSuccess) continue;
+            const size_t elems = plane_elems(root, *f.plane);
+            e = f.dtype == hrcomm::kFloat ? fold_plane_launch<float>(to, from, elems, root->stream) :
+                f.dtype == hrcomm::kDouble ? fold_plane_launch<double>(to, from, elems, root->stream) : fold_plane_launch<uint32_t>(to, from, elems, root->stream);
+        }
+    HIP_TRY(timed_end(e, ev, root->stream, root->post_events));
+    HIP_TRY(hipStreamSynchronize(root->stream));
+    for (int k = 1; k < n; k++) {
+        root->moments_n += ctxs[k]->moments_n; ctxs[k]->moments_n = 0;
+        root->buckets_n += ctxs[k]->buckets_n; ctxs[k]->buckets_n = 0;
+    }
+    for (int i = 0; i < n; i++) fold_invalidate(ctxs[i]);
+    return drain_events(root);
+}
+// RCCL: per plane one ncclReduce in place to root 0 behind the render work on each context's stream, the two counts as a 2-word u64 buffer through
+// the same reduce, then the non-roots' planes are zeroed on their streams.  `group`: one thread drives several ranks — their calls sit between
+// ncclGroupStart and ncclGroupEnd.  The summation order is RCCL's.
+static int fold_rccl(hr_ctx **ctxs, int n, bool group) {
+    const hrcomm::Api &api = hrcomm::api();
+    CallScratch scratch;
+    std::vector<uint64_t *> d_n(n, nullptr);
+    std::vector<uint64_t> h_n((size_t)n * 2);
+    for (int i = 0; i < n; i++) {
+        hr_ctx *c = ctxs[i];
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(scratch.alloc((void **)&d_n[i], 2 * sizeof(uint64_t)));
+        h_n[i * 2] = c->moments_n; h_n[i * 2 + 1] = c->buckets_n;
+        HIP_TRY(hipMemcpyAsync(d_n[i], &h_n[i * 2], 2 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    }
+    if (group) NCCL_TRY(api.GroupStart());
+    int r_ = 0;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && !r_ && e == hipSuccess; i++) {
+        hr_ctx *c = ctxs[i];
+        if ((e = hipSetDevice(c->device)) != hipSuccess) break;
+        for (const FoldPlane &f : FOLD_PLANES) {
+            void *p = fold_plane_ptr(c, *f.plane);
+            if (p && !r_) r_ = api.Reduce(p, p, plane_elems(c, *f.plane), f.dtype, hrcomm::kSum, 0, c->comm, c->stream);
+        }
+        if (!r_) r_ = api.Reduce(d_n[i], d_n[i], 2, hrcomm::kUint64, hrcomm::kSum, 0, c->comm, c->stream);
+    }
+    const int g_ = group ? api.GroupEnd() : 0;
+    if (e != hipSuccess) return fail(HR_ERR_DEVICE, "hr_fold_statistics: %s", hipGetErrorString(e));
+    if (r_ || g_) return fail(HR_ERR_DEVICE, "hr_fold_statistics: %s failed: %s", r_ ? "ncclReduce" : "ncclGroupEnd", api.GetErrorString(r_ ? r_ : g_));
+    for (int i = 0; i < n; i++) {
+        hr_ctx *c = ctxs[i];
+        HIP_TRY(hipSetDevice(c->device));
+        if (c->comm_rank != 0) {
+            for (const FoldPlane &f : FOLD_PLANES)
+                if (void *p = fold_plane_ptr(c, *f.plane)) HIP_TRY(hipMemsetAsync(p, 0, plane_bytes(c, *f.plane), c->stream));
+        } else
+            HIP_TRY(hipMemcpyAsync(&h_n[i * 2], d_n[i], 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    for (int i = 0; i < n; i++) {
+        hr_ctx *c = ctxs[i];
+        HIP_TRY(hipSetDevice(c->device));
+        int rc = sync_all(c);
+        if (rc) return rc;
+        c->moments_n = c->comm_rank == 0 ? h_n[i * 2] : 0;
+        c->buckets_n = c->comm_rank == 0 ? h_n[i * 2 + 1] : 0;
+        fold_invalidate(c);
+    }
+    return HR_OK;
+}
+int hr_fold_statistics_group(hr_ctx **ctxs, int n) {
+    static const char *const who = "hr_fold_statistics_group";
+    int rc = fold_group_refusal(ctxs, n, who);
+    if (rc) return rc;
+    const bool same_device = !ctxs[0]->same_device_peers.empty();
+    if (!same_device && !hrcomm::load()) return fail(HR_ERR_UNSUPPORTED, "%s", hrcomm::api().error.c_str());
+    rc = same_device ? fold_same_device(ctxs, n) : fold_rccl(ctxs, n, true);
+    // a fold that fails on the way (HR_ERR_DEVICE) may have moved some planes and not others, and the counts not at all: nothing made of them
+    // stands on any rank, and the group's statistics are the host's to start over (hr_clear)
+    if (rc) for (int i = 0; i < n; i++) fold_invalidate(ctxs[i]);
+    return rc;
+}
+int hr_fold_statistics(hr_ctx *c) {
+    static const char *const who = "hr_fold_statistics";
+    int rc = fold_refusal(c, who);
+    if (rc) return rc;
+    // a context of a same-device group knows its peers: the fold is the group's, whichever of them asks
+    if (!c->same_device_peers.empty()) return hr_fold_statistics_group(c->same_device_peers.data(), (int)c->same_device_peers.size());
+    if (c->comm_path == HR_COMM_RCCL_GROUP && c->comm_world > 1)
+        return fail(HR_ERR_INVALID, "%s: this context is one of %d that one process drives (hr_comm_init_local): hr_fold_statistics_group folds them in one RCCL group", who, c->comm_world);
+    if (!hrcomm::load()) return fail(HR_ERR_UNSUPPORTED, "%s", hrcomm::api().error.c_str());
+    if ((rc = fold_rccl(&c, 1, false))) fold_invalidate(c);   // (as in the group form: a fold that failed on the way leaves nothing to trust)
+    return rc;
+}
 
 // What the communicator says about itself — asked of RCCL, not remembered from the init call: the evidence a bench line needs that
 // its all-reduce ran over N ranks (ncclCommCount / ncclCommUserRank / ncclCommCuDevice / ncclGetVersion).
@@ -2296,6 +2485,26 @@ static int set_robust_buckets(hr_ctx *c, double value) {
     return HR_OK;
 }
 
+// The options of the sharded statistics, asked before hr_set_option's own keys: true when `key` is one of them, `rc` is then the call's.
+// "bucket_by_sampling": which bucket a sampling goes into — 0: the pixel's ordinal mod K, 1: (the sampling's index - 1) mod K.  Buckets filled under
+// one rule mean nothing under the other: switched while robust_buckets is on they start over as they do with another K — the counts and the moments
+// with them while sample_counts runs, R and a D made of R are gone.  With robust_buckets off the value is only recorded; any value but 0 and 1 is
+// refused and changes nothing.
+static bool set_sharding_option(hr_ctx *c, const std::string &key, double value, int &rc) {
+    if (key != "bucket_by_sampling") return false;
+    rc = HR_OK;
+    if (value != 0 && value != 1) { rc = fail(HR_ERR_INVALID, "bucket_by_sampling must be 0 (a pixel's j-th sampling in bucket j mod K) or 1 (sampling s in bucket (s - 1) mod K)"); return true; }
+    if ((value == 1) == c->bucket_by_sampling) return true;
+    if ((rc = sync_all(c))) return true;
+    c->bucket_by_sampling = value == 1;
+    if (!c->robust_on) return true;
+    if (c->denoised_by_robust) invalidate_denoised(c);
+    invalidate_robust(c);
+    if ((rc = plane_zero(c, BUCKETS))) return true;
+    if (c->counts_on) { invalidate_denoised(c); if ((rc = plane_zero(c, COUNTS))) return true; rc = plane_zero(c, MOMENTS); }
+    return true;
+}
+
 static const char *const RR_EXCLUDES_PRECISE = "russian_roulette and precise_shading 1 exclude each other (the roulette estimator has no f64 instantiation)";
 int hr_set_option(hr_ctx *c, const char *key, double value) {
     if (!c || !key) return fail(HR_ERR_INVALID, "hr_set_option: null argument");
@@ -2303,6 +2512,7 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
     std::string k = key;
     // the pair is refused where it is asked for, whichever comes second, and what was in force stays (hr_render keeps its own check)
     if (k == "precise_shading" && value == 1 && c->rr_start) return fail(HR_ERR_UNSUPPORTED, "%s", RR_EXCLUDES_PRECISE);
+    { int rc; if (set_sharding_option(c, k, value, rc)) return rc; }
     if (const OptionRow *row = find_row(PRODUCT_OPTIONS, [&](const OptionRow &r) { return k == r.key; })) return apply_option(c, *row, value);
     // per-pixel first and second moments of the per-sampling values, for the noise estimate, and how many samplings every pixel
     // has received: what a tile mask (hr_set_tile_mask) needs — the mask goes when the counts go

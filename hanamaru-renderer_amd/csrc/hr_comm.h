@@ -14,6 +14,7 @@ namespace hrcomm {
 typedef struct { char internal[128]; } UniqueId;   // ncclUniqueId (NCCL_UNIQUE_ID_BYTES = 128)
 typedef void *Comm;                                // ncclComm_t
 enum { kFloat = 7, kSum = 0 };                     // ncclFloat32, ncclSum
+enum { kUint32 = 3, kUint64 = 5, kDouble = 8 };    // ncclUint32, ncclUint64, ncclFloat64 (hr_fold_statistics: the counts, the samplings behind the planes, moments and buckets)
 
 struct Api {
     void *lib = nullptr;
@@ -21,6 +22,7 @@ struct Api {
     int (*CommInitRank)(Comm *, int, UniqueId, int) = nullptr;
     int (*CommInitAll)(Comm *, int, const int *) = nullptr;
     int (*AllReduce)(const void *, void *, size_t, int, int, Comm, hipStream_t) = nullptr;
+    int (*Reduce)(const void *, void *, size_t, int, int, int, Comm, hipStream_t) = nullptr;   // (send, recv, count, dtype, op, root, comm, stream)
     int (*GroupStart)() = nullptr;
     int (*GroupEnd)() = nullptr;
     int (*CommDestroy)(Comm) = nullptr;
@@ -75,6 +77,7 @@ inline bool load() {
     a.CommInitRank = (int (*)(Comm *, int, UniqueId, int))sym("ncclCommInitRank");
     a.CommInitAll = (int (*)(Comm *, int, const int *))sym("ncclCommInitAll");
     a.AllReduce = (int (*)(const void *, void *, size_t, int, int, Comm, hipStream_t))sym("ncclAllReduce");
+    a.Reduce = (int (*)(const void *, void *, size_t, int, int, int, Comm, hipStream_t))sym("ncclReduce");
     a.GroupStart = (int (*)())sym("ncclGroupStart");
     a.GroupEnd = (int (*)())sym("ncclGroupEnd");
     a.CommDestroy = (int (*)(Comm))sym("ncclCommDestroy");

@@ -187,13 +187,21 @@ static AccumulateFn select_accumulate_kernel(bool moments, bool counts, bool lis
     return fn_of(find_row(ACCUMULATE_VARIANTS, [&](const AccumulateVariant &r) { return r.mom == moments && r.cnts == counts && r.list == list; }));
 }
 
-// ---- bucket_kernel<CNTS, LIST> (trace_kernel.h): a launch's per-sampling pixel values into the sample buckets (option robust_buckets) ----
+// ---- bucket_kernel<CNTS, LIST, BYS> (trace_kernel.h): a launch's per-sampling pixel values into the sample buckets (option robust_buckets) ----
 typedef void (*BucketFn)(RenderParams, const float *, double *, const uint32_t *, uint32_t, unsigned long long);
-struct BucketVariant { bool cnts, list; BucketFn fn; };
-static const BucketVariant BUCKET_VARIANTS[] = {HR_VARIANT(bucket_kernel, false, false), HR_VARIANT(bucket_kernel, true, false), HR_VARIANT(bucket_kernel, true, true)};
-// sample_counts as the option has it; list: a tile mask is in force (it needs the counts: no <false, true> row)
-static BucketFn select_bucket_kernel(bool counts, bool list) {
-    return fn_of(find_row(BUCKET_VARIANTS, [&](const BucketVariant &r) { return r.cnts == counts && r.list == list; }));
+// (a row of two flags is the ordinal form of option bucket_by_sampling 0: BYS takes its default, false)
+struct BucketVariant {
+    bool cnts, list, bys;
+    BucketFn fn;
+    constexpr BucketVariant(bool c, bool l, BucketFn f) : cnts(c), list(l), bys(false), fn(f) {}
+    constexpr BucketVariant(bool c, bool l, bool b, BucketFn f) : cnts(c), list(l), bys(b), fn(f) {}
+};
+static const BucketVariant BUCKET_VARIANTS[] = {HR_VARIANT(bucket_kernel, false, false), HR_VARIANT(bucket_kernel, true, false), HR_VARIANT(bucket_kernel, true, true),
+                                                // option bucket_by_sampling 1: the same three launches, the bucket taken from the sampling's index
+                                                HR_VARIANT(bucket_kernel, false, false, true), HR_VARIANT(bucket_kernel, true, false, true), HR_VARIANT(bucket_kernel, true, true, true)};
+// sample_counts / bucket_by_sampling as the options have them; list: a tile mask is in force (it needs the counts: no <false, true, ..> row)
+static BucketFn select_bucket_kernel(bool counts, bool list, bool by_sampling) {
+    return fn_of(find_row(BUCKET_VARIANTS, [&](const BucketVariant &r) { return r.cnts == counts && r.list == list && r.bys == by_sampling; }));
 }
 
 // ---- robust_noise_kernel<K, STAGE> (post_kernels.h): the robust noise estimate of the sample buckets, one row per K the option robust_buckets takes ----

@@ -343,7 +343,11 @@ __device__ __forceinline__ float quad_sum(float v) {
 // buckets[reg_h][reg_w][K][3], one sampling at a time from the value in the buffer — the buckets do not depend on how samplings are cut into launches.
 // j starts at `start`, the samplings behind the buckets before this launch; CNTS (option "sample_counts"): at the pixel's own count, which
 // accumulate_kernel bumps behind this kernel.  LIST (a tile mask): one wave per ACTIVE tile, no other pixel is touched.
-template <bool CNTS, bool LIST = false>
+// BYS (option "bucket_by_sampling"): the bucket is the sampling's, not the pixel's ordinal's — sampling s goes into bucket
+// (s - 1) mod K whatever the pixel has received before, so that the buckets of contexts that shard the samplings add up (hr_fold_statistics).
+// `start` is then the launch's first bucket, (sampling_begin - 1) mod K, the step per sampling is stride mod K, and no count is read: CNTS only
+// names the row.  One context rendering samplings 1 .. n from a clear: the same additions in the same order as the ordinal form.
+template <bool CNTS, bool LIST = false, bool BYS = false>
 __global__ __launch_bounds__(256) void bucket_kernel(RenderParams rp, const float *__restrict__ recs, double *__restrict__ buckets, const uint32_t *__restrict__ counts, uint32_t K,
                                                       unsigned long long start) {
     const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -355,14 +359,16 @@ __global__ __launch_bounds__(256) void bucket_kernel(RenderParams rp, const floa
     const f4 *src = reinterpret_cast<const f4 *>(recs + (size_t)tile * rp.num_k * REC_ITEM_FLOATS) + lane;
     const size_t pixel = adds ? (size_t)py * rp_reg_w(rp) + px : 0;
     double *bk = buckets + pixel * K * 3;
-    uint32_t b = adds ? (uint32_t)((CNTS ? (unsigned long long)counts[pixel] : start) % K) : 0u;
+    uint32_t b = adds ? (uint32_t)((CNTS && !BYS ? (unsigned long long)counts[pixel] : start) % K) : 0u;
+    const uint32_t step = BYS ? rp.stride % K : 1u;   // (read by the BYS form only: the ordinal form steps as it always has)
     for (uint32_t k = 0; k < rp.num_k; k++) {   // (every lane of the wave is here: the trip count is the launch's)
         const f4 v = valid ? src[(size_t)k * (REC_ITEM_FLOATS / 4u)] : f4{0.0f, 0.0f, 0.0f, 0.0f};
         const float xr = quad_sum(path_radiance_in(v.x)), xg = quad_sum(path_radiance_in(v.y)), xb = quad_sum(path_radiance_in(v.z));
         if (adds) {
             double *o = bk + b * 3u;
             o[0] += (double)xr; o[1] += (double)xg; o[2] += (double)xb;
-            b = b + 1u == K ? 0u : b + 1u;
+            if (BYS) { b += step; if (b >= K) b -= K; }
+            else b = b + 1u == K ? 0u : b + 1u;
         }
     }
 }

@@ -216,6 +216,8 @@ def hip_lib():
         L.hr_read_robust_noise_trim.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.hr_select_tiles_robust.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint32)]
         L.hr_denoise_robust.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)]
+        L.hr_fold_statistics.argtypes = [C.c_void_p]
+        L.hr_fold_statistics_group.argtypes = [C.POINTER(C.c_void_p), C.c_int]
         _hip = L
     return _hip
 
@@ -268,6 +270,16 @@ def allreduce_accumulators(renderers):
     L = hip_lib()
     arr = (C.c_void_p * len(renderers))(*[r._h for r in renderers])
     rc = L.hr_allreduce_accumulators(arr, len(renderers))
+    if rc != 0:
+        raise HipError(rc, L.hr_last_error().decode())
+
+
+def fold_statistics(renderers):
+    """hr_fold_statistics_group: the renderers of one comm_init_local group, in its order — accumulator, moments, sample counts and buckets
+    (option bucket_by_sampling 1) of every renderer move to renderers[0], the others hold zeros; every renderer goes on rendering."""
+    L = hip_lib()
+    arr = (C.c_void_p * len(renderers))(*[r._h for r in renderers])
+    rc = L.hr_fold_statistics_group(arr, len(renderers))
     if rc != 0:
         raise HipError(rc, L.hr_last_error().decode())
 
@@ -489,6 +501,10 @@ class Renderer:
 
     def allreduce_accumulator(self):
         self._check(self.L.hr_allreduce_accumulator(self._h))
+
+    def fold_statistics(self):
+        """hr_fold_statistics: this rank's part of the fold into rank 0 (comm_init_rank: every rank calls it)."""
+        self._check(self.L.hr_fold_statistics(self._h))
 
     def total_device_ptr(self):
         return self.L.hr_total_device_ptr(self._h)

@@ -282,7 +282,7 @@ int hr_accumulator_sum(hr_ctx *ctx, int which, double out_rgb[3]);
  *     fixed order (two calls return identical bits).  hr_read_noise_image: e of every pixel, w*h doubles.
  *   - Multi-GPU: each context counts and accumulates its own shard (hr_render's stride).  Moments are additive: a host adds the ranks'
  *     hr_read_moments results and counts in rank order and may hr_write_moments the total into one context to ask for the estimate.
- *     (There is no library-side collective for them.)
+ *     hr_fold_statistics (below) does that on the device: it moves every rank's moments and count to rank 0, which then answers.
  *   - All of them synchronise (they read results back), like hr_accumulator_sum. */
 typedef struct hr_noise {
     uint64_t samplings, pixels, pixels_above;
@@ -307,7 +307,7 @@ int hr_read_noise_image(hr_ctx *ctx, double floor, double *host /* w*h */);
  *     all three).  The accumulator and the moments are bit-identical with the option on or off.  hr_render_debug returns HR_ERR_UNSUPPORTED
  *     while it is on.  With the option off the functions below return HR_ERR_INVALID (hr_get_tile_mask excepted).
  *   - hr_read_sample_counts / hr_write_sample_counts: w*h uint32, row-major, top row first — resume, tile stitching, shards.  Counts are
- *     additive like moments: a host adds the ranks' counts (there is no library-side collective).
+ *     additive like moments: a host adds the ranks' counts, or hr_fold_statistics (below) moves them to rank 0.
  *   - With "sample_counts" and "moments" both on, hr_noise_estimate and hr_read_noise_image take the PIXEL's count as n, and return
  *     HR_ERR_INVALID if any pixel of the region has a count below 2.  hr_noise.samplings keeps its meaning (samplings issued since the
  *     moments were zeroed).  With "sample_counts" off nothing about the two changes.  The counts are the moments' n, so the two cover the
@@ -427,8 +427,8 @@ int hr_resolve_denoised(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 
  *     on.  The option does not need "moments".  The accumulator, the moments and the counts are bit-identical with the option on or off, and
  *     with it off nothing more is launched.
  *   - hr_read_buckets / hr_write_buckets: w*h*K*3 doubles and the samplings behind them — resume, tile stitching.  Buckets of several ranks can
- *     be added only when every rank rendered a multiple of K samplings (bucket b of every rank then holds the same share); there is no
- *     library-side collective.
+ *     be added only when every rank rendered a multiple of K samplings (bucket b of every rank then holds the same share) — or, whatever
+ *     they rendered, when they were filled with option "bucket_by_sampling" 1 (see hr_fold_statistics below, which then adds them on the device).
  *   - hr_robust computes R (w x h x 3 floats of radiance) and the trim plane (w x h bytes) — both allocated on first use; its time goes to
  *     hr_stats.post_kernel_ms.  The definition is csrc/robust_core.h, to the bit (f64; + - x /, comparisons and one truncation; one IEEE
  *     operation per step, no FMA).  For a pixel with n samplings (its own count with "sample_counts" on, else the count behind the buckets) and
@@ -495,6 +495,42 @@ int hr_select_tiles_robust(hr_ctx *ctx, double floor, double threshold, uint32_t
  *     the buckets, the accumulator, the moments nor the counts. */
 int hr_denoise_robust(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */);
 
+/* ---- sharded statistics: buckets by sampling, and the fold into rank 0 ----------------------------------------------------------
+ * Contexts that shard the samplings (hr_render's stride) each hold a share of every additive plane.  hr_fold_statistics moves the shares to
+ * rank 0 of the communicator, so that ONE context answers every question with the functions above, unchanged: hr_noise_estimate,
+ * hr_select_tiles, hr_denoise, hr_robust, hr_robust_noise_estimate, hr_select_tiles_robust, hr_denoise_robust, hr_resolve_counted, hr_read_*.
+ *   - Option "bucket_by_sampling" 0 (default) / 1.  With 1 sampling s goes into bucket (s - 1) mod K whatever the pixel has received before; s is
+ *     the index hr_render renders (s_begin, s_begin + stride, ..), and no count is read.  With 0 nothing differs by a bit from the ordinal form
+ *     above.  hr_robust, the robust noise family and hr_denoise_robust are unchanged: they take bucket b to hold n_b = (n - b + K - 1) / K
+ *     samplings, which is right if and only if the pixel has received samplings 1 .. n — on whatever contexts, once their buckets are added.  One
+ *     context rendering 1 .. n from a clear gets buckets bit-identical to the ordinal form's; a host that skips or repeats indices gets what it
+ *     asked for.  Switching the option while "robust_buckets" is on starts the buckets over exactly as another K does (the counts and the moments
+ *     with them while "sample_counts" is on; R and a D of hr_denoise_robust are invalid); with "robust_buckets" off the value is only recorded.
+ *     Any value other than 0 or 1 is HR_ERR_INVALID and changes nothing.
+ *   - What a fold moves: the accumulator (fp32), and where their option is on the moments (f64) with their count, the sample counts (u32) and
+ *     the buckets (f64) with their count.  Afterwards rank 0's own planes hold the sum over all ranks and its two counts are the sums; every
+ *     other rank's planes are zero and its counts 0.  The global sum is preserved, so every rank simply goes on rendering and a later fold adds
+ *     what came since.  A bound accumulator (hr_bind_accumulator) is folded in place.
+ *   - Contexts that share one device (HR_COMM_SAME_DEVICE_SUM): a kernel adds rank 1, 2, .. to rank 0 in rank order — ((r0 + r1) + r2) .. to the
+ *     bit in every type — and zeroes them; its time goes to rank 0's hr_stats.post_kernel_ms.  RCCL groups and ranks: one ncclReduce per plane in
+ *     place to root 0, behind the render work on the context's stream, then the plane is zeroed on the other ranks; the summation order is
+ *     RCCL's, so the result is equal to rounding, not to the bit.
+ *   - hr_fold_statistics is the form of one process per GPU (hr_comm_init_rank; every rank calls it); hr_fold_statistics_group the form of one
+ *     process with n contexts (hr_comm_init_local; ctxs in the order the group was made of, one ncclGroupStart / ncclGroupEnd).  For a context of
+ *     a same-device group hr_fold_statistics folds the whole group, whichever context asks.
+ *   - Both synchronise.  On EVERY rank the all-reduced total (hr_total_device_ptr), R and D are invalid afterwards; the tile mask, the guide
+ *     planes, the options and hr_stats.paths stay.  (A host that selects tiles on rank 0 sets rank 0's mask on the others itself.)
+ *   - HR_ERR_INVALID, and nothing is touched: no communicator; n is not the group's size or ctxs are not the contexts of ONE hr_comm_init_local call in its order; the
+ *     contexts of the group differ in resolution, region, which of "moments", "sample_counts", "robust_buckets" are on, or K; "robust_buckets" is
+ *     on with "bucket_by_sampling" 0 (ordinal buckets of different contexts do not add up); hr_fold_statistics on a context of an
+ *     hr_comm_init_local group of several devices.  In the one-process-per-GPU form each rank can check only itself: ranks that differ there hand
+ *     RCCL buffers of different sizes, which is the host's to avoid.  HR_ERR_NO_TARGET without a resolution, HR_ERR_UNSUPPORTED when RCCL is
+ *     needed and cannot be loaded.  A group of one is a valid fold that moves nothing and still invalidates.
+ *   - HR_ERR_DEVICE (a launch, a copy or an RCCL call failed on the way) is no refusal: some planes may have moved and others not, the counts are
+ *     as they were, and the total, R and D are invalid on every rank.  The group's statistics cannot be trusted after it: hr_clear every context. */
+int hr_fold_statistics(hr_ctx *ctx);
+int hr_fold_statistics_group(hr_ctx **ctxs, int n);
+
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):
  *   "counters"      0 / 1: instrumented build of the trace kernel (fills the counter fields of hr_stats)
@@ -526,6 +562,8 @@ int hr_get_stats(hr_ctx *ctx, hr_stats *out);
  *                   hr_resolve_counted (see there); the image does not change by a bit
  *   "robust_buckets" 0 (default) / K in {3, 5, .., 15}: keep K sample buckets per pixel for hr_robust (see there; 3 K doubles per pixel); the
  *                   image does not change by a bit
+ *   "bucket_by_sampling" 0 (default) / 1: with 1 sampling s goes into bucket (s - 1) mod K instead of the pixel's j-th into j mod K, so that the
+ *                   buckets of contexts that shard the samplings add up (see hr_fold_statistics); the image does not change by a bit
  *   next hr_render_guides:
  *   "guide_bounces" 0 (default) .. 8, a whole number: how many mirrors and glass surfaces the guide rays follow to the first rough hit (see
  *                   "guide planes" above).  A new value drops the guide planes and the denoised image; the value it already has changes

@@ -111,6 +111,9 @@ extern "C" {
     pub fn hr_select_tiles_robust(ctx: *mut HrCtx, floor: f64, threshold: f64, active: *mut u32) -> c_int;
     // hr_denoise's filter on the robust radiance and its bucket-spread variance; D is hr_read_denoised's / hr_resolve_denoised's
     pub fn hr_denoise_robust(ctx: *mut HrCtx, p: *const HrDenoiseParams /* null = defaults */) -> c_int;
+    // every additive plane (accumulator, moments, counts, buckets filled under option "bucket_by_sampling" 1) moves to rank 0, which then answers
+    pub fn hr_fold_statistics(ctx: *mut HrCtx) -> c_int;
+    pub fn hr_fold_statistics_group(ctxs: *mut *mut HrCtx, n: c_int) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----
