@@ -90,12 +90,54 @@ HR_DENOISE_HD double denoise_kernel_weight(double x) {
     return u * u;
 }
 
+// h of the tap (i, j), i, j = -2 .. 2: k[|i|] k[|j|], k = {3/8, 1/4, 1/16}
+HR_DENOISE_HD double denoise_tap_h(int i, int j) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double K[3] = {0.375, 0.25, 0.0625};
+    return K[i < 0 ? -i : i] * K[j < 0 ? -j : j];
+}
+
+// The guide terms of a tap, from the guides gp[8] of the pixel and gq[8] of the tap (zp = (double)gp[6] and zp2 = zp zp come from the caller: a level
+// takes them once for its 25 taps).  Every x is made of (a - b)^2 and Z_p^2 + Z_q^2: swapping the pixel and the tap gives the same bits.
+struct DenoiseGuideX { double n, a, z, h; };
+HR_DENOISE_HD DenoiseGuideX denoise_guide_x(const float *gp, const float *gq, double zp, double zp2, const DenoiseSigmas &sg) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    DenoiseGuideX r;
+    const double n0 = (double)gp[3] - (double)gq[3], n1 = (double)gp[4] - (double)gq[4], n2 = (double)gp[5] - (double)gq[5];
+    r.n = ((n0 * n0 + n1 * n1) + n2 * n2) / sg.n2;
+    const double a0 = (double)gp[0] - (double)gq[0], a1 = (double)gp[1] - (double)gq[1], a2 = (double)gp[2] - (double)gq[2];
+    r.a = ((a0 * a0 + a1 * a1) + a2 * a2) / sg.a2;
+    const double zq = (double)gq[6], dz = zp - zq;
+    r.z = (dz * dz) / (sg.z2 * (zp2 + zq * zq) + DENOISE_TINY);
+    const double dh = (double)gp[7] - (double)gq[7];
+    r.h = dh * dh;
+    return r;
+}
+// the guide part of the tap's weight: (((h K(x_n)) K(x_a)) K(x_z)) K(x_h)
+HR_DENOISE_HD double denoise_guide_product(double hw, const DenoiseGuideX &x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return (((hw * denoise_kernel_weight(x.n)) * denoise_kernel_weight(x.a)) * denoise_kernel_weight(x.z)) * denoise_kernel_weight(x.h);
+}
+// both for one pair of pixels (restore_core.h: a spread without the colour term)
+HR_DENOISE_HD double denoise_guide_weight(double hw, const float *gp, const float *gq, const DenoiseSigmas &sg) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double zp = (double)gp[6];
+    return denoise_guide_product(hw, denoise_guide_x(gp, gq, zp, zp * zp, sg));
+}
+
 // One level for the pixel (x, y) of a w x h image: in[h][w][6] -> out[6]; guides[h][w][8].
 HR_DENOISE_HD void denoise_level(const double *in, const float *guides, uint32_t w, uint32_t h, uint32_t x, uint32_t y, uint32_t step, const DenoiseSigmas &sg, double *out) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    const double K[3] = {0.375, 0.25, 0.0625};
     const size_t p = (size_t)y * w + x;
     const double *cp = in + p * 6;
     const float *gp = guides + p * 8;
@@ -111,19 +153,12 @@ HR_DENOISE_HD void denoise_level(const double *in, const float *guides, uint32_t
             const size_t q = (size_t)qy * w + (size_t)qx;
             const double *cq = in + q * 6;
             const float *gq = guides + q * 8;
-            const double hw = K[i < 0 ? -i : i] * K[j < 0 ? -j : j];
-            const double n0 = (double)gp[3] - (double)gq[3], n1 = (double)gp[4] - (double)gq[4], n2 = (double)gp[5] - (double)gq[5];
-            const double xn = ((n0 * n0 + n1 * n1) + n2 * n2) / sg.n2;
-            const double a0 = (double)gp[0] - (double)gq[0], a1 = (double)gp[1] - (double)gq[1], a2 = (double)gp[2] - (double)gq[2];
-            const double xa = ((a0 * a0 + a1 * a1) + a2 * a2) / sg.a2;
-            const double zq = (double)gq[6], dz = zp - zq;
-            const double xz = (dz * dz) / (sg.z2 * (zp2 + zq * zq) + DENOISE_TINY);
-            const double dh = (double)gp[7] - (double)gq[7];
-            const double xh = dh * dh;
+            const double hw = denoise_tap_h(i, j);
+            const DenoiseGuideX gx = denoise_guide_x(gp, gq, zp, zp2, sg);
             const double c0 = cp[0] - cq[0], c1 = cp[1] - cq[1], c2 = cp[2] - cq[2];
             const double sv_q = (cq[3] + cq[4]) + cq[5];
             const double xc = ((c0 * c0 + c1 * c1) + c2 * c2) / (sg.c2 * (sv_p + sv_q) + DENOISE_TINY);
-            const double wt = ((((hw * denoise_kernel_weight(xn)) * denoise_kernel_weight(xa)) * denoise_kernel_weight(xz)) * denoise_kernel_weight(xh)) * denoise_kernel_weight(xc);
+            const double wt = denoise_guide_product(hw, gx) * denoise_kernel_weight(xc);
             const double w2 = wt * wt;
             sw = sw + wt;
             for (int c = 0; c < 3; c++) {

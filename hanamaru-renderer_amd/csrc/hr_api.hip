@@ -10,11 +10,12 @@
 //   wf_kernels.h     the split pipeline (option trace_mode 1): wf_start_kernel, wf_traverse_kernel (the same traversal at <= 64 VGPRs),
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
 //   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
-//                    robust_kernel, robust_denoise_init_kernel and robust_noise_kernel (robust_core.h)
+//                    robust_kernel, robust_denoise_init_kernel and robust_noise_kernel (robust_core.h); restore_init_kernel, spread_norm_kernel,
+//                    spread_gather_kernel and restore_final_kernel (restore_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
-// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane, robust noise image and its trim plane) are rows of one
+// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane, robust noise image and its trim plane, restored robust image) are rows of one
 // table, PLANES, with one set of routines for their bytes, life cycle, zeroing and host copies; scratch a call needs lives in a CallScratch.
 #include <hip/hip_runtime.h>
 
@@ -138,6 +139,10 @@ struct hr_ctx {
     float *robust = nullptr;
     uint8_t *robust_trim = nullptr;
     bool robust_valid = false;
+    // the restored robust radiance R' of the last hr_robust_restore, valid until anything it was made of changes: the buckets, the
+    // counts, the guides, the target (invalidate_restored) — and, when its base was D (restored_on_d), a new D
+    float *restored = nullptr;
+    bool restored_valid = false, restored_on_d = false;
     // the robust noise estimate: e_R of every pixel and the trim behind it, as the last estimate or selection left them (allocated
     // when one is first asked for; every call that reads them has just written them)
     double *robust_noise_img = nullptr;
@@ -364,9 +369,12 @@ static void invalidate_totals(hr_ctx *c) {
     for (hr_ctx *p : c->same_device_peers) p->total_valid = false;
 }
 // the accumulator, the moments, the counts or the guides of `c` are about to change, or its target: the denoised image is no longer theirs
-static void invalidate_denoised(hr_ctx *c) { c->denoised_valid = false; }
+// (everything D is made of, R' is made of or may be: R' goes with it; a NEW D takes only an R' that was based on D — new_denoised)
+static void invalidate_restored(hr_ctx *c) { c->restored_valid = false; }
+static void invalidate_denoised(hr_ctx *c) { c->denoised_valid = false; invalidate_restored(c); }
+static void new_denoised(hr_ctx *c) { c->denoised_valid = false; if (c->restored_on_d) invalidate_restored(c); }
 // the same for the robust radiance: the buckets or the counts of `c` are about to change, its accumulator or its target
-static void invalidate_robust(hr_ctx *c) { c->robust_valid = false; }
+static void invalidate_robust(hr_ctx *c) { c->robust_valid = false; invalidate_restored(c); }
 static int drain_events(hr_ctx *c) {
     auto sum = [](std::vector<EventPair> &ev, double &acc) -> hipError_t {
         // a pair whose query fails is dropped with the rest (left in the list it would fail every later drain, i.e. every later API call)
@@ -467,7 +475,7 @@ static int free_mask_buffers(hr_ctx *c) {
 //   WITH_OPTION   allocated while the option `on` is on: when it is switched on, and by set_target while it is on; gone when it is switched off
 //   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate; guides: the first
 //                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise; robust, robust_trim: the first hr_robust; robust_noise_img,
-//                 robust_noise_trim: the first robust noise estimate), freed by set_target —
+//                 robust_noise_trim: the first robust noise estimate; restored: the first hr_robust_restore), freed by set_target —
 //                 noise_img also with the moments it is made of, guides also by hr_upload_scene (they show the scene), robust, robust_trim
 //                 and the robust noise planes also with the buckets they are made of
 // at_alloc: zeroed when allocated.  at_clear: zeroed by hr_clear.  n: the count that belongs to the plane's contents and is zeroed with them.
@@ -499,8 +507,9 @@ static const Plane ROBUST{PLANE_SLOT(robust), sizeof(float), 3, ON_FIRST_USE, fa
 static const Plane ROBUST_TRIM{PLANE_SLOT(robust_trim), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
 static const Plane ROBUST_NOISE_IMG{PLANE_SLOT(robust_noise_img), sizeof(double), 1, ON_FIRST_USE, false, false};
 static const Plane ROBUST_NOISE_TRIM{PLANE_SLOT(robust_noise_trim), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
+static const Plane RESTORED{PLANE_SLOT(restored), sizeof(float), 3, ON_FIRST_USE, false, false};
 #undef PLANE_SLOT
-static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM, &ROBUST_NOISE_IMG, &ROBUST_NOISE_TRIM};
+static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM, &ROBUST_NOISE_IMG, &ROBUST_NOISE_TRIM, &RESTORED};
 
 static size_t region_pixels(const hr_ctx *c) { return (size_t)c->RW * c->RH; }
 static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps * (p.per ? c->*p.per : 1u); }
@@ -604,6 +613,7 @@ static int create_resources(hr_ctx *c) {
     for (const RobustNoiseVariant &v : ROBUST_NOISE_VARIANTS) if (v.lds()) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     for (const RobustVariant &v : ROBUST_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     for (const RobustDenoiseInitVariant &v : ROBUST_DENOISE_INIT_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
+    for (const RestoreInitVariant &v : RESTORE_INIT_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     HIP_TRY(hipFuncSetAttribute((const void *)seed_debug_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 8));
     // The seed kernel owns all 160 KiB of a CU's LDS and runs next to the trace side of the previous batch: a trace-side kernel that
     // uses ANY LDS (the compiler promotes small private arrays to LDS unless told not to, see the Makefile) could not share a CU
@@ -2035,7 +2045,7 @@ int hr_denoise(hr_ctx *c, const hr_denoise_params *params) {
     CallScratch scratch;
     double *cv[2] = {nullptr, nullptr};
     for (int k = 0; k < 2; k++) HIP_TRY_AS(who, scratch.alloc((void **)&cv[k], (size_t)pixels * 6 * sizeof(double)));
-    invalidate_denoised(c);
+    new_denoised(c);
     const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
     const int demodulate = p.demodulate && p.levels ? 1 : 0;   // without a level there is nothing to filter: D = (float)C0, as the header says
     EventPair ev;
@@ -2085,7 +2095,7 @@ int hr_robust(hr_ctx *c) {
     if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_kernel instantiation for %u buckets (kernel_variants.h)", who, c->robust_k);
     if (!c->robust && (rc = plane_alloc(c, ROBUST))) return rc;
     if (!c->robust_trim && (rc = plane_alloc(c, ROBUST_TRIM))) return rc;
-    invalidate_robust(c);
+    c->robust_valid = false;   // (R alone: R' is not made of R)
     const size_t pixels = region_pixels(c);
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
@@ -2326,7 +2336,7 @@ int hr_denoise_robust(hr_ctx *c, const hr_denoise_params *params) {
     CallScratch scratch;
     double *cv[2] = {nullptr, nullptr};
     for (int k = 0; k < 2; k++) HIP_TRY_AS(who, scratch.alloc((void **)&cv[k], pixels * 6 * sizeof(double)));
-    invalidate_denoised(c);
+    new_denoised(c);
     const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
     const int demodulate = p.demodulate && p.levels ? 1 : 0;   // without a level there is nothing to filter: D = (float)C = R
     EventPair ev;
@@ -2341,6 +2351,87 @@ int hr_denoise_robust(hr_ctx *c, const hr_denoise_params *params) {
     c->denoised_valid = true;
     c->denoised_by_robust = true;
     return drain_events(c);
+}
+
+// ---- the restored robust resolve (restore_core.h): R' = base + the trimmed buckets' excess, spread along the guide planes ----
+// Everything that is refused is refused before anything is touched: R' of an earlier call stays.  Nothing but R' (and, without guide planes, the
+// guides) is written: R, D, the buckets, the accumulator, the moments and the counts are read only or not at all.
+int hr_restore_default_params(hr_restore_params *out) {
+    if (!out) return fail(HR_ERR_INVALID, "hr_restore_default_params: null argument");
+    memset(out, 0, sizeof *out);
+    out->levels = 4; out->base = 0;
+    out->sigma_n = 0.5; out->sigma_a = 0.25; out->sigma_z = 0.1;
+    return HR_OK;
+}
+int hr_robust_restore(hr_ctx *c, const hr_restore_params *params) {
+    static const char *const who = "hr_robust_restore";
+    int rc = plane_ready(c, BUCKETS, who);
+    if (rc) return rc;
+    hr_restore_params p;
+    if (params) p = *params;
+    else (void)hr_restore_default_params(&p);
+    if (p.levels > RESTORE_MAX_LEVELS) return fail(HR_ERR_INVALID, "%s: levels must be in [0,%u]", who, RESTORE_MAX_LEVELS);
+    if (p.base > 1u) return fail(HR_ERR_INVALID, "%s: base must be 0 (the robust radiance) or 1 (the denoised robust radiance)", who);
+    for (double s : {p.sigma_n, p.sigma_a, p.sigma_z})
+        if (!(s > 0.0) || !(s < INFINITY)) return fail(HR_ERR_INVALID, "%s: every sigma must be positive and finite", who);
+    if (p.base == 1u && !(c->denoised && c->denoised_valid && c->denoised_by_robust))
+        return fail(HR_ERR_INVALID, "%s: base 1 needs a valid denoised image made by hr_denoise_robust", who);
+    const uint32_t K = c->robust_k;
+    if (!c->counts && c->buckets_n < K) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the %u buckets, the excess of the bucket means needs one in each", who, (unsigned long long)c->buckets_n, K);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = hr_synchronize(c))) return rc;
+    if (c->counts) {
+        uint32_t mm[2];
+        if ((rc = counts_range(c, mm))) return rc;
+        if (mm[0] < K) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), %u bucket means need one in each", who, mm[0], K);
+        if ((uint64_t)mm[1] > c->buckets_n)
+            return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the buckets cover %llu (the counts and the buckets must cover the same samplings)", who, mm[1], (unsigned long long)c->buckets_n);
+    }
+    const RestoreInitVariant *v = select_restore_init_kernel(K);
+    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no restore_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
+    if (!c->guides_valid && (rc = hr_render_guides(c))) return rc;   // (base 1 never comes here: a valid D has valid guides)
+    const size_t pixels = region_pixels(c);
+    if (!c->restored && (rc = plane_alloc(c, RESTORED))) return rc;
+    CallScratch scratch;
+    double *cx = nullptr, *S = nullptr, *xp[2] = {nullptr, nullptr};
+    HIP_TRY_AS(who, scratch.alloc((void **)&cx, pixels * 6 * sizeof(double)));
+    if (p.levels) {
+        HIP_TRY_AS(who, scratch.alloc((void **)&S, pixels * 3 * sizeof(double)));
+        for (uint32_t k = 0; k < (p.levels > 1u ? 2u : 1u); k++) HIP_TRY_AS(who, scratch.alloc((void **)&xp[k], pixels * 3 * sizeof(double)));
+    }
+    invalidate_restored(c);
+    const DenoiseSigmas sg = denoise_sigmas(1.0, p.sigma_n, p.sigma_a, p.sigma_z);
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
+    hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, cx, pixels);
+    const double *X = cx + 3;
+    uint32_t xs = 6;
+    for (uint32_t l = 0; l < p.levels; l++) {
+        hipLaunchKernelGGL(spread_norm_kernel, tiles2d, dim3(32, 8), 0, c->stream, X, xs, c->guides, S, c->RW, c->RH, 1u << l, sg);
+        hipLaunchKernelGGL(spread_gather_kernel, tiles2d, dim3(32, 8), 0, c->stream, S, c->guides, xp[l & 1u], c->RW, c->RH, 1u << l, sg);
+        X = xp[l & 1u]; xs = 3;
+    }
+    hipLaunchKernelGGL(restore_final_kernel, flat, dim3(256), 0, c->stream, cx, p.base ? c->denoised : (const float *)nullptr, X, xs, c->restored, (uint32_t)pixels);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
+    c->restored_valid = true;
+    c->restored_on_d = p.base == 1u;
+    return drain_events(c);
+}
+// R' of the last hr_robust_restore, while nothing it was made of has changed (`who`: the entry point)
+static int restored_ready(hr_ctx *c, const char *who, const void *host) {
+    if (!c || !host) return fail(HR_ERR_INVALID, "%s: null argument", who);
+    if (!c->restored || !c->restored_valid) return fail(HR_ERR_INVALID, "%s: no restored image (hr_robust_restore first; anything that changes its inputs invalidates it)", who);
+    return HR_OK;
+}
+int hr_read_restored(hr_ctx *c, float *host) {
+    int rc = restored_ready(c, "hr_read_restored", host);
+    return rc ? rc : plane_read(c, RESTORED, c->restored, host);
+}
+int hr_resolve_restored(hr_ctx *c, uint8_t *host_rgb8) {
+    int rc = restored_ready(c, "hr_resolve_restored", host_rgb8);
+    return rc ? rc : resolve_region(c, 0, host_rgb8, c->restored);
 }
 
 int hr_get_stats(hr_ctx *c, hr_stats *out) {
@@ -2476,7 +2567,7 @@ static int set_robust_buckets(hr_ctx *c, double value) {
     invalidate_robust(c);
     c->robust_on = false;
     c->robust_k = 0;
-    if ((rc = plane_free(c, BUCKETS)) || (rc = plane_free(c, ROBUST)) || (rc = plane_free(c, ROBUST_TRIM)) || (rc = plane_free(c, ROBUST_NOISE_IMG)) || (rc = plane_free(c, ROBUST_NOISE_TRIM))) return rc;
+    if ((rc = plane_free(c, BUCKETS)) || (rc = plane_free(c, ROBUST)) || (rc = plane_free(c, ROBUST_TRIM)) || (rc = plane_free(c, ROBUST_NOISE_IMG)) || (rc = plane_free(c, ROBUST_NOISE_TRIM)) || (rc = plane_free(c, RESTORED))) return rc;
     if (value == 0) return HR_OK;
     c->robust_k = (uint32_t)value;
     if ((rc = plane_alloc(c, BUCKETS))) { (void)plane_free(c, BUCKETS); c->robust_k = 0; return rc; }

@@ -248,3 +248,16 @@ static const RobustDenoiseInitVariant ROBUST_DENOISE_INIT_VARIANTS[] = {
 static const RobustDenoiseInitVariant *select_robust_denoise_init_kernel(uint32_t k) {
     return find_row(ROBUST_DENOISE_INIT_VARIANTS, [&](const RobustDenoiseInitVariant &r) { return r.k == k; });
 }
+
+// ---- restore_init_kernel<K> (post_kernels.h): the init pass of hr_robust_restore, {C, X} of every pixel, one row per K ----
+// It stages a workgroup's span through lds() bytes of dynamic LDS as the two families above do (robust_stage_span; create_resources raises the limit).
+typedef void (*RestoreInitFn)(const double *, const uint32_t *, unsigned long long, double *, size_t);
+struct RestoreInitVariant { uint32_t k; RestoreInitFn fn; uint32_t lds() const { return 256u * 3u * k * (uint32_t)sizeof(double); } };
+static const RestoreInitVariant RESTORE_INIT_VARIANTS[] = {
+    HR_VARIANT(restore_init_kernel, 3),  HR_VARIANT(restore_init_kernel, 5),  HR_VARIANT(restore_init_kernel, 7),  HR_VARIANT(restore_init_kernel, 9),
+    HR_VARIANT(restore_init_kernel, 11), HR_VARIANT(restore_init_kernel, 13), HR_VARIANT(restore_init_kernel, 15),
+};
+// K as option robust_buckets has it
+static const RestoreInitVariant *select_restore_init_kernel(uint32_t k) {
+    return find_row(RESTORE_INIT_VARIANTS, [&](const RestoreInitVariant &r) { return r.k == k; });
+}

@@ -5,6 +5,7 @@
 #include "denoise_core.h"
 #include "device_scene.h"
 #include "post_core.h"
+#include "restore_core.h"
 #include "robust_core.h"
 
 using namespace hr;
@@ -157,4 +158,38 @@ __global__ __launch_bounds__(256) void robust_noise_kernel(const double *__restr
         o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
         o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
     }
+}
+
+// The restored robust resolve R' (restore_core.h).  The kernels carry no arithmetic of their own: every value is the core's.
+// restore_init_kernel<K>: the shape of robust_denoise_init_kernel — one workgroup per span of 256 pixels, the span through robust_stage_span's LDS —,
+// {C, X} of the pixel into the call-scoped plane of 6 doubles per pixel.  counts == nullptr: every pixel has n_all samplings.
+template <uint32_t K>
+__global__ __launch_bounds__(256) void restore_init_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all,
+                                                           double *__restrict__ cx, size_t pixels) {
+    const size_t base = (size_t)blockIdx.x * 256u, i = base + threadIdx.x;
+    const double *B = robust_stage_span<K>(buckets, base, pixels);
+    if (i >= pixels) return;
+    uint8_t t;
+    robust_pixel_excess_k<K>(B, counts ? (uint64_t)counts[i] : (uint64_t)n_all, cx + i * 6, &t);
+}
+// One level of the spread, two launches, one thread per pixel, every element one writer, no atomics: S = X / N (X: xs doubles from one pixel to the
+// next), then X' as the gather of S.  A pixel's guides are two 16-byte loads per tap (restore_guides).
+__global__ __launch_bounds__(256) void spread_norm_kernel(const double *__restrict__ X, uint32_t xs, const float *__restrict__ guides, double *__restrict__ S, uint32_t W, uint32_t H,
+                                                          uint32_t step, DenoiseSigmas sg) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= W || y >= H) return;
+    restore_norm(X, xs, guides, W, H, x, y, step, sg, S + ((size_t)y * W + x) * 3);
+}
+__global__ __launch_bounds__(256) void spread_gather_kernel(const double *__restrict__ S, const float *__restrict__ guides, double *__restrict__ out, uint32_t W, uint32_t H,
+                                                            uint32_t step, DenoiseSigmas sg) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= W || y >= H) return;
+    restore_gather(S, guides, W, H, x, y, step, sg, out + ((size_t)y * W + x) * 3);
+}
+// R' = (float)(base + X_L): base C of the init plane, or D != nullptr: the denoised robust radiance
+__global__ __launch_bounds__(256) void restore_final_kernel(const double *__restrict__ cx, const float *__restrict__ D, const double *__restrict__ X, uint32_t xs,
+                                                            float *__restrict__ restored, uint32_t pixels) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    restore_final(cx + (size_t)i * 6, D ? D + (size_t)i * 3 : nullptr, X + (size_t)i * xs, restored + (size_t)i * 3);
 }

@@ -17,7 +17,9 @@
 // hr_resolve_robust; the buckets ride in the checkpoint behind the other trailers),
 // --robust-noise (with --robust: --noise-target, --adaptive and --noise-image judge the robust image by the spread of its bucket means,
 // hr_robust_noise_estimate / hr_select_tiles_robust / hr_read_robust_noise_image), --robust-denoise (with --robust: the FINAL
-// image is the a-trous filter's over the robust radiance and its bucket-spread variance, hr_denoise_robust + hr_resolve_denoised).
+// image is the a-trous filter's over the robust radiance and its bucket-spread variance, hr_denoise_robust + hr_resolve_denoised),
+// --robust-restore / --restore-levels N (with --robust: the FINAL image is the robust radiance — with --robust-denoise the denoised one — plus the
+// trimmed buckets' excess spread along the guide planes, hr_robust_restore + hr_resolve_restored).
 // The file is in main's order: Options and parse_options (everything that can be refused before a device is opened), then Run, whose members
 // are main's steps.  The checkpoint's format is host/checkpoint.h's; what a render demands of a file is said in Run::resume.
 #include <algorithm>
@@ -127,7 +129,15 @@ static void usage(const char *prog) {
            "                        write the FINAL image through the a-trous filter on the robust radiance (hr_denoise_robust: --denoise's filter, fed\n"
            "                        with the trimmed mean of the K bucket means and the winsorized variance of their spread instead of the raw moments;\n"
            "                        progress images stay --robust's).  --denoise-levels, --guide-bounces and --guide-image work as with --denoise.  A\n"
-           "                        pixel with fewer than K samplings: the robust image is written unfiltered.  Needs --robust.\n",
+           "                        pixel with fewer than K samplings: the robust image is written unfiltered.  Needs --robust.\n"
+           "        --robust-restore\n"
+           "                        write the FINAL image with the energy the robust resolve drops given back (hr_robust_restore: what the trimmed hot\n"
+           "                        buckets hold above the highest kept one is spread over the neighbourhood along the guide planes and added; the image\n"
+           "                        keeps the brightness of the plain mean at a larger error than --robust alone; progress images stay --robust's).\n"
+           "                        With --robust-denoise the excess goes on top of the denoised image.  --guide-bounces works as with --denoise.  A\n"
+           "                        pixel with fewer than K samplings: the image is written unrestored.  Needs --robust.\n"
+           "        --restore-levels N\n"
+           "                        spread levels, 0 .. 5 (default 4; the taps of level l are 2^l pixels apart).  Needs --robust-restore.\n",
            prog);
 }
 
@@ -155,6 +165,8 @@ struct Options {
     std::string robust_png;
     bool robust_noise = false;       // --robust-noise: the noise questions are asked of the buckets (e_R), not of the moments
     bool robust_denoise = false;     // --robust-denoise: the final image is hr_denoise_robust's
+    bool robust_restore = false;     // --robust-restore: the final image is hr_robust_restore's
+    long long restore_levels = -1;   // -1: the library's default
     // what the flags add up to:
     bool counts = false, moments = false;   // hr_set_option "sample_counts", "moments"
     double noise_e = 0.05;                  // the threshold of "above" and of the grey map
@@ -259,6 +271,10 @@ static int parse_options(int argc, char **argv, Options &o) {
         } else if (a == "--robust-image") o.robust_png = val("robust-image");
         else if (a == "--robust-noise") o.robust_noise = true;
         else if (a == "--robust-denoise") o.robust_denoise = true;
+        else if (a == "--robust-restore") o.robust_restore = true;
+        else if (a == "--restore-levels") {
+            if (!whole("--restore-levels", val("restore-levels"), 0, 5, 1, "a whole number in 0 .. 5", &o.restore_levels)) return 1;
+        }
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
     if (o.batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
@@ -273,8 +289,10 @@ static int parse_options(int argc, char **argv, Options &o) {
         if (o.debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
     }
     if (o.robust_denoise && !o.robust_k) { fprintf(stderr, "--robust-denoise needs --robust (it filters the robust radiance by the spread of the sample buckets).\n"); return 1; }
+    if (o.robust_restore && !o.robust_k) { fprintf(stderr, "--robust-restore needs --robust (it gives back the energy the robust resolve drops).\n"); return 1; }
+    if (o.restore_levels >= 0 && !o.robust_restore) { fprintf(stderr, "--restore-levels needs --robust-restore.\n"); return 1; }
     if (o.denoise_levels >= 0 && !o.denoise && !o.robust_denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
-    if (o.guide_bounces >= 0 && !o.denoise && !o.robust_denoise && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
+    if (o.guide_bounces >= 0 && !o.denoise && !o.robust_denoise && !o.robust_restore && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
     if (o.denoise || !o.guide_prefix.empty()) {
         if (!one_device(o, "--denoise / --guide-image render on one device: the library denoises one context's accumulator, moments and counts (a sharded host sums them into one), this program's device loop does not.")) return 1;
         if (o.debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
@@ -431,14 +449,25 @@ int Run::combine() {
 // host-side sum: device 0 resolves the total from its accumulator, then gets its own partial sums back
 int Run::resolve(uint32_t s, uint8_t *out) {
     if (o.robust_k) {   // (one device, no --denoise: checked with the flags)
+        bool denoised = false;
         if (o.robust_denoise && final_image) {
             hr_denoise_params dp;
             if (hr_denoise_default_params(&dp) != 0) return 1;
             if (o.denoise_levels >= 0) dp.levels = (uint32_t)o.denoise_levels;
             const int rc = hr_denoise_robust(ctx, &dp);   // (HR_ERR_INVALID: a pixel with fewer than K samplings — the flags' values were checked when they were read)
-            if (rc == 0) { have_guides = true; return hr_resolve_denoised(ctx, out); }   // (it rendered the guide planes, nothing has dropped them since)
+            if (rc == 0) { have_guides = true; denoised = true; if (!o.robust_restore) return hr_resolve_denoised(ctx, out); }   // (it rendered the guide planes, nothing has dropped them since)
+            else if (rc != HR_ERR_INVALID) return rc;
+            else tee("robust-denoise: fewer than K samplings behind a pixel, the robust image is not denoised.");
+        }
+        if (o.robust_restore && final_image) {   // on top of D when there is one, else of the robust radiance
+            hr_restore_params rp;
+            if (hr_restore_default_params(&rp) != 0) return 1;
+            if (o.restore_levels >= 0) rp.levels = (uint32_t)o.restore_levels;
+            rp.base = denoised ? 1u : 0u;
+            const int rc = hr_robust_restore(ctx, &rp);   // (HR_ERR_INVALID: a pixel with fewer than K samplings)
+            if (rc == 0) { have_guides = true; return hr_resolve_restored(ctx, out); }
             if (rc != HR_ERR_INVALID) return rc;
-            tee("robust-denoise: fewer than K samplings behind a pixel, the robust image is not denoised.");
+            tee("robust-restore: fewer than K samplings behind a pixel, the robust image is not restored.");
         }
         return hr_robust(ctx) != 0 ? 1 : hr_resolve_robust(ctx, out);
     }

@@ -85,6 +85,10 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_double), ("sigma_normal", C.c_double), ("sigma_albedo", C.c_double), ("sigma_depth", C.c_double)]
 
 
+class RestoreParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("base", C.c_uint32), ("sigma_n", C.c_double), ("sigma_a", C.c_double), ("sigma_z", C.c_double)]
+
+
 COMM_PATHS = {0: "none", 1: "rccl-rank", 2: "rccl-group", 3: "same-device-fallback"}
 
 
@@ -216,6 +220,10 @@ def hip_lib():
         L.hr_read_robust_noise_trim.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.hr_select_tiles_robust.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint32)]
         L.hr_denoise_robust.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)]
+        L.hr_restore_default_params.argtypes = [C.POINTER(RestoreParams)]
+        L.hr_robust_restore.argtypes = [C.c_void_p, C.POINTER(RestoreParams)]
+        L.hr_read_restored.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_resolve_restored.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_fold_statistics.argtypes = [C.c_void_p]
         L.hr_fold_statistics_group.argtypes = [C.POINTER(C.c_void_p), C.c_int]
         _hip = L
@@ -286,6 +294,16 @@ def fold_statistics(renderers):
 
 class HostError(RuntimeError):
     pass
+
+
+def restore_default_params():
+    """hr_restore_default_params: the documented defaults as a RestoreParams (needs no device)."""
+    L = hip_lib()
+    p = RestoreParams()
+    rc = L.hr_restore_default_params(C.byref(p))
+    if rc != 0:
+        raise HipError(rc, L.hr_last_error().decode())
+    return p
 
 
 class HipError(RuntimeError):
@@ -362,7 +380,7 @@ def load_obj(path, matrix=None):
 _PLANES = {
     "accumulator": ((3,), np.float32), "rgb8": ((3,), np.uint8), "moments": ((6,), np.float64), "noise": ((), np.float64),
     "sample_counts": ((), np.uint32), "guides": ((8,), np.float32), "denoised": ((3,), np.float32), "buckets": ((3,), np.float64),
-    "robust": ((3,), np.float32), "robust_trim": ((), np.uint8),
+    "robust": ((3,), np.float32), "robust_trim": ((), np.uint8), "restored": ((3,), np.float32),
 }
 
 
@@ -641,6 +659,25 @@ class Renderer:
     def resolve_robust(self):
         """hr_resolve_robust: resolve() of the robust radiance."""
         return self._read_plane(self.L.hr_resolve_robust, "rgb8")
+
+    # ---- the restored robust resolve (include/hanamaru_hip.h)
+    def robust_restore(self, **params):
+        """hr_robust_restore: R' = base + the trimmed buckets' excess spread along the guide planes; the defaults, with any of levels, base,
+        sigma_n, sigma_a, sigma_z replaced (base 1: on top of the D of denoise_robust())."""
+        p = restore_default_params()
+        for k, v in params.items():
+            if k not in dict(RestoreParams._fields_):
+                raise TypeError("robust_restore() has no parameter %r" % k)
+            setattr(p, k, v)
+        self._check(self.L.hr_robust_restore(self._h, C.byref(p)))
+
+    def read_restored(self):
+        """hr_read_restored: (h, w, 3) float32 radiance."""
+        return self._read_plane(self.L.hr_read_restored, "restored")
+
+    def resolve_restored(self):
+        """hr_resolve_restored: resolve() of the restored robust radiance."""
+        return self._read_plane(self.L.hr_resolve_restored, "rgb8")
 
     # ---- the robust noise estimate of the buckets, and the selection of tiles by it (include/hanamaru_hip.h)
     def robust_noise_estimate(self, floor=0.01, threshold=0.05):

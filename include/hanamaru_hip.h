@@ -495,6 +495,34 @@ int hr_select_tiles_robust(hr_ctx *ctx, double floor, double threshold, uint32_t
  *     the buckets, the accumulator, the moments nor the counts. */
 int hr_denoise_robust(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */);
 
+/* ---- the restored robust resolve R' (csrc/restore_core.h is the definition) -------------------------------------------------------
+ * R is biased dark where it trims: a trimmed bucket's energy is gone.  R' gives it back without giving the hot pixel back: per pixel and channel the
+ * excess X = what the t hot buckets hold above the highest kept bucket mean, over K (robust_pixel_excess_k: never negative, 0 where nothing is
+ * trimmed), is spread over `levels` a-trous levels along the guide planes — each pixel hands X w(p,q) / sum_q w(p,q) to its 5 x 5 taps, w the
+ * denoiser's tap weight without its colour term (h K(x_n) K(x_a) K(x_z) K(x_h)), written as a gather since w is symmetric to the bit — and added:
+ * R'_c = (float)(base_c + X_L,c).  base 0: C, the robust radiance before its rounding; base 1: D of hr_denoise_robust.  All f64, + - x / max only:
+ * the device, the header under a host compiler and a numpy restatement agree bit for bit.
+ *   - Needs "robust_buckets" != 0; works on the region and with "sample_counts" (every pixel's own n); renders the guide planes itself
+ *     (hr_render_guides) when there are none; synchronises; its time goes to hr_stats.post_kernel_ms.
+ *   - HR_ERR_INVALID, with R', R, D, the buckets, the counts and the mask exactly as they were: the option off; a pixel of the region with fewer
+ *     than K samplings; a count beyond the samplings behind the buckets; levels > 5; a sigma that is not positive and finite; base > 1; base 1
+ *     without a valid D made by hr_denoise_robust.
+ *   - R' is valid until anything that invalidates a D of hr_denoise_robust happens (hr_render, hr_render_debug, hr_clear, every hr_write_*,
+ *     hr_render_guides, "guide_bounces", switching "robust_buckets", "moments" or "sample_counts", the target), and with base 1 until a new D is
+ *     made.  The call touches neither R's nor D's validity, nor the buckets, nor the accumulator.  hr_read_restored and hr_resolve_restored return
+ *     HR_ERR_INVALID without a valid R'.
+ *   - levels = 0, base 0: R' = (float)(C + X); where no pixel trims R' is R bit for bit and hr_resolve_restored gives hr_resolve_robust's bytes.
+ *   - What it is not: X is noisy — it is the firefly energy itself — so R' has a larger error than R (DESIGN.md 4.14 has the measured rows). */
+typedef struct hr_restore_params {
+    uint32_t levels;   /* 0..5 */
+    uint32_t base;     /* 0: the robust radiance | 1: the denoised robust radiance of hr_denoise_robust */
+    double sigma_n, sigma_a, sigma_z;
+} hr_restore_params;
+int hr_restore_default_params(hr_restore_params *out);     /* 4, 0, 0.5, 0.25, 0.1 */
+int hr_robust_restore(hr_ctx *ctx, const hr_restore_params *p /* NULL = defaults */);
+int hr_read_restored(hr_ctx *ctx, float *host /* w*h*3 radiance */);
+int hr_resolve_restored(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on R' with scale 1.0f */
+
 /* ---- sharded statistics: buckets by sampling, and the fold into rank 0 ----------------------------------------------------------
  * Contexts that shard the samplings (hr_render's stride) each hold a share of every additive plane.  hr_fold_statistics moves the shares to
  * rank 0 of the communicator, so that ONE context answers every question with the functions above, unchanged: hr_noise_estimate,

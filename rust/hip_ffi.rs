@@ -33,6 +33,8 @@ pub const HR_MESH: i32 = 2;
 /// hr_denoise_params: the a-trous denoiser's parameters (hr_denoise_default_params fills in the defaults)
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrDenoiseParams { pub levels: u32, pub demodulate: u32, pub sigma_color: f64, pub sigma_normal: f64,
                                                                          pub sigma_albedo: f64, pub sigma_depth: f64 }
+/// hr_restore_params: the restored robust resolve's parameters (hr_restore_default_params fills in the defaults)
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrRestoreParams { pub levels: u32, pub base: u32, pub sigma_n: f64, pub sigma_a: f64, pub sigma_z: f64 }
 pub enum HrCtx {}
 
 extern "C" {
@@ -111,6 +113,11 @@ extern "C" {
     pub fn hr_select_tiles_robust(ctx: *mut HrCtx, floor: f64, threshold: f64, active: *mut u32) -> c_int;
     // hr_denoise's filter on the robust radiance and its bucket-spread variance; D is hr_read_denoised's / hr_resolve_denoised's
     pub fn hr_denoise_robust(ctx: *mut HrCtx, p: *const HrDenoiseParams /* null = defaults */) -> c_int;
+    // the restored robust resolve R' = base + the trimmed buckets' excess spread along the guide planes (base 0: R before rounding, 1: D of hr_denoise_robust)
+    pub fn hr_restore_default_params(out: *mut HrRestoreParams) -> c_int;
+    pub fn hr_robust_restore(ctx: *mut HrCtx, p: *const HrRestoreParams /* null = defaults */) -> c_int;
+    pub fn hr_read_restored(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 */) -> c_int;
+    pub fn hr_resolve_restored(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
     // every additive plane (accumulator, moments, counts, buckets filled under option "bucket_by_sampling" 1) moves to rank 0, which then answers
     pub fn hr_fold_statistics(ctx: *mut HrCtx) -> c_int;
     pub fn hr_fold_statistics_group(ctxs: *mut *mut HrCtx, n: c_int) -> c_int;
@@ -129,6 +136,7 @@ const _: () = assert!(std::mem::size_of::<HrSceneDesc>() == 248 && std::mem::ali
 const _: () = assert!(std::mem::size_of::<HrCommInfo>() == 32 && std::mem::align_of::<HrCommInfo>() == 8);   // hr_comm_info_t
 const _: () = assert!(std::mem::size_of::<HrNoise>() == 40 && std::mem::align_of::<HrNoise>() == 8);   // hr_noise
 const _: () = assert!(std::mem::size_of::<HrDenoiseParams>() == 40 && std::mem::align_of::<HrDenoiseParams>() == 8);   // hr_denoise_params
+const _: () = assert!(std::mem::size_of::<HrRestoreParams>() == 32 && std::mem::align_of::<HrRestoreParams>() == 8);   // hr_restore_params
 const _: () = assert!(std::mem::size_of::<Vector3>() == 24);   // hr_vec3
 #[cfg(test)]
 mod layout {
@@ -191,6 +199,11 @@ mod layout {
         assert_eq!(off!(HrDenoiseParams, sigma_normal), 16);
         assert_eq!(off!(HrDenoiseParams, sigma_albedo), 24);
         assert_eq!(off!(HrDenoiseParams, sigma_depth), 32);
+        assert_eq!(off!(HrRestoreParams, levels), 0);
+        assert_eq!(off!(HrRestoreParams, base), 4);
+        assert_eq!(off!(HrRestoreParams, sigma_n), 8);
+        assert_eq!(off!(HrRestoreParams, sigma_a), 16);
+        assert_eq!(off!(HrRestoreParams, sigma_z), 24);
     }
 }
 // ---- END GENERATED ----
