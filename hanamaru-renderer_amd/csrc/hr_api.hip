@@ -17,6 +17,7 @@
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
 // The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane, robust noise image and its trim plane, restored robust image) are rows of one
 // table, PLANES, with one set of routines for their bytes, life cycle, zeroing and host copies; scratch a call needs lives in a CallScratch.
+// The images made of them and kept for later reads (guides, D, R, R') are rows of a second table, IMAGES: what each goes stale with, and one check for its reads.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -96,6 +97,10 @@ struct CallScratch {
 
 struct EventPair { hipEvent_t a, b; };
 
+// What a derived image (IMAGES, behind the planes) can be made of: a call that changes one of these says so to changed().
+enum : uint32_t { SRC_ACCUM = 1, SRC_MOMENTS = 2, SRC_COUNTS = 4, SRC_BUCKETS = 8, SRC_GUIDES = 16, SRC_SCENE = 32, SRC_TARGET = 64, SRC_NEW_D = 128 };
+enum ImageId { GUIDE_IMAGE, D_IMAGE, R_IMAGE, RESTORED_IMAGE, N_IMAGES };
+
 struct hr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -123,14 +128,13 @@ struct hr_ctx {
     bool counts_on = false;
     uint32_t *counts = nullptr;
     // the denoiser: the guide planes {albedo rgb, normal xyz, depth, coverage} of the region — rendered by hr_render_guides or written
-    // by the host — and the denoised radiance D of the last hr_denoise, valid until anything it was made of changes (invalidate_denoised)
+    // by the host — and the denoised radiance D of the last hr_denoise or hr_denoise_robust
     float *guides = nullptr, *denoised = nullptr;
-    bool guides_valid = false, denoised_valid = false;
-    bool denoised_by_robust = false;   // D was made by hr_denoise_robust: switching robust_buckets invalidates it as well
+    // the derived images' validity (IMAGES): the sources the image in place goes stale with, as it was made; 0: there is none
+    uint32_t made_of[N_IMAGES] = {};
     uint32_t guide_bounces = 0;   // option "guide_bounces": mirrors and glass the guide rays follow to the first non-delta hit (0: the first hit's planes)
     // option "robust_buckets" = K: per pixel K x 3 sums of the per-sampling values, sampling j of a pixel in bucket j mod K
-    // (bucket_kernel), the samplings behind them, and the robust radiance R with its trim plane of the last hr_robust, valid until anything it was
-    // made of changes (invalidate_robust)
+    // (bucket_kernel), the samplings behind them, and the robust radiance R with its trim plane of the last hr_robust
     bool robust_on = false;
     uint32_t robust_k = 0;
     bool bucket_by_sampling = false;   // option "bucket_by_sampling" (DESIGN.md §4.13): sampling s in bucket (s - 1) mod K, so that shards add up (hr_fold_statistics)
@@ -138,11 +142,8 @@ struct hr_ctx {
     uint64_t buckets_n = 0;
     float *robust = nullptr;
     uint8_t *robust_trim = nullptr;
-    bool robust_valid = false;
-    // the restored robust radiance R' of the last hr_robust_restore, valid until anything it was made of changes: the buckets, the
-    // counts, the guides, the target (invalidate_restored) — and, when its base was D (restored_on_d), a new D
+    // the restored robust radiance R' of the last hr_robust_restore
     float *restored = nullptr;
-    bool restored_valid = false, restored_on_d = false;
     // the robust noise estimate: e_R of every pixel and the trim behind it, as the last estimate or selection left them (allocated
     // when one is first asked for; every call that reads them has just written them)
     double *robust_noise_img = nullptr;
@@ -363,18 +364,15 @@ static int govern_reset(hr_ctx *c) {
     HIP_TRY(hipMemcpy(c->gov, &h, sizeof h, hipMemcpyHostToDevice));
     return HR_OK;
 }
-// the accumulator of `c` is about to change: totals that include it are stale — its own and, in a same-device group, its peers'
-static void invalidate_totals(hr_ctx *c) {
-    c->total_valid = false;
-    for (hr_ctx *p : c->same_device_peers) p->total_valid = false;
+// `sources` of `c` are about to change: every derived image made of one of them is stale, and with the accumulator the totals
+// that include it — its own and, in a same-device group, its peers'
+static void changed(hr_ctx *c, uint32_t sources) {
+    if (sources & SRC_ACCUM) {
+        c->total_valid = false;
+        for (hr_ctx *p : c->same_device_peers) p->total_valid = false;
+    }
+    for (uint32_t &made_of : c->made_of) if (made_of & sources) made_of = 0;
 }
-// the accumulator, the moments, the counts or the guides of `c` are about to change, or its target: the denoised image is no longer theirs
-// (everything D is made of, R' is made of or may be: R' goes with it; a NEW D takes only an R' that was based on D — new_denoised)
-static void invalidate_restored(hr_ctx *c) { c->restored_valid = false; }
-static void invalidate_denoised(hr_ctx *c) { c->denoised_valid = false; invalidate_restored(c); }
-static void new_denoised(hr_ctx *c) { c->denoised_valid = false; if (c->restored_on_d) invalidate_restored(c); }
-// the same for the robust radiance: the buckets or the counts of `c` are about to change, its accumulator or its target
-static void invalidate_robust(hr_ctx *c) { c->robust_valid = false; invalidate_restored(c); }
 static int drain_events(hr_ctx *c) {
     auto sum = [](std::vector<EventPair> &ev, double &acc) -> hipError_t {
         // a pair whose query fails is dropped with the rest (left in the list it would fail every later drain, i.e. every later API call)
@@ -546,9 +544,8 @@ static int plane_write(hr_ctx *c, const Plane &p, void *dev, const void *host) {
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
     if (rc) return rc;
-    if (dev == c->accum) invalidate_totals(c);
-    invalidate_denoised(c);   // every plane a host can write is one the denoised image is made of
-    if (dev != c->guides) invalidate_robust(c);   // (the guide planes are none of the robust radiance's inputs)
+    // (conservative, kept: a write of one statistics plane counts as a write of all three)
+    changed(c, dev == c->guides ? SRC_GUIDES : (dev == c->accum ? SRC_ACCUM : 0u) | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS);
     HIP_TRY(hipMemcpy(dev, host, plane_bytes(c, p), hipMemcpyHostToDevice));
     return HR_OK;
 }
@@ -567,6 +564,36 @@ static int option_plane_write(hr_ctx *c, const Plane &p, const char *who, const 
     int rc = plane_ready(c, p, who);
     if (!rc && !host) rc = fail(HR_ERR_INVALID, "%s: null argument", who);
     return rc ? rc : plane_write(c, p, *p.slot(c), host);
+}
+
+// ------------------------------------------------------------------------------------------ derived images
+// What is made of the planes and kept until one of its sources changes: its plane(s), the sources it goes stale with whoever made
+// it — the maker adds what was decided when it was made (hr_ctx::made_of) —, the option its reads ask for first, and what they say when there is
+// none.  Every call that changes a source says so to changed(); nothing else clears made_of.  "kept": more than the data flow needs, as it always was.
+struct Image {
+    const Plane *plane, *second;   // (second: R's trim plane)
+    uint32_t stale_with;
+    const Plane *option;
+    const char *none;
+};
+static const Image IMAGES[N_IMAGES] = {
+    {&GUIDES, nullptr, SRC_GUIDES | SRC_SCENE | SRC_TARGET, nullptr, "no guide planes (hr_render_guides or hr_write_guides first)"},
+    // D: + SRC_MOMENTS made by hr_denoise, + SRC_BUCKETS made by hr_denoise_robust (for that one the accumulator is kept)
+    {&DENOISED, nullptr, SRC_ACCUM | SRC_COUNTS | SRC_GUIDES | SRC_SCENE | SRC_TARGET | SRC_NEW_D, nullptr, "no denoised image (hr_denoise first; anything that changes its inputs invalidates it)"},
+    {&ROBUST, &ROBUST_TRIM, SRC_COUNTS | SRC_BUCKETS | SRC_TARGET, &BUCKETS, "no robust image (hr_robust first; anything that changes its inputs invalidates it)"},
+    // R': + SRC_NEW_D made on D (base 1); the accumulator is kept
+    {&RESTORED, nullptr, SRC_ACCUM | SRC_COUNTS | SRC_BUCKETS | SRC_GUIDES | SRC_SCENE | SRC_TARGET, nullptr, "no restored image (hr_robust_restore first; anything that changes its inputs invalidates it)"},
+};
+static bool image_valid(const hr_ctx *c, ImageId id) { return c->made_of[id] != 0; }
+static void image_made(hr_ctx *c, ImageId id, uint32_t decided = 0) { c->made_of[id] = IMAGES[id].stale_with | decided; }
+// the image of an entry point that reads it (`who`): the option first where it has one, then the arguments, then the image itself
+static int image_ready(hr_ctx *c, ImageId id, const char *who, const void *host) {
+    const Image &im = IMAGES[id];
+    int rc;
+    if (im.option && (rc = plane_ready(c, *im.option, who))) return rc;
+    if (!c || !host) return fail(HR_ERR_INVALID, "%s: null argument", who);
+    if (!*im.plane->slot(c) || (im.second && !*im.second->slot(c)) || !image_valid(c, id)) return fail(HR_ERR_INVALID, "%s: %s", who, im.none);
+    return HR_OK;
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -861,8 +888,7 @@ int hr_upload_scene(hr_ctx *c, const hr_scene_desc *sd) {
     rc = flatten_scene(sd, hs, ferr, c->max_leaf, gpu_build ? 0.0 : c->split_ratio, !gpu_build);
     if (rc) return fail(rc, "hr_upload_scene: %s", ferr.c_str());   // a description that is refused leaves the scene in place
     free_scene(c);
-    c->guides_valid = false;   // the guide planes show the scene that goes
-    invalidate_denoised(c);
+    changed(c, SRC_SCENE);   // the guide planes show the scene that goes
     if ((rc = plane_free(c, GUIDES))) return rc;
     Scene &d = c->dsc;
     d = hs.view();
@@ -930,9 +956,7 @@ static int set_target(hr_ctx *c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y
     // no target while the buffers are being replaced (a failed allocation leaves the context without one, not with dangling
     // pointers); a caller-bound accumulator was sized for the old target: it is unbound, the caller rebinds
     c->accum = nullptr; c->W = c->H = 0; c->RX = c->RY = c->RW = c->RH = 0; c->total_valid = false;
-    c->guides_valid = false;
-    invalidate_denoised(c);
-    invalidate_robust(c);
+    changed(c, SRC_TARGET);
     unbind_accumulator(c);
     for (const Plane *p : PLANES) if ((rc = plane_free(c, *p))) return rc;
     if ((rc = remove_mask(c))) return rc;   // the mask is over the old region's tiles
@@ -1017,9 +1041,7 @@ int hr_bind_accumulator(hr_ctx *c, float *device_rgb) {
         if (device_rgb) g_bound[device_rgb] = std::make_pair((const hr_ctx *)c, bytes);
     }
     c->accum = device_rgb ? device_rgb : c->accum_own;
-    invalidate_totals(c);
-    invalidate_denoised(c);
-    invalidate_robust(c);
+    changed(c, SRC_ACCUM | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS);   // (conservative, kept: another accumulator counts as other statistics)
     return HR_OK;
 }
 void *hr_accumulator_device_ptr(hr_ctx *c) { return c ? c->accum : nullptr; }
@@ -1039,9 +1061,7 @@ int hr_clear(hr_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
     if (rc) return rc;
-    invalidate_totals(c);
-    invalidate_denoised(c);
-    invalidate_robust(c);
+    changed(c, SRC_ACCUM | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS);
     // the planes the table marks, the accumulator through c->accum (it may be the caller's bound buffer); the tile mask stays: a setting, like the region
     for (const Plane *p : PLANES)
         if (p->at_clear && (rc = plane_zero(c, *p, c->stream, p == &ACCUM_OWN ? c->accum : nullptr))) return rc;
@@ -1250,9 +1270,7 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
     if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_render: hr_set_resolution not called");
     if (s_end <= s_begin) return HR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    invalidate_totals(c);
-    invalidate_denoised(c);
-    invalidate_robust(c);
+    changed(c, SRC_ACCUM | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS);
     if (c->precise_opt == 1 && c->rr_start) return fail(HR_ERR_UNSUPPORTED, "hr_render: russian_roulette and precise_shading exclude each other (the roulette estimator has no f64 instantiation)");
     const uint32_t total_k = (s_end - s_begin + stride - 1) / stride;
     const bool list = c->mask_on;
@@ -1367,8 +1385,7 @@ int hr_render_debug(hr_ctx *c, int mode) {
     if (c->counts_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option sample_counts on (a debug sampling goes into the accumulator without being counted)");
     if (c->robust_on) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: not with option robust_buckets on (a debug sampling goes into the accumulator without per-sampling values)");
     HIP_TRY(hipSetDevice(c->device));
-    invalidate_totals(c);
-    invalidate_denoised(c);
+    changed(c, SRC_ACCUM);   // (the accumulator alone: the three options are off)
     const DebugRenderFn fn = select_debug_render_kernel(c->counters, c->dsc.qnodes != nullptr);
     if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_debug: no kernel instantiation for these options (kernel_variants.h)");
     return launch_tile_pass(c, fn, mode, c->accum, c->d_counters);
@@ -1626,11 +1643,7 @@ static int fold_group_refusal(hr_ctx **ctxs, int n, const char *who) {
     return HR_OK;
 }
 // what holds on every rank after a fold: the planes changed hands, so nothing made of them stands
-static void fold_invalidate(hr_ctx *c) {
-    invalidate_totals(c);
-    invalidate_denoised(c);
-    invalidate_robust(c);
-}
+static void fold_invalidate(hr_ctx *c) { changed(c, SRC_ACCUM | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS); }
 // One device: for k = 1 .. n-1 in rank order root += peer_k, peer_k = 0, plane by plane — ((r0 + r1) + r2) .. to the bit.  Ordered as
 // allreduce_enqueue orders its sum: every context's render work is waited for, the kernels run on rank 0's stream, and they are finished
 // before the call returns (they write the PEERS' planes: a peer's next hr_render must not race with them).
@@ -1890,12 +1903,27 @@ static int counts_cover_an_estimate(hr_ctx *c, const char *who) {
         return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the moments cover %llu (the counts and the moments must cover the same samplings)", who, mm[1], (unsigned long long)c->moments_n);
     return HR_OK;
 }
+// the floor and the threshold of an estimate or a selection (`who`)
+static int floor_and_threshold_ok(const char *who, double floor, double threshold) {
+    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "%s: floor must be a positive finite radiance", who);
+    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
+    return HR_OK;
+}
+// the summary of an estimate from its kernel's block summaries h[block] = {sum, max, above}, added in index order
+static void noise_summary(const std::vector<double> &h, uint64_t samplings, size_t pixels, hr_noise *est) {
+    double sum = 0.0, mx = 0.0, above = 0.0;
+    for (size_t b = 0; b < h.size() / 3; b++) { sum += h[b * 3]; mx = h[b * 3 + 1] > mx ? h[b * 3 + 1] : mx; above += h[b * 3 + 2]; }
+    est->samplings = samplings;
+    est->pixels = (uint64_t)pixels;
+    est->pixels_above = (uint64_t)above;
+    est->mean_error = sum / (double)pixels;
+    est->max_error = mx;
+}
 // host_img: the image as well (or NULL); est: the summary (or NULL)
 static int noise_run(hr_ctx *c, const char *who, double floor, double threshold, double *host_img, hr_noise *est) {
     int rc = plane_ready(c, MOMENTS, who);
     if (rc) return rc;
-    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "%s: floor must be a positive finite radiance", who);
-    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
+    if ((rc = floor_and_threshold_ok(who, floor, threshold))) return rc;
     if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
     if ((rc = hr_synchronize(c))) return rc;
     if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;
@@ -1911,15 +1939,7 @@ static int noise_run(hr_ctx *c, const char *who, double floor, double threshold,
     HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (host_img) HIP_TRY_AS(who, hipMemcpyAsync(host_img, c->noise_img, plane_bytes(c, NOISE_IMG), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
-    if (est) {
-        double sum = 0.0, mx = 0.0, above = 0.0;
-        for (unsigned b = 0; b < NOISE_BLOCKS; b++) { sum += h[b * 3]; mx = h[b * 3 + 1] > mx ? h[b * 3 + 1] : mx; above += h[b * 3 + 2]; }
-        est->samplings = c->moments_n;
-        est->pixels = (uint64_t)pixels;
-        est->pixels_above = (uint64_t)above;
-        est->mean_error = sum / (double)pixels;
-        est->max_error = mx;
-    }
+    if (est) noise_summary(h, c->moments_n, pixels, est);
     return HR_OK;
 }
 int hr_noise_estimate(hr_ctx *c, double floor, double threshold, hr_noise *out) {
@@ -1996,20 +2016,18 @@ int hr_render_guides(hr_ctx *c) {
     int rc;
     if ((rc = debug_refusal(c, "hr_render_guides", A_SCENE)) || (rc = debug_refusal(c, "hr_render_guides", A_TARGET))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    invalidate_denoised(c);
-    c->guides_valid = false;
+    changed(c, SRC_GUIDES);
     if (!c->guides && (rc = plane_alloc(c, GUIDES))) return rc;
     const GuideRenderFn fn = select_guide_render_kernel(c->dsc.qnodes != nullptr);
     const GuideChainFn chain = select_guide_chain_kernel(c->dsc.qnodes != nullptr);
     if (c->guide_bounces ? !chain : !fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_guides: no kernel instantiation for this node format (kernel_variants.h)");
     if ((rc = c->guide_bounces ? launch_tile_pass(c, chain, c->guide_bounces, c->guides) : launch_tile_pass(c, fn, c->guides))) return rc;
-    c->guides_valid = true;
+    image_made(c, GUIDE_IMAGE);
     return HR_OK;
 }
 int hr_read_guides(hr_ctx *c, float *host) {
-    if (!c || !host) return fail(HR_ERR_INVALID, "hr_read_guides: null argument");
-    if (!c->guides || !c->guides_valid) return fail(HR_ERR_INVALID, "hr_read_guides: no guide planes (hr_render_guides or hr_write_guides first)");
-    return plane_read(c, GUIDES, c->guides, host);
+    int rc = image_ready(c, GUIDE_IMAGE, "hr_read_guides", host);
+    return rc ? rc : plane_read(c, GUIDES, c->guides, host);
 }
 int hr_write_guides(hr_ctx *c, const float *host) {
     if (!c || !host) return fail(HR_ERR_INVALID, "hr_write_guides: null argument");
@@ -2017,59 +2035,73 @@ int hr_write_guides(hr_ctx *c, const float *host) {
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if (!c->guides && (rc = plane_alloc(c, GUIDES))) return rc;
-    c->guides_valid = false;
-    if ((rc = plane_write(c, GUIDES, c->guides, host))) return rc;
-    c->guides_valid = true;
+    if ((rc = plane_write(c, GUIDES, c->guides, host))) return rc;   // (it says changed(SRC_GUIDES): the planes of before go with what was made of them)
+    image_made(c, GUIDE_IMAGE);
     return HR_OK;
 }
+// the parameters of a denoiser (`who`), or the defaults, checked into `p`
+static int denoise_params(const char *who, const hr_denoise_params *params, hr_denoise_params &p) {
+    if (params) p = *params;
+    else (void)hr_denoise_default_params(&p);
+    if (p.levels > DENOISE_MAX_LEVELS) return fail(HR_ERR_INVALID, "%s: levels must be in [0,%u]", who, DENOISE_MAX_LEVELS);
+    if (p.demodulate > 1u) return fail(HR_ERR_INVALID, "%s: demodulate must be 0 or 1", who);
+    for (double s : {p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth})
+        if (!(s > 0.0) || !(s < INFINITY)) return fail(HR_ERR_INVALID, "%s: every sigma must be positive and finite", who);
+    return HR_OK;
+}
+// The à-trous run of both denoisers (`who`), whose checks are done and whose guide planes are there: D from the {C, V} plane that `init(grid, cv,
+// demodulate)` — the caller's own launch on c->stream — fills, through p.levels levels and the final pass.  `made_of`: the source D is made of
+// besides what every D is (IMAGES).  The scratch planes go with the call.
+extern "C++" {   // (a template inside the C ABI's block)
+template <class Init>
+static int atrous_run(hr_ctx *c, const char *who, const hr_denoise_params &p, uint32_t made_of, Init init) {
+    int rc;
+    const size_t pixels = region_pixels(c);
+    if (!c->denoised && (rc = plane_alloc(c, DENOISED))) return rc;
+    CallScratch scratch;
+    double *cv[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++) HIP_TRY_AS(who, scratch.alloc((void **)&cv[k], pixels * 6 * sizeof(double)));
+    changed(c, SRC_NEW_D);
+    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
+    const int demodulate = p.demodulate && p.levels ? 1 : 0;   // without a level there is nothing to filter: D = (float)C, as the header says
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
+    init(flat, cv[0], demodulate);
+    for (uint32_t l = 0; l < p.levels; l++)
+        hipLaunchKernelGGL(atrous_kernel, tiles2d, dim3(32, 8), 0, c->stream, cv[l & 1u], c->guides, cv[(l + 1u) & 1u], c->RW, c->RH, 1u << l, sg);
+    hipLaunchKernelGGL(denoise_final_kernel, flat, dim3(256), 0, c->stream, cv[p.levels & 1u], c->guides, c->denoised, (uint32_t)pixels, demodulate);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
+    image_made(c, D_IMAGE, made_of);
+    return drain_events(c);
+}
+}  // extern "C++"
 int hr_denoise(hr_ctx *c, const hr_denoise_params *params) {
     static const char *const who = "hr_denoise";
     int rc = plane_ready(c, MOMENTS, who);
     if (rc) return rc;
     hr_denoise_params p;
-    if (params) p = *params;
-    else (void)hr_denoise_default_params(&p);
     // what is refused is refused before anything is touched: the denoised image of an earlier call stays
-    if (p.levels > DENOISE_MAX_LEVELS) return fail(HR_ERR_INVALID, "%s: levels must be in [0,%u]", who, DENOISE_MAX_LEVELS);
-    if (p.demodulate > 1u) return fail(HR_ERR_INVALID, "%s: demodulate must be 0 or 1", who);
-    for (double s : {p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth})
-        if (!(s > 0.0) || !(s < INFINITY)) return fail(HR_ERR_INVALID, "%s: every sigma must be positive and finite", who);
+    if ((rc = denoise_params(who, params, p))) return rc;
     if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
     if (c->moments_n >= (1ull << 30)) return fail(HR_ERR_INVALID, "%s: %llu samplings do not fit the resolve's 32-bit scale", who, (unsigned long long)c->moments_n);
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = hr_synchronize(c))) return rc;
     if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;
-    if (!c->guides_valid && (rc = hr_render_guides(c))) return rc;
+    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;
     const uint32_t pixels = (uint32_t)region_pixels(c);
-    if (!c->denoised && (rc = plane_alloc(c, DENOISED))) return rc;
-    CallScratch scratch;
-    double *cv[2] = {nullptr, nullptr};
-    for (int k = 0; k < 2; k++) HIP_TRY_AS(who, scratch.alloc((void **)&cv[k], (size_t)pixels * 6 * sizeof(double)));
-    new_denoised(c);
-    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
-    const int demodulate = p.demodulate && p.levels ? 1 : 0;   // without a level there is nothing to filter: D = (float)C0, as the header says
-    EventPair ev;
-    HIP_TRY(timed_begin(ev, c->stream));
-    const dim3 flat((pixels + 255) / 256), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
-    hipLaunchKernelGGL(denoise_init_kernel, flat, dim3(256), 0, c->stream, c->accum, c->moments, c->counts, (uint32_t)c->moments_n, c->guides, cv[0], pixels, demodulate);
-    for (uint32_t l = 0; l < p.levels; l++)
-        hipLaunchKernelGGL(atrous_kernel, tiles2d, dim3(32, 8), 0, c->stream, cv[l & 1u], c->guides, cv[(l + 1u) & 1u], c->RW, c->RH, 1u << l, sg);
-    hipLaunchKernelGGL(denoise_final_kernel, flat, dim3(256), 0, c->stream, cv[p.levels & 1u], c->guides, c->denoised, pixels, demodulate);
-    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
-    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
-    c->denoised_valid = true;
-    c->denoised_by_robust = false;
-    return drain_events(c);
+    return atrous_run(c, who, p, SRC_MOMENTS, [&](dim3 flat, double *cv, int demodulate) {
+        hipLaunchKernelGGL(denoise_init_kernel, flat, dim3(256), 0, c->stream, c->accum, c->moments, c->counts, (uint32_t)c->moments_n, c->guides, cv, pixels, demodulate);
+    });
 }
 int hr_read_denoised(hr_ctx *c, float *host) {
-    if (!c || !host) return fail(HR_ERR_INVALID, "hr_read_denoised: null argument");
-    if (!c->denoised || !c->denoised_valid) return fail(HR_ERR_INVALID, "hr_read_denoised: no denoised image (hr_denoise first; anything that changes its inputs invalidates it)");
-    return plane_read(c, DENOISED, c->denoised, host);
+    int rc = image_ready(c, D_IMAGE, "hr_read_denoised", host);
+    return rc ? rc : plane_read(c, DENOISED, c->denoised, host);
 }
 int hr_resolve_denoised(hr_ctx *c, uint8_t *host_rgb8) {
-    if (!c || !host_rgb8) return fail(HR_ERR_INVALID, "hr_resolve_denoised: null argument");
-    if (!c->denoised || !c->denoised_valid) return fail(HR_ERR_INVALID, "hr_resolve_denoised: no denoised image (hr_denoise first; anything that changes its inputs invalidates it)");
-    return resolve_region(c, 0, host_rgb8, c->denoised);
+    int rc = image_ready(c, D_IMAGE, "hr_resolve_denoised", host_rgb8);
+    return rc ? rc : resolve_region(c, 0, host_rgb8, c->denoised);
 }
 
 // ---- option "robust_buckets": the sample buckets and the firefly-robust resolve made of them (robust_core.h) ----
@@ -2095,34 +2127,26 @@ int hr_robust(hr_ctx *c) {
     if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_kernel instantiation for %u buckets (kernel_variants.h)", who, c->robust_k);
     if (!c->robust && (rc = plane_alloc(c, ROBUST))) return rc;
     if (!c->robust_trim && (rc = plane_alloc(c, ROBUST_TRIM))) return rc;
-    c->robust_valid = false;   // (R alone: R' is not made of R)
+    c->made_of[R_IMAGE] = 0;   // (R alone: R' is not made of R)
     const size_t pixels = region_pixels(c);
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
     hipLaunchKernelGGL(v->fn, dim3((unsigned)((pixels + 255) / 256)), dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->robust, c->robust_trim, pixels);
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
-    c->robust_valid = true;
+    image_made(c, R_IMAGE);
     return drain_events(c);
 }
-// R of the last hr_robust, while nothing it was made of has changed (`who`: the entry point)
-static int robust_ready(hr_ctx *c, const char *who, const void *host) {
-    int rc = plane_ready(c, BUCKETS, who);
-    if (rc) return rc;
-    if (!host) return fail(HR_ERR_INVALID, "%s: null argument", who);
-    if (!c->robust || !c->robust_trim || !c->robust_valid) return fail(HR_ERR_INVALID, "%s: no robust image (hr_robust first; anything that changes its inputs invalidates it)", who);
-    return HR_OK;
-}
 int hr_read_robust(hr_ctx *c, float *host) {
-    int rc = robust_ready(c, "hr_read_robust", host);
+    int rc = image_ready(c, R_IMAGE, "hr_read_robust", host);
     return rc ? rc : plane_read(c, ROBUST, c->robust, host);
 }
 int hr_read_robust_trim(hr_ctx *c, uint8_t *host) {
-    int rc = robust_ready(c, "hr_read_robust_trim", host);
+    int rc = image_ready(c, R_IMAGE, "hr_read_robust_trim", host);
     return rc ? rc : plane_read(c, ROBUST_TRIM, c->robust_trim, host);
 }
 int hr_resolve_robust(hr_ctx *c, uint8_t *host_rgb8) {
-    int rc = robust_ready(c, "hr_resolve_robust", host_rgb8);
+    int rc = image_ready(c, R_IMAGE, "hr_resolve_robust", host_rgb8);
     return rc ? rc : resolve_region(c, 0, host_rgb8, c->robust);
 }
 
@@ -2230,11 +2254,27 @@ int hr_select_tiles(hr_ctx *c, double floor, double threshold, uint32_t *active)
     int rc = plane_ready(c, MOMENTS, "hr_select_tiles");
     if (rc) return rc;
     if ((rc = plane_ready(c, COUNTS, "hr_select_tiles"))) return rc;
-    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "hr_select_tiles: floor must be a positive finite radiance");
-    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "hr_select_tiles: threshold must not be negative");
+    if ((rc = floor_and_threshold_ok("hr_select_tiles", floor, threshold))) return rc;
     if ((rc = hr_synchronize(c))) return rc;   // (also: no kernel is reading the list that is about to be rewritten)
     if ((rc = counts_cover_an_estimate(c, "hr_select_tiles"))) return rc;
     return select_tiles_run(c, "hr_select_tiles", nullptr, floor, threshold, active);
+}
+
+// What every call that takes the K bucket means of a pixel asks of the buckets (`who`), after its own checks: a sampling in each bucket of every
+// pixel — without the counts K samplings behind the buckets; with them, read on the device behind the context's work (the call is synchronised on
+// the way, as its callers always were at this point), K for every pixel and none beyond the samplings the buckets cover.
+static int buckets_cover_every_pixel(hr_ctx *c, const char *who) {
+    const uint32_t K = c->robust_k;
+    if (!c->counts && c->buckets_n < K) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the %u buckets, the bucket means need one in each", who, (unsigned long long)c->buckets_n, K);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = hr_synchronize(c);
+    if (rc || !c->counts) return rc;
+    uint32_t mm[2];
+    if ((rc = counts_range(c, mm))) return rc;
+    if (mm[0] < K) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), %u bucket means need one in each", who, mm[0], K);
+    if ((uint64_t)mm[1] > c->buckets_n)
+        return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the buckets cover %llu (the counts and the buckets must cover the same samplings)", who, mm[1], (unsigned long long)c->buckets_n);
+    return HR_OK;
 }
 
 // ---- the robust noise estimate of the sample buckets, and the selection of tiles by it (robust_core.h) ----
@@ -2244,19 +2284,9 @@ static int robust_noise_run(hr_ctx *c, const char *who, bool need_counts, double
     int rc = plane_ready(c, BUCKETS, who);
     if (rc) return rc;
     if (need_counts && (rc = plane_ready(c, COUNTS, who))) return rc;
-    if (!(floor > 0.0) || !(floor < INFINITY)) return fail(HR_ERR_INVALID, "%s: floor must be a positive finite radiance", who);
-    if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
+    if ((rc = floor_and_threshold_ok(who, floor, threshold))) return rc;
     const uint32_t K = c->robust_k;
-    if (!c->counts && c->buckets_n < K) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the %u buckets, the spread of the bucket means needs one in each", who, (unsigned long long)c->buckets_n, K);
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = hr_synchronize(c))) return rc;   // (for the selection also: no kernel is reading the list that is about to be rewritten)
-    if (c->counts) {
-        uint32_t mm[2];
-        if ((rc = counts_range(c, mm))) return rc;
-        if (mm[0] < K) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), the spread of %u bucket means needs one in each", who, mm[0], K);
-        if ((uint64_t)mm[1] > c->buckets_n)
-            return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the buckets cover %llu (the counts and the buckets must cover the same samplings)", who, mm[1], (unsigned long long)c->buckets_n);
-    }
+    if ((rc = buckets_cover_every_pixel(c, who))) return rc;   // (synchronised — for the selection also: no kernel is reading the list that is about to be rewritten)
     const RobustNoiseVariant *v = select_robust_noise_kernel(K, ROBUST_NOISE_STAGED);
     if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_noise_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
     const size_t pixels = region_pixels(c);
@@ -2273,15 +2303,7 @@ static int robust_noise_run(hr_ctx *c, const char *who, bool need_counts, double
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
     HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
-    if (est) {
-        double sum = 0.0, mx = 0.0, above = 0.0;
-        for (unsigned b = 0; b < ROBUST_NOISE_BLOCKS; b++) { sum += h[b * 3]; mx = h[b * 3 + 1] > mx ? h[b * 3 + 1] : mx; above += h[b * 3 + 2]; }
-        est->samplings = c->buckets_n;
-        est->pixels = (uint64_t)pixels;
-        est->pixels_above = (uint64_t)above;
-        est->mean_error = sum / (double)pixels;
-        est->max_error = mx;
-    }
+    if (est) noise_summary(h, c->buckets_n, pixels, est);
     return drain_events(c);
 }
 int hr_robust_noise_estimate(hr_ctx *c, double floor, double threshold, hr_noise *out) {
@@ -2311,46 +2333,16 @@ int hr_denoise_robust(hr_ctx *c, const hr_denoise_params *params) {
     int rc = plane_ready(c, BUCKETS, who);
     if (rc) return rc;
     hr_denoise_params p;
-    if (params) p = *params;
-    else (void)hr_denoise_default_params(&p);
-    if (p.levels > DENOISE_MAX_LEVELS) return fail(HR_ERR_INVALID, "%s: levels must be in [0,%u]", who, DENOISE_MAX_LEVELS);
-    if (p.demodulate > 1u) return fail(HR_ERR_INVALID, "%s: demodulate must be 0 or 1", who);
-    for (double s : {p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth})
-        if (!(s > 0.0) || !(s < INFINITY)) return fail(HR_ERR_INVALID, "%s: every sigma must be positive and finite", who);
+    if ((rc = denoise_params(who, params, p))) return rc;
     const uint32_t K = c->robust_k;
-    if (!c->counts && c->buckets_n < K) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the %u buckets, the spread of the bucket means needs one in each", who, (unsigned long long)c->buckets_n, K);
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = hr_synchronize(c))) return rc;
-    if (c->counts) {
-        uint32_t mm[2];
-        if ((rc = counts_range(c, mm))) return rc;
-        if (mm[0] < K) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), the spread of %u bucket means needs one in each", who, mm[0], K);
-        if ((uint64_t)mm[1] > c->buckets_n)
-            return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the buckets cover %llu (the counts and the buckets must cover the same samplings)", who, mm[1], (unsigned long long)c->buckets_n);
-    }
+    if ((rc = buckets_cover_every_pixel(c, who))) return rc;
     const RobustDenoiseInitVariant *v = select_robust_denoise_init_kernel(K);
     if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_denoise_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
-    if (!c->guides_valid && (rc = hr_render_guides(c))) return rc;
+    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;
     const size_t pixels = region_pixels(c);
-    if (!c->denoised && (rc = plane_alloc(c, DENOISED))) return rc;
-    CallScratch scratch;
-    double *cv[2] = {nullptr, nullptr};
-    for (int k = 0; k < 2; k++) HIP_TRY_AS(who, scratch.alloc((void **)&cv[k], pixels * 6 * sizeof(double)));
-    new_denoised(c);
-    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
-    const int demodulate = p.demodulate && p.levels ? 1 : 0;   // without a level there is nothing to filter: D = (float)C = R
-    EventPair ev;
-    HIP_TRY(timed_begin(ev, c->stream));
-    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
-    hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->guides, cv[0], pixels, demodulate);
-    for (uint32_t l = 0; l < p.levels; l++)
-        hipLaunchKernelGGL(atrous_kernel, tiles2d, dim3(32, 8), 0, c->stream, cv[l & 1u], c->guides, cv[(l + 1u) & 1u], c->RW, c->RH, 1u << l, sg);
-    hipLaunchKernelGGL(denoise_final_kernel, flat, dim3(256), 0, c->stream, cv[p.levels & 1u], c->guides, c->denoised, (uint32_t)pixels, demodulate);
-    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
-    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
-    c->denoised_valid = true;
-    c->denoised_by_robust = true;
-    return drain_events(c);
+    return atrous_run(c, who, p, SRC_BUCKETS, [&](dim3 flat, double *cv, int demodulate) {   // (without a level: D = (float)C = R)
+        hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->guides, cv, pixels, demodulate);
+    });
 }
 
 // ---- the restored robust resolve (restore_core.h): R' = base + the trimmed buckets' excess, spread along the guide planes ----
@@ -2374,22 +2366,13 @@ int hr_robust_restore(hr_ctx *c, const hr_restore_params *params) {
     if (p.base > 1u) return fail(HR_ERR_INVALID, "%s: base must be 0 (the robust radiance) or 1 (the denoised robust radiance)", who);
     for (double s : {p.sigma_n, p.sigma_a, p.sigma_z})
         if (!(s > 0.0) || !(s < INFINITY)) return fail(HR_ERR_INVALID, "%s: every sigma must be positive and finite", who);
-    if (p.base == 1u && !(c->denoised && c->denoised_valid && c->denoised_by_robust))
+    if (p.base == 1u && !(c->denoised && (c->made_of[D_IMAGE] & SRC_BUCKETS)))
         return fail(HR_ERR_INVALID, "%s: base 1 needs a valid denoised image made by hr_denoise_robust", who);
     const uint32_t K = c->robust_k;
-    if (!c->counts && c->buckets_n < K) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the %u buckets, the excess of the bucket means needs one in each", who, (unsigned long long)c->buckets_n, K);
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = hr_synchronize(c))) return rc;
-    if (c->counts) {
-        uint32_t mm[2];
-        if ((rc = counts_range(c, mm))) return rc;
-        if (mm[0] < K) return fail(HR_ERR_INVALID, "%s: a pixel of the region has received %u samplings (option sample_counts), %u bucket means need one in each", who, mm[0], K);
-        if ((uint64_t)mm[1] > c->buckets_n)
-            return fail(HR_ERR_INVALID, "%s: a pixel has received %u samplings but the buckets cover %llu (the counts and the buckets must cover the same samplings)", who, mm[1], (unsigned long long)c->buckets_n);
-    }
+    if ((rc = buckets_cover_every_pixel(c, who))) return rc;
     const RestoreInitVariant *v = select_restore_init_kernel(K);
     if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no restore_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
-    if (!c->guides_valid && (rc = hr_render_guides(c))) return rc;   // (base 1 never comes here: a valid D has valid guides)
+    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;   // (base 1 never comes here: a valid D has valid guides)
     const size_t pixels = region_pixels(c);
     if (!c->restored && (rc = plane_alloc(c, RESTORED))) return rc;
     CallScratch scratch;
@@ -2399,7 +2382,7 @@ int hr_robust_restore(hr_ctx *c, const hr_restore_params *params) {
         HIP_TRY_AS(who, scratch.alloc((void **)&S, pixels * 3 * sizeof(double)));
         for (uint32_t k = 0; k < (p.levels > 1u ? 2u : 1u); k++) HIP_TRY_AS(who, scratch.alloc((void **)&xp[k], pixels * 3 * sizeof(double)));
     }
-    invalidate_restored(c);
+    c->made_of[RESTORED_IMAGE] = 0;
     const DenoiseSigmas sg = denoise_sigmas(1.0, p.sigma_n, p.sigma_a, p.sigma_z);
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
@@ -2415,22 +2398,15 @@ int hr_robust_restore(hr_ctx *c, const hr_restore_params *params) {
     hipLaunchKernelGGL(restore_final_kernel, flat, dim3(256), 0, c->stream, cx, p.base ? c->denoised : (const float *)nullptr, X, xs, c->restored, (uint32_t)pixels);
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
-    c->restored_valid = true;
-    c->restored_on_d = p.base == 1u;
+    image_made(c, RESTORED_IMAGE, p.base == 1u ? SRC_NEW_D : 0u);
     return drain_events(c);
 }
-// R' of the last hr_robust_restore, while nothing it was made of has changed (`who`: the entry point)
-static int restored_ready(hr_ctx *c, const char *who, const void *host) {
-    if (!c || !host) return fail(HR_ERR_INVALID, "%s: null argument", who);
-    if (!c->restored || !c->restored_valid) return fail(HR_ERR_INVALID, "%s: no restored image (hr_robust_restore first; anything that changes its inputs invalidates it)", who);
-    return HR_OK;
-}
 int hr_read_restored(hr_ctx *c, float *host) {
-    int rc = restored_ready(c, "hr_read_restored", host);
+    int rc = image_ready(c, RESTORED_IMAGE, "hr_read_restored", host);
     return rc ? rc : plane_read(c, RESTORED, c->restored, host);
 }
 int hr_resolve_restored(hr_ctx *c, uint8_t *host_rgb8) {
-    int rc = restored_ready(c, "hr_resolve_restored", host_rgb8);
+    int rc = image_ready(c, RESTORED_IMAGE, "hr_resolve_restored", host_rgb8);
     return rc ? rc : resolve_region(c, 0, host_rgb8, c->restored);
 }
 
@@ -2542,7 +2518,7 @@ static int set_plane_option(hr_ctx *c, double value, const Plane &p, const Plane
     if (value == 1 && !c->W) return fail(HR_ERR_NO_TARGET, "%s: hr_set_resolution not called", p.option);
     int rc = sync_all(c);
     if (rc) return rc;
-    if (value == 0 || !(c->*p.on)) { invalidate_denoised(c); invalidate_robust(c); }   // the moments or the counts go, or start over
+    if (value == 0 || !(c->*p.on)) changed(c, SRC_MOMENTS | SRC_COUNTS);   // the moments or the counts go, or start over (conservative, kept: whichever of the two it is)
     if (value == 0) {
         c->*p.on = false;
         if ((rc = off_first(c))) return rc;
@@ -2561,10 +2537,9 @@ static int set_robust_buckets(hr_ctx *c, double value) {
     if (value != 0 && !robust_valid_k(value)) return fail(HR_ERR_INVALID, "robust_buckets must be 0 (off) or an odd number of buckets in [3,15]");
     if (value != 0 && !c->W) return fail(HR_ERR_NO_TARGET, "robust_buckets: hr_set_resolution not called");
     if (c->robust_on && (uint32_t)value == c->robust_k) return HR_OK;
-    if (c->denoised_by_robust) invalidate_denoised(c);   // a D of hr_denoise_robust is made of the buckets that go
+    changed(c, SRC_BUCKETS);
     int rc = sync_all(c);
     if (rc) return rc;
-    invalidate_robust(c);
     c->robust_on = false;
     c->robust_k = 0;
     if ((rc = plane_free(c, BUCKETS)) || (rc = plane_free(c, ROBUST)) || (rc = plane_free(c, ROBUST_TRIM)) || (rc = plane_free(c, ROBUST_NOISE_IMG)) || (rc = plane_free(c, ROBUST_NOISE_TRIM)) || (rc = plane_free(c, RESTORED))) return rc;
@@ -2572,7 +2547,7 @@ static int set_robust_buckets(hr_ctx *c, double value) {
     c->robust_k = (uint32_t)value;
     if ((rc = plane_alloc(c, BUCKETS))) { (void)plane_free(c, BUCKETS); c->robust_k = 0; return rc; }
     c->robust_on = true;
-    if (c->counts_on) { invalidate_denoised(c); if ((rc = plane_zero(c, COUNTS)) || (rc = plane_zero(c, MOMENTS))) return rc; }
+    if (c->counts_on) { changed(c, SRC_COUNTS | SRC_MOMENTS); if ((rc = plane_zero(c, COUNTS)) || (rc = plane_zero(c, MOMENTS))) return rc; }
     return HR_OK;
 }
 
@@ -2589,10 +2564,9 @@ static bool set_sharding_option(hr_ctx *c, const std::string &key, double value,
     if ((rc = sync_all(c))) return true;
     c->bucket_by_sampling = value == 1;
     if (!c->robust_on) return true;
-    if (c->denoised_by_robust) invalidate_denoised(c);
-    invalidate_robust(c);
+    changed(c, SRC_BUCKETS);
     if ((rc = plane_zero(c, BUCKETS))) return true;
-    if (c->counts_on) { invalidate_denoised(c); if ((rc = plane_zero(c, COUNTS))) return true; rc = plane_zero(c, MOMENTS); }
+    if (c->counts_on) { changed(c, SRC_COUNTS | SRC_MOMENTS); if ((rc = plane_zero(c, COUNTS))) return true; rc = plane_zero(c, MOMENTS); }
     return true;
 }
 
@@ -2622,8 +2596,7 @@ int hr_set_option(hr_ctx *c, const char *key, double value) {
         if (!(value >= 0 && value <= 8) || value != std::floor(value)) return fail(HR_ERR_INVALID, "guide_bounces must be a whole number in [0,8]");
         if ((uint32_t)value == c->guide_bounces) return HR_OK;
         c->guide_bounces = (uint32_t)value;
-        c->guides_valid = false;
-        invalidate_denoised(c);
+        changed(c, SRC_GUIDES);
         return HR_OK;
     }
     if (k == "max_tail_gib") {

@@ -227,9 +227,12 @@ static const RobustNoiseVariant *select_robust_noise_kernel(uint32_t k, bool sta
 }
 
 // ---- robust_kernel<K> and robust_denoise_init_kernel<K> (post_kernels.h): hr_robust and the init pass of hr_denoise_robust, one row per K ----
-// Both stage a workgroup's span through lds() bytes of dynamic LDS (robust_stage_span; create_resources raises the limit).
+// Both stage a workgroup's span through lds() bytes of dynamic LDS (robust_stage_span; create_resources raises the limit): a row of these
+// families, and of restore_init_kernel's below, is a KRow of the kernel's type.
+template <class Fn>
+struct KRow { uint32_t k; Fn fn; uint32_t lds() const { return 256u * 3u * k * (uint32_t)sizeof(double); } };
 typedef void (*RobustFn)(const double *, const uint32_t *, unsigned long long, float *, uint8_t *, size_t);
-struct RobustVariant { uint32_t k; RobustFn fn; uint32_t lds() const { return 256u * 3u * k * (uint32_t)sizeof(double); } };
+typedef KRow<RobustFn> RobustVariant;
 static const RobustVariant ROBUST_VARIANTS[] = {
     HR_VARIANT(robust_kernel, 3),  HR_VARIANT(robust_kernel, 5),  HR_VARIANT(robust_kernel, 7),  HR_VARIANT(robust_kernel, 9),
     HR_VARIANT(robust_kernel, 11), HR_VARIANT(robust_kernel, 13), HR_VARIANT(robust_kernel, 15),
@@ -239,7 +242,7 @@ static const RobustVariant *select_robust_kernel(uint32_t k) {
     return find_row(ROBUST_VARIANTS, [&](const RobustVariant &r) { return r.k == k; });
 }
 typedef void (*RobustDenoiseInitFn)(const double *, const uint32_t *, unsigned long long, const float *, double *, size_t, int);
-struct RobustDenoiseInitVariant { uint32_t k; RobustDenoiseInitFn fn; uint32_t lds() const { return 256u * 3u * k * (uint32_t)sizeof(double); } };
+typedef KRow<RobustDenoiseInitFn> RobustDenoiseInitVariant;
 static const RobustDenoiseInitVariant ROBUST_DENOISE_INIT_VARIANTS[] = {
     HR_VARIANT(robust_denoise_init_kernel, 3),  HR_VARIANT(robust_denoise_init_kernel, 5),  HR_VARIANT(robust_denoise_init_kernel, 7),
     HR_VARIANT(robust_denoise_init_kernel, 9),  HR_VARIANT(robust_denoise_init_kernel, 11), HR_VARIANT(robust_denoise_init_kernel, 13),
@@ -252,7 +255,7 @@ static const RobustDenoiseInitVariant *select_robust_denoise_init_kernel(uint32_
 // ---- restore_init_kernel<K> (post_kernels.h): the init pass of hr_robust_restore, {C, X} of every pixel, one row per K ----
 // It stages a workgroup's span through lds() bytes of dynamic LDS as the two families above do (robust_stage_span; create_resources raises the limit).
 typedef void (*RestoreInitFn)(const double *, const uint32_t *, unsigned long long, double *, size_t);
-struct RestoreInitVariant { uint32_t k; RestoreInitFn fn; uint32_t lds() const { return 256u * 3u * k * (uint32_t)sizeof(double); } };
+typedef KRow<RestoreInitFn> RestoreInitVariant;
 static const RestoreInitVariant RESTORE_INIT_VARIANTS[] = {
     HR_VARIANT(restore_init_kernel, 3),  HR_VARIANT(restore_init_kernel, 5),  HR_VARIANT(restore_init_kernel, 7),  HR_VARIANT(restore_init_kernel, 9),
     HR_VARIANT(restore_init_kernel, 11), HR_VARIANT(restore_init_kernel, 13), HR_VARIANT(restore_init_kernel, 15),

@@ -42,12 +42,10 @@ __global__ __launch_bounds__(256) void denoise_final_kernel(const double *__rest
     denoise_final(cv + (size_t)i * 6, guides + (size_t)i * 8, demodulate, d + (size_t)i * 3);
 }
 
-// A workgroup's 256 pixels through LDS, the staged form DESIGN.md §4.11 measured and kept (robust_noise_kernel below has it written out in its loop):
-// the pixels of workgroup `base / 256` are one contiguous span of 256 x 24 K bytes; the lanes load it as consecutive doubles (a wave's load is 512
+// A workgroup's 256 pixels through LDS, the staged form DESIGN.md §4.11 measured and kept (robust_noise_kernel below has it written out in its loop, and keeps
+// it: with this call in the loop the compiler allocates and schedules all seven staged rows differently): the pixels of workgroup `base / 256` are one contiguous span of 256 x 24 K bytes; the lanes load it as consecutive doubles (a wave's load is 512
 // contiguous bytes; past the last pixel of the image: zeros, nothing is read), park it in 256 x 24 K bytes of dynamic LDS, and every lane gets its own
 // pixel's 3 K doubles back (stride 3 K doubles, 3 K odd: no bank conflict).  Every thread of the workgroup calls it (the barrier).
-template <uint32_t K>
-constexpr uint32_t robust_stage_lds_bytes() { return 256u * 3u * K * (uint32_t)sizeof(double); }
 template <uint32_t K>
 __device__ __forceinline__ const double *robust_stage_span(const double *__restrict__ buckets, size_t base, size_t pixels) {
     extern __shared__ double robust_stage[];
@@ -104,8 +102,6 @@ __global__ __launch_bounds__(256) void robust_denoise_init_kernel(const double *
 //   false  every lane loads its own 24 K contiguous bytes from global memory: a wave's load touches 64 lines 24 K bytes apart
 // The loop runs the same number of times for every thread of a workgroup (the barriers), a lane past the last pixel computes nothing.
 constexpr unsigned ROBUST_NOISE_BLOCKS = 1024;
-template <uint32_t K>
-constexpr uint32_t robust_noise_lds_bytes() { return 256u * 3u * K * (uint32_t)sizeof(double); }
 template <uint32_t K, bool STAGE>
 __global__ __launch_bounds__(256) void robust_noise_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all, size_t pixels,
                                                            double floor, double threshold, double *__restrict__ img, uint8_t *__restrict__ trim, double *__restrict__ out) {
