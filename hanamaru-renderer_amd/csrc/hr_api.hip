@@ -11,13 +11,14 @@
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
 //   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
 //                    robust_kernel, robust_denoise_init_kernel and robust_noise_kernel (robust_core.h); restore_init_kernel, spread_norm_kernel,
-//                    spread_gather_kernel and restore_final_kernel (restore_core.h)
+//                    spread_gather_kernel and restore_final_kernel (restore_core.h); select_init_kernel, atrous3_kernel, select_pick_kernel and
+//                    select_smooth_kernel (select_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
-// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane, robust noise image and its trim plane, restored robust image) are rows of one
+// The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane, robust noise image and its trim plane, restored robust image, selected image and its level plane) are rows of one
 // table, PLANES, with one set of routines for their bytes, life cycle, zeroing and host copies; scratch a call needs lives in a CallScratch.
-// The images made of them and kept for later reads (guides, D, R, R') are rows of a second table, IMAGES: what each goes stale with, and one check for its reads.
+// The images made of them and kept for later reads (guides, D, R, R', S) are rows of a second table, IMAGES: what each goes stale with, and one check for its reads.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -99,7 +100,7 @@ struct EventPair { hipEvent_t a, b; };
 
 // What a derived image (IMAGES, behind the planes) can be made of: a call that changes one of these says so to changed().
 enum : uint32_t { SRC_ACCUM = 1, SRC_MOMENTS = 2, SRC_COUNTS = 4, SRC_BUCKETS = 8, SRC_GUIDES = 16, SRC_SCENE = 32, SRC_TARGET = 64, SRC_NEW_D = 128 };
-enum ImageId { GUIDE_IMAGE, D_IMAGE, R_IMAGE, RESTORED_IMAGE, N_IMAGES };
+enum ImageId { GUIDE_IMAGE, D_IMAGE, R_IMAGE, RESTORED_IMAGE, SELECTED_IMAGE, N_IMAGES };
 
 struct hr_ctx {
     int device = 0;
@@ -144,6 +145,9 @@ struct hr_ctx {
     uint8_t *robust_trim = nullptr;
     // the restored robust radiance R' of the last hr_robust_restore
     float *restored = nullptr;
+    // the selected radiance S of the last hr_denoise_select and the level each pixel took
+    float *selected = nullptr;
+    uint8_t *selected_levels = nullptr;
     // the robust noise estimate: e_R of every pixel and the trim behind it, as the last estimate or selection left them (allocated
     // when one is first asked for; every call that reads them has just written them)
     double *robust_noise_img = nullptr;
@@ -473,7 +477,8 @@ static int free_mask_buffers(hr_ctx *c) {
 //   WITH_OPTION   allocated while the option `on` is on: when it is switched on, and by set_target while it is on; gone when it is switched off
 //   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate; guides: the first
 //                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise; robust, robust_trim: the first hr_robust; robust_noise_img,
-//                 robust_noise_trim: the first robust noise estimate; restored: the first hr_robust_restore), freed by set_target —
+//                 robust_noise_trim: the first robust noise estimate; restored: the first hr_robust_restore; selected, selected_levels: the first
+//                 hr_denoise_select), freed by set_target —
 //                 noise_img also with the moments it is made of, guides also by hr_upload_scene (they show the scene), robust, robust_trim
 //                 and the robust noise planes also with the buckets they are made of
 // at_alloc: zeroed when allocated.  at_clear: zeroed by hr_clear.  n: the count that belongs to the plane's contents and is zeroed with them.
@@ -506,8 +511,10 @@ static const Plane ROBUST_TRIM{PLANE_SLOT(robust_trim), sizeof(uint8_t), 1, ON_F
 static const Plane ROBUST_NOISE_IMG{PLANE_SLOT(robust_noise_img), sizeof(double), 1, ON_FIRST_USE, false, false};
 static const Plane ROBUST_NOISE_TRIM{PLANE_SLOT(robust_noise_trim), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
 static const Plane RESTORED{PLANE_SLOT(restored), sizeof(float), 3, ON_FIRST_USE, false, false};
+static const Plane SELECTED{PLANE_SLOT(selected), sizeof(float), 3, ON_FIRST_USE, false, false};
+static const Plane SELECTED_LEVELS{PLANE_SLOT(selected_levels), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
 #undef PLANE_SLOT
-static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM, &ROBUST_NOISE_IMG, &ROBUST_NOISE_TRIM, &RESTORED};
+static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM, &ROBUST_NOISE_IMG, &ROBUST_NOISE_TRIM, &RESTORED, &SELECTED, &SELECTED_LEVELS};
 
 static size_t region_pixels(const hr_ctx *c) { return (size_t)c->RW * c->RH; }
 static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps * (p.per ? c->*p.per : 1u); }
@@ -571,7 +578,7 @@ static int option_plane_write(hr_ctx *c, const Plane &p, const char *who, const 
 // it — the maker adds what was decided when it was made (hr_ctx::made_of) —, the option its reads ask for first, and what they say when there is
 // none.  Every call that changes a source says so to changed(); nothing else clears made_of.  "kept": more than the data flow needs, as it always was.
 struct Image {
-    const Plane *plane, *second;   // (second: R's trim plane)
+    const Plane *plane, *second;   // (second: R's trim plane, S's level plane)
     uint32_t stale_with;
     const Plane *option;
     const char *none;
@@ -583,6 +590,9 @@ static const Image IMAGES[N_IMAGES] = {
     {&ROBUST, &ROBUST_TRIM, SRC_COUNTS | SRC_BUCKETS | SRC_TARGET, &BUCKETS, "no robust image (hr_robust first; anything that changes its inputs invalidates it)"},
     // R': + SRC_NEW_D made on D (base 1); the accumulator is kept
     {&RESTORED, nullptr, SRC_ACCUM | SRC_COUNTS | SRC_BUCKETS | SRC_GUIDES | SRC_SCENE | SRC_TARGET, nullptr, "no restored image (hr_robust_restore first; anything that changes its inputs invalidates it)"},
+    // S and its level plane: neither says nor listens to "a new D"
+    {&SELECTED, &SELECTED_LEVELS, SRC_ACCUM | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS | SRC_GUIDES | SRC_SCENE | SRC_TARGET, &BUCKETS,
+     "no selected image (hr_denoise_select first; anything that changes its inputs invalidates it)"},
 };
 static bool image_valid(const hr_ctx *c, ImageId id) { return c->made_of[id] != 0; }
 static void image_made(hr_ctx *c, ImageId id, uint32_t decided = 0) { c->made_of[id] = IMAGES[id].stale_with | decided; }
@@ -641,6 +651,7 @@ static int create_resources(hr_ctx *c) {
     for (const RobustVariant &v : ROBUST_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     for (const RobustDenoiseInitVariant &v : ROBUST_DENOISE_INIT_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     for (const RestoreInitVariant &v : RESTORE_INIT_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
+    for (const SelectInitVariant &v : SELECT_INIT_VARIANTS) HIP_TRY(hipFuncSetAttribute((const void *)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds()));
     HIP_TRY(hipFuncSetAttribute((const void *)seed_debug_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 8));
     // The seed kernel owns all 160 KiB of a CU's LDS and runs next to the trace side of the previous batch: a trace-side kernel that
     // uses ANY LDS (the compiler promotes small private arrays to LDS unless told not to, see the Makefile) could not share a CU
@@ -2408,6 +2419,83 @@ int hr_read_restored(hr_ctx *c, float *host) {
 int hr_resolve_restored(hr_ctx *c, uint8_t *host_rgb8) {
     int rc = image_ready(c, RESTORED_IMAGE, "hr_resolve_restored", host_rgb8);
     return rc ? rc : resolve_region(c, 0, host_rgb8, c->restored);
+}
+
+// ---- the denoiser that picks its level per pixel (select_core.h): S and its level plane L ----
+// Everything that is refused is refused before anything is touched: S of an earlier call stays.  Nothing but S, L (and, without guide planes, the
+// guides) is written: D, R, R', the buckets, the accumulator, the moments and the counts are read only or not at all.
+int hr_select_default_params(hr_select_params *out) {
+    if (!out) return fail(HR_ERR_INVALID, "hr_select_default_params: null argument");
+    memset(out, 0, sizeof *out);
+    out->smooth = 2;   // the lowest worst case of tools/select_quality.py's table
+    return HR_OK;
+}
+int hr_denoise_select(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select) {
+    static const char *const who = "hr_denoise_select";
+    int rc = plane_ready(c, BUCKETS, who);
+    if (rc || (rc = plane_ready(c, MOMENTS, who))) return rc;
+    hr_denoise_params p;
+    if ((rc = denoise_params(who, params, p))) return rc;
+    hr_select_params s;
+    if (select) s = *select;
+    else (void)hr_select_default_params(&s);
+    if (s.smooth > SELECT_MAX_SMOOTH) return fail(HR_ERR_INVALID, "%s: smooth must be in [0,%u]", who, SELECT_MAX_SMOOTH);
+    if (s.reserved != 0u) return fail(HR_ERR_INVALID, "%s: reserved must be 0", who);
+    if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
+    if (c->moments_n >= (1ull << 30)) return fail(HR_ERR_INVALID, "%s: %llu samplings do not fit the resolve's 32-bit scale", who, (unsigned long long)c->moments_n);
+    if (c->moments_n != c->buckets_n)
+        return fail(HR_ERR_INVALID, "%s: the moments cover %llu samplings, the buckets %llu (they must cover the same samplings)", who, (unsigned long long)c->moments_n, (unsigned long long)c->buckets_n);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = hr_synchronize(c))) return rc;
+    if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;   // (every n >= 2 and none beyond the moments' — which are the buckets')
+    const uint32_t K = c->robust_k;
+    const SelectInitVariant *v = select_select_init_kernel(K);
+    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no select_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
+    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;
+    const size_t pixels = region_pixels(c);
+    // the call's planes first: a device without room leaves S as it was
+    CallScratch scratch;
+    double *st[2] = {nullptr, nullptr}, *raw = nullptr, *e[2] = {nullptr, nullptr}, *best = nullptr;   // (st: 18 planes of a double per pixel each, raw: 6; post_kernels.h)
+    for (int k = 0; k < (p.levels ? 2 : 1); k++) HIP_TRY_AS(who, scratch.alloc((void **)&st[k], pixels * 18 * sizeof(double)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&raw, pixels * 6 * sizeof(double)));
+    for (int k = 0; k < (s.smooth ? 2 : 0); k++) HIP_TRY_AS(who, scratch.alloc((void **)&e[k], pixels * sizeof(double)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&best, pixels * sizeof(double)));
+    if (!c->selected && (rc = plane_alloc(c, SELECTED))) return rc;
+    if (!c->selected_levels && (rc = plane_alloc(c, SELECTED_LEVELS))) return rc;
+    c->made_of[SELECTED_IMAGE] = 0;
+    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
+    const int demodulate = p.demodulate && p.levels ? 1 : 0;   // as hr_denoise: without a level there is nothing to filter
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
+    hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (uint32_t)c->moments_n, c->accum, c->moments, c->guides, st[0], raw, pixels, demodulate);
+    for (uint32_t l = 0; l <= p.levels; l++) {
+        double *cur = st[l & 1u], *nxt = st[(l + 1u) & 1u];
+        if (s.smooth) {
+            hipLaunchKernelGGL(select_pick_kernel, flat, dim3(256), 0, c->stream, cur, raw, c->guides, (const double *)nullptr, e[0], l, best, c->selected_levels, c->selected, (uint32_t)pixels,
+                               demodulate);
+            for (uint32_t t = 0; t < s.smooth; t++) hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, e[t & 1u], e[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
+        }
+        hipLaunchKernelGGL(select_pick_kernel, flat, dim3(256), 0, c->stream, cur, raw, c->guides, s.smooth ? e[s.smooth & 1u] : (const double *)nullptr, (double *)nullptr, l, best,
+                           c->selected_levels, c->selected, (uint32_t)pixels, demodulate);
+        if (l < p.levels) hipLaunchKernelGGL(atrous3_kernel, tiles2d, dim3(32, 8), 0, c->stream, cur, c->guides, nxt, c->RW, c->RH, 1u << l, sg);
+    }
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
+    image_made(c, SELECTED_IMAGE);
+    return drain_events(c);
+}
+int hr_read_selected(hr_ctx *c, float *host) {
+    int rc = image_ready(c, SELECTED_IMAGE, "hr_read_selected", host);
+    return rc ? rc : plane_read(c, SELECTED, c->selected, host);
+}
+int hr_read_selected_levels(hr_ctx *c, uint8_t *host) {
+    int rc = image_ready(c, SELECTED_IMAGE, "hr_read_selected_levels", host);
+    return rc ? rc : plane_read(c, SELECTED_LEVELS, c->selected_levels, host);
+}
+int hr_resolve_selected(hr_ctx *c, uint8_t *host_rgb8) {
+    int rc = image_ready(c, SELECTED_IMAGE, "hr_resolve_selected", host_rgb8);
+    return rc ? rc : resolve_region(c, 0, host_rgb8, c->selected);
 }
 
 int hr_get_stats(hr_ctx *c, hr_stats *out) {

@@ -264,3 +264,16 @@ static const RestoreInitVariant RESTORE_INIT_VARIANTS[] = {
 static const RestoreInitVariant *select_restore_init_kernel(uint32_t k) {
     return find_row(RESTORE_INIT_VARIANTS, [&](const RestoreInitVariant &r) { return r.k == k; });
 }
+
+// ---- select_init_kernel<K> (post_kernels.h): the init pass of hr_denoise_select, the three states and the halves' raw radiance, one row per K ----
+// It stages a workgroup's span through lds() bytes of dynamic LDS as the three families above do (robust_stage_span; create_resources raises the limit).
+typedef void (*SelectInitFn)(const double *, const uint32_t *, uint32_t, const float *, const double *, const float *, double *, double *, size_t, int);
+typedef KRow<SelectInitFn> SelectInitVariant;
+static const SelectInitVariant SELECT_INIT_VARIANTS[] = {
+    HR_VARIANT(select_init_kernel, 3),  HR_VARIANT(select_init_kernel, 5),  HR_VARIANT(select_init_kernel, 7),  HR_VARIANT(select_init_kernel, 9),
+    HR_VARIANT(select_init_kernel, 11), HR_VARIANT(select_init_kernel, 13), HR_VARIANT(select_init_kernel, 15),
+};
+// K as option robust_buckets has it
+static const SelectInitVariant *select_select_init_kernel(uint32_t k) {
+    return find_row(SELECT_INIT_VARIANTS, [&](const SelectInitVariant &r) { return r.k == k; });
+}

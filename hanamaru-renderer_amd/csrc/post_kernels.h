@@ -7,6 +7,7 @@
 #include "post_core.h"
 #include "restore_core.h"
 #include "robust_core.h"
+#include "select_core.h"
 
 using namespace hr;
 
@@ -188,4 +189,85 @@ __global__ __launch_bounds__(256) void restore_final_kernel(const double *__rest
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pixels) return;
     restore_final(cx + (size_t)i * 6, D ? D + (size_t)i * 3 : nullptr, X + (size_t)i * xs, restored + (size_t)i * 3);
+}
+
+// The denoiser that picks its level per pixel (select_core.h).  The kernels carry no arithmetic of their own: every value is the core's.
+// The three states lie in call-scoped memory as 18 planes of one double per pixel — component c of state s (0: A, 1: B, 2: W) is plane 6 s + c —
+// and the halves' level-0 radiance {A0, B0} as 6 more: a wave's load of one component is contiguous (a row of 32 lanes reads 256 bytes; with 6
+// doubles per pixel side by side it would be spread over 1,536), and the pick reads the three C components it needs and no V.  select_plane_at is the
+// one place that says so; the other layout — a pixel's N doubles side by side — is kept for the comparison of DESIGN.md §4.16: a library built with
+// -DHR_SELECT_INTERLEAVED (`make EXPFLAGS=-DHR_SELECT_INTERLEAVED`) runs it instead — the same bits, another time.
+template <uint32_t N>   // N: the planes of the block (18: the states, 6: {A0, B0})
+__device__ __forceinline__ size_t select_plane_at(uint32_t plane, size_t q, size_t pixels) {
+#if defined(HR_SELECT_INTERLEAVED)
+    return q * N + plane;
+#else
+    return (size_t)plane * pixels + q;
+#endif
+}
+struct SelectPlanes {
+    const double *base;
+    size_t pixels;
+    __device__ __forceinline__ double operator()(int s, size_t q, int c) const { return base[select_plane_at<18>((uint32_t)(s * 6 + c), q, pixels)]; }
+};
+// select_init_kernel<K>: the shape of robust_denoise_init_kernel — one workgroup per span of 256 pixels, the span through robust_stage_span's LDS —,
+// the initial {C, V} of A, B and W into `st` and {A0, B0} into `raw`.  K is a template parameter: no array is indexed at run time, nothing goes to
+// scratch.  Every pixel has n >= 2 samplings (hr_denoise_select has checked).  counts == nullptr: every pixel has n_all samplings.
+template <uint32_t K>
+__global__ __launch_bounds__(256) void select_init_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, uint32_t n_all, const float *__restrict__ acc,
+                                                          const double *__restrict__ moments, const float *__restrict__ guides, double *__restrict__ st, double *__restrict__ raw,
+                                                          size_t pixels, int demodulate) {
+    const size_t base = (size_t)blockIdx.x * 256u, i = base + threadIdx.x;
+    const double *B = robust_stage_span<K>(buckets, base, pixels);
+    if (i >= pixels) return;
+    double a[6], b[6], w[6];
+    select_init_k<K>(B, counts ? counts[i] : n_all, acc + i * 3, moments + i * 6, guides + i * 8, demodulate, a, b, w);
+#pragma unroll
+    for (uint32_t c = 0; c < 6; c++) { st[select_plane_at<18>(c, i, pixels)] = a[c]; st[select_plane_at<18>(6 + c, i, pixels)] = b[c]; st[select_plane_at<18>(12 + c, i, pixels)] = w[c]; }
+#pragma unroll
+    for (uint32_t c = 0; c < 3; c++) { raw[select_plane_at<6>(c, i, pixels)] = a[c]; raw[select_plane_at<6>(3 + c, i, pixels)] = b[c]; }
+}
+// One level of the three states in one launch (select_level3): a tap's guides are read once and its guide weight is computed once for the three
+// colour weights — three atrous_kernel launches read them and compute it three times.  One thread per pixel, straight from global memory like
+// atrous_kernel: at steps >= 4 an LDS tile with its halo would be mostly holes, and the 25 taps of neighbouring pixels meet in the caches.
+// select_level3 unrolls its 25 taps: what bounds a level is the latency of a tap's chain of loads, divisions and sums, and unrolled the loads of
+// many taps are in flight under the arithmetic of the others (DESIGN.md §4.16 has the three measurements).
+__global__ __launch_bounds__(256) void atrous3_kernel(const double *__restrict__ in, const float *__restrict__ guides, double *__restrict__ out, uint32_t W, uint32_t H, uint32_t step,
+                                                      DenoiseSigmas sg) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t pixels = (size_t)W * H, p = (size_t)y * W + x;
+    double o[3][6];
+    select_level3(SelectPlanes{in, pixels}, guides, W, H, x, y, step, sg, o);
+#pragma unroll
+    for (int s = 0; s < 3; s++) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) out[select_plane_at<18>((uint32_t)(s * 6 + c), p, pixels)] = o[s][c];
+    }
+}
+// The error of level l and the pick.  e_out != nullptr: e_l of every pixel into that plane, nothing else (the smoothing passes come next).
+// Otherwise the pick, with the error taken from e_in (the smoothed plane) or, e_in == nullptr, computed here (smooth = 0: one launch per level).
+__global__ __launch_bounds__(256) void select_pick_kernel(const double *__restrict__ st, const double *__restrict__ raw, const float *__restrict__ guides,
+                                                          const double *__restrict__ e_in, double *__restrict__ e_out, uint32_t l, double *__restrict__ best,
+                                                          uint8_t *__restrict__ L, float *__restrict__ S, uint32_t pixels, int demodulate) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    const SelectPlanes at{st, pixels};
+    const size_t p = i;
+    double e;
+    if (e_in) e = e_in[p];
+    else {
+        const double fa[3] = {at(0, p, 0), at(0, p, 1), at(0, p, 2)}, fb[3] = {at(1, p, 0), at(1, p, 1), at(1, p, 2)};
+        const double a0[3] = {raw[select_plane_at<6>(0, p, pixels)], raw[select_plane_at<6>(1, p, pixels)], raw[select_plane_at<6>(2, p, pixels)]};
+        const double b0[3] = {raw[select_plane_at<6>(3, p, pixels)], raw[select_plane_at<6>(4, p, pixels)], raw[select_plane_at<6>(5, p, pixels)]};
+        e = select_error(fa, fb, a0, b0);
+    }
+    if (e_out) { e_out[p] = e; return; }
+    const double fw[3] = {at(2, p, 0), at(2, p, 1), at(2, p, 2)};   // (denoise_final reads C alone)
+    select_pick(e, l, fw, guides + p * 8, demodulate, best + p, L + p, S + p * 3);
+}
+__global__ __launch_bounds__(256) void select_smooth_kernel(const double *__restrict__ e, double *__restrict__ out, uint32_t W, uint32_t H, uint32_t step) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= W || y >= H) return;
+    out[(size_t)y * W + x] = select_smooth(e, W, H, x, y, step);
 }

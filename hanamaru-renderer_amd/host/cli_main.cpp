@@ -19,7 +19,9 @@
 // hr_robust_noise_estimate / hr_select_tiles_robust / hr_read_robust_noise_image), --robust-denoise (with --robust: the FINAL
 // image is the a-trous filter's over the robust radiance and its bucket-spread variance, hr_denoise_robust + hr_resolve_denoised),
 // --robust-restore / --restore-levels N (with --robust: the FINAL image is the robust radiance — with --robust-denoise the denoised one — plus the
-// trimmed buckets' excess spread along the guide planes, hr_robust_restore + hr_resolve_restored).
+// trimmed buckets' excess spread along the guide planes, hr_robust_restore + hr_resolve_restored),
+// --denoise-auto K / --select-smooth N / --level-image FILE (options "moments" and "robust_buckets": the FINAL image is --denoise's filter with the
+// level picked per pixel from the held-out halves of the K sample buckets, hr_denoise_select + hr_resolve_selected).
 // The file is in main's order: Options and parse_options (everything that can be refused before a device is opened), then Run, whose members
 // are main's steps.  The checkpoint's format is host/checkpoint.h's; what a render demands of a file is said in Run::resume.
 #include <algorithm>
@@ -137,7 +139,18 @@ static void usage(const char *prog) {
            "                        With --robust-denoise the excess goes on top of the denoised image.  --guide-bounces works as with --denoise.  A\n"
            "                        pixel with fewer than K samplings: the image is written unrestored.  Needs --robust.\n"
            "        --restore-levels N\n"
-           "                        spread levels, 0 .. 5 (default 4; the taps of level l are 2^l pixels apart).  Needs --robust-restore.\n",
+           "                        spread levels, 0 .. 5 (default 4; the taps of level l are 2^l pixels apart).  Needs --robust-restore.\n"
+           "        --denoise-auto K\n"
+           "                        keep per-pixel sample moments and K sample buckets (K odd, 3 .. 15) and write the FINAL image through --denoise's\n"
+           "                        filter with the level picked PER PIXEL, 0 .. --denoise-levels (hr_denoise_select: the two halves of the buckets are\n"
+           "                        filtered apart and each is judged against the raw pixel of the other; progress images stay as they are).\n"
+           "                        --denoise-levels, --guide-bounces and --guide-image work as with --denoise.  A pixel with fewer than 2 samplings,\n"
+           "                        or a --resume whose checkpoint has no buckets: the image is written unfiltered.  One device only; not with\n"
+           "                        --robust, --denoise or --debug.\n"
+           "        --select-smooth N\n"
+           "                        smoothing passes over the per-level error planes before the pick, 0 .. 3 (default 2).  Needs --denoise-auto.\n"
+           "        --level-image FILE.png\n"
+           "                        write an 8-bit grey map of level / --denoise-levels, the level each pixel took (needs --denoise-auto)\n",
            prog);
 }
 
@@ -167,6 +180,9 @@ struct Options {
     bool robust_denoise = false;     // --robust-denoise: the final image is hr_denoise_robust's
     bool robust_restore = false;     // --robust-restore: the final image is hr_robust_restore's
     long long restore_levels = -1;   // -1: the library's default
+    long long auto_k = 0;            // --denoise-auto K: options "moments" and "robust_buckets", the final image is hr_denoise_select's (0: off)
+    long long select_smooth = -1;    // -1: the library's default
+    std::string level_png;
     // what the flags add up to:
     bool counts = false, moments = false;   // hr_set_option "sample_counts", "moments"
     double noise_e = 0.05;                  // the threshold of "above" and of the grey map
@@ -272,6 +288,11 @@ static int parse_options(int argc, char **argv, Options &o) {
         else if (a == "--robust-noise") o.robust_noise = true;
         else if (a == "--robust-denoise") o.robust_denoise = true;
         else if (a == "--robust-restore") o.robust_restore = true;
+        else if (a == "--denoise-auto") {
+            if (!whole("--denoise-auto", val("denoise-auto"), 3, 15, 2, "an odd number of buckets in 3 .. 15", &o.auto_k)) return 1;
+        } else if (a == "--select-smooth") {
+            if (!whole("--select-smooth", val("select-smooth"), 0, 3, 1, "a whole number in 0 .. 3", &o.select_smooth)) return 1;
+        } else if (a == "--level-image") o.level_png = val("level-image");
         else if (a == "--restore-levels") {
             if (!whole("--restore-levels", val("restore-levels"), 0, 5, 1, "a whole number in 0 .. 5", &o.restore_levels)) return 1;
         }
@@ -288,11 +309,19 @@ static int parse_options(int argc, char **argv, Options &o) {
         if (o.have_adaptive && o.have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
         if (o.debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
     }
+    if (o.auto_k) {   // before everything else about these flags: nothing of --denoise-auto is half accepted
+        if (o.robust_k) { fprintf(stderr, "--denoise-auto cannot be combined with --robust (it filters the plain mean, and keeps sample buckets of its own: two final images).\n"); return 1; }
+        if (o.denoise) { fprintf(stderr, "--denoise-auto cannot be combined with --denoise (one filter with one level for the frame, one with a level per pixel: two final images).\n"); return 1; }
+        if (o.debug) { fprintf(stderr, "--denoise-auto cannot be combined with --debug (the debug renderer has no samplings to split into halves).\n"); return 1; }
+        if (!one_device(o, "--denoise-auto renders on one device: the library picks the levels from one context's moments and sample buckets, this program's device loop does not fold them.")) return 1;
+    }
+    if (o.select_smooth >= 0 && !o.auto_k) { fprintf(stderr, "--select-smooth needs --denoise-auto.\n"); return 1; }
+    if (!o.level_png.empty() && !o.auto_k) { fprintf(stderr, "--level-image needs --denoise-auto.\n"); return 1; }
     if (o.robust_denoise && !o.robust_k) { fprintf(stderr, "--robust-denoise needs --robust (it filters the robust radiance by the spread of the sample buckets).\n"); return 1; }
     if (o.robust_restore && !o.robust_k) { fprintf(stderr, "--robust-restore needs --robust (it gives back the energy the robust resolve drops).\n"); return 1; }
     if (o.restore_levels >= 0 && !o.robust_restore) { fprintf(stderr, "--restore-levels needs --robust-restore.\n"); return 1; }
-    if (o.denoise_levels >= 0 && !o.denoise && !o.robust_denoise) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
-    if (o.guide_bounces >= 0 && !o.denoise && !o.robust_denoise && !o.robust_restore && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
+    if (o.denoise_levels >= 0 && !o.denoise && !o.robust_denoise && !o.auto_k) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
+    if (o.guide_bounces >= 0 && !o.denoise && !o.robust_denoise && !o.robust_restore && !o.auto_k && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
     if (o.denoise || !o.guide_prefix.empty()) {
         if (!one_device(o, "--denoise / --guide-image render on one device: the library denoises one context's accumulator, moments and counts (a sharded host sums them into one), this program's device loop does not.")) return 1;
         if (o.debug) { fprintf(stderr, "--denoise / --guide-image cannot be combined with --debug (the debug renderer has no samplings whose variance could guide a filter).\n"); return 1; }
@@ -304,7 +333,7 @@ static int parse_options(int argc, char **argv, Options &o) {
         if (o.denoise) { fprintf(stderr, "--robust cannot be combined with --denoise (the filter reads the raw moments, not the robust radiance: two final images).\n"); return 1; }
         if (o.debug) { fprintf(stderr, "--robust cannot be combined with --debug (the debug renderer has no samplings to put into buckets).\n"); return 1; }
     }
-    o.moments = o.have_target || !o.noise_png.empty() || o.have_adaptive || o.denoise;
+    o.moments = o.have_target || !o.noise_png.empty() || o.have_adaptive || o.denoise || o.auto_k != 0;
     if (o.moments && o.debug) { fprintf(stderr, "--noise-target / --noise-image cannot be combined with --debug (the debug renderer has no samplings to measure).\n"); return 1; }
     o.noise_e = o.have_adaptive ? o.adaptive_e : o.have_target && o.noise_target > 0.0 ? o.noise_target : (o.have_target ? 0.0 : 0.05);
     o.region[2] = o.width, o.region[3] = o.height;
@@ -347,6 +376,8 @@ struct Run {
     bool host_sum = false;
     std::vector<float> sum_acc, part;
     bool have_guides = false;   // the context holds guide planes (for --guide-image)
+    bool have_levels = false;   // the context holds a selected image and its level plane (for --level-image)
+    uint32_t select_levels = 0; // the levels that selection could choose from
     bool final_image = false;   // set by whoever writes the render's last image: --denoise filters that one only
     std::vector<double> mom_tot, mom_part, mom_own;
     hr_noise noise_last;
@@ -415,6 +446,7 @@ int Run::open_devices() {
         if (o.counts) CHECK_HR(hr_set_option(ctxs[r], "sample_counts", 1.0));
         if (o.guide_bounces >= 0) CHECK_HR(hr_set_option(ctxs[r], "guide_bounces", (double)o.guide_bounces));
         if (o.robust_k) CHECK_HR(hr_set_option(ctxs[r], "robust_buckets", (double)o.robust_k));
+        if (o.auto_k) CHECK_HR(hr_set_option(ctxs[r], "robust_buckets", (double)o.auto_k));
     }
     ctx = ctxs[0];
     if (ndev > 1) tee("devices: %u.", ndev);
@@ -470,6 +502,17 @@ int Run::resolve(uint32_t s, uint8_t *out) {
             tee("robust-restore: fewer than K samplings behind a pixel, the robust image is not restored.");
         }
         return hr_robust(ctx) != 0 ? 1 : hr_resolve_robust(ctx, out);
+    }
+    if (o.auto_k && final_image) {   // (one device, neither --robust nor --denoise: checked with the flags)
+        hr_denoise_params dp;
+        hr_select_params sp;
+        if (hr_denoise_default_params(&dp) != 0 || hr_select_default_params(&sp) != 0) return 1;
+        if (o.denoise_levels >= 0) dp.levels = (uint32_t)o.denoise_levels;
+        if (o.select_smooth >= 0) sp.smooth = (uint32_t)o.select_smooth;
+        const int rc = hr_denoise_select(ctx, &dp, &sp);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings, or buckets that do not cover the moments' samplings)
+        if (rc == 0) { have_guides = true; have_levels = true; select_levels = dp.levels; return hr_resolve_selected(ctx, out); }
+        if (rc != HR_ERR_INVALID) return rc;
+        tee("denoise-auto: %s; the image is not denoised.", hr_last_error());
     }
     if (o.denoise && final_image) {
         hr_denoise_params dp;
@@ -853,6 +896,15 @@ int Run::write_reports() {
         for (size_t i = 0; i < pixels; i++) for (int k = 0; k < 3; k++) img[i * 3 + k] = byte(0.5f * g[i * 8 + 3 + k] + 0.5f * g[i * 8 + 7]);
         if (write_png(o.guide_prefix + "_normal.png", img.data(), out_w, out_h)) return 1;
         if (write_grey(o.guide_prefix + "_depth.png", out_w, out_h, [&](size_t i) { return std::min(1.0f, std::max(0.0f, zmax > 0.0f ? g[i * 8 + 6] / zmax : 0.0f)); })) return 1;
+    }
+    if (o.auto_k && have_levels) {   // which level the pixels took; and its map
+        std::vector<uint8_t> lev(pixels);
+        CHECK_HR(hr_read_selected_levels(ctx, lev.data()));
+        uint64_t sum = 0;
+        for (uint8_t v : lev) sum += v;
+        tee("denoise-auto: buckets=%lld levels=%u mean level=%.3f", o.auto_k, select_levels, (double)sum / (double)lev.size());
+        // grey map of level / levels
+        if (!o.level_png.empty() && write_grey(o.level_png, out_w, out_h, [&](size_t i) { return select_levels ? (double)lev[i] / (double)select_levels : 0.0; })) return 1;
     }
     if (o.robust_k) {   // how much the robust resolve dropped; and its map
         std::vector<uint8_t> trim(pixels);

@@ -89,6 +89,10 @@ class RestoreParams(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("base", C.c_uint32), ("sigma_n", C.c_double), ("sigma_a", C.c_double), ("sigma_z", C.c_double)]
 
 
+class SelectParams(C.Structure):
+    _fields_ = [("smooth", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 COMM_PATHS = {0: "none", 1: "rccl-rank", 2: "rccl-group", 3: "same-device-fallback"}
 
 
@@ -224,6 +228,11 @@ def hip_lib():
         L.hr_robust_restore.argtypes = [C.c_void_p, C.POINTER(RestoreParams)]
         L.hr_read_restored.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_resolve_restored.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_select_default_params.argtypes = [C.POINTER(SelectParams)]
+        L.hr_denoise_select.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(SelectParams)]
+        L.hr_read_selected.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_read_selected_levels.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_resolve_selected.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_fold_statistics.argtypes = [C.c_void_p]
         L.hr_fold_statistics_group.argtypes = [C.POINTER(C.c_void_p), C.c_int]
         _hip = L
@@ -294,6 +303,16 @@ def fold_statistics(renderers):
 
 class HostError(RuntimeError):
     pass
+
+
+def select_default_params():
+    """hr_select_default_params: the documented defaults as a SelectParams (needs no device)."""
+    L = hip_lib()
+    p = SelectParams()
+    rc = L.hr_select_default_params(C.byref(p))
+    if rc != 0:
+        raise HipError(rc, L.hr_last_error().decode())
+    return p
 
 
 def restore_default_params():
@@ -381,6 +400,7 @@ _PLANES = {
     "accumulator": ((3,), np.float32), "rgb8": ((3,), np.uint8), "moments": ((6,), np.float64), "noise": ((), np.float64),
     "sample_counts": ((), np.uint32), "guides": ((8,), np.float32), "denoised": ((3,), np.float32), "buckets": ((3,), np.float64),
     "robust": ((3,), np.float32), "robust_trim": ((), np.uint8), "restored": ((3,), np.float32),
+    "selected": ((3,), np.float32), "selected_levels": ((), np.uint8),
 }
 
 
@@ -678,6 +698,32 @@ class Renderer:
     def resolve_restored(self):
         """hr_resolve_restored: resolve() of the restored robust radiance."""
         return self._read_plane(self.L.hr_resolve_restored, "rgb8")
+
+    # ---- the denoiser that picks its level per pixel (include/hanamaru_hip.h)
+    def denoise_select(self, smooth=None, **params):
+        """hr_denoise_select: S and its level plane L — hr_denoise's filter with the level picked per pixel from the held-out sample halves;
+        the denoiser's defaults with any of levels, demodulate, sigma_* replaced, and `smooth` passes over the error planes (None: the default)."""
+        p = denoise_default_params()
+        for k, v in params.items():
+            if k not in dict(DenoiseParams._fields_):
+                raise TypeError("denoise_select() has no parameter %r" % k)
+            setattr(p, k, v)
+        s = select_default_params()
+        if smooth is not None:
+            s.smooth = smooth
+        self._check(self.L.hr_denoise_select(self._h, C.byref(p), C.byref(s)))
+
+    def read_selected(self):
+        """hr_read_selected: (h, w, 3) float32 radiance."""
+        return self._read_plane(self.L.hr_read_selected, "selected")
+
+    def read_selected_levels(self):
+        """hr_read_selected_levels: (h, w) uint8, the level each pixel took."""
+        return self._read_plane(self.L.hr_read_selected_levels, "selected_levels")
+
+    def resolve_selected(self):
+        """hr_resolve_selected: resolve() of the selected radiance."""
+        return self._read_plane(self.L.hr_resolve_selected, "rgb8")
 
     # ---- the robust noise estimate of the buckets, and the selection of tiles by it (include/hanamaru_hip.h)
     def robust_noise_estimate(self, floor=0.01, threshold=0.05):

@@ -523,6 +523,44 @@ int hr_robust_restore(hr_ctx *ctx, const hr_restore_params *p /* NULL = defaults
 int hr_read_restored(hr_ctx *ctx, float *host /* w*h*3 radiance */);
 int hr_resolve_restored(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on R' with scale 1.0f */
 
+/* ---- the denoiser that picks its level per pixel: S and its level plane L (csrc/select_core.h is the definition) ------------------
+ * hr_denoise applies one `levels` to the whole frame, and a level too many RAISES the error of a converged pixel.  hr_denoise_select runs
+ * hr_denoise's filter through every level 0 .. levels and keeps, per pixel, the level whose held-out error is the lowest.  The pixel's K sample
+ * buckets split into two halves for free (even and odd b); each half is filtered on its own — the same levels, the same guides — and judged
+ * against the RAW pixel of the other half, which its noise is independent of:
+ *         n_b = (n - b + K - 1) / K;   n_A, n_B: the samplings of the even and of the odd buckets;   A0_c = (sum_{b even} B[b][c]) / n_A / 4, B0 likewise
+ *         states {C, V}:  W = hr_denoise's {C0, V0};   A = {A0, V0 n / n_A};   B = {B0, V0 n / n_B}   (demodulated as hr_denoise's, A0 and B0 too)
+ *         F_X,l = state X after l levels;   e_l = sum_c (F_A,l,c - B0_c)^2 + (F_B,l,c - A0_c)^2
+ *         e_l smoothed by `smooth` passes of the 5 x 5 a-trous kernel (steps 1, 2, 4; weights h alone);   L = the lowest l with the smallest e_l
+ *         (strict comparison: ties and NaN keep the lower level);   S = hr_denoise's final pass on F_W,L
+ *     All f64, + - x / and comparisons only: the device, the header under a host compiler and a numpy restatement agree bit for bit.  Where
+ *     L(p) = l, S(p) has the bits of hr_denoise(levels = l)'s D at p; with levels = 0 hr_resolve_selected gives hr_resolve's bytes.
+ *   - Needs "robust_buckets" != 0 AND "moments" on; works on the region (the taps stop at its edge) and with "sample_counts" (every pixel's own
+ *     n); renders the guide planes itself (hr_render_guides) when there are none; synchronises; its time goes to hr_stats.post_kernel_ms.
+ *   - HR_ERR_INVALID, decided before anything is touched — an earlier S stays readable and unchanged: either option off; a pixel of the region
+ *     with fewer than 2 samplings; moments, buckets (and counts) that do not cover the same samplings; the parameters hr_denoise refuses;
+ *     smooth > 3; reserved != 0.
+ *   - S and L are valid until the accumulator, the moments, the counts, the buckets, the guides, the scene or the target change (hr_render,
+ *     hr_clear, every hr_write_*, hr_render_guides, "guide_bounces", switching "robust_buckets", "moments" or "sample_counts", hr_upload_scene,
+ *     hr_set_resolution, hr_set_region).  A new D, R or R' and hr_set_tile_mask leave them alone, and the call touches none of D, R, R'.
+ *     hr_read_selected, hr_read_selected_levels and hr_resolve_selected return HR_ERR_INVALID with "robust_buckets" off or without a valid S.
+ *   - Memory for the call: about 360 bytes per pixel (746 MB at 1920x1080) — the three states twice, the halves' raw radiance, two error planes
+ *     and the best error; S (12 B) and L (1 B) per pixel stay.  HR_ERR_DEVICE "out of memory" when the device has no room; nothing is written then.
+ *   - What it is not: e_l is the error of filters on n / 2 samplings, so it leans towards more smoothing than the whole buffer needs; with
+ *     smooth = 0 the pick is correlated with the pixel's own noise (the default, 2, has the lowest worst case of DESIGN.md 4.16's table; 0 is the
+ *     better choice for short renders with first-hit guides); it is the plain estimator, not the robust one; there is no temporal part.
+ *     Cost at 1920x1080 with K = 9 and levels 4 on one MI355X: 5.0 ms of hr_stats.post_kernel_ms with smooth 0, 5.3 ms with smooth 2 — 0.63 of
+ *     three hr_denoise calls (tools/select_rate.py). */
+typedef struct hr_select_params {
+    uint32_t smooth;     /* 0..3 passes over the error planes */
+    uint32_t reserved;   /* 0 */
+} hr_select_params;
+int hr_select_default_params(hr_select_params *out);       /* 2, 0; needs no device */
+int hr_denoise_select(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */, const hr_select_params *s /* NULL = defaults */);
+int hr_read_selected(hr_ctx *ctx, float *host /* w*h*3 radiance */);
+int hr_read_selected_levels(hr_ctx *ctx, uint8_t *host /* w*h: the level each pixel took */);
+int hr_resolve_selected(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on S with scale 1.0f */
+
 /* ---- sharded statistics: buckets by sampling, and the fold into rank 0 ----------------------------------------------------------
  * Contexts that shard the samplings (hr_render's stride) each hold a share of every additive plane.  hr_fold_statistics moves the shares to
  * rank 0 of the communicator, so that ONE context answers every question with the functions above, unchanged: hr_noise_estimate,

@@ -35,6 +35,8 @@ pub const HR_MESH: i32 = 2;
                                                                          pub sigma_albedo: f64, pub sigma_depth: f64 }
 /// hr_restore_params: the restored robust resolve's parameters (hr_restore_default_params fills in the defaults)
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrRestoreParams { pub levels: u32, pub base: u32, pub sigma_n: f64, pub sigma_a: f64, pub sigma_z: f64 }
+/// hr_select_params: the per-pixel level selection's parameters (hr_select_default_params fills in the defaults)
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrSelectParams { pub smooth: u32, pub reserved: u32 }
 pub enum HrCtx {}
 
 extern "C" {
@@ -118,6 +120,12 @@ extern "C" {
     pub fn hr_robust_restore(ctx: *mut HrCtx, p: *const HrRestoreParams /* null = defaults */) -> c_int;
     pub fn hr_read_restored(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 */) -> c_int;
     pub fn hr_resolve_restored(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
+    // the denoiser that picks its level per pixel from the held-out halves of the sample buckets: S and its level plane L (needs "robust_buckets" and "moments")
+    pub fn hr_select_default_params(out: *mut HrSelectParams) -> c_int;
+    pub fn hr_denoise_select(ctx: *mut HrCtx, p: *const HrDenoiseParams /* null = defaults */, s: *const HrSelectParams /* null = defaults */) -> c_int;
+    pub fn hr_read_selected(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 */) -> c_int;
+    pub fn hr_read_selected_levels(ctx: *mut HrCtx, host: *mut u8 /* w*h */) -> c_int;
+    pub fn hr_resolve_selected(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
     // every additive plane (accumulator, moments, counts, buckets filled under option "bucket_by_sampling" 1) moves to rank 0, which then answers
     pub fn hr_fold_statistics(ctx: *mut HrCtx) -> c_int;
     pub fn hr_fold_statistics_group(ctxs: *mut *mut HrCtx, n: c_int) -> c_int;
@@ -137,6 +145,7 @@ const _: () = assert!(std::mem::size_of::<HrCommInfo>() == 32 && std::mem::align
 const _: () = assert!(std::mem::size_of::<HrNoise>() == 40 && std::mem::align_of::<HrNoise>() == 8);   // hr_noise
 const _: () = assert!(std::mem::size_of::<HrDenoiseParams>() == 40 && std::mem::align_of::<HrDenoiseParams>() == 8);   // hr_denoise_params
 const _: () = assert!(std::mem::size_of::<HrRestoreParams>() == 32 && std::mem::align_of::<HrRestoreParams>() == 8);   // hr_restore_params
+const _: () = assert!(std::mem::size_of::<HrSelectParams>() == 8 && std::mem::align_of::<HrSelectParams>() == 4);   // hr_select_params
 const _: () = assert!(std::mem::size_of::<Vector3>() == 24);   // hr_vec3
 #[cfg(test)]
 mod layout {
@@ -204,6 +213,8 @@ mod layout {
         assert_eq!(off!(HrRestoreParams, sigma_n), 8);
         assert_eq!(off!(HrRestoreParams, sigma_a), 16);
         assert_eq!(off!(HrRestoreParams, sigma_z), 24);
+        assert_eq!(off!(HrSelectParams, smooth), 0);
+        assert_eq!(off!(HrSelectParams, reserved), 4);
     }
 }
 // ---- END GENERATED ----

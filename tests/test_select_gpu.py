@@ -1,0 +1,227 @@
+"""The denoiser that picks its level per pixel on the MI355X: hr_denoise_select against csrc/select_core.h compiled for the host —
+bit for bit: f64, + - x / and comparisons, no contraction — on real renders, against hr_denoise level by level, the validity of S, the refusals,
+the quality ordering on the device, and the CLI."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import test_select_cpu as sl
+from cli import ASSETS, run_cli
+from gpu_helpers import error_of, renderer, same
+from test_robust_cpu import rel_sq_error
+
+pytestmark = pytest.mark.gpu
+
+HR_ERR_INVALID = -1
+
+
+@pytest.fixture(scope="module")
+def core(tmp_path_factory):
+    return sl.build_core(tmp_path_factory.mktemp("select_gpu"))
+
+
+def _err(ha, fn, *a, **kw):
+    return error_of(ha, fn, *a, **kw)[0]
+
+
+def _checker(w, h):
+    ty, tx = (h + 3) // 4, (w + 3) // 4
+    yy, xx = np.mgrid[0:ty, 0:tx]
+    return ((xx + yy) & 1).astype(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------------------------- S and L against the host core
+
+# (frame, region, quant_nodes, K, sample_counts with a tile mask that leaves unequal counts, bucket_by_sampling)
+# 37x19: two workgroups of the 32x8 kernels in either direction, neither full; 96x54: 5,184 pixels — 20 full spans of 256 and a partial one;
+# the region: offset from the origin, 37x19 — no multiple of 32x8
+CASES = {
+    "small-K3": ((37, 19), None, 1, 3, False, 0),
+    "frame-fp32nodes-K9": ((96, 54), None, 0, 9, False, 0),
+    "small-counts-K9": ((37, 19), None, 1, 9, True, 0),
+    "region-counts-bys-K3": ((64, 48), (5, 3, 37, 19), 0, 3, True, 1),
+    "frame-bys-K9": ((96, 54), None, 1, 9, False, 1),
+}
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_s_and_l_equal_the_host_core(ha, scenes, core, case):
+    frame, region, qn, K, counted, bys = CASES[case]
+    w, h = region[2:] if region else frame
+    with renderer(ha, scenes("cornell_mini")[0], {"quant_nodes": qn, "bucket_by_sampling": bys}, None, frame, region, moments=True, counts=counted, buckets=K) as r:
+        r.render(1, 12)
+        if counted:                                                                    # half of the tiles get five samplings more: counts 11 and 16
+            r.set_tile_mask(_checker(w, h))
+            r.render(12, 17)
+            r.set_tile_mask(None)
+        r.render_guides()
+        acc, (mom, mom_n), (B, b_n), g = r.read_accumulator(), r.read_moments(), r.read_buckets(), r.read_guides()
+        n = r.read_sample_counts() if counted else mom_n
+        assert mom_n == b_n and (not counted or (n.min() == 11 and n.max() == 16))
+        picked = set()
+        for levels in (0, 1, 4):
+            for smooth in (0, 2):
+                r.denoise_select(levels=levels, smooth=smooth)
+                S, L = sl.core_select(core, B, acc, mom, n, g, smooth=smooth, levels=levels)
+                assert np.array_equal(r.read_selected_levels(), L), (case, levels, smooth)
+                assert same(r.read_selected(), S), (case, levels, smooth)
+                picked |= set(np.unique(L).tolist())
+        r.denoise_select(levels=4, demodulate=0)                                       # (the default smooth)
+        S, L = sl.core_select(core, B, acc, mom, n, g, smooth=ha.select_default_params().smooth, levels=4, demodulate=0)
+        assert np.array_equal(r.read_selected_levels(), L) and same(r.read_selected(), S), case
+        assert len(picked) >= 3, picked
+
+
+# ---------------------------------------------------------------------------------------------------------------- S against hr_denoise
+
+@pytest.mark.parametrize("K", [3, 9])
+def test_s_is_hr_denoise_where_the_level_is_picked(ha, scenes, K):
+    n, levels = 11, 4
+    with renderer(ha, scenes("cornell_mini")[0], None, None, (96, 54), moments=True, buckets=K) as r:
+        r.render(1, n + 1)
+        for smooth in (0, 2):
+            r.denoise_select(levels=levels, smooth=smooth)
+            S, L = r.read_selected(), r.read_selected_levels()
+            assert L.max() <= levels
+            seen = 0
+            for lev in range(levels + 1):
+                r.denoise(levels=lev)
+                m = L == lev
+                assert same(S[m], r.read_denoised()[m]), (K, smooth, lev)
+                seen += bool(m.any())
+            assert seen >= 3
+            assert same(r.read_selected(), S)                                          # a new D is none of S's business
+        r.denoise_select(levels=0)
+        assert not r.read_selected_levels().any()
+        assert np.array_equal(r.resolve_selected(), r.resolve(n))
+
+
+# ---------------------------------------------------------------------------------------------------------------- validity and refusals
+
+def test_validity(ha, scenes):
+    K, n, shape = 9, 11, (19, 37)
+    with renderer(ha, scenes("cornell_mini")[0], None, None, (37, 19), moments=True, counts=True, buckets=K) as r:
+        for read in (r.read_selected, r.read_selected_levels, r.resolve_selected):     # before the first make
+            assert _err(ha, read) == HR_ERR_INVALID
+        r.render(1, n + 1)
+        B, b_n = r.read_buckets()
+        mom, m_n = r.read_moments()
+        r.render_guides()
+
+        def fresh():
+            r.denoise_select()
+            assert r.read_selected().shape == shape + (3,) and r.read_selected_levels().shape == shape and r.resolve_selected().shape == shape + (3,)
+
+        for what, call in [("render", lambda: r.render(n + 1, n + 2)), ("write_buckets", lambda: r.write_buckets(B, b_n)), ("write_moments", lambda: r.write_moments(mom, m_n)),
+                           ("render_guides", r.render_guides), ("set_region", lambda: r.set_region(0, 0, 37, 19)), ("another K", lambda: r.set_option("robust_buckets", 5))]:
+            fresh()
+            call()
+            for read in (r.read_selected, r.read_selected_levels, r.resolve_selected):
+                assert _err(ha, read) == HR_ERR_INVALID, what
+            if what in ("render", "set_region", "another K"):                           # start over: the same eleven samplings in K buckets
+                r.set_option("robust_buckets", K)
+                r.clear()
+                r.render(1, n + 1)
+        fresh()
+        S, L = r.read_selected(), r.read_selected_levels()
+        r.denoise()
+        r.robust()
+        r.set_tile_mask(_checker(37, 19))
+        r.set_tile_mask(None)
+        assert same(r.read_selected(), S) and np.array_equal(r.read_selected_levels(), L)
+        # refusals: the earlier S stays readable and unchanged
+        for bad in ({"levels": 6}, {"demodulate": 2}, {"sigma_color": 0.0}, {"sigma_depth": float("nan")}, {"smooth": 4}):
+            assert _err(ha, r.denoise_select, **bad) == HR_ERR_INVALID, bad
+            assert same(r.read_selected(), S) and np.array_equal(r.read_selected_levels(), L), bad
+        reserved = ha.SelectParams(0, 1)
+        assert r.L.hr_denoise_select(r._h, None, C.byref(reserved)) == HR_ERR_INVALID
+        assert same(r.read_selected(), S) and np.array_equal(r.read_selected_levels(), L)
+        assert r.L.hr_denoise_select(r._h, None, None) == 0                            # NULL = defaults
+        assert same(r.read_selected(), S) and np.array_equal(r.read_selected_levels(), L)
+        # a pixel with one sampling (writing the counts makes S stale; the refused call leaves everything else alone)
+        counts = r.read_sample_counts()
+        low = counts.copy()
+        low[7, 9] = 1
+        r.write_sample_counts(low)
+        assert _err(ha, r.denoise_select) == HR_ERR_INVALID and _err(ha, r.read_selected) == HR_ERR_INVALID
+        r.write_sample_counts(counts)
+        fresh()
+        assert same(r.read_selected(), S)
+        # either option off
+        r.set_option("moments", 0)
+        assert _err(ha, r.denoise_select) == HR_ERR_INVALID
+        r.set_option("moments", 1)
+        r.set_option("robust_buckets", 0)
+        assert _err(ha, r.denoise_select) == HR_ERR_INVALID and _err(ha, r.read_selected) == HR_ERR_INVALID
+
+
+def test_asking_goes_to_post_kernel_ms_and_changes_nothing_else(ha, scenes):
+    with renderer(ha, scenes("cornell_mini")[0], None, None, (37, 19), moments=True, buckets=3) as r:
+        r.render(1, 9)
+        r.render_guides()
+        acc, mom, B = r.read_accumulator(), r.read_moments(), r.read_buckets()
+        before = r.stats()
+        r.denoise_select(smooth=1)
+        after = r.stats()
+        assert after["post_kernel_ms"] > before["post_kernel_ms"] and after["trace_launches"] == before["trace_launches"]
+        assert same(r.read_accumulator(), acc) and same(r.read_moments()[0], mom[0]) and same(r.read_buckets()[0], B[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------- quality
+
+def test_quality_on_the_device(ha, scenes):
+    """96x54, K = 9, first-hit guides, default denoise parameters, smooth 0, the truth 2,048 samplings from 100001 rendered by hr_render: on rtcamp6_v3_1
+    at 64 samplings — the case of DESIGN.md §4.9's finding — the selection's error is below the whole-buffer filter's at levels = 4.  Measured, fixed 4 ->
+    select over the raw mean's: 0.357 -> 0.223 at 16 samplings, 0.884 -> 0.510 at 64 (with the default smooth, 2: 0.348 and 0.801)."""
+    w, h, K, truth_n = 96, 54, 9, 2048
+    with ha.Renderer(0) as r:
+        r.upload_scene(scenes("rtcamp6_v3_1")[0])
+        r.set_resolution(w, h)
+        r.set_option("moments", 1)
+        r.set_option("robust_buckets", K)
+        got = {}
+        for n in (16, 64):
+            r.clear()
+            r.render(1, n + 1)
+            mean = r.read_accumulator() / np.float32(4 * n)
+            r.denoise()
+            D = r.read_denoised()
+            r.denoise_select()
+            default = r.read_selected()
+            r.denoise_select(smooth=0)
+            got[n] = (mean, D, r.read_selected(), r.read_selected_levels(), default)
+        r.set_option("robust_buckets", 0)
+        r.set_option("moments", 0)
+        r.clear()
+        r.render(100001, 100001 + truth_n)
+        truth = r.read_accumulator().astype(np.float64) / (4.0 * truth_n)
+    for n in (16, 64):
+        e_mean, e_fixed, e_sel = (rel_sq_error(x, truth) for x in got[n][:3])
+        print("rtcamp6_v3_1 on the device guide_bounces=0 n=%d K=%d: fixed-4 / raw %.3f  select (smooth 0) / raw %.3f  mean level %.3f  select (default smooth) / raw %.3f"
+              % (n, K, e_fixed / e_mean, e_sel / e_mean, got[n][3].mean(), rel_sq_error(got[n][4], truth) / e_mean))
+        if n == 64:
+            assert e_sel / e_mean < e_fixed / e_mean
+
+
+# ---------------------------------------------------------------------------------------------------------------- the CLI
+
+def test_cli_denoise_auto(ha, scenes, tmp_path):
+    w, h = 37, 19
+    args = ["--assets", ASSETS, "--scene", "cornell_mini", "-w", str(w), "-h", str(h), "-t", "1000", "-i", "1000"]
+    full, short = tmp_path / "full", tmp_path / "short"
+    level_png = str(full / "levels.png")
+    r = run_cli(args + ["-s", "16", "--denoise-auto", "9", "--denoise-levels", "3", "--select-smooth", "1", "--level-image", level_png], full, timeout=120)
+    assert r.returncode == 0 and "is not denoised" not in r.stdout and "denoise-auto: buckets=9 levels=3" in r.stdout, r.stdout
+    r = run_cli(args + ["-s", "1", "--denoise-auto", "9"], short, timeout=120)
+    assert r.returncode == 0 and r.stdout.count("the image is not denoised.") == 1, r.stdout
+    with renderer(ha, scenes("cornell_mini")[0], None, None, (w, h), moments=True, buckets=9) as lib:
+        lib.render(1, 17)
+        lib.denoise_select(levels=3, smooth=1)
+        assert np.array_equal(ha.decode_image(str(full / "result.png"))[..., :3], lib.resolve_selected())
+        L = lib.read_selected_levels()
+        grey = ha.decode_image(level_png)[..., 0]
+        assert np.array_equal(grey == 0, L == 0) and np.array_equal(grey == 255, L == 3)
+        lib.clear()
+        lib.render(1, 2)
+        assert np.array_equal(ha.decode_image(str(short / "result.png"))[..., :3], lib.resolve(1))

@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kres  # noqa: E402
 
 PARENT_ARITY = {"trace_kernel": 7, "accumulate_kernel": 3, "wf_start_kernel": 2, "seed_seg_kernel": 4, "noise_kernel": 1}
-PATTERN = re.compile(r"trace_kernel|seed_seg_kernel|accumulate_kernel|wf_|tonemap|bilateral|noise_kernel|governor|select_tiles|counts_min|seed_isaac64|seed_pc|debug_render|trace_debug|guide_|atrous|denoise_|bucket_kernel|robust_kernel|restore_|spread_")
+PATTERN = re.compile(r"trace_kernel|seed_seg_kernel|accumulate_kernel|wf_|tonemap|bilateral|noise_kernel|governor|select_|counts_min|seed_isaac64|seed_pc|debug_render|trace_debug|guide_|atrous|denoise_|bucket_kernel|robust_kernel|restore_|spread_")
 KEYS = ["vgpr", "sgpr", "vspill", "sspill", "scratch", "lds", "occ"]
 
 
