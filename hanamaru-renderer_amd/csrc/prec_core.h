@@ -15,6 +15,7 @@ namespace hr {
 // position error by 2 t / r per bounce: fp32 ray state leaves 100 - 1,000 ppm of the paths that took the reference's branches off by more than
 // 1e-3 in such scenes, this leaves 0 - 6.  What stays fp32: the walk, albedo / emission lookups, the sky lookup, NEE (sample
 // point, weight), radiometry.
+static const double OFFSET_D = 1e-4;   // config.rs:8 in the reference's precision ((double)OFFSET_F is 9.99999975e-5: 2.5e-12 on every origin)
 struct D3 { double x, y, z; };
 HD D3 dv(double x, double y, double z) { D3 r; r.x = x; r.y = y; r.z = z; return r; }
 HD D3 operator+(D3 a, D3 b) { return dv(a.x + b.x, a.y + b.y, a.z + b.z); }
@@ -36,14 +37,14 @@ HD void sample_refraction_f64(double r0, D3 pos, D3 in, D3 n, double ior, D3 &no
     const D3 rdir = dreflect(in, on);
     const double vn = ddot(in, on);
     const double k = 1.0 - nnt * nnt * (1.0 - vn * vn);      // vector.rs:64-71
-    if (k < 0.0) { no = pos + on * (double)OFFSET_F; nd = rdir; refl = 1.0f; return; }
+    if (k < 0.0) { no = pos + on * OFFSET_D; nd = rdir; refl = 1.0f; return; }
     const D3 tdir = in * nnt - on * (nnt * vn + sqrt(k));
-    if (tdir.x == 0.0 && tdir.y == 0.0 && tdir.z == 0.0) { no = pos + on * (double)OFFSET_F; nd = rdir; refl = 1.0f; return; }
+    if (tdir.x == 0.0 && tdir.y == 0.0 && tdir.z == 0.0) { no = pos + on * OFFSET_D; nd = rdir; refl = 1.0f; return; }
     const double cos_i = -ddot(in, on), cos_t = -ddot(tdir, on);
     const double a = nnt * cos_i - cos_t, b = nnt * cos_i + cos_t, c = nnt * cos_t - cos_i, d = nnt * cos_t + cos_i;
     const double fr = 0.5 * (a * a / (b * b) + c * c / (d * d));
-    if (r0 <= fr) { no = pos + on * (double)OFFSET_F; nd = rdir; refl = 1.0f; }
-    else { no = pos - on * (double)OFFSET_F; nd = tdir; refl = (float)(nnt * nnt); transmitted = true; }
+    if (r0 <= fr) { no = pos + on * OFFSET_D; nd = rdir; refl = 1.0f; }
+    else { no = pos - on * OFFSET_D; nd = tdir; refl = (float)(nnt * nnt); transmitted = true; }
 }
 
 // sin / cos of 2 pi r for r in [0, 1), to f64 accuracy: quadrant + Taylor polynomials on [-pi/4, pi/4] (no f64 transcendental hardware;
@@ -82,6 +83,15 @@ HD D3 sample_ggx_half_f64(double r0, double r1, D3 n, double alpha2) {  // mater
     const double cos_theta = sqrt(fmin((1.0 - r1) / (1.0 + (alpha2 - 1.0) * r1), 1.0));
     const double sin_theta = sqrt(fmax(1.0 - cos_theta * cos_theta, 0.0));
     return t * (sin_theta * cs) + b * (sin_theta * sn) + n * cos_theta;
+}
+
+// The GGX bounce's reflectance scalar f * saturate(g * v.h / (h.n * v.n)) (material.rs:123-141) from its four dot products, in f64.
+HD double ggx_refl_f64(double lnd, double vn, double vh, double hn, float alpha2, float param) {
+    const double a2 = (double)alpha2;
+    const double lam_l = 0.5 * sqrt(1.0 + a2 * (1.0 / (lnd * lnd) - 1.0)) - 0.5, lam_v = 0.5 * sqrt(1.0 + a2 * (1.0 / (vn * vn) - 1.0)) - 0.5;
+    const double g = 1.0 / (1.0 + lam_l + lam_v), om = 1.0 - vh, f = (double)param + (1.0 - (double)param) * (om * om * om * om * om);
+    const double q = g * vh / (hn * vn);
+    return f * (q > 0.0 ? (q < 1.0 ? q : 1.0) : 0.0);      // saturate: a NaN counts as 0 (f64::max / min)
 }
 
 // What shading a hit in f64 produces: the material at the hit, the fp32 normal (for NEE and the log), the next ray in f64, the sampled bounce's scalar.
@@ -197,8 +207,8 @@ HD void shade_hit_f64(const Scene &sc, V3f ro, V3f rd, V3f fo, V3f fd, const Tra
     D3 &no = x.no, &nd = x.nd;
     no = dv(0, 0, 0); nd = dv(0, 0, 0);
     switch (m.surface) {       // material.rs:91-151
-        case 0: no = pos + n * (double)OFFSET_F; nd = sample_diffuse_f64(r0, r1, n); x.cur_refl = 1.0f; break;
-        case 1: no = pos + n * (double)OFFSET_F; nd = dreflect(d, n); x.cur_refl = 1.0f; break;
+        case 0: no = pos + n * OFFSET_D; nd = sample_diffuse_f64(r0, r1, n); x.cur_refl = 1.0f; break;
+        case 1: no = pos + n * OFFSET_D; nd = dreflect(d, n); x.cur_refl = 1.0f; break;
         case 2: sample_refraction_f64(r0, pos, d, n, (double)m.param, no, nd, x.cur_refl, transmitted); break;
         case 3: {
             const float alpha2 = m.roughness * m.roughness;
@@ -208,12 +218,8 @@ HD void shade_hit_f64(const Scene &sc, V3f ro, V3f rd, V3f fo, V3f fd, const Tra
             if (signbit(lnd)) { sampled = false; break; }
             // the reflectance scalar in f64 too (material.rs:123-141): a bounce that leaves at grazing incidence has l.n ~ 1e-20 here, (l.n)^2
             // underflows in fp32, and 1 / 0 x alpha2 = 0 (a texel of roughness 0) is a NaN the f64 reference does not have
-            const double vn = -ddot(d, n), vh = -ddot(d, hh), hn = ddot(hh, n), a2 = (double)alpha2;
-            const double lam_l = 0.5 * sqrt(1.0 + a2 * (1.0 / (lnd * lnd) - 1.0)) - 0.5, lam_v = 0.5 * sqrt(1.0 + a2 * (1.0 / (vn * vn) - 1.0)) - 0.5;
-            const double g = 1.0 / (1.0 + lam_l + lam_v), om = 1.0 - vh, f = (double)m.param + (1.0 - (double)m.param) * (om * om * om * om * om);
-            const double q = g * vh / (hn * vn);
-            x.cur_refl = (float)(f * (q > 0.0 ? (q < 1.0 ? q : 1.0) : 0.0));      // saturate: a NaN counts as 0 (f64::max / min)
-            no = pos + n * (double)OFFSET_F;
+            x.cur_refl = (float)ggx_refl_f64(lnd, -ddot(d, n), -ddot(d, hh), ddot(hh, n), alpha2, m.param);
+            no = pos + n * OFFSET_D;
             break;
         }
         default: {

@@ -512,14 +512,30 @@ HD V3f sample_ggx_half(float r0, float r1, V3f n, float alpha2) {  // material.r
     // cos^2 = (1 - r1) / den, and sin^2 = 1 - cos^2 = alpha2 r1 / den taken from the same quotient instead of by subtraction: for a
     // near-mirror GGX (alpha2 -> 0) cos^2 is 1 - O(alpha2), and 1 - cos^2 in fp32 would be rounding noise of ~1e-7, i.e. a half
     // vector tilted by ~4e-4 where the f64 reference (material.rs:260-269, sqrt(1 - cos^2) with 1e-16 noise) tilts it by 1e-8
-    const float iden = HR_RCP(1.0f + (alpha2 - 1.0f) * r1);
+    // the denominator 1 + (alpha2 - 1) r1 as (1 - r1) + alpha2 r1: alpha2 - 1 rounds alpha2 < 3e-8 away altogether, and towards r1 = 1 the
+    // denominator is nothing but that term (roughness 1e-4, r1 = 1 - 2^-12: 4e-5 of it, 2e-5 of the direction)
+    const float iden = HR_RCP(fmaf(alpha2, r1, 1.0f - r1));
     float cos_theta = HR_SQRT(fmaxf((1.0f - r1) * iden, 0.0f));
     float sin_theta = HR_SQRT(fmaxf(alpha2 * r1 * iden, 0.0f));
     return t * (sin_theta * cs) + b * (sin_theta * sn) + n * cos_theta;
 }
-HD float smith_lambda(float xn, float alpha2) { float a = HR_RCP(xn * xn) - 1.0f; return 0.5f * HR_SQRT(1.0f + alpha2 * a) - 0.5f; }
-HD float g_smith_joint(float ln, float vn, float alpha2) { return HR_RCP(1.0f + smith_lambda(ln, alpha2) + smith_lambda(vn, alpha2)); }
+// The Smith term (material.rs:271-280) without its quotients.  1 + 2 lambda(x) = sqrt(1 + alpha2 (1 / x^2 - 1)) = S(x) / |x| with
+// S(x) = sqrt(alpha2 + (1 - alpha2) x^2), so   l.n v.n (1 + lambda_l + lambda_v) = (v.n S(l.n) + sgn(v.n) l.n S(v.n)) / 2   for l.n >= 0,
+// and both places the reference divides G by l.n v.n need only ONE reciprocal, of a sum that stays away from 0 as long as alpha does: written
+// as in the reference, 1 / x^2 is inf from x = 1e-19 on, G is 0 and G / (l.n v.n) is 0 where the limit is 1 / (2 alpha v.n), or 0 x inf.
+HD float smith_s(float xn, float alpha2) { return HR_SQRT(fmaf(xn * xn, 1.0f - alpha2, alpha2)); }
+HD float smith_denominator(float ln, float vn, float alpha2) { return fmaf(vn, smith_s(ln, alpha2), copysignf(ln * smith_s(vn, alpha2), vn)); }
 HD float f_schlick(float vh, float f0) { float x = 1.0f - vh, x2 = x * x; return f0 + (1.0f - f0) * (x * (x2 * x2)); }
+// tmp = 1 - (1 - alpha2) (h.n)^2 of the GGX distribution (material.rs:73), in f64 from the unnormalised half vector: (|h|^2 - (1 - alpha2) (h.n)^2)
+// / |h|^2.  In fp32 alpha2 = 1e-8 is lost in 1 - alpha2, h.n rounds to 1, tmp is 0 and D is inf at the centre of a near-mirror lobe; and the
+// reference's value there depends on n.n - 1 (the normal is a unit vector to fp32 only) as much as on the angle, which no fp32 form sees.
+// ~14 f64 operations per NEE term; one float leaves.
+HD float ggx_tmp(V3f light, V3f view, V3f n, float roughness) {
+    const double hx = (double)light.x + (double)view.x, hy = (double)light.y + (double)view.y, hz = (double)light.z + (double)view.z;
+    const double hh = fma(hx, hx, fma(hy, hy, hz * hz)), hn = fma(hx, (double)n.x, fma(hy, (double)n.y, hz * (double)n.z));
+    const double a2 = (double)roughness * (double)roughness;
+    return (float)fma(a2 - 1.0, hn * hn, hh) * HR_RCP((float)hh);   // (an explicit FMA, as in dot(): the same bits in every inlined copy)
+}
 
 HD float bsdf_eval(int32_t surface, float param, float roughness, V3f view, V3f n, V3f light) {  // material.rs:53-89
     if (surface == 0) return 1.0f / PI_F;
@@ -530,10 +546,15 @@ HD float bsdf_eval(int32_t surface, float param, float roughness, V3f view, V3f 
     // (a shadow ray toward an emitter sample at the very height of a horizontal face: one path in ~10^10, a NaN pixel in a 1,024-sampling
     // frame of cornell_mini).  The limit of bsdf x (l.n) for l.n -> 0+ is 0 (the Smith term vanishes): 0 is what a grazing sample adds.
     if (!(ln > 0.0f)) return 0.0f;
-    float vn = dot(view, n), vh = dot(view, h), hn = dot(h, n);
-    float tmp = 1.0f - (1.0f - alpha2) * hn * hn;
-    float d = alpha2 * HR_RCP(PI_F * tmp * tmp);
-    return d * g_smith_joint(ln, vn, alpha2) * f_schlick(vh, param) * HR_RCP(4.0f * ln * vn);
+    float vn = dot(view, n), vh = dot(view, h);
+    // D F = (alpha / tmp)^2 F / pi and G / (4 l.n v.n) = 1 / (2 smith_denominator), joined so that no intermediate leaves fp32 while the result is
+    // in it: alpha / tmp squared in two steps around the factor below 1, and the last step a reciprocal of (denominator / (D F)) — D F may be 1e30
+    // where the result is 1e35, the Smith quotient 1e35 where D F is 1e-5.  |tmp| is kept at or above alpha2, its minimum over unit vectors (sin^2 + alpha2 cos^2; only a normal
+    // longer than 1 takes the reference's below it), and above 1e-18: f64 resolves tmp to 1e-16, so an alpha2 below that is rounded away at the exact
+    // mirror direction — there the reference's own value is rounding noise (1e-30 for roughness 1e-30, 0 / 0 for roughness 0), this one small and finite.
+    const float r = roughness * HR_RCP(fmaxf(fabsf(ggx_tmp(light, view, n, roughness)), fmaxf(alpha2, 1e-18f)));
+    const float df = r * (f_schlick(vh, param) * (1.0f / PI_F)) * r;
+    return 0.5f * HR_RCP(smith_denominator(ln, vn, alpha2) * HR_RCP(df));
 }
 // material.rs:154-199
 // `transmitted`: true when the ray leaves along the refracted direction (false: Fresnel reflection or total internal reflection) —
@@ -570,7 +591,8 @@ HD bool bsdf_sample(const PointMat &m, float r0, float r1, V3f pos, V3f view, V3
             float ln = dot(l, n);
             if (signbit(ln)) return false;
             float vn = dot(view, n), vh = dot(view, h), hn = dot(h, n);
-            refl = f_schlick(vh, m.param) * saturatef(g_smith_joint(ln, vn, alpha2) * vh * HR_RCP(hn * vn));
+            // G v.h / (h.n v.n) = 2 v.h l.n / (h.n smith_denominator): at v.n = 1e-20 the reference's form is 0 x inf here (G underflows)
+            refl = f_schlick(vh, m.param) * saturatef(2.0f * vh * ln * HR_RCP(hn * smith_denominator(ln, vn, alpha2)));
             no = pos + n * OFFSET_F; nd = l;
             return true;
         }

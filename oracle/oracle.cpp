@@ -1166,6 +1166,43 @@ ORC_API double orc_material_bsdf(int surface, double param, double roughness, co
     m.surface = surface; m.param = param; m.albedo = V3(1, 1, 1); m.emission = V3(); m.roughness = roughness;
     return material_bsdf(m, V3(view[0], view[1], view[2]), V3(normal[0], normal[1], normal[2]), V3(light[0], light[1], light[2]));
 }
+// The same on n points at once (tests/shade_sweeps.py asks ~27 questions per point: every input moved to its fp32 neighbours).
+// view / normal / light / position: n x 3 doubles.  sample: out = n x 9 doubles, the 8 of orc_material_sample + transmitted(1)/not(0).
+ORC_API int orc_material_bsdf_n(size_t n, const int32_t *surface, const double *param, const double *roughness, const double *view, const double *normal,
+                                const double *light, double *out) {
+    for (size_t i = 0; i < n; i++) out[i] = orc_material_bsdf(surface[i], param[i], roughness[i], view + 3 * i, normal + 3 * i, light + 3 * i);
+    return 0;
+}
+ORC_API int orc_material_sample_n(size_t n, const int32_t *surface, const double *param, const double *roughness, const double *r0, const double *r1,
+                                  const double *position, const double *view, const double *normal, double *out) {
+    for (size_t i = 0; i < n; i++) {
+        PointMaterial m;
+        m.surface = surface[i]; m.param = param[i]; m.albedo = V3(1, 1, 1); m.emission = V3(); m.roughness = roughness[i];
+        SampleResult res;
+        res.ray.origin = V3(); res.ray.direction = V3(); res.reflectance = 0.0;
+        const double *p = position + 3 * i, *v = view + 3 * i, *nn = normal + 3 * i;
+        bool ok = material_sample(m, r0[i], r1[i], V3(p[0], p[1], p[2]), V3(v[0], v[1], v[2]), V3(nn[0], nn[1], nn[2]), res);
+        double *o = out + 9 * i;
+        o[0] = ok ? 1.0 : 0.0;
+        o[1] = res.ray.origin.x; o[2] = res.ray.origin.y; o[3] = res.ray.origin.z;
+        o[4] = res.ray.direction.x; o[5] = res.ray.direction.y; o[6] = res.ray.direction.z;
+        o[7] = res.reflectance; o[8] = res.transmitted ? 1.0 : 0.0;
+    }
+    return 0;
+}
+// importance_sample_ggx_half (material.rs:260-269) and the GGX bounce's scalar f * saturate(g * v.h / (h.n * v.n)) (material.rs:123-141) from its
+// four dot products — the pieces precise shading spells in f64 (csrc/prec_core.h)
+ORC_API int orc_ggx_half_n(size_t n, const double *r0, const double *r1, const double *normal, const double *alpha2, double *out) {
+    for (size_t i = 0; i < n; i++) {
+        V3 h = importance_sample_ggx_half(r0[i], r1[i], V3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]), alpha2[i]);
+        out[3 * i] = h.x; out[3 * i + 1] = h.y; out[3 * i + 2] = h.z;
+    }
+    return 0;
+}
+ORC_API int orc_ggx_scalar_n(size_t n, const double *ln, const double *vn, const double *vh, const double *hn, const double *alpha2, const double *f0, double *out) {
+    for (size_t i = 0; i < n; i++) out[i] = f_schlick(vh[i], f0[i]) * saturate(g_smith_joint(ln[i], vn[i], alpha2[i]) * vh[i] / (hn[i] * vn[i]));
+    return 0;
+}
 
 // material / texture lookups for unit tests: sample a skybox direction
 ORC_API int orc_skybox_sample(const orc_scene *os, const double *dir, double *rgb) {

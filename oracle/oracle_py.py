@@ -40,6 +40,10 @@ def lib():
         L.orc_material_sample.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_material_bsdf.argtypes = [C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_material_bsdf.restype = C.c_double
+        L.orc_material_bsdf_n.argtypes = [C.c_size_t] + [C.c_void_p] * 7
+        L.orc_material_sample_n.argtypes = [C.c_size_t] + [C.c_void_p] * 9
+        L.orc_ggx_half_n.argtypes = [C.c_size_t] + [C.c_void_p] * 5
+        L.orc_ggx_scalar_n.argtypes = [C.c_size_t] + [C.c_void_p] * 7
         L.orc_skybox_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_image_sample_bilinear.argtypes = [C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_void_p]
         L.orc_bvh_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -185,6 +189,51 @@ def material_sample(surface, param, roughness, r0, r1, position, view, normal):
 def material_bsdf(surface, param, roughness, view, normal, light):
     v, n, l = (np.ascontiguousarray(a, dtype=np.float64) for a in (view, normal, light))
     return lib().orc_material_bsdf(surface, param, roughness, v.ctypes.data, n.ctypes.data, l.ctypes.data)
+
+
+def _f64(a, shape):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    assert a.shape == shape, (a.shape, shape)
+    return a
+
+
+def material_bsdf_n(surface, param, roughness, view, normal, light):
+    """material_bsdf on n points: surface [n] int, param / roughness [n], view / normal / light [n, 3] -> [n] float64."""
+    s = np.ascontiguousarray(surface, dtype=np.int32)
+    n = len(s)
+    p, r = _f64(param, (n,)), _f64(roughness, (n,))
+    v, nn, l = _f64(view, (n, 3)), _f64(normal, (n, 3)), _f64(light, (n, 3))
+    out = np.empty(n, dtype=np.float64)
+    lib().orc_material_bsdf_n(n, s.ctypes.data, p.ctypes.data, r.ctypes.data, v.ctypes.data, nn.ctypes.data, l.ctypes.data, out.ctypes.data)
+    return out
+
+
+def material_sample_n(surface, param, roughness, r0, r1, position, view, normal):
+    """material_sample on n points -> [n, 9] float64 {some, origin xyz, direction xyz, reflectance, transmitted}."""
+    s = np.ascontiguousarray(surface, dtype=np.int32)
+    n = len(s)
+    p, r, a, b = _f64(param, (n,)), _f64(roughness, (n,)), _f64(r0, (n,)), _f64(r1, (n,))
+    pos, v, nn = _f64(position, (n, 3)), _f64(view, (n, 3)), _f64(normal, (n, 3))
+    out = np.empty((n, 9), dtype=np.float64)
+    lib().orc_material_sample_n(n, s.ctypes.data, p.ctypes.data, r.ctypes.data, a.ctypes.data, b.ctypes.data, pos.ctypes.data, v.ctypes.data,
+                                nn.ctypes.data, out.ctypes.data)
+    return out
+
+
+def ggx_half_n(r0, r1, normal, alpha2):
+    n = len(r0)
+    a, b, nn, a2 = _f64(r0, (n,)), _f64(r1, (n,)), _f64(normal, (n, 3)), _f64(alpha2, (n,))
+    out = np.empty((n, 3), dtype=np.float64)
+    lib().orc_ggx_half_n(n, a.ctypes.data, b.ctypes.data, nn.ctypes.data, a2.ctypes.data, out.ctypes.data)
+    return out
+
+
+def ggx_scalar_n(ln, vn, vh, hn, alpha2, f0):
+    n = len(ln)
+    arrs = [_f64(x, (n,)) for x in (ln, vn, vh, hn, alpha2, f0)]
+    out = np.empty(n, dtype=np.float64)
+    lib().orc_ggx_scalar_n(n, *[x.ctypes.data for x in arrs], out.ctypes.data)
+    return out
 
 
 def isaac64(seed, count, skip=0):
