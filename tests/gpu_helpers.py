@@ -48,9 +48,9 @@ def options(renderer, opts=None, dbg=None):
 
 
 def bits(a):
-    """the array's bit patterns (4- and 8-byte element types)"""
+    """the array's bit patterns (1-, 4- and 8-byte element types)"""
     a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 def same(a, b):

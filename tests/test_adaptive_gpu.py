@@ -8,7 +8,8 @@ import pytest
 import ckpt
 from cli import ASSETS, run_cli
 from gpu_helpers import error_of, renderer, retarget, same
-from test_moments_cpu import ulp_distance
+from post_numpy import noise_reference as _noise_reference
+from post_numpy import ulp_distance
 
 pytestmark = pytest.mark.gpu
 
@@ -172,18 +173,6 @@ def test_resolve_counted(ha, scenes, name):
             got = r.resolve_counted()
             r.write_sample_counts(np.full((RH, RW), S))
             assert np.array_equal(got, r.resolve(S)) and np.array_equal(got, r.resolve_counted())
-
-
-def _noise_reference(mom, n, floor):
-    """tests/test_moments_cpu.py's restatement of the definition with a count per pixel."""
-    mom = np.asarray(mom, dtype=np.float64)
-    n = np.asarray(n, dtype=np.float64)[..., None]
-    s1, s2 = mom[..., 0:3], mom[..., 3:6]
-    m = s1 / n
-    var = np.maximum(0.0, (s2 - s1 * m) / (n - 1.0))
-    se = np.sqrt(var / n) / 4.0
-    mu = m / 4.0
-    return ((se[..., 0] + se[..., 1]) + se[..., 2]) / (((mu[..., 0] + mu[..., 1]) + mu[..., 2]) + 3.0 * np.float64(floor))
 
 
 def _tile_max(img):

@@ -10,7 +10,8 @@ import pytest
 import ckpt
 from cli import ASSETS, run_cli
 from gpu_helpers import error_of, renderer, same
-from test_denoise_cpu import DEFAULTS, core, core_denoise, synthetic_inputs  # noqa: F401  (core: the g++-built harness, a fixture)
+from post_cores import core, core_denoise  # noqa: F401  (core: the g++-built harness, a fixture)
+from post_numpy import synthetic_inputs
 
 pytestmark = pytest.mark.gpu
 

@@ -7,7 +7,7 @@ Shapes: an 80x45 frame (20x12 tiles, the bottom row of tiles overhangs) and a 5x
 import numpy as np
 import pytest
 
-import test_robust_cpu as rc
+import post_cores as pc
 from gpu_helpers import error_of, retarget, same
 
 pytestmark = pytest.mark.gpu
@@ -160,8 +160,8 @@ def test_same_device_fold_is_rank_order_addition_to_the_bit(ha, scenes):
         _close(rs)
 
 
-def test_fold_equals_one_context_within_the_rounding_bound(ha, scenes, tmp_path):
-    core = rc.build_core(tmp_path)
+def test_fold_equals_one_context_within_the_rounding_bound(ha, scenes):
+    core = pc.lib()
     rs = _contexts(ha, scenes(SCENE)[0], 4)
     one, rs = rs[3], rs[:3]
     try:
@@ -181,7 +181,7 @@ def test_fold_equals_one_context_within_the_rounding_bound(ha, scenes, tmp_path)
             assert np.abs(acc - racc).max() <= 1e-5 * max(1.0, np.abs(racc).max()), target
             # R of rank 0 is the CPU definition's R of the buckets rank 0 holds, bit for bit (no trim decision is judged across two roundings)
             rs[0].robust()
-            R, trim = rc.core_robust(core, got["buckets"][0], got["sample_counts"][0])
+            R, trim = pc.core_robust(core, got["buckets"][0], got["sample_counts"][0])
             assert same(rs[0].read_robust(), R) and np.array_equal(rs[0].read_robust_trim(), trim), target
             assert R.any()
     finally:

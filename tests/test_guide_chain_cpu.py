@@ -8,7 +8,7 @@ import pytest
 
 import guide_chain as gc
 from cli import run_cli
-from test_denoise_cpu import bits
+from gpu_helpers import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 48, 27

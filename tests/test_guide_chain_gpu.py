@@ -10,7 +10,7 @@ import pytest
 import guide_chain as gc
 from cli import ASSETS, run_cli
 from gpu_helpers import bits, error_of, renderer, same
-from test_denoise_cpu import core, core_denoise  # noqa: F401  (core: the g++-built filter harness, a fixture)
+from post_cores import core, core_denoise  # noqa: F401  (core: the g++-built filter harness, a fixture)
 from test_guide_chain_cpu import harness  # noqa: F401  (the g++-built host form, a fixture)
 
 pytestmark = pytest.mark.gpu

@@ -9,7 +9,7 @@ import pytest
 import ckpt
 from cli import ASSETS, run_cli
 from gpu_helpers import error_of, renderer, same
-from test_moments_cpu import noise_reference, ulp_distance
+from post_numpy import noise_reference, ulp_distance
 
 pytestmark = pytest.mark.gpu
 

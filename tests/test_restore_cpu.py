@@ -2,221 +2,22 @@
 csrc/restore_core.h compiled for the host against an independent numpy restatement of their definition — bit for bit: + - x / max and comparisons
 in f64 without contraction —, the properties of the excess X, exact impulse cases, the conservation of the spread energy within a bound derived
 from the operation count, the quality figures on the checker's per-sampling renders, and the entry points declared, exported and bound."""
-import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import test_denoise_cpu as dn
-import test_robust_denoise_cpu as rd
+import interface_checks as ic
 from cli import run_cli
-from test_robust_cpu import bits, fill_buckets, heavy_tailed, rel_sq_error
+from post_cores import core, core_excess, core_r, core_restore, core_spread  # noqa: F401  (core: the g++-built harness, a fixture)
+from post_numpy import ALL_K
+from post_numpy import RESTORE_DEFAULTS as DEFAULTS
+from post_numpy import bits, flat_guides, heavy_tailed, numpy_excess, numpy_restore, numpy_spread, synthetic_buckets, synthetic_inputs, tie_pixel
+from post_quality import SHORT_N as QN
+from post_quality import oracle_short_render, restore_figures
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ALL_K = rd.ALL_K
-TINY = 1e-30
-DEFAULTS = {"levels": 4, "base": 0, "sigma_n": 0.5, "sigma_a": 0.25, "sigma_z": 0.1}
 U = 2.0 ** -53
-
-HARNESS = r'''
-#include <vector>
-#include "restore_core.h"
-using namespace hr;
-// counts may be null (every pixel: n_all)
-extern "C" void excess_run(const double *buckets, const uint32_t *counts, uint64_t n_all, uint32_t K, uint64_t pixels, double *cx, uint8_t *trim) {
-    for (size_t p = 0; p < pixels; p++) robust_pixel_excess(buckets + p * K * 3, K, counts ? (uint64_t)counts[p] : n_all, cx + p * 6, trim + p);
-}
-// sig = {sigma_n, sigma_a, sigma_z}; D (may be null): the base; x_out (may be null): X_L, w*h*3 doubles
-extern "C" void restore_run(const double *buckets, const uint32_t *counts, uint64_t n_all, uint32_t K, const float *guides, uint32_t w, uint32_t h, uint32_t levels,
-                            const double *sig, const float *D, float *r, double *x_out) {
-    std::vector<double> work((size_t)w * h * 15);
-    restore_image(buckets, counts, n_all, K, guides, w, h, levels, denoise_sigmas(1.0, sig[0], sig[1], sig[2]), D, work.data(), r, x_out);
-}
-// the spread alone on a given excess X[h][w][3] -> out[h][w][3]
-extern "C" void spread_run(const double *X, const float *guides, uint32_t w, uint32_t h, uint32_t levels, const double *sig, double *out) {
-    const size_t pixels = (size_t)w * h;
-    const DenoiseSigmas sg = denoise_sigmas(1.0, sig[0], sig[1], sig[2]);
-    std::vector<double> a(X, X + pixels * 3), b(pixels * 3), S(pixels * 3);
-    for (uint32_t l = 0; l < levels; l++) {
-        for (uint32_t y = 0; y < h; y++)
-            for (uint32_t x = 0; x < w; x++) restore_norm(a.data(), 3, guides, w, h, x, y, 1u << l, sg, S.data() + ((size_t)y * w + x) * 3);
-        for (uint32_t y = 0; y < h; y++)
-            for (uint32_t x = 0; x < w; x++) restore_gather(S.data(), guides, w, h, x, y, 1u << l, sg, b.data() + ((size_t)y * w + x) * 3);
-        a.swap(b);
-    }
-    for (size_t i = 0; i < pixels * 3; i++) out[i] = a[i];
-}
-'''
-
-
-def build_core(directory):
-    src, so = directory / "restore_harness.cpp", directory / "librestore_harness.so"
-    src.write_text(HARNESS)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "hanamaru-renderer_amd", "csrc"), "-o", str(so), str(src)], check=True)
-    lib = C.CDLL(str(so))
-    lib.excess_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.restore_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.spread_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return build_core(tmp_path_factory.mktemp("restore"))
-
-
-@pytest.fixture(scope="module")
-def rcore(tmp_path_factory):
-    return rd.build_core(tmp_path_factory.mktemp("restore_robust"))
-
-
-def _sig(params):
-    return np.array([params["sigma_n"], params["sigma_a"], params["sigma_z"]], dtype=np.float64)
-
-
-def core_excess(lib, buckets, n):
-    """robust_pixel_excess over buckets (.., K, 3); n: one count or per-pixel counts.  Returns (cx float64 (.., 6), trim uint8 (..))."""
-    b, K, shape, counts, cp, n_all = rd._image_args(buckets, n)
-    cx, trim = np.zeros(shape + (6,)), np.zeros(shape, dtype=np.uint8)
-    lib.excess_run(b.ctypes.data, cp, n_all, K, int(np.prod(shape, dtype=np.int64)), cx.ctypes.data, trim.ctypes.data)
-    return cx, trim
-
-
-def core_restore(lib, buckets, n, guides, D=None, want_x=False, **over):
-    """restore_image over an (h, w, K, 3) image of buckets; D: the base of base 1 (h, w, 3) float32."""
-    params = dict(DEFAULTS, **over)
-    b, K, shape, counts, cp, n_all = rd._image_args(buckets, n)
-    h, w = shape
-    guides = np.ascontiguousarray(guides, dtype=np.float32)
-    assert guides.shape == (h, w, 8) and (D is not None) == bool(params["base"])
-    if D is not None:
-        D = np.ascontiguousarray(D, dtype=np.float32)
-        assert D.shape == (h, w, 3)
-    r = np.zeros((h, w, 3), dtype=np.float32)
-    x = np.zeros((h, w, 3)) if want_x else None
-    sig = _sig(params)
-    lib.restore_run(b.ctypes.data, cp, n_all, K, guides.ctypes.data, w, h, int(params["levels"]), sig.ctypes.data, D.ctypes.data if D is not None else None,
-                    r.ctypes.data, x.ctypes.data if want_x else None)
-    return (r, x) if want_x else r
-
-
-def core_spread(lib, X, guides, **over):
-    params = dict(DEFAULTS, **over)
-    X = np.ascontiguousarray(X, dtype=np.float64)
-    h, w = X.shape[:2]
-    guides = np.ascontiguousarray(guides, dtype=np.float32)
-    assert guides.shape == (h, w, 8) and X.shape == (h, w, 3)
-    out = np.zeros((h, w, 3))
-    sig = _sig(params)
-    lib.spread_run(X.ctypes.data, guides.ctypes.data, w, h, int(params["levels"]), sig.ctypes.data, out.ctypes.data)
-    return out
-
-
-# ---- the numpy restatement ----
-def numpy_excess(buckets, n):
-    """The definition in the comment of restore_core.h, restated on whole arrays: every line one IEEE f64 operation per element, every sum sequential
-    from its first term.  Every n >= K.  Returns (cx (.., 6), trim)."""
-    B = np.asarray(buckets, dtype=np.float64)
-    K, shape = B.shape[-2], B.shape[:-2]
-    B = B.reshape(-1, K, 3)
-    P = B.shape[0]
-    n = np.broadcast_to(np.asarray(n, dtype=np.uint64).reshape(-1), (P,))
-    assert (n >= K).all()
-    with np.errstate(divide="ignore", invalid="ignore", under="ignore"):
-        nb = (n[:, None] - np.arange(K, dtype=np.uint64)[None, :] + np.uint64(K - 1)) // np.uint64(K)
-        m = B / nb.astype(np.float64)[..., None] / 4.0
-        y = (m[..., 0] + m[..., 1]) + m[..., 2]
-        order = np.argsort(y, axis=1, kind="stable")                                  # ascending by (y, b)
-        ys = np.take_along_axis(y, order, 1)
-        ms = np.take_along_axis(m, order[..., None], 1)
-        T = ys[:, 0].copy()
-        Gn = float(1 - K) * ys[:, 0]
-        for i in range(2, K + 1):
-            T = T + ys[:, i - 1]
-            Gn = Gn + float(2 * i - K - 1) * ys[:, i - 1]
-        G = Gn / (float(K) * T)
-        want = np.trunc(np.where((T > 0.0) & (G > 0.0), G * float(K) / 2.0, 0.0)).astype(np.int64)
-        trim = np.minimum((K - 1) // 2, want)
-        cx = np.zeros((P, 6))
-        for t in range((K - 1) // 2 + 1):
-            s = ms[:, t, :].copy()
-            for i in range(t + 1, K - t):
-                s = s + ms[:, i, :]
-            Cc = s / float(K - 2 * t)
-            X = np.zeros((P, 3))
-            if t:
-                top = ms[:, K - 1 - t, :]
-                e = ms[:, K - t, :] - top
-                for i in range(K - t + 1, K):
-                    e = e + (ms[:, i, :] - top)
-                q = e / float(K)
-                X = np.where(q > 0.0, q, 0.0)
-            cx = np.where((trim == t)[:, None], np.concatenate([Cc, X], axis=1), cx)
-    return cx.reshape(shape + (6,)), trim.astype(np.uint8).reshape(shape)
-
-
-def _tap_weight(g, P, Q, i, j, sn2, sa2, sz2):
-    A, N, Z, H = g[..., 0:3], g[..., 3:6], g[..., 6], g[..., 7]
-    k = (0.375, 0.25, 0.0625)
-    d = N[P] - N[Q]
-    xn = ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) / sn2
-    d = A[P] - A[Q]
-    xa = ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) / sa2
-    dz = Z[P] - Z[Q]
-    xz = (dz * dz) / (sz2 * (Z[P] * Z[P] + Z[Q] * Z[Q]) + TINY)
-    dh = H[P] - H[Q]
-    xh = dh * dh
-    return ((((k[abs(i)] * k[abs(j)]) * dn._weight(xn)) * dn._weight(xa)) * dn._weight(xz)) * dn._weight(xh)
-
-
-def _taps(h, w, s):
-    for j in range(-2, 3):
-        for i in range(-2, 3):
-            dx, dy = s * i, s * j
-            y0, y1, x0, x1 = max(0, -dy), min(h, h - dy), max(0, -dx), min(w, w - dx)
-            if y0 < y1 and x0 < x1:                                                   # (else the tap is outside the image for every pixel: skipped)
-                yield i, j, (slice(y0, y1), slice(x0, x1)), (slice(y0 + dy, y1 + dy), slice(x0 + dx, x1 + dx))
-
-
-def numpy_spread(X, guides, **over):
-    """restore_norm and restore_gather, level by level, on an excess X (h, w, 3)."""
-    p = dict(DEFAULTS, **over)
-    g = np.asarray(guides, dtype=np.float32).astype(np.float64)
-    X = np.asarray(X, dtype=np.float64)
-    h, w = X.shape[:2]
-    sn2, sa2, sz2 = p["sigma_n"] * p["sigma_n"], p["sigma_a"] * p["sigma_a"], p["sigma_z"] * p["sigma_z"]
-    with np.errstate(under="ignore"):
-        for lev in range(int(p["levels"])):
-            N = np.zeros((h, w))
-            for i, j, P, Q in _taps(h, w, 1 << lev):
-                N[P] = N[P] + _tap_weight(g, P, Q, i, j, sn2, sa2, sz2)
-            S = X / N[..., None]
-            out = np.zeros((h, w, 3))
-            for i, j, P, Q in _taps(h, w, 1 << lev):
-                out[P] = out[P] + _tap_weight(g, P, Q, i, j, sn2, sa2, sz2)[..., None] * S[Q]
-            X = out
-    return X
-
-
-def numpy_restore(buckets, n, guides, D=None, **over):
-    cx, _ = numpy_excess(buckets, n)
-    x = numpy_spread(cx[..., 3:6], guides, **over)
-    base = cx[..., 0:3] if D is None else np.asarray(D, dtype=np.float32).astype(np.float64)
-    return (base + x).astype(np.float32), x
-
-
-def flat_guides(w, h):
-    g = np.zeros((h, w, 8), dtype=np.float32)
-    g[..., 0:3] = 0.5
-    g[..., 5] = 1.0
-    g[..., 6] = 4.0
-    g[..., 7] = 1.0
-    return g
 
 
 # ---- 1. the header against numpy ----
@@ -225,30 +26,30 @@ def test_excess_against_numpy(core, K):
     shape = (23, 37)
     trimmed = 0
     for n in (K, 2 * K - 1, 64):
-        B = rd.synthetic_buckets(200 + K, K, shape, n)                                # the planted cases: equal buckets, one hot bucket, zeros,
+        B = synthetic_buckets(200 + K, K, shape, n)                                # the planted cases: equal buckets, one hot bucket, zeros,
         got, ref = core_excess(core, B, n), numpy_excess(B, n)                        # negative sums, tiny values, equal keys straddling the trim
         assert np.array_equal(bits(got[0]), bits(ref[0])) and np.array_equal(got[1], ref[1]), (K, n)
         assert np.isfinite(got[0]).all()
         trimmed += int((got[0][..., 3:6] > 0).sum())
     assert trimmed > 0
     counts = np.random.default_rng(K).integers(K, 3 * K + 3, size=shape).astype(np.uint32)
-    B = rd.synthetic_buckets(300 + K, K, shape, counts)
+    B = synthetic_buckets(300 + K, K, shape, counts)
     got, ref = core_excess(core, B, counts), numpy_excess(B, counts)
     assert np.array_equal(bits(got[0]), bits(ref[0])) and np.array_equal(got[1], ref[1])
-    for X in (rd.tie_pixel()[None], rd.tie_pixel(True)[None]) if K == 9 else ():
+    for X in (tie_pixel()[None], tie_pixel(True)[None]) if K == 9 else ():
         assert np.array_equal(bits(core_excess(core, X, 9)[0]), bits(numpy_excess(X, 9)[0]))
 
 
 # ---- 2. properties of X and C ----
 @pytest.mark.parametrize("K", ALL_K)
-def test_c_is_r_and_x_is_zero_without_a_trim(core, rcore, K):
+def test_c_is_r_and_x_is_zero_without_a_trim(core, K):
     shape = (23, 37)
     counts = np.random.default_rng(K).integers(0, 3 * K + 3, size=shape).astype(np.uint32)
     counts[0, :4] = [0, 1, K - 1, K]
     for n in (K, 2 * K - 1, 64, counts):
-        B = rd.synthetic_buckets(400 + K, K, shape, n)
+        B = synthetic_buckets(400 + K, K, shape, n)
         cx, trim = core_excess(core, B, n)
-        R, tr = rd.core_r(rcore, B, n)
+        R, tr = core_r(core, B, n)
         assert np.array_equal(bits(cx[..., 0:3].astype(np.float32)), bits(R)) and np.array_equal(trim, tr), K   # n = 0 and n < K among the counts
         assert (cx[..., 3:6][trim == 0] == 0).all() and not np.signbit(cx[..., 3:6]).any()
         assert (cx[..., 3:6] >= 0).all()
@@ -283,11 +84,11 @@ SHAPES = [(37, 23), (1, 1), (5, 1), (1, 5)]
 @pytest.mark.parametrize("w,h", SHAPES)
 @pytest.mark.parametrize("K", [3, 9, 15])
 def test_restore_against_numpy(core, w, h, K):
-    g = dn.synthetic_inputs(11, w, h)[3]
+    g = synthetic_inputs(11, w, h)[3]
     counts = np.random.default_rng(w * h + K).integers(K, 3 * K + 3, size=(h, w)).astype(np.uint32)
     D = np.random.default_rng(K).gamma(2.0, 0.5, size=(h, w, 3)).astype(np.float32)
     for n in (2 * K + 1, counts):
-        B = rd.synthetic_buckets(800 + K, K, (h, w), n)
+        B = synthetic_buckets(800 + K, K, (h, w), n)
         for levels in (0, 1, 5):
             for base in (0, 1):
                 got, x = core_restore(core, B, n, g, D=D if base else None, want_x=True, levels=levels, base=base)
@@ -348,7 +149,7 @@ def conservation_bound(levels):
 @pytest.mark.parametrize("levels", [1, 2, 3, 4, 5])
 def test_the_spread_conserves_the_excess(core, levels):
     w, h = 37, 23
-    g = dn.synthetic_inputs(11, w, h)[3]
+    g = synthetic_inputs(11, w, h)[3]
     rng = np.random.default_rng(levels)
     X = heavy_tailed(rng, 1, (h, w))[0].astype(np.float64) * (rng.random((h, w, 1)) < 0.2)
     out = core_spread(core, X, g, levels=levels)
@@ -379,38 +180,18 @@ def test_an_edge_beyond_sigma_keeps_each_side_its_own(core):
 
 
 # ---- 6. quality on the checker's per-sampling renders (the figures of DESIGN.md §4.14, with half the truth set of tools/restore_quality.py) ----
-def restore_figures(core, rcore, x, guides, truth, K):
-    """{R / mean, R' / mean, R' (base DR) / mean, sum R / sum M, sum R' / sum M, R' / R} of the samplings x (n, h, w, 3): relative squared errors against
-    the truth as ratios, and the energy against M, the plain mean of the bucket means."""
-    n = x.shape[0]
-    B = fill_buckets(x, K)
-    acc = np.zeros(x.shape[1:], dtype=np.float32)
-    for s in range(n):
-        acc = acc + x[s]
-    nb = (n - np.arange(K) + K - 1) // K
-    M = (B / nb[:, None] / 4.0).mean(axis=-2)
-    R = rd.core_r(rcore, B, n)[0]
-    Rp = core_restore(core, B, n, guides)
-    DR = rd.core_filter(rcore, B, n, guides)
-    Rpd = core_restore(core, B, n, guides, D=DR, base=1)
-    e_mean = rel_sq_error(acc / np.float32(4 * n), truth)
-    e_r, e_rp, e_rpd = rel_sq_error(R, truth), rel_sq_error(Rp, truth), rel_sq_error(Rpd, truth)
-    return {"R/mean": e_r / e_mean, "R'/mean": e_rp / e_mean, "R'(DR)/mean": e_rpd / e_mean, "sumR/sumM": float(R.astype(np.float64).sum() / M.sum()),
-            "sumR'/sumM": float(Rp.astype(np.float64).sum() / M.sum()), "R'/R": e_rp / e_r}
-
-
 @pytest.mark.parametrize("name", ["rtcamp6_v3_1", "cornell_mini"])
-def test_quality_on_the_oracle(core, rcore, orc, scenes, name):
+def test_quality_on_the_oracle(core, orc, scenes, name):
     """96x54, 16 samplings, guide_bounces 2, default parameters, truth samplings 100001 .. 100512 (the renders test_robust_denoise_cpu.py shares).
     Asserted on rtcamp6_v3_1 at K = 5: R' is closer to the energy of the plain mean than R is, and its error is below the plain mean's.  Everything
     else is printed: R' / R is above 1 — restoring the energy costs error —, and on cornell_mini, which loses under 1 % of its energy, nothing is
     asserted.  Measured, K = 5: rtcamp6_v3_1 sum R / sum M 0.819, sum R' / sum M 0.999, R / mean 0.109, R' / mean 0.238, R' (base DR) / mean 0.223,
     R' / R 2.19; cornell_mini 0.997, 1.000, 0.586, 0.784, 0.663, 1.34.  K = 9: rtcamp6_v3_1 0.724, 1.004, 0.072, 0.246, 0.259, 3.43; cornell_mini
     0.992, 1.000, 0.445, 0.994, 1.034, 2.23 (R' on DR there is WORSE than the plain mean)."""
-    x, _, _, guides, truth = rd.oracle_short_render(orc, scenes, name)
+    x, _, _, guides, truth = oracle_short_render(orc, scenes, name)
     for K in (5, 9):
-        f = restore_figures(core, rcore, x, guides, truth, K)
-        print("%s n=%d K=%d: " % (name, rd.QN, K) + "  ".join("%s %.3f" % kv for kv in f.items()))
+        f = restore_figures(core, x, guides, truth, K)
+        print("%s n=%d K=%d: " % (name, QN, K) + "  ".join("%s %.3f" % kv for kv in f.items()))
         if name == "rtcamp6_v3_1" and K == 5:
             assert abs(f["sumR'/sumM"] - 1.0) < abs(f["sumR/sumM"] - 1.0)
             assert f["R'/mean"] < 1.0
@@ -418,19 +199,16 @@ def test_quality_on_the_oracle(core, rcore, orc, scenes, name):
 
 # ---- 7. plumbing ----
 def test_entry_points_declared_exported_and_bound(ha):
-    raw = open(os.path.join(ROOT, "include", "hanamaru_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"typedef\s+struct\s+hr_restore_params\s*\{\s*uint32_t\s+levels\s*;\s*uint32_t\s+base\s*;\s*double\s+sigma_n\s*,\s*sigma_a\s*,\s*sigma_z\s*;\s*\}\s*hr_restore_params\s*;", text)
-    assert re.search(r"int\s+hr_restore_default_params\s*\(\s*hr_restore_params\s*\*\s*\w+\s*\)\s*;", text)
-    assert re.search(r"int\s+hr_robust_restore\s*\(\s*hr_ctx\s*\*\s*\w*\s*,\s*const\s+hr_restore_params\s*\*\s*\w+\s*\)\s*;", text)
-    assert re.search(r"int\s+hr_read_restored\s*\(\s*hr_ctx\s*\*\s*\w*\s*,\s*float\s*\*\s*\w+\s*\)\s*;", text)
-    assert re.search(r"int\s+hr_resolve_restored\s*\(\s*hr_ctx\s*\*\s*\w*\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;", text)
-    assert int(re.search(r"#define\s+HR_ABI_VERSION\s+(\d+)", text).group(1)) == 7       # functions were added, none changed
-    lib = C.CDLL(ha.HIP_LIB)
-    ffi = open(os.path.join(ROOT, "rust", "hip_ffi.rs")).read()
-    integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    text = ic.header_text()
+    assert ic.declared(text, r"typedef\s+struct\s+hr_restore_params\s*\{\s*uint32_t\s+levels\s*;\s*uint32_t\s+base\s*;\s*double\s+sigma_n\s*,\s*sigma_a\s*,\s*sigma_z\s*;\s*\}\s*hr_restore_params\s*;")
+    assert ic.declared(text, r"int\s+hr_restore_default_params\s*\(\s*hr_restore_params\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_robust_restore\s*\(\s*%s\s*,\s*const\s+hr_restore_params\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_read_restored\s*\(\s*%s\s*,\s*float\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_resolve_restored\s*\(\s*%s\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;")
+    assert ic.abi_version(text) == 7       # functions were added, none changed
+    ffi, integration = ic.rust_ffi(), ic.read("INTEGRATION.md")
     for fn in ("hr_restore_default_params", "hr_robust_restore", "hr_read_restored", "hr_resolve_restored"):
-        assert hasattr(lib, fn), fn
+        assert not ic.exported_and_bound(ha, (fn,)), fn
         assert len(getattr(ha.hip_lib(), fn).argtypes) == (1 if fn == "hr_restore_default_params" else 2)
         assert "pub fn %s(" % fn in ffi and "pub fn %s(" % fn in integration, fn
     assert "size_of::<HrRestoreParams>() == 32" in ffi
@@ -442,8 +220,7 @@ def test_entry_points_declared_exported_and_bound(ha):
 
 
 def test_kernel_rows():
-    kv = open(os.path.join(ROOT, "hanamaru-renderer_amd", "csrc", "kernel_variants.h")).read()
-    pk = open(os.path.join(ROOT, "hanamaru-renderer_amd", "csrc", "post_kernels.h")).read()
+    kv, pk = ic.kernel_variants(), ic.read("hanamaru-renderer_amd", "csrc", "post_kernels.h")
     for K in ALL_K:
         assert "HR_VARIANT(restore_init_kernel, %d)" % K in kv, K
     assert "select_restore_init_kernel" in kv
@@ -454,10 +231,10 @@ def test_kernel_rows():
 def test_cli_help_lists_the_flags(tmp_path):
     r = run_cli(["--help"], tmp_path)
     assert r.returncode == 0
-    readme = open(os.path.join(ROOT, "README.md")).read()
+    readme = ic.read("README.md")
     for flag in ("--robust-restore", "--restore-levels"):
         assert flag in r.stdout and flag in readme, flag
-    tools = open(os.path.join(ROOT, "tools", "README.md")).read()
+    tools = ic.read("tools", "README.md")
     assert "restore_quality.py" in tools and "restore_rate.py" in tools
 
 
@@ -468,7 +245,7 @@ def test_cli_help_lists_the_flags(tmp_path):
                                        (["--robust", "5", "--robust-restore", "--gpus", "2"], "one device"),
                                        (["--robust", "5", "--robust-restore", "--denoise"], "--denoise")])
 def test_cli_refuses_before_any_device(tmp_path, args, word):
-    r = run_cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
+    r, left_a_result = ic.cli_refused(tmp_path, args)
     assert r.returncode == 1, r.stdout
     assert word in r.stdout
-    assert not (tmp_path / "result.txt").exists()
+    assert not left_a_result

@@ -4,26 +4,21 @@ asking changes nothing else, the quality figures on the device, and the CLI."""
 import numpy as np
 import pytest
 
-import test_restore_cpu as rs
-import test_robust_denoise_cpu as rd
+import post_cores as pc
+import post_numpy as pn
 from cli import ASSETS, run_cli
 from gpu_helpers import error_of, renderer, retarget, same
+from post_cores import core  # noqa: F401  (the g++-built harness, a fixture)
+from post_numpy import rel_sq_error, synthetic_inputs
 from test_adaptive_gpu import MASKS
-from test_denoise_cpu import synthetic_inputs
-from test_robust_cpu import rel_sq_error
 
 pytestmark = pytest.mark.gpu
 
 HR_ERR_INVALID = -1
-ALL_K = rd.ALL_K
+ALL_K = pn.ALL_K
 RW, RH = 37, 23
 # the 80 x 45 frame (3,600 pixels: 14 full spans of 256 and one of 16), a 37 x 23 region (851 pixels: a partial last span), one pixel
 TARGETS = {"frame": ((80, 45), None, (80, 45)), "region": ((64, 48), (5, 3, RW, RH), (RW, RH)), "1x1": ((1, 1), None, (1, 1))}
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return rs.build_core(tmp_path_factory.mktemp("restore_gpu"))
 
 
 def _counts(K, shape):
@@ -48,7 +43,7 @@ def test_restored_equals_the_host_core(ha, scenes, core, K):
             for n in (2 * K + 1, _counts(K, (h, w))):
                 per_pixel = not np.isscalar(n)
                 retarget(r, frame, region, counts=per_pixel, buckets=K)
-                B = rd.synthetic_buckets(900 + K, K, (h, w), n)
+                B = pn.synthetic_buckets(900 + K, K, (h, w), n)
                 r.write_buckets(B, int(n.max()) if per_pixel else n)
                 if per_pixel:
                     r.write_sample_counts(n)
@@ -58,13 +53,13 @@ def test_restored_equals_the_host_core(ha, scenes, core, K):
                 for levels in (0, 1, 4):
                     for base in (0, 1):
                         r.robust_restore(levels=levels, base=base)
-                        want = rs.core_restore(core, B, n, g, D=D if base else None, levels=levels, base=base)
+                        want = pc.core_restore(core, B, n, g, D=D if base else None, levels=levels, base=base)
                         assert same(r.read_restored(), want), (K, target, per_pixel, levels, base)
                 assert same(r.read_denoised(), D)                                      # D is still valid, and the same
                 if target == "frame" and not per_pixel:
-                    assert not same(rs.core_restore(core, B, n, g, levels=4), rs.core_restore(core, B, n, g, levels=0))
+                    assert not same(pc.core_restore(core, B, n, g, levels=4), pc.core_restore(core, B, n, g, levels=0))
                     r.robust()
-                    assert not same(rs.core_restore(core, B, n, g, levels=0), r.read_robust())   # X is somewhere
+                    assert not same(pc.core_restore(core, B, n, g, levels=0), r.read_robust())   # X is somewhere
 
 
 # ---------------------------------------------------------------------------------------------------------------- entry points and state
@@ -92,11 +87,11 @@ def test_levels_zero_without_a_trim_is_the_robust_image(ha, scenes, core, K):
             assert trims or K != 9
             r.robust_restore(levels=0)
             B, n = r.read_buckets()
-            assert n == 20 and same(r.read_restored(), rs.core_restore(core, B, n, r.read_guides(), levels=0))
+            assert n == 20 and same(r.read_restored(), pc.core_restore(core, B, n, r.read_guides(), levels=0))
             assert r.read_guides().any() and same(r.read_restored(), R) == (not trims)  # the call rendered the guides; X is where a pixel trims
             assert same(r.read_robust(), R)                                            # R is still valid
             r.robust_restore()
-            assert same(r.read_restored(), rs.core_restore(core, B, n, r.read_guides()))
+            assert same(r.read_restored(), pc.core_restore(core, B, n, r.read_guides()))
             if trims:
                 assert r.read_restored().astype(np.float64).sum() > R.astype(np.float64).sum()
             else:
@@ -120,7 +115,7 @@ def test_refusals_touch_nothing(ha, scenes):
         assert _err(ha, r.read_restored) == HR_ERR_INVALID and _err(ha, r.resolve_restored) == HR_ERR_INVALID
         r.set_option("robust_buckets", K)
         counts = _counts(K, (h, w))
-        B = rd.synthetic_buckets(1, K, (h, w), counts)
+        B = pn.synthetic_buckets(1, K, (h, w), counts)
         r.write_buckets(B, int(counts.max()))
         r.write_sample_counts(counts)
         r.write_guides(g)

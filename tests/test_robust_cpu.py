@@ -1,118 +1,18 @@
 """Sample buckets and the firefly-robust resolve on the CPU tier: csrc/robust_core.h compiled for the host against an independent
 numpy restatement of the definition in include/hanamaru_hip.h — bit for bit: the estimator is + - x /, comparisons and one truncation in f64 without
 contraction —, its corner cases, its quality on the checker's per-sampling renders, and the entry points declared, exported and bound."""
-import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import interface_checks as ic
 from cli import run_cli
+from post_cores import core, core_robust  # noqa: F401  (core: the g++-built harness, a fixture)
+from post_numpy import bits, fill_buckets, heavy_tailed, numpy_robust, rel_sq_error
+from post_quality import QH, QK, QN, QTRUTH, QW, oracle_buckets_and_truth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("hr_read_buckets", "hr_write_buckets", "hr_robust", "hr_read_robust", "hr_read_robust_trim", "hr_resolve_robust")
-
-HARNESS = r'''
-#include "robust_core.h"
-using namespace hr;
-// counts may be null (every pixel: n_all)
-extern "C" void robust_run(const double *buckets, const uint32_t *counts, uint64_t n_all, uint32_t K, uint64_t pixels, float *R, uint8_t *trim) {
-    robust_image(buckets, counts, n_all, K, (size_t)pixels, R, trim);
-}
-extern "C" int robust_k_ok(double k) { return robust_valid_k(k) ? 1 : 0; }
-'''
-
-
-def build_core(directory):
-    src, so = directory / "robust_harness.cpp", directory / "librobust_harness.so"
-    src.write_text(HARNESS)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "hanamaru-renderer_amd", "csrc"), "-o", str(so), str(src)], check=True)
-    lib = C.CDLL(str(so))
-    lib.robust_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.robust_k_ok.argtypes = [C.c_double]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return build_core(tmp_path_factory.mktemp("robust"))
-
-
-def core_robust(lib, buckets, n):
-    """The host-compiled core over an image of buckets (.., K, 3).  n: one count for every pixel, or an array of per-pixel counts.
-    Returns (R float32 (.., 3), trim uint8 (..))."""
-    b = np.ascontiguousarray(buckets, dtype=np.float64)
-    K, shape = b.shape[-2], b.shape[:-2]
-    assert b.shape[-1] == 3
-    pixels = int(np.prod(shape, dtype=np.int64))
-    counts = None if np.isscalar(n) else np.ascontiguousarray(n, dtype=np.uint32)
-    assert counts is None or counts.shape == shape
-    R = np.zeros(shape + (3,), dtype=np.float32)
-    trim = np.zeros(shape, dtype=np.uint8)
-    lib.robust_run(b.ctypes.data, counts.ctypes.data if counts is not None else None, int(n) if counts is None else 0, K, pixels, R.ctypes.data, trim.ctypes.data)
-    return R, trim
-
-
-def numpy_robust(buckets, n):
-    """include/hanamaru_hip.h's definition, restated on whole arrays: every line one IEEE f64 operation per element, every sum sequential."""
-    B = np.asarray(buckets, dtype=np.float64)
-    K, shape = B.shape[-2], B.shape[:-2]
-    B = B.reshape(-1, K, 3)
-    P = B.shape[0]
-    n = np.broadcast_to(np.asarray(n, dtype=np.uint64).reshape(-1), (P,))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        s = B[:, 0, :].copy()
-        for b in range(1, K):
-            s = s + B[:, b, :]
-        plain = s / n.astype(np.float64)[:, None] / 4.0
-        nn = np.maximum(n, np.uint64(K))                                              # (where n < K the robust branch is not taken)
-        nb = (nn[:, None] - np.arange(K, dtype=np.uint64)[None, :] + np.uint64(K - 1)) // np.uint64(K)
-        m = B / nb.astype(np.float64)[..., None] / 4.0
-        y = (m[..., 0] + m[..., 1]) + m[..., 2]
-        order = np.argsort(y, axis=1, kind="stable")                                  # ascending by (y, b)
-        ys = np.take_along_axis(y, order, 1)
-        ms = np.take_along_axis(m, order[..., None], 1)
-        T = ys[:, 0].copy()
-        Gn = float(1 - K) * ys[:, 0]
-        for i in range(2, K + 1):
-            T = T + ys[:, i - 1]
-            Gn = Gn + float(2 * i - K - 1) * ys[:, i - 1]
-        G = Gn / (float(K) * T)
-        want = np.trunc(np.where((T > 0.0) & (G > 0.0), G * float(K) / 2.0, 0.0)).astype(np.int64)
-        trim = np.minimum((K - 1) // 2, want)
-        robust = np.zeros((P, 3))
-        for t in range((K - 1) // 2 + 1):
-            s = ms[:, t, :].copy()
-            for i in range(t + 1, K - t):
-                s = s + ms[:, i, :]
-            robust = np.where((trim == t)[:, None], s / float(K - 2 * t), robust)
-    small = (n < np.uint64(K))[:, None]
-    R = np.where((n == 0)[:, None], 0.0, np.where(small, plain, robust)).astype(np.float32)
-    trim = np.where(small[:, 0], 0, trim).astype(np.uint8)
-    return R.reshape(shape + (3,)), trim.reshape(shape)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def fill_buckets(x, K, start=0):
-    """The bucket sums of per-sampling values x (n, .., 3), fp32, one sampling at a time in f64: sampling j into bucket (start + j) mod K."""
-    B = np.zeros(x.shape[1:-1] + (K, 3))
-    for j in range(x.shape[0]):
-        B[..., (start + j) % K, :] += x[j].astype(np.float32).astype(np.float64)
-    return B
-
-
-def heavy_tailed(rng, n, shape):
-    """Per-sampling values with rare very bright outliers: what NEE to a small emitter without MIS produces."""
-    x = rng.gamma(2.0, 0.5, size=(n,) + shape + (3,))
-    hot = rng.random((n,) + shape + (1,)) < 0.03
-    return np.where(hot, x * 400.0, x).astype(np.float32)
 
 
 @pytest.mark.parametrize("K", [3, 9, 15])
@@ -210,23 +110,6 @@ def test_valid_k(core):
 
 
 # ---- quality on the checker's per-sampling renders (the figures of DESIGN.md §4.10, with a shorter truth set) ----
-QW, QH, QN, QK, QTRUTH = 48, 27, 64, 9, 2048
-
-
-def rel_sq_error(x, t):
-    return float(np.mean((x.astype(np.float64) - t) ** 2 / (t ** 2 + 0.01 ** 2)))
-
-
-def oracle_buckets_and_truth(osc, w, h, n, ks, truth_n, truth_begin=100001):
-    """({K: buckets of samplings 1 .. n}, fp32 accumulator of them, truth radiance from truth_n samplings starting at truth_begin)."""
-    x = np.stack([osc.render(w, h, s, s + 1)[0] for s in range(1, n + 1)]).astype(np.float32)    # x_s: one sampling's 2x2 sum per pixel
-    acc = np.zeros((h, w, 3), dtype=np.float32)
-    for s in range(n):
-        acc = acc + x[s]
-    truth, _ = osc.render(w, h, truth_begin, truth_begin + truth_n)
-    return {K: fill_buckets(x, K) for K in ks}, acc, truth.astype(np.float64) / (4.0 * truth_n)
-
-
 @pytest.mark.parametrize("name,measured", [("rtcamp6_v3_1", 0.034), ("cornell_mini", 0.297)])
 def test_quality_on_the_oracle(core, scenes, name, measured):
     _, osc = scenes(name)
@@ -250,34 +133,30 @@ def test_a_quiet_scene_is_left_alone(core, scenes):
 
 # ---- interface ----
 def test_entry_points_declared_exported_and_bound(ha):
-    raw = open(os.path.join(ROOT, "include", "hanamaru_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    c = r"hr_ctx\s*\*\s*\w*"
-    assert re.search(r"int\s+hr_read_buckets\s*\(\s*%s\s*,\s*double\s*\*\s*\w+\s*,\s*uint64_t\s*\*\s*\w+\s*\)\s*;" % c, text)
-    assert re.search(r"int\s+hr_write_buckets\s*\(\s*%s\s*,\s*const\s+double\s*\*\s*\w+\s*,\s*uint64_t\s+\w+\s*\)\s*;" % c, text)
-    assert re.search(r"int\s+hr_robust\s*\(\s*%s\s*\)\s*;" % c, text)
-    assert re.search(r"int\s+hr_read_robust\s*\(\s*%s\s*,\s*float\s*\*\s*\w+\s*\)\s*;" % c, text)
-    assert re.search(r"int\s+hr_read_robust_trim\s*\(\s*%s\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;" % c, text)
-    assert re.search(r"int\s+hr_resolve_robust\s*\(\s*%s\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;" % c, text)
-    assert int(re.search(r"#define\s+HR_ABI_VERSION\s+(\d+)", text).group(1)) == 7       # functions were added, none changed
+    raw, text = ic.header_text(raw=True), ic.header_text()
+    assert ic.declared(text, r"int\s+hr_read_buckets\s*\(\s*%s\s*,\s*double\s*\*\s*\w+\s*,\s*uint64_t\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_write_buckets\s*\(\s*%s\s*,\s*const\s+double\s*\*\s*\w+\s*,\s*uint64_t\s+\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_robust\s*\(\s*%s\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_read_robust\s*\(\s*%s\s*,\s*float\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_read_robust_trim\s*\(\s*%s\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_resolve_robust\s*\(\s*%s\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;")
+    assert ic.abi_version(text) == 7       # functions were added, none changed
     assert "448 MB" in raw                                                              # the memory figure
-    debug = open(os.path.join(ROOT, "include", "hanamaru_hip_debug.h")).read()
+    debug = ic.read("include", "hanamaru_hip_debug.h")
     assert "robust" not in debug and "bucket" not in debug
-    lib = C.CDLL(ha.HIP_LIB)
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
+    assert not ic.exported_and_bound(ha, ENTRY_POINTS)
     for m in ("read_buckets", "write_buckets", "robust", "read_robust", "read_robust_trim", "resolve_robust"):
         assert callable(getattr(ha.Renderer, m, None)), m
     L = ha.hip_lib()
     assert len(L.hr_read_buckets.argtypes) == 3 and len(L.hr_write_buckets.argtypes) == 3 and len(L.hr_robust.argtypes) == 1
     assert len(L.hr_read_robust.argtypes) == 2 and len(L.hr_read_robust_trim.argtypes) == 2 and len(L.hr_resolve_robust.argtypes) == 2
-    ffi = open(os.path.join(ROOT, "rust", "hip_ffi.rs")).read()
+    ffi = ic.rust_ffi()
     for name in ENTRY_POINTS:
         assert re.search(r"pub fn %s\(ctx: \*mut HrCtx" % name, ffi), name
 
 
 def test_bucket_kernel_rows():
-    kv = open(os.path.join(ROOT, "hanamaru-renderer_amd", "csrc", "kernel_variants.h")).read()
+    kv = ic.kernel_variants()
     for row in ("HR_VARIANT(bucket_kernel, false, false)", "HR_VARIANT(bucket_kernel, true, false)", "HR_VARIANT(bucket_kernel, true, true)"):
         assert row in kv, row
     assert "select_bucket_kernel" in kv
@@ -291,7 +170,7 @@ def test_cli_help_lists_the_robust_flags(tmp_path):
     assert r.returncode == 0
     for flag in ("--robust K", "--robust-image FILE.png"):
         assert flag in r.stdout, flag
-    readme = open(os.path.join(ROOT, "README.md")).read()
+    readme = ic.read("README.md")
     assert "--robust K" in readme and "--robust-image" in readme
 
 
@@ -300,7 +179,7 @@ def test_cli_help_lists_the_robust_flags(tmp_path):
                                        (["--robust", "9", "--gpus", "2"], "one device"), (["--robust", "9", "--gpu-ids", "0,1"], "one device"),
                                        (["--robust", "9", "--debug"], "--debug"), (["--robust-image", "t.png"], "--robust")])
 def test_cli_refuses_before_any_device(tmp_path, args, word):
-    r = run_cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
+    r, left_a_result = ic.cli_refused(tmp_path, args)
     assert r.returncode == 1, r.stdout
     assert word in r.stdout
-    assert not (tmp_path / "result.txt").exists()
+    assert not left_a_result

@@ -4,22 +4,19 @@ against the run-time K definition, the refusals and state rules, that asking cha
 import numpy as np
 import pytest
 
-import test_robust_denoise_cpu as rd
+import post_cores as pc
+import post_numpy as pn
+import post_quality as pq
 from cli import ASSETS, run_cli
 from gpu_helpers import error_of, renderer, retarget, same
+from post_cores import core  # noqa: F401  (the g++-built harness, a fixture)
+from post_numpy import rel_sq_error, synthetic_inputs
 from test_adaptive_gpu import MASKS, RH, RW, TARGETS
-from test_denoise_cpu import synthetic_inputs
-from test_robust_cpu import rel_sq_error
 
 pytestmark = pytest.mark.gpu
 
 HR_ERR_INVALID = -1
-ALL_K = rd.ALL_K
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return rd.build_core(tmp_path_factory.mktemp("robust_denoise_gpu"))
+ALL_K = pn.ALL_K
 
 
 def _counts(K, shape, low=None):
@@ -49,7 +46,7 @@ def test_d_equals_the_host_core(ha, scenes, core, K):
             for n in (2 * K + 1, _counts(K, (h, w))):
                 per_pixel = not np.isscalar(n)
                 retarget(r, frame, region, counts=per_pixel, buckets=K)
-                B = rd.synthetic_buckets(900 + K, K, (h, w), n)
+                B = pn.synthetic_buckets(900 + K, K, (h, w), n)
                 r.write_buckets(B, int(n.max()) if per_pixel else n)
                 if per_pixel:
                     r.write_sample_counts(n)
@@ -57,10 +54,10 @@ def test_d_equals_the_host_core(ha, scenes, core, K):
                 for levels in (0, 1, 4):
                     for dem in (0, 1):
                         r.denoise_robust(levels=levels, demodulate=dem)
-                        want = rd.core_filter(core, B, n, g, levels=levels, demodulate=dem)
+                        want = pc.core_filter(core, B, n, g, levels=levels, demodulate=dem)
                         assert same(r.read_denoised(), want), (K, target, per_pixel, levels, dem)
                 if target == "frame" and not per_pixel:
-                    assert not same(rd.core_filter(core, B, n, g, levels=1), rd.core_filter(core, B, n, g, levels=0))
+                    assert not same(pc.core_filter(core, B, n, g, levels=1), pc.core_filter(core, B, n, g, levels=0))
 
 
 @pytest.mark.parametrize("K", [9, 3])
@@ -89,19 +86,19 @@ def test_robust_equals_the_run_time_definition(ha, scenes, core, K):
         for target in sorted(TARGETS):
             counts = _counts(K, (RH, RW), low=0)
             retarget(r, *TARGETS[target], counts=True, buckets=K)
-            B = rd.synthetic_buckets(950 + K, K, (RH, RW), counts)
+            B = pn.synthetic_buckets(950 + K, K, (RH, RW), counts)
             r.write_buckets(B, 123)
             r.write_sample_counts(counts)
             r.robust()
-            R, trim = rd.core_r(core, B, counts)
+            R, trim = pc.core_r(core, B, counts)
             assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (K, target)
             assert (r.read_robust()[counts == 0] == 0).all()
             retarget(r, *TARGETS[target], buckets=K)
             for n in (0, K - 1, K, 2 * K + 1):
-                B = rd.synthetic_buckets(960 + K, K, (RH, RW), max(n, 1))
+                B = pn.synthetic_buckets(960 + K, K, (RH, RW), max(n, 1))
                 r.write_buckets(B, n)
                 r.robust()
-                R, trim = rd.core_r(core, B, n)
+                R, trim = pc.core_r(core, B, n)
                 assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (K, target, n)
 
 
@@ -122,7 +119,7 @@ def test_refusals_touch_nothing(ha, scenes):
         assert _err(ha, r.denoise_robust) == HR_ERR_INVALID                            # the option is off
         r.set_option("robust_buckets", K)
         counts = _counts(K, (RH, RW))
-        B = rd.synthetic_buckets(1, K, (RH, RW), counts)
+        B = pn.synthetic_buckets(1, K, (RH, RW), counts)
         r.write_buckets(B, int(counts.max()))
         r.write_sample_counts(counts)
         r.write_guides(g)
@@ -242,11 +239,11 @@ def test_asking_changes_nothing_else(ha, scenes):
 def test_quality_on_the_device(ha, scenes, name):
     """The CPU tier's configuration — 96x54, 16 samplings, guide_bounces 2, default parameters — with the truth rendered by hr_render from
     samplings 100001 .. 101024: the denoised R beats R alone and beats hr_denoise on the same samplings (K = 5 asserted, K = 9 printed)."""
-    w, h, n, truth_n = rd.QW, rd.QH, rd.QN, 1024
+    w, h, n, truth_n = pq.SHORT_W, pq.SHORT_H, pq.SHORT_N, 1024
     with ha.Renderer(0) as r:
         r.upload_scene(scenes(name)[0])
         r.set_resolution(w, h)
-        r.set_option("guide_bounces", rd.QBOUNCES)
+        r.set_option("guide_bounces", pq.SHORT_BOUNCES)
         r.set_option("moments", 1)
         got = {}
         for K in (5, 9):

@@ -5,9 +5,12 @@ import numpy as np
 import pytest
 
 import ckpt
-import test_robust_cpu as rc
+import post_cores as pc
+import post_numpy as pn
+import post_quality as pq
 from cli import ASSETS, run_cli
 from gpu_helpers import bits, error_of, renderer, retarget, same
+from post_cores import core  # noqa: F401  (the g++-built harness, a fixture)
 from test_adaptive_gpu import MASKS, MODES, RH, RW, SCENES, TARGETS, _pixels
 
 pytestmark = pytest.mark.gpu
@@ -54,11 +57,6 @@ def sequential_buckets(x, samplings, K, counts=None):
             add = add * (j < counts)[..., None]
         B[:, :, j % K, :] += add
     return B
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return rc.build_core(tmp_path_factory.mktemp("robust_gpu"))
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -137,7 +135,7 @@ def test_tile_masks(ha, scenes, core, name, target):
         assert same(r.read_buckets()[0], sequential_buckets(x, range(1, 13), K, counts))
         # .. and the robust radiance takes every pixel's own count
         r.robust()
-        R, trim = rc.core_robust(core, r.read_buckets()[0], counts)
+        R, trim = pc.core_robust(core, r.read_buckets()[0], counts)
         assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim)
         assert (r.read_robust()[counts == 0] == 0).all()
 
@@ -159,7 +157,7 @@ def test_robust_equals_the_host_core(ha, scenes, core, name):
                 B, n = r.read_buckets()
                 assert n == N
                 r.robust()
-                R, trim = rc.core_robust(core, B, N)
+                R, trim = pc.core_robust(core, B, N)
                 got = r.read_robust()
                 assert same(got, R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 assert np.isfinite(got).all() and got.sum() > 0
@@ -175,29 +173,29 @@ def test_robust_equals_the_host_core(ha, scenes, core, name):
                 counts = r.read_sample_counts()
                 assert set(np.unique(counts)) == {7, N}
                 r.robust()
-                R, trim = rc.core_robust(core, r.read_buckets()[0], counts)
+                R, trim = pc.core_robust(core, r.read_buckets()[0], counts)
                 assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 # written synthetic buckets and counts: n = 0, n < K, n = K, n > K side by side
                 rng = np.random.default_rng(K)
                 counts = rng.integers(0, 3 * K + 3, size=(RH, RW)).astype(np.uint32)
                 counts[0, :4] = [0, 1, K - 1, K]
-                x = rc.heavy_tailed(rng, int(counts.max()), (RH, RW))
+                x = pn.heavy_tailed(rng, int(counts.max()), (RH, RW))
                 x = x * (np.arange(x.shape[0])[:, None, None, None] < counts[None, ..., None])
-                B = rc.fill_buckets(x, K)
+                B = pn.fill_buckets(x, K)
                 r.write_buckets(B, 123)
                 r.write_sample_counts(counts)
                 back, n = r.read_buckets()
                 assert same(back, B) and n == 123
                 r.robust()
-                R, trim = rc.core_robust(core, B, counts)
+                R, trim = pc.core_robust(core, B, counts)
                 assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 assert np.array_equal(r.resolve_robust(), _resolve_of(r, R))
                 # without the counts every pixel has the samplings behind the buckets
                 _aim(r, target, K)
-                B = rc.fill_buckets(rc.heavy_tailed(rng, 2 * K + 1, (RH, RW)), K)
+                B = pn.fill_buckets(pn.heavy_tailed(rng, 2 * K + 1, (RH, RW)), K)
                 r.write_buckets(B, 2 * K + 1)
                 r.robust()
-                R, trim = rc.core_robust(core, B, 2 * K + 1)
+                R, trim = pc.core_robust(core, B, 2 * K + 1)
                 assert same(r.read_robust(), R) and np.array_equal(r.read_robust_trim(), trim), (target, K)
                 # every bucket equal: R is that mean, and the bytes are hr_resolve's of it
                 v = (rng.integers(1, 2 ** 12, size=(RH, RW, 3)) / 256.0).astype(np.float32)
@@ -295,7 +293,7 @@ def test_state_rules(ha, scenes):
 
 @pytest.mark.parametrize("name", SCENES)
 def test_quality_ratio_on_the_device(ha, scenes, core, name):
-    w, h, n, K, truth_n = rc.QW, rc.QH, rc.QN, rc.QK, rc.QTRUTH
+    w, h, n, K, truth_n = pq.QW, pq.QH, pq.QN, pq.QK, pq.QTRUTH
     with ha.Renderer(0) as r:
         r.upload_scene(scenes(name)[0])
         r.set_resolution(w, h)
@@ -304,12 +302,12 @@ def test_quality_ratio_on_the_device(ha, scenes, core, name):
         acc = r.read_accumulator()
         r.robust()
         R, trim = r.read_robust(), r.read_robust_trim()
-        assert same(R, rc.core_robust(core, r.read_buckets()[0], n)[0])
+        assert same(R, pc.core_robust(core, r.read_buckets()[0], n)[0])
         r.set_option("robust_buckets", 0)
         r.clear()
         r.render(100001, 100001 + truth_n)                                           # the truth: 2,048 further samplings
         truth = r.read_accumulator().astype(np.float64) / (4.0 * truth_n)
-        e_mean, e_rob = rc.rel_sq_error(acc / np.float32(4 * n), truth), rc.rel_sq_error(R, truth)
+        e_mean, e_rob = pn.rel_sq_error(acc / np.float32(4 * n), truth), pn.rel_sq_error(R, truth)
         print("%s on the device: relMSE mean %.4g robust %.4g ratio %.3f, energy kept %.3f, pixels trimmed %.3f"
               % (name, e_mean, e_rob, e_rob / e_mean, R.astype(np.float64).sum() / (acc.astype(np.float64).sum() / (4 * n)), (trim > 0).mean()))
         assert e_rob / e_mean < 1.0

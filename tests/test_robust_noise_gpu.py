@@ -6,10 +6,12 @@ import re
 import numpy as np
 import pytest
 
-import test_robust_cpu as rc
-import test_robust_noise_cpu as rn
+import post_cores as pc
+import post_numpy as pn
+import post_quality as pq
 from cli import ASSETS, run_cli
 from gpu_helpers import error_of, renderer, retarget, same
+from post_cores import core  # noqa: F401  (the g++-built harness, a fixture)
 from test_adaptive_gpu import MASKS, RH, RW, TARGETS, TX, TY, _pixels
 
 pytestmark = pytest.mark.gpu
@@ -17,11 +19,6 @@ pytestmark = pytest.mark.gpu
 HR_ERR_INVALID = -1
 FLOOR = 0.01
 BLOCKS, THREADS = 1024, 256                             # robust_noise_kernel's grid (post_kernels.h)
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return rn.build_error_core(tmp_path_factory.mktemp("robust_noise_gpu"))
 
 
 def ulp_distance(a, b):
@@ -52,7 +49,7 @@ def fixed_order_sum(img):
 def synthetic_buckets(K, n=64, seed=0):
     """Heavy-tailed buckets of n samplings for the 37x23 window with the corner cases planted — the last pixel of the last row among them."""
     rng = np.random.default_rng(1000 * K + seed)
-    B = rc.fill_buckets(rc.heavy_tailed(rng, n, (RH, RW)), K)
+    B = pn.fill_buckets(pn.heavy_tailed(rng, n, (RH, RW)), K)
     B[0, 0] = np.float64([3.0, 10.0, 0.5]) * 4.0 * (n // K)                            # equal buckets (n a multiple of K or not: the keys differ then)
     B[0, 1] = 0.0
     B[0, 1, K // 2] = [1.0, 2.0, 0.5]                                                  # one hot bucket
@@ -64,8 +61,8 @@ def synthetic_buckets(K, n=64, seed=0):
 
 
 def check_against_host(core, r, B, n, K, what):
-    e, trim = rn.core_error(core, B, n, FLOOR)
-    ss = rn.numpy_error(B, n, FLOOR, parts=True)[4]
+    e, trim = pc.core_error(core, B, n, FLOOR)
+    ss = pn.numpy_error(B, n, FLOOR, parts=True)[4]
     img = r.robust_noise_image(FLOOR)
     assert img.shape == (RH, RW) and np.isfinite(img).all() and (img >= 0).all(), what
     d = ulp_distance(img, e)
@@ -77,7 +74,7 @@ def check_against_host(core, r, B, n, K, what):
     return img, int(d.max())
 
 
-@pytest.mark.parametrize("K", rn.ALL_K)
+@pytest.mark.parametrize("K", pn.ALL_K)
 def test_image_and_summary_against_the_host_core(ha, scenes, core, K):
     worst = 0
     with renderer(ha, scenes("cornell_mini")[0], None, None, *TARGETS["frame"], buckets=K) as r:
@@ -104,11 +101,11 @@ def test_image_and_summary_against_the_host_core(ha, scenes, core, K):
             retarget(r, *TARGETS[target], counts=True, buckets=K)
             rng = np.random.default_rng(K)
             counts = rng.integers(K, 3 * K + 3, size=(RH, RW)).astype(np.uint32)
-            x = rc.heavy_tailed(rng, int(counts.max()), (RH, RW))
-            B = rc.fill_buckets(x * (np.arange(x.shape[0])[:, None, None, None] < counts[None, ..., None]), K)
+            x = pn.heavy_tailed(rng, int(counts.max()), (RH, RW))
+            B = pn.fill_buckets(x * (np.arange(x.shape[0])[:, None, None, None] < counts[None, ..., None]), K)
             r.write_buckets(B, int(counts.max()))
             r.write_sample_counts(counts)
-            e, trim = rn.core_error(core, B, counts, FLOOR)
+            e, trim = pc.core_error(core, B, counts, FLOOR)
             img = r.robust_noise_image(FLOOR)
             assert ulp_distance(img, e).max() <= 4 and np.array_equal(r.robust_noise_trim(FLOOR), trim), (K, target)
     print("K = %d: worst %d ulp" % (K, worst))
@@ -132,10 +129,10 @@ def test_per_pixel_counts_through_a_render(ha, scenes, core):
         assert set(np.unique(counts)) == {3, 8, 15}
         B, n = r.read_buckets()
         assert n == 15
-        e, trim = rn.core_error(core, B, counts, FLOOR)
+        e, trim = pc.core_error(core, B, counts, FLOOR)
         img = r.robust_noise_image(FLOOR)
         assert ulp_distance(img, e).max() <= 4 and np.array_equal(r.robust_noise_trim(FLOOR), trim)
-        assert not same(img, rn.core_error(core, B, 15, FLOOR)[0])                    # (the pixel's n matters)
+        assert not same(img, pc.core_error(core, B, 15, FLOOR)[0])                    # (the pixel's n matters)
 
 
 def _tiles_above(img, thr):
@@ -258,7 +255,7 @@ def test_asking_changes_nothing_else(ha, scenes):
 def test_calibration_on_rendered_buckets(ha, scenes):
     """rtcamp6_v3_1 at 48x27, K = 9, samplings 1 .. 64 against 65 .. 128: z = (Ry_A - Ry_B) / sqrt(se_A^2 + se_B^2) with the device's e_R (se = e_R den,
     den and Ry from the read-back buckets), RMS within §4.7's gate."""
-    w, h, n, K = rn.QW, rn.QH, rn.QN, rn.QK
+    w, h, n, K = pq.QW, pq.QH, pq.QN, pq.QK
     with ha.Renderer(0) as r:
         r.upload_scene(scenes("rtcamp6_v3_1")[0])
         r.set_resolution(w, h)
@@ -270,7 +267,7 @@ def test_calibration_on_rendered_buckets(ha, scenes):
             B, got = r.read_buckets()
             assert got == n
             e = r.robust_noise_image(FLOOR)
-            ref, _, _, ry, _ = rn.numpy_error(B, n, FLOOR, parts=True)
+            ref, _, _, ry, _ = pn.numpy_error(B, n, FLOOR, parts=True)
             assert ulp_distance(e, ref).max() <= 4
             sets.append((ry, e * (ry + 3.0 * FLOOR)))
     (ra, sa), (rb, sb) = sets

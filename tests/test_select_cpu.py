@@ -2,194 +2,33 @@
 numpy restatement of its definition — bit for bit: + - x / and comparisons in f64 without contraction —, its consequences (S against the fixed
 levels, equal halves, a planted firefly), the entry points declared, exported and bound, and the quality ordering on the checker's renders."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import guide_chain as gc
-import test_denoise_cpu as dn
+import interface_checks as ic
 from cli import run_cli
-from test_robust_cpu import bits, fill_buckets, rel_sq_error
+from post_cores import core, core_denoise, core_select  # noqa: F401  (core: the g++-built harness, a fixture)
+from post_numpy import ALL_K, EPS, bits, fill_buckets, numpy_select, rel_sq_error, sums_of, synthetic_inputs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ALL_K = (3, 5, 7, 9, 11, 13, 15)
-EPS, TINY = 1e-3, 1e-30
 ENTRY_POINTS = ("hr_select_default_params", "hr_denoise_select", "hr_read_selected", "hr_read_selected_levels", "hr_resolve_selected")
-
-HARNESS = r'''
-#include <vector>
-#include "select_core.h"
-using namespace hr;
-// sig = {sigma_color, sigma_normal, sigma_albedo, sigma_depth}; counts may be null (every pixel: n_all); states (may be null): w*h*18 doubles
-extern "C" void select_run(const double *buckets, uint32_t K, const uint32_t *counts, uint32_t n_all, const float *acc, const double *mom, const float *guides, uint32_t w, uint32_t h,
-                           uint32_t levels, int demodulate, const double *sig, uint32_t smooth, float *S, uint8_t *L, double *states) {
-    std::vector<double> work((size_t)w * h * 45);
-    select_image(buckets, K, counts, n_all, acc, mom, guides, w, h, levels, demodulate, denoise_sigmas(sig[0], sig[1], sig[2], sig[3]), smooth, work.data(), S, L, states);
-}
-'''
-
-
-def build_core(directory):
-    src, so = directory / "select_harness.cpp", directory / "libselect_harness.so"
-    src.write_text(HARNESS)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "hanamaru-renderer_amd", "csrc"), "-o", str(so), str(src)], check=True)
-    lib = C.CDLL(str(so))
-    lib.select_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
-                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    return lib
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return build_core(tmp_path_factory.mktemp("select"))
-
-
-@pytest.fixture(scope="module")
-def dcore(tmp_path_factory):
-    return dn.build_core(tmp_path_factory.mktemp("select_denoise"))
-
-
-def core_select(lib, buckets, acc, mom, n, guides, smooth=0, want_states=False, **over):
-    """select_image over an (h, w, K, 3) image of buckets.  n: one count for every pixel, or an (h, w) array.  Returns (S, L[, states (3, h, w, 6)])."""
-    params = dict(dn.DEFAULTS, **over)
-    b = np.ascontiguousarray(buckets, dtype=np.float64)
-    h, w, K = b.shape[:3]
-    acc = np.ascontiguousarray(acc, dtype=np.float32)
-    mom = np.ascontiguousarray(mom, dtype=np.float64)
-    guides = np.ascontiguousarray(guides, dtype=np.float32)
-    assert acc.shape == (h, w, 3) and mom.shape == (h, w, 6) and guides.shape == (h, w, 8) and b.shape[3] == 3
-    counts = None if np.isscalar(n) else np.ascontiguousarray(n, dtype=np.uint32)
-    S, L = np.zeros((h, w, 3), dtype=np.float32), np.zeros((h, w), dtype=np.uint8)
-    states = np.zeros((3, h, w, 6)) if want_states else None
-    sig = dn._sig(params)
-    lib.select_run(b.ctypes.data, K, counts.ctypes.data if counts is not None else None, int(n) if counts is None else 0, acc.ctypes.data, mom.ctypes.data, guides.ctypes.data,
-                   w, h, int(params["levels"]), int(params["demodulate"]), sig.ctypes.data, int(smooth), S.ctypes.data, L.ctypes.data,
-                   states.ctypes.data if want_states else None)
-    return (S, L, states) if want_states else (S, L)
-
-
-# ---- the numpy restatement ----
-def _taps(h, w, s):
-    for j in range(-2, 3):
-        for i in range(-2, 3):
-            dx, dy = s * i, s * j
-            y0, y1, x0, x1 = max(0, -dy), min(h, h - dy), max(0, -dx), min(w, w - dx)
-            if y0 < y1 and x0 < x1:                                                   # (else the tap is outside the image for every pixel: skipped)
-                yield i, j, (slice(y0, y1), slice(x0, x1)), (slice(y0 + dy, y1 + dy), slice(x0 + dx, x1 + dx))
-
-
-def _level(state, g, s, p):
-    """denoise_core.h's level with step s on one state (h, w, 6)."""
-    Cc, V = state[..., 0:3], state[..., 3:6]
-    h, w = Cc.shape[:2]
-    A, N, Z, H = g[..., 0:3], g[..., 3:6], g[..., 6], g[..., 7]
-    sc2, sn2, sa2, sz2 = (p[k] * p[k] for k in ("sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth"))
-    k = (0.375, 0.25, 0.0625)
-    sw, sC, sV = np.zeros((h, w)), np.zeros((h, w, 3)), np.zeros((h, w, 3))
-    sumV = (V[..., 0] + V[..., 1]) + V[..., 2]
-    for i, j, P, Q in _taps(h, w, s):
-        d = N[P] - N[Q]
-        xn = ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) / sn2
-        d = A[P] - A[Q]
-        xa = ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) / sa2
-        dz = Z[P] - Z[Q]
-        xz = (dz * dz) / (sz2 * (Z[P] * Z[P] + Z[Q] * Z[Q]) + TINY)
-        dh = H[P] - H[Q]
-        xh = dh * dh
-        d = Cc[P] - Cc[Q]
-        xc = ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) / (sc2 * (sumV[P] + sumV[Q]) + TINY)
-        wt = (((((k[abs(i)] * k[abs(j)]) * dn._weight(xn)) * dn._weight(xa)) * dn._weight(xz)) * dn._weight(xh)) * dn._weight(xc)
-        w2 = wt * wt
-        sw[P] = sw[P] + wt
-        sC[P] = sC[P] + wt[..., None] * Cc[Q]
-        sV[P] = sV[P] + w2[..., None] * V[Q]
-    return np.concatenate([sC / sw[..., None], sV / (sw * sw)[..., None]], axis=-1)
-
-
-def _smooth(e, s):
-    h, w = e.shape
-    k = (0.375, 0.25, 0.0625)
-    se, sh = np.zeros((h, w)), np.zeros((h, w))
-    for i, j, P, Q in _taps(h, w, s):
-        hw = k[abs(i)] * k[abs(j)]
-        se[P] = se[P] + hw * e[Q]
-        sh[P] = sh[P] + hw
-    return se / sh
-
-
-def numpy_select(buckets, acc, mom, n, guides, smooth=0, **over):
-    """The definition in the comment of select_core.h, restated on whole arrays: every line one IEEE f64 operation per element, every bucket sum
-    sequential from its first term, the taps in row order.  Returns (S, L, states (3, h, w, 6))."""
-    p = dict(dn.DEFAULTS, **over)
-    B = np.asarray(buckets, dtype=np.float64)
-    h, w, K = B.shape[:3]
-    acc = np.asarray(acc, dtype=np.float32)
-    mom = np.asarray(mom, dtype=np.float64)
-    g = np.asarray(guides, dtype=np.float32).astype(np.float64)
-    cnt = np.full((h, w), n, dtype=np.uint32) if np.isscalar(n) else np.asarray(n, dtype=np.uint32)
-    assert (cnt >= 2).all()
-    levels = int(p["levels"])
-    dem = bool(p["demodulate"]) and levels > 0
-    with np.errstate(under="ignore", invalid="ignore", over="ignore"):
-        nb = (cnt.astype(np.int64)[..., None] - np.arange(K)[None, None, :] + (K - 1)) // K
-        nA, nB = nb[..., 0::2].sum(axis=-1).astype(np.float64)[..., None], nb[..., 1::2].sum(axis=-1).astype(np.float64)[..., None]
-        sa, sb = B[..., 0, :].copy(), B[..., 1, :].copy()
-        for b in range(2, K):
-            if b & 1:
-                sb = sb + B[..., b, :]
-            else:
-                sa = sa + B[..., b, :]
-        A0, B0 = sa / nA / 4.0, sb / nB / 4.0
-        scale = (np.float32(1.0) / (cnt * np.uint32(4)).astype(np.float32)).astype(np.float64)     # the resolve's fp32 scale, correctly rounded
-        nd = cnt.astype(np.float64)[..., None]
-        C0 = acc.astype(np.float64) * scale[..., None]
-        s1, s2 = mom[..., 0:3], mom[..., 3:6]
-        var = (s2 - s1 * (s1 / nd)) / (nd - 1.0)
-        V0 = np.where(var > 0.0, var, 0.0) / nd / 16.0
-        VA, VB = V0 * nd / nA, V0 * nd / nB
-        a = g[..., 0:3] + EPS
-        if dem:
-            a2 = a * a
-            C0, V0, A0, VA, B0, VB = C0 / a, V0 / a2, A0 / a, VA / a2, B0 / a, VB / a2
-        FA, FB, FW = np.concatenate([A0, VA], axis=-1), np.concatenate([B0, VB], axis=-1), np.concatenate([C0, V0], axis=-1)
-        best = S = L = None
-        for lev in range(levels + 1):
-            dA, dB = FA[..., 0:3] - B0, FB[..., 0:3] - A0
-            e = ((dA[..., 0] * dA[..., 0] + dB[..., 0] * dB[..., 0]) + (dA[..., 1] * dA[..., 1] + dB[..., 1] * dB[..., 1])) + (dA[..., 2] * dA[..., 2] + dB[..., 2] * dB[..., 2])
-            for t in range(int(smooth)):
-                e = _smooth(e, 1 << t)
-            final = (FW[..., 0:3] * a if dem else FW[..., 0:3]).astype(np.float32)
-            if lev == 0:
-                best, L, S = e, np.zeros((h, w), dtype=np.uint8), final
-            else:
-                take = e < best
-                best, L, S = np.where(take, e, best), np.where(take, np.uint8(lev), L), np.where(take[..., None], final, S)
-            if lev < levels:
-                FA, FB, FW = _level(FA, g, 1 << lev, p), _level(FB, g, 1 << lev, p), _level(FW, g, 1 << lev, p)
-    return S, L.astype(np.uint8), np.stack([FA, FB, FW])
 
 
 def synthetic(seed, w, h, K, n, firefly=0.03):
-    """Consistent inputs of one render: per-sampling values whose mean follows dn.synthetic_inputs' guides, with rare bright outliers, summed into
+    """Consistent inputs of one render: per-sampling values whose mean follows synthetic_inputs' guides, with rare bright outliers, summed into
     the fp32 accumulator, the f64 moments and the K buckets (sampling j of a pixel into bucket j mod K).  n: one count, or per-pixel counts (a pixel
     holds its own prefix).  Returns (buckets, acc, mom, n, guides)."""
     rng = np.random.default_rng(seed)
-    g = dn.synthetic_inputs(seed, w, h, n=2)[3]
+    g = synthetic_inputs(seed, w, h, n=2)[3]
     cnt = np.full((h, w), n, dtype=np.uint32) if np.isscalar(n) else np.asarray(n, dtype=np.uint32)
     mean = 4.0 * (g[..., 0:3].astype(np.float64) + 0.05)
     N = int(cnt.max())
     x = rng.gamma(2.0, 0.5, size=(N, h, w, 3)) * mean
     x = np.where(rng.random((N, h, w, 1)) < firefly, x * 200.0, x).astype(np.float32)
     x = x * (np.arange(N)[:, None, None, None] < cnt[None, ..., None])
-    acc = np.zeros((h, w, 3), dtype=np.float32)
-    for s in range(N):
-        acc = acc + x[s]
-    xd = x.astype(np.float64)
-    mom = np.concatenate([xd.sum(axis=0), (xd * xd).sum(axis=0)], axis=-1)
+    acc, mom = sums_of(x)
     return fill_buckets(x, K), acc, mom, n, g
 
 
@@ -226,7 +65,7 @@ def test_core_against_numpy(core, w, h, K):
 # ---- 2. S against the fixed levels ----
 @pytest.mark.parametrize("K", [3, 9])
 @pytest.mark.parametrize("dem", [0, 1])
-def test_s_has_the_bits_of_the_fixed_level(core, dcore, K, dem):
+def test_s_has_the_bits_of_the_fixed_level(core, K, dem):
     w, h, levels = 37, 19, 5
     for n in (2 * K + 1, unequal_counts(K, w, h, K)):
         B, acc, mom, n, g = synthetic(200 + K, w, h, K, n)
@@ -235,7 +74,7 @@ def test_s_has_the_bits_of_the_fixed_level(core, dcore, K, dem):
         for lev in range(levels + 1):
             # (hr_denoise(levels = 0) drops the demodulation, a pixel that picks level 0 under it is (float)((C / a) a): the float of C unless C
             # lies within two f64 ulps of the boundary between two floats, which none of these does)
-            D = dn.core_denoise(dcore, acc, mom, n, g, levels=lev, demodulate=dem)
+            D = core_denoise(core, acc, mom, n, g, levels=lev, demodulate=dem)
             m = L == lev
             if m.any():
                 assert np.array_equal(bits(S[m]), bits(D[m])), (K, dem, lev)
@@ -263,7 +102,7 @@ def test_equal_halves_give_level_zero(core, smooth):
     B = np.repeat((16.0 * r)[:, :, None, :], K, axis=2)
     acc = (48.0 * r).astype(np.float32)
     mom = np.concatenate([48.0 * r, 1.5 * n * (4.0 * r) ** 2], axis=-1)
-    g = dn.synthetic_inputs(3, w, h)[3]
+    g = synthetic_inputs(3, w, h)[3]
     for dem in (0, 1):
         S, L, st = core_select(core, B, acc, mom, n, g, smooth=smooth, want_states=True, levels=4, demodulate=dem)
         assert not np.array_equal(bits(st[2]), bits(core_select(core, B, acc, mom, n, g, want_states=True, levels=0)[2][2]))   # the levels did filter
@@ -306,21 +145,18 @@ def test_a_planted_firefly_is_filtered_and_the_rest_is_left_alone(core):
 
 # ---- 5. plumbing ----
 def test_entry_points_declared_exported_and_bound(ha):
-    raw = open(os.path.join(ROOT, "include", "hanamaru_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"typedef\s+struct\s+\w*\s*\{\s*uint32_t\s+smooth\s*;\s*uint32_t\s+reserved\s*;\s*\}\s*hr_select_params\s*;", text)
-    assert re.search(r"int\s+hr_select_default_params\s*\(\s*hr_select_params\s*\*\s*\w+\s*\)\s*;", text)
-    assert re.search(r"int\s+hr_denoise_select\s*\(\s*hr_ctx\s*\*\s*\w*\s*,\s*const\s+hr_denoise_params\s*\*\s*\w+\s*,\s*const\s+hr_select_params\s*\*\s*\w+\s*\)\s*;", text)
-    assert re.search(r"int\s+hr_read_selected\s*\(\s*hr_ctx\s*\*\s*\w*\s*,\s*float\s*\*\s*\w+\s*\)\s*;", text)
-    assert re.search(r"int\s+hr_read_selected_levels\s*\(\s*hr_ctx\s*\*\s*\w*\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;", text)
-    assert re.search(r"int\s+hr_resolve_selected\s*\(\s*hr_ctx\s*\*\s*\w*\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;", text)
-    assert int(re.search(r"#define\s+HR_ABI_VERSION\s+(\d+)", text).group(1)) == 7       # functions were added, none changed
-    lib = C.CDLL(ha.HIP_LIB)
-    ffi = open(os.path.join(ROOT, "rust", "hip_ffi.rs")).read()
-    integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    text = ic.header_text()
+    assert ic.declared(text, r"typedef\s+struct\s+\w*\s*\{\s*uint32_t\s+smooth\s*;\s*uint32_t\s+reserved\s*;\s*\}\s*hr_select_params\s*;")
+    assert ic.declared(text, r"int\s+hr_select_default_params\s*\(\s*hr_select_params\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_denoise_select\s*\(\s*%s\s*,\s*const\s+hr_denoise_params\s*\*\s*\w+\s*,\s*const\s+hr_select_params\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_read_selected\s*\(\s*%s\s*,\s*float\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_read_selected_levels\s*\(\s*%s\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;")
+    assert ic.declared(text, r"int\s+hr_resolve_selected\s*\(\s*%s\s*,\s*uint8_t\s*\*\s*\w+\s*\)\s*;")
+    assert ic.abi_version(text) == 7       # functions were added, none changed
+    ffi, integration = ic.rust_ffi(), ic.read("INTEGRATION.md")
     arity = {"hr_select_default_params": 1, "hr_denoise_select": 3}
     for fn in ENTRY_POINTS:
-        assert hasattr(lib, fn), fn
+        assert not ic.exported_and_bound(ha, (fn,)), fn
         assert len(getattr(ha.hip_lib(), fn).argtypes) == arity.get(fn, 2)
         assert "pub fn %s(" % fn in ffi and "pub fn %s(" % fn in integration, fn
     assert "size_of::<HrSelectParams>() == 8" in ffi
@@ -333,8 +169,7 @@ def test_entry_points_declared_exported_and_bound(ha):
 
 
 def test_kernel_rows():
-    kv = open(os.path.join(ROOT, "hanamaru-renderer_amd", "csrc", "kernel_variants.h")).read()
-    pk = open(os.path.join(ROOT, "hanamaru-renderer_amd", "csrc", "post_kernels.h")).read()
+    kv, pk = ic.kernel_variants(), ic.read("hanamaru-renderer_amd", "csrc", "post_kernels.h")
     for K in ALL_K:
         assert "HR_VARIANT(select_init_kernel, %d)" % K in kv, K
     assert "select_select_init_kernel" in kv
@@ -345,10 +180,10 @@ def test_kernel_rows():
 def test_cli_help_lists_the_flags(tmp_path):
     r = run_cli(["--help"], tmp_path)
     assert r.returncode == 0
-    readme = open(os.path.join(ROOT, "README.md")).read()
+    readme = ic.read("README.md")
     for flag in ("--denoise-auto", "--select-smooth", "--level-image"):
         assert flag in r.stdout and flag in readme, flag
-    tools = open(os.path.join(ROOT, "tools", "README.md")).read()
+    tools = ic.read("tools", "README.md")
     assert "select_quality.py" in tools and "select_rate.py" in tools
 
 
@@ -361,10 +196,10 @@ def test_cli_help_lists_the_flags(tmp_path):
                                        (["--select-smooth", "1"], "--select-smooth needs --denoise-auto"),
                                        (["--level-image", "l.png"], "--level-image needs --denoise-auto")])
 def test_cli_refuses_before_any_device(tmp_path, args, word):
-    r = run_cli(["-w", "64", "-h", "48", "-s", "8"] + args, tmp_path)
+    r, left_a_result = ic.cli_refused(tmp_path, args)
     assert r.returncode == 1, r.stdout
     assert word in r.stdout
-    assert not (tmp_path / "result.txt").exists()
+    assert not left_a_result
 
 
 # ---- 6. quality on the checker's per-sampling renders (the figures of DESIGN.md §4.16, with half the truth set of tools/select_quality.py) ----
@@ -383,26 +218,17 @@ def oracle_render(orc, scenes, name, n_max=64):
     return _oracle[name]
 
 
-def sums_of(x):
-    """(fp32 accumulator, f64 moments) of the samplings x (n, h, w, 3), one sampling at a time"""
-    acc = np.zeros(x.shape[1:], dtype=np.float32)
-    for s in range(x.shape[0]):
-        acc = acc + x[s]
-    xd = x.astype(np.float64)
-    return acc, np.concatenate([xd.sum(axis=0), (xd * xd).sum(axis=0)], axis=-1)
-
-
-def quality_ratios(core, dcore, x, guides, truth, K, smooth=0):
+def quality_ratios(core, x, guides, truth, K, smooth=0):
     """(fixed-levels-4 / raw, select / raw): relative squared errors against the truth over the raw mean's"""
     n = x.shape[0]
     acc, mom = sums_of(x)
     e_raw = rel_sq_error(acc / np.float32(4 * n), truth)
-    e_fixed = rel_sq_error(dn.core_denoise(dcore, acc, mom, n, guides), truth)
+    e_fixed = rel_sq_error(core_denoise(core, acc, mom, n, guides), truth)
     e_sel = rel_sq_error(core_select(core, fill_buckets(x, K), acc, mom, n, guides, smooth=smooth)[0], truth)
     return e_fixed / e_raw, e_sel / e_raw
 
 
-def test_quality_on_the_oracle(core, dcore, orc, scenes):
+def test_quality_on_the_oracle(core, orc, scenes):
     """96x54, K = 9, default parameters, smooth 0, truth samplings 100001 .. 101024 (half of tools/select_quality.py's 2,048).  Asserted on
     rtcamp6_v3_1 with first-hit guides, the case of DESIGN.md §4.9's finding, at 16 and at 64 samplings: the selection's error is below the
     whole-buffer filter's at levels = 4.  A host prototype measured fixed -> select 0.52 -> 0.31 (n = 16) and 1.95 -> 1.03 (n = 64), a gap of
@@ -411,7 +237,7 @@ def test_quality_on_the_oracle(core, dcore, orc, scenes):
     x, guides, truth = oracle_render(orc, scenes, "rtcamp6_v3_1")
     for bounces in (0, 2):
         for n in (16, 64):
-            fixed, sel = quality_ratios(core, dcore, x[:n], guides[bounces], truth, QK)
+            fixed, sel = quality_ratios(core, x[:n], guides[bounces], truth, QK)
             print("rtcamp6_v3_1 guide_bounces=%d n=%d K=%d: fixed-4 / raw %.3f  select / raw %.3f" % (bounces, n, QK, fixed, sel))
             if bounces == 0:
                 assert sel < fixed, (n, fixed, sel)

@@ -6,19 +6,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_select_cpu as sl
+import post_cores as pc
 from cli import ASSETS, run_cli
 from gpu_helpers import error_of, renderer, same
-from test_robust_cpu import rel_sq_error
+from post_cores import core  # noqa: F401  (the g++-built harness, a fixture)
+from post_numpy import rel_sq_error
 
 pytestmark = pytest.mark.gpu
 
 HR_ERR_INVALID = -1
-
-
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
-    return sl.build_core(tmp_path_factory.mktemp("select_gpu"))
 
 
 def _err(ha, fn, *a, **kw):
@@ -63,12 +59,12 @@ def test_s_and_l_equal_the_host_core(ha, scenes, core, case):
         for levels in (0, 1, 4):
             for smooth in (0, 2):
                 r.denoise_select(levels=levels, smooth=smooth)
-                S, L = sl.core_select(core, B, acc, mom, n, g, smooth=smooth, levels=levels)
+                S, L = pc.core_select(core, B, acc, mom, n, g, smooth=smooth, levels=levels)
                 assert np.array_equal(r.read_selected_levels(), L), (case, levels, smooth)
                 assert same(r.read_selected(), S), (case, levels, smooth)
                 picked |= set(np.unique(L).tolist())
         r.denoise_select(levels=4, demodulate=0)                                       # (the default smooth)
-        S, L = sl.core_select(core, B, acc, mom, n, g, smooth=ha.select_default_params().smooth, levels=4, demodulate=0)
+        S, L = pc.core_select(core, B, acc, mom, n, g, smooth=ha.select_default_params().smooth, levels=4, demodulate=0)
         assert np.array_equal(r.read_selected_levels(), L) and same(r.read_selected(), S), case
         assert len(picked) >= 3, picked
 

@@ -7,7 +7,6 @@ parameters.  Prints mean((x - t)^2 / (t^2 + 0.01^2)) of the denoised image over 
 import argparse
 import os
 import sys
-import tempfile
 
 import numpy as np
 
@@ -16,7 +15,7 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), os.pa
 import guide_chain as gc  # noqa: E402
 import hanamaru_amd as ha  # noqa: E402
 import oracle_py as orc  # noqa: E402
-import test_denoise_cpu as dn  # noqa: E402  (build_core / core_denoise: the g++ build of denoise_core.h)
+import post_cores as pc  # noqa: E402  (lib / core_denoise: the g++ build of denoise_core.h)
 
 W, H, TRUTH = 96, 54, 2048
 
@@ -27,32 +26,30 @@ def main():
     ap.add_argument("--bounces", default="0,1,2,4,8")
     args = ap.parse_args()
     bounces = [int(k) for k in args.bounces.split(",")]
-    with tempfile.TemporaryDirectory() as tmp:
-        from pathlib import Path
-        core = dn.build_core(Path(tmp))
-        print("| scene | samplings | " + " | ".join("K = %d" % k for k in bounces) + " |")
-        print("|---|---|" + "---|" * len(bounces))
-        for name in args.scenes.split(","):
-            sc = ha.Scene(name)
-            osc = orc.OracleScene(sc.desc_ptr)
-            guides = {k: gc.planes_of(gc.oracle_chain(orc, osc, sc.desc, W, H, k)[0]).astype(np.float32) for k in bounces}
-            acc = np.zeros((H, W, 3))
-            s1, s2 = np.zeros((H, W, 3)), np.zeros((H, W, 3))
-            short = {}
-            for s in range(1, TRUTH + 1):
-                x, _ = osc.render(W, H, s, s + 1)                       # one sampling: the sum of the pixel's four sub-samples
-                acc += x
-                if s <= 64:
-                    s1 += x
-                    s2 += x * x
-                if s in (16, 64):
-                    short[s] = (acc.astype(np.float32), np.concatenate([s1, s2], axis=-1))
-            truth = acc / (4.0 * TRUTH)
-            for s in (16, 64):
-                a, mom = short[s]
-                e_raw = gc.rel_sq_error(a / np.float32(4 * s), truth)
-                cells = ["%.2f" % (gc.rel_sq_error(dn.core_denoise(core, a, mom, s, guides[k]), truth) / e_raw) for k in bounces]
-                print("| %s | %d | " % (name, s) + " | ".join(cells) + " |", flush=True)
+    core = pc.lib()
+    print("| scene | samplings | " + " | ".join("K = %d" % k for k in bounces) + " |")
+    print("|---|---|" + "---|" * len(bounces))
+    for name in args.scenes.split(","):
+        sc = ha.Scene(name)
+        osc = orc.OracleScene(sc.desc_ptr)
+        guides = {k: gc.planes_of(gc.oracle_chain(orc, osc, sc.desc, W, H, k)[0]).astype(np.float32) for k in bounces}
+        acc = np.zeros((H, W, 3))
+        s1, s2 = np.zeros((H, W, 3)), np.zeros((H, W, 3))
+        short = {}
+        for s in range(1, TRUTH + 1):
+            x, _ = osc.render(W, H, s, s + 1)                       # one sampling: the sum of the pixel's four sub-samples
+            acc += x
+            if s <= 64:
+                s1 += x
+                s2 += x * x
+            if s in (16, 64):
+                short[s] = (acc.astype(np.float32), np.concatenate([s1, s2], axis=-1))
+        truth = acc / (4.0 * TRUTH)
+        for s in (16, 64):
+            a, mom = short[s]
+            e_raw = gc.rel_sq_error(a / np.float32(4 * s), truth)
+            cells = ["%.2f" % (gc.rel_sq_error(pc.core_denoise(core, a, mom, s, guides[k]), truth) / e_raw) for k in bounces]
+            print("| %s | %d | " % (name, s) + " | ".join(cells) + " |", flush=True)
 
 
 if __name__ == "__main__":

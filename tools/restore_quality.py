@@ -8,8 +8,6 @@ means, per scene, sampling count n, K and guide_bounces."""
 import argparse
 import os
 import sys
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
@@ -18,8 +16,8 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), os.pa
 import guide_chain as gc  # noqa: E402
 import hanamaru_amd as ha  # noqa: E402
 import oracle_py as orc  # noqa: E402
-import test_restore_cpu as rs  # noqa: E402  (the g++ build of restore_core.h: restore_figures)
-import test_robust_denoise_cpu as rd  # noqa: E402  (the g++ build of robust_core.h)
+import post_cores as pc  # noqa: E402  (the g++ build of restore_core.h, robust_core.h and denoise_core.h)
+from post_quality import restore_figures  # noqa: E402
 
 W, H = 96, 54
 KS, NS, BOUNCES = (5, 9), (16, 64), (0, 2)
@@ -30,22 +28,21 @@ def main():
     ap.add_argument("--scenes", default="cornell_mini,rtcamp6_v3_1")
     ap.add_argument("--truth", type=int, default=1024)
     args = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        core, rcore = rs.build_core(Path(tmp)), rd.build_core(Path(tmp))
-        print("| scene | n | K | bounces | R / mean | R' / mean | R' (base DR) / mean | sum R / sum M | sum R' / sum M |")
-        print("|---|---|---|---|---|---|---|---|---|")
-        for name in args.scenes.split(","):
-            sc = ha.Scene(name)
-            osc = orc.OracleScene(sc.desc_ptr)
-            guides = {b: gc.planes_of(gc.oracle_chain(orc, osc, sc.desc, W, H, b)[0]).astype(np.float32) for b in BOUNCES}
-            x = np.stack([osc.render(W, H, s, s + 1)[0] for s in range(1, max(NS) + 1)]).astype(np.float32)
-            truth = osc.render(W, H, 100001, 100001 + args.truth)[0].astype(np.float64) / (4.0 * args.truth)
-            for n in NS:
-                for K in KS:
-                    for b in BOUNCES:
-                        f = rs.restore_figures(core, rcore, x[:n], guides[b], truth, K)
-                        print("| %s | %d | %d | %d | %.3f | %.3f | %.3f | %.4f | %.4f |" % (name, n, K, b, f["R/mean"], f["R'/mean"], f["R'(DR)/mean"], f["sumR/sumM"], f["sumR'/sumM"]),
-                              flush=True)
+    core = pc.lib()
+    print("| scene | n | K | bounces | R / mean | R' / mean | R' (base DR) / mean | sum R / sum M | sum R' / sum M |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for name in args.scenes.split(","):
+        sc = ha.Scene(name)
+        osc = orc.OracleScene(sc.desc_ptr)
+        guides = {b: gc.planes_of(gc.oracle_chain(orc, osc, sc.desc, W, H, b)[0]).astype(np.float32) for b in BOUNCES}
+        x = np.stack([osc.render(W, H, s, s + 1)[0] for s in range(1, max(NS) + 1)]).astype(np.float32)
+        truth = osc.render(W, H, 100001, 100001 + args.truth)[0].astype(np.float64) / (4.0 * args.truth)
+        for n in NS:
+            for K in KS:
+                for b in BOUNCES:
+                    f = restore_figures(core, x[:n], guides[b], truth, K)
+                    print("| %s | %d | %d | %d | %.3f | %.3f | %.3f | %.4f | %.4f |" % (name, n, K, b, f["R/mean"], f["R'/mean"], f["R'(DR)/mean"], f["sumR/sumM"], f["sumR'/sumM"]),
+                          flush=True)
 
 
 if __name__ == "__main__":

@@ -10,8 +10,6 @@ compiled by g++ — the estimator the device runs — gives e_R for K in {5, 9, 
 import argparse
 import os
 import sys
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
@@ -19,8 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "hanamaru-renderer_amd", "python")]
 import hanamaru_amd as ha  # noqa: E402
 import oracle_py as orc  # noqa: E402
-import test_robust_cpu as rb  # noqa: E402  (fill_buckets)
-import test_robust_noise_cpu as rn  # noqa: E402  (build_error_core / core_error: the g++ build of robust_core.h; numpy_error for se and Ry)
+import post_cores as pc  # noqa: E402  (lib / core_error: the g++ build of robust_core.h)
+from post_numpy import fill_buckets, numpy_error  # noqa: E402  (numpy_error for se and Ry)
 
 W, H, FLOOR = 48, 27, 0.01
 KS, NS = (5, 9, 15), (16, 64, 256)
@@ -40,30 +38,29 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="rtcamp6_v3_1,cornell_mini,spheres")
     args = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        core = rn.build_error_core(Path(tmp))
-        print("| scene | n | K | RMS z | mean e_R (A / B) | mean raw e (A / B) | se = 0 (A / B) |")
-        print("|---|---|---|---|---|---|---|")
-        for name in args.scenes.split(","):
-            sc = ha.Scene(name)
-            osc = orc.OracleScene(sc.desc_ptr)
-            x = np.stack([osc.render(W, H, s, s + 1)[0] for s in range(1, 2 * max(NS) + 1)]).astype(np.float32)
-            for n in NS:
-                sets = (x[:n], x[n:2 * n])
-                raw = [raw_error(s).mean() for s in sets]
-                for K in KS:
-                    e, se, ry = [], [], []
-                    for s in sets:
-                        B = rb.fill_buckets(s, K)
-                        e.append(rn.core_error(core, B, n, FLOOR)[0])
-                        _, _, se_s, ry_s, _ = rn.numpy_error(B, n, FLOOR, parts=True)
-                        se.append(se_s)
-                        ry.append(ry_s)
-                    den = np.sqrt(se[0] ** 2 + se[1] ** 2)
-                    ok = den > 0
-                    rms = np.sqrt(np.mean(((ry[0] - ry[1])[ok] / den[ok]) ** 2))
-                    print("| %s | %d | %d | %.2f | %.4f / %.4f | %.4f / %.4f | %.4f / %.4f |"
-                          % (name, n, K, rms, e[0].mean(), e[1].mean(), raw[0], raw[1], (se[0] == 0).mean(), (se[1] == 0).mean()), flush=True)
+    core = pc.lib()
+    print("| scene | n | K | RMS z | mean e_R (A / B) | mean raw e (A / B) | se = 0 (A / B) |")
+    print("|---|---|---|---|---|---|---|")
+    for name in args.scenes.split(","):
+        sc = ha.Scene(name)
+        osc = orc.OracleScene(sc.desc_ptr)
+        x = np.stack([osc.render(W, H, s, s + 1)[0] for s in range(1, 2 * max(NS) + 1)]).astype(np.float32)
+        for n in NS:
+            sets = (x[:n], x[n:2 * n])
+            raw = [raw_error(s).mean() for s in sets]
+            for K in KS:
+                e, se, ry = [], [], []
+                for s in sets:
+                    B = fill_buckets(s, K)
+                    e.append(pc.core_error(core, B, n, FLOOR)[0])
+                    _, _, se_s, ry_s, _ = numpy_error(B, n, FLOOR, parts=True)
+                    se.append(se_s)
+                    ry.append(ry_s)
+                den = np.sqrt(se[0] ** 2 + se[1] ** 2)
+                ok = den > 0
+                rms = np.sqrt(np.mean(((ry[0] - ry[1])[ok] / den[ok]) ** 2))
+                print("| %s | %d | %d | %.2f | %.4f / %.4f | %.4f / %.4f | %.4f / %.4f |"
+                      % (name, n, K, rms, e[0].mean(), e[1].mean(), raw[0], raw[1], (se[0] == 0).mean(), (se[1] == 0).mean()), flush=True)
 
 
 if __name__ == "__main__":

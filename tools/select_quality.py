@@ -8,8 +8,6 @@ and the worst case of every smooth over the table: the default of hr_select_para
 import argparse
 import os
 import sys
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
@@ -18,9 +16,8 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), os.pa
 import guide_chain as gc  # noqa: E402
 import hanamaru_amd as ha  # noqa: E402
 import oracle_py as orc  # noqa: E402
-import test_denoise_cpu as dn  # noqa: E402  (build_core / core_denoise: the g++ build of denoise_core.h)
-import test_select_cpu as sl  # noqa: E402  (build_core / core_select: the g++ build of select_core.h)
-from test_robust_cpu import fill_buckets, rel_sq_error  # noqa: E402
+import post_cores as pc  # noqa: E402  (lib / core_denoise / core_select: the g++ build of denoise_core.h and select_core.h)
+from post_numpy import fill_buckets, rel_sq_error, sums_of  # noqa: E402
 
 W, H = 96, 54
 SMOOTH = (0, 1, 2, 3)
@@ -35,27 +32,26 @@ def main():
     K = args.buckets
     worst = {s: 0.0 for s in SMOOTH}
     worst_fixed = 0.0
-    with tempfile.TemporaryDirectory() as tmp:
-        dcore, core = dn.build_core(Path(tmp)), sl.build_core(Path(tmp))
-        print("| scene, guide_bounces | samplings | fixed 4 | " + " | ".join("select, smooth %d" % s for s in SMOOTH) + " |")
-        print("|---|---|---|" + "---|" * len(SMOOTH))
-        for name in args.scenes.split(","):
-            sc = ha.Scene(name)
-            osc = orc.OracleScene(sc.desc_ptr)
-            x = np.stack([osc.render(W, H, s, s + 1)[0] for s in range(1, 65)]).astype(np.float32)   # x_s: one sampling's 2x2 sum per pixel
-            truth = osc.render(W, H, 100001, 100001 + args.truth)[0].astype(np.float64) / (4.0 * args.truth)
-            for bounces in (0, 2):
-                guides = gc.planes_of(gc.oracle_chain(orc, osc, sc.desc, W, H, bounces)[0]).astype(np.float32)
-                for n in (16, 64):
-                    acc, mom = sl.sums_of(x[:n])
-                    B = fill_buckets(x[:n], K)
-                    e_raw = rel_sq_error(acc / np.float32(4 * n), truth)
-                    fixed = rel_sq_error(dn.core_denoise(dcore, acc, mom, n, guides), truth) / e_raw
-                    sel = {s: rel_sq_error(sl.core_select(core, B, acc, mom, n, guides, smooth=s)[0], truth) / e_raw for s in SMOOTH}
-                    worst_fixed = max(worst_fixed, fixed)
-                    for s in SMOOTH:
-                        worst[s] = max(worst[s], sel[s])
-                    print("| %s, %d | %d | %.2f | " % (name, bounces, n, fixed) + " | ".join("%.2f" % sel[s] for s in SMOOTH) + " |", flush=True)
+    core = pc.lib()
+    print("| scene, guide_bounces | samplings | fixed 4 | " + " | ".join("select, smooth %d" % s for s in SMOOTH) + " |")
+    print("|---|---|---|" + "---|" * len(SMOOTH))
+    for name in args.scenes.split(","):
+        sc = ha.Scene(name)
+        osc = orc.OracleScene(sc.desc_ptr)
+        x = np.stack([osc.render(W, H, s, s + 1)[0] for s in range(1, 65)]).astype(np.float32)   # x_s: one sampling's 2x2 sum per pixel
+        truth = osc.render(W, H, 100001, 100001 + args.truth)[0].astype(np.float64) / (4.0 * args.truth)
+        for bounces in (0, 2):
+            guides = gc.planes_of(gc.oracle_chain(orc, osc, sc.desc, W, H, bounces)[0]).astype(np.float32)
+            for n in (16, 64):
+                acc, mom = sums_of(x[:n])
+                B = fill_buckets(x[:n], K)
+                e_raw = rel_sq_error(acc / np.float32(4 * n), truth)
+                fixed = rel_sq_error(pc.core_denoise(core, acc, mom, n, guides), truth) / e_raw
+                sel = {s: rel_sq_error(pc.core_select(core, B, acc, mom, n, guides, smooth=s)[0], truth) / e_raw for s in SMOOTH}
+                worst_fixed = max(worst_fixed, fixed)
+                for s in SMOOTH:
+                    worst[s] = max(worst[s], sel[s])
+                print("| %s, %d | %d | %.2f | " % (name, bounces, n, fixed) + " | ".join("%.2f" % sel[s] for s in SMOOTH) + " |", flush=True)
     print("| worst case | | %.4f | " % worst_fixed + " | ".join("%.4f" % worst[s] for s in SMOOTH) + " |")
     print("lowest worst case (a tie goes to the fewer passes): smooth %d" % min(SMOOTH, key=lambda s: (worst[s], s)))
 
