@@ -112,6 +112,7 @@ struct hr_ctx {
     Scene dsc{};
     bool have_scene = false;
     uint64_t st_nodes = 0, st_tris = 0, st_spheres = 0, st_cuboids = 0;
+    uint32_t num_images = 0;   // of the scene in place: what hr_debug_texture checks its image indices against
     // target
     uint32_t W = 0, H = 0;
     // the region (hr_set_region): the window [RX, RX + RW) x [RY, RY + RH) of the W x H frame that is rendered; the accumulator and
@@ -944,6 +945,7 @@ int hr_upload_scene(hr_ctx *c, const hr_scene_desc *sd) {
         if (c->quant_nodes && !hs.qnodes.empty() && (r = upload(c, hs.qnodes, &d.qnodes))) return r;
     }
     c->st_nodes = d.num_nodes; c->st_tris = hs.num_input_tris; c->st_spheres = d.num_spheres; c->st_cuboids = d.num_cuboids;
+    c->num_images = (uint32_t)hs.images.size();
     c->have_scene = true;
     if ((r = govern_reset(c))) return r;   // another scene: the balance of the two kernels is another one
     return HR_OK;
@@ -2921,6 +2923,82 @@ int hr_debug_trace(hr_ctx *c, uint32_t n, const float *rays, const float *shadow
     HIP_TRY_AS("hr_debug_trace", hipMemcpy(out, d_out, (size_t)n * 8 * 4, hipMemcpyDeviceToHost));
     HIP_TRY_AS("hr_debug_trace", hipMemcpy(out_element, d_el, (size_t)n * 4, hipMemcpyDeviceToHost));
     return drain_events(c);
+}
+
+// The point queries (query_core.h): hr_debug_intersect's pattern — scratch for the call, one launch of 64-thread groups, a point per thread.
+int hr_debug_surface(hr_ctx *c, uint32_t n, const float *rays, const float *fix, const double *draws, int precise, float *out, double *out64, int32_t *out_element) {
+    if (!c || !rays || !out || !out_element || !n) return fail(HR_ERR_INVALID, "hr_debug_surface: bad argument");
+    int rc = debug_refusal(c, "hr_debug_surface", NO_REGION | NO_MASK | A_SCENE);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    CallScratch scratch;
+    float *d_rays = nullptr, *d_fix = nullptr, *d_out = nullptr;
+    double *d_draws = nullptr, *d_out64 = nullptr;
+    int32_t *d_el = nullptr;
+    HIP_TRY_AS("hr_debug_surface", scratch.alloc((void **)&d_rays, (size_t)n * 6 * 4));
+    if (fix) HIP_TRY_AS("hr_debug_surface", scratch.alloc((void **)&d_fix, (size_t)n * 6 * 4));
+    if (draws) HIP_TRY_AS("hr_debug_surface", scratch.alloc((void **)&d_draws, (size_t)n * 2 * 8));
+    HIP_TRY_AS("hr_debug_surface", scratch.alloc((void **)&d_out, (size_t)n * QUERY_SURFACE_FLOATS * 4));
+    if (out64) HIP_TRY_AS("hr_debug_surface", scratch.alloc((void **)&d_out64, (size_t)n * 6 * 8));
+    HIP_TRY_AS("hr_debug_surface", scratch.alloc((void **)&d_el, (size_t)n * 4));
+    HIP_TRY_AS("hr_debug_surface", hipMemcpy(d_rays, rays, (size_t)n * 6 * 4, hipMemcpyHostToDevice));
+    if (fix) HIP_TRY_AS("hr_debug_surface", hipMemcpy(d_fix, fix, (size_t)n * 6 * 4, hipMemcpyHostToDevice));
+    if (draws) HIP_TRY_AS("hr_debug_surface", hipMemcpy(d_draws, draws, (size_t)n * 2 * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(surface_debug_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, n, d_rays, d_fix, d_draws, precise, d_out, d_out64, d_el);
+    HIP_TRY_AS("hr_debug_surface", hipGetLastError());
+    HIP_TRY_AS("hr_debug_surface", hipStreamSynchronize(c->stream));
+    HIP_TRY_AS("hr_debug_surface", hipMemcpy(out, d_out, (size_t)n * QUERY_SURFACE_FLOATS * 4, hipMemcpyDeviceToHost));
+    if (out64) HIP_TRY_AS("hr_debug_surface", hipMemcpy(out64, d_out64, (size_t)n * 6 * 8, hipMemcpyDeviceToHost));
+    HIP_TRY_AS("hr_debug_surface", hipMemcpy(out_element, d_el, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return HR_OK;
+}
+
+int hr_debug_sky(hr_ctx *c, uint32_t n, const float *dirs, float *rgb, uint32_t *where) {
+    if (!c || !dirs || !rgb || !where || !n) return fail(HR_ERR_INVALID, "hr_debug_sky: bad argument");
+    int rc = debug_refusal(c, "hr_debug_sky", NO_REGION | NO_MASK | A_SCENE);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    CallScratch scratch;
+    float *d_dirs = nullptr, *d_rgb = nullptr;
+    uint32_t *d_where = nullptr;
+    HIP_TRY_AS("hr_debug_sky", scratch.alloc((void **)&d_dirs, (size_t)n * 3 * 4));
+    HIP_TRY_AS("hr_debug_sky", scratch.alloc((void **)&d_rgb, (size_t)n * 3 * 4));
+    HIP_TRY_AS("hr_debug_sky", scratch.alloc((void **)&d_where, (size_t)n * 3 * 4));
+    HIP_TRY_AS("hr_debug_sky", hipMemcpy(d_dirs, dirs, (size_t)n * 3 * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sky_debug_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, n, d_dirs, d_rgb, d_where);
+    HIP_TRY_AS("hr_debug_sky", hipGetLastError());
+    HIP_TRY_AS("hr_debug_sky", hipStreamSynchronize(c->stream));
+    HIP_TRY_AS("hr_debug_sky", hipMemcpy(rgb, d_rgb, (size_t)n * 3 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY_AS("hr_debug_sky", hipMemcpy(where, d_where, (size_t)n * 3 * 4, hipMemcpyDeviceToHost));
+    return HR_OK;
+}
+
+int hr_debug_texture(hr_ctx *c, uint32_t n, const int32_t *image, const double *uv, float *rgb, float *rough64, uint32_t *quad) {
+    if (!c || !image || !uv || !rgb || !rough64 || !quad || !n) return fail(HR_ERR_INVALID, "hr_debug_texture: bad argument");
+    int rc = debug_refusal(c, "hr_debug_texture", NO_REGION | NO_MASK | A_SCENE);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; i++)   // the kernel indexes the scene's image table with it
+        if (image[i] < 0 || (uint32_t)image[i] >= c->num_images) return fail(HR_ERR_INVALID, "hr_debug_texture: point %u names image %d, the scene has %u", i, image[i], c->num_images);
+    HIP_TRY(hipSetDevice(c->device));
+    CallScratch scratch;
+    int32_t *d_image = nullptr;
+    double *d_uv = nullptr;
+    float *d_rgb = nullptr, *d_rough = nullptr;
+    uint32_t *d_quad = nullptr;
+    HIP_TRY_AS("hr_debug_texture", scratch.alloc((void **)&d_image, (size_t)n * 4));
+    HIP_TRY_AS("hr_debug_texture", scratch.alloc((void **)&d_uv, (size_t)n * 2 * 8));
+    HIP_TRY_AS("hr_debug_texture", scratch.alloc((void **)&d_rgb, (size_t)n * 3 * 4));
+    HIP_TRY_AS("hr_debug_texture", scratch.alloc((void **)&d_rough, (size_t)n * 4));
+    HIP_TRY_AS("hr_debug_texture", scratch.alloc((void **)&d_quad, (size_t)n * 4 * 4));
+    HIP_TRY_AS("hr_debug_texture", hipMemcpy(d_image, image, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY_AS("hr_debug_texture", hipMemcpy(d_uv, uv, (size_t)n * 2 * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(texture_debug_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->dsc, n, d_image, d_uv, d_rgb, d_rough, d_quad);
+    HIP_TRY_AS("hr_debug_texture", hipGetLastError());
+    HIP_TRY_AS("hr_debug_texture", hipStreamSynchronize(c->stream));
+    HIP_TRY_AS("hr_debug_texture", hipMemcpy(rgb, d_rgb, (size_t)n * 3 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY_AS("hr_debug_texture", hipMemcpy(rough64, d_rough, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY_AS("hr_debug_texture", hipMemcpy(quad, d_quad, (size_t)n * 4 * 4, hipMemcpyDeviceToHost));
+    return HR_OK;
 }
 
 }  // extern "C"

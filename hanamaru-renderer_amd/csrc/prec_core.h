@@ -102,11 +102,13 @@ struct PrecHit { PointMat m; Surf s; V3f nf; D3 no, nd; float cur_refl; bool sam
 // fp32 lookups: a 1e-4-texel shift there is a 1e-5 change of a colour.  The value is computed inside the primitive's branch and ONE float leaves it:
 // with the coordinates kept in f64 across the material fetch the megakernel form rendered scenes without a single texture 25 % slower (register
 // pressure), as device functions that are not inlined 40 % (the calls' spills) — NOTES P.
-HD float roughness_map_f64(const Scene &sc, int32_t image, double u, double v) {   // texture.rs:29-114, channel x
+// `corner` (hr_debug_texture only; nullptr in the render path): the quad's integer corner (ix1, iy1), as the lookup itself took it.
+HD float roughness_map_f64(const Scene &sc, int32_t image, double u, double v, uint32_t *corner = nullptr) {   // texture.rs:29-114, channel x
     const ImageRef im = sc.images[image];
     const double x = u * (double)im.width, y = v * (double)im.height;
     const double x1 = floor(x), y1 = floor(y), x2 = x1 + 1.0, y2 = y1 + 1.0;
     const uint32_t ix1 = f32_as_u32_sat((float)x1), ix2 = f32_as_u32_sat((float)x2), iy1 = f32_as_u32_sat((float)y1), iy2 = f32_as_u32_sat((float)y2);
+    if (corner) { corner[0] = ix1; corner[1] = iy1; }
     const float w11 = (float)((x2 - x) * (y2 - y)), w21 = (float)((x - x1) * (y2 - y)), w12 = (float)((x2 - x) * (y - y1)), w22 = (float)((x - x1) * (y - y1));
     const float g = texel(sc, im, ix1, iy1).x * w11 + texel(sc, im, ix2, iy1).x * w21 + texel(sc, im, ix1, iy2).x * w12 + texel(sc, im, ix2, iy2).x * w22;
     return gamma_to_linear(g);
@@ -151,10 +153,7 @@ HD void shade_hit_f64(const Scene &sc, V3f ro, V3f rd, V3f fo, V3f fd, const Tra
         n = nn * (1.0 / sqrt(ddot(nn, nn)));
         pos = c + nn;
         if (want_uv) {  // scene.rs:67-71
-            const V3f nf = narrow(n);
-            s.v = 1.0f - acosf(fminf(fmaxf(nf.y, -1.0f), 1.0f)) * (1.0f / PI_F);
-            float sg = signbit(nf.z) ? -1.0f : 1.0f;
-            s.u = 0.5f - sg * acosf(fminf(fmaxf(nf.x * HR_RSQ(nf.x * nf.x + nf.z * nf.z), -1.0f), 1.0f)) * (1.0f / PI2_F);
+            sphere_uv(narrow(n), s.u, s.v);
             const int32_t rimg = sc.materials[s.elem].roughness_img;
             if (rimg >= 0) rough64 = roughness_on_sphere_f64(sc, rimg, n.x, n.y, n.z);
         }

@@ -359,6 +359,16 @@ HD void ray_fix_load(const float *recs, uint32_t lb, uint32_t twice_a, V3f &fo, 
     }
 }
 
+// A sphere's texture coordinates (scene.rs:67-71) from its fp32 normal: v = 1 - theta / pi, u = 0.5 - phi / 2 pi with theta the angle to +y and phi
+// the signed angle from +x towards +z.  The reference takes both angles as acos — of n.y and of n.x / |n.xz|, the sign of n.z put back —, which in
+// fp32 loses half its digits where the argument nears +-1: sqrt(2 x 6e-8) = 3.5e-4 rad, i.e. 5.5e-5 of u along the whole meridians n.z ~ 0 (the
+// seam and the one opposite) and 1.1e-4 of v round the poles, 0.1 texel of a 1024-texel map.  atan2 of the same components is the same angle, well
+// conditioned everywhere: at n.z = +-0 it gives 0 / +-pi as sign x acos did, and at the exact pole (0 / 0 in the reference) a finite u.
+HD void sphere_uv(V3f n, float &u, float &v) {
+    v = 1.0f - atan2f(HR_SQRT(fmaf(n.x, n.x, n.z * n.z)), n.y) * (1.0f / PI_F);
+    u = 0.5f - atan2f(n.z, n.x) * (1.0f / PI2_F);
+}
+
 HD void hit_surface(const Scene &sc, const Ray &r, const TraceState &ts, bool want_uv, Surf &s, const RayFix &fix) {
     s.pos = r.o + r.d * ts.t;
     s.u = ts.u; s.v = ts.v;
@@ -375,11 +385,7 @@ HD void hit_surface(const Scene &sc, const Ray &r, const TraceState &ts, bool wa
             s.pos = v3(h.px, h.py, h.pz);
             s.n = v3(h.nx, h.ny, h.nz);
         }
-        if (want_uv) {  // scene.rs:67-71
-            s.v = 1.0f - acosf(fminf(fmaxf(s.n.y, -1.0f), 1.0f)) * (1.0f / PI_F);
-            float sg = signbit(s.n.z) ? -1.0f : 1.0f;
-            s.u = 0.5f - sg * acosf(fminf(fmaxf(s.n.x * HR_RSQ(s.n.x * s.n.x + s.n.z * s.n.z), -1.0f), 1.0f)) * (1.0f / PI2_F);
-        }
+        if (want_uv) sphere_uv(s.n, s.u, s.v);
     } else {
         const f4 mn = sc.cuboids[2 * ts.prim], mx = sc.cuboids[2 * ts.prim + 1];
         s.elem = float_as_int(mn.w);
@@ -433,7 +439,12 @@ HD V3f sample_bilinear(const Scene &sc, int32_t image, float u, float v) {
     float x2 = x1 + 1.0f, y2 = y1 + 1.0f;
     uint32_t ix1 = f32_as_u32_sat(x1), ix2 = f32_as_u32_sat(x2), iy1 = f32_as_u32_sat(y1), iy2 = f32_as_u32_sat(y2);
     V3f p11 = texel(sc, im, ix1, iy1), p12 = texel(sc, im, ix1, iy2), p21 = texel(sc, im, ix2, iy1), p22 = texel(sc, im, ix2, iy2);
-    V3f g = p11 * ((x2 - x) * (y2 - y)) + p21 * ((x - x1) * (y2 - y)) + p12 * ((x2 - x) * (y - y1)) + p22 * ((x - x1) * (y - y1));
+    // the weights from the fractional part: for 0 <= x < 2^24 both x - x1 and x1 + 1 are exact and 1 - (x - x1) is x2 - x to the bit (below 0,
+    // x - x1 rounds and the two may differ in the last bit); beyond 2^24, x1 + 1 rounds back to x1 and (x2 - x), (x - x1) would both be 0 — a
+    // black texel where the reference's f64 clamps to the border's (a coordinate of 5e9: tests/lookup_sweeps.py, the `as u32` saturation).
+    // (sky_sample's footprint branch keeps x2 - x: its x is clamped to [0, sky_w].)
+    const float fx = x - x1, fy = y - y1, gx = 1.0f - fx, gy = 1.0f - fy;
+    V3f g = p11 * (gx * gy) + p21 * (fx * gy) + p12 * (gx * fy) + p22 * (fx * fy);
     return v3(gamma_to_linear(g.x), gamma_to_linear(g.y), gamma_to_linear(g.z));
 }
 HD V3f tex_sample(const Scene &sc, int32_t image, V3f tint, float u, float v) {  // texture.rs:108-114
@@ -764,13 +775,20 @@ HD void plog_hit(PathLog &l, int32_t elem) { l.hash = (l.hash ^ (uint32_t)(elem 
 HD uint32_t quad_hash16(uint32_t ix, uint32_t iy) { return ((ix * 0x9E3779B1u) ^ (iy * 0x85EBCA77u)) >> 16; }
 HD void plog_quad_add(PathLog &l, uint32_t ix, uint32_t iy) { l.ev9 = (l.ev9 & 0xffffu) | ((((l.ev9 >> 16) + quad_hash16(ix, iy)) & 0xffffu) << 16); }
 // the corner (x1, y1) sample_bilinear() starts from (texture.rs:30-33), from the same fp32 products
+HD void quad_corner(const Scene &sc, int32_t image, float u, float v, uint32_t &ix1, uint32_t &iy1) {
+    const ImageRef im = sc.images[image];
+    ix1 = f32_as_u32_sat(floorf(u * (float)im.width)); iy1 = f32_as_u32_sat(floorf(v * (float)im.height));
+}
 HD void plog_quad(const Scene &sc, PathLog &l, int32_t image, float u, float v) {
     if (image < 0) return;
-    const ImageRef im = sc.images[image];
-    plog_quad_add(l, f32_as_u32_sat(floorf(u * (float)im.width)), f32_as_u32_sat(floorf(v * (float)im.height)));
+    uint32_t ix1, iy1;
+    quad_corner(sc, image, u, v, ix1, iy1);
+    plog_quad_add(l, ix1, iy1);
 }
-// face and corner of sky_sample()'s lookup: the same comparisons and quotients (scene.rs:295-319)
-HD void plog_sky(const Scene &sc, PathLog &l, V3f d) {
+// face and corner of sky_sample()'s lookup: the same comparisons and quotients (scene.rs:295-319).  sky_where returns them (the log hashes
+// them, hr_debug_sky hands them out).
+struct SkyWhere { int face; uint32_t x1, y1; };
+HD SkyWhere sky_where(const Scene &sc, V3f d) {
     float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
     int face; float u, v;
     if (ax > ay && ax > az) {
@@ -784,10 +802,16 @@ HD void plog_sky(const Scene &sc, PathLog &l, V3f d) {
         if (!signbit(d.z)) { face = 4; u = d.x * i; v = d.y * i; } else { face = 5; u = d.x * i; v = -d.y * i; }
     }
     u = 0.5f * (u + 1.0f); v = 0.5f * (v + 1.0f);
-    plog_hit(l, 0x2000 + face);
     uint32_t w = sc.sky_w, h = sc.sky_h;
     if (!sc.sky_quads) { const ImageRef im = sc.images[sc.sky_image[face]]; w = im.width; h = im.height; }
-    plog_quad_add(l, f32_as_u32_sat(floorf(u * (float)w)), f32_as_u32_sat(floorf(v * (float)h)));
+    SkyWhere sw;
+    sw.face = face; sw.x1 = f32_as_u32_sat(floorf(u * (float)w)); sw.y1 = f32_as_u32_sat(floorf(v * (float)h));
+    return sw;
+}
+HD void plog_sky(const Scene &sc, PathLog &l, V3f d) {
+    const SkyWhere sw = sky_where(sc, d);
+    plog_hit(l, 0x2000 + sw.face);
+    plog_quad_add(l, sw.x1, sw.y1);
 }
 // which face of scene.rs:160-182's cascade a cuboid hit took, from the normal hit_surface() chose
 HD int32_t cuboid_face_of(V3f n) { return n.y > 0.0f ? 0 : n.y < 0.0f ? 1 : n.x < 0.0f ? 2 : n.x > 0.0f ? 3 : n.z < 0.0f ? 4 : n.z > 0.0f ? 5 : 6; }

@@ -8,6 +8,7 @@
 #include "device_scene.h"
 #include "isaac_core.h"
 #include "pt_core.h"
+#include "query_core.h"
 
 using namespace hr;
 
@@ -431,6 +432,27 @@ __global__ void intersect_debug_kernel(Scene sc, uint32_t n, const float *__rest
     LaneCounters lc;
     while (ts.cur != NODE_END) trace_step<false>(sc, r, ts, &lc);
     write_hit_record(sc, r, ts, i, out, out_elem);
+}
+
+// hr_debug_surface / hr_debug_sky / hr_debug_texture: one ray or point per thread through query_core.h — what lies between "the walk found
+// primitive k at distance t" and "the BSDF is evaluated" (hit_surface, material_at, shade_hit_f64's geometry half), the sky and the texture lookups.
+__global__ __launch_bounds__(64) void surface_debug_kernel(Scene sc, uint32_t n, const float *__restrict__ rays, const float *__restrict__ fix, const double *__restrict__ draws,
+                                                           int precise, float *__restrict__ out, double *__restrict__ out64, int32_t *__restrict__ out_elem) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    query_surface(sc, rays + (size_t)i * 6, fix ? fix + (size_t)i * 6 : nullptr, draws ? draws + (size_t)i * 2 : nullptr, precise != 0,
+                  out + (size_t)i * QUERY_SURFACE_FLOATS, out64 ? out64 + (size_t)i * 6 : nullptr, out_elem + i);
+}
+__global__ __launch_bounds__(64) void sky_debug_kernel(Scene sc, uint32_t n, const float *__restrict__ dirs, float *__restrict__ rgb, uint32_t *__restrict__ where) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    query_sky(sc, dirs + (size_t)i * 3, rgb + (size_t)i * 3, where + (size_t)i * 3);
+}
+__global__ __launch_bounds__(64) void texture_debug_kernel(Scene sc, uint32_t n, const int32_t *__restrict__ image, const double *__restrict__ uv, float *__restrict__ rgb,
+                                                           float *__restrict__ rough64, uint32_t *__restrict__ quad) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    query_texture(sc, image[i], uv + (size_t)i * 2, rgb + (size_t)i * 3, rough64 + i, quad + (size_t)i * 4);
 }
 
 // DebugRenderer (renderer.rs:101-146) through the production traversal: one wave per 4x4-pixel tile, one lane per (pixel, sub-sample) as in the

@@ -182,6 +182,9 @@ def hip_lib():
         L.hr_debug_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hr_debug_draws.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.hr_debug_intersect.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hr_debug_surface.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hr_debug_sky.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hr_debug_texture.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hr_debug_path_log.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.hr_debug_path_draws.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.hr_debug_path_draw_residuals.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -786,3 +789,29 @@ class Renderer:
             assert sl.shape[0] == r.shape[0]
         self._check(self.L.hr_debug_trace(self._h, r.shape[0], r.ctypes.data, sl.ctypes.data if sl is not None else None, out.ctypes.data, el.ctypes.data))
         return out, el
+
+    def debug_surface(self, rays, fix=None, draws=None, precise=False):
+        """hr_debug_surface: (out [n, 24] float32, out64 [n, 6] float64, element [n] int32) — hanamaru_hip_debug.h has the record's layout."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        f = None if fix is None else np.ascontiguousarray(fix, dtype=np.float32).reshape(n, 6)
+        d = None if draws is None else np.ascontiguousarray(draws, dtype=np.float64).reshape(n, 2)
+        out, out64, el = np.empty((n, 24), dtype=np.float32), np.empty((n, 6), dtype=np.float64), np.empty((n,), dtype=np.int32)
+        self._check(self.L.hr_debug_surface(self._h, n, r.ctypes.data, None if f is None else f.ctypes.data, None if d is None else d.ctypes.data,
+                                            1 if precise else 0, out.ctypes.data, out64.ctypes.data, el.ctypes.data))
+        return out, out64, el
+
+    def debug_sky(self, dirs):
+        """hr_debug_sky: (rgb [n, 3] float32, where [n, 3] uint32 = {face + 8 on the footprint table's form, x1, y1})."""
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        rgb, where = np.empty((d.shape[0], 3), dtype=np.float32), np.empty((d.shape[0], 3), dtype=np.uint32)
+        self._check(self.L.hr_debug_sky(self._h, d.shape[0], d.ctypes.data, rgb.ctypes.data, where.ctypes.data))
+        return rgb, where
+
+    def debug_texture(self, image, uv):
+        """hr_debug_texture: (rgb [n, 3] float32, rough64 [n] float32, quad [n, 4] uint32 = the fp32 lookup's corner, the f64 read's corner)."""
+        im = np.ascontiguousarray(image, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(uv, dtype=np.float64).reshape(im.shape[0], 2)
+        rgb, rough, quad = np.empty((im.shape[0], 3), dtype=np.float32), np.empty((im.shape[0],), dtype=np.float32), np.empty((im.shape[0], 4), dtype=np.uint32)
+        self._check(self.L.hr_debug_texture(self._h, im.shape[0], im.ctypes.data, c.ctypes.data, rgb.ctypes.data, rough.ctypes.data, quad.ctypes.data))
+        return rgb, rough, quad

@@ -80,6 +80,28 @@ int hr_debug_intersect(hr_ctx *ctx, uint32_t n, const float *rays, float *out, i
  * the visibility verdict of renderer.rs:280 is then  hit && (distance - shadow_len)^2 < 4e-4. */
 int hr_debug_trace(hr_ctx *ctx, uint32_t n, const float *rays, const float *shadow_len, float *out, int32_t *out_element);
 
+/* What lies between "the walk found primitive k at distance t" and "the BSDF is evaluated", point by point (tests/lookup_sweeps.py).  The
+ * kernels unpack the arguments and call the render path's own functions (csrc/query_core.h).
+ *
+ * hr_debug_surface: closest hit of n rays by hr_debug_intersect's scalar walk, then the surface and the material at the hit.
+ *   rays: n * 6 floats.  fix: n * 6 floats or NULL — what rounding an f64 ray to `rays` took away (origin, direction), the residuals a path's
+ *   first ray carries.  draws: n * 2 doubles or NULL (0.5, 0.5) — the iteration's draws, read by precise == 1 only.
+ *   out: n * 24 floats { hit, distance, pos xyz, normal xyz, u, v, cuboid face (scene.rs:160-182's cascade: 0 Y+, 1 Y-, 2 X-, 3 X+, 4 Z-, 5 Z+;
+ *   -1: not a cuboid), surface, param, albedo rgb, emission rgb, roughness, then for precise == 1 the sampled bounce's scalar, sampled (0 / 1),
+ *   transmitted (0 / 1), else zeros; slot 23 is 0 }.  A miss: { 0, the search limit, zeros }, element -1.
+ *   precise == 0: hit_surface + material_at (fp32 shading).  precise == 1: shade_hit_f64 (precise shading): normal, u, v, element and material are
+ *   its, pos stays the fp32 walk's, and out64 (n * 6 doubles or NULL) takes the next ray's origin and direction.
+ * hr_debug_sky: rgb[i] = the sky in direction dirs[i] (n * 3 floats), by the lookup the uploaded scene uses; where[i] = { cube-map face
+ *   (scene.rs:295-319: 0 +x .. 5 -z) + 8 when the lookup went through the footprint table (six faces of one size), x1, y1 } — the integer
+ *   corner of the texel quad (texture.rs:30-33), as hr_debug_path_log hashes it.
+ * hr_debug_texture: rgb[i] = bilinear lookup (texture.rs:29-49) in image[i] (an index into the uploaded scene's images; out of range:
+ *   HR_ERR_INVALID) at (float)uv[i]; rough64[i] = the red channel read at the f64 coordinates, as precise shading reads a roughness map;
+ *   quad[i] = four words: the fp32 lookup's corner (x1, y1), then the corner the f64 read started from. */
+int hr_debug_surface(hr_ctx *ctx, uint32_t n, const float *rays, const float *fix, const double *draws, int precise, float *out, double *out64,
+                     int32_t *out_element);
+int hr_debug_sky(hr_ctx *ctx, uint32_t n, const float *dirs, float *rgb, uint32_t *where);
+int hr_debug_texture(hr_ctx *ctx, uint32_t n, const int32_t *image, const double *uv, float *rgb, float *rough64, uint32_t *quad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,12 +292,15 @@ static inline V3 sample_nearest_screen(const Image &im, uint32_t x, uint32_t y) 
 // path-log bookkeeping (PathLog below; no influence on the algorithm): while calc_pixel traces a MAIN ray with a log attached, every bilinear
 // lookup adds a 16-bit hash of its integer corner (x1, y1) to *t_quad_sum — the texel quad the value is interpolated in
 static thread_local uint32_t *t_quad_sum = nullptr;
+// the same for the point sweeps (orc_skybox_sample_n, orc_image_sample_bilinear_n): the corner itself, of the last lookup
+static thread_local uint32_t *t_quad_corner = nullptr;
 static inline uint32_t quad_hash16(uint32_t ix, uint32_t iy) { return ((ix * 0x9E3779B1u) ^ (iy * 0x85EBCA77u)) >> 16; }
 static V3 sample_bilinear(const Image &im, double u, double v) {  // texture.rs:29-49
     double x = u * (double)im.width, y = v * (double)im.height;
     double x1 = std::floor(x), y1 = std::floor(y);
     double x2 = x1 + 1.0, y2 = y1 + 1.0;
     if (t_quad_sum) *t_quad_sum = (*t_quad_sum + quad_hash16(f64_as_u32(x1), f64_as_u32(y1))) & 0xffffu;
+    if (t_quad_corner) { t_quad_corner[0] = f64_as_u32(x1); t_quad_corner[1] = f64_as_u32(y1); }
     V3 p11 = sample_nearest_screen(im, f64_as_u32(x1), f64_as_u32(y1));
     V3 p12 = sample_nearest_screen(im, f64_as_u32(x1), f64_as_u32(y2));
     V3 p21 = sample_nearest_screen(im, f64_as_u32(x2), f64_as_u32(y1));
@@ -1215,6 +1218,33 @@ ORC_API int orc_image_sample_bilinear(const orc_scene *os, uint32_t image, doubl
     V3 c = sample_bilinear(os->s.images[image], u, v);
     rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
     return 0;
+}
+
+// The three lookups on n points at once (tests/lookup_sweeps.py asks ~13 questions per point): loops over the entries above.
+// intersect_material_n: rays n x 6, out n x 19 (orc_intersect_material's record), element n.
+ORC_API int orc_intersect_material_n(const orc_scene *os, size_t n, const double *rays, double *out, int32_t *out_element) {
+    for (size_t i = 0; i < n; i++) orc_intersect_material(os, rays + 6 * i, out + 19 * i, out_element + i);
+    return 0;
+}
+// skybox_sample_n: dirs n x 3, rgb n x 3, where n x 3 = {face, x1, y1: the integer corner of the lookup's texel quad}
+ORC_API int orc_skybox_sample_n(const orc_scene *os, size_t n, const double *dirs, double *rgb, uint32_t *where) {
+    for (size_t i = 0; i < n; i++) {
+        where[3 * i] = (uint32_t)skybox_face(V3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+        t_quad_corner = where + 3 * i + 1;
+        orc_skybox_sample(os, dirs + 3 * i, rgb + 3 * i);
+        t_quad_corner = nullptr;
+    }
+    return 0;
+}
+// image_sample_bilinear_n: image n, uv n x 2, rgb n x 3, quad n x 2
+ORC_API int orc_image_sample_bilinear_n(const orc_scene *os, size_t n, const int32_t *image, const double *uv, double *rgb, uint32_t *quad) {
+    int rc = 0;
+    for (size_t i = 0; i < n && !rc; i++) {
+        t_quad_corner = quad + 2 * i;
+        rc = image[i] < 0 ? -1 : orc_image_sample_bilinear(os, (uint32_t)image[i], uv[2 * i], uv[2 * i + 1], rgb + 3 * i);
+        t_quad_corner = nullptr;
+    }
+    return rc;
 }
 
 // BVH shape statistics.  element < 0 -> top-level BVH.

@@ -46,6 +46,9 @@ def lib():
         L.orc_ggx_scalar_n.argtypes = [C.c_size_t] + [C.c_void_p] * 7
         L.orc_skybox_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_image_sample_bilinear.argtypes = [C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_void_p]
+        L.orc_intersect_material_n.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_skybox_sample_n.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_image_sample_bilinear_n.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_bvh_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_top_leaves.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.orc_num_emissions.argtypes = [C.c_void_p]
@@ -152,6 +155,30 @@ class OracleScene:
         rc = lib().orc_image_sample_bilinear(self._h, image, u, v, out.ctypes.data)
         assert rc == 0
         return out
+
+    def intersect_material_n(self, rays):
+        """intersect_material on n rays: (out [n, 19] float64 {hit, distance, position, normal, u, v, surface, param, albedo, emission, roughness},
+        element [n] int32)"""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out, el = np.zeros((r.shape[0], 19), dtype=np.float64), np.empty((r.shape[0],), dtype=np.int32)
+        lib().orc_intersect_material_n(self._h, r.shape[0], r.ctypes.data, out.ctypes.data, el.ctypes.data)
+        return out, el
+
+    def skybox_n(self, dirs):
+        """skybox on n directions: (rgb [n, 3] float64, where [n, 3] uint32 = {face, x1, y1 of the texel quad})"""
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        rgb, where = np.zeros((d.shape[0], 3), dtype=np.float64), np.zeros((d.shape[0], 3), dtype=np.uint32)
+        lib().orc_skybox_sample_n(self._h, d.shape[0], d.ctypes.data, rgb.ctypes.data, where.ctypes.data)
+        return rgb, where
+
+    def image_bilinear_n(self, image, uv):
+        """image_bilinear on n points: (rgb [n, 3] float64, quad [n, 2] uint32)"""
+        im = np.ascontiguousarray(image, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(uv, dtype=np.float64).reshape(im.shape[0], 2)
+        rgb, quad = np.zeros((im.shape[0], 3), dtype=np.float64), np.zeros((im.shape[0], 2), dtype=np.uint32)
+        rc = lib().orc_image_sample_bilinear_n(self._h, im.shape[0], im.ctypes.data, c.ctypes.data, rgb.ctypes.data, quad.ctypes.data)
+        assert rc == 0
+        return rgb, quad
 
     def bvh_stats(self, element):
         st = (C.c_uint64 * 11)()

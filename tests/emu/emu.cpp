@@ -19,6 +19,7 @@
 #include "post_core.h"
 #include <cstdlib>
 #include "pt_core.h"
+#include "query_core.h"
 #include "wf_core.h"
 
 using namespace hr;
@@ -664,6 +665,41 @@ int emu_intersect(const emu_scene *e, uint32_t n, const float *rays, float *out,
         }
         out_elem[i] = elem;
     }
+    return 0;
+}
+
+// hr_debug_surface / hr_debug_sky / hr_debug_texture on the host: the same per-point functions (csrc/query_core.h), the same signatures
+int emu_surface(const emu_scene *e, uint32_t n, const float *rays, const float *fix, const double *draws, int precise, float *out, double *out64, int32_t *out_elem) {
+    for (uint32_t i = 0; i < n; i++)
+        query_surface(e->view, rays + (size_t)i * 6, fix ? fix + (size_t)i * 6 : nullptr, draws ? draws + (size_t)i * 2 : nullptr, precise != 0,
+                      out + (size_t)i * QUERY_SURFACE_FLOATS, out64 ? out64 + (size_t)i * 6 : nullptr, out_elem + i);
+    return 0;
+}
+int emu_sky(const emu_scene *e, uint32_t n, const float *dirs, float *rgb, uint32_t *where) {
+    for (uint32_t i = 0; i < n; i++) query_sky(e->view, dirs + (size_t)i * 3, rgb + (size_t)i * 3, where + (size_t)i * 3);
+    return 0;
+}
+int emu_texture(const emu_scene *e, uint32_t n, const int32_t *image, const double *uv, float *rgb, float *rough64, uint32_t *quad) {
+    for (uint32_t i = 0; i < n; i++) {
+        if (image[i] < 0 || (size_t)image[i] >= e->hs.images.size()) return 1;
+        query_texture(e->view, image[i], uv + (size_t)i * 2, rgb + (size_t)i * 3, rough64 + i, quad + (size_t)i * 4);
+    }
+    return 0;
+}
+
+// 1 when the scene's sky lookup goes through the footprint table (six faces of one size), 0 for the per-face form
+int emu_sky_form(const emu_scene *e) { return e->view.sky_quads ? 1 : 0; }
+// A deliberately WRONG footprint table (tests/test_lookups_cpu.py shows that the sweeps notice it): the table's last corner column, x = sky_w,
+// takes the texels of column sky_w - 2 instead of the clamped column sky_w - 1.
+int emu_break_sky_quads(emu_scene *e) {
+    HostScene &hs = e->hs;
+    if (hs.sky_quads.empty() || hs.sky_w < 2) return 1;
+    const uint32_t w = hs.sky_w, h = hs.sky_h;
+    for (uint32_t f = 0; f < 6; f++)
+        for (uint32_t y = 0; y <= h; y++) {
+            uint32_t *row = hs.sky_quads.data() + (((size_t)f * (h + 1u) + y) * (w + 2u)) * 2u;
+            row[2u * w] = row[2u * (w - 2u)]; row[2u * w + 1u] = row[2u * (w - 2u) + 1u];
+        }
     return 0;
 }
 

@@ -32,6 +32,9 @@ def lib():
         L.emu_path_log.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.emu_render_debug.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.emu_intersect.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.emu_surface.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.emu_sky.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.emu_texture.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.emu_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
@@ -105,6 +108,41 @@ class EmuScene:
         el = np.empty((r.shape[0],), dtype=np.int32)
         lib().emu_intersect(self._h, r.shape[0], r.ctypes.data, out.ctypes.data, el.ctypes.data)
         return out, el
+
+    # the twins of Renderer.debug_surface / debug_sky / debug_texture (csrc/query_core.h on the host): same arguments, same results
+    def debug_surface(self, rays, fix=None, draws=None, precise=False):
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        f = None if fix is None else np.ascontiguousarray(fix, dtype=np.float32).reshape(n, 6)
+        d = None if draws is None else np.ascontiguousarray(draws, dtype=np.float64).reshape(n, 2)
+        out, out64, el = np.empty((n, 24), dtype=np.float32), np.empty((n, 6), dtype=np.float64), np.empty((n,), dtype=np.int32)
+        lib().emu_surface(self._h, n, r.ctypes.data, None if f is None else f.ctypes.data, None if d is None else d.ctypes.data, 1 if precise else 0,
+                          out.ctypes.data, out64.ctypes.data, el.ctypes.data)
+        return out, out64, el
+
+    def sky_form(self):
+        """1: the sky lookup goes through the footprint table (six faces of one size); 0: the per-face form"""
+        lib().emu_sky_form.argtypes = [C.c_void_p]
+        return int(lib().emu_sky_form(self._h))
+
+    def break_sky_quads(self):
+        """a deliberately wrong footprint table: its last corner column takes the texels of column w - 2 (the sweeps must notice)"""
+        lib().emu_break_sky_quads.argtypes = [C.c_void_p]
+        assert lib().emu_break_sky_quads(self._h) == 0
+
+    def debug_sky(self, dirs):
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        rgb, where = np.empty((d.shape[0], 3), dtype=np.float32), np.empty((d.shape[0], 3), dtype=np.uint32)
+        lib().emu_sky(self._h, d.shape[0], d.ctypes.data, rgb.ctypes.data, where.ctypes.data)
+        return rgb, where
+
+    def debug_texture(self, image, uv):
+        im = np.ascontiguousarray(image, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(uv, dtype=np.float64).reshape(im.shape[0], 2)
+        rgb, rough, quad = np.empty((im.shape[0], 3), dtype=np.float32), np.empty((im.shape[0],), dtype=np.float32), np.empty((im.shape[0], 4), dtype=np.uint32)
+        rc = lib().emu_texture(self._h, im.shape[0], im.ctypes.data, c.ctypes.data, rgb.ctypes.data, rough.ctypes.data, quad.ctypes.data)
+        assert rc == 0
+        return rgb, rough, quad
 
 
 PLOC_TOP_DEFAULT = 8192   # lbvh_core.h PLOC_TOP_CLUSTERS
