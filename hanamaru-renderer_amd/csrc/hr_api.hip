@@ -12,7 +12,7 @@
 //   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
 //                    robust_kernel, robust_denoise_init_kernel and robust_noise_kernel (robust_core.h); restore_init_kernel, spread_norm_kernel,
 //                    spread_gather_kernel and restore_final_kernel (restore_core.h); select_init_kernel, atrous3_kernel, select_pick_kernel and
-//                    select_smooth_kernel (select_core.h)
+//                    select_smooth_kernel (select_core.h); select_noise_kernel and select_noise_error_kernel (select_noise_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
@@ -2432,13 +2432,16 @@ int hr_select_default_params(hr_select_params *out) {
     out->smooth = 2;   // the lowest worst case of tools/select_quality.py's table
     return HR_OK;
 }
-int hr_denoise_select(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select) {
-    static const char *const who = "hr_denoise_select";
+// What hr_denoise_select and the error estimate of its image (selected_noise_run) ask before they touch anything, in one order: the options, the
+// parameters (p, s: the caller's or the defaults), the samplings behind the planes, then ft — {floor, threshold} of an estimate, or nullptr: none
+// to check —, then the device's part: the counts, the init kernel's row (v), the guide planes (rendered when there are none).
+// need_counts: hr_select_tiles_selected (it also needs option sample_counts).
+static int select_ready(hr_ctx *c, const char *who, const hr_denoise_params *params, const hr_select_params *select, bool need_counts, const double *ft,
+                        hr_denoise_params &p, hr_select_params &s, const SelectInitVariant *&v) {
     int rc = plane_ready(c, BUCKETS, who);
     if (rc || (rc = plane_ready(c, MOMENTS, who))) return rc;
-    hr_denoise_params p;
+    if (need_counts && (rc = plane_ready(c, COUNTS, who))) return rc;
     if ((rc = denoise_params(who, params, p))) return rc;
-    hr_select_params s;
     if (select) s = *select;
     else (void)hr_select_default_params(&s);
     if (s.smooth > SELECT_MAX_SMOOTH) return fail(HR_ERR_INVALID, "%s: smooth must be in [0,%u]", who, SELECT_MAX_SMOOTH);
@@ -2447,13 +2450,23 @@ int hr_denoise_select(hr_ctx *c, const hr_denoise_params *params, const hr_selec
     if (c->moments_n >= (1ull << 30)) return fail(HR_ERR_INVALID, "%s: %llu samplings do not fit the resolve's 32-bit scale", who, (unsigned long long)c->moments_n);
     if (c->moments_n != c->buckets_n)
         return fail(HR_ERR_INVALID, "%s: the moments cover %llu samplings, the buckets %llu (they must cover the same samplings)", who, (unsigned long long)c->moments_n, (unsigned long long)c->buckets_n);
+    if (ft && (rc = floor_and_threshold_ok(who, ft[0], ft[1]))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = hr_synchronize(c))) return rc;
     if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;   // (every n >= 2 and none beyond the moments' — which are the buckets')
     const uint32_t K = c->robust_k;
-    const SelectInitVariant *v = select_select_init_kernel(K);
+    v = select_select_init_kernel(K);
     if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no select_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
     if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;
+    return HR_OK;
+}
+int hr_denoise_select(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select) {
+    static const char *const who = "hr_denoise_select";
+    hr_denoise_params p;
+    hr_select_params s;
+    const SelectInitVariant *v = nullptr;
+    int rc = select_ready(c, who, params, select, false, nullptr, p, s, v);
+    if (rc) return rc;
     const size_t pixels = region_pixels(c);
     // the call's planes first: a device without room leaves S as it was
     CallScratch scratch;
@@ -2498,6 +2511,89 @@ int hr_read_selected_levels(hr_ctx *c, uint8_t *host) {
 int hr_resolve_selected(hr_ctx *c, uint8_t *host_rgb8) {
     int rc = image_ready(c, SELECTED_IMAGE, "hr_resolve_selected", host_rgb8);
     return rc ? rc : resolve_region(c, 0, host_rgb8, c->selected);
+}
+
+// ---- the error estimate of S, its stop rule and its tile selection (select_noise_core.h) ----
+// One run behind the four entry points (`who`): hr_denoise_select's pipeline with select_noise_kernel in the pick's place, everything in call
+// scratch — the run's own S and L too — so no kept image and no validity word is touched (the guide planes are rendered when there are none, as
+// hr_denoise_select does).  Everything that is refused is refused before anything is touched.  What is asked for: est (the summary of e_S),
+// host_img (e_S), host_mse (M), tiles (the selection by e_S; `active` may be null).  floor and threshold are checked unless host_mse alone is asked.
+// The call holds 453 bytes per pixel with levels and smooth: the states twice (288), {A0, B0} (48), {va0, vb0} (48), e and m twice (32), best (8),
+// M (8), e_S (8), S (12), L (1).
+static int selected_noise_run(hr_ctx *c, const char *who, const hr_denoise_params *params, const hr_select_params *select, double floor, double threshold, hr_noise *est,
+                              double *host_img, double *host_mse, bool tiles, uint32_t *active) {
+    hr_denoise_params p;
+    hr_select_params s;
+    const SelectInitVariant *v = nullptr;
+    const bool want_error = est || host_img || tiles;
+    const double ft[2] = {floor, threshold};
+    int rc = select_ready(c, who, params, select, tiles, want_error ? ft : nullptr, p, s, v);
+    if (rc) return rc;
+    const size_t pixels = region_pixels(c);
+    CallScratch scratch;
+    double *st[2] = {nullptr, nullptr}, *raw = nullptr, *var0 = nullptr, *e[2] = {nullptr, nullptr}, *m[2] = {nullptr, nullptr}, *best = nullptr, *M = nullptr, *img = nullptr, *d = nullptr;
+    float *S = nullptr;
+    uint8_t *L = nullptr;
+    for (int k = 0; k < (p.levels ? 2 : 1); k++) HIP_TRY_AS(who, scratch.alloc((void **)&st[k], pixels * 18 * sizeof(double)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&raw, pixels * 6 * sizeof(double)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&var0, pixels * 6 * sizeof(double)));
+    for (int k = 0; k < (s.smooth ? 2 : 0); k++) {
+        HIP_TRY_AS(who, scratch.alloc((void **)&e[k], pixels * sizeof(double)));
+        HIP_TRY_AS(who, scratch.alloc((void **)&m[k], pixels * sizeof(double)));
+    }
+    HIP_TRY_AS(who, scratch.alloc((void **)&best, pixels * sizeof(double)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&M, pixels * sizeof(double)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&S, pixels * 3 * sizeof(float)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&L, pixels));
+    std::vector<double> h(SELECT_NOISE_BLOCKS * 3);
+    if (want_error) {
+        HIP_TRY_AS(who, scratch.alloc((void **)&img, pixels * sizeof(double)));
+        HIP_TRY_AS(who, scratch.alloc((void **)&d, h.size() * sizeof(double)));
+    }
+    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
+    const int demodulate = p.demodulate && p.levels ? 1 : 0;
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
+    hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (uint32_t)c->moments_n, c->accum, c->moments, c->guides, st[0], raw, pixels, demodulate);
+    for (uint32_t l = 0; l <= p.levels; l++) {
+        double *cur = st[l & 1u], *nxt = st[(l + 1u) & 1u];
+        if (s.smooth) {
+            hipLaunchKernelGGL(select_noise_kernel, flat, dim3(256), 0, c->stream, cur, raw, var0, c->guides, (const double *)nullptr, (const double *)nullptr, e[0], m[0], l, best, L, S, M,
+                               (uint32_t)pixels, demodulate);
+            for (uint32_t t = 0; t < s.smooth; t++) {
+                hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, e[t & 1u], e[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
+                hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, m[t & 1u], m[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
+            }
+        }
+        hipLaunchKernelGGL(select_noise_kernel, flat, dim3(256), 0, c->stream, cur, raw, var0, c->guides, s.smooth ? e[s.smooth & 1u] : (const double *)nullptr,
+                           s.smooth ? m[s.smooth & 1u] : (const double *)nullptr, (double *)nullptr, (double *)nullptr, l, best, L, S, M, (uint32_t)pixels, demodulate);
+        if (l < p.levels) hipLaunchKernelGGL(atrous3_kernel, tiles2d, dim3(32, 8), 0, c->stream, cur, c->guides, nxt, c->RW, c->RH, 1u << l, sg);
+    }
+    if (want_error) hipLaunchKernelGGL(select_noise_error_kernel, dim3(SELECT_NOISE_BLOCKS), dim3(256), 0, c->stream, M, S, pixels, floor, threshold, img, d);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    if (est) HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (host_img) HIP_TRY_AS(who, hipMemcpyAsync(host_img, img, pixels * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (host_mse) HIP_TRY_AS(who, hipMemcpyAsync(host_mse, M, pixels * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
+    if (est) noise_summary(h, c->moments_n, pixels, est);
+    if (tiles && (rc = select_tiles_run(c, who, img, floor, threshold, active))) return rc;
+    return drain_events(c);
+}
+int hr_selected_noise_estimate(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select, double floor, double threshold, hr_noise *out) {
+    if (c && !out) return fail(HR_ERR_INVALID, "hr_selected_noise_estimate: null argument");
+    return selected_noise_run(c, "hr_selected_noise_estimate", params, select, floor, threshold, out, nullptr, nullptr, false, nullptr);
+}
+int hr_read_selected_noise_image(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select, double floor, double *host) {
+    if (c && !host) return fail(HR_ERR_INVALID, "hr_read_selected_noise_image: null argument");
+    return selected_noise_run(c, "hr_read_selected_noise_image", params, select, floor, 0.0, nullptr, host, nullptr, false, nullptr);
+}
+int hr_read_selected_mse(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select, double *host) {
+    if (c && !host) return fail(HR_ERR_INVALID, "hr_read_selected_mse: null argument");
+    return selected_noise_run(c, "hr_read_selected_mse", params, select, 0.0, 0.0, nullptr, nullptr, host, false, nullptr);
+}
+int hr_select_tiles_selected(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select, double floor, double threshold, uint32_t *active) {
+    return selected_noise_run(c, "hr_select_tiles_selected", params, select, floor, threshold, nullptr, nullptr, nullptr, true, active);
 }
 
 int hr_get_stats(hr_ctx *c, hr_stats *out) {

@@ -8,6 +8,7 @@
 #include "restore_core.h"
 #include "robust_core.h"
 #include "select_core.h"
+#include "select_noise_core.h"
 
 using namespace hr;
 
@@ -270,4 +271,79 @@ __global__ __launch_bounds__(256) void select_smooth_kernel(const double *__rest
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= W || y >= H) return;
     out[(size_t)y * W + x] = select_smooth(e, W, H, x, y, step);
+}
+
+// The error estimate of S (select_noise_core.h).  The kernels carry no arithmetic of their own: every value is the core's.  The run is
+// hr_denoise_select's with select_noise_kernel in select_pick_kernel's place: select_init_kernel, atrous3_kernel and select_smooth_kernel (over the e
+// plane and over the m plane) are launched as they are.  var0: six more planes of a double per pixel, {va0, vb0} — the V of F_A,0 and F_B,0, which the
+// ping-pong of the states overwrites at level 2; the launch of level 0 that computes m writes them, every later one reads them.
+// select_noise_kernel has select_pick_kernel's three forms.  e_out != nullptr: e_l and m_l of every pixel into e_out and m_out, nothing else (the
+// smoothing passes come next).  Otherwise the pick with M beside it, the error and m taken from e_in and m_in (the smoothed planes) or, e_in == nullptr,
+// computed here (smooth = 0: one launch per level).
+__global__ __launch_bounds__(256) void select_noise_kernel(const double *__restrict__ st, const double *__restrict__ raw, double *__restrict__ var0, const float *__restrict__ guides,
+                                                           const double *__restrict__ e_in, const double *__restrict__ m_in, double *__restrict__ e_out, double *__restrict__ m_out,
+                                                           uint32_t l, double *__restrict__ best, uint8_t *__restrict__ L, float *__restrict__ S, double *__restrict__ M,
+                                                           uint32_t pixels, int demodulate) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    const SelectPlanes at{st, pixels};
+    const size_t p = i;
+    const float *g = guides + p * 8;
+    double e, m;
+    if (e_in) { e = e_in[p]; m = m_in[p]; }
+    else {
+        double fa[6], fb[6], a0[3], b0[3], va0[3], vb0[3];
+#pragma unroll
+        for (int c = 0; c < 6; c++) { fa[c] = at(0, p, c); fb[c] = at(1, p, c); }
+#pragma unroll
+        for (uint32_t c = 0; c < 3; c++) {
+            a0[c] = raw[select_plane_at<6>(c, p, pixels)];
+            b0[c] = raw[select_plane_at<6>(3 + c, p, pixels)];
+            if (l == 0u) {
+                va0[c] = fa[3 + c]; vb0[c] = fb[3 + c];
+                var0[select_plane_at<6>(c, p, pixels)] = va0[c];
+                var0[select_plane_at<6>(3 + c, p, pixels)] = vb0[c];
+            } else {
+                va0[c] = var0[select_plane_at<6>(c, p, pixels)];
+                vb0[c] = var0[select_plane_at<6>(3 + c, p, pixels)];
+            }
+        }
+        e = select_error(fa, fb, a0, b0);
+        m = select_noise_m(fa, fb, a0, b0, va0, vb0, g, demodulate);
+    }
+    if (e_out) { e_out[p] = e; m_out[p] = m; return; }
+    const double va[3] = {at(0, p, 3), at(0, p, 4), at(0, p, 5)}, vb[3] = {at(1, p, 3), at(1, p, 4), at(1, p, 5)};
+    const double fw[6] = {at(2, p, 0), at(2, p, 1), at(2, p, 2), at(2, p, 3), at(2, p, 4), at(2, p, 5)};
+    const double mse = select_noise_mse(m, va, vb, fw + 3, g, demodulate);
+    select_noise_pick(e, mse, l, fw, g, demodulate, best + p, L + p, S + p * 3, M + p);
+}
+// e_S of every pixel from M and the run's S into `img`, and the summary out[block] = {sum of e_S, max of e_S, pixels with e_S > threshold}, reduced in
+// robust_noise_kernel's fixed order — a fixed grid, every thread its strided pixels in order, lanes and waves in order, the host adds the blocks'
+// partial sums in index order: two calls return identical bits.
+constexpr unsigned SELECT_NOISE_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void select_noise_error_kernel(const double *__restrict__ M, const float *__restrict__ S, size_t pixels, double floor, double threshold,
+                                                                 double *__restrict__ img, double *__restrict__ out) {
+    double sum = 0.0, mx = 0.0, above = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < pixels; i += (size_t)gridDim.x * 256u) {
+        const double e = select_noise_error(M[i], S + i * 3, floor);
+        img[i] = e;
+        sum += e;
+        mx = e > mx ? e : mx;
+        above += e > threshold ? 1.0 : 0.0;
+    }
+    __shared__ double part[4][3];
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_down(sum, off);
+        const double o = __shfl_down(mx, off);
+        mx = o > mx ? o : mx;
+        above += __shfl_down(above, off);
+    }
+    if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][0] = sum; part[threadIdx.x >> 6][1] = mx; part[threadIdx.x >> 6][2] = above; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *o = out + (size_t)blockIdx.x * 3;
+        o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
+        o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
+        o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
+    }
 }

@@ -21,7 +21,9 @@
 // --robust-restore / --restore-levels N (with --robust: the FINAL image is the robust radiance — with --robust-denoise the denoised one — plus the
 // trimmed buckets' excess spread along the guide planes, hr_robust_restore + hr_resolve_restored),
 // --denoise-auto K / --select-smooth N / --level-image FILE (options "moments" and "robust_buckets": the FINAL image is --denoise's filter with the
-// level picked per pixel from the held-out halves of the K sample buckets, hr_denoise_select + hr_resolve_selected).
+// level picked per pixel from the held-out halves of the K sample buckets, hr_denoise_select + hr_resolve_selected),
+// --auto-noise (with --denoise-auto: --noise-target, --adaptive and --noise-image judge the image --denoise-auto shows by its estimated error,
+// hr_selected_noise_estimate / hr_select_tiles_selected / hr_read_selected_noise_image).
 // The file is in main's order: Options and parse_options (everything that can be refused before a device is opened), then Run, whose members
 // are main's steps.  The checkpoint's format is host/checkpoint.h's; what a render demands of a file is said in Run::resume.
 #include <algorithm>
@@ -149,6 +151,10 @@ static void usage(const char *prog) {
            "                        --robust, --denoise or --debug.\n"
            "        --select-smooth N\n"
            "                        smoothing passes over the per-level error planes before the pick, 0 .. 3 (default 2).  Needs --denoise-auto.\n"
+           "        --auto-noise    judge the noise of the image --denoise-auto shows, not of the plain mean: --noise-target asks\n"
+           "                        hr_selected_noise_estimate, --adaptive asks hr_select_tiles_selected and --noise-image maps min(1, e_S / E), e_S the\n"
+           "                        estimated relative error of the selected radiance (a propagated variance plus a held-out bias), with this run's\n"
+           "                        --denoise-levels and --select-smooth.  Needs --denoise-auto; one device; not with --robust-noise or --resume.\n"
            "        --level-image FILE.png\n"
            "                        write an 8-bit grey map of level / --denoise-levels, the level each pixel took (needs --denoise-auto)\n",
            prog);
@@ -182,6 +188,7 @@ struct Options {
     long long restore_levels = -1;   // -1: the library's default
     long long auto_k = 0;            // --denoise-auto K: options "moments" and "robust_buckets", the final image is hr_denoise_select's (0: off)
     long long select_smooth = -1;    // -1: the library's default
+    bool auto_noise = false;         // --auto-noise: the noise questions are asked of the image --denoise-auto shows (e_S), not of the moments
     std::string level_png;
     // what the flags add up to:
     bool counts = false, moments = false;   // hr_set_option "sample_counts", "moments"
@@ -293,6 +300,7 @@ static int parse_options(int argc, char **argv, Options &o) {
         } else if (a == "--select-smooth") {
             if (!whole("--select-smooth", val("select-smooth"), 0, 3, 1, "a whole number in 0 .. 3", &o.select_smooth)) return 1;
         } else if (a == "--level-image") o.level_png = val("level-image");
+        else if (a == "--auto-noise") o.auto_noise = true;
         else if (a == "--restore-levels") {
             if (!whole("--restore-levels", val("restore-levels"), 0, 5, 1, "a whole number in 0 .. 5", &o.restore_levels)) return 1;
         }
@@ -308,6 +316,12 @@ static int parse_options(int argc, char **argv, Options &o) {
         if (!one_device(o, "--adaptive / --sample-image render on one device: the library can shard an adaptive render (masks and additive counts), this program's device loop does not.")) return 1;
         if (o.have_adaptive && o.have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
         if (o.debug) { fprintf(stderr, "--adaptive / --sample-image cannot be combined with --debug (the debug renderer has no samplings to count).\n"); return 1; }
+    }
+    if (o.auto_noise) {   // (before --denoise-auto's own: every refusal of this flag names it)
+        if (!o.auto_k) { fprintf(stderr, "--auto-noise needs --denoise-auto (it judges the noise of the image --denoise-auto shows).\n"); return 1; }
+        if (o.robust_noise) { fprintf(stderr, "--auto-noise cannot be combined with --robust-noise (two images to judge the noise of).\n"); return 1; }
+        if (!o.ckpt_in.empty()) { fprintf(stderr, "--auto-noise cannot be combined with --resume (the checkpoint does not carry the sample buckets --denoise-auto keeps).\n"); return 1; }
+        if (!one_device(o, "--auto-noise renders on one device, as --denoise-auto does: the library estimates from one context's moments and sample buckets.")) return 1;
     }
     if (o.auto_k) {   // before everything else about these flags: nothing of --denoise-auto is half accepted
         if (o.robust_k) { fprintf(stderr, "--denoise-auto cannot be combined with --robust (it filters the plain mean, and keeps sample buckets of its own: two final images).\n"); return 1; }
@@ -404,6 +418,7 @@ struct Run {
     // what the steps share
     int combine();
     int resolve(uint32_t s, uint8_t *out);
+    int select_params(hr_denoise_params *dp, hr_select_params *sp);
     int noise_query(hr_noise *est, double *img, std::vector<double> *tot_out, uint64_t *n_out);
     int noise_check_now();
     int save(uint32_t s);
@@ -506,9 +521,7 @@ int Run::resolve(uint32_t s, uint8_t *out) {
     if (o.auto_k && final_image) {   // (one device, neither --robust nor --denoise: checked with the flags)
         hr_denoise_params dp;
         hr_select_params sp;
-        if (hr_denoise_default_params(&dp) != 0 || hr_select_default_params(&sp) != 0) return 1;
-        if (o.denoise_levels >= 0) dp.levels = (uint32_t)o.denoise_levels;
-        if (o.select_smooth >= 0) sp.smooth = (uint32_t)o.select_smooth;
+        if (select_params(&dp, &sp)) return 1;
         const int rc = hr_denoise_select(ctx, &dp, &sp);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings, or buckets that do not cover the moments' samplings)
         if (rc == 0) { have_guides = true; have_levels = true; select_levels = dp.levels; return hr_resolve_selected(ctx, out); }
         if (rc != HR_ERR_INVALID) return rc;
@@ -530,11 +543,19 @@ int Run::resolve(uint32_t s, uint8_t *out) {
     return hr_write_accumulator(ctx, part.data()) != 0 ? 1 : rc;
 }
 
+// --denoise-auto's parameters as the flags give them: hr_denoise_select's and, with --auto-noise, the estimate's of the image it will make
+int Run::select_params(hr_denoise_params *dp, hr_select_params *sp) {
+    if (hr_denoise_default_params(dp) != 0 || hr_select_default_params(sp) != 0) return 1;
+    if (o.denoise_levels >= 0) dp->levels = (uint32_t)o.denoise_levels;
+    if (o.select_smooth >= 0) sp->smooth = (uint32_t)o.select_smooth;
+    return 0;
+}
 // The noise estimate of everything rendered so far.  Several devices: every device holds the moments of its own samplings; they are
 // additive, so the host adds them in rank order (as sum_acc does for accumulators without RCCL), device 0 estimates the total and gets
 // its own moments back.  tot_out / n_out: the summed moments and their count as well (for the checkpoint).
 // Returns 0, 1 = error, 2 = fewer than two samplings behind the moments (no variance yet).
 // --robust-noise (one device): the same questions asked of the sample buckets, e_R in place of e; 2 = a pixel with fewer than K samplings.
+// --auto-noise (one device): asked of the image --denoise-auto shows, e_S in place of e; 2 = a pixel with fewer than 2 samplings.
 int Run::noise_query(hr_noise *est, double *img, std::vector<double> *tot_out, uint64_t *n_out) {
     uint64_t n_own = 0, n_tot = 0;
     const size_t len = (size_t)o.out_w * o.out_h * 6;
@@ -556,8 +577,17 @@ int Run::noise_query(hr_noise *est, double *img, std::vector<double> *tot_out, u
     }
     memset(est, 0, sizeof *est);
     // (HR_ERR_INVALID: n < 2, with --robust-noise n < K — floor and threshold were checked with the flags)
-    int rc = o.robust_noise ? hr_robust_noise_estimate(ctx, o.noise_floor, o.noise_e, est) : hr_noise_estimate(ctx, o.noise_floor, o.noise_e, est);
-    if (rc == 0 && img) rc = o.robust_noise ? hr_read_robust_noise_image(ctx, o.noise_floor, img) : hr_read_noise_image(ctx, o.noise_floor, img);
+    int rc;
+    if (o.auto_noise) {
+        hr_denoise_params dp;
+        hr_select_params sp;
+        if (select_params(&dp, &sp)) return 1;
+        rc = hr_selected_noise_estimate(ctx, &dp, &sp, o.noise_floor, o.noise_e, est);
+        if (rc == 0 && img) rc = hr_read_selected_noise_image(ctx, &dp, &sp, o.noise_floor, img);
+    } else {
+        rc = o.robust_noise ? hr_robust_noise_estimate(ctx, o.noise_floor, o.noise_e, est) : hr_noise_estimate(ctx, o.noise_floor, o.noise_e, est);
+        if (rc == 0 && img) rc = o.robust_noise ? hr_read_robust_noise_image(ctx, o.noise_floor, img) : hr_read_noise_image(ctx, o.noise_floor, img);
+    }
     if (ndev > 1 && hr_write_moments(ctx, mom_own.data(), n_own) != 0) return 1;
     if (tot_out) *tot_out = mom_tot;
     if (n_out) *n_out = n_tot;
@@ -785,7 +815,13 @@ int Run::render() {
         if (q.empty() && have_adaptive && next_s <= sampling && (uint64_t)next_s > check_at) {   // the tiles are chosen again, and nothing is in flight
             uint32_t active = all_tiles;
             // (HR_ERR_INVALID: a pixel with fewer than 2 samplings, with --robust-noise fewer than K — no estimate yet, go on as before)
-            const int rc = o.robust_noise ? hr_select_tiles_robust(ctx, noise_floor, adaptive_e, &active) : hr_select_tiles(ctx, noise_floor, adaptive_e, &active);
+            int rc;
+            if (o.auto_noise) {   // (--auto-noise: e_S of the image --denoise-auto will show)
+                hr_denoise_params dp;
+                hr_select_params sp;
+                if (select_params(&dp, &sp)) return 1;
+                rc = hr_select_tiles_selected(ctx, &dp, &sp, noise_floor, adaptive_e, &active);
+            } else rc = o.robust_noise ? hr_select_tiles_robust(ctx, noise_floor, adaptive_e, &active) : hr_select_tiles(ctx, noise_floor, adaptive_e, &active);
             if (rc != 0 && rc != HR_ERR_INVALID) { fprintf(stderr, "hr_select_tiles: %s\n", hr_last_error()); return 1; }
             if (rc == 0) {
                 printf("adaptive: samplings=%u active=%u tiles=%u\n", next_s - 1, active, all_tiles);

@@ -236,6 +236,11 @@ def hip_lib():
         L.hr_read_selected.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_read_selected_levels.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_resolve_selected.argtypes = [C.c_void_p, C.c_void_p]
+        _sel = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(SelectParams)]
+        L.hr_selected_noise_estimate.argtypes = _sel + [C.c_double, C.c_double, C.POINTER(Noise)]
+        L.hr_read_selected_noise_image.argtypes = _sel + [C.c_double, C.c_void_p]
+        L.hr_read_selected_mse.argtypes = _sel + [C.c_void_p]
+        L.hr_select_tiles_selected.argtypes = _sel + [C.c_double, C.c_double, C.POINTER(C.c_uint32)]
         L.hr_fold_statistics.argtypes = [C.c_void_p]
         L.hr_fold_statistics_group.argtypes = [C.POINTER(C.c_void_p), C.c_int]
         _hip = L
@@ -715,6 +720,43 @@ class Renderer:
         if smooth is not None:
             s.smooth = smooth
         self._check(self.L.hr_denoise_select(self._h, C.byref(p), C.byref(s)))
+
+    # ---- the error estimate of the selected radiance, and the selection of tiles by it (include/hanamaru_hip.h)
+    @staticmethod
+    def _select_args(who, smooth, params):
+        """(DenoiseParams, SelectParams) by reference from denoise_select()'s keywords"""
+        p = denoise_default_params()
+        for k, v in params.items():
+            if k not in dict(DenoiseParams._fields_):
+                raise TypeError("%s() has no parameter %r" % (who, k))
+            setattr(p, k, v)
+        s = select_default_params()
+        if smooth is not None:
+            s.smooth = smooth
+        return C.byref(p), C.byref(s)
+
+    def selected_noise_estimate(self, floor=0.01, threshold=0.05, smooth=None, **params):
+        """hr_selected_noise_estimate: {samplings, pixels, pixels_above, mean_error, max_error} of e_S, the estimated relative error of the image
+        denoise_select(smooth, **params) makes."""
+        n = Noise()
+        self._check(self.L.hr_selected_noise_estimate(self._h, *self._select_args("selected_noise_estimate", smooth, params), float(floor), float(threshold), C.byref(n)))
+        return {k: getattr(n, k) for k, _ in n._fields_}
+
+    def selected_noise_image(self, floor=0.01, smooth=None, **params):
+        """hr_read_selected_noise_image: e_S of every pixel, (h, w) float64."""
+        p, s = self._select_args("selected_noise_image", smooth, params)
+        return self._read_plane(self.L.hr_read_selected_noise_image, "noise", p, s, float(floor))
+
+    def selected_mse(self, smooth=None, **params):
+        """hr_read_selected_mse: M of every pixel, (h, w) float64 — the estimated mean squared error of the selected radiance."""
+        p, s = self._select_args("selected_mse", smooth, params)
+        return self._read_plane(self.L.hr_read_selected_mse, "noise", p, s)
+
+    def select_tiles_selected(self, floor=0.01, threshold=0.05, smooth=None, **params):
+        """hr_select_tiles_selected: select_tiles() with e_S in place of e; returns the active tiles left."""
+        n = C.c_uint32()
+        self._check(self.L.hr_select_tiles_selected(self._h, *self._select_args("select_tiles_selected", smooth, params), float(floor), float(threshold), C.byref(n)))
+        return int(n.value)
 
     def read_selected(self):
         """hr_read_selected: (h, w, 3) float32 radiance."""

@@ -561,6 +561,36 @@ int hr_read_selected(hr_ctx *ctx, float *host /* w*h*3 radiance */);
 int hr_read_selected_levels(hr_ctx *ctx, uint8_t *host /* w*h: the level each pixel took */);
 int hr_resolve_selected(hr_ctx *ctx, uint8_t *host_rgb8);  /* renderer.rs:64-90 on S with scale 1.0f */
 
+/* ---- the error estimate of S, its stop rule and its tile selection (csrc/select_noise_core.h is the definition) -----------------
+ * hr_noise_estimate judges the raw mean and hr_robust_noise_estimate judges R; these four judge S, the image hr_denoise_select makes with the
+ * parameters handed in (NULL = defaults).  Per level l and pixel, from the states of hr_denoise_select above (k_c = (A_c + eps)^2 with
+ * demodulate && levels, else no factor at all):
+ *         m_l = sum_c k_c (((F_A,l,c - B0_c)^2 + (F_B,l,c - A0_c)^2) - (V_A,0,c + V_B,0,c)) / 2      the held-out MSE of a half filter: half A is
+ *               independent of B0, so E[(F_A,l - B0)^2] = MSE(F_A,l) + Var(B0), and Var(B0) is the level-0 variance that is subtracted
+ *         m^_l = m_l through the same `smooth` passes as e_l;   vh = sum_c k_c (V_A,l,c + V_B,l,c) / 2;   vw = sum_c k_c V_W,l,c
+ *         mse_l = vw + max(0, m^_l - vh)        the whole-buffer filter's propagated variance plus the half filters' squared bias
+ *         M = mse_L at the level L the pick takes;   e_S = sqrt(M) / (S_r + S_g + S_b + 3 floor), 0 where that denominator is not positive
+ *     M is f64, + - x / and comparisons only: the device, the header under a host compiler and a numpy restatement agree bit for bit.
+ *   - hr_selected_noise_estimate: hr_noise of e_S (samplings: the count behind the moments), reduced on the device in a fixed order — two calls
+ *     return identical bits.  hr_read_selected_noise_image: e_S of every pixel.  hr_read_selected_mse: M of every pixel (radiance squared).
+ *   - hr_select_tiles_selected (needs "sample_counts" as well) is hr_select_tiles with e_S in place of e: a tile stays active iff e_S > threshold
+ *     for one of its in-region pixels, e_S exactly the value hr_read_selected_noise_image returns; ANDed with the mask in force, compacted alike.
+ *   - Each call runs hr_denoise_select's pipeline in memory of its own, S and L included, and leaves every kept image and its validity exactly
+ *     as it was: S, L, D, R, R'.  The guide planes are the exception: they are rendered when there are none, as hr_denoise_select does.
+ *   - HR_ERR_INVALID, decided before anything is touched: whatever hr_denoise_select refuses, in its order; floor <= 0 or not finite;
+ *     threshold < 0; hr_select_tiles_selected without "sample_counts".
+ *   - All four work on the region, synchronise, and book their time to hr_stats.post_kernel_ms.
+ *   - Memory for the call: about 453 bytes per pixel (939 MB at 1920x1080) — hr_denoise_select's 360, the two level-0 variances (48), two planes
+ *     of m (16), M (8), e_S (8) and the call's own S and L (13); nothing stays.  HR_ERR_DEVICE "out of memory" when the device has no room; nothing
+ *     is touched then.
+ *   - What it is not: the bias is that of filters on n / 2 samplings, whose colour kernel is wider — the estimate is conservative; the colour
+ *     weights of A and B use V_W of all samplings; at L = 0 the clamp lets the positive half of the noise of m^_0 - vh_0 through; it is blind to
+ *     what both halves share (guide errors, fireflies that have not happened yet). */
+int hr_selected_noise_estimate(hr_ctx *ctx, const hr_denoise_params *p, const hr_select_params *s, double floor, double threshold, hr_noise *out);
+int hr_read_selected_noise_image(hr_ctx *ctx, const hr_denoise_params *p, const hr_select_params *s, double floor, double *host /* w*h: e_S */);
+int hr_read_selected_mse(hr_ctx *ctx, const hr_denoise_params *p, const hr_select_params *s, double *host /* w*h: M */);
+int hr_select_tiles_selected(hr_ctx *ctx, const hr_denoise_params *p, const hr_select_params *s, double floor, double threshold, uint32_t *active /* may be NULL */);
+
 /* ---- sharded statistics: buckets by sampling, and the fold into rank 0 ----------------------------------------------------------
  * Contexts that shard the samplings (hr_render's stride) each hold a share of every additive plane.  hr_fold_statistics moves the shares to
  * rank 0 of the communicator, so that ONE context answers every question with the functions above, unchanged: hr_noise_estimate,

@@ -126,6 +126,12 @@ extern "C" {
     pub fn hr_read_selected(ctx: *mut HrCtx, host: *mut f32 /* w*h*3 */) -> c_int;
     pub fn hr_read_selected_levels(ctx: *mut HrCtx, host: *mut u8 /* w*h */) -> c_int;
     pub fn hr_resolve_selected(ctx: *mut HrCtx, host_rgb8: *mut u8) -> c_int;
+    // the error estimate e_S of the image hr_denoise_select makes with (p, s) — a propagated variance plus a held-out bias — and the selection of
+    // tiles by it; every kept image stays as it was (hr_select_tiles_selected also needs option "sample_counts")
+    pub fn hr_selected_noise_estimate(ctx: *mut HrCtx, p: *const HrDenoiseParams, s: *const HrSelectParams, floor: f64, threshold: f64, out: *mut HrNoise) -> c_int;
+    pub fn hr_read_selected_noise_image(ctx: *mut HrCtx, p: *const HrDenoiseParams, s: *const HrSelectParams, floor: f64, host: *mut f64 /* w*h */) -> c_int;
+    pub fn hr_read_selected_mse(ctx: *mut HrCtx, p: *const HrDenoiseParams, s: *const HrSelectParams, host: *mut f64 /* w*h */) -> c_int;
+    pub fn hr_select_tiles_selected(ctx: *mut HrCtx, p: *const HrDenoiseParams, s: *const HrSelectParams, floor: f64, threshold: f64, active: *mut u32) -> c_int;
     // every additive plane (accumulator, moments, counts, buckets filled under option "bucket_by_sampling" 1) moves to rank 0, which then answers
     pub fn hr_fold_statistics(ctx: *mut HrCtx) -> c_int;
     pub fn hr_fold_statistics_group(ctxs: *mut *mut HrCtx, n: c_int) -> c_int;
