@@ -2038,6 +2038,32 @@ int hr_render_guides(hr_ctx *c) {
     image_made(c, GUIDE_IMAGE);
     return HR_OK;
 }
+// hr_render_guides with the planes averaged over `lens_points` (4 or 16) points of the thin lens per sub-sample: guide_lens_kernel, one launch, the
+// same contract and accounting.  A camera without an aperture has one lens point: the call is hr_render_guides then, to the bit.  What is refused is
+// refused before anything is touched: the planes and what was filtered with them stay.
+int hr_render_guides_lens(hr_ctx *c, uint32_t lens_points) {
+    if (!c) return fail(HR_ERR_INVALID, "hr_render_guides_lens: null ctx");
+    if (!guide_lens_count_ok(lens_points)) return fail(HR_ERR_INVALID, "hr_render_guides_lens: lens_points must be 4 or 16");
+    int rc;
+    if ((rc = debug_refusal(c, "hr_render_guides_lens", A_SCENE)) || (rc = debug_refusal(c, "hr_render_guides_lens", A_TARGET))) return rc;
+    if (c->dsc.cam.lens_radius == 0.0f) return hr_render_guides(c);
+    HIP_TRY(hipSetDevice(c->device));
+    const GuideLensFn fn = select_guide_lens_kernel(c->dsc.qnodes != nullptr);
+    if (!fn) return fail(HR_ERR_UNSUPPORTED, "hr_render_guides_lens: no kernel instantiation for this node format (kernel_variants.h)");
+    changed(c, SRC_GUIDES);
+    if (!c->guides && (rc = plane_alloc(c, GUIDES))) return rc;
+    if ((rc = launch_tile_pass(c, fn, c->guide_bounces, lens_points, c->guides))) return rc;
+    image_made(c, GUIDE_IMAGE);
+    return HR_OK;
+}
+// the table of guide_lens_point (pt_core.h): uv = {u0, v0, u1, v1, ..}; needs no device
+int hr_guide_lens_points(int lens_shape, uint32_t lens_points, float *uv) {
+    if (!uv) return fail(HR_ERR_INVALID, "hr_guide_lens_points: null argument");
+    if (lens_shape != 0 && lens_shape != 1) return fail(HR_ERR_INVALID, "hr_guide_lens_points: lens_shape must be 0 (square) or 1 (circle)");
+    if (!guide_lens_count_ok(lens_points)) return fail(HR_ERR_INVALID, "hr_guide_lens_points: lens_points must be 4 or 16");
+    for (uint32_t i = 0; i < lens_points; i++) guide_lens_point(lens_shape, lens_points, i, uv[2 * i], uv[2 * i + 1]);
+    return HR_OK;
+}
 int hr_read_guides(hr_ctx *c, float *host) {
     int rc = image_ready(c, GUIDE_IMAGE, "hr_read_guides", host);
     return rc ? rc : plane_read(c, GUIDES, c->guides, host);

@@ -110,6 +110,13 @@ static const GuideChainVariant GUIDE_CHAIN_VARIANTS[] = {HR_VARIANT(guide_chain_
 static GuideChainFn select_guide_chain_kernel(bool qn) {
     return fn_of(find_row(GUIDE_CHAIN_VARIANTS, [&](const GuideChainVariant &r) { return r.qn == qn; }));
 }
+// ---- guide_lens_kernel<QN> (trace_kernel.h): the chain averaged over the lens points of hr_render_guides_lens, one row per node format ----
+typedef void (*GuideLensFn)(Scene, RenderParams, uint32_t, uint32_t, float *);
+struct GuideLensVariant { bool qn; GuideLensFn fn; };
+static const GuideLensVariant GUIDE_LENS_VARIANTS[] = {HR_VARIANT(guide_lens_kernel, true), HR_VARIANT(guide_lens_kernel, false)};
+static GuideLensFn select_guide_lens_kernel(bool qn) {
+    return fn_of(find_row(GUIDE_LENS_VARIANTS, [&](const GuideLensVariant &r) { return r.qn == qn; }));
+}
 typedef void (*TraceDebugFn)(Scene, RenderParams, uint32_t, const float *, const float *, float *, int32_t *, Counters *);
 struct TraceDebugVariant { bool qn, cnt; TraceDebugFn fn; };
 static const TraceDebugVariant TRACE_DEBUG_VARIANTS[] = {HR_VARIANT(trace_debug_kernel, true, false), HR_VARIANT(trace_debug_kernel, false, false),

@@ -963,6 +963,40 @@ HD void debug_camera_ray(const Scene &sc, const RenderParams &rp, uint32_t px, u
     const CameraF &c = sc.cam;
     ray_set(ray, v3(c.eye), normalize(ncx * v3(c.phr) + ncy * v3(c.phu) + c.focus_distance * v3(c.forward)));
 }
+// The lens points of the lens-sampled guide planes (hr_render_guides_lens; guide_lens_kernel in trace_kernel.h): a fixed table per
+// lens shape (0 Square, 1 Circle: camera.rs:31-36) and L in {4, 16}, in sample_on_lens' [-1, 1]^2 convention (camera.rs:66-81), in 64ths — every
+// coordinate is a multiple of 1/64, point i + L/2 is the mirror image (-u, -v) of point i, so the centroid is exactly 0, and every point is
+// strictly inside the lens.  THE ORDER IS PART OF THE DEFINITION (the planes are an fp32 sum over l = 0 .. L-1):
+//   L = 4, both shapes:  (1/2, 1/2), (-1/2, 1/2), then their mirror images
+//   Circle, L = 16:      i = 0, 1: (1/4, 1/4), (-1/4, 1/4); i = 2 .. 7: the ring of radius ~0.79 counter-clockwise from 0 degrees in steps of 30,
+//                        (51, 0), (44, 25), (25, 44), (0, 51), (-25, 44), (-44, 25) / 64; i = 8 .. 15: the mirror images of 0 .. 7
+//   Square, L = 16:      the cell centres {+-1/4, +-3/4}^2: i = 0 .. 7 the upper half, row v = 3/4 then v = 1/4, u from 3/4 down to -3/4;
+//                        i = 8 .. 15: the mirror images of 0 .. 7
+static constexpr int8_t GUIDE_LENS_4[2][2] = {{32, 32}, {-32, 32}};
+static constexpr int8_t GUIDE_LENS_CIRCLE_16[8][2] = {{16, 16}, {-16, 16}, {51, 0}, {44, 25}, {25, 44}, {0, 51}, {-25, 44}, {-44, 25}};
+static constexpr int8_t GUIDE_LENS_SQUARE_16[8][2] = {{48, 48}, {16, 48}, {-16, 48}, {-48, 48}, {48, 16}, {16, 16}, {-16, 16}, {-48, 16}};
+HD bool guide_lens_count_ok(uint32_t L) { return L == 4u || L == 16u; }
+// point i of L (i < L, guide_lens_count_ok(L)); any lens_shape but 0 is the circle, as in lens_accept
+HD void guide_lens_point(int lens_shape, uint32_t L, uint32_t i, float &u, float &v) {
+    const uint32_t half = L >> 1, j = i < half ? i : i - half;
+    const int8_t *p = L == 4u ? GUIDE_LENS_4[j] : lens_shape == 0 ? GUIDE_LENS_SQUARE_16[j] : GUIDE_LENS_CIRCLE_16[j];
+    const float s = i < half ? 1.0f / 64.0f : -1.0f / 64.0f;
+    u = (float)p[0] * s; v = (float)p[1] * s;
+}
+// ray_with_dof (camera.rs:83-96) through the lens point (u, v) in fp32, no RNG: debug_camera_ray's normalised coordinates, the origin moved to
+// eye + lens_pos and the direction still through the pixel's point of the focus plane.  With lens_radius == 0 or u = v = 0 it is the pinhole ray.
+HD void guide_lens_ray(const Scene &sc, const RenderParams &rp, uint32_t px, uint32_t py, uint32_t sub, float u, float v, Ray &ray) {
+    float fx = (float)px, fy = (float)(rp.height - py);
+    float ox = (float)(sub & 1u) * 0.5f - 0.5f, oy = (float)(sub >> 1) * 0.5f - 0.5f;
+    float m = (float)(rp.width < rp.height ? rp.width : rp.height);
+    float ncx = ((fx + ox) * 2.0f - (float)rp.width) * HR_RCP(m), ncy = ((fy + oy) * 2.0f - (float)rp.height) * HR_RCP(m);
+    const CameraF &c = sc.cam;
+    // (+ zero: a lens offset of -0 becomes +0, and x - (+0) is x for every x, -0 included: the pinhole ray's bits, sign of zero and octant too;
+    //  eye - (0 - lens) is eye + lens, the same single rounding)
+    const V3f zero = v3(0.0f, 0.0f, 0.0f);
+    const V3f lens = ((u * c.lens_radius) * v3(c.right) + (v * c.lens_radius) * v3(c.up)) + zero;
+    ray_set(ray, v3(c.eye) - (zero - lens), normalize(ncx * v3(c.phr) + ncy * v3(c.phu) + c.focus_distance * v3(c.forward) - lens));
+}
 // The primary ray's result.  Returns true when the pixel still needs the shadow ray `sh` of the Shading mode (renderer.rs:121-131):
 // the pixel is then val + lit * (shadow ray hit something ? 0.5 : 1); otherwise it is val.
 HD bool debug_primary(const Scene &sc, const Ray &ray, const TraceState &ts, int mode, V3f &val, V3f &lit, Ray &sh) {

@@ -539,3 +539,52 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void guide_chain_kernel(Scene sc,
     }
     guide_store(rp, active, px, py, sub, g, guides);
 }
+
+// guide_store's sibling for the lens-sampled planes: the quad's sum of the lanes' sums over `lens` lens points, x 0.25f / lens (a power of two: exact)
+__device__ __forceinline__ void guide_store_lens(const RenderParams &rp, const bool active, uint32_t px, uint32_t py, uint32_t sub, uint32_t lens, float *g, float *__restrict__ guides) {
+    for (int k = 0; k < 8; k++) g[k] = quad_sum(g[k]);
+    if (active && sub == 0u) {
+        const float scale = 0.25f / (float)lens;
+        float *o = guides + ((size_t)py * rp_reg_w(rp) + px) * 8;
+        for (int k = 0; k < 8; k++) o[k] = g[k] * scale;
+    }
+}
+// The guide planes through the thin lens (hr_render_guides_lens): guide_chain_kernel's tile / lane mapping and chain, once per lens
+// point l = 0 .. lens - 1 of guide_lens_point (pt_core.h) along guide_lens_ray, the eight values added per lane in that order; a ray that misses adds
+// eight zeros.  `lens` is 4 or 16 (hr_api.hip checks it) and the launch's, so every lane of the wave runs the same trips.
+// Registers: the eight sums live across every walk beside the chain's eight values.  At 5 waves per SIMD (96 VGPRs, the chain kernel's occupancy) they
+// fit without scratch only when the lane's pixel does not: the wave's tile is made a scalar (readfirstlane: the wave index is uniform), and px, py, sub
+// are formed a second time before the store from the lane's rank in the wave — the same lane id, spelled so that the compiler cannot keep the first
+// result (it otherwise spills three registers around the loop).
+template <bool QN>
+__global__ __launch_bounds__(64 * TRACE_WAVES, 5) void guide_lens_kernel(Scene sc, RenderParams rp, uint32_t bounces, uint32_t lens, float *__restrict__ guides) {
+    const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * TRACE_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (tile >= rp.tiles_x * rp.tiles_y) return;
+    uint32_t px, py, sub;
+    tile_lane_pixel(rp, tile, lane, px, py, sub);
+    const bool active = rp_in_region(rp, px, py);
+    LaneCounters lc = {0, 0, 0, 0, 0, 0};
+    WaveStats ws = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}, 0};
+    Path p;
+    p.q = active ? lane : PATH_IDLE;
+    p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
+    uint32_t tick = 0;
+    float sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t l = 0; l < lens; l++) {
+        float u, v;
+        guide_lens_point(sc.cam.lens_shape, lens, l, u, v);
+        guide_lens_ray(sc, rp, rp.org_x + (active ? px : 0u), rp.org_y + (active ? py : 0u), sub, u, v, p.ray);
+        float g[8];
+        GuideChain gc;
+        guide_chain_begin(gc, g);
+        bool more = active;
+        for (uint32_t j = 0;; j++) {
+            walk_wave<false, QN>(sc, rp, p, more, T_INF, lc, ws, tick);
+            more = more && guide_chain_link(sc, p.ray, p.ts, j >= bounces, gc, g);
+            if (!wave_ballot(more)) break;
+        }
+        for (int k = 0; k < 8; k++) sum[k] += g[k];
+    }
+    tile_lane_pixel(rp, tile, lane_rank(~0ull), px, py, sub);   // (= threadIdx.x & 63: the values of above, see the head comment)
+    guide_store_lens(rp, active, px, py, sub, lens, sum, guides);
+}

@@ -12,7 +12,8 @@
 // with a relative standard error above E are rendered on; hr_select_tiles, hr_resolve_counted),
 // --denoise / --denoise-levels N / --guide-image PREFIX (option "moments": the final image is the variance-guided a-trous filter's, hr_denoise +
 // hr_resolve_denoised; the guide planes as images of their own, hr_render_guides + hr_read_guides), --guide-bounces K (option "guide_bounces":
-// the guide rays follow mirrors and glass for up to K bounces to the first rough hit; 0, the default, is the first hit),
+// the guide rays follow mirrors and glass for up to K bounces to the first rough hit; 0, the default, is the first hit), --guide-lens L
+// (hr_render_guides_lens: the guide planes averaged over 4 or 16 fixed points of the thin lens, rendered once when the devices are opened),
 // --robust K / --robust-image FILE (option "robust_buckets": every image is the firefly-robust resolve of K sample buckets per pixel, hr_robust +
 // hr_resolve_robust; the buckets ride in the checkpoint behind the other trailers),
 // --robust-noise (with --robust: --noise-target, --adaptive and --noise-image judge the robust image by the spread of its bucket means,
@@ -118,6 +119,10 @@ static void usage(const char *prog) {
            "                        the guide planes follow mirrors and glass (Specular and Refraction surfaces) for up to K bounces, 0 .. 8, to the\n"
            "                        first rough hit: albedo is the product along the chain, the normal the last hit's, depth the path length.\n"
            "                        Default 0: the first hit.  Needs --denoise or --guide-image.\n"
+           "        --guide-lens L  average the guide planes over L = 4 or 16 fixed points of the camera's thin lens (hr_render_guides_lens), so that\n"
+           "                        they are as soft as the image where it is out of focus; about L times the pinhole pass.  A scene without an\n"
+           "                        aperture gets the pinhole planes.  Works with --guide-bounces.  Needs --denoise, --robust-denoise,\n"
+           "                        --robust-restore, --denoise-auto or --guide-image.\n"
            "        --robust K      keep K sample buckets per pixel (K odd, 3 .. 15; 3 K doubles per pixel) and write every image, progress and final,\n"
            "                        through the firefly-robust resolve (hr_robust + hr_resolve_robust: an adaptive median of the K bucket means, which\n"
            "                        drops the buckets a few very bright paths landed in; biased dark where it trims).  Works with --region,\n"
@@ -180,6 +185,7 @@ struct Options {
     long long denoise_levels = -1;   // -1: the library's default
     std::string guide_prefix;
     long long guide_bounces = -1;    // -1: not given (the library's default, 0)
+    long long guide_lens = 0;        // --guide-lens L: 4 or 16 lens points behind every guide value (0: not given, pinhole planes)
     long long robust_k = 0;          // --robust K: option "robust_buckets" (0: off)
     std::string robust_png;
     bool robust_noise = false;       // --robust-noise: the noise questions are asked of the buckets (e_R), not of the moments
@@ -289,6 +295,8 @@ static int parse_options(int argc, char **argv, Options &o) {
         } else if (a == "--guide-image") o.guide_prefix = val("guide-image");
         else if (a == "--guide-bounces") {
             if (!whole("--guide-bounces", val("guide-bounces"), 0, 8, 1, "a whole number in 0 .. 8", &o.guide_bounces)) return 1;
+        } else if (a == "--guide-lens") {
+            if (!whole("--guide-lens", val("guide-lens"), 4, 16, 12, "4 or 16", &o.guide_lens)) return 1;
         } else if (a == "--robust") {
             if (!whole("--robust", val("robust"), 3, 15, 2, "an odd number of buckets in 3 .. 15", &o.robust_k)) return 1;
         } else if (a == "--robust-image") o.robust_png = val("robust-image");
@@ -335,6 +343,7 @@ static int parse_options(int argc, char **argv, Options &o) {
     if (o.robust_restore && !o.robust_k) { fprintf(stderr, "--robust-restore needs --robust (it gives back the energy the robust resolve drops).\n"); return 1; }
     if (o.restore_levels >= 0 && !o.robust_restore) { fprintf(stderr, "--restore-levels needs --robust-restore.\n"); return 1; }
     if (o.denoise_levels >= 0 && !o.denoise && !o.robust_denoise && !o.auto_k) { fprintf(stderr, "--denoise-levels needs --denoise.\n"); return 1; }
+    if (o.guide_lens && !o.denoise && !o.robust_denoise && !o.robust_restore && !o.auto_k && o.guide_prefix.empty()) { fprintf(stderr, "--guide-lens needs --denoise, --robust-denoise, --robust-restore, --denoise-auto or --guide-image.\n"); return 1; }
     if (o.guide_bounces >= 0 && !o.denoise && !o.robust_denoise && !o.robust_restore && !o.auto_k && o.guide_prefix.empty()) { fprintf(stderr, "--guide-bounces needs --denoise or --guide-image.\n"); return 1; }
     if (o.denoise || !o.guide_prefix.empty()) {
         if (!one_device(o, "--denoise / --guide-image render on one device: the library denoises one context's accumulator, moments and counts (a sharded host sums them into one), this program's device loop does not.")) return 1;
@@ -464,6 +473,9 @@ int Run::open_devices() {
         if (o.auto_k) CHECK_HR(hr_set_option(ctxs[r], "robust_buckets", (double)o.auto_k));
     }
     ctx = ctxs[0];
+    // --guide-lens: the planes are rendered here, once, where the library would otherwise render pinhole planes at the first call that needs them
+    // (one device: checked with the flags; nothing this program does afterwards drops them)
+    if (o.guide_lens) { CHECK_HR(hr_render_guides_lens(ctx, (uint32_t)o.guide_lens)); have_guides = true; }
     if (ndev > 1) tee("devices: %u.", ndev);
     tee("init scene: %.2f sec.", now_sec() - init_begin);
     // The image needs the sum of all devices' accumulators: ONE all-reduce over RCCL (hr_allreduce_accumulators — the sum lands

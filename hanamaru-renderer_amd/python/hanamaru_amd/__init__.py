@@ -211,6 +211,8 @@ def hip_lib():
         L.hr_select_tiles.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_uint32)]
         L.hr_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
         L.hr_render_guides.argtypes = [C.c_void_p]
+        L.hr_render_guides_lens.argtypes = [C.c_void_p, C.c_uint32]
+        L.hr_guide_lens_points.argtypes = [C.c_int, C.c_uint32, C.c_void_p]
         L.hr_read_guides.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_write_guides.argtypes = [C.c_void_p, C.c_void_p]
         L.hr_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)]
@@ -311,6 +313,17 @@ def fold_statistics(renderers):
 
 class HostError(RuntimeError):
     pass
+
+
+def guide_lens_points(lens_shape, lens_points):
+    """hr_guide_lens_points: the (lens_points, 2) float32 table of lens coordinates (u, v) that hr_render_guides_lens averages over, in the order
+    it sums them; lens_shape 0 Square, 1 Circle; lens_points 4 or 16 (needs no device)."""
+    L = hip_lib()
+    uv = np.zeros((max(int(lens_points), 1), 2), dtype=np.float32)
+    rc = L.hr_guide_lens_points(int(lens_shape), int(lens_points), uv.ctypes.data)
+    if rc != 0:
+        raise HipError(rc, L.hr_last_error().decode())
+    return uv
 
 
 def select_default_params():
@@ -629,6 +642,11 @@ class Renderer:
         """hr_render_guides: one pinhole pass into the guide planes (set_option("guide_bounces", K), K in 0 .. 8: through up to K mirrors and
         glass surfaces to the first rough hit; default 0, the first hit)."""
         self._check(self.L.hr_render_guides(self._h))
+
+    def render_guides_lens(self, lens_points):
+        """hr_render_guides_lens: render_guides with the planes averaged over lens_points (4 or 16) fixed points of the thin lens per sub-sample
+        (guide_lens_points has the table); a camera without an aperture gets render_guides' planes."""
+        self._check(self.L.hr_render_guides_lens(self._h, int(lens_points)))
 
     def read_guides(self):
         """hr_read_guides: (h, w, 8) float32 {albedo rgb, normal xyz, depth, coverage}."""

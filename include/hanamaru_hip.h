@@ -361,6 +361,19 @@ int hr_select_tiles(hr_ctx *ctx, double floor, double threshold, uint32_t *activ
  *     the chain, the normal the terminal hit's world normal, depth the path length summed over the segments; coverage, the 2x2 mean, the layout,
  *     the region contract, the ignored tile mask and the accounting are as above.  The definition is guide_chain_link in csrc/pt_core.h; with
  *     K = 0 it is the first hit's values bit for bit.  Setting a new value drops the guide planes (rendered or written) and invalidates D.
+ *   - hr_render_guides_lens(ctx, L), L = 4 or 16: the image is rendered through the thin lens (camera.rs:83-96) and the pinhole planes are sharper
+ *     than it where it is out of focus.  This call is hr_render_guides with each sub-sample's values averaged over L fixed points of the lens: the
+ *     ray of lens point (u, v) starts at eye + lens_radius (u right + v up) and passes through the sub-sample's point of the focus plane, in fp32
+ *     (guide_lens_ray in csrc/pt_core.h); the chain of "guide_bounces" runs along it; per sub-sample the eight values are added in fp32 over
+ *     l = 0 .. L - 1, the four sub-samples as before, and the sum x 0.25 / L is stored.  A ray that misses adds eight zeros: coverage is the
+ *     fraction of the 4 L rays that hit.  The points are a fixed table (guide_lens_point; no RNG): multiples of 1/64 in the reference's [-1, 1]^2
+ *     lens coordinates, symmetric under (u, v) -> (-u, -v), centroid exactly 0, all strictly inside the lens.  hr_guide_lens_points(lens_shape
+ *     0 Square | 1 Circle, L, uv) returns them as {u0, v0, u1, v1, ..} in the order they are summed; it needs no device.  Everything else is
+ *     hr_render_guides' contract: the whole region whatever the tile mask, a region's planes are the frame's window bit for bit, nothing but the
+ *     guide planes is touched, the time goes to debug_kernel_ms / debug_launches (one launch), the planes count as rendered planes (they replace
+ *     the old ones and invalidate D; a new "guide_bounces" value drops them; a later hr_render_guides replaces them with pinhole planes).  L other
+ *     than 4 or 16 is HR_ERR_INVALID and leaves the planes and D as they were.  A camera with lens_radius == 0 has one lens point: the call then
+ *     IS hr_render_guides (the same kernels, the same bits).  The cost is about L pinhole passes.
  *   - hr_denoise computes D, w x h x 3 floats of radiance (what accumulator x 1 / (4 n) is), from this context's OWN accumulator — never the
  *     all-reduced total: a sharded host writes the summed accumulator, moments and counts into one context, as it does for the estimate —,
  *     the moments and the guides.  The definition is csrc/denoise_core.h, to the bit (f64, + - x / max only, one IEEE operation per step, no FMA):
@@ -402,6 +415,8 @@ typedef struct hr_denoise_params {
 } hr_denoise_params;
 int hr_denoise_default_params(hr_denoise_params *out);
 int hr_render_guides(hr_ctx *ctx);                         /* one pinhole pass into the guide buffer ("guide_bounces": through mirrors and glass) */
+int hr_render_guides_lens(hr_ctx *ctx, uint32_t lens_points /* 4 | 16 */);   /* the same, averaged over fixed points of the thin lens */
+int hr_guide_lens_points(int lens_shape, uint32_t lens_points, float *uv /* 2*lens_points */);   /* the lens points' table; needs no device */
 int hr_read_guides(hr_ctx *ctx, float *host /* w*h*8 */);  /* the planes as outputs in their own right (AOVs) */
 int hr_write_guides(hr_ctx *ctx, const float *host);       /* resume, stitching, synthetic inputs */
 int hr_denoise(hr_ctx *ctx, const hr_denoise_params *p /* NULL = defaults */);

@@ -94,6 +94,8 @@ extern "C" {
     // guide planes {albedo rgb, normal xyz, depth, coverage} (w*h*8 floats) and the variance-guided a-trous denoiser (needs option "moments")
     pub fn hr_denoise_default_params(out: *mut HrDenoiseParams) -> c_int;
     pub fn hr_render_guides(ctx: *mut HrCtx) -> c_int;
+    pub fn hr_render_guides_lens(ctx: *mut HrCtx, lens_points: u32 /* 4 | 16 */) -> c_int;
+    pub fn hr_guide_lens_points(lens_shape: c_int, lens_points: u32, uv: *mut f32 /* 2*lens_points */) -> c_int;
     pub fn hr_read_guides(ctx: *mut HrCtx, host: *mut f32 /* w*h*8 */) -> c_int;
     pub fn hr_write_guides(ctx: *mut HrCtx, host: *const f32) -> c_int;
     pub fn hr_denoise(ctx: *mut HrCtx, p: *const HrDenoiseParams /* null = defaults */) -> c_int;
