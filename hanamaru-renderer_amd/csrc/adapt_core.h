@@ -40,7 +40,7 @@ HD bool adapt_pixel_above(const RenderParams &rp, uint32_t tile, uint32_t pix, c
     if (!rp_in_region(rp, px, py)) return false;
     return e_img[(size_t)py * rp_reg_w(rp) + px] > threshold;
 }
-// the rule for a whole tile (the device asks one lane per pixel and takes the ballot: select_tiles_kernel, hr_api.hip)
+// the rule for a whole tile (the device asks one lane per pixel and takes the ballot: select_tiles_kernel, post_kernels.h)
 HD bool adapt_tile_active(const RenderParams &rp, uint32_t tile, const double *moments, const uint32_t *counts, double floor, double threshold) {
     bool any = false;
     for (uint32_t pix = 0; pix < 16u; pix++) any = adapt_pixel_active(rp, tile, pix, moments, counts, floor, threshold) || any;

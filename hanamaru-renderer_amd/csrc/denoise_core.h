@@ -44,7 +44,7 @@ HR_DENOISE_HD DenoiseSigmas denoise_sigmas(double sigma_color, double sigma_norm
 }
 
 // the fp32 scale of a pixel with n samplings: hr_resolve's 1.0f / (float)(n * 4u).  The device's fp32 division is not correctly rounded, so the
-// quotient is taken in f64 and rounded once more: the same float for every n whose odd part is below 2^28 (tonemap_gamma_counted_kernel, hr_api.hip)
+// quotient is taken in f64 and rounded once more: the same float for every n whose odd part is below 2^28 (tonemap_gamma_counted_kernel, post_kernels.h)
 HR_DENOISE_HD float denoise_scale(uint32_t n) { return (float)(1.0 / (double)(float)(n * 4u)); }
 
 // variance of the pixel's mean radiance in one channel: noise_channel_se's var / n, over 16 (the radiance is the per-sampling value over 4)

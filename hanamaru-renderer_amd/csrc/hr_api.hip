@@ -9,11 +9,15 @@
 //                    and debug_render_kernel (renderer.rs:101-146)
 //   wf_kernels.h     the split pipeline (option trace_mode 1): wf_start_kernel, wf_traverse_kernel (the same traversal at <= 64 VGPRs),
 //                    wf_shade_kernel — the megakernel cut at scene.intersect, the path parked in HBM between the two
-//   post_kernels.h   tonemap_gamma_kernel, bilateral_quantise_kernel; the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
+//   post_kernels.h   tonemap_gamma_kernel, tonemap_gamma_counted_kernel, bilateral_quantise_kernel; summary_block_reduce — the estimates' one fixed-order
+//                    reduction — with noise_kernel (noise_core.h) and counts_min_kernel; select_tiles_kernel and select_tiles_image_kernel (adapt_core.h);
+//                    the denoiser: denoise_init_kernel, atrous_kernel, denoise_final_kernel (denoise_core.h);
 //                    robust_kernel, robust_denoise_init_kernel and robust_noise_kernel (robust_core.h); restore_init_kernel, spread_norm_kernel,
 //                    spread_gather_kernel and restore_final_kernel (restore_core.h); select_init_kernel, atrous3_kernel, select_pick_kernel and
 //                    select_smooth_kernel (select_core.h); select_noise_kernel and select_noise_error_kernel (select_noise_core.h)
 //   gpu_bvh.h        the device BVH builders' kernels (option bvh_builder = 1 LBVH, 2 PLOC)
+//   here             governor_kernel, add_accumulator_kernel, fold_plane_kernel (hr_fold_statistics), accumulator_sum_kernel
+// The exported functions are declared extern "C" by the two headers; their definitions here follow those declarations and so have C linkage.
 // Which instantiation of these kernels a launch runs is decided in kernel_variants.h: one table and one select_*() per family; the launch sites
 // here call the selector, create_resources walks the tables (the seed kernels' LDS attribute, the trace side's "no LDS" guard).
 // The buffers that have the render region's shape (accumulator, resolve buffers, all-reduced total, moments, noise image, counts, guides, denoised image, sample buckets, robust image and its trim plane, robust noise image and its trim plane, restored robust image, selected image and its level plane) are rows of one
@@ -90,8 +94,6 @@ struct CallScratch {
 #include "trace_kernel.h"
 #include "wf_kernels.h"
 #include "post_kernels.h"
-#include "noise_core.h"
-#include "adapt_core.h"
 #include "kernel_variants.h"
 
 // ------------------------------------------------------------------------------------------ context
@@ -606,12 +608,22 @@ static int image_ready(hr_ctx *c, ImageId id, const char *who, const void *host)
     if (!*im.plane->slot(c) || (im.second && !*im.second->slot(c)) || !image_valid(c, id)) return fail(HR_ERR_INVALID, "%s: %s", who, im.none);
     return HR_OK;
 }
+// the host copy of the image's plane (second: of its second plane) behind hr_read_*; image_resolve (behind resolve_region) is hr_resolve_*'s
+static int image_read(hr_ctx *c, ImageId id, const char *who, void *host, bool second = false) {
+    const Plane &p = second ? *IMAGES[id].second : *IMAGES[id].plane;
+    int rc = image_ready(c, id, who, host);
+    return rc ? rc : plane_read(c, p, *p.slot(c), host);
+}
+// the guide planes of a call that filters along them: the valid ones, or the ones it renders now
+static int guides_or_render(hr_ctx *c) { return image_valid(c, GUIDE_IMAGE) ? HR_OK : hr_render_guides(c); }
+// a bucket count K without a row in `kernel`'s table (`who`: the entry point)
+static int no_instantiation(const char *who, const char *kernel, uint32_t K) {
+    return fail(HR_ERR_UNSUPPORTED, "%s: no %s instantiation for %u buckets (kernel_variants.h)", who, kernel, K);
+}
 
 // ------------------------------------------------------------------------------------------ C ABI
 
 static int create_resources(hr_ctx *c);
-
-extern "C" {
 
 const char *hr_last_error(void) { return g_err.c_str(); }
 int hr_abi_version(void) { return HR_ABI_VERSION; }
@@ -1373,7 +1385,6 @@ int hr_render(hr_ctx *c, uint32_t s_begin, uint32_t s_end, uint32_t stride) {
 // One pass of a single-ray tile kernel (trace_kernel.h: the debug renderer, the guide kernels) over the region: one wave per 4x4-pixel tile, the
 // trace side's knobs (the kernels read leaf_den and node_unroll of them), timed into debug_kernel_ms / debug_launches.  `args`: what the kernel
 // takes behind (Scene, RenderParams).
-extern "C++" {   // (a template inside the C ABI's block)
 template <class Fn, class... Args>
 static int launch_tile_pass(hr_ctx *c, Fn fn, Args... args) {
     RenderParams rp{};
@@ -1386,7 +1397,6 @@ static int launch_tile_pass(hr_ctx *c, Fn fn, Args... args) {
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->debug_events, &c->debug_launches));
     return HR_OK;
 }
-}  // extern "C++"
 
 int hr_render_debug(hr_ctx *c, int mode) {
     if (!c || mode < 0 || mode > 3) return fail(HR_ERR_INVALID, "hr_render_debug: mode must be 0..3");
@@ -1588,7 +1598,6 @@ struct FoldPlane { const Plane *plane; int dtype; };
 static const FoldPlane FOLD_PLANES[] = {{&ACCUM_OWN, hrcomm::kFloat}, {&MOMENTS, hrcomm::kDouble}, {&COUNTS, hrcomm::kUint32}, {&BUCKETS, hrcomm::kDouble}};
 static void *fold_plane_ptr(hr_ctx *c, const Plane &p) { return &p == &ACCUM_OWN ? (void *)c->accum : (p.on && !(c->*p.on)) ? nullptr : *p.slot(c); }
 
-extern "C++" {   // (templates inside the C ABI's block)
 __device__ __forceinline__ void fold_add(double2 &a, const double2 &b) { a.x += b.x; a.y += b.y; }
 __device__ __forceinline__ void fold_add(float4 &a, const float4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 __device__ __forceinline__ void fold_add(uint4 &a, const uint4 &b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
@@ -1625,7 +1634,6 @@ static hipError_t fold_plane_launch(void *root, void *peer, size_t n, hipStream_
     hipLaunchKernelGGL(fold_plane_kernel<T>, dim3(grid), dim3(256), 0, st, (T *)root, (T *)peer, n, nvec);
     return hipGetLastError();
 }
-}  // extern "C++"
 
 // What a fold asks of one context, before anything is touched (`who`: the entry point).
 static int fold_refusal(hr_ctx *c, const char *who) {
@@ -1836,58 +1844,6 @@ int hr_write_moments(hr_ctx *c, const double *host, uint64_t samplings) {
     return HR_OK;
 }
 
-// e of every pixel into `img`, and its summary, reduced in a fixed order (the scheme of accumulator_sum_kernel: a fixed grid, every thread its
-// strided pixels in order, lanes and waves in order, the host adds the blocks' partial sums in index order): reproducible run to run.
-// out[block] = {sum of e, max of e, pixels with e > threshold}.
-// CNTS (option "sample_counts" on): n is the PIXEL's own count (every one >= 2: noise_run has checked), not the samplings issued.
-static const unsigned NOISE_BLOCKS = 1024;
-extern "C++" {   // (a template inside the C ABI's block)
-template <bool CNTS>
-__global__ __launch_bounds__(256) void noise_kernel(const double *__restrict__ moments, size_t pixels, uint64_t samplings, double floor, double threshold,
-                                                    double *__restrict__ img, double *__restrict__ out, const uint32_t *__restrict__ counts) {
-    double sum = 0.0, mx = 0.0, above = 0.0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
-        double m[6];
-        for (int k = 0; k < 6; k++) m[k] = moments[i * 6 + k];
-        const double e = hr::noise_pixel_error(m, CNTS ? (uint64_t)counts[i] : samplings, floor);
-        img[i] = e;
-        sum += e;
-        mx = e > mx ? e : mx;
-        above += e > threshold ? 1.0 : 0.0;
-    }
-    __shared__ double part[4][3];
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_down(sum, off);
-        const double o = __shfl_down(mx, off);
-        mx = o > mx ? o : mx;
-        above += __shfl_down(above, off);
-    }
-    if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][0] = sum; part[threadIdx.x >> 6][1] = mx; part[threadIdx.x >> 6][2] = above; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double *o = out + (size_t)blockIdx.x * 3;
-        o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
-        o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
-        o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
-    }
-}
-}  // extern "C++"
-// the smallest and the largest count of a pixel of the region (option "sample_counts") into out[0], out[1]: an estimate needs 2 samplings behind
-// EVERY pixel, and no pixel can have received more samplings than the moments have seen issued
-__global__ __launch_bounds__(256) void counts_min_kernel(const uint32_t *__restrict__ counts, size_t pixels, uint32_t *__restrict__ out) {
-    uint32_t mn = 0xffffffffu, mx = 0u;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t v = counts[i];
-        mn = v < mn ? v : mn;
-        mx = v > mx ? v : mx;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_down((int)mn, off), p = (uint32_t)__shfl_down((int)mx, off);
-        mn = o < mn ? o : mn;
-        mx = p > mx ? p : mx;
-    }
-    if ((threadIdx.x & 63u) == 0u) { atomicMin(out, mn); atomicMax(out + 1, mx); }
-}
 static int select_out_buffer(hr_ctx *c) {
     if (!c->d_select_out) HIP_TRY(hipMalloc((void **)&c->d_select_out, 3 * sizeof(uint32_t)));
     return HR_OK;
@@ -1922,37 +1878,49 @@ static int floor_and_threshold_ok(const char *who, double floor, double threshol
     if (!(threshold >= 0.0)) return fail(HR_ERR_INVALID, "%s: threshold must not be negative", who);
     return HR_OK;
 }
-// the summary of an estimate from its kernel's block summaries h[block] = {sum, max, above}, added in index order
-static void noise_summary(const std::vector<double> &h, uint64_t samplings, size_t pixels, hr_noise *est) {
-    double sum = 0.0, mx = 0.0, above = 0.0;
-    for (size_t b = 0; b < h.size() / 3; b++) { sum += h[b * 3]; mx = h[b * 3 + 1] > mx ? h[b * 3 + 1] : mx; above += h[b * 3 + 2]; }
-    est->samplings = samplings;
-    est->pixels = (uint64_t)pixels;
-    est->pixels_above = (uint64_t)above;
-    est->mean_error = sum / (double)pixels;
-    est->max_error = mx;
+// the samplings behind the moments cover a variance (`who`); needs_resolve_scale: and fit the scale the resolve of a denoised image works with
+static int moments_cover_an_estimate(const hr_ctx *c, const char *who, bool needs_resolve_scale) {
+    if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
+    if (needs_resolve_scale && c->moments_n >= (1ull << 30)) return fail(HR_ERR_INVALID, "%s: %llu samplings do not fit the resolve's 32-bit scale", who, (unsigned long long)c->moments_n);
+    return HR_OK;
 }
+// The host side of an estimate's summary (summary_block_reduce, post_kernels.h) for one call: the kernel's out[SUMMARY_BLOCKS] = {sum, max, above}
+// in the call's scratch, their copy to the host on c->stream and, once that stream is synchronised, the summary: the blocks added in index order.
+struct BlockSummaries {
+    double *dev = nullptr;
+    std::vector<double> host = std::vector<double>(SUMMARY_BLOCKS * 3);
+    hipError_t alloc(CallScratch &scratch) { return scratch.alloc((void **)&dev, host.size() * sizeof(double)); }
+    hipError_t fetch(const hr_ctx *c) { return hipMemcpyAsync(host.data(), dev, host.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream); }
+    void summary(uint64_t samplings, size_t pixels, hr_noise *est) const {
+        double sum = 0.0, mx = 0.0, above = 0.0;
+        for (size_t b = 0; b < SUMMARY_BLOCKS; b++) { sum += host[b * 3]; mx = host[b * 3 + 1] > mx ? host[b * 3 + 1] : mx; above += host[b * 3 + 2]; }
+        est->samplings = samplings;
+        est->pixels = (uint64_t)pixels;
+        est->pixels_above = (uint64_t)above;
+        est->mean_error = sum / (double)pixels;
+        est->max_error = mx;
+    }
+};
 // host_img: the image as well (or NULL); est: the summary (or NULL)
 static int noise_run(hr_ctx *c, const char *who, double floor, double threshold, double *host_img, hr_noise *est) {
     int rc = plane_ready(c, MOMENTS, who);
     if (rc) return rc;
     if ((rc = floor_and_threshold_ok(who, floor, threshold))) return rc;
-    if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
+    if ((rc = moments_cover_an_estimate(c, who, false))) return rc;
     if ((rc = hr_synchronize(c))) return rc;
     if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;
     const size_t pixels = region_pixels(c);
     if (!c->noise_img && (rc = plane_alloc(c, NOISE_IMG))) return rc;
     CallScratch scratch;
-    double *d = nullptr;
-    std::vector<double> h(NOISE_BLOCKS * 3);
-    HIP_TRY(scratch.alloc((void **)&d, h.size() * sizeof(double)));
-    if (c->counts) hipLaunchKernelGGL(noise_kernel<true>, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d, c->counts);
-    else hipLaunchKernelGGL(noise_kernel<false>, dim3(NOISE_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, d, (const uint32_t *)nullptr);
+    BlockSummaries blocks;
+    HIP_TRY(blocks.alloc(scratch));
+    if (c->counts) hipLaunchKernelGGL(noise_kernel<true>, dim3(SUMMARY_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, blocks.dev, c->counts);
+    else hipLaunchKernelGGL(noise_kernel<false>, dim3(SUMMARY_BLOCKS), dim3(256), 0, c->stream, c->moments, pixels, c->moments_n, floor, threshold, c->noise_img, blocks.dev, (const uint32_t *)nullptr);
     HIP_TRY_AS(who, hipGetLastError());
-    HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY_AS(who, blocks.fetch(c));
     if (host_img) HIP_TRY_AS(who, hipMemcpyAsync(host_img, c->noise_img, plane_bytes(c, NOISE_IMG), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
-    if (est) noise_summary(h, c->moments_n, pixels, est);
+    if (est) blocks.summary(c->moments_n, pixels, est);
     return HR_OK;
 }
 int hr_noise_estimate(hr_ctx *c, double floor, double threshold, hr_noise *out) {
@@ -1968,18 +1936,6 @@ int hr_read_noise_image(hr_ctx *c, double floor, double *host) {
 int hr_read_sample_counts(hr_ctx *c, uint32_t *host) { return option_plane_read(c, COUNTS, "hr_read_sample_counts", host); }
 int hr_write_sample_counts(hr_ctx *c, const uint32_t *host) { return option_plane_write(c, COUNTS, "hr_write_sample_counts", host); }
 
-// hr_resolve's first kernel with every pixel's own count: the scale is hr_resolve's expression 1.0f / (float)(count * 4u), which hr_resolve works
-// out on the host, i.e. correctly rounded.  The device's fp32 division is not (the Makefile trades that for speed), so the quotient is taken in
-// f64 and rounded to fp32: the same float as the host's for every count whose odd part is below 2^28 (a quotient 1 / n lies at least
-// 1 / (odd(n) 2^25) of its value away from the midpoint of two floats, and rounding twice can only differ from rounding once within 2^-53).
-// A pixel without samplings is radiance 0, whatever the accumulator holds.
-__global__ void tonemap_gamma_counted_kernel(const float *__restrict__ acc, const uint32_t *__restrict__ counts, float *__restrict__ out, uint32_t n) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t k = counts[i];
-    if (k) tonemap_gamma(acc[i * 3], acc[i * 3 + 1], acc[i * 3 + 2], (float)(1.0 / (double)(float)(k * 4u)), &out[i * 3]);
-    else tonemap_gamma(0.0f, 0.0f, 0.0f, 0.0f, &out[i * 3]);
-}
 // The resolve behind hr_resolve (every pixel scaled by 1 / (4 samplings)) and hr_resolve_counted (samplings == 0: by its own count): the first
 // kernel differs, the rest is one.  The region's accumulator is resolved as an image of its own: the bilateral filter's clamp and wrap act at
 // the region's edges.
@@ -2011,6 +1967,11 @@ int hr_resolve_counted(hr_ctx *c, uint8_t *host_rgb8) {
     if (!host_rgb8) return fail(HR_ERR_INVALID, "hr_resolve_counted: null argument");
     if (!c->accum) return fail(HR_ERR_NO_TARGET, "hr_resolve_counted: no accumulator");
     return resolve_region(c, 0, host_rgb8);
+}
+// the resolve of a derived image's (float) radiance plane behind hr_resolve_* (`who`)
+static int image_resolve(hr_ctx *c, ImageId id, const char *who, uint8_t *host_rgb8) {
+    int rc = image_ready(c, id, who, host_rgb8);
+    return rc ? rc : resolve_region(c, 0, host_rgb8, (const float *)*IMAGES[id].plane->slot(c));
 }
 
 // ---- the denoiser: guide planes, the à-trous filter and its resolve (denoise_core.h) ----
@@ -2064,10 +2025,7 @@ int hr_guide_lens_points(int lens_shape, uint32_t lens_points, float *uv) {
     for (uint32_t i = 0; i < lens_points; i++) guide_lens_point(lens_shape, lens_points, i, uv[2 * i], uv[2 * i + 1]);
     return HR_OK;
 }
-int hr_read_guides(hr_ctx *c, float *host) {
-    int rc = image_ready(c, GUIDE_IMAGE, "hr_read_guides", host);
-    return rc ? rc : plane_read(c, GUIDES, c->guides, host);
-}
+int hr_read_guides(hr_ctx *c, float *host) { return image_read(c, GUIDE_IMAGE, "hr_read_guides", host); }
 int hr_write_guides(hr_ctx *c, const float *host) {
     if (!c || !host) return fail(HR_ERR_INVALID, "hr_write_guides: null argument");
     if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_write_guides: hr_set_resolution not called");
@@ -2091,7 +2049,6 @@ static int denoise_params(const char *who, const hr_denoise_params *params, hr_d
 // The à-trous run of both denoisers (`who`), whose checks are done and whose guide planes are there: D from the {C, V} plane that `init(grid, cv,
 // demodulate)` — the caller's own launch on c->stream — fills, through p.levels levels and the final pass.  `made_of`: the source D is made of
 // besides what every D is (IMAGES).  The scratch planes go with the call.
-extern "C++" {   // (a template inside the C ABI's block)
 template <class Init>
 static int atrous_run(hr_ctx *c, const char *who, const hr_denoise_params &p, uint32_t made_of, Init init) {
     int rc;
@@ -2115,7 +2072,6 @@ static int atrous_run(hr_ctx *c, const char *who, const hr_denoise_params &p, ui
     image_made(c, D_IMAGE, made_of);
     return drain_events(c);
 }
-}  // extern "C++"
 int hr_denoise(hr_ctx *c, const hr_denoise_params *params) {
     static const char *const who = "hr_denoise";
     int rc = plane_ready(c, MOMENTS, who);
@@ -2123,25 +2079,18 @@ int hr_denoise(hr_ctx *c, const hr_denoise_params *params) {
     hr_denoise_params p;
     // what is refused is refused before anything is touched: the denoised image of an earlier call stays
     if ((rc = denoise_params(who, params, p))) return rc;
-    if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
-    if (c->moments_n >= (1ull << 30)) return fail(HR_ERR_INVALID, "%s: %llu samplings do not fit the resolve's 32-bit scale", who, (unsigned long long)c->moments_n);
+    if ((rc = moments_cover_an_estimate(c, who, true))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = hr_synchronize(c))) return rc;
     if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;
-    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;
+    if ((rc = guides_or_render(c))) return rc;
     const uint32_t pixels = (uint32_t)region_pixels(c);
     return atrous_run(c, who, p, SRC_MOMENTS, [&](dim3 flat, double *cv, int demodulate) {
         hipLaunchKernelGGL(denoise_init_kernel, flat, dim3(256), 0, c->stream, c->accum, c->moments, c->counts, (uint32_t)c->moments_n, c->guides, cv, pixels, demodulate);
     });
 }
-int hr_read_denoised(hr_ctx *c, float *host) {
-    int rc = image_ready(c, D_IMAGE, "hr_read_denoised", host);
-    return rc ? rc : plane_read(c, DENOISED, c->denoised, host);
-}
-int hr_resolve_denoised(hr_ctx *c, uint8_t *host_rgb8) {
-    int rc = image_ready(c, D_IMAGE, "hr_resolve_denoised", host_rgb8);
-    return rc ? rc : resolve_region(c, 0, host_rgb8, c->denoised);
-}
+int hr_read_denoised(hr_ctx *c, float *host) { return image_read(c, D_IMAGE, "hr_read_denoised", host); }
+int hr_resolve_denoised(hr_ctx *c, uint8_t *host_rgb8) { return image_resolve(c, D_IMAGE, "hr_resolve_denoised", host_rgb8); }
 
 // ---- option "robust_buckets": the sample buckets and the firefly-robust resolve made of them (robust_core.h) ----
 int hr_read_buckets(hr_ctx *c, double *host, uint64_t *samplings) {
@@ -2163,7 +2112,7 @@ int hr_robust(hr_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = hr_synchronize(c))) return rc;
     const RobustVariant *v = select_robust_kernel(c->robust_k);
-    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_kernel instantiation for %u buckets (kernel_variants.h)", who, c->robust_k);
+    if (!v) return no_instantiation(who, "robust_kernel", c->robust_k);
     if (!c->robust && (rc = plane_alloc(c, ROBUST))) return rc;
     if (!c->robust_trim && (rc = plane_alloc(c, ROBUST_TRIM))) return rc;
     c->made_of[R_IMAGE] = 0;   // (R alone: R' is not made of R)
@@ -2176,18 +2125,9 @@ int hr_robust(hr_ctx *c) {
     image_made(c, R_IMAGE);
     return drain_events(c);
 }
-int hr_read_robust(hr_ctx *c, float *host) {
-    int rc = image_ready(c, R_IMAGE, "hr_read_robust", host);
-    return rc ? rc : plane_read(c, ROBUST, c->robust, host);
-}
-int hr_read_robust_trim(hr_ctx *c, uint8_t *host) {
-    int rc = image_ready(c, R_IMAGE, "hr_read_robust_trim", host);
-    return rc ? rc : plane_read(c, ROBUST_TRIM, c->robust_trim, host);
-}
-int hr_resolve_robust(hr_ctx *c, uint8_t *host_rgb8) {
-    int rc = image_ready(c, R_IMAGE, "hr_resolve_robust", host_rgb8);
-    return rc ? rc : resolve_region(c, 0, host_rgb8, c->robust);
-}
+int hr_read_robust(hr_ctx *c, float *host) { return image_read(c, R_IMAGE, "hr_read_robust", host); }
+int hr_read_robust_trim(hr_ctx *c, uint8_t *host) { return image_read(c, R_IMAGE, "hr_read_robust_trim", host, true); }
+int hr_resolve_robust(hr_ctx *c, uint8_t *host_rgb8) { return image_resolve(c, R_IMAGE, "hr_resolve_robust", host_rgb8); }
 
 // the mask's host side from its flags: the count of active tiles and of their in-region pixels
 static void mask_totals(hr_ctx *c) {
@@ -2234,26 +2174,6 @@ int hr_get_tile_mask(hr_ctx *c, uint8_t *mask, uint32_t *active) {
     return HR_OK;
 }
 
-// The tile rule on the device: 16 lanes per tile (one per pixel), four tiles per wave; the ballot of a tile's lanes is its flag, ANDed with the
-// flag it had (have_prev: a mask is in force — a tile that went inactive stays inactive).  The ascending compaction of the flags into the list
-// is hipcub's DeviceSelect::Flagged over the tile indices: deterministic, two calls give identical lists.
-__device__ __forceinline__ void tile_flag_from_lanes(bool hot, uint32_t tile, uint32_t tiles, uint32_t pix, int have_prev, uint32_t *__restrict__ flags) {
-    const unsigned long long m = wave_ballot(hot);
-    const bool any = ((m >> (((threadIdx.x & 63u) >> 4) * 16u)) & 0xffffull) != 0ull;
-    if (pix == 0u && tile < tiles) flags[tile] = any && (!have_prev || flags[tile] != 0u) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void select_tiles_kernel(RenderParams rp, const double *__restrict__ moments, const uint32_t *__restrict__ counts, double floor, double threshold,
-                                                           int have_prev, uint32_t *__restrict__ flags) {
-    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
-    const bool hot = tile < tiles && hr::adapt_pixel_active(rp, tile, pix, moments, counts, floor, threshold);
-    tile_flag_from_lanes(hot, tile, tiles, pix, have_prev, flags);
-}
-// the same with the rule of hr_select_tiles_robust: e_R (the image a robust noise estimate has just left) in place of e
-__global__ __launch_bounds__(256) void select_tiles_image_kernel(RenderParams rp, const double *__restrict__ e_img, double threshold, int have_prev, uint32_t *__restrict__ flags) {
-    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
-    const bool hot = tile < tiles && hr::adapt_pixel_above(rp, tile, pix, e_img, threshold);
-    tile_flag_from_lanes(hot, tile, tiles, pix, have_prev, flags);
-}
 // The selection behind hr_select_tiles and hr_select_tiles_robust (`who`), whose checks are done: the flags by the rule (e_img == nullptr: the
 // moments', else that image's), the compaction, the host's mask.
 static int select_tiles_run(hr_ctx *c, const char *who, const double *e_img, double floor, double threshold, uint32_t *active) {
@@ -2327,22 +2247,21 @@ static int robust_noise_run(hr_ctx *c, const char *who, bool need_counts, double
     const uint32_t K = c->robust_k;
     if ((rc = buckets_cover_every_pixel(c, who))) return rc;   // (synchronised — for the selection also: no kernel is reading the list that is about to be rewritten)
     const RobustNoiseVariant *v = select_robust_noise_kernel(K, ROBUST_NOISE_STAGED);
-    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_noise_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
+    if (!v) return no_instantiation(who, "robust_noise_kernel", K);
     const size_t pixels = region_pixels(c);
     if (!c->robust_noise_img && (rc = plane_alloc(c, ROBUST_NOISE_IMG))) return rc;
     if (!c->robust_noise_trim && (rc = plane_alloc(c, ROBUST_NOISE_TRIM))) return rc;
     CallScratch scratch;
-    double *d = nullptr;
-    std::vector<double> h(ROBUST_NOISE_BLOCKS * 3);
-    HIP_TRY(scratch.alloc((void **)&d, h.size() * sizeof(double)));
+    BlockSummaries blocks;
+    HIP_TRY(blocks.alloc(scratch));
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
-    hipLaunchKernelGGL(v->fn, dim3(ROBUST_NOISE_BLOCKS), dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, pixels, floor, threshold,
-                       c->robust_noise_img, c->robust_noise_trim, d);
+    hipLaunchKernelGGL(v->fn, dim3(SUMMARY_BLOCKS), dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, pixels, floor, threshold,
+                       c->robust_noise_img, c->robust_noise_trim, blocks.dev);
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
-    HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY_AS(who, blocks.fetch(c));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));
-    if (est) noise_summary(h, c->buckets_n, pixels, est);
+    if (est) blocks.summary(c->buckets_n, pixels, est);
     return drain_events(c);
 }
 int hr_robust_noise_estimate(hr_ctx *c, double floor, double threshold, hr_noise *out) {
@@ -2376,8 +2295,8 @@ int hr_denoise_robust(hr_ctx *c, const hr_denoise_params *params) {
     const uint32_t K = c->robust_k;
     if ((rc = buckets_cover_every_pixel(c, who))) return rc;
     const RobustDenoiseInitVariant *v = select_robust_denoise_init_kernel(K);
-    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no robust_denoise_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
-    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;
+    if (!v) return no_instantiation(who, "robust_denoise_init_kernel", K);
+    if ((rc = guides_or_render(c))) return rc;
     const size_t pixels = region_pixels(c);
     return atrous_run(c, who, p, SRC_BUCKETS, [&](dim3 flat, double *cv, int demodulate) {   // (without a level: D = (float)C = R)
         hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (unsigned long long)c->buckets_n, c->guides, cv, pixels, demodulate);
@@ -2410,8 +2329,8 @@ int hr_robust_restore(hr_ctx *c, const hr_restore_params *params) {
     const uint32_t K = c->robust_k;
     if ((rc = buckets_cover_every_pixel(c, who))) return rc;
     const RestoreInitVariant *v = select_restore_init_kernel(K);
-    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no restore_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
-    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;   // (base 1 never comes here: a valid D has valid guides)
+    if (!v) return no_instantiation(who, "restore_init_kernel", K);
+    if ((rc = guides_or_render(c))) return rc;   // (base 1 never comes here: a valid D has valid guides)
     const size_t pixels = region_pixels(c);
     if (!c->restored && (rc = plane_alloc(c, RESTORED))) return rc;
     CallScratch scratch;
@@ -2440,14 +2359,8 @@ int hr_robust_restore(hr_ctx *c, const hr_restore_params *params) {
     image_made(c, RESTORED_IMAGE, p.base == 1u ? SRC_NEW_D : 0u);
     return drain_events(c);
 }
-int hr_read_restored(hr_ctx *c, float *host) {
-    int rc = image_ready(c, RESTORED_IMAGE, "hr_read_restored", host);
-    return rc ? rc : plane_read(c, RESTORED, c->restored, host);
-}
-int hr_resolve_restored(hr_ctx *c, uint8_t *host_rgb8) {
-    int rc = image_ready(c, RESTORED_IMAGE, "hr_resolve_restored", host_rgb8);
-    return rc ? rc : resolve_region(c, 0, host_rgb8, c->restored);
-}
+int hr_read_restored(hr_ctx *c, float *host) { return image_read(c, RESTORED_IMAGE, "hr_read_restored", host); }
+int hr_resolve_restored(hr_ctx *c, uint8_t *host_rgb8) { return image_resolve(c, RESTORED_IMAGE, "hr_resolve_restored", host_rgb8); }
 
 // ---- the denoiser that picks its level per pixel (select_core.h): S and its level plane L ----
 // Everything that is refused is refused before anything is touched: S of an earlier call stays.  Nothing but S, L (and, without guide planes, the
@@ -2472,8 +2385,7 @@ static int select_ready(hr_ctx *c, const char *who, const hr_denoise_params *par
     else (void)hr_select_default_params(&s);
     if (s.smooth > SELECT_MAX_SMOOTH) return fail(HR_ERR_INVALID, "%s: smooth must be in [0,%u]", who, SELECT_MAX_SMOOTH);
     if (s.reserved != 0u) return fail(HR_ERR_INVALID, "%s: reserved must be 0", who);
-    if (!c->counts && c->moments_n < 2) return fail(HR_ERR_INVALID, "%s: %llu samplings behind the moments, a variance needs 2", who, (unsigned long long)c->moments_n);
-    if (c->moments_n >= (1ull << 30)) return fail(HR_ERR_INVALID, "%s: %llu samplings do not fit the resolve's 32-bit scale", who, (unsigned long long)c->moments_n);
+    if ((rc = moments_cover_an_estimate(c, who, true))) return rc;
     if (c->moments_n != c->buckets_n)
         return fail(HR_ERR_INVALID, "%s: the moments cover %llu samplings, the buckets %llu (they must cover the same samplings)", who, (unsigned long long)c->moments_n, (unsigned long long)c->buckets_n);
     if (ft && (rc = floor_and_threshold_ok(who, ft[0], ft[1]))) return rc;
@@ -2482,10 +2394,49 @@ static int select_ready(hr_ctx *c, const char *who, const hr_denoise_params *par
     if (c->counts && (rc = counts_cover_an_estimate(c, who))) return rc;   // (every n >= 2 and none beyond the moments' — which are the buckets')
     const uint32_t K = c->robust_k;
     v = select_select_init_kernel(K);
-    if (!v) return fail(HR_ERR_UNSUPPORTED, "%s: no select_init_kernel instantiation for %u buckets (kernel_variants.h)", who, K);
-    if (!image_valid(c, GUIDE_IMAGE) && (rc = hr_render_guides(c))) return rc;
-    return HR_OK;
+    if (!v) return no_instantiation(who, "select_init_kernel", K);
+    return guides_or_render(c);
 }
+// The pipeline hr_denoise_select and the estimate of its error (selected_noise_run) share, whose checks are done (select_ready: p, s, v), in two
+// steps: a caller allocates its own planes between them and brackets the launches with its event pair.
+//   planes()   the common call scratch: the states twice (once without a level), {A0, B0}, with smoothing e twice, best
+//   launch()   select_init_kernel, then for l = 0 .. levels: [with smoothing: pass(e_in = nullptr, e_out = e[0]), then s.smooth times
+//              select_smooth_kernel over e and, behind it, over the plane pair `more` (or nullptr),] pass(e_in = the smoothed e or nullptr,
+//              e_out = nullptr), and atrous3_kernel to the next level
+// `pass(flat, cur, e_in, e_out, l, demodulate)`: the caller's own launch on c->stream, in the idiom of atrous_run's init — select_pick_kernel or
+// select_noise_kernel, which have these forms (post_kernels.h).
+struct SelectRun {
+    CallScratch scratch;
+    double *st[2] = {nullptr, nullptr}, *raw = nullptr, *e[2] = {nullptr, nullptr}, *best = nullptr;   // (st: 18 planes of a double per pixel each, raw: 6; post_kernels.h)
+    int planes(hr_ctx *c, const char *who, const hr_denoise_params &p, const hr_select_params &s) {
+        const size_t pixels = region_pixels(c);
+        for (int k = 0; k < (p.levels ? 2 : 1); k++) HIP_TRY_AS(who, scratch.alloc((void **)&st[k], pixels * 18 * sizeof(double)));
+        HIP_TRY_AS(who, scratch.alloc((void **)&raw, pixels * 6 * sizeof(double)));
+        for (int k = 0; k < (s.smooth ? 2 : 0); k++) HIP_TRY_AS(who, scratch.alloc((void **)&e[k], pixels * sizeof(double)));
+        HIP_TRY_AS(who, scratch.alloc((void **)&best, pixels * sizeof(double)));
+        return HR_OK;
+    }
+    template <class Pass>
+    void launch(hr_ctx *c, const hr_denoise_params &p, const hr_select_params &s, const SelectInitVariant *v, double *const *more, Pass pass) {
+        const size_t pixels = region_pixels(c);
+        const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
+        const int demodulate = p.demodulate && p.levels ? 1 : 0;   // as hr_denoise: without a level there is nothing to filter
+        const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
+        hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (uint32_t)c->moments_n, c->accum, c->moments, c->guides, st[0], raw, pixels, demodulate);
+        for (uint32_t l = 0; l <= p.levels; l++) {
+            double *cur = st[l & 1u], *nxt = st[(l + 1u) & 1u];
+            if (s.smooth) {
+                pass(flat, cur, nullptr, e[0], l, demodulate);
+                for (uint32_t t = 0; t < s.smooth; t++) {
+                    hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, e[t & 1u], e[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
+                    if (more) hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, more[t & 1u], more[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
+                }
+            }
+            pass(flat, cur, s.smooth ? e[s.smooth & 1u] : nullptr, nullptr, l, demodulate);
+            if (l < p.levels) hipLaunchKernelGGL(atrous3_kernel, tiles2d, dim3(32, 8), 0, c->stream, cur, c->guides, nxt, c->RW, c->RH, 1u << l, sg);
+        }
+    }
+};
 int hr_denoise_select(hr_ctx *c, const hr_denoise_params *params, const hr_select_params *select) {
     static const char *const who = "hr_denoise_select";
     hr_denoise_params p;
@@ -2493,51 +2444,25 @@ int hr_denoise_select(hr_ctx *c, const hr_denoise_params *params, const hr_selec
     const SelectInitVariant *v = nullptr;
     int rc = select_ready(c, who, params, select, false, nullptr, p, s, v);
     if (rc) return rc;
-    const size_t pixels = region_pixels(c);
-    // the call's planes first: a device without room leaves S as it was
-    CallScratch scratch;
-    double *st[2] = {nullptr, nullptr}, *raw = nullptr, *e[2] = {nullptr, nullptr}, *best = nullptr;   // (st: 18 planes of a double per pixel each, raw: 6; post_kernels.h)
-    for (int k = 0; k < (p.levels ? 2 : 1); k++) HIP_TRY_AS(who, scratch.alloc((void **)&st[k], pixels * 18 * sizeof(double)));
-    HIP_TRY_AS(who, scratch.alloc((void **)&raw, pixels * 6 * sizeof(double)));
-    for (int k = 0; k < (s.smooth ? 2 : 0); k++) HIP_TRY_AS(who, scratch.alloc((void **)&e[k], pixels * sizeof(double)));
-    HIP_TRY_AS(who, scratch.alloc((void **)&best, pixels * sizeof(double)));
+    const uint32_t pixels = (uint32_t)region_pixels(c);
+    SelectRun run;
+    if ((rc = run.planes(c, who, p, s))) return rc;   // the call's planes first: a device without room leaves S as it was
     if (!c->selected && (rc = plane_alloc(c, SELECTED))) return rc;
     if (!c->selected_levels && (rc = plane_alloc(c, SELECTED_LEVELS))) return rc;
     c->made_of[SELECTED_IMAGE] = 0;
-    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
-    const int demodulate = p.demodulate && p.levels ? 1 : 0;   // as hr_denoise: without a level there is nothing to filter
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
-    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
-    hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (uint32_t)c->moments_n, c->accum, c->moments, c->guides, st[0], raw, pixels, demodulate);
-    for (uint32_t l = 0; l <= p.levels; l++) {
-        double *cur = st[l & 1u], *nxt = st[(l + 1u) & 1u];
-        if (s.smooth) {
-            hipLaunchKernelGGL(select_pick_kernel, flat, dim3(256), 0, c->stream, cur, raw, c->guides, (const double *)nullptr, e[0], l, best, c->selected_levels, c->selected, (uint32_t)pixels,
-                               demodulate);
-            for (uint32_t t = 0; t < s.smooth; t++) hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, e[t & 1u], e[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
-        }
-        hipLaunchKernelGGL(select_pick_kernel, flat, dim3(256), 0, c->stream, cur, raw, c->guides, s.smooth ? e[s.smooth & 1u] : (const double *)nullptr, (double *)nullptr, l, best,
-                           c->selected_levels, c->selected, (uint32_t)pixels, demodulate);
-        if (l < p.levels) hipLaunchKernelGGL(atrous3_kernel, tiles2d, dim3(32, 8), 0, c->stream, cur, c->guides, nxt, c->RW, c->RH, 1u << l, sg);
-    }
+    run.launch(c, p, s, v, nullptr, [&](dim3 flat, const double *cur, const double *e_in, double *e_out, uint32_t l, int demodulate) {
+        hipLaunchKernelGGL(select_pick_kernel, flat, dim3(256), 0, c->stream, cur, run.raw, c->guides, e_in, e_out, l, run.best, c->selected_levels, c->selected, pixels, demodulate);
+    });
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
     image_made(c, SELECTED_IMAGE);
     return drain_events(c);
 }
-int hr_read_selected(hr_ctx *c, float *host) {
-    int rc = image_ready(c, SELECTED_IMAGE, "hr_read_selected", host);
-    return rc ? rc : plane_read(c, SELECTED, c->selected, host);
-}
-int hr_read_selected_levels(hr_ctx *c, uint8_t *host) {
-    int rc = image_ready(c, SELECTED_IMAGE, "hr_read_selected_levels", host);
-    return rc ? rc : plane_read(c, SELECTED_LEVELS, c->selected_levels, host);
-}
-int hr_resolve_selected(hr_ctx *c, uint8_t *host_rgb8) {
-    int rc = image_ready(c, SELECTED_IMAGE, "hr_resolve_selected", host_rgb8);
-    return rc ? rc : resolve_region(c, 0, host_rgb8, c->selected);
-}
+int hr_read_selected(hr_ctx *c, float *host) { return image_read(c, SELECTED_IMAGE, "hr_read_selected", host); }
+int hr_read_selected_levels(hr_ctx *c, uint8_t *host) { return image_read(c, SELECTED_IMAGE, "hr_read_selected_levels", host, true); }
+int hr_resolve_selected(hr_ctx *c, uint8_t *host_rgb8) { return image_resolve(c, SELECTED_IMAGE, "hr_resolve_selected", host_rgb8); }
 
 // ---- the error estimate of S, its stop rule and its tile selection (select_noise_core.h) ----
 // One run behind the four entry points (`who`): hr_denoise_select's pipeline with select_noise_kernel in the pick's place, everything in call
@@ -2556,53 +2481,35 @@ static int selected_noise_run(hr_ctx *c, const char *who, const hr_denoise_param
     int rc = select_ready(c, who, params, select, tiles, want_error ? ft : nullptr, p, s, v);
     if (rc) return rc;
     const size_t pixels = region_pixels(c);
-    CallScratch scratch;
-    double *st[2] = {nullptr, nullptr}, *raw = nullptr, *var0 = nullptr, *e[2] = {nullptr, nullptr}, *m[2] = {nullptr, nullptr}, *best = nullptr, *M = nullptr, *img = nullptr, *d = nullptr;
+    SelectRun run;
+    if ((rc = run.planes(c, who, p, s))) return rc;
+    CallScratch &scratch = run.scratch;
+    double *var0 = nullptr, *m[2] = {nullptr, nullptr}, *M = nullptr, *img = nullptr;
     float *S = nullptr;
     uint8_t *L = nullptr;
-    for (int k = 0; k < (p.levels ? 2 : 1); k++) HIP_TRY_AS(who, scratch.alloc((void **)&st[k], pixels * 18 * sizeof(double)));
-    HIP_TRY_AS(who, scratch.alloc((void **)&raw, pixels * 6 * sizeof(double)));
     HIP_TRY_AS(who, scratch.alloc((void **)&var0, pixels * 6 * sizeof(double)));
-    for (int k = 0; k < (s.smooth ? 2 : 0); k++) {
-        HIP_TRY_AS(who, scratch.alloc((void **)&e[k], pixels * sizeof(double)));
-        HIP_TRY_AS(who, scratch.alloc((void **)&m[k], pixels * sizeof(double)));
-    }
-    HIP_TRY_AS(who, scratch.alloc((void **)&best, pixels * sizeof(double)));
+    for (int k = 0; k < (s.smooth ? 2 : 0); k++) HIP_TRY_AS(who, scratch.alloc((void **)&m[k], pixels * sizeof(double)));
     HIP_TRY_AS(who, scratch.alloc((void **)&M, pixels * sizeof(double)));
     HIP_TRY_AS(who, scratch.alloc((void **)&S, pixels * 3 * sizeof(float)));
     HIP_TRY_AS(who, scratch.alloc((void **)&L, pixels));
-    std::vector<double> h(SELECT_NOISE_BLOCKS * 3);
+    BlockSummaries blocks;
     if (want_error) {
         HIP_TRY_AS(who, scratch.alloc((void **)&img, pixels * sizeof(double)));
-        HIP_TRY_AS(who, scratch.alloc((void **)&d, h.size() * sizeof(double)));
+        HIP_TRY_AS(who, blocks.alloc(scratch));
     }
-    const DenoiseSigmas sg = denoise_sigmas(p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth);
-    const int demodulate = p.demodulate && p.levels ? 1 : 0;
     EventPair ev;
     HIP_TRY(timed_begin(ev, c->stream));
-    const dim3 flat((unsigned)((pixels + 255) / 256)), tiles2d((c->RW + 31) / 32, (c->RH + 7) / 8);
-    hipLaunchKernelGGL(v->fn, flat, dim3(256), v->lds(), c->stream, c->buckets, c->counts, (uint32_t)c->moments_n, c->accum, c->moments, c->guides, st[0], raw, pixels, demodulate);
-    for (uint32_t l = 0; l <= p.levels; l++) {
-        double *cur = st[l & 1u], *nxt = st[(l + 1u) & 1u];
-        if (s.smooth) {
-            hipLaunchKernelGGL(select_noise_kernel, flat, dim3(256), 0, c->stream, cur, raw, var0, c->guides, (const double *)nullptr, (const double *)nullptr, e[0], m[0], l, best, L, S, M,
-                               (uint32_t)pixels, demodulate);
-            for (uint32_t t = 0; t < s.smooth; t++) {
-                hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, e[t & 1u], e[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
-                hipLaunchKernelGGL(select_smooth_kernel, tiles2d, dim3(32, 8), 0, c->stream, m[t & 1u], m[(t + 1u) & 1u], c->RW, c->RH, 1u << t);
-            }
-        }
-        hipLaunchKernelGGL(select_noise_kernel, flat, dim3(256), 0, c->stream, cur, raw, var0, c->guides, s.smooth ? e[s.smooth & 1u] : (const double *)nullptr,
-                           s.smooth ? m[s.smooth & 1u] : (const double *)nullptr, (double *)nullptr, (double *)nullptr, l, best, L, S, M, (uint32_t)pixels, demodulate);
-        if (l < p.levels) hipLaunchKernelGGL(atrous3_kernel, tiles2d, dim3(32, 8), 0, c->stream, cur, c->guides, nxt, c->RW, c->RH, 1u << l, sg);
-    }
-    if (want_error) hipLaunchKernelGGL(select_noise_error_kernel, dim3(SELECT_NOISE_BLOCKS), dim3(256), 0, c->stream, M, S, pixels, floor, threshold, img, d);
+    run.launch(c, p, s, v, s.smooth ? m : nullptr, [&](dim3 flat, const double *cur, const double *e_in, double *e_out, uint32_t l, int demodulate) {
+        hipLaunchKernelGGL(select_noise_kernel, flat, dim3(256), 0, c->stream, cur, run.raw, var0, c->guides, e_in, e_in ? m[s.smooth & 1u] : nullptr, e_out, e_out ? m[0] : nullptr, l, run.best,
+                           L, S, M, (uint32_t)pixels, demodulate);
+    });
+    if (want_error) hipLaunchKernelGGL(select_noise_error_kernel, dim3(SUMMARY_BLOCKS), dim3(256), 0, c->stream, M, S, pixels, floor, threshold, img, blocks.dev);
     HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
-    if (est) HIP_TRY_AS(who, hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (est) HIP_TRY_AS(who, blocks.fetch(c));
     if (host_img) HIP_TRY_AS(who, hipMemcpyAsync(host_img, img, pixels * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (host_mse) HIP_TRY_AS(who, hipMemcpyAsync(host_mse, M, pixels * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the scratch planes go with the call
-    if (est) noise_summary(h, c->moments_n, pixels, est);
+    if (est) blocks.summary(c->moments_n, pixels, est);
     if (tiles && (rc = select_tiles_run(c, who, img, floor, threshold, active))) return rc;
     return drain_events(c);
 }
@@ -3122,5 +3029,3 @@ int hr_debug_texture(hr_ctx *c, uint32_t n, const int32_t *image, const double *
     HIP_TRY_AS("hr_debug_texture", hipMemcpy(quad, d_quad, (size_t)n * 4 * 4, hipMemcpyDeviceToHost));
     return HR_OK;
 }
-
-}  // extern "C"

@@ -1,14 +1,18 @@
-// Post chain kernels: renderer.rs:64-90 — included by hr_api.hip only (one translation unit: the kernels and the C ABI that launches them).
+// Post chain kernels: renderer.rs:64-90, and every kernel of the estimates, selections and denoisers of §4.7 to §4.17 — included by hr_api.hip only
+// (one translation unit: the kernels and the C ABI that launches them).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "adapt_core.h"
 #include "denoise_core.h"
 #include "device_scene.h"
+#include "noise_core.h"
 #include "post_core.h"
 #include "restore_core.h"
 #include "robust_core.h"
 #include "select_core.h"
 #include "select_noise_core.h"
+#include "trace_kernel.h"   // wave_ballot
 
 using namespace hr;
 
@@ -17,10 +21,103 @@ __global__ void tonemap_gamma_kernel(const float *__restrict__ acc, float *__res
     if (i >= n) return;
     tonemap_gamma(acc[i * 3], acc[i * 3 + 1], acc[i * 3 + 2], scale, &out[i * 3]);
 }
+// hr_resolve's first kernel with every pixel's own count: the scale is hr_resolve's expression 1.0f / (float)(count * 4u), which hr_resolve works
+// out on the host, i.e. correctly rounded.  The device's fp32 division is not (the Makefile trades that for speed), so the quotient is taken in
+// f64 and rounded to fp32: the same float as the host's for every count whose odd part is below 2^28 (a quotient 1 / n lies at least
+// 1 / (odd(n) 2^25) of its value away from the midpoint of two floats, and rounding twice can only differ from rounding once within 2^-53).
+// A pixel without samplings is radiance 0, whatever the accumulator holds.
+__global__ void tonemap_gamma_counted_kernel(const float *__restrict__ acc, const uint32_t *__restrict__ counts, float *__restrict__ out, uint32_t n) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = counts[i];
+    if (k) tonemap_gamma(acc[i * 3], acc[i * 3 + 1], acc[i * 3 + 2], (float)(1.0 / (double)(float)(k * 4u)), &out[i * 3]);
+    else tonemap_gamma(0.0f, 0.0f, 0.0f, 0.0f, &out[i * 3]);
+}
 __global__ void bilateral_quantise_kernel(const float *__restrict__ img, uint8_t *__restrict__ out, uint32_t W, uint32_t H) {
     uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= W || y >= H) return;
     bilateral_quantise(img, W, H, x, y, &out[((size_t)y * W + x) * 3]);
+}
+
+// The summary of an estimate's image, {sum of e, max of e, pixels with e > threshold}, reduced in a FIXED ORDER, so that two calls return identical
+// bits (the scheme of accumulator_sum_kernel, hr_api.hip): a grid of SUMMARY_BLOCKS workgroups of 256 threads, every thread its strided pixels in
+// order (the kernel's own loop), then — here — the lanes of a wave down the __shfl_down ladder 32, 16, .. 1, the four waves' partial results in
+// wave order ((w0 + w1) + w2) + w3 into out[block] = {sum, max, above}; the host adds the blocks in index order (BlockSummaries::summary, hr_api.hip).
+// The tail of noise_kernel, robust_noise_kernel and select_noise_error_kernel; every thread of the workgroup calls it (the barrier).
+constexpr unsigned SUMMARY_BLOCKS = 1024;
+__device__ __forceinline__ void summary_block_reduce(double sum, double mx, double above, double *out) {
+    __shared__ double part[4][3];
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_down(sum, off);
+        const double o = __shfl_down(mx, off);
+        mx = o > mx ? o : mx;
+        above += __shfl_down(above, off);
+    }
+    if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][0] = sum; part[threadIdx.x >> 6][1] = mx; part[threadIdx.x >> 6][2] = above; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *o = out + (size_t)blockIdx.x * 3;
+        o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
+        o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
+        o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
+    }
+}
+
+// The noise estimate of the moments (noise_core.h): e of every pixel into `img`, and its summary into out[block]
+// (summary_block_reduce: reproducible run to run).
+// CNTS (option "sample_counts" on): n is the PIXEL's own count (every one >= 2: noise_run has checked), not the samplings issued.
+template <bool CNTS>
+__global__ __launch_bounds__(256) void noise_kernel(const double *__restrict__ moments, size_t pixels, uint64_t samplings, double floor, double threshold,
+                                                    double *__restrict__ img, double *__restrict__ out, const uint32_t *__restrict__ counts) {
+    double sum = 0.0, mx = 0.0, above = 0.0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
+        double m[6];
+        for (int k = 0; k < 6; k++) m[k] = moments[i * 6 + k];
+        const double e = hr::noise_pixel_error(m, CNTS ? (uint64_t)counts[i] : samplings, floor);
+        img[i] = e;
+        sum += e;
+        mx = e > mx ? e : mx;
+        above += e > threshold ? 1.0 : 0.0;
+    }
+    summary_block_reduce(sum, mx, above, out);
+}
+// the smallest and the largest count of a pixel of the region (option "sample_counts") into out[0], out[1]: an estimate needs 2 samplings behind
+// EVERY pixel, and no pixel can have received more samplings than the moments have seen issued
+__global__ __launch_bounds__(256) void counts_min_kernel(const uint32_t *__restrict__ counts, size_t pixels, uint32_t *__restrict__ out) {
+    uint32_t mn = 0xffffffffu, mx = 0u;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t v = counts[i];
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_down((int)mn, off), p = (uint32_t)__shfl_down((int)mx, off);
+        mn = o < mn ? o : mn;
+        mx = p > mx ? p : mx;
+    }
+    if ((threadIdx.x & 63u) == 0u) { atomicMin(out, mn); atomicMax(out + 1, mx); }
+}
+
+// The tile rule on the device (adapt_core.h): 16 lanes per tile (one per pixel), four tiles per wave; the ballot of a tile's lanes
+// is its flag, ANDed with the flag it had (have_prev: a mask is in force — a tile that went inactive stays inactive).  The ascending compaction of
+// the flags into the list is hipcub's DeviceSelect::Flagged over the tile indices (select_tiles_run, hr_api.hip): deterministic, two calls give
+// identical lists.
+__device__ __forceinline__ void tile_flag_from_lanes(bool hot, uint32_t tile, uint32_t tiles, uint32_t pix, int have_prev, uint32_t *__restrict__ flags) {
+    const unsigned long long m = wave_ballot(hot);
+    const bool any = ((m >> (((threadIdx.x & 63u) >> 4) * 16u)) & 0xffffull) != 0ull;
+    if (pix == 0u && tile < tiles) flags[tile] = any && (!have_prev || flags[tile] != 0u) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void select_tiles_kernel(RenderParams rp, const double *__restrict__ moments, const uint32_t *__restrict__ counts, double floor, double threshold,
+                                                           int have_prev, uint32_t *__restrict__ flags) {
+    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
+    const bool hot = tile < tiles && hr::adapt_pixel_active(rp, tile, pix, moments, counts, floor, threshold);
+    tile_flag_from_lanes(hot, tile, tiles, pix, have_prev, flags);
+}
+// the same with the rule of hr_select_tiles_robust: e_R (the image a robust noise estimate has just left) in place of e
+__global__ __launch_bounds__(256) void select_tiles_image_kernel(RenderParams rp, const double *__restrict__ e_img, double threshold, int have_prev, uint32_t *__restrict__ flags) {
+    const uint32_t tile = blockIdx.x * 16u + (threadIdx.x >> 4), pix = threadIdx.x & 15u, tiles = rp.tiles_x * rp.tiles_y;
+    const bool hot = tile < tiles && hr::adapt_pixel_above(rp, tile, pix, e_img, threshold);
+    tile_flag_from_lanes(hot, tile, tiles, pix, have_prev, flags);
 }
 
 // The à-trous denoiser (denoise_core.h): one thread per pixel; an init kernel, one launch per level between two ping-pong planes
@@ -93,9 +190,8 @@ __global__ __launch_bounds__(256) void robust_denoise_init_kernel(const double *
 }
 
 // The robust noise estimate (robust_pixel_error_k, robust_core.h): e_R of every pixel into `img`, the trim it took into `trim`
-// (or nullptr), and the summary out[block] = {sum of e_R, max of e_R, pixels with e_R > threshold}, reduced in a fixed order — a fixed grid,
-// every thread its strided pixels in order, lanes and waves in order, the host adds the blocks' partial sums in index order (the scheme of
-// noise_kernel, hr_api.hip): two calls return identical bits.  The kernel carries no arithmetic of its own.
+// (or nullptr), and the summary out[block] = {sum of e_R, max of e_R, pixels with e_R > threshold}, reduced in noise_kernel's fixed order
+// (summary_block_reduce): two calls return identical bits.  The kernel carries no arithmetic of its own.
 // K is a template parameter: the pixel's K keys live in registers, no array is indexed at run time, nothing goes to scratch.  counts == nullptr: every pixel has n_all samplings.
 // STAGE: how the lanes come by their pixel's 3 K doubles — the arithmetic, and so every bit, is the same.
 //   true   a workgroup's 256 pixels are one contiguous span of 256 x 24 K bytes: its lanes load it as consecutive doubles (a wave's load is 512
@@ -103,7 +199,6 @@ __global__ __launch_bounds__(256) void robust_denoise_init_kernel(const double *
 //          no bank conflict)
 //   false  every lane loads its own 24 K contiguous bytes from global memory: a wave's load touches 64 lines 24 K bytes apart
 // The loop runs the same number of times for every thread of a workgroup (the barriers), a lane past the last pixel computes nothing.
-constexpr unsigned ROBUST_NOISE_BLOCKS = 1024;
 template <uint32_t K, bool STAGE>
 __global__ __launch_bounds__(256) void robust_noise_kernel(const double *__restrict__ buckets, const uint32_t *__restrict__ counts, unsigned long long n_all, size_t pixels,
                                                            double floor, double threshold, double *__restrict__ img, uint8_t *__restrict__ trim, double *__restrict__ out) {
@@ -141,21 +236,7 @@ __global__ __launch_bounds__(256) void robust_noise_kernel(const double *__restr
         }
         if (STAGE) __syncthreads();   // the next round overwrites the span
     }
-    __shared__ double part[4][3];
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_down(sum, off);
-        const double o = __shfl_down(mx, off);
-        mx = o > mx ? o : mx;
-        above += __shfl_down(above, off);
-    }
-    if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][0] = sum; part[threadIdx.x >> 6][1] = mx; part[threadIdx.x >> 6][2] = above; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double *o = out + (size_t)blockIdx.x * 3;
-        o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
-        o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
-        o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
-    }
+    summary_block_reduce(sum, mx, above, out);
 }
 
 // The restored robust resolve R' (restore_core.h).  The kernels carry no arithmetic of their own: every value is the core's.
@@ -318,9 +399,7 @@ __global__ __launch_bounds__(256) void select_noise_kernel(const double *__restr
     select_noise_pick(e, mse, l, fw, g, demodulate, best + p, L + p, S + p * 3, M + p);
 }
 // e_S of every pixel from M and the run's S into `img`, and the summary out[block] = {sum of e_S, max of e_S, pixels with e_S > threshold}, reduced in
-// robust_noise_kernel's fixed order — a fixed grid, every thread its strided pixels in order, lanes and waves in order, the host adds the blocks'
-// partial sums in index order: two calls return identical bits.
-constexpr unsigned SELECT_NOISE_BLOCKS = 1024;
+// robust_noise_kernel's fixed order (summary_block_reduce): two calls return identical bits.
 __global__ __launch_bounds__(256) void select_noise_error_kernel(const double *__restrict__ M, const float *__restrict__ S, size_t pixels, double floor, double threshold,
                                                                  double *__restrict__ img, double *__restrict__ out) {
     double sum = 0.0, mx = 0.0, above = 0.0;
@@ -331,19 +410,5 @@ __global__ __launch_bounds__(256) void select_noise_error_kernel(const double *_
         mx = e > mx ? e : mx;
         above += e > threshold ? 1.0 : 0.0;
     }
-    __shared__ double part[4][3];
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_down(sum, off);
-        const double o = __shfl_down(mx, off);
-        mx = o > mx ? o : mx;
-        above += __shfl_down(above, off);
-    }
-    if ((threadIdx.x & 63u) == 0u) { part[threadIdx.x >> 6][0] = sum; part[threadIdx.x >> 6][1] = mx; part[threadIdx.x >> 6][2] = above; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double *o = out + (size_t)blockIdx.x * 3;
-        o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
-        o[1] = fmax(fmax(part[0][1], part[1][1]), fmax(part[2][1], part[3][1]));
-        o[2] = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
-    }
+    summary_block_reduce(sum, mx, above, out);
 }

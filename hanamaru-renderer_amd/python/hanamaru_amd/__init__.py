@@ -249,13 +249,30 @@ def hip_lib():
     return _hip
 
 
+def _ok(L, rc):
+    if rc != 0:
+        raise HipError(rc, L.hr_last_error().decode())
+
+
+def _with(defaults_fn, struct, who, params):
+    """defaults_fn()'s `struct` with the keywords `params` replaced; a keyword that is no field of it is who()'s TypeError"""
+    p = defaults_fn()
+    for k, v in params.items():
+        if k not in dict(struct._fields_):
+            raise TypeError("%s() has no parameter %r" % (who, k))
+        setattr(p, k, v)
+    return p
+
+
+def _noise_dict(n):
+    return {k: getattr(n, k) for k, _ in n._fields_}
+
+
 def denoise_default_params():
     """hr_denoise_default_params: the documented defaults as a DenoiseParams (needs no device)."""
     L = hip_lib()
     p = DenoiseParams()
-    rc = L.hr_denoise_default_params(C.byref(p))
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_denoise_default_params(C.byref(p)))
     return p
 
 
@@ -266,9 +283,7 @@ def comm_unique_id():
     """ncclGetUniqueId through the library: bytes to hand to every rank's Renderer.comm_init_rank."""
     L = hip_lib()
     buf = (C.c_char * COMM_ID_BYTES)()
-    rc = L.hr_comm_get_unique_id(buf)
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_comm_get_unique_id(buf))
     return bytes(buf)
 
 
@@ -278,9 +293,7 @@ def comm_library():
     L.hr_comm_library.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
     buf = C.create_string_buffer(4096)
     reused = C.c_int(0)
-    rc = L.hr_comm_library(buf, 4096, C.byref(reused))
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_comm_library(buf, 4096, C.byref(reused)))
     return buf.value.decode(), bool(reused.value)
 
 
@@ -288,17 +301,13 @@ def comm_init_local(renderers):
     """One process driving several GPUs: ncclCommInitAll over the renderers' devices."""
     L = hip_lib()
     arr = (C.c_void_p * len(renderers))(*[r._h for r in renderers])
-    rc = L.hr_comm_init_local(arr, len(renderers))
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_comm_init_local(arr, len(renderers)))
 
 
 def allreduce_accumulators(renderers):
     L = hip_lib()
     arr = (C.c_void_p * len(renderers))(*[r._h for r in renderers])
-    rc = L.hr_allreduce_accumulators(arr, len(renderers))
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_allreduce_accumulators(arr, len(renderers)))
 
 
 def fold_statistics(renderers):
@@ -320,9 +329,7 @@ def guide_lens_points(lens_shape, lens_points):
     it sums them; lens_shape 0 Square, 1 Circle; lens_points 4 or 16 (needs no device)."""
     L = hip_lib()
     uv = np.zeros((max(int(lens_points), 1), 2), dtype=np.float32)
-    rc = L.hr_guide_lens_points(int(lens_shape), int(lens_points), uv.ctypes.data)
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_guide_lens_points(int(lens_shape), int(lens_points), uv.ctypes.data))
     return uv
 
 
@@ -330,9 +337,7 @@ def select_default_params():
     """hr_select_default_params: the documented defaults as a SelectParams (needs no device)."""
     L = hip_lib()
     p = SelectParams()
-    rc = L.hr_select_default_params(C.byref(p))
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_select_default_params(C.byref(p)))
     return p
 
 
@@ -340,9 +345,7 @@ def restore_default_params():
     """hr_restore_default_params: the documented defaults as a RestoreParams (needs no device)."""
     L = hip_lib()
     p = RestoreParams()
-    rc = L.hr_restore_default_params(C.byref(p))
-    if rc != 0:
-        raise HipError(rc, L.hr_last_error().decode())
+    _ok(L, L.hr_restore_default_params(C.byref(p)))
     return p
 
 
@@ -439,8 +442,7 @@ class Renderer:
         self._robust_k = 0    # option "robust_buckets" as last accepted
 
     def _check(self, rc):
-        if rc != 0:
-            raise HipError(rc, self.L.hr_last_error().decode())
+        _ok(self.L, rc)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -593,7 +595,7 @@ class Renderer:
         """hr_noise_estimate: {samplings, pixels, pixels_above, mean_error, max_error} of the per-pixel relative standard error e."""
         n = Noise()
         self._check(self.L.hr_noise_estimate(self._h, float(floor), float(threshold), C.byref(n)))
-        return {k: getattr(n, k) for k, _ in n._fields_}
+        return _noise_dict(n)
 
     def noise_image(self, floor=0.01):
         """hr_read_noise_image: e of every pixel, (h, w) float64."""
@@ -657,21 +659,13 @@ class Renderer:
 
     def denoise(self, **params):
         """hr_denoise: the defaults, with any of levels, demodulate, sigma_color, sigma_normal, sigma_albedo, sigma_depth replaced."""
-        p = denoise_default_params()
-        for k, v in params.items():
-            if k not in dict(DenoiseParams._fields_):
-                raise TypeError("denoise() has no parameter %r" % k)
-            setattr(p, k, v)
+        p = _with(denoise_default_params, DenoiseParams, "denoise", params)
         self._check(self.L.hr_denoise(self._h, C.byref(p)))
 
     def denoise_robust(self, **params):
         """hr_denoise_robust: denoise()'s filter on the robust radiance and its bucket-spread variance (option robust_buckets; no moments
         needed); D is read with read_denoised / resolve_denoised."""
-        p = denoise_default_params()
-        for k, v in params.items():
-            if k not in dict(DenoiseParams._fields_):
-                raise TypeError("denoise_robust() has no parameter %r" % k)
-            setattr(p, k, v)
+        p = _with(denoise_default_params, DenoiseParams, "denoise_robust", params)
         self._check(self.L.hr_denoise_robust(self._h, C.byref(p)))
 
     def read_denoised(self):
@@ -710,11 +704,7 @@ class Renderer:
     def robust_restore(self, **params):
         """hr_robust_restore: R' = base + the trimmed buckets' excess spread along the guide planes; the defaults, with any of levels, base,
         sigma_n, sigma_a, sigma_z replaced (base 1: on top of the D of denoise_robust())."""
-        p = restore_default_params()
-        for k, v in params.items():
-            if k not in dict(RestoreParams._fields_):
-                raise TypeError("robust_restore() has no parameter %r" % k)
-            setattr(p, k, v)
+        p = _with(restore_default_params, RestoreParams, "robust_restore", params)
         self._check(self.L.hr_robust_restore(self._h, C.byref(p)))
 
     def read_restored(self):
@@ -729,25 +719,13 @@ class Renderer:
     def denoise_select(self, smooth=None, **params):
         """hr_denoise_select: S and its level plane L — hr_denoise's filter with the level picked per pixel from the held-out sample halves;
         the denoiser's defaults with any of levels, demodulate, sigma_* replaced, and `smooth` passes over the error planes (None: the default)."""
-        p = denoise_default_params()
-        for k, v in params.items():
-            if k not in dict(DenoiseParams._fields_):
-                raise TypeError("denoise_select() has no parameter %r" % k)
-            setattr(p, k, v)
-        s = select_default_params()
-        if smooth is not None:
-            s.smooth = smooth
-        self._check(self.L.hr_denoise_select(self._h, C.byref(p), C.byref(s)))
+        self._check(self.L.hr_denoise_select(self._h, *self._select_args("denoise_select", smooth, params)))
 
     # ---- the error estimate of the selected radiance, and the selection of tiles by it (include/hanamaru_hip.h)
     @staticmethod
     def _select_args(who, smooth, params):
         """(DenoiseParams, SelectParams) by reference from denoise_select()'s keywords"""
-        p = denoise_default_params()
-        for k, v in params.items():
-            if k not in dict(DenoiseParams._fields_):
-                raise TypeError("%s() has no parameter %r" % (who, k))
-            setattr(p, k, v)
+        p = _with(denoise_default_params, DenoiseParams, who, params)
         s = select_default_params()
         if smooth is not None:
             s.smooth = smooth
@@ -758,7 +736,7 @@ class Renderer:
         denoise_select(smooth, **params) makes."""
         n = Noise()
         self._check(self.L.hr_selected_noise_estimate(self._h, *self._select_args("selected_noise_estimate", smooth, params), float(floor), float(threshold), C.byref(n)))
-        return {k: getattr(n, k) for k, _ in n._fields_}
+        return _noise_dict(n)
 
     def selected_noise_image(self, floor=0.01, smooth=None, **params):
         """hr_read_selected_noise_image: e_S of every pixel, (h, w) float64."""
@@ -793,7 +771,7 @@ class Renderer:
         """hr_robust_noise_estimate: {samplings, pixels, pixels_above, mean_error, max_error} of e_R, the winsorized relative error of R's channel sum."""
         n = Noise()
         self._check(self.L.hr_robust_noise_estimate(self._h, float(floor), float(threshold), C.byref(n)))
-        return {k: getattr(n, k) for k, _ in n._fields_}
+        return _noise_dict(n)
 
     def robust_noise_image(self, floor=0.01):
         """hr_read_robust_noise_image: e_R of every pixel, (h, w) float64."""
