@@ -228,9 +228,15 @@ HD void trace_node(const Scene &sc, const Ray &r, TraceState &ts, LaneCounters *
     node_advance<SPEC>(ts, node_hit(nd, r, ts.t), leaf ? nd.a : nd.b, leaf ? nd.b : nd.a);
 }
 // One visit on the 16-byte nodes: a single 16-byte load; the six planes are grid coordinates, exact in fp32, and the box test is
-// six FMAs on the ray's precomputed (qinv, qc).  The grid planes lie at least one step outside the true box and the fp32 error
-// of q * qinv + qc is ~0.004 steps, so the test can only over-report hits (more visits), never lose one.  Same visits in the same order as
-// trace_node() on the 32-byte records of the same tree, plus the few extra ones the fatter boxes let through.
+// six FMAs on the ray's precomputed (qinv, qc).  The grid planes lie on the grid outside the true box, at least QMARGIN = 0.05 step away
+// (device_scene.h q_low / q_high), and the fp32 error of q * qinv + qc is three roundings of 2^-24 on values up to |qmin - o|: 0.004 steps
+// each for an origin inside the scene, 0.004 (D + 1) for one D scene extents away.  For origins within about three scene extents the test
+// can therefore only over-report hits (more visits), never lose one: same visits in the same order as trace_node() on the 32-byte records of
+// the same tree, plus the few extra ones the fatter boxes let through, and the same hits to the bit.  Further out that is a measurement,
+// not a construction — and trace_node()'s own test is no more exact there, it rounds plane - o to 2^-24 D extents as well.  Measured
+// on the device (tests/trace_sweeps.py, profiles/trace_sweeps.txt): up to 1,000 extents every ray returns the 32-byte walk's bits (1,800
+// rays per rung at primitives of 0.2 extents and more, 6,000 per rung at primitives of 0.01 - 0.1 extents); beyond, on the small
+// primitives, 2 of 6,000 rays differ at 3,000 extents, 5 at 10,000, 49 at 100,000 — all of them rays whose hit fp32 no longer resolves.
 template <bool CNT, bool SPEC = false>
 HD void trace_qnode(const Scene &sc, const Ray &r, TraceState &ts, LaneCounters *cn) {
     const QNode nd = *reinterpret_cast<const QNode *>(reinterpret_cast<const char *>(sc.qnodes) + ts.cur);   // ts.cur: byte offset, octant copy included

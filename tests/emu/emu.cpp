@@ -631,24 +631,39 @@ void emu_set_walk_mode(int mode) { g_walk_mode = mode; }
 uint32_t emu_gov_budget_next(uint32_t B, float ratio, uint32_t lo, uint32_t hi, uint32_t step) { return gov_budget_next(B, ratio, lo, hi, step); }
 uint64_t emu_last_node_tests(void) { return g_node_tests; }
 
-int emu_intersect(const emu_scene *e, uint32_t n, const float *rays, float *out, int32_t *out_elem) {
+// Deliberately WRONG walks (tests/test_trace_sweeps_cpu.py shows that the sweeps notice them): bit 0 = the newer of two parked leaves is
+// dropped instead of tested, bit 1 = a shadow query's search limit is shadow_len instead of shadow_len + 0.03f.  0 = the walk as it is.
+static int g_walk_mutant = 0;
+void emu_set_walk_mutant(int bits) { g_walk_mutant = bits; }
+
+// hr_debug_trace on the host, one lane at a time (trace_debug_kernel, trace_kernel.h): shadow_len[i] > 0 marks a shadow query — the search limit
+// shadow_len + 0.03f, the shadow-phase bit, shadow_early_out after every leaf; shadow_len null or <= 0: a closest-hit query to T_INF.  The walk
+// is emu_set_walk_mode's.  out[i][8] / out_elem as hr_debug_trace (write_hit_record).
+int emu_trace(const emu_scene *e, uint32_t n, const float *rays, const float *shadow_len, float *out, int32_t *out_elem) {
     const Scene &sc = e->view;
     g_node_tests = 0;
     if (g_walk_mode == 2 && !sc.qnodes) return 1;
     for (uint32_t i = 0; i < n; i++) {
-        Ray r;
-        ray_set(r, v3(rays[i * 6], rays[i * 6 + 1], rays[i * 6 + 2]), v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]));
-        ray_quantise(sc, r);
-        TraceState ts;
-        trace_begin(ts, T_INF, g_walk_mode == 2 ? r.start : 0u);   // 16-byte records: byte offset of the octant's copy; 32-byte records: node index
+        Path p;
+        p.q = 0u; p.tile = 0u; p.st = 1u;
+        ray_set(p.ray, v3(rays[i * 6], rays[i * 6 + 1], rays[i * 6 + 2]), v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]));
+        ray_quantise(sc, p.ray);
+        const float sl = shadow_len ? shadow_len[i] : 0.0f;
+        p.shadow_len = sl;
+        if (sl > 0.0f) p.st |= 16u;
+        const Ray &r = p.ray;
+        TraceState &ts = p.ts;
+        // 16-byte records: byte offset of the octant's copy; 32-byte records: node index
+        trace_begin(ts, sl > 0.0f ? ((g_walk_mutant & 2) ? sl : sl + 0.03f) : T_INF, g_walk_mode == 2 ? r.start : 0u);
         LaneCounters lc = {0, 0, 0, 0, 0, 0};
         if (g_walk_mode == 0) {
-            while (ts.cur != NODE_END) trace_step<true>(sc, r, ts, &lc);
+            while (ts.cur != NODE_END) { trace_step<true>(sc, r, ts, &lc); shadow_early_out(p); }
         } else {
             while (!trace_done(ts)) {
                 if (g_walk_mode == 2) while (ts.cur != NODE_END && ts.leaf2 == 0) trace_qnode<true, true>(sc, r, ts, &lc);
                 else while (ts.cur != NODE_END && ts.leaf2 == 0) trace_node<true, true>(sc, r, ts, &lc);
-                if (ts.leaf) trace_leaf_next<true>(sc, r, ts, &lc);
+                if ((g_walk_mutant & 1) && ts.leaf2) { ts.leaf = ts.leaf2; ts.leaf2 = 0u; }
+                if (ts.leaf) { trace_leaf_next<true>(sc, r, ts, &lc); shadow_early_out(p); }
             }
         }
         g_node_tests += lc.node_tests;
@@ -665,6 +680,42 @@ int emu_intersect(const emu_scene *e, uint32_t n, const float *rays, float *out,
         }
         out_elem[i] = elem;
     }
+    return 0;
+}
+int emu_intersect(const emu_scene *e, uint32_t n, const float *rays, float *out, int32_t *out_elem) { return emu_trace(e, n, rays, nullptr, out, out_elem); }
+
+// Deliberately WRONG trees, edited in the built scene's arrays.  One octant's copy with the near and far planes of one axis exchanged, in both
+// record formats (what an emit_node that got an octant bit wrong would leave):
+int emu_break_octant_planes(emu_scene *e, int octant, int axis) {
+    HostScene &hs = e->hs;
+    if (octant < 0 || octant > 7 || axis < 0 || axis > 2 || !hs.num_nodes) return 1;
+    for (uint32_t i = 0; i < hs.num_nodes; i++) {
+        Node &nd = hs.nodes[(size_t)octant * hs.num_nodes + i];
+        if (axis == 0) std::swap(nd.nearx, nd.farx); else if (axis == 1) std::swap(nd.neary, nd.fary); else std::swap(nd.nearz, nd.farz);
+        if (hs.qnodes.empty()) continue;
+        QNode &q = hs.qnodes[(size_t)octant * (hs.num_nodes + 1u) + i];
+        if (axis == 0) { const uint32_t a = q.xy_near & 0xffffu, b = q.xy_far & 0xffffu; q.xy_near = (q.xy_near & 0xffff0000u) | b; q.xy_far = (q.xy_far & 0xffff0000u) | a; }
+        else if (axis == 1) { const uint32_t a = q.xy_near >> 16, b = q.xy_far >> 16; q.xy_near = (q.xy_near & 0xffffu) | (b << 16); q.xy_far = (q.xy_far & 0xffffu) | (a << 16); }
+        else q.z_nf = (q.z_nf >> 16) | (q.z_nf << 16);
+    }
+    return 0;
+}
+// ... and every quantised box `steps` grid steps smaller on each side (what a quantisation that rounded inwards would leave); the 32-byte
+// records stay as they are
+int emu_shrink_qboxes(emu_scene *e, int steps) {
+    HostScene &hs = e->hs;
+    if (hs.qnodes.empty() || steps < 0) return 1;
+    auto in = [steps](uint32_t nearq, uint32_t farq, uint32_t &n2, uint32_t &f2) {   // (near > far in the octants that look down the axis)
+        const int s = nearq <= farq ? steps : -steps;
+        n2 = (uint32_t)std::min(65535, std::max(0, (int)nearq + s)); f2 = (uint32_t)std::min(65535, std::max(0, (int)farq - s));
+    };
+    for (int o = 0; o < 8; o++)
+        for (uint32_t i = 0; i < hs.num_nodes; i++) {
+            QNode &q = hs.qnodes[(size_t)o * (hs.num_nodes + 1u) + i];
+            uint32_t nx, fx, ny, fy, nz, fz;
+            in(q.xy_near & 0xffffu, q.xy_far & 0xffffu, nx, fx); in(q.xy_near >> 16, q.xy_far >> 16, ny, fy); in(q.z_nf & 0xffffu, q.z_nf >> 16, nz, fz);
+            q.xy_near = nx | (ny << 16); q.xy_far = fx | (fy << 16); q.z_nf = nz | (fz << 16);
+        }
     return 0;
 }
 

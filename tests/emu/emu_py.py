@@ -32,6 +32,10 @@ def lib():
         L.emu_path_log.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.emu_render_debug.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         L.emu_intersect.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.emu_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.emu_set_walk_mutant.argtypes = [C.c_int]
+        L.emu_break_octant_planes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.emu_shrink_qboxes.argtypes = [C.c_void_p, C.c_int]
         L.emu_surface.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.emu_sky.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.emu_texture.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -109,6 +113,25 @@ class EmuScene:
         lib().emu_intersect(self._h, r.shape[0], r.ctypes.data, out.ctypes.data, el.ctypes.data)
         return out, el
 
+    def trace(self, rays, shadow_len=None):
+        """Renderer.debug_trace's twin (emu_trace): shadow_len > 0 marks shadow queries (limit shadow_len + 0.03f, shadow_early_out after every
+        leaf), on the walk set_walk_mode chose"""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        sl = None if shadow_len is None else np.ascontiguousarray(shadow_len, dtype=np.float32).reshape(r.shape[0])
+        out = np.empty((r.shape[0], 8), dtype=np.float32)
+        el = np.empty((r.shape[0],), dtype=np.int32)
+        rc = lib().emu_trace(self._h, r.shape[0], r.ctypes.data, None if sl is None else sl.ctypes.data, out.ctypes.data, el.ctypes.data)
+        assert rc == 0
+        return out, el
+
+    def break_octant_planes(self, octant, axis):
+        """a deliberately wrong tree: one octant's copy with the near and far planes of one axis exchanged, in both record formats"""
+        assert lib().emu_break_octant_planes(self._h, octant, axis) == 0
+
+    def shrink_qboxes(self, steps=2):
+        """a deliberately wrong tree: every quantised box `steps` grid steps smaller on each side"""
+        assert lib().emu_shrink_qboxes(self._h, steps) == 0
+
     # the twins of Renderer.debug_surface / debug_sky / debug_texture (csrc/query_core.h on the host): same arguments, same results
     def debug_surface(self, rays, fix=None, draws=None, precise=False):
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
@@ -166,6 +189,15 @@ def set_walk_mode(mode):
     """0 = node + leaf per visit, 1 = the trace kernel's postponed-leaf schedule, 2 = that schedule on the 16-byte quantised
     nodes (EmuScene.intersect)."""
     lib().emu_set_walk_mode(mode)
+
+
+WALK_MUTANT_DROP_SECOND_LEAF, WALK_MUTANT_BARE_SHADOW_LIMIT = 1, 2
+
+
+def set_walk_mutant(bits):
+    """a deliberately wrong walk for EmuScene.trace / intersect (0 = the walk as it is): bit 0 drops the newer of two parked leaves, bit 1 takes
+    a shadow query's search limit as shadow_len instead of shadow_len + 0.03f"""
+    lib().emu_set_walk_mutant(bits)
 
 
 def set_draw_residuals(on):
