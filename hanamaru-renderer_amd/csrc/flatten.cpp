@@ -330,19 +330,24 @@ int flatten_scene(const hr_scene_desc *sd, HostScene &out, std::string &err, int
             }
         }
     }
-    const hr_camera &cam = sd->camera;
+    return flatten_camera(sd->camera, out.cam, out.camd, err);
+}
+
+int flatten_camera(const hr_camera &cam, CameraF &camf, CameraD &camd, std::string &err) {
+    auto f3 = [](float *dst, const hr_vec3 &v) { dst[0] = (float)v.x; dst[1] = (float)v.y; dst[2] = (float)v.z; };
+    auto fin3 = [](const hr_vec3 &v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
     if (!(fin3(cam.eye) && fin3(cam.right) && fin3(cam.up) && fin3(cam.forward) && fin3(cam.plane_half_right) && fin3(cam.plane_half_up) &&
           std::isfinite(cam.lens_radius) && std::isfinite(cam.focus_distance)))
         return ferr(err, HR_ERR_INVALID, "camera is not finite");
-    memset(&out.cam, 0, sizeof out.cam);
-    f3(out.cam.eye, cam.eye); f3(out.cam.right, cam.right); f3(out.cam.up, cam.up); f3(out.cam.forward, cam.forward);
-    f3(out.cam.phr, cam.plane_half_right); f3(out.cam.phu, cam.plane_half_up);
-    out.cam.lens_radius = (float)cam.lens_radius; out.cam.focus_distance = (float)cam.focus_distance; out.cam.lens_shape = cam.lens_shape;
+    memset(&camf, 0, sizeof camf);
+    f3(camf.eye, cam.eye); f3(camf.right, cam.right); f3(camf.up, cam.up); f3(camf.forward, cam.forward);
+    f3(camf.phr, cam.plane_half_right); f3(camf.phu, cam.plane_half_up);
+    camf.lens_radius = (float)cam.lens_radius; camf.focus_distance = (float)cam.focus_distance; camf.lens_shape = cam.lens_shape;
     {
         auto d3 = [](double *dst, const hr_vec3 &v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
-        d3(out.camd.eye, cam.eye); d3(out.camd.right, cam.right); d3(out.camd.up, cam.up); d3(out.camd.forward, cam.forward);
-        d3(out.camd.phr, cam.plane_half_right); d3(out.camd.phu, cam.plane_half_up);
-        out.camd.lens_radius = cam.lens_radius; out.camd.focus_distance = cam.focus_distance;
+        d3(camd.eye, cam.eye); d3(camd.right, cam.right); d3(camd.up, cam.up); d3(camd.forward, cam.forward);
+        d3(camd.phr, cam.plane_half_right); d3(camd.phu, cam.plane_half_up);
+        camd.lens_radius = cam.lens_radius; camd.focus_distance = cam.focus_distance;
     }
     return HR_OK;
 }

@@ -51,5 +51,8 @@ struct HostScene {
 // SAH cost drops by more than 30 %); 0 = off
 // host_bvh = false: no tree is built, primitives keep their input order (the device builds the tree, csrc/gpu_bvh.h)
 int flatten_scene(const hr_scene_desc *sd, HostScene &out, std::string &err, int max_leaf = 4, double split_ratio = -1.0, bool host_bvh = true);
+// the camera of a description in the kernels' two precisions (what flatten_scene does with sd->camera, and hr_set_camera with a camera of its own);
+// a camera that is not finite is HR_ERR_INVALID and leaves camf and camd as they were
+int flatten_camera(const hr_camera &cam, CameraF &camf, CameraD &camd, std::string &err);
 
 }  // namespace hr

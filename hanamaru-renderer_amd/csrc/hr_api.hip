@@ -102,7 +102,7 @@ struct EventPair { hipEvent_t a, b; };
 
 // What a derived image (IMAGES, behind the planes) can be made of: a call that changes one of these says so to changed().
 enum : uint32_t { SRC_ACCUM = 1, SRC_MOMENTS = 2, SRC_COUNTS = 4, SRC_BUCKETS = 8, SRC_GUIDES = 16, SRC_SCENE = 32, SRC_TARGET = 64, SRC_NEW_D = 128 };
-enum ImageId { GUIDE_IMAGE, D_IMAGE, R_IMAGE, RESTORED_IMAGE, SELECTED_IMAGE, N_IMAGES };
+enum ImageId { GUIDE_IMAGE, D_IMAGE, R_IMAGE, RESTORED_IMAGE, SELECTED_IMAGE, MOTION_IMAGE, N_IMAGES };
 
 struct hr_ctx {
     int device = 0;
@@ -113,6 +113,7 @@ struct hr_ctx {
     std::vector<void *> scene_allocs;
     Scene dsc{};
     bool have_scene = false;
+    hr_camera camera{};           // the f64 camera in place, as hr_upload_scene or hr_set_camera took it (hr_get_camera)
     uint64_t st_nodes = 0, st_tris = 0, st_spheres = 0, st_cuboids = 0;
     uint32_t num_images = 0;   // of the scene in place: what hr_debug_texture checks its image indices against
     // target
@@ -134,6 +135,8 @@ struct hr_ctx {
     // the denoiser: the guide planes {albedo rgb, normal xyz, depth, coverage} of the region — rendered by hr_render_guides or written
     // by the host — and the denoised radiance D of the last hr_denoise or hr_denoise_robust
     float *guides = nullptr, *denoised = nullptr;
+    // temporal reuse: the motion plane {mx, my, code} of every sub-sample, written by the host, that hr_reproject gathers along
+    float *motion = nullptr;
     // the derived images' validity (IMAGES): the sources the image in place goes stale with, as it was made; 0: there is none
     uint32_t made_of[N_IMAGES] = {};
     uint32_t guide_bounces = 0;   // option "guide_bounces": mirrors and glass the guide rays follow to the first non-delta hit (0: the first hit's planes)
@@ -481,7 +484,7 @@ static int free_mask_buffers(hr_ctx *c) {
 //   ON_FIRST_USE  allocated by the first call that needs it (accum_total: the first all-reduce; noise_img: the first estimate; guides: the first
 //                 hr_render_guides / hr_write_guides; denoised: the first hr_denoise; robust, robust_trim: the first hr_robust; robust_noise_img,
 //                 robust_noise_trim: the first robust noise estimate; restored: the first hr_robust_restore; selected, selected_levels: the first
-//                 hr_denoise_select), freed by set_target —
+//                 hr_denoise_select; motion: the first hr_write_motion), freed by set_target —
 //                 noise_img also with the moments it is made of, guides also by hr_upload_scene (they show the scene), robust, robust_trim
 //                 and the robust noise planes also with the buckets they are made of
 // at_alloc: zeroed when allocated.  at_clear: zeroed by hr_clear.  n: the count that belongs to the plane's contents and is zeroed with them.
@@ -516,8 +519,9 @@ static const Plane ROBUST_NOISE_TRIM{PLANE_SLOT(robust_noise_trim), sizeof(uint8
 static const Plane RESTORED{PLANE_SLOT(restored), sizeof(float), 3, ON_FIRST_USE, false, false};
 static const Plane SELECTED{PLANE_SLOT(selected), sizeof(float), 3, ON_FIRST_USE, false, false};
 static const Plane SELECTED_LEVELS{PLANE_SLOT(selected_levels), sizeof(uint8_t), 1, ON_FIRST_USE, false, false};
+static const Plane MOTION{PLANE_SLOT(motion), sizeof(float), 12, ON_FIRST_USE, false, false};
 #undef PLANE_SLOT
-static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM, &ROBUST_NOISE_IMG, &ROBUST_NOISE_TRIM, &RESTORED, &SELECTED, &SELECTED_LEVELS};
+static const Plane *const PLANES[] = {&ACCUM_OWN, &POST_TMP, &RGB8, &ACCUM_TOTAL, &MOMENTS, &NOISE_IMG, &COUNTS, &GUIDES, &DENOISED, &BUCKETS, &ROBUST, &ROBUST_TRIM, &ROBUST_NOISE_IMG, &ROBUST_NOISE_TRIM, &RESTORED, &SELECTED, &SELECTED_LEVELS, &MOTION};
 
 static size_t region_pixels(const hr_ctx *c) { return (size_t)c->RW * c->RH; }
 static size_t plane_elems(const hr_ctx *c, const Plane &p) { return region_pixels(c) * p.comps * (p.per ? c->*p.per : 1u); }
@@ -555,7 +559,7 @@ static int plane_write(hr_ctx *c, const Plane &p, void *dev, const void *host) {
     int rc = sync_all(c);
     if (rc) return rc;
     // (conservative, kept: a write of one statistics plane counts as a write of all three)
-    changed(c, dev == c->guides ? SRC_GUIDES : (dev == c->accum ? SRC_ACCUM : 0u) | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS);
+    changed(c, dev == c->guides ? SRC_GUIDES : dev == c->motion ? 0u : (dev == c->accum ? SRC_ACCUM : 0u) | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS);   // (nothing is kept that is made of the motion plane)
     HIP_TRY(hipMemcpy(dev, host, plane_bytes(c, p), hipMemcpyHostToDevice));
     return HR_OK;
 }
@@ -596,6 +600,8 @@ static const Image IMAGES[N_IMAGES] = {
     // S and its level plane: neither says nor listens to "a new D"
     {&SELECTED, &SELECTED_LEVELS, SRC_ACCUM | SRC_MOMENTS | SRC_COUNTS | SRC_BUCKETS | SRC_GUIDES | SRC_SCENE | SRC_TARGET, &BUCKETS,
      "no selected image (hr_denoise_select first; anything that changes its inputs invalidates it)"},
+    // the motion plane: it relates the view in place to an earlier one
+    {&MOTION, nullptr, SRC_SCENE | SRC_TARGET, nullptr, "no motion plane (hr_write_motion first; a new camera, scene or target makes it stale)"},
 };
 static bool image_valid(const hr_ctx *c, ImageId id) { return c->made_of[id] != 0; }
 static void image_made(hr_ctx *c, ImageId id, uint32_t decided = 0) { c->made_of[id] = IMAGES[id].stale_with | decided; }
@@ -676,6 +682,7 @@ static int create_resources(hr_ctx *c) {
         for (const WfStartVariant &v : WF_START_VARIANTS) beside_seed.push_back((const void *)v.fn);
         for (const WfTraverseVariant &v : WF_TRAVERSE_VARIANTS) beside_seed.push_back((const void *)v.fn);
         for (const WfShadeVariant &v : WF_SHADE_VARIANTS) beside_seed.push_back((const void *)v.fn);
+        for (const MotionVariant &v : MOTION_VARIANTS) beside_seed.push_back((const void *)v.fn);   // (a frame's motion pass may be enqueued behind the frame before's render)
         for (const void *f : beside_seed) {
             hipFuncAttributes fa;
             HIP_TRY(hipFuncGetAttributes(&fa, f));
@@ -958,8 +965,34 @@ int hr_upload_scene(hr_ctx *c, const hr_scene_desc *sd) {
     }
     c->st_nodes = d.num_nodes; c->st_tris = hs.num_input_tris; c->st_spheres = d.num_spheres; c->st_cuboids = d.num_cuboids;
     c->num_images = (uint32_t)hs.images.size();
+    c->camera = sd->camera;
     c->have_scene = true;
     if ((r = govern_reset(c))) return r;   // another scene: the balance of the two kernels is another one
+    return HR_OK;
+}
+
+// The camera of the scene in place, replaced where it lives: Scene::cam, which every launch takes by value, and the one CameraD on the device — with
+// flatten_scene's conversions (flatten_camera).  What shows the old view goes, as with hr_upload_scene; what is accumulated stays, and so does the tree.
+int hr_set_camera(hr_ctx *c, const hr_camera *cam) {
+    if (!c || !cam) return fail(HR_ERR_INVALID, "hr_set_camera: null argument");
+    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_set_camera: no scene uploaded");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    CameraF camf;
+    CameraD camd;
+    std::string ferr;
+    if ((rc = flatten_camera(*cam, camf, camd, ferr))) return fail(rc, "hr_set_camera: %s", ferr.c_str());   // the camera in place stays
+    HIP_TRY(hipMemcpy(const_cast<CameraD *>(c->dsc.camd), &camd, sizeof camd, hipMemcpyHostToDevice));
+    c->dsc.cam = camf;
+    c->camera = *cam;
+    changed(c, SRC_SCENE);
+    return plane_free(c, GUIDES);
+}
+int hr_get_camera(hr_ctx *c, hr_camera *out) {
+    if (!c || !out) return fail(HR_ERR_INVALID, "hr_get_camera: null argument");
+    if (!c->have_scene) return fail(HR_ERR_NO_SCENE, "hr_get_camera: no scene uploaded");
+    *out = c->camera;
     return HR_OK;
 }
 
@@ -2091,6 +2124,98 @@ int hr_denoise(hr_ctx *c, const hr_denoise_params *params) {
 }
 int hr_read_denoised(hr_ctx *c, float *host) { return image_read(c, D_IMAGE, "hr_read_denoised", host); }
 int hr_resolve_denoised(hr_ctx *c, uint8_t *host_rgb8) { return image_resolve(c, D_IMAGE, "hr_resolve_denoised", host_rgb8); }
+
+// ---- temporal reuse: the motion plane and the gather of a frame's history along it (reproject_core.h) ----
+int hr_reproject_default_params(hr_reproject_params *out) {
+    if (!out) return fail(HR_ERR_INVALID, "hr_reproject_default_params: null argument");
+    memset(out, 0, sizeof *out);
+    out->max_history = 32; out->min_roughness = 0.3; out->depth_tolerance = 1e-3;
+    return HR_OK;
+}
+// the parameters of hr_render_motion / hr_reproject (`who`), or the defaults, checked into `p`
+static int reproject_params(const char *who, const hr_reproject_params *params, hr_reproject_params &p) {
+    if (params) p = *params;
+    else (void)hr_reproject_default_params(&p);
+    if (!p.max_history) return fail(HR_ERR_INVALID, "%s: max_history must be positive", who);
+    for (double v : {p.min_roughness, p.depth_tolerance})
+        if (!(v >= 0.0) || !(v < INFINITY)) return fail(HR_ERR_INVALID, "%s: min_roughness and depth_tolerance must be finite and not negative", who);
+    return HR_OK;
+}
+// One pass over the whole region, whatever tile mask is set, into the motion plane (stored): motion_kernel, one launch, hr_render_guides' contract and
+// accounting.  `from`: the camera of the frame whose history is to be reused, as Camera::new builds it.
+int hr_render_motion(hr_ctx *c, const hr_camera *from, const hr_reproject_params *params) {
+    static const char *const who = "hr_render_motion";
+    if (!c || !from) return fail(HR_ERR_INVALID, "%s: null argument", who);
+    int rc;
+    hr_reproject_params p;
+    if ((rc = reproject_params(who, params, p))) return rc;
+    if ((rc = debug_refusal(c, who, A_SCENE)) || (rc = debug_refusal(c, who, A_TARGET))) return rc;
+    CameraF camf;
+    CameraD camd;
+    std::string ferr;
+    if ((rc = flatten_camera(*from, camf, camd, ferr))) return fail(rc, "%s: %s", who, ferr.c_str());
+    ReprojectCam rc0;
+    for (int k = 0; k < 3; k++) { rc0.eye[k] = camd.eye[k]; rc0.forward[k] = camd.forward[k]; rc0.phr[k] = camd.phr[k]; rc0.phu[k] = camd.phu[k]; }
+    rc0.focus = camd.focus_distance;
+    HIP_TRY(hipSetDevice(c->device));
+    const MotionFn fn = select_motion_kernel(c->dsc.qnodes != nullptr);
+    if (!fn) return fail(HR_ERR_UNSUPPORTED, "%s: no kernel instantiation for this node format (kernel_variants.h)", who);
+    c->made_of[MOTION_IMAGE] = 0;
+    if (!c->motion && (rc = plane_alloc(c, MOTION))) return rc;
+    if ((rc = launch_tile_pass(c, fn, rc0, (float)p.min_roughness, (float)p.depth_tolerance, c->motion))) return rc;
+    image_made(c, MOTION_IMAGE);
+    return HR_OK;
+}
+int hr_read_motion(hr_ctx *c, float *host) { return image_read(c, MOTION_IMAGE, "hr_read_motion", host); }
+int hr_write_motion(hr_ctx *c, const float *host) {
+    if (!c || !host) return fail(HR_ERR_INVALID, "hr_write_motion: null argument");
+    if (!c->accum || !c->W) return fail(HR_ERR_NO_TARGET, "hr_write_motion: hr_set_resolution not called");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if (!c->motion && (rc = plane_alloc(c, MOTION))) return rc;
+    if ((rc = plane_write(c, MOTION, c->motion, host))) return rc;
+    image_made(c, MOTION_IMAGE);
+    return HR_OK;
+}
+// The region's accumulator, counts and moments replaced by their history along the motion plane: reproject_kernel reads the call's copy of the three
+// as they were and writes the planes in place.  What is refused is refused before anything is touched.
+int hr_reproject(hr_ctx *c, const hr_reproject_params *params) {
+    static const char *const who = "hr_reproject";
+    int rc = plane_ready(c, COUNTS, who);
+    if (rc) return rc;
+    hr_reproject_params p;
+    if ((rc = reproject_params(who, params, p))) return rc;
+    if (c->robust_on) return fail(HR_ERR_UNSUPPORTED, "%s: not with option robust_buckets on (buckets are not carried along the motion plane)", who);
+    if (c->mask_on) return fail(HR_ERR_INVALID, "%s: not while a tile mask is set (the history replaces every pixel of the region)", who);
+    if (!c->motion || !image_valid(c, MOTION_IMAGE)) return fail(HR_ERR_INVALID, "%s: %s", who, IMAGES[MOTION_IMAGE].none);
+    if (!c->accum) return fail(HR_ERR_NO_TARGET, "%s: no accumulator", who);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = hr_synchronize(c))) return rc;
+    const bool with_moments = c->moments_on && c->moments;
+    CallScratch scratch;
+    float *old_acc = nullptr;
+    uint32_t *old_counts = nullptr;
+    double *old_mom = nullptr;
+    HIP_TRY_AS(who, scratch.alloc((void **)&old_acc, plane_bytes(c, ACCUM_OWN)));
+    HIP_TRY_AS(who, scratch.alloc((void **)&old_counts, plane_bytes(c, COUNTS)));
+    if (with_moments) HIP_TRY_AS(who, scratch.alloc((void **)&old_mom, plane_bytes(c, MOMENTS)));
+    HIP_TRY_AS(who, hipMemcpyAsync(old_acc, c->accum, plane_bytes(c, ACCUM_OWN), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY_AS(who, hipMemcpyAsync(old_counts, c->counts, plane_bytes(c, COUNTS), hipMemcpyDeviceToDevice, c->stream));
+    if (with_moments) HIP_TRY_AS(who, hipMemcpyAsync(old_mom, c->moments, plane_bytes(c, MOMENTS), hipMemcpyDeviceToDevice, c->stream));
+    changed(c, SRC_ACCUM | SRC_MOMENTS | SRC_COUNTS);
+    EventPair ev;
+    HIP_TRY(timed_begin(ev, c->stream));
+    hipLaunchKernelGGL(reproject_kernel, dim3((c->RW + 31) / 32, (c->RH + 7) / 8), dim3(32, 8), 0, c->stream, c->motion, old_acc, old_counts, old_mom, c->RW, c->RH, p.max_history,
+                       c->accum, c->counts, c->moments);
+    HIP_TRY(timed_end(hipGetLastError(), ev, c->stream, c->post_events));
+    HIP_TRY_AS(who, hipStreamSynchronize(c->stream));   // the copies go with the call
+    if (with_moments) {   // no count exceeds the samplings behind the moments: they become the largest count written
+        uint32_t mm[2];
+        if ((rc = counts_range(c, mm))) return rc;
+        c->moments_n = mm[1];
+    }
+    return drain_events(c);
+}
 
 // ---- option "robust_buckets": the sample buckets and the firefly-robust resolve made of them (robust_core.h) ----
 int hr_read_buckets(hr_ctx *c, double *host, uint64_t *samplings) {

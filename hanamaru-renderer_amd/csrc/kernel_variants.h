@@ -117,6 +117,13 @@ static const GuideLensVariant GUIDE_LENS_VARIANTS[] = {HR_VARIANT(guide_lens_ker
 static GuideLensFn select_guide_lens_kernel(bool qn) {
     return fn_of(find_row(GUIDE_LENS_VARIANTS, [&](const GuideLensVariant &r) { return r.qn == qn; }));
 }
+// ---- motion_kernel<QN> (trace_kernel.h): the motion plane of hr_render_motion, one row per node format ----
+typedef void (*MotionFn)(Scene, RenderParams, ReprojectCam, float, float, float *);
+struct MotionVariant { bool qn; MotionFn fn; };
+static const MotionVariant MOTION_VARIANTS[] = {HR_VARIANT(motion_kernel, true), HR_VARIANT(motion_kernel, false)};
+static MotionFn select_motion_kernel(bool qn) {
+    return fn_of(find_row(MOTION_VARIANTS, [&](const MotionVariant &r) { return r.qn == qn; }));
+}
 typedef void (*TraceDebugFn)(Scene, RenderParams, uint32_t, const float *, const float *, float *, int32_t *, Counters *);
 struct TraceDebugVariant { bool qn, cnt; TraceDebugFn fn; };
 static const TraceDebugVariant TRACE_DEBUG_VARIANTS[] = {HR_VARIANT(trace_debug_kernel, true, false), HR_VARIANT(trace_debug_kernel, false, false),

@@ -8,6 +8,7 @@
 #include "device_scene.h"
 #include "noise_core.h"
 #include "post_core.h"
+#include "reproject_core.h"
 #include "restore_core.h"
 #include "robust_core.h"
 #include "select_core.h"
@@ -80,6 +81,17 @@ __global__ __launch_bounds__(256) void noise_kernel(const double *__restrict__ m
         above += e > threshold ? 1.0 : 0.0;
     }
     summary_block_reduce(sum, mx, above, out);
+}
+// hr_reproject's gather (reproject_pixel, reproject_core.h): one thread per pixel of the W x H region.  old_*: the call's copy of the
+// planes as they were (a pixel's taps are other pixels' old values); acc, counts, mom (nullptr with old_mom: option "moments" off): the planes in
+// place, every element one writer.  The kernel carries no arithmetic of its own; a tap's index is formed only after its f64 range check.
+__global__ __launch_bounds__(256) void reproject_kernel(const float *__restrict__ motion, const float *__restrict__ old_acc, const uint32_t *__restrict__ old_counts,
+                                                        const double *__restrict__ old_mom, uint32_t W, uint32_t H, uint32_t max_history, float *__restrict__ acc,
+                                                        uint32_t *__restrict__ counts, double *__restrict__ mom) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t i = (size_t)y * W + x;
+    counts[i] = reproject_pixel(motion + i * 12, old_acc, old_counts, old_mom, W, H, x, y, max_history, acc + i * 3, old_mom ? mom + i * 6 : nullptr);
 }
 // the smallest and the largest count of a pixel of the region (option "sample_counts") into out[0], out[1]: an estimate needs 2 samplings behind
 // EVERY pixel, and no pixel can have received more samplings than the moments have seen issued

@@ -16,6 +16,7 @@
 
 #include "device_scene.h"
 #include "isaac_core.h"
+#include "reproject_core.h"
 
 namespace hr {
 
@@ -1066,6 +1067,54 @@ HD bool guide_chain_link(const Scene &sc, Ray &ray, const TraceState &ts, bool l
     bsdf_sample(pm, 1.0f, 0.0f, s.pos, -ray.d, s.n, no, nd, refl, transmitted);
     ray_set(ray, no, nd);
     return true;
+}
+// The motion plane (hr_render_motion; motion_kernel in trace_kernel.h): where the point a sub-sample's pinhole ray sees was in the
+// frame of an earlier camera `from`, and whether it may be reused.  Per lane, after the walk of the primary ray (closest hit `ts`, limit T_INF):
+//   motion_point    the point and its class.  A hit: hit_surface and material_at (uv where material_needs_uv says so); Specular, Refraction and
+//                   GGXRefraction, and GGX with a roughness below min_roughness, are view-dependent: out = {0, 0, 3}, no second walk.  Otherwise the
+//                   point is s.pos — for a miss the point at infinity along ray.d — and goes through reproject_project and reproject_motion
+//                   (reproject_core.h, f64): behind `from`: out = {0, 0, 1}; off its frame: out = {mx, my, 1}; else out = {mx, my, 0}, `ray2` is the
+//                   ray from (float)eye0 along normalize((float)v), `len` the fp32 length of (float)v (a miss: -1) and the answer is true: the
+//                   lane walks ray2, closest hit, limit T_INF.  (px, py): the FRAME pixel.
+//   motion_verdict  after that walk (`ts2`): a point is visible from the old eye when the walk hits with |t - len| <= depth_tolerance x len, a sky
+//                   direction when it misses; otherwise out[2] = 2.  fp32, each step one operation.
+// The lens is ignored, as the guide planes ignore it.
+HD bool motion_point(const Scene &sc, const RenderParams &rp, const ReprojectCam &from, float min_roughness, const Ray &ray, const TraceState &ts, uint32_t px, uint32_t py,
+                     uint32_t sub, float *out, Ray &ray2, float &len) {
+    out[0] = 0.0f; out[1] = 0.0f; out[2] = (float)REPROJECT_VIEW_DEPENDENT;
+    len = -1.0f;
+    const bool hit = ts.prim >= 0;
+    V3f x = ray.d;
+    if (hit) {
+        Surf s;
+        hit_surface(sc, ray, ts, material_needs_uv(sc, hit_element(sc, ts)), s);
+        PointMat pm;
+        material_at(sc, s.elem, s.u, s.v, pm);
+        if (pm.surface == 1 || pm.surface == 2 || pm.surface == 4 || (pm.surface == 3 && pm.roughness < min_roughness)) return false;
+        x = s.pos;
+    }
+    const float xf[3] = {x.x, x.y, x.z};
+    double v[3], ncx, ncy, mx, my;
+    out[2] = (float)REPROJECT_OFF_FRAME;
+    if (!reproject_project(from, xf, !hit, v, ncx, ncy)) return false;
+    const bool inside = reproject_motion(ncx, ncy, rp.width, rp.height, px, py, (double)(sub & 1u) * 0.5 - 0.5, (double)(sub >> 1) * 0.5 - 0.5, mx, my);
+    out[0] = (float)mx; out[1] = (float)my;
+    if (!inside) return false;
+    out[2] = (float)REPROJECT_OK;
+    const V3f vf = v3((float)v[0], (float)v[1], (float)v[2]);
+    if (hit) len = sqrtf(dot(vf, vf));
+    ray_set(ray2, v3((float)from.eye[0], (float)from.eye[1], (float)from.eye[2]), normalize(vf));
+    return true;
+}
+HD void motion_verdict(const TraceState &ts2, float len, float depth_tolerance, float *out) {
+    const bool hit = ts2.prim >= 0;
+    bool visible;
+    if (len < 0.0f) visible = !hit;
+    else {
+        const float d = ts2.t - len, bound = depth_tolerance * len;
+        visible = hit && fabsf(d) <= bound;
+    }
+    if (!visible) out[2] = (float)REPROJECT_OCCLUDED;
 }
 // scalar form (host emulation): one node + its leaf per step
 template <bool CNT>

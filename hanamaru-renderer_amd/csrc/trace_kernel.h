@@ -540,6 +540,40 @@ __global__ __launch_bounds__(64 * TRACE_WAVES) void guide_chain_kernel(Scene sc,
     guide_store(rp, active, px, py, sub, g, guides);
 }
 
+// The motion plane (hr_render_motion): guide_render_kernel's tile / lane mapping and pinhole ray, then per lane motion_point (pt_core.h):
+// the class of the hit and its projection into the frame of the camera `from`.  The lanes whose point lies in that frame and may be reused send a
+// second ray from the old eye — the others are parked, and the walk is skipped when no lane has one — and motion_verdict compares what it hits
+// with the point.  Every lane of the region stores its own {mx, my, code}: motion[reg_h][reg_w][4][3], sub-samples in lane order.
+template <bool QN>
+__global__ __launch_bounds__(64 * TRACE_WAVES) void motion_kernel(Scene sc, RenderParams rp, ReprojectCam from, float min_roughness, float depth_tolerance, float *__restrict__ motion) {
+    const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * TRACE_WAVES + (threadIdx.x >> 6);
+    if (tile >= rp.tiles_x * rp.tiles_y) return;
+    uint32_t px, py, sub;
+    tile_lane_pixel(rp, tile, lane, px, py, sub);
+    const bool active = rp_in_region(rp, px, py);
+    LaneCounters lc = {0, 0, 0, 0, 0, 0};
+    WaveStats ws = {{0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}, 0};
+    Path p;
+    p.q = active ? lane : PATH_IDLE;
+    p.tile = tile; p.st = 1u; p.shadow_len = 0.0f;
+    const uint32_t fx = rp.org_x + (active ? px : 0u), fy = rp.org_y + (active ? py : 0u);
+    debug_camera_ray(sc, rp, fx, fy, sub, p.ray);
+    uint32_t tick = 0;
+    walk_wave<false, QN>(sc, rp, p, active, T_INF, lc, ws, tick);
+    float out[3] = {0.0f, 0.0f, 0.0f}, len = -1.0f;
+    Ray second = p.ray;
+    const bool more = active && motion_point(sc, rp, from, min_roughness, p.ray, p.ts, fx, fy, sub, out, second, len);
+    if (wave_ballot(more)) {
+        p.ray = second;
+        walk_wave<false, QN>(sc, rp, p, more, T_INF, lc, ws, tick);
+        if (more) motion_verdict(p.ts, len, depth_tolerance, out);
+    }
+    if (active) {
+        float *o = motion + (((size_t)py * rp_reg_w(rp) + px) * 4u + sub) * 3u;
+        o[0] = out[0]; o[1] = out[1]; o[2] = out[2];
+    }
+}
+
 // guide_store's sibling for the lens-sampled planes: the quad's sum of the lanes' sums over `lens` lens points, x 0.25f / lens (a power of two: exact)
 __device__ __forceinline__ void guide_store_lens(const RenderParams &rp, const bool active, uint32_t px, uint32_t py, uint32_t sub, uint32_t lens, float *g, float *__restrict__ guides) {
     for (int k = 0; k < 8; k++) g[k] = quad_sum(g[k]);

@@ -161,7 +161,13 @@ static void usage(const char *prog) {
            "                        estimated relative error of the selected radiance (a propagated variance plus a held-out bias), with this run's\n"
            "                        --denoise-levels and --select-smooth.  Needs --denoise-auto; one device; not with --robust-noise or --resume.\n"
            "        --level-image FILE.png\n"
-           "                        write an 8-bit grey map of level / --denoise-levels, the level each pixel took (needs --denoise-auto)\n",
+           "                        write an 8-bit grey map of level / --denoise-levels, the level each pixel took (needs --denoise-auto)\n"
+           "        --frames N      render N frames of -s samplings each and write them as frame_000.png .. (hr_set_camera between them: the scene is\n"
+           "                        uploaded and its tree built once).  Frame f renders samplings f S + 1 .. (f + 1) S and prints one \"frame f:\" line.\n"
+           "                        One device; only with -w -h -s --scene --assets --precise / --no-precise --denoise --denoise-levels --guide-bounces.\n"
+           "        --orbit DEG     degrees per frame: the camera turns about the vertical axis through its focus point (default 0).  Needs --frames.\n"
+           "        --temporal M    every frame after the first starts from the frame before it, reprojected along a motion plane (hr_render_motion of\n"
+           "                        the previous camera, hr_reproject), with at most M samplings of history per pixel.  Needs --frames.\n",
            prog);
 }
 
@@ -196,6 +202,11 @@ struct Options {
     long long select_smooth = -1;    // -1: the library's default
     bool auto_noise = false;         // --auto-noise: the noise questions are asked of the image --denoise-auto shows (e_S), not of the moments
     std::string level_png;
+    long long frames = 0;            // --frames N: a sequence of N frames (0: one image, as always)
+    double orbit_deg = 0.0;          // --orbit DEG: degrees per frame about the vertical axis through the focus point
+    long long temporal = 0;          // --temporal M: hr_reproject's max_history (0: every frame starts from nothing)
+    bool have_orbit = false;
+    std::string beyond_frames;       // the first flag given that --frames does not go with
     // what the flags add up to:
     bool counts = false, moments = false;   // hr_set_option "sample_counts", "moments"
     double noise_e = 0.05;                  // the threshold of "above" and of the grey map
@@ -256,6 +267,21 @@ static int parse_options(int argc, char **argv, Options &o) {
             return argv[++i];
         };
         if (a == "--help") { usage(argv[0]); return 0; }
+        {
+            static const char *const with_frames[] = {"-w", "--width", "-h", "--height", "-s", "--sampling", "--scene", "--assets", "--precise", "--no-precise", "--denoise",
+                                                      "--denoise-levels", "--guide-bounces", "--frames", "--orbit", "--temporal"};
+            bool known = false;
+            for (const char *f : with_frames) known = known || a == f;
+            if (!known && o.beyond_frames.empty()) o.beyond_frames = a;
+        }
+        if (a == "--frames") {
+            if (!whole("--frames", val("frames"), 1, 999, 1, "a whole number of frames in 1 .. 999", &o.frames)) return 1;
+        } else if (a == "--orbit") {
+            if (!number("--orbit", val("orbit"), &o.orbit_deg)) return 1;
+            o.have_orbit = true;
+        } else if (a == "--temporal") {
+            if (!whole("--temporal", val("temporal"), 1, 0x7fffffffll, 1, "a whole number of samplings, at least 1", &o.temporal)) return 1;
+        }
         else if (a == "-d" || a == "--debug") o.debug = true;
         else if (a == "-w" || a == "--width") o.width = (uint32_t)strtoul(val("w"), nullptr, 10);
         else if (a == "-h" || a == "--height") o.height = (uint32_t)strtoul(val("h"), nullptr, 10);
@@ -314,12 +340,19 @@ static int parse_options(int argc, char **argv, Options &o) {
         }
         else { fprintf(stderr, "Unrecognized option: '%s'.\n", a.c_str()); return 1; }
     }
+    if (!o.frames && (o.have_orbit || o.temporal)) { fprintf(stderr, "--orbit / --temporal need --frames.\n"); return 1; }
+    if (o.frames && !o.beyond_frames.empty()) {
+        fprintf(stderr, "--frames cannot be combined with %s: a sequence renders on one device, from nothing, with -w -h -s --scene --assets --precise / --no-precise --denoise --denoise-levels --guide-bounces only.\n",
+                o.beyond_frames.c_str());
+        return 1;
+    }
+    if (o.frames && (!o.sampling || o.sampling > 0xffffffffu / (uint32_t)o.frames)) { fprintf(stderr, "--frames: -s samplings per frame must be positive and N x S must fit 32 bits.\n"); return 1; }
     if (o.batch < 1) { fprintf(stderr, "--batch must be at least 1.\n"); return 1; }
     if (o.launch < 0) { fprintf(stderr, "--launch must be at least 1 (or 0: automatic).\n"); return 1; }
     if (o.inflight < 1) { fprintf(stderr, "--inflight must be at least 1.\n"); return 1; }
     if (o.width == 0 || o.height == 0) { fprintf(stderr, "width and height must be positive.\n"); return 1; }
     if (o.gpus < 1) { fprintf(stderr, "--gpus must be at least 1.\n"); return 1; }
-    o.counts = o.have_adaptive || !o.sample_png.empty();
+    o.counts = o.have_adaptive || !o.sample_png.empty() || o.frames != 0;   // (a sequence resolves every frame with the pixels' own counts)
     if (o.counts) {
         if (!one_device(o, "--adaptive / --sample-image render on one device: the library can shard an adaptive render (masks and additive counts), this program's device loop does not.")) return 1;
         if (o.have_adaptive && o.have_target) { fprintf(stderr, "--adaptive and --noise-target are two stop rules: give one of them.\n"); return 1; }
@@ -420,6 +453,7 @@ struct Run {
     int open_devices();
     int resume();
     int render();
+    int render_frames();
     int write_checkpoint();
     int write_result_png();
     int write_reports();
@@ -870,6 +904,70 @@ int Run::render() {
     return 0;
 }
 
+// the whole camera — eye and all five vectors — turned by `degrees` about the vertical axis through eye + focus_distance x forward
+static hr_camera orbit_camera(const hr_camera &c, double degrees) {
+    const double a = degrees * 3.14159265358979323846 / 180.0, ca = cos(a), sa = sin(a);
+    auto rot = [&](const hr_vec3 &v) { return hr_vec3{ca * v.x + sa * v.z, v.y, ca * v.z - sa * v.x}; };
+    const hr_vec3 pivot = {c.eye.x + c.focus_distance * c.forward.x, c.eye.y + c.focus_distance * c.forward.y, c.eye.z + c.focus_distance * c.forward.z};
+    hr_camera out = c;
+    const hr_vec3 rel = rot(hr_vec3{c.eye.x - pivot.x, c.eye.y - pivot.y, c.eye.z - pivot.z});
+    out.eye = hr_vec3{pivot.x + rel.x, pivot.y + rel.y, pivot.z + rel.z};
+    out.right = rot(c.right); out.up = rot(c.up); out.forward = rot(c.forward);
+    out.plane_half_right = rot(c.plane_half_right); out.plane_half_up = rot(c.plane_half_up);
+    return out;
+}
+// --frames N: frame f is samplings f S + 1 .. (f + 1) S at the camera of frame f - 1 turned by --orbit, set with hr_set_camera (the scene and its tree
+// stay).  With --temporal M it starts from frame f - 1's accumulator, counts and moments, reprojected (hr_render_motion of the previous camera,
+// hr_reproject); without, from nothing.  Every frame is resolved with the pixels' own counts, with --denoise through hr_denoise.  The samplings go out
+// in the launches Run::render makes of them, so --frames 1 writes the plain run's final image.
+int Run::render_frames() {
+    const uint32_t S = o.sampling;
+    const uint64_t per_sampling = ((uint64_t)(o.out_w + 3) / 4) * ((o.out_h + 3) / 4) * 64u;
+    const uint32_t lsize = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(4, (33177600ull + per_sampling - 1) / per_sampling));
+    hr_camera cam, prev;
+    CHECK_HR(hr_get_camera(ctx, &cam));
+    hr_reproject_params rp;
+    CHECK_HR(hr_reproject_default_params(&rp));
+    if (o.temporal) rp.max_history = (uint32_t)o.temporal;
+    std::vector<uint32_t> counts((size_t)o.out_w * o.out_h);
+    for (uint32_t f = 0; f < (uint32_t)o.frames; f++) {
+        const double t0 = now_sec();
+        uint32_t history = 0;
+        if (f) {
+            prev = cam;
+            cam = orbit_camera(prev, o.orbit_deg);
+            CHECK_HR(hr_set_camera(ctx, &cam));
+            if (o.temporal) {
+                CHECK_HR(hr_render_motion(ctx, &prev, &rp));
+                CHECK_HR(hr_reproject(ctx, &rp));
+                CHECK_HR(hr_read_sample_counts(ctx, counts.data()));
+                for (uint32_t n : counts) history = std::max(history, n);
+            } else CHECK_HR(hr_clear(ctx));
+        }
+        const uint32_t begin_s = f * S + 1, end_s = begin_s + S;
+        for (uint32_t b = begin_s; b < end_s; b += lsize) CHECK_HR(hr_render(ctx, b, std::min(end_s, b + lsize), 1));
+        CHECK_HR(hr_synchronize(ctx));
+        final_image = true;
+        sampled = end_s - 1;
+        bool denoised = false;
+        if (o.denoise) {
+            hr_denoise_params dp;
+            CHECK_HR(hr_denoise_default_params(&dp));
+            if (o.denoise_levels >= 0) dp.levels = (uint32_t)o.denoise_levels;
+            const int rc = hr_denoise(ctx, &dp);   // (HR_ERR_INVALID: a pixel with fewer than 2 samplings)
+            if (rc == 0) { CHECK_HR(hr_resolve_denoised(ctx, rgb.data())); denoised = true; }
+            else if (rc != HR_ERR_INVALID) { fprintf(stderr, "hr_denoise: %s\n", hr_last_error()); return 1; }
+            else tee("denoise: fewer than 2 samplings behind a pixel, frame %u is not denoised.", f);
+        }
+        if (!denoised) CHECK_HR(hr_resolve_counted(ctx, rgb.data()));
+        char path[32];
+        snprintf(path, sizeof path, "frame_%03u.png", f);
+        if (write_png(path, rgb.data(), o.out_w, o.out_h)) return 1;
+        tee("frame %u: samplings %u .. %u, history up to %u, %s, %.3f sec.", f, begin_s, end_s - 1, history, path, now_sec() - t0);
+    }
+    return 0;
+}
+
 // --checkpoint: everything is read from the devices first, then written in one go; a file keeps the bytes it always had: the trailers
 // of what this render did not keep are not there
 int Run::write_checkpoint() {
@@ -1005,7 +1103,9 @@ int main(int argc, char **argv) {
     g_log = fopen("result.txt", "w");
     Run run(o);
     run.print_settings();
-    if (run.open_devices() || run.resume() || run.render() || run.write_checkpoint() || run.write_result_png() || run.write_reports()) return 1;
+    if (o.frames) {
+        if (run.open_devices() || run.render_frames()) return 1;
+    } else if (run.open_devices() || run.resume() || run.render() || run.write_checkpoint() || run.write_result_png() || run.write_reports()) return 1;
     run.close();
     return 0;
 }

@@ -93,6 +93,10 @@ class SelectParams(C.Structure):
     _fields_ = [("smooth", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ReprojectParams(C.Structure):
+    _fields_ = [("max_history", C.c_uint32), ("_pad", C.c_uint32), ("min_roughness", C.c_double), ("depth_tolerance", C.c_double)]
+
+
 COMM_PATHS = {0: "none", 1: "rccl-rank", 2: "rccl-group", 3: "same-device-fallback"}
 
 
@@ -245,6 +249,13 @@ def hip_lib():
         L.hr_select_tiles_selected.argtypes = _sel + [C.c_double, C.c_double, C.POINTER(C.c_uint32)]
         L.hr_fold_statistics.argtypes = [C.c_void_p]
         L.hr_fold_statistics_group.argtypes = [C.POINTER(C.c_void_p), C.c_int]
+        L.hr_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.hr_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        L.hr_render_motion.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(ReprojectParams)]
+        L.hr_read_motion.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_write_motion.argtypes = [C.c_void_p, C.c_void_p]
+        L.hr_reproject_default_params.argtypes = [C.POINTER(ReprojectParams)]
+        L.hr_reproject.argtypes = [C.c_void_p, C.POINTER(ReprojectParams)]
         _hip = L
     return _hip
 
@@ -341,6 +352,14 @@ def select_default_params():
     return p
 
 
+def reproject_default_params():
+    """hr_reproject_default_params: the documented defaults as a ReprojectParams (needs no device)."""
+    L = hip_lib()
+    p = ReprojectParams()
+    _ok(L, L.hr_reproject_default_params(C.byref(p)))
+    return p
+
+
 def restore_default_params():
     """hr_restore_default_params: the documented defaults as a RestoreParams (needs no device)."""
     L = hip_lib()
@@ -424,7 +443,7 @@ _PLANES = {
     "accumulator": ((3,), np.float32), "rgb8": ((3,), np.uint8), "moments": ((6,), np.float64), "noise": ((), np.float64),
     "sample_counts": ((), np.uint32), "guides": ((8,), np.float32), "denoised": ((3,), np.float32), "buckets": ((3,), np.float64),
     "robust": ((3,), np.float32), "robust_trim": ((), np.uint8), "restored": ((3,), np.float32),
-    "selected": ((3,), np.float32), "selected_levels": ((), np.uint8),
+    "selected": ((3,), np.float32), "selected_levels": ((), np.uint8), "motion": ((4, 3), np.float32),
 }
 
 
@@ -675,6 +694,35 @@ class Renderer:
     def resolve_denoised(self):
         """hr_resolve_denoised: resolve() of the denoised radiance."""
         return self._read_plane(self.L.hr_resolve_denoised, "rgb8")
+
+    # ---- camera moves that keep their history (include/hanamaru_hip.h)
+    def set_camera(self, camera):
+        """hr_set_camera: replace the camera of the scene in place (a Camera); the tree, the textures and what is accumulated stay."""
+        self._check(self.L.hr_set_camera(self._h, C.byref(camera)))
+
+    def camera(self):
+        """hr_get_camera: the f64 camera in place, as a Camera."""
+        out = Camera()
+        self._check(self.L.hr_get_camera(self._h, C.byref(out)))
+        return out
+
+    def render_motion(self, from_camera, **params):
+        """hr_render_motion: the motion plane of the camera in place against the earlier camera `from_camera` (a Camera); the defaults, with any
+        of min_roughness, depth_tolerance replaced."""
+        p = _with(reproject_default_params, ReprojectParams, "render_motion", params)
+        self._check(self.L.hr_render_motion(self._h, C.byref(from_camera), C.byref(p)))
+
+    def read_motion(self):
+        """hr_read_motion: (h, w, 4, 3) float32 {mx, my, code} per sub-sample."""
+        return self._read_plane(self.L.hr_read_motion, "motion")
+
+    def write_motion(self, motion):
+        self._write_plane(self.L.hr_write_motion, "motion", motion)
+
+    def reproject(self, **params):
+        """hr_reproject: the defaults, with any of max_history, min_roughness, depth_tolerance replaced."""
+        p = _with(reproject_default_params, ReprojectParams, "reproject", params)
+        self._check(self.L.hr_reproject(self._h, C.byref(p)))
 
     # ---- option "robust_buckets": the sample buckets and the firefly-robust resolve (include/hanamaru_hip.h)
     def read_buckets(self):

@@ -401,7 +401,7 @@ int hr_select_tiles(hr_ctx *ctx, double floor, double threshold, uint32_t *activ
  *     pixel depends on inputs up to 2 x (2^levels - 1) pixels away, so pixels within that distance of the edge differ from the full-frame
  *     result and those further inside equal it.  As with the bilateral filter, exact tiles of a frame come from stitching the tiles'
  *     accumulators, moments, counts and guides into one full-frame context.
- *   - What it is not: there is no temporal part.  By default the guides are the FIRST hit's — what is seen through or in glass and mirrors is
+ *   - What it is not: the filter itself has no temporal part — history comes in before it, as counts and moments (hr_reproject below).  By default the guides are the FIRST hit's — what is seen through or in glass and mirrors is
  *     guided by the glass surface; "guide_bounces" follows mirrors and glass to the first rough hit, but not low-roughness GGX, only one branch
  *     at glass (no separate reflect / transmit planes), and the normal is not reflected into a mirror's virtual space.  The sigmas are design
  *     parameters: the defaults are the best row of a small host-side sweep (DESIGN.md 4.9 has the tables).  With first-hit guides that sweep
@@ -641,6 +641,80 @@ int hr_select_tiles_selected(hr_ctx *ctx, const hr_denoise_params *p, const hr_s
  *     as they were, and the total, R and D are invalid on every rank.  The group's statistics cannot be trusted after it: hr_clear every context. */
 int hr_fold_statistics(hr_ctx *ctx);
 int hr_fold_statistics_group(hr_ctx **ctxs, int n);
+
+/* ---- camera moves that keep their history ------------------------------------------------------------------------------------
+ * The scene description carries its camera, and hr_upload_scene flattens, builds and uploads everything again.  A turntable or fly-through
+ * changes the camera only:
+ *   - hr_set_camera replaces the camera of the scene in place — the fp32 camera the kernels take and the f64 one on the device — with the
+ *     conversions of hr_upload_scene.  After it every entry point gives the bits that a fresh context gives after hr_upload_scene of the same
+ *     description with camera = cam: hr_render, hr_render_debug, the guide passes and the hr_debug_* queries, both shading modes, both trace
+ *     pipelines, both node formats.  HR_ERR_NO_SCENE before a scene is uploaded; a camera that is not finite is HR_ERR_INVALID and the camera in
+ *     place stays.  It synchronises, drops the guide planes and the motion plane (they show the old view) and makes every derived image that shows
+ *     the scene stale, as hr_upload_scene does.  It touches neither the accumulator, the counts, the moments, the buckets, the tile mask, the
+ *     region, the BVH, the textures nor hr_stats.bvh_build_ms / bvh_builder_used: what is accumulated stays accumulated — a host that wants a fresh
+ *     frame calls hr_clear, one that wants to carry the old frame over calls hr_reproject.
+ *   - hr_get_camera: the f64 camera in place, as it was uploaded or set (HR_ERR_NO_SCENE without a scene).
+ *   - The motion plane: h x w x 4 x 3 floats, row-major, top row first: {mx, my, code} for each of a pixel's 2x2 sub-samples in the kernels' lane
+ *     order (sub-sample s has sx = s & 1, sy = s >> 1 of renderer.rs:51-53).  (mx, my): where the point this sub-sample sees was in an EARLIER
+ *     frame, as an offset in pixels from the pixel itself, y pointing down — the history of pixel (px, py) is at (px + mx, py + my) of the old
+ *     planes.  code: 0 = may be reused; 1 = behind the old camera or off its frame; 2 = hidden from the old eye; 3 = a view-dependent surface
+ *     (mirror, glass, smooth GGX); anything but 0 is "no history".  hr_read_motion returns the plane as an output in its own right (an AOV: motion
+ *     vectors; HR_ERR_INVALID without a valid plane); hr_write_motion replaces it (synthetic inputs, stitched tiles; HR_ERR_NO_TARGET without a
+ *     target).  The plane is allocated on first use and goes stale with hr_set_camera, hr_upload_scene, hr_set_resolution and hr_set_region;
+ *     hr_clear keeps it.
+ *   - hr_render_motion(ctx, from, params) renders the plane for the camera in place against the earlier camera `from`: one pass of the production
+ *     traversal, two walks per sub-sample at most.  The scene is static and the library owns a ray tracer, so whether a history sample is valid is
+ *     asked exactly, with a visibility ray from the old eye, not by comparing depth and normal planes.  Per sub-sample (motion_point and
+ *     motion_verdict in csrc/pt_core.h; the f64 steps are reproject_project and reproject_motion in csrc/reproject_core.h, to the bit):
+ *       1. the PINHOLE ray of the frame pixel and sub-sample (the rays of hr_render_debug and hr_render_guides), closest hit;
+ *       2. a hit on Specular, Refraction or GGXRefraction, or on GGX with roughness below min_roughness, is view-dependent: {0, 0, 3}.  Otherwise the
+ *          point is the fp32 hit point x, or for a miss the point at infinity along the ray direction d;
+ *       3. into `from`, in f64: v = x - eye0 (a miss: v = d);  c = v . forward0, c <= 0: {0, 0, 1};  k = c / focus0;
+ *          ncx = (v . phr0) / ((phr0 . phr0) k), ncy likewise with phu0 — the inverse of camera.rs:98-107, which needs `from` as Camera::new builds
+ *          it (camera.rs:45-64): right, up and forward orthogonal, plane_half_right along right, plane_half_up along up.  With m = min(W, H):
+ *          fx = (ncx m + W) / 2, fy = (ncy m + H) / 2 (renderer.rs:36,53-54), the sub-sample's own gx = px + ox, gy = (H - py) + oy;
+ *          mx = fx - gx, my = gy - fy, a component with |.| < 2^-10 stored as 0 (a camera that did not move hands every pixel its own history
+ *          exactly); fx outside [-1, W + 1] or fy outside [-1, H + 1]: {mx, my, 1};
+ *       4. the sub-samples still at code 0 send a ray from (float)eye0 along normalize((float)v), closest hit: a point is visible when the walk
+ *          hits with |t - |v|| <= depth_tolerance |v| (fp32), a sky direction when it misses; otherwise code 2.
+ *     It follows hr_render_guides: the whole region whatever the tile mask; a region's plane is the frame's window bit for bit; it touches neither
+ *     the accumulator, the statistics planes nor hr_stats.paths; one launch, timed into debug_kernel_ms / debug_launches; it does not synchronise.
+ *     params = NULL: the defaults; the parameters hr_reproject refuses are refused here.  The lens is ignored, as the guide planes ignore it: with
+ *     depth of field the motion is that of the pinhole image.
+ *   - hr_reproject replaces the region's accumulator, counts and (with option "moments" on) moments by the history gathered along the motion
+ *     plane; the next hr_render adds the new frame's samplings on top, and hr_resolve_counted, the noise estimate, tile selection and hr_denoise
+ *     work as before, because every pixel knows its count.  The definition is reproject_pixel in csrc/reproject_core.h, to the bit (f64; + - x /,
+ *     floor and comparisons, one IEEE operation per step, no FMA).  For each sub-sample with code 0 and a finite motion with |component| <= 2^20:
+ *         u = px + mx,  v = py + my;  x0 = floor(u),  y0 = floor(v);  ax = u - x0,  ay = v - y0;  taps (x0 + i, y0 + j), i, j in {0, 1}, j outer;
+ *         w = (i ? ax : 1 - ax) (j ? ay : 1 - ay); a tap is skipped when w == 0, outside the region, or when its old count n_q is 0; else
+ *         Wp += w,  N += w n_q,  A_c += w (acc_q,c / n_q),  and with moments  M1_c += w (S1_q,c / n_q),  M2_c += w (S2_q,c / n_q)
+ *     and per pixel n' = min(max_history, floor(N / 4)) — sub-samples and taps without history count as none, so a half-disoccluded pixel gets
+ *     proportionally less —;  Wp == 0 or n' == 0: every plane of the pixel is 0;  else acc'_c = (float)((A_c / Wp) n'), S1'_c = (M1_c / Wp) n',
+ *     S2' likewise, count' = n'.  The samplings behind the moments become the largest count written (no count exceeds them).  It reads a copy of
+ *     the old planes that lives for the call (w x h x (12 + 4 + 48) bytes), synchronises, and puts its time into hr_stats.post_kernel_ms.
+ *     HR_ERR_INVALID: no valid motion plane, "sample_counts" off, a tile mask set, max_history == 0, or a min_roughness or depth_tolerance that is
+ *     not finite and >= 0.  HR_ERR_UNSUPPORTED: "robust_buckets" on (buckets are not carried).  What is refused touches nothing.  On success
+ *     everything made of the accumulator, the moments or the counts is stale (D, R', S, the all-reduced total).
+ *   - hr_reproject_params: max_history caps the count a pixel carries over — the weight of the past against the new frame's samplings —;
+ *     min_roughness and depth_tolerance are hr_render_motion's (steps 2 and 4), and hr_reproject only checks them.  params = NULL: hr_reproject_default_params' (32, 0.3, 1e-3; it needs no device).  These are design parameters nobody has measured.
+ *   - The caller's rule: a path's seed depends only on its pixel, sub-sample and sampling index.  A sequence must therefore give every frame fresh
+ *     sampling indices — frame f renders samplings f S + 1 .. (f + 1) S —, or a still camera adds the history's own samples a second time.
+ *   - What it is not: depth of field is ignored.  GGX above min_roughness is reused although it is mildly view-dependent.  Lighting on a reused diffuse point is
+ *     view-independent only up to what it sees through glossy occluders: max_history is the limit on that.  A silhouette pixel of the old frame is
+ *     a blend and hands the blend on: there is no per-tap validation.  Buckets are not carried.  Geometry does not move. */
+typedef struct hr_reproject_params {
+    uint32_t max_history;     /* > 0 */
+    uint32_t _pad;
+    double min_roughness;     /* >= 0 */
+    double depth_tolerance;   /* >= 0 */
+} hr_reproject_params;
+int hr_set_camera(hr_ctx *ctx, const hr_camera *cam);
+int hr_get_camera(hr_ctx *ctx, hr_camera *out);
+int hr_render_motion(hr_ctx *ctx, const hr_camera *from, const hr_reproject_params *p /* NULL = defaults */);
+int hr_read_motion(hr_ctx *ctx, float *host /* w*h*12 */);
+int hr_write_motion(hr_ctx *ctx, const float *host);
+int hr_reproject_default_params(hr_reproject_params *out);
+int hr_reproject(hr_ctx *ctx, const hr_reproject_params *p /* NULL = defaults */);
 
 int hr_get_stats(hr_ctx *ctx, hr_stats *out);
 /* Options that leave the image as the reference computes it (the summation order of the accumulator aside):

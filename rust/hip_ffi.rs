@@ -37,6 +37,8 @@ pub const HR_MESH: i32 = 2;
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrRestoreParams { pub levels: u32, pub base: u32, pub sigma_n: f64, pub sigma_a: f64, pub sigma_z: f64 }
 /// hr_select_params: the per-pixel level selection's parameters (hr_select_default_params fills in the defaults)
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrSelectParams { pub smooth: u32, pub reserved: u32 }
+/// hr_reproject_params: the parameters of hr_render_motion and hr_reproject (hr_reproject_default_params fills in the defaults)
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct HrReprojectParams { pub max_history: u32, pub _pad: u32, pub min_roughness: f64, pub depth_tolerance: f64 }
 pub enum HrCtx {}
 
 extern "C" {
@@ -137,6 +139,14 @@ extern "C" {
     // every additive plane (accumulator, moments, counts, buckets filled under option "bucket_by_sampling" 1) moves to rank 0, which then answers
     pub fn hr_fold_statistics(ctx: *mut HrCtx) -> c_int;
     pub fn hr_fold_statistics_group(ctxs: *mut *mut HrCtx, n: c_int) -> c_int;
+    // camera moves that keep their history
+    pub fn hr_set_camera(ctx: *mut HrCtx, cam: *const HrCamera) -> c_int;
+    pub fn hr_get_camera(ctx: *mut HrCtx, out: *mut HrCamera) -> c_int;
+    pub fn hr_render_motion(ctx: *mut HrCtx, from: *const HrCamera, p: *const HrReprojectParams /* null = defaults */) -> c_int;
+    pub fn hr_read_motion(ctx: *mut HrCtx, host: *mut f32 /* w*h*12 */) -> c_int;
+    pub fn hr_write_motion(ctx: *mut HrCtx, host: *const f32) -> c_int;
+    pub fn hr_reproject_default_params(out: *mut HrReprojectParams) -> c_int;
+    pub fn hr_reproject(ctx: *mut HrCtx, p: *const HrReprojectParams /* null = defaults */) -> c_int;
 }
 
 // ---- GENERATED by tools/gen_rust_layout.py from include/hanamaru_hip.h: do not edit ----
@@ -154,6 +164,7 @@ const _: () = assert!(std::mem::size_of::<HrNoise>() == 40 && std::mem::align_of
 const _: () = assert!(std::mem::size_of::<HrDenoiseParams>() == 40 && std::mem::align_of::<HrDenoiseParams>() == 8);   // hr_denoise_params
 const _: () = assert!(std::mem::size_of::<HrRestoreParams>() == 32 && std::mem::align_of::<HrRestoreParams>() == 8);   // hr_restore_params
 const _: () = assert!(std::mem::size_of::<HrSelectParams>() == 8 && std::mem::align_of::<HrSelectParams>() == 4);   // hr_select_params
+const _: () = assert!(std::mem::size_of::<HrReprojectParams>() == 24 && std::mem::align_of::<HrReprojectParams>() == 8);   // hr_reproject_params
 const _: () = assert!(std::mem::size_of::<Vector3>() == 24);   // hr_vec3
 #[cfg(test)]
 mod layout {
@@ -223,6 +234,9 @@ mod layout {
         assert_eq!(off!(HrRestoreParams, sigma_z), 24);
         assert_eq!(off!(HrSelectParams, smooth), 0);
         assert_eq!(off!(HrSelectParams, reserved), 4);
+        assert_eq!(off!(HrReprojectParams, max_history), 0);
+        assert_eq!(off!(HrReprojectParams, min_roughness), 8);
+        assert_eq!(off!(HrReprojectParams, depth_tolerance), 16);
     }
 }
 // ---- END GENERATED ----
